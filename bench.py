@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: state reconstructions/s, 3-qubit MLE (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: qt_mle_batch on B = 1000 independent
 3-qubit trials per GPU ('proj-set' POVM, 1e5 shots per setting, Ginibre state of
@@ -9,11 +9,19 @@ np.random.default_rng(1234); counts drawn on the host from np.random.seed(7) in 
 reference's call order -- SURVEY.md section 8d).  Counts are resident in HBM before the timed
 region.
 
+A plain run does only what the headline needs: set-up, --preroll-ms of the step and the W warm-up steps
+(untimed), the K timed steps, then the result line.  --dump-outputs DIR writes what the last timed step
+returned to its caller (rank 0's batch) as DIR/<name>.npy in float64: rho.npy (B, d, d, 2) = real and
+imaginary parts, nit.npy, nfev.npy, status.npy (B,).  Beyond 64 MB in all, a fixed seeded sample of the
+trials is written instead, with its indices in sample_index.npy.  Every other measurement and check
+below (no_preroll, cpu_baseline, saturated_batch, iterating, other_configs, configs4_weak, the bootstrap
+legs) runs only with --full; without it their keys are null.
+
 N > 1: one rank per GPU over RCCL.  Either the driver starts the ranks (torchrun: WORLD_SIZE is
 set) or `python bench.py --gpus N` starts them itself as a CHILD `python -m torch.distributed.run`
 before anything in this process has touched the GPU.  Each rank reconstructs its own 1000 trials
 (weak scaling, no data-path collective); the group size is asserted equal to --gpus and reported as
-"rccl_ranks".  After the headline the sharded legs run on every rank:
+"rccl_ranks".  With --full, after the headline the sharded legs run on every rank:
   "configs4_weak"     5-qubit MLE (configs[4]), 256 trials per rank, weak-scaled;
 and five STRONG-scaled bootstrap CIs (interval.py:598-612), each rank doing its shard of: [draw +] reconstruct with the
 Hilbert-Schmidt distance in the same pass (qt_mle_dist_batch) + sort of its shard + the order statistics across ranks
@@ -24,9 +32,9 @@ Hilbert-Schmidt distance in the same pass (qt_mle_dist_batch) + sort of its shar
   "bootstrap_ci_large" 2 097 152 resamples at n = 3 (a size where sharding matters), with "serial_ms" = what does not shard;
   "bootstrap_ci_large_device_draw"  the same size, every resample distinct and drawn by its rank, the draw inside the region.
 
-The contract's W warm-up + K timed steps run twice: straight after the host drew the counts ("no_preroll") and again after
---preroll-ms (40 ms, untimed, reported as "preroll_ms") of the same step, which brings the GPU back to its running clocks;
-`value` is the second.  `python bench.py --profile` regenerates profiles/round3_pmc_traffic.json (rocprofv3 PMC passes as
+`value` is timed after --preroll-ms (40 ms, untimed, reported as "preroll_ms") of the same step, which brings the GPU back
+to its running clocks.  With --full the W warm-up + K timed steps also run once before the pre-roll, straight after the host
+drew the counts ("no_preroll").  `python bench.py --profile` regenerates profiles/round3_pmc_traffic.json (rocprofv3 PMC passes as
 child processes); `roofline.traffic` is reported only when that file was measured on this build of the library.
 
 Rank 0 prints ONE JSON line (contract in the task statement) that also carries
@@ -161,7 +169,24 @@ def vector_resamples(povm, bloch, shots, n, seed):
 
 
 PMC_FILE = "round3_pmc_traffic.json"
-SHORT_FLAGS = ["--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--bootstrap-points", "0", "--no-other-configs"]
+SHORT_FLAGS = ["--full", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--bootstrap-points", "0", "--no-other-configs"]
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write per-trial arrays (leading axis = trial) as out_dir/<name>.npy in float64, complex as a trailing (re, im) axis.
+    Above DUMP_LIMIT_BYTES in all, the same seeded sample of trials is taken from every array (indices in sample_index.npy)."""
+    arrays = {k: (np.stack([v.real, v.imag], -1) if np.iscomplexobj(v) else v).astype(np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_trial = sum(v[0].nbytes for v in arrays.values())
+    if n * per_trial > DUMP_LIMIT_BYTES:
+        n_keep = (DUMP_LIMIT_BYTES - 4096) // (per_trial + 8)  # 4096 for the .npy headers, 8 B per trial of sample_index
+        keep = np.sort(np.random.default_rng(2024).choice(n, n_keep, replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["sample_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def library_hash():
@@ -305,6 +330,11 @@ def main():
     ap.add_argument("--launch-check", action="store_true", help="form the process group (gloo, CPU) and exit: launcher test")
     ap.add_argument("--profile", action="store_true",
                     help="regenerate profiles/" + PMC_FILE + " and the kernel stats from rocprofv3 passes of the short command (child processes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (no_preroll, CPU baselines, saturated batch, iterating, other "
+                         "configs, configs[4], bootstrap legs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy in float64")
     args = ap.parse_args()
     if args.profile:
         sys.exit(run_profile())
@@ -323,7 +353,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
     cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_per_core > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_per_core > 0:
         try:
             cpu_all = cpu_all_cores(args.shots, args.cpu_per_core)
         except Exception as exc:  # the single-core figure below is the contract; this one is a supplement
@@ -431,7 +461,7 @@ def main():
 
     # First the contract's W + K exactly as written: the GPU sat idle while the host drew the counts, and W x 15 us of
     # warm-up end before its power state has moved -- reported as "no_preroll" (both figures).
-    cold_elapsed, cold_kernel_ms = timed_steps() if args.preroll_ms > 0 else (None, None)
+    cold_elapsed, cold_kernel_ms = timed_steps() if args.full and args.preroll_ms > 0 else (None, None)
     # pre-roll: bring the GPU back to its running clocks with the same step.  Outside the timed region.
     t_pre = time.perf_counter()
     while (time.perf_counter() - t_pre) * 1e3 < args.preroll_ms:
@@ -446,6 +476,8 @@ def main():
     nfev = nfev_d.cpu().numpy()
     status = st_d.cpu().numpy()
     rho_h = rho_d.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rho": rho_h, "nit": nit, "nfev": nfev, "status": status})
     assert np.all(status == 0), "non-zero trial status in the benchmark batch"
     value = world * B * args.steps / elapsed
 
@@ -510,7 +542,7 @@ def main():
 
     # ---- the same step at a batch that fills the chip (occupancy hides the single-wave latency) ----
     sat = None
-    if rank == 0 and args.saturation_batch > 0:
+    if args.full and rank == 0 and args.saturation_batch > 0:
         Bs = args.saturation_batch
         reps = (Bs + B - 1) // B
         big = torch.from_numpy(np.ascontiguousarray(np.concatenate([counts] * reps)[:Bs])).cuda()
@@ -562,7 +594,7 @@ def main():
 
     # ---- the regime in which BFGS iterates (state.py:204-215 is THE hot loop of SURVEY 3.3) -------
     iterating = None
-    if rank == 0 and not args.no_other_configs:
+    if args.full and rank == 0 and not args.no_other_configs:
         qo = _oracle()
         iterating = {}
         povm_np = np.asarray(povm)
@@ -611,7 +643,7 @@ def main():
 
     # ---- the other single-GPU configurations of BASELINE.json, one short measurement each ---------
     others = None
-    if rank == 0 and not args.no_other_configs:
+    if args.full and rank == 0 and not args.no_other_configs:
         others = {}
         # configs[2]: 2-qubit process tomography of a depolarizing channel, Choi linear inversion + CPTP
         np.random.seed(11)
@@ -727,7 +759,7 @@ def main():
 
     # ---- configs[4]: 5-qubit MLE, tensor-product Pauli POVM, 1e6 shots per setting; 256 trials PER RANK (weak) ----
     c4 = None
-    if not args.no_other_configs:
+    if args.full and not args.no_other_configs:
         n5 = 5
         rho5 = ginibre(np.random.default_rng(1234), 2**n5)
         povm5 = qp.generate_measurement_matrix("proj-set", n5)
@@ -887,7 +919,7 @@ def main():
         return leg
 
     boot = boot_dev = boot5 = boot_large = boot_large_dev = None
-    if args.bootstrap_points > 0:
+    if args.full and args.bootstrap_points > 0:
         from quantpy_amd.tomography.state import born_probabilities
 
         tmg = qp.StateTomograph(state)
@@ -974,7 +1006,7 @@ def main():
 
     # ---- CPU baseline: the oracle on a bounded sample, one host core (rank 0, N = 1 only) -------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         qo = _oracle()
         try:
             from threadpoolctl import threadpool_limits

@@ -19,11 +19,11 @@ timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_
 step "rocprofv3 --kernel-trace --stats of the driver command"
 ( cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_bench_under_rocprof.err ); echo "rc=$?"
 cp $(find $OUT/${TAG}_stats -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_kernel_stats.csv 2>/dev/null
-step "bench, default flags"
-timeout -k 10 900 python3 bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; echo "rc=$?"
+step "bench, default flags with every side measurement (--full)"
+timeout -k 10 900 python3 bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; echo "rc=$?"
 step "bench, two gloo ranks sharing cuda:0 / one-rank RCCL"
-timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --share-gpu0 --no-cpu-baseline > $OUT/${TAG}_bench_2rank_gloo_shared_gpu.json 2> $OUT/${TAG}_bench_2rank.err; echo "rc=$?"
-QT_BENCH_FORCE_DIST=1 timeout -k 10 600 python3 bench.py --no-cpu-baseline > $OUT/${TAG}_bench_1rank_rccl.json 2> $OUT/${TAG}_bench_1rank.err; echo "rc=$?"
+timeout -k 10 600 python3 bench.py --full --gpus 2 --backend gloo --share-gpu0 --no-cpu-baseline > $OUT/${TAG}_bench_2rank_gloo_shared_gpu.json 2> $OUT/${TAG}_bench_2rank.err; echo "rc=$?"
+QT_BENCH_FORCE_DIST=1 timeout -k 10 600 python3 bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench_1rank_rccl.json 2> $OUT/${TAG}_bench_1rank.err; echo "rc=$?"
 step "timing scripts"
 timeout -k 10 300 python3 scripts/headline_timing.py 500 > $OUT/${TAG}_headline_timing.txt 2>&1
 timeout -k 10 300 python3 scripts/iterating_timing.py > $OUT/${TAG}_iterating_timing.txt 2>&1

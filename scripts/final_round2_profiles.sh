@@ -13,12 +13,12 @@ step "bash scripts/collect_profiles_r2.sh $TAG"
 bash scripts/collect_profiles_r2.sh $TAG > $OUT/${TAG}_collect.log 2>&1
 step "python3 bench.py --gpus 1 --steps 20 --warmup 5"
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_driver_cmd.json 2> $OUT/${TAG}_bench_driver_cmd.err
-step "python3 bench.py"
-python3 bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
-step "python3 bench.py --gpus 2 --backend gloo --share-gpu0 --no-cpu-baselin"
-python3 bench.py --gpus 2 --backend gloo --share-gpu0 --no-cpu-baseline > $OUT/${TAG}_bench_2rank_gloo_shared_gpu.json 2> $OUT/${TAG}_bench_2rank.err
-step "QT_BENCH_FORCE_DIST=1 python3 bench.py --no-cpu-baseline"
-QT_BENCH_FORCE_DIST=1 python3 bench.py --no-cpu-baseline > $OUT/${TAG}_bench_1rank_rccl.json 2> $OUT/${TAG}_bench_1rank.err
+step "python3 bench.py --full"
+python3 bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+step "python3 bench.py --full --gpus 2 --backend gloo --share-gpu0 --no-cpu-baseline"
+python3 bench.py --full --gpus 2 --backend gloo --share-gpu0 --no-cpu-baseline > $OUT/${TAG}_bench_2rank_gloo_shared_gpu.json 2> $OUT/${TAG}_bench_2rank.err
+step "QT_BENCH_FORCE_DIST=1 python3 bench.py --full --no-cpu-baseline"
+QT_BENCH_FORCE_DIST=1 python3 bench.py --full --no-cpu-baseline > $OUT/${TAG}_bench_1rank_rccl.json 2> $OUT/${TAG}_bench_1rank.err
 step "python3 scripts/headline_timing.py 500"
 python3 scripts/headline_timing.py 500 > $OUT/${TAG}_headline_timing.txt 2>&1
 step "python3 scripts/iterating_timing.py"

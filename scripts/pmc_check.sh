@@ -2,7 +2,7 @@
 # one counter per pass vs five counters in one pass: SQ_INSTS_VALU of k_mle_start<3> at B = 65536
 OUT=$PWD/gpurun_out
 export TMPDIR=/tmp
-SHORT="$GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --bootstrap-points 0 --no-other-configs --saturation-batch 65536"
+SHORT="$PWD/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --bootstrap-points 0 --no-other-configs --saturation-batch 65536"
 cd /tmp
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU -d $OUT/pmcchk_single -o run --output-format csv -- python3 $SHORT > $OUT/pmcchk_single.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_WAVES -d $OUT/pmcchk_pair -o run --output-format csv -- python3 $SHORT > $OUT/pmcchk_pair.log 2>&1
