@@ -5,17 +5,14 @@
 //   - Bloch / parameter index k = l  (vectors b, w, x, g of length D live one element per lane),
 //   - matrix element (i, j) = (l / d, l % d) of every d x d complex matrix (rho, L, G, V),
 //   - row m = c*G + l of the M-row POVM contraction, chunk by chunk.
-// A workgroup is WPB = 4 waves, one per SIMD of a CU.  The waves share ONE read-only LDS image of
-// the current (M x D) operand (left inverse for 'lin', then the weighted POVM A' for the NLL),
-// row-padded to D + 1 doubles so that both access directions -- lane = column (A'^T r, A^+ f) and
-// lane = row (A' b) -- are bank-conflict free.  Measured motivation (profiles/round1_v1_*): with
-// every wave streaming its own 111 KB of A' from L2 per evaluation the batch pulled 14-22 TB/s out
-// of L2 and each wave, alone on its SIMD, sat on L2 latency; from LDS the operand is read at LDS
-// rate and HBM/L2 see it once per workgroup.  After the cooperative image load the waves run
-// independently (wave-level fences only), so trials diverge freely inside BFGS.
-// Per-trial scratch (rho, L, V, b, r, f: ~7 KB) also lives in LDS; the BFGS inverse Hessian
-// (D x D f64) lives in registers, one row per lane.  POVMs too large for the image (M (D+1) 8 B
-// + scratch > 160 KB) take the ALDS = false instantiation, which streams the operand from L2.
+// A workgroup is WPB = 4 waves, one per SIMD of a CU; the waves run independently (wave-level
+// fences only), so trials diverge freely inside BFGS.  A dense (M x D) operand -- the left inverse
+// for 'lin', the weighted POVM A' for the NLL -- is streamed from L2 by every wave (dot_global:
+// 16 loads in flight per lane); a product POVM needs no dense operand at all (ProductView).  An
+// LDS-resident operand image shared by the waves was measured slower in both regimes and removed
+// (profiles/round1_v3_*).  Per-trial scratch (rho, L, V, b, r, f: ~7 KB) lives in LDS behind the
+// workgroup's product-POVM tables; the BFGS inverse Hessian (D x D f64) lives in registers, one
+// row per lane (n = 1, 2; n = 3 runs the two-loop form).
 //
 // Reference semantics implemented (paths into /root/reference/quantpy):
 //   lin:  tomography/state.py:191-202, PSD clip :267-273
@@ -220,21 +217,6 @@ __device__ __forceinline__ double dot_global(const double* __restrict__ base, si
   for (; m < n; ++m) acc[0] = fma(base[(size_t)m * stride + lane_off], lds_vec[m], acc[0]);
   return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
-// The same product with the operand in the LDS image: img[m * stride + lane_off].
-__device__ __forceinline__ double dot_lds(const double* img, int stride, int lane_off, const double* lds_vec, int n) {
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  const double* p = img + lane_off;
-  int m = 0;
-#pragma unroll 4
-  for (; m + 4 <= n; m += 4) {
-    a0 = fma(p[(m + 0) * stride], lds_vec[m + 0], a0);
-    a1 = fma(p[(m + 1) * stride], lds_vec[m + 1], a1);
-    a2 = fma(p[(m + 2) * stride], lds_vec[m + 2], a2);
-    a3 = fma(p[(m + 3) * stride], lds_vec[m + 3], a3);
-  }
-  for (; m < n; ++m) a0 = fma(p[m * stride], lds_vec[m], a0);
-  return (a0 + a1) + (a2 + a3);
-}
 
 // Unitary 2x2 rotation J = [[c, w], [-conj(w), c]] that (nearly) annihilates a_pq of
 // [[app, apq], [conj(apq), aqq]]: with delta = (aqq - app)/2 and
@@ -315,7 +297,7 @@ struct EstOut {
   double* dist;          // [B], or nullptr
 };
 
-template <int NQ, bool ALDS>
+template <int NQ>
 struct Small {
   static constexpr int d = 1 << NQ;
   static constexpr int D = d * d;
@@ -325,7 +307,6 @@ struct Small {
   static constexpr int NT = 64 * WPB;      // threads per workgroup
   static constexpr int TPB = TPW * WPB;    // trials per workgroup
   static constexpr int T = d * (d - 1) / 2;
-  static constexpr int LDA = D + 1;        // row pitch of the LDS operand image
   // Row pitch of the d x d complex matrix images: 9 at d = 8, so that the rows one column is read
   // from (pitch 144 B = 36 banks) fall on distinct LDS banks; a pitch of 8 (128 B) makes every such
   // ds_read_b128 a 4-way bank conflict.  d = 2, 4 have no conflict to begin with.
@@ -351,7 +332,6 @@ struct Small {
     const int Mp = (M + 1) & ~1;
     return oM + (R1 > 0 ? 3 : 2) * Mp + (v_on_rbuf(M) ? 0 : MAT);
   }
-  __host__ __device__ static int image_doubles(int M) { return ALDS ? ((M * LDA + 1) & ~1) : 0; }
   // Index tables of a product POVM, staged once per workgroup (shared by its waves): forward stage
   // tables, backward stage tables, R-order row map.
   __host__ __device__ static int ipow_h(int b, int e) {
@@ -377,14 +357,13 @@ struct Small {
     return R1 > 0 ? (table_ints(M, R1) / 2 + ((M + 1) & ~1) + 8 * R1) : 0;
   }
   __host__ __device__ static size_t lds_bytes(int M, int R1 = 0, int extra = 0) {
-    return ((size_t)image_doubles(M) + table_doubles(M, R1) + (size_t)TPB * (trial_doubles(M, R1) + extra)) * sizeof(double);
+    return ((size_t)table_doubles(M, R1) + (size_t)TPB * (trial_doubles(M, R1) + extra)) * sizeof(double);
   }
 
   // ---- per-lane context ---------------------------------------------------------------
   struct Ctx {
     int l, i, j, e;  // lane in group, matrix element, its slot i * LD + j in a matrix image
     double* sm;      // this trial's LDS scratch
-    double* img;     // the workgroup's operand image (ALDS)
     const int *tfwd, *tbwd, *trmap;  // the workgroup's copy of the product-POVM index tables (LDS)
     const double* twrow;             // ... and of the row weights N_s / sum(N), R-order
     const double *ttab, *ptab;       // ... and of the one-qubit tables T [R1][4], pinv(T)^T [R1][4]
@@ -428,13 +407,12 @@ struct Small {
     c.M = pv.M;
     c.Mp = (pv.M + 1) & ~1;
     c.pv = pv;
-    c.img = smem_block;
     const int r1 = pv.pr.enabled ? pv.pr.R1 : 0;
-    int* tabs = reinterpret_cast<int*>(smem_block + image_doubles(pv.M));
+    int* tabs = reinterpret_cast<int*>(smem_block);
     c.tfwd = tabs;
     c.tbwd = tabs + fwd_ints(r1);
     c.trmap = c.tbwd + bwd_ints(r1);
-    double* wrow = smem_block + image_doubles(pv.M) + table_ints(pv.M, r1) / 2;
+    double* wrow = smem_block + table_ints(pv.M, r1) / 2;
     double* t1 = wrow + ((pv.M + 1) & ~1);
     c.twrow = wrow;
     c.ttab = t1;
@@ -453,7 +431,7 @@ struct Small {
       }
       __syncthreads();
     }
-    c.sm = smem_block + image_doubles(pv.M) + table_doubles(pv.M, r1) + slot * (trial_doubles(pv.M, r1) + pv.extra);
+    c.sm = smem_block + table_doubles(pv.M, r1) + slot * (trial_doubles(pv.M, r1) + pv.extra);
     int xm = 0, zm = 0, ny = 0;
 #pragma unroll
     for (int b = 0; b < NQ; ++b) {
@@ -488,15 +466,6 @@ struct Small {
       c.src_im = d + T + tt;
     }
     if (c.l == 0) c.sm[oVec + D] = 0.0;  // (this trial's scratch: c.sm is set above)
-  }
-
-  // Cooperative copy of a row-major [M][D] operand into the padded LDS image (whole workgroup).
-  __device__ static void load_image(const Ctx& c, const double* __restrict__ g) {
-    if (!ALDS) return;
-    __syncthreads();  // every wave is done with the previous image
-    const int total = c.M * D;
-    for (int e = threadIdx.x; e < total; e += NT) c.img[(e / D) * LDA + (e % D)] = g[e];
-    __syncthreads();
   }
 
   // Bloch index of the Pauli string with X-type mask x and Z-type mask z.
@@ -808,16 +777,14 @@ struct Small {
   }
   // sum_m Op[m][lane] * vec[m]   (lane = column)
   __device__ __forceinline__ static double col_dot(const Ctx& c, const double* g_rowmajor, const double* vec) {
-    if (ALDS) return dot_lds(c.img, LDA, c.l, vec, c.M);
     return dot_global<16>(g_rowmajor, D, (unsigned)c.l, vec, c.M);
   }
   // sum_k Op[row][k] * vec[k]    (lane = row), g_transposed = [D][M]
   __device__ __forceinline__ static double row_dot(const Ctx& c, const double* g_transposed, int row, const double* vec) {
-    if (ALDS) return dot_lds(c.img + row * LDA, 1, 0, vec, D);
     return dot_global<(D < 16 ? D : 16)>(g_transposed, (size_t)c.M, (unsigned)row, vec, D);
   }
 
-  // ---- a6: linear inversion (image = PinvT).  Returns lane's element of rho; vec() = Bloch vector.
+  // ---- a6: linear inversion (operand PinvT).  Returns lane's element of rho; vec() = Bloch vector.
   __device__ static cd lin_invert(const Ctx& c, double& bloch_l) {
     if (c.prod()) {
       if (c.pv.pr.uniform) {
@@ -1155,7 +1122,7 @@ struct Small {
     return m;
   }
 
-  // ---- a9: NLL value and exact gradient at x (image = Aw).  Needs freq[] loaded.  Leaves L in Bm().
+  // ---- a9: NLL value and exact gradient at x (operand Aw).  Needs freq[] loaded.  Leaves L in Bm().
   // `start` (first evaluation of a trial, at the Cholesky parameters of a matrix that is still at hand):
   // rho(x) = L L^dagger / Tr is that matrix, and its factor already sits in Bm() up to the scale
   // start->lscale, so L L^dagger is not formed again.
@@ -1307,11 +1274,11 @@ struct Small {
 // =========================================================================================
 
 // a6 + a7
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) k_lin_batch(PovmView pv, const int64_t* __restrict__ counts, int B, int physical,
                                                    EstOut rho, double* __restrict__ bloch_out,
                                                    int32_t* __restrict__ status) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
   bool live;
@@ -1321,7 +1288,6 @@ __global__ void __launch_bounds__(256) k_lin_batch(PovmView pv, const int64_t* _
   S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
   S::make_ctx(c, smem, pv);
   QT_STAMP(0);
-  S::load_image(c, pv.PinvT);
   const bool shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
   QT_STAMP(1);
   double bl;
@@ -1340,7 +1306,7 @@ __global__ void __launch_bounds__(256) k_lin_batch(PovmView pv, const int64_t* _
 template <int NQ>
 __global__ void __launch_bounds__(256) k_chol_param(PovmView pv, const double* __restrict__ rho, int B,
                                                     double* __restrict__ x, int32_t* __restrict__ status) {
-  using S = Small<NQ, false>;
+  using S = Small<NQ>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
   S::make_ctx(c, smem, pv);
@@ -1360,7 +1326,7 @@ __global__ void __launch_bounds__(256) k_chol_param(PovmView pv, const double* _
 template <int NQ>
 __global__ void __launch_bounds__(256) k_chol_unparam(PovmView pv, const double* __restrict__ x, int B,
                                                       double* __restrict__ llh) {
-  using S = Small<NQ, false>;
+  using S = Small<NQ>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
   S::make_ctx(c, smem, pv);
@@ -1377,18 +1343,17 @@ __global__ void __launch_bounds__(256) k_chol_unparam(PovmView pv, const double*
 }
 
 // a9
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) k_nll_batch(PovmView pv, const double* __restrict__ x,
                                                    const int64_t* __restrict__ counts, int B, double* __restrict__ f,
                                                    double* __restrict__ grad) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
   S::make_ctx(c, smem, pv);
   bool live;
   const int b = S::trial_index(B, &live);
   const int bb = live ? b : B - 1;
-  S::load_image(c, pv.Aw);
   S::load_freq(c, counts + (size_t)bb * pv.M);
   double fv, gl;
   S::nll_grad(c, x[(size_t)bb * S::D + c.l], fv, gl);
@@ -1406,14 +1371,14 @@ __global__ void __launch_bounds__(256) k_nll_batch(PovmView pv, const double* __
 // Held to four wavefronts per SIMD (128 VGPRs): the saturated batches run four workgroups per CU, and one
 // register more -- the EstOut pointers of round 3 made it 129 -- takes a workgroup off every CU (measured: 0.372 -> 0.416 ms
 // per 65 536 trials).
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_mle_start(PovmView pv, const int64_t* __restrict__ counts, int B, int init,
                                                    int max_iter, double gtol, EstOut rho,
                                                    int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                    double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                    double* __restrict__ ws_x, double* __restrict__ ws_g,
                                                    double* __restrict__ ws_f, int32_t* __restrict__ ws_active) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   constexpr int D = S::D, G = S::G, d = S::d;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
@@ -1428,13 +1393,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   double xk;
   typename S::StartPoint sp;
   if (init == 0) {
-    S::load_image(c, pv.PinvT);
     double bl;
     const cd lin = S::lin_invert(c, bl);
-    S::load_image(c, pv.Aw);  // (barrier inside: every wave is past its read of the left inverse)
     sp.rho = S::make_feasible(c, lin, &xk, &ok, &sp.lscale);  // physical 'lin' estimate, Cholesky-parametrised
   } else {
-    S::load_image(c, pv.Aw);
     sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
     sp.lscale = 1.0;
     xk = S::cholesky_param(c, sp.rho, ok);
@@ -1473,12 +1435,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
 // meet gtol.  One (value, gradient) evaluation per loop pass; the line search is the state machine of
 // qt_linesearch.h; the inverse Hessian is one row per lane in registers.  `mine` marks the groups that
 // iterate; the others idle through the evaluations on finite dummy values.
-template <int NQ, bool ALDS>
-__device__ __forceinline__ void bfgs_iterate(const typename Small<NQ, ALDS>::Ctx& c, bool mine, double xk, double gk,
+template <int NQ>
+__device__ __forceinline__ void bfgs_iterate(const typename Small<NQ>::Ctx& c, bool mine, double xk, double gk,
                                              double fk, int b, int max_iter, double gtol, EstOut rho,
                                              int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                              double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   constexpr int D = S::D, G = S::G;
   bool active = mine;
   double H[D];
@@ -1615,13 +1577,13 @@ __device__ __forceinline__ void bfgs_iterate(const typename Small<NQ, ALDS>::Ctx
 // (tests/test_gpu_state.py runs the reference's 70 golden trials through both).
 // LP > 0 (k_mle_fused: one workgroup per CU, LDS to spare): the first LP pairs stay in the trial's LDS and only later
 // ones go to the global workspace -- a lone wave would otherwise wait out an L2 round trip per block of pairs.
-template <int NQ, bool ALDS, int LP = 0>
-__device__ __forceinline__ void bfgs_iterate_2l(const typename Small<NQ, ALDS>::Ctx& c, bool mine, double xk, double gk,
+template <int NQ, int LP = 0>
+__device__ __forceinline__ void bfgs_iterate_2l(const typename Small<NQ>::Ctx& c, bool mine, double xk, double gk,
                                                 double fk, int b, int max_iter, double gtol, EstOut rho,
                                                 int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                 double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                 double* __restrict__ pairs) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   constexpr int D = S::D, G = S::G;
   bool active = mine;
   double* my = pairs + (size_t)b * max_iter * 2 * D + c.l;  // s_i[l] at my[2 i D], y_i[l] at my[(2 i + 1) D]
@@ -1748,14 +1710,14 @@ __device__ __forceinline__ void bfgs_iterate_2l(const typename Small<NQ, ALDS>::
 #define QT_BFGS_WAVES 2  // waves per SIMD the BFGS kernel is compiled for; measured at B = 65 536 (15-iteration trials): 3 waves
                          // (<= 168 VGPRs, 18 spilled) 5.29 ms, 2 waves (205 VGPRs, no scratch) 5.39 ms -- instruction-bound either way
 #endif
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFGS_WAVES))) k_mle_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B, int max_iter,
                                                   double gtol, EstOut rho, int32_t* __restrict__ nit_out,
                                                   int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                   int32_t* __restrict__ status_out, const double* __restrict__ ws_x,
                                                   const double* __restrict__ ws_g, const double* __restrict__ ws_f,
                                                   const int32_t* __restrict__ ws_active, double* __restrict__ pairs) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   constexpr int D = S::D;
   bool live;
   const int b = S::trial_index(B, &live);
@@ -1765,7 +1727,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFG
   typename S::Ctx c;
   S::make_ctx(c, smem, pv);
   const int bb = live ? b : B - 1;
-  S::load_image(c, pv.Aw);
   S::load_freq(c, counts + (size_t)bb * pv.M);
   // inactive trials of a live wave idle through the loop on dummy finite values
   const double xk = mine ? ws_x[(size_t)b * D + c.l] : (c.l < S::d ? 1.0 : 0.0);
@@ -1774,9 +1735,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFG
   // n = 3: two-loop form (the 64 x 64 inverse Hessian would cost 128 VGPRs per lane); n = 1, 2: H is 4 / 16 doubles
   // per lane and stays in registers
   if constexpr (NQ == 3)
-    bfgs_iterate_2l<NQ, ALDS>(c, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+    bfgs_iterate_2l<NQ>(c, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
   else
-    bfgs_iterate<NQ, ALDS>(c, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
+    bfgs_iterate<NQ>(c, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
 }
 
 constexpr int kFusedLdsPairs = 24;  // (s, y) pairs of k_mle_fused<3> kept in LDS: 24 KB per trial, 4 trials per workgroup
@@ -1784,13 +1745,13 @@ constexpr int kFusedLdsPairs = 24;  // (s, y) pairs of k_mle_fused<3> kept in LD
 // a10 in ONE launch, for batches small enough that its 256-VGPR footprint (two waves per SIMD) is no
 // handicap: start point, first evaluation and -- for the waves that still hold an open trial -- the BFGS
 // loop.  Saves the second launch (2.5-4 us when nothing iterates, ~10 % of a 1000-trial step).
-template <int NQ, bool ALDS>
+template <int NQ>
 __device__ __forceinline__ void mle_fused_body(const PovmView& pv, const int64_t* __restrict__ counts, int B, int init,
                                                int max_iter, double gtol, EstOut rho,
                                                int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                double* __restrict__ pairs) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   constexpr int D = S::D, G = S::G, d = S::d;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
@@ -1807,14 +1768,11 @@ __device__ __forceinline__ void mle_fused_body(const PovmView& pv, const int64_t
   double xk;
   typename S::StartPoint sp;
   if (init == 0) {
-    S::load_image(c, pv.PinvT);
     double bl;
     const cd lin = S::lin_invert(c, bl);
     QT_STAMP(2);
-    S::load_image(c, pv.Aw);
     sp.rho = S::template make_feasible<true>(c, lin, &xk, &ok, &sp.lscale);  // one wave per SIMD: speculative inverse (cholesky_param)
   } else {
-    S::load_image(c, pv.Aw);
     sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
     sp.lscale = 1.0;
     xk = S::cholesky_param(c, sp.rho, ok);
@@ -1855,29 +1813,29 @@ __device__ __forceinline__ void mle_fused_body(const PovmView& pv, const int64_t
   // n = 3: two-loop form, the first kFusedLdsPairs (s, y) pairs in LDS (the 64 x 64 inverse Hessian took 128 VGPRs per lane
   // and ~460 AGPR moves per iteration); n = 1, 2: the 4 / 16-entry Hessian rows stay in registers
   if constexpr (NQ == 3)
-    bfgs_iterate_2l<NQ, ALDS, kFusedLdsPairs>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out,
+    bfgs_iterate_2l<NQ, kFusedLdsPairs>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out,
                                               status_out, pairs);
   else
-    bfgs_iterate<NQ, ALDS>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
+    bfgs_iterate<NQ>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
 }
 
 // Two entry points over the same body: the fully mixed start (`init = 'mixed'`: every trial iterates, ~10x the duration)
 // runs under its own kernel name, so that a profiler's per-kernel average of k_mle_fused is the average of the
 // 'lin'-start launches (bench.py's timed steps) and not a mixture with the iterating side measurements.
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) k_mle_fused(PovmView pv, const int64_t* __restrict__ counts, int B, int max_iter,
                                                    double gtol, EstOut rho, int32_t* __restrict__ nit_out,
                                                    int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                    int32_t* __restrict__ status_out, double* __restrict__ pairs) {
-  mle_fused_body<NQ, ALDS>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) k_mle_fused_mixed(PovmView pv, const int64_t* __restrict__ counts, int B,
                                                          int max_iter, double gtol, EstOut rho,
                                                          int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                          double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                          double* __restrict__ pairs) {
-  mle_fused_body<NQ, ALDS>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 
 // Metropolis-Hastings chain on the Cholesky parameters (reference mhmc.py:80-119 with
@@ -1885,12 +1843,12 @@ __global__ void __launch_bounds__(256) k_mle_fused_mixed(PovmView pv, const int6
 // uniforms drawn on the host in the reference's order.  Step t:
 //   x' = (x + step * delta_t) / ||x + step * delta_t||,  alpha = exp(nll(x) - nll(x')),  accept iff u_t <= alpha.
 // chain[c][t][:] = the state AFTER step t, accepted[c][t] = 0 / 1.
-template <int NQ, bool ALDS>
+template <int NQ>
 __global__ void __launch_bounds__(256) k_mhmc_state(PovmView pv, const int64_t* __restrict__ counts, int C,
                                                     const double* __restrict__ x_init, const double* __restrict__ deltas,
                                                     const double* __restrict__ uniforms, int T_steps, double step,
                                                     double* __restrict__ chain, int32_t* __restrict__ accepted) {
-  using S = Small<NQ, ALDS>;
+  using S = Small<NQ>;
   constexpr int D = S::D, G = S::G;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   typename S::Ctx c;
@@ -1898,7 +1856,6 @@ __global__ void __launch_bounds__(256) k_mhmc_state(PovmView pv, const int64_t* 
   bool live;
   const int b = S::trial_index(C, &live);
   const int bb = live ? b : C - 1;
-  S::load_image(c, pv.Aw);
   S::load_freq(c, counts + (size_t)bb * pv.M);
   double x = x_init[(size_t)bb * D + c.l];
   double f, unused;

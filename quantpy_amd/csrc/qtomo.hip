@@ -68,6 +68,8 @@ struct DevBuf {
   }
 };
 
+constexpr int kStageBufs = 8;  // arrays one host-pointer call may stage (qt_mle_batch: counts, centre and six outputs)
+
 }  // namespace
 
 struct qt_handle {
@@ -78,15 +80,9 @@ struct qt_handle {
   // Pinned host mailbox for the small transfers of host-pointer calls (counts of a few trials in, rho / nit / status
   // out): hipMemcpyAsync from / to pageable memory blocks the caller ~10 us per copy, a one-trial qt_mle_batch makes six.
   // Through pinned memory they are asynchronous; outputs are copied to the caller's arrays once the stream has been
-  // waited for (drain_mailbox).  Transfers above kMailMax, or when the box is full, take the direct route.
-  struct Pending {
-    void* dst;
-    const void* src;
-    size_t bytes;
-  };
+  // waited for (Call::done).  Transfers above kMailMax, or when the box is full, take the direct route.
   char* mail = nullptr;
   size_t mail_used = 0;
-  std::vector<Pending> mail_pending;
   // POVM cache.  The dense operands A, A^T, A', A'^T ([M][D] each: 64 MB at n = 5) exist when `dense_ready`;
   // a product POVM at n >= 4 never reads them and builds them only on demand (ensure_dense), likewise the dense
   // left inverse (`pinv_ready`, compute_dense_pinv).
@@ -99,8 +95,10 @@ struct qt_handle {
   // product-POVM (Kronecker) description, valid when prod.enabled
   DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd, pr_aug;
   qt::ProductView prod{};
-  // staging for host-pointer calls
-  DevBuf in0, in1, out0, out1, out2, out3, out4, out5, proc_aug, proc_ws;
+  // staging for host-pointer calls: one buffer per array of a call, in the order the call registers them (Call)
+  DevBuf stage[kStageBufs];
+  DevBuf proc_aug, proc_ws;
+  DevBuf gram;  // qt_moment_batch: P^T P
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -149,9 +147,6 @@ struct DeviceScope {
   if (!(h)) return fail(QT_ERR_ARG, "null handle");                                                          \
   DeviceScope qt_scope_((h)->device);                                                                        \
   if (qt_scope_.err != hipSuccess) return fail(QT_ERR_HIP, "hipSetDevice(%d): %s", (h)->device, hipGetErrorString(qt_scope_.err)); \
-  /* outputs a FAILED host-pointer call left parked in the mailbox must never be copied into that caller's (possibly */   \
-  /* freed) arrays by the next call's drain: a successful call has drained before it returned */                          \
-  (h)->mail_pending.clear();                                                                                               \
   (h)->mail_used = 0
 
 inline int grid_for(size_t total, int block = 256, int cap = 8192) {
@@ -174,55 +169,6 @@ inline char* mail_alloc(qt_handle_t* h, size_t bytes) {
   h->mail_used = at + bytes;
   return h->mail + at;
 }
-// after the stream has been waited for: hand the outputs parked in the mailbox to the caller's arrays
-inline void drain_mailbox(qt_handle_t* h) {
-  for (const auto& p : h->mail_pending) memcpy(p.dst, p.src, p.bytes);
-  h->mail_pending.clear();
-  h->mail_used = 0;
-}
-
-// Resolve an input array: device pointer as-is, or staged copy of a host array.
-template <class T>
-int stage_in(qt_handle_t* h, DevBuf& buf, const T* src, size_t count, int flags, const T** out) {
-  if (flags & QT_DEVICE_PTR) {
-    *out = src;
-    return 0;
-  }
-  HIPCHK(buf.ensure(count * sizeof(T)));
-  const void* from = src;
-  if (char* m = mail_alloc(h, count * sizeof(T))) {
-    memcpy(m, src, count * sizeof(T));
-    from = m;
-  }
-  HIPCHK(hipMemcpyAsync(buf.p, from, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  *out = buf.as<T>();
-  return 0;
-}
-template <class T>
-int stage_out(qt_handle_t*, DevBuf& buf, T* dst, size_t count, int flags, T** out) {
-  if (!dst) {
-    *out = nullptr;
-    return 0;
-  }
-  if (flags & QT_DEVICE_PTR) {
-    *out = dst;
-    return 0;
-  }
-  HIPCHK(buf.ensure(count * sizeof(T)));
-  *out = buf.as<T>();
-  return 0;
-}
-template <class T>
-int fetch_out(qt_handle_t* h, const T* dev, T* dst, size_t count, int flags) {
-  if (!dst || (flags & QT_DEVICE_PTR)) return 0;
-  if (char* m = mail_alloc(h, count * sizeof(T))) {
-    HIPCHK(hipMemcpyAsync(m, dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-    h->mail_pending.push_back({dst, m, count * sizeof(T)});
-    return 0;
-  }
-  HIPCHK(hipMemcpyAsync(dst, dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
-  return 0;
-}
 // Wait for the handle's stream.  hipStreamSynchronize / hipEventSynchronize park the thread and wake it through an
 // interrupt: ~50 us of latency measured around a 330 us timed region (20 steps of bench.py) and on every host-pointer
 // call.  Most waits here are shorter than a millisecond, so: record an event, poll it for up to ~2 ms, then block.
@@ -242,45 +188,129 @@ int wait_stream(qt_handle_t* h) {
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     const hipError_t q = hipStreamQuery(h->stream);
-    if (q == hipSuccess) {
-      drain_mailbox(h);
-      return 0;
-    }
+    if (q == hipSuccess) return 0;
     if (q != hipErrorNotReady) return fail(QT_ERR_HIP, "hipStreamQuery: %s", hipGetErrorString(q));
     if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  drain_mailbox(h);
   return 0;
 }
-// for the entry points that block on the stream themselves
-#define QT_STREAM_SYNC(h)                       \
-  do {                                          \
-    HIPCHK(hipStreamSynchronize((h)->stream));  \
-    drain_mailbox(h);                           \
-  } while (0)
-int finish(qt_handle_t* h, int flags) {
-  HIPCHK(hipGetLastError());
-  if (!(flags & QT_DEVICE_PTR)) return wait_stream(h);
-  return 0;
-}
-int count_bad(const int32_t* status, int B, int flags) {
-  if (!status || (flags & QT_DEVICE_PTR)) return 0;
-  int bad = 0;
-  for (int b = 0; b < B; ++b) bad += status[b] != 0;
-  return bad;
-}
+
+// The host-pointer / device-pointer convention of the C ABI, one object per entry point that takes or returns the
+// caller's arrays.  With QT_DEVICE_PTR the arrays are device memory and pass straight through: nothing is recorded and
+// done() costs one hipGetLastError.  Otherwise every array gets a staging buffer of its own (h->stage[], in the order
+// the call registers them), small inputs go through the pinned mailbox, and done() copies the outputs back after the
+// launches, in registration order.  Those copy-backs live in the Call: a call that returns early with an error drops
+// them, so they never reach arrays its caller may already have freed.
+class Call {
+ public:
+  // `fn` (the calling entry point, by default) names the call in errors
+  Call(qt_handle_t* h, int flags, const char* fn = __builtin_FUNCTION())
+      : h_(h), fn_(fn), dev_((flags & QT_DEVICE_PTR) != 0) {}
+  bool device() const { return dev_; }
+  // direction of a copy from device memory to the caller's array
+  hipMemcpyKind to_caller() const { return dev_ ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
+
+  // Input array: the caller's device pointer, or a staged copy of its host array.  A null or empty array passes through.
+  template <class T>
+  int in(const T* src, size_t count, const T** dev) {
+    *dev = src;
+    if (dev_ || !src || count == 0) return 0;
+    DevBuf* buf;
+    if (int r = next(&buf, count * sizeof(T))) return r;
+    const void* from = src;
+    if (char* m = mail_alloc(h_, count * sizeof(T))) {
+      memcpy(m, src, count * sizeof(T));
+      from = m;
+    }
+    HIPCHK(hipMemcpyAsync(buf->p, from, count * sizeof(T), hipMemcpyHostToDevice, h_->stream));
+    *dev = buf->as<T>();
+    return 0;
+  }
+  // Output array (null: not wanted, *dev = null): the caller's device pointer, or a buffer that done() copies back.
+  template <class T>
+  int out(T* dst, size_t count, T** dev) {
+    *dev = dst;
+    if (dev_ || !dst) return 0;
+    DevBuf* buf;
+    if (int r = next(&buf, count * sizeof(T))) return r;
+    *dev = buf->as<T>();
+    back_[nback_++] = {dst, buf->p, count * sizeof(T), nullptr};
+    return 0;
+  }
+  // Array updated in place: staged in like an input, copied back like an output.
+  template <class T>
+  int inout(T* x, size_t count, T** dev) {
+    const T* d;
+    if (int r = in(static_cast<const T*>(x), count, &d)) return r;
+    *dev = const_cast<T*>(d);
+    if (d != x) back_[nback_++] = {x, d, count * sizeof(T), nullptr};
+    return 0;
+  }
+  // The caller's array from / to device memory the handle owns: one direct copy, enqueued now (a null dst: none).
+  template <class T>
+  int copy_in(T* resident, const T* src, size_t count) {
+    HIPCHK(hipMemcpyAsync(resident, src, count * sizeof(T), dev_ ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                          h_->stream));
+    return 0;
+  }
+  template <class T>
+  int copy_out(T* dst, const T* resident, size_t count) {
+    if (dst) HIPCHK(hipMemcpyAsync(dst, resident, count * sizeof(T), to_caller(), h_->stream));
+    return 0;
+  }
+  // The caller's array into a host vector, synchronously.
+  template <class T>
+  int read(std::vector<T>& v, const T* src, size_t count) {
+    v.resize(count);
+    if (dev_) HIPCHK(hipMemcpy(v.data(), src, count * sizeof(T), hipMemcpyDeviceToHost));
+    else memcpy(v.data(), src, count * sizeof(T));
+    return 0;
+  }
+
+  // End of the call: enqueue the copy-backs, check the launches, and with host arrays wait for the stream and hand the
+  // outputs parked in the mailbox over.  Returns the number of non-zero entries of status[B] (host arrays; 0 otherwise).
+  int done(const int32_t* status = nullptr, int B = 0) {
+    for (int k = 0; k < nback_; ++k) {
+      Back& o = back_[k];
+      o.mail = mail_alloc(h_, o.bytes);
+      HIPCHK(hipMemcpyAsync(o.mail ? o.mail : o.dst, o.dev, o.bytes, hipMemcpyDeviceToHost, h_->stream));
+    }
+    HIPCHK(hipGetLastError());
+    if (dev_) return 0;
+    if (int r = wait_stream(h_)) return r;
+    for (int k = 0; k < nback_; ++k)
+      if (back_[k].mail) memcpy(back_[k].dst, back_[k].mail, back_[k].bytes);
+    int bad = 0;
+    if (status)
+      for (int b = 0; b < B; ++b) bad += status[b] != 0;
+    return bad;
+  }
+
+ private:
+  struct Back {  // a pending copy-back: dev -> (mail ->) dst
+    void* dst;
+    const void* dev;
+    size_t bytes;
+    char* mail;
+  };
+  int next(DevBuf** buf, size_t bytes) {
+    if (nbuf_ == kStageBufs) return fail(QT_ERR_ARG, "%s: more than %d staged arrays", fn_, kStageBufs);
+    *buf = &h_->stage[nbuf_++];
+    HIPCHK((*buf)->ensure(bytes));
+    return 0;
+  }
+  qt_handle_t* h_;
+  const char* fn_;
+  bool dev_;
+  int nbuf_ = 0, nback_ = 0;
+  Back back_[kStageBufs];  // at most one per staging buffer
+};
 
 constexpr size_t kLdsLimit = 160 * 1024;  // LDS per CU on gfx950; one workgroup may use all of it
-// Measured (profiles/round1_v3_*): a lone wave per SIMD pays ~7-10 ns of issue per LDS read, more than
-// for a global load that lands asynchronously, and the image costs occupancy at large batch: the L2
-// streaming variant is faster in both regimes, so the image variant is kept but not selected.
-#ifdef QT_PREFER_LDS_IMAGE
-constexpr bool kPreferLdsImage = true;
-#endif
 
-// Launch KERNEL<NQ, ALDS> for the handle's n: the LDS-image variant when image + scratch fit in
-// 160 KB, else the variant that streams the operand from L2.  ARGS is the parenthesised argument list.
+// Dynamic LDS above the 64 KB default needs the kernel's attribute raised first.  (The n <= 3 kernels of qt_small.h
+// stream their dense operand from L2 -- dot_global -- and hold only per-trial scratch and the product-POVM tables there.)
 template <class K>
 int allow_big_lds(K kernel, size_t bytes) {
   if (bytes <= 64 * 1024) return 0;
@@ -290,42 +320,30 @@ int allow_big_lds(K kernel, size_t bytes) {
   return 0;
 }
 
-#define QT_LAUNCH_ONE(KERNEL, NQV, ALDSV, M_, B_, ARGS)                                                   \
+// Launch KERNEL<n> (qt_small.h) for the handle's n = 1..3 over B_ trials.  LDS_ is the dynamic LDS size, an expression in
+// S_ = qt::Small<n>; ARGS is the parenthesised argument list.
+#define QT_LAUNCH_N(KERNEL, NQV, LDS_, B_, ARGS)                                                          \
   do {                                                                                                    \
-    using S_ = qt::Small<NQV, ALDSV>;                                                                     \
-    const size_t lds_ = S_::lds_bytes(M_, h->prod.enabled ? h->prod.R1 : 0, h->lds_extra);                \
+    using S_ = qt::Small<NQV>;                                                                            \
+    const size_t lds_ = LDS_;                                                                             \
     if (lds_ > kLdsLimit) return fail(QT_ERR_UNSUPPORTED, "POVM too large for the n<=3 kernels (%zu B of LDS)", lds_); \
-    if (int r_ = allow_big_lds(KERNEL<NQV, ALDSV>, lds_)) return r_;                                      \
+    if (int r_ = allow_big_lds(KERNEL<NQV>, lds_)) return r_;                                             \
     const int grid_ = ((B_) + S_::TPB - 1) / S_::TPB;                                                     \
-    hipLaunchKernelGGL((KERNEL<NQV, ALDSV>), dim3(grid_), dim3(S_::NT), lds_, h->stream, QT_UNPACK ARGS); \
+    hipLaunchKernelGGL((KERNEL<NQV>), dim3(grid_), dim3(S_::NT), lds_, h->stream, QT_UNPACK ARGS);        \
   } while (0)
+#define QT_LAUNCH_SMALL_LDS(KERNEL, LDS_, B_, ARGS)                                                         \
+  switch (h->nq) {                                                                                          \
+    case 1: QT_LAUNCH_N(KERNEL, 1, LDS_, B_, ARGS); break;                                                  \
+    case 2: QT_LAUNCH_N(KERNEL, 2, LDS_, B_, ARGS); break;                                                  \
+    case 3: QT_LAUNCH_N(KERNEL, 3, LDS_, B_, ARGS); break;                                                  \
+    default: return fail(QT_ERR_UNSUPPORTED, "estimators support n_qubits 1..3 in this release (got %d)", h->nq); \
+  }
 #define QT_UNPACK(...) __VA_ARGS__
-#ifdef QT_PREFER_LDS_IMAGE  /* the measured-slower variant: instantiated only on request (a third of the build time) */
-#define QT_LAUNCH_N(KERNEL, NQV, M_, B_, ARGS)                          \
-  do {                                                                  \
-    if (kPreferLdsImage && qt::Small<NQV, true>::lds_bytes(M_, h->prod.enabled ? h->prod.R1 : 0) <= kLdsLimit) \
-      QT_LAUNCH_ONE(KERNEL, NQV, true, M_, B_, ARGS);                   \
-    else                                                                \
-      QT_LAUNCH_ONE(KERNEL, NQV, false, M_, B_, ARGS);                  \
-  } while (0)
-#else
-#define QT_LAUNCH_N(KERNEL, NQV, M_, B_, ARGS) QT_LAUNCH_ONE(KERNEL, NQV, false, M_, B_, ARGS)
-#endif
-#define QT_LAUNCH_SMALL(KERNEL, M_, B_, ARGS)                                                               \
-  switch (h->nq) {                                                                                          \
-    case 1: QT_LAUNCH_N(KERNEL, 1, M_, B_, ARGS); break;                                                    \
-    case 2: QT_LAUNCH_N(KERNEL, 2, M_, B_, ARGS); break;                                                    \
-    case 3: QT_LAUNCH_N(KERNEL, 3, M_, B_, ARGS); break;                                                    \
-    default: return fail(QT_ERR_UNSUPPORTED, "estimators support n_qubits 1..3 in this release (got %d)", h->nq); \
-  }
-// kernels without an operand image (Cholesky parametrisation)
-#define QT_LAUNCH_SMALL_NOIMG(KERNEL, B_, ARGS)                                                             \
-  switch (h->nq) {                                                                                          \
-    case 1: { using S_ = qt::Small<1, false>; hipLaunchKernelGGL((KERNEL<1>), dim3(((B_) + S_::TPB - 1) / S_::TPB), dim3(S_::NT), S_::lds_bytes(0), h->stream, QT_UNPACK ARGS); } break; \
-    case 2: { using S_ = qt::Small<2, false>; hipLaunchKernelGGL((KERNEL<2>), dim3(((B_) + S_::TPB - 1) / S_::TPB), dim3(S_::NT), S_::lds_bytes(0), h->stream, QT_UNPACK ARGS); } break; \
-    case 3: { using S_ = qt::Small<3, false>; hipLaunchKernelGGL((KERNEL<3>), dim3(((B_) + S_::TPB - 1) / S_::TPB), dim3(S_::NT), S_::lds_bytes(0), h->stream, QT_UNPACK ARGS); } break; \
-    default: return fail(QT_ERR_UNSUPPORTED, "estimators support n_qubits 1..3 in this release (got %d)", h->nq); \
-  }
+// the estimators: per-trial scratch for an M_-row POVM (+ h->lds_extra) and the product-POVM tables
+#define QT_LAUNCH_SMALL(KERNEL, M_, B_, ARGS) \
+  QT_LAUNCH_SMALL_LDS(KERNEL, S_::lds_bytes(M_, h->prod.enabled ? h->prod.R1 : 0, h->lds_extra), B_, ARGS)
+// the Cholesky parametrisation, which reads no POVM: scratch only
+#define QT_LAUNCH_SMALL_NOPOVM(KERNEL, B_, ARGS) QT_LAUNCH_SMALL_LDS(KERNEL, S_::lds_bytes(0), B_, ARGS)
 
 // ---- n = 4, 5: workgroup-per-trial kernels (qt_large.h) ---------------------------------------------
 int compute_dense_pinv_fwd(qt_handle_t* h);
@@ -461,10 +479,10 @@ void qt_destroy(qt_handle_t* h) {
   (void)hipStreamSynchronize(h->stream);
   for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_aug})
     b->release();
-  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->aug, &h->info, &h->kron_dig, &h->in0, &h->in1,
-                    &h->out0, &h->out1, &h->out2, &h->out3, &h->out4, &h->out5, &h->proc_aug, &h->proc_ws, &h->ws_x, &h->ws_g, &h->ws_f,
-                    &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
+  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->aug, &h->info, &h->kron_dig, &h->proc_aug,
+                    &h->proc_ws, &h->gram, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
+  for (DevBuf& b : h->stage) b.release();
   h->proc.release();
   if (h->mail) (void)hipHostFree(h->mail);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -481,7 +499,7 @@ int qt_sync(qt_handle_t* h) {
 
 int qt_set_stream(qt_handle_t* h, void* hip_stream) {
   QT_ENTER(h);
-  QT_STREAM_SYNC(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
   if (h->own_stream && h->stream) HIPCHK(hipStreamDestroy(h->stream));
   if (hip_stream) {
     h->stream = hip_stream == QT_STREAM_LEGACY ? hipStreamLegacy : static_cast<hipStream_t>(hip_stream);
@@ -535,13 +553,13 @@ int qt_timer_end(qt_handle_t* h, double* elapsed_ms) {
 
 int qt_pauli_basis(qt_handle_t* h, double* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!out) return fail(QT_ERR_ARG, "null out");
   const size_t n = (size_t)h->D * h->D * 2;
   double* dout;
-  if (int r = stage_out(h, h->out0, out, n, flags, &dout)) return r;
+  if (int r = c.out(out, n, &dout)) return r;
   hipLaunchKernelGGL(qt::k_pauli_basis, dim3(grid_for(n / 2)), dim3(256), 0, h->stream, h->nq, dout);
-  if (int r = fetch_out(h, dout, out, n, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // Row digits for k_povm_kron: row = s K + k with s = sum_q s_q S1^(n-1-q), k likewise; byte q = s_q K1 + k_q.
@@ -568,7 +586,7 @@ static int ensure_kron_digits(qt_handle_t* h, int S1, int K1) {
   h->kron_S1 = h->kron_K1 = 0;
   HIPCHK(h->kron_dig.ensure(dig.size() * sizeof(unsigned long long)));
   HIPCHK(hipMemcpyAsync(h->kron_dig.p, dig.data(), dig.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
-  QT_STREAM_SYNC(h);  // `dig` goes out of scope
+  HIPCHK(hipStreamSynchronize(h->stream));  // `dig` goes out of scope
   h->kron_S1 = S1;
   h->kron_K1 = K1;
   return 0;
@@ -588,6 +606,7 @@ static int launch_povm_kron(qt_handle_t* h, const double* dtable, int S1, int K1
 
 int qt_povm_kron(qt_handle_t* h, const double* povm1, int S1, int K1, double* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!povm1 || !out || S1 < 1 || K1 < 1) return fail(QT_ERR_ARG, "bad povm_kron arguments");
   size_t S = 1, K = 1;
   for (int q = 0; q < h->nq; ++q) {
@@ -597,11 +616,10 @@ int qt_povm_kron(qt_handle_t* h, const double* povm1, int S1, int K1, double* ou
   const size_t n = S * K * h->D;
   const double* din;
   double* dout;
-  if (int r = stage_in(h, h->in0, povm1, (size_t)S1 * K1 * 4, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, out, n, flags, &dout)) return r;
+  if (int r = c.in(povm1, (size_t)S1 * K1 * 4, &din)) return r;
+  if (int r = c.out(out, n, &dout)) return r;
   if (int r = launch_povm_kron(h, din, S1, K1, dout)) return r;
-  if (int r = fetch_out(h, dout, out, n, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // Dense operands A ([M][D]; the Kronecker power of the table for a product POVM), A^T, A', A'^T -- built when first
@@ -645,7 +663,7 @@ static int compute_dense_pinv(qt_handle_t* h) {
   int info = 0;
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipGetLastError());
-  QT_STREAM_SYNC(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "A^T A is singular (no pivot in column %d): POVM not informationally complete", info - 1);
   h->pinv_ready = true;
   return 0;
@@ -675,17 +693,16 @@ static int begin_povm(qt_handle_t* h, int S, int K) {
 
 int qt_set_povm(qt_handle_t* h, const double* A, int S, int K, const double* Ns, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!A || !Ns || S < 1 || K < 1) return fail(QT_ERR_ARG, "bad set_povm arguments");
   if (int r = begin_povm(h, S, K)) return r;
-  const hipMemcpyKind kind = (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIPCHK(h->A.ensure((size_t)S * K * h->D * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(h->A.p, A, (size_t)S * K * h->D * sizeof(double), kind, h->stream));
-  HIPCHK(hipMemcpyAsync(h->Ns.p, Ns, S * sizeof(double), kind, h->stream));
+  if (int r = c.copy_in(h->A.as<double>(), A, (size_t)S * K * h->D)) return r;
+  if (int r = c.copy_in(h->Ns.as<double>(), Ns, (size_t)S)) return r;
   h->a_loaded = true;
   {
-    std::vector<double> ns((size_t)S);
-    if (flags & QT_DEVICE_PTR) HIPCHK(hipMemcpy(ns.data(), Ns, ns.size() * sizeof(double), hipMemcpyDeviceToHost));
-    else memcpy(ns.data(), Ns, ns.size() * sizeof(double));
+    std::vector<double> ns;
+    if (int r = c.read(ns, Ns, (size_t)S)) return r;
     h->ns_tot = 0.0;
     for (double v : ns) h->ns_tot += v;
   }
@@ -696,6 +713,7 @@ int qt_set_povm(qt_handle_t* h, const double* A, int S, int K, const double* Ns,
 
 int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, const double* Ns, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!povm1 || !Ns || S1 < 1 || K1 < 1) return fail(QT_ERR_ARG, "bad set_povm_product arguments");
   const int n = h->nq, R1 = S1 * K1;
   long long S = 1, K = 1, M = 1;
@@ -708,14 +726,9 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
   if (R1 > 255) return fail(QT_ERR_UNSUPPORTED, "one-qubit table with %d rows (> 255)", R1);
   if (int r = begin_povm(h, (int)S, (int)K)) return r;
   // host copies of the small inputs (table and shots) for the index tables
-  std::vector<double> t1((size_t)R1 * 4), ns((size_t)S);
-  if (flags & QT_DEVICE_PTR) {
-    HIPCHK(hipMemcpy(t1.data(), povm1, t1.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ns.data(), Ns, ns.size() * sizeof(double), hipMemcpyDeviceToHost));
-  } else {
-    memcpy(t1.data(), povm1, t1.size() * sizeof(double));
-    memcpy(ns.data(), Ns, ns.size() * sizeof(double));
-  }
+  std::vector<double> t1, ns;
+  if (int r = c.read(t1, povm1, (size_t)R1 * 4)) return r;
+  if (int r = c.read(ns, Ns, (size_t)S)) return r;
   HIPCHK(h->pr_T.ensure(t1.size() * sizeof(double)));
   HIPCHK(hipMemcpyAsync(h->pr_T.p, t1.data(), t1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->Ns.p, ns.data(), ns.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -795,7 +808,7 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
   int info = 0;
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipGetLastError());
-  QT_STREAM_SYNC(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "the one-qubit table is not informationally complete");
   h->prod.T = h->pr_T.as<double>();
   h->prod.P1T = h->pr_P1T.as<double>();
@@ -816,29 +829,28 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
 
 int qt_get_left_inverse(qt_handle_t* h, double* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (!out) return fail(QT_ERR_ARG, "null out");
   if (!h->pinv_ready)
     if (int r = compute_dense_pinv(h)) return r;
-  const size_t bytes = (size_t)h->D * h->M * sizeof(double);
-  HIPCHK(hipMemcpyAsync(out, h->Pinv.p, bytes, (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                        h->stream));
-  return finish(h, flags);
+  if (int r = c.copy_out(out, h->Pinv.as<double>(), (size_t)h->D * h->M)) return r;
+  return c.done();
 }
 
 int qt_born_probs(qt_handle_t* h, const double* bloch, int B, double* p, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (B < 0 || (B > 0 && (!bloch || !p))) return fail(QT_ERR_ARG, "bad born_probs arguments");
   if (B == 0) return 0;
   const double* din;
   double* dout;
-  if (int r = stage_in(h, h->in0, bloch, (size_t)B * h->D, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, p, (size_t)B * h->M, flags, &dout)) return r;
+  if (int r = c.in(bloch, (size_t)B * h->D, &din)) return r;
+  if (int r = c.out(p, (size_t)B * h->M, &dout)) return r;
   if (h->nq >= 4 && h->prod.enabled) {  // factorised contraction, one workgroup per state
     QT_LAUNCH_LARGE(qt::k_born_large, B, h->M, h->prod.R1, (h->view(), din, B, dout));
-    if (int r = fetch_out(h, dout, p, (size_t)B * h->M, flags)) return r;
-    return finish(h, flags);
+    return c.done();
   }
   if (int r = ensure_dense(h)) return r;
   const int gx = (h->M + 255) / 256;
@@ -879,57 +891,56 @@ int qt_born_probs(qt_handle_t* h, const double* bloch, int B, double* p, int fla
     hipLaunchKernelGGL(qt::k_born<TB>, dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream, h->AT.as<double>(),
                        h->M, h->D, h->d, din, B, dout);
   }
-  if (int r = fetch_out(h, dout, p, (size_t)B * h->M, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_bloch_from_mat(qt_handle_t* h, const double* mat, int B, double* bloch, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || (B > 0 && (!mat || !bloch))) return fail(QT_ERR_ARG, "bad bloch_from_mat arguments");
   if (B == 0) return 0;
   const double* din;
   double* dout;
   const size_t n = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, mat, n * 2, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, bloch, n, flags, &dout)) return r;
+  if (int r = c.in(mat, n * 2, &din)) return r;
+  if (int r = c.out(bloch, n, &dout)) return r;
   hipLaunchKernelGGL(qt::k_bloch_from_mat, dim3(grid_for(n)), dim3(256), 0, h->stream, h->nq, din, B, dout);
-  if (int r = fetch_out(h, dout, bloch, n, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_mat_from_bloch(qt_handle_t* h, const double* bloch, int B, double* mat, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || (B > 0 && (!mat || !bloch))) return fail(QT_ERR_ARG, "bad mat_from_bloch arguments");
   if (B == 0) return 0;
   const double* din;
   double* dout;
   const size_t n = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, bloch, n, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, mat, n * 2, flags, &dout)) return r;
+  if (int r = c.in(bloch, n, &din)) return r;
+  if (int r = c.out(mat, n * 2, &dout)) return r;
   hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for(n)), dim3(256), 0, h->stream, h->nq, din, B, dout);
-  if (int r = fetch_out(h, dout, mat, n * 2, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // a6 + a7 (+ a16 when `dist` is asked for): one body behind qt_lin_batch and qt_lin_dist_batch
 static int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centre, double* rho,
                           double* dist, double* bloch_out, int32_t* status, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad lin_batch arguments");
   if (B == 0) return 0;
   const int64_t* dc;
-  const double* dcen = nullptr;
+  const double* dcen;
   double *drho, *dbl, *ddist;
   int32_t* dst;
   const size_t nel = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, counts, (size_t)B * h->M, flags, &dc)) return r;
-  if (dist)
-    if (int r = stage_in(h, h->in1, centre, (size_t)h->D * 2, flags, &dcen)) return r;
-  if (int r = stage_out(h, h->out0, rho, nel * 2, flags, &drho)) return r;
-  if (int r = stage_out(h, h->out1, bloch_out, nel, flags, &dbl)) return r;
-  if (int r = stage_out(h, h->out2, status, (size_t)B, flags, &dst)) return r;
-  if (int r = stage_out(h, h->out3, dist, (size_t)B, flags, &ddist)) return r;
+  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
+  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
+  if (int r = c.out(rho, nel * 2, &drho)) return r;
+  if (int r = c.out(bloch_out, nel, &dbl)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
+  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
   const qt::EstOut eo{drho, dcen, ddist};
   if (h->nq >= 4) {
     if (int r = prepare_large(h, true)) return r;
@@ -937,12 +948,7 @@ static int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int phys
   } else {
     QT_LAUNCH_SMALL(qt::k_lin_batch, h->M, B, (h->view(), dc, B, physical, eo, dbl, dst));
   }
-  if (int r = fetch_out(h, drho, rho, nel * 2, flags)) return r;
-  if (int r = fetch_out(h, dbl, bloch_out, nel, flags)) return r;
-  if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, ddist, dist, (size_t)B, flags)) return r;
-  if (int r = finish(h, flags)) return r;
-  return count_bad(status, B, flags);
+  return c.done(status, B);
 }
 
 int qt_lin_batch(qt_handle_t* h, const int64_t* counts, int B, int physical, double* rho, double* bloch_out,
@@ -959,48 +965,47 @@ int qt_lin_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int physical
 
 int qt_chol_param(qt_handle_t* h, const double* rho, int B, double* x, int32_t* status, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || (B > 0 && (!rho || !x))) return fail(QT_ERR_ARG, "bad chol_param arguments");
   if (B == 0) return 0;
   const double* din;
   double* dx;
   int32_t* dst;
   const size_t nel = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, rho, nel * 2, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, x, nel, flags, &dx)) return r;
-  if (int r = stage_out(h, h->out2, status, (size_t)B, flags, &dst)) return r;
+  if (int r = c.in(rho, nel * 2, &din)) return r;
+  if (int r = c.out(x, nel, &dx)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
   qt::PovmView pv{};
   if (h->nq >= 4) {
     QT_LAUNCH_LARGE(qt::k_chol_param_large, B, 0, 1, (pv, din, B, dx, dst));
   } else {
-    QT_LAUNCH_SMALL_NOIMG(qt::k_chol_param, B, (pv, din, B, dx, dst));
+    QT_LAUNCH_SMALL_NOPOVM(qt::k_chol_param, B, (pv, din, B, dx, dst));
   }
-  if (int r = fetch_out(h, dx, x, nel, flags)) return r;
-  if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-  if (int r = finish(h, flags)) return r;
-  return count_bad(status, B, flags);
+  return c.done(status, B);
 }
 
 int qt_chol_unparam(qt_handle_t* h, const double* x, int B, double* LLh, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || (B > 0 && (!x || !LLh))) return fail(QT_ERR_ARG, "bad chol_unparam arguments");
   if (B == 0) return 0;
   const double* din;
   double* dout;
   const size_t nel = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, x, nel, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, LLh, nel * 2, flags, &dout)) return r;
+  if (int r = c.in(x, nel, &din)) return r;
+  if (int r = c.out(LLh, nel * 2, &dout)) return r;
   qt::PovmView pv{};
   if (h->nq >= 4) {
     QT_LAUNCH_LARGE(qt::k_chol_unparam_large, B, 0, 1, (pv, din, B, dout));
   } else {
-    QT_LAUNCH_SMALL_NOIMG(qt::k_chol_unparam, B, (pv, din, B, dout));
+    QT_LAUNCH_SMALL_NOPOVM(qt::k_chol_unparam, B, (pv, din, B, dout));
   }
-  if (int r = fetch_out(h, dout, LLh, nel * 2, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_nll_batch(qt_handle_t* h, const double* x, const int64_t* counts, int B, double* f, double* grad, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (B < 0 || (B > 0 && (!x || !counts || !f))) return fail(QT_ERR_ARG, "bad nll_batch arguments");
   if (B == 0) return 0;
@@ -1008,23 +1013,22 @@ int qt_nll_batch(qt_handle_t* h, const double* x, const int64_t* counts, int B, 
   const int64_t* dc;
   double *df, *dg;
   const size_t nel = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, x, nel, flags, &dx)) return r;
-  if (int r = stage_in(h, h->in1, counts, (size_t)B * h->M, flags, &dc)) return r;
-  if (int r = stage_out(h, h->out0, f, (size_t)B, flags, &df)) return r;
-  if (int r = stage_out(h, h->out1, grad, nel, flags, &dg)) return r;
+  if (int r = c.in(x, nel, &dx)) return r;
+  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
+  if (int r = c.out(f, (size_t)B, &df)) return r;
+  if (int r = c.out(grad, nel, &dg)) return r;
   if (h->nq >= 4) {
     QT_LAUNCH_LARGE(qt::k_nll_large, B, h->M, h->prod.R1, (h->view(), dx, dc, B, df, dg));
   } else {
     QT_LAUNCH_SMALL(qt::k_nll_batch, h->M, B, (h->view(), dx, dc, B, df, dg));
   }
-  if (int r = fetch_out(h, df, f, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dg, grad, nel, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_init, const double* deltas,
                   const double* uniforms, int T, double step, double* chain, int32_t* accepted, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (C < 0 || T < 0 || (C > 0 && T > 0 && (!counts || !x_init || !deltas || !uniforms || !chain || !accepted)))
     return fail(QT_ERR_ARG, "bad mhmc_state arguments");
@@ -1035,16 +1039,14 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
   double* dch;
   int32_t* dacc;
   const size_t nel = (size_t)C * T * h->D;
-  if (int r = stage_in(h, h->in0, counts, (size_t)C * h->M, flags, &dc)) return r;
-  if (int r = stage_in(h, h->in1, x_init, (size_t)C * h->D, flags, &dx)) return r;
-  if (int r = stage_in(h, h->out2, deltas, nel, flags, &dd)) return r;
-  if (int r = stage_in(h, h->out3, uniforms, (size_t)C * T, flags, &du)) return r;
-  if (int r = stage_out(h, h->out0, chain, nel, flags, &dch)) return r;
-  if (int r = stage_out(h, h->out1, accepted, (size_t)C * T, flags, &dacc)) return r;
+  if (int r = c.in(counts, (size_t)C * h->M, &dc)) return r;
+  if (int r = c.in(x_init, (size_t)C * h->D, &dx)) return r;
+  if (int r = c.in(deltas, nel, &dd)) return r;
+  if (int r = c.in(uniforms, (size_t)C * T, &du)) return r;
+  if (int r = c.out(chain, nel, &dch)) return r;
+  if (int r = c.out(accepted, (size_t)C * T, &dacc)) return r;
   QT_LAUNCH_SMALL(qt::k_mhmc_state, h->M, C, (h->view(), dc, C, dx, dd, du, T, step, dch, dacc));
-  if (int r = fetch_out(h, dch, chain, nel, flags)) return r;
-  if (int r = fetch_out(h, dacc, accepted, (size_t)C * T, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch and qt_mle_dist_batch
@@ -1052,26 +1054,26 @@ static int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init
                           const double* centre, double* rho, double* dist, int32_t* nit, int32_t* nfev, double* fun,
                           int32_t* status, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad mle_batch arguments");
   if (init != QT_INIT_LIN && init != QT_INIT_MIXED) return fail(QT_ERR_ARG, "init must be QT_INIT_LIN or QT_INIT_MIXED");
   if (max_iter < 0) return fail(QT_ERR_ARG, "max_iter < 0");
   if (B == 0) return 0;
   const int64_t* dc;
-  const double* dcen = nullptr;
+  const double* dcen;
   double *drho, *dfun, *ddist;
   int32_t *dnit, *dnfev, *dst;
   const size_t nel = (size_t)B * h->D;
-  if (int r = stage_in(h, h->in0, counts, (size_t)B * h->M, flags, &dc)) return r;
-  if (dist)
-    if (int r = stage_in(h, h->in1, centre, (size_t)h->D * 2, flags, &dcen)) return r;
-  if (int r = stage_out(h, h->out0, rho, nel * 2, flags, &drho)) return r;
-  if (int r = stage_out(h, h->out5, dist, (size_t)B, flags, &ddist)) return r;
+  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
+  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
+  if (int r = c.out(rho, nel * 2, &drho)) return r;
+  if (int r = c.out(nit, (size_t)B, &dnit)) return r;
+  if (int r = c.out(nfev, (size_t)B, &dnfev)) return r;
+  if (int r = c.out(fun, (size_t)B, &dfun)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
+  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
   const qt::EstOut eo{drho, dcen, ddist};
-  if (int r = stage_out(h, h->out1, nit, (size_t)B, flags, &dnit)) return r;
-  if (int r = stage_out(h, h->out2, nfev, (size_t)B, flags, &dnfev)) return r;
-  if (int r = stage_out(h, h->out3, fun, (size_t)B, flags, &dfun)) return r;
-  if (int r = stage_out(h, h->out4, status, (size_t)B, flags, &dst)) return r;
   if (h->nq >= 4) {
     if (int r = prepare_large(h, init == QT_INIT_LIN)) return r;
     // BFGS history: 2 D doubles per iteration and trial, processed in chunks of <= 4 GiB
@@ -1154,14 +1156,7 @@ static int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init
       h->lds_extra = 0;
     }
   }
-  if (int r = fetch_out(h, drho, rho, nel * 2, flags)) return r;
-  if (int r = fetch_out(h, dnit, nit, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dnfev, nfev, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dfun, fun, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, ddist, dist, (size_t)B, flags)) return r;
-  if (int r = finish(h, flags)) return r;
-  return count_bad(status, B, flags);
+  return c.done(status, B);
 }
 
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
@@ -1179,50 +1174,49 @@ int qt_mle_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int init, in
 
 int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, int B, double* dist, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || (B > 0 && (!rho || !centre || !dist))) return fail(QT_ERR_ARG, "bad hs_dist arguments");
   if (B == 0) return 0;
   const double *dr, *dcn;
   double* dd;
-  if (int r = stage_in(h, h->in0, rho, (size_t)B * h->D * 2, flags, &dr)) return r;
-  if (int r = stage_in(h, h->in1, centre, (size_t)h->D * 2, flags, &dcn)) return r;
-  if (int r = stage_out(h, h->out0, dist, (size_t)B, flags, &dd)) return r;
+  if (int r = c.in(rho, (size_t)B * h->D * 2, &dr)) return r;
+  if (int r = c.in(centre, (size_t)h->D * 2, &dcn)) return r;
+  if (int r = c.out(dist, (size_t)B, &dd)) return r;
   hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, h->d, dr, dcn, B, dd);
-  if (int r = fetch_out(h, dd, dist, (size_t)B, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // the same for dim x dim matrices of any size (the Choi matrices of an n-qubit channel are 4^n x 4^n: 2n-qubit objects)
 int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* centre, int B, double* dist, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (dim < 1 || dim > 4096 || B < 0 || (B > 0 && (!rho || !centre || !dist))) return fail(QT_ERR_ARG, "bad hs_dist arguments");
   if (B == 0) return 0;
   const size_t ne = (size_t)dim * dim;
   const double *dr, *dcn;
   double* dd;
-  if (int r = stage_in(h, h->in0, rho, (size_t)B * ne * 2, flags, &dr)) return r;
-  if (int r = stage_in(h, h->in1, centre, ne * 2, flags, &dcn)) return r;
-  if (int r = stage_out(h, h->out0, dist, (size_t)B, flags, &dd)) return r;
+  if (int r = c.in(rho, (size_t)B * ne * 2, &dr)) return r;
+  if (int r = c.in(centre, ne * 2, &dcn)) return r;
+  if (int r = c.out(dist, (size_t)B, &dd)) return r;
   hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, dim, dr, dcn, B, dd);
-  if (int r = fetch_out(h, dd, dist, (size_t)B, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // ---- a16: interval.py:610-612 ------------------------------------------------------------------------
 int qt_sort_f64(qt_handle_t* h, double* x, long long n, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (n < 0 || (n > 0 && !x)) return fail(QT_ERR_ARG, "bad sort arguments");
   if (n > 0x7fffffffLL) return fail(QT_ERR_UNSUPPORTED, "qt_sort_f64 sorts at most 2^31 - 1 values");
   if (n == 0) return 0;
-  const double* din;
-  if (int r = stage_in(h, h->in0, (const double*)x, (size_t)n, flags, &din)) return r;
-  double* dx = const_cast<double*>(din);
+  double* dx;
+  if (int r = c.inout(x, (size_t)n, &dx)) return r;
   if (n <= 8192) {  // one workgroup, bitonic network in LDS
     int np2 = 2;
     while (np2 < n) np2 <<= 1;
     hipLaunchKernelGGL(qt::k_sort_small, dim3(1), dim3(np2 / 2 < 1024 ? (np2 / 2 < 64 ? 64 : np2 / 2) : 1024), np2 * sizeof(double),
                        h->stream, dx, (int)n, np2);
-    if (int r = fetch_out(h, (const double*)dx, x, (size_t)n, flags)) return r;
-    return finish(h, flags);
+    return c.done();
   }
   HIPCHK(h->sort_alt.ensure((size_t)n * sizeof(double)));
   hipcub::DoubleBuffer<double> keys(dx, h->sort_alt.as<double>());
@@ -1232,24 +1226,23 @@ int qt_sort_f64(qt_handle_t* h, double* x, long long n, int flags) {
   HIPCHK(hipcub::DeviceRadixSort::SortKeys(h->sort_tmp.p, tmp_bytes, keys, (int)n, 0, 64, h->stream));
   if (keys.Current() != dx)
     HIPCHK(hipMemcpyAsync(dx, keys.Current(), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  if (int r = fetch_out(h, (const double*)dx, x, (size_t)n, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_sorted_quantiles(qt_handle_t* h, const double* sorted, long long n, const double* conf_levels, int n_levels,
                         double* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (n < 1 || n_levels < 0 || !sorted || (n_levels > 0 && (!conf_levels || !out)))
     return fail(QT_ERR_ARG, "bad sorted_quantiles arguments");
   if (n_levels == 0) return 0;
   const double *ds, *dq;
   double* dout;
-  if (int r = stage_in(h, h->in0, sorted, (size_t)n, flags, &ds)) return r;
-  if (int r = stage_in(h, h->in1, conf_levels, (size_t)n_levels, flags, &dq)) return r;
-  if (int r = stage_out(h, h->out0, out, (size_t)n_levels, flags, &dout)) return r;
+  if (int r = c.in(sorted, (size_t)n, &ds)) return r;
+  if (int r = c.in(conf_levels, (size_t)n_levels, &dq)) return r;
+  if (int r = c.out(out, (size_t)n_levels, &dout)) return r;
   hipLaunchKernelGGL(qt::k_interp_sorted, dim3((n_levels + 255) / 256), dim3(256), 0, h->stream, ds, n, dq, n_levels, dout);
-  if (int r = fetch_out(h, dout, out, (size_t)n_levels, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // ---- a16 over several ranks: the order statistics interp1d needs from a sample whose sorted shards live on N ranks
@@ -1257,71 +1250,71 @@ int qt_sorted_quantiles(qt_handle_t* h, const double* sorted, long long n, const
 int qt_select_splitters(qt_handle_t* h, const double* sorted, long long n, long long stride, int P, double* splitters,
                         int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (n < 0 || stride < 1 || P < 1 || (n > 0 && !sorted) || !splitters) return fail(QT_ERR_ARG, "bad select_splitters arguments");
   const double* ds;
   double* dout;
-  if (int r = stage_in(h, h->in0, sorted, (size_t)(n > 0 ? n : 1), n > 0 ? flags : QT_DEVICE_PTR, &ds)) return r;
-  if (int r = stage_out(h, h->out0, splitters, (size_t)P, flags, &dout)) return r;
+  if (int r = c.in(sorted, (size_t)n, &ds)) return r;
+  if (int r = c.out(splitters, (size_t)P, &dout)) return r;
   hipLaunchKernelGGL(qt::k_select_splitters, dim3((P + 255) / 256), dim3(256), 0, h->stream, ds, n, stride, P, dout);
-  if (int r = fetch_out(h, dout, splitters, (size_t)P, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_select_bracket(qt_handle_t* h, const double* splitters, int N, int P, const int64_t* sizes, long long stride,
                       long long n_total, const double* conf_levels, int L, uint64_t* lo_key, uint64_t* hi_key, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (N < 1 || P < 1 || L < 1 || stride < 1 || n_total < 0 || !splitters || !sizes || !conf_levels || !lo_key || !hi_key)
     return fail(QT_ERR_ARG, "bad select_bracket arguments");
   const double *dspl, *dq;
   const int64_t* dsz;
   uint64_t *dlo, *dhi;
-  if (int r = stage_in(h, h->in0, splitters, (size_t)N * P, flags, &dspl)) return r;
-  if (int r = stage_in(h, h->in1, sizes, (size_t)N, flags, &dsz)) return r;
-  if (int r = stage_in(h, h->out2, conf_levels, (size_t)L, flags, &dq)) return r;
-  if (int r = stage_out(h, h->out0, lo_key, (size_t)L, flags, &dlo)) return r;
-  if (int r = stage_out(h, h->out1, hi_key, (size_t)L, flags, &dhi)) return r;
+  if (int r = c.in(splitters, (size_t)N * P, &dspl)) return r;
+  if (int r = c.in(sizes, (size_t)N, &dsz)) return r;
+  if (int r = c.in(conf_levels, (size_t)L, &dq)) return r;
+  if (int r = c.out(lo_key, (size_t)L, &dlo)) return r;
+  if (int r = c.out(hi_key, (size_t)L, &dhi)) return r;
   hipLaunchKernelGGL(qt::k_select_init, dim3((L + 255) / 256), dim3(256), 0, h->stream,
                      reinterpret_cast<unsigned long long*>(dlo), reinterpret_cast<unsigned long long*>(dhi), L);
   hipLaunchKernelGGL(qt::k_select_bracket, dim3((unsigned)(((size_t)N * P + 255) / 256)), dim3(256), 0, h->stream, dspl, N, P,
                      reinterpret_cast<const long long*>(dsz), stride, n_total, dq, L,
                      reinterpret_cast<unsigned long long*>(dlo), reinterpret_cast<unsigned long long*>(dhi));
-  if (int r = fetch_out(h, (const uint64_t*)dlo, lo_key, (size_t)L, flags)) return r;
-  if (int r = fetch_out(h, (const uint64_t*)dhi, hi_key, (size_t)L, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_select_window(qt_handle_t* h, const double* sorted, long long n, const uint64_t* lo_key, const uint64_t* hi_key, int L,
                      int W, double* window, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (n < 0 || L < 1 || W < 1 || (n > 0 && !sorted) || !lo_key || !hi_key || !window)
     return fail(QT_ERR_ARG, "bad select_window arguments");
   const double* ds;
   const uint64_t *dlo, *dhi;
   double* dwin;
   const size_t wn = (size_t)L * (2 + W);
-  if (int r = stage_in(h, h->in0, sorted, (size_t)(n > 0 ? n : 1), n > 0 ? flags : QT_DEVICE_PTR, &ds)) return r;
-  if (int r = stage_in(h, h->in1, lo_key, (size_t)L, flags, &dlo)) return r;
-  if (int r = stage_in(h, h->out2, hi_key, (size_t)L, flags, &dhi)) return r;
-  if (int r = stage_out(h, h->out0, window, wn, flags, &dwin)) return r;
+  if (int r = c.in(sorted, (size_t)n, &ds)) return r;
+  if (int r = c.in(lo_key, (size_t)L, &dlo)) return r;
+  if (int r = c.in(hi_key, (size_t)L, &dhi)) return r;
+  if (int r = c.out(window, wn, &dwin)) return r;
   hipLaunchKernelGGL(qt::k_select_window, dim3(L), dim3(256), 0, h->stream, ds, n,
                      reinterpret_cast<const unsigned long long*>(dlo), reinterpret_cast<const unsigned long long*>(dhi), W, dwin);
-  if (int r = fetch_out(h, dwin, window, wn, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_select_finish(qt_handle_t* h, const double* windows, int N, int L, int W, long long n_total, const double* conf_levels,
                      double* out, int32_t* overflow, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (N < 1 || L < 1 || W < 1 || n_total < 1 || !windows || !conf_levels || !out || !overflow)
     return fail(QT_ERR_ARG, "bad select_finish arguments");
   const double *dw, *dq;
   double* dout;
   int32_t* dfl;
   const size_t wn = (size_t)N * L * (2 + W);
-  if (int r = stage_in(h, h->in0, windows, wn, flags, &dw)) return r;
-  if (int r = stage_in(h, h->in1, conf_levels, (size_t)L, flags, &dq)) return r;
-  if (int r = stage_out(h, h->out0, out, (size_t)L, flags, &dout)) return r;
-  if (int r = stage_out(h, h->out1, overflow, 1, flags, &dfl)) return r;
+  if (int r = c.in(windows, wn, &dw)) return r;
+  if (int r = c.in(conf_levels, (size_t)L, &dq)) return r;
+  if (int r = c.out(out, (size_t)L, &dout)) return r;
+  if (int r = c.out(overflow, 1, &dfl)) return r;
   HIPCHK(hipMemsetAsync(dfl, 0, sizeof(int32_t), h->stream));
   size_t cap = (size_t)N * W;
   if (cap > 16000) cap = 16000;  // 128 KB of LDS; a larger union raises the overflow flag (heavy ties: take the merge path)
@@ -1329,15 +1322,14 @@ int qt_select_finish(qt_handle_t* h, const double* windows, int N, int L, int W,
   if (int r = allow_big_lds(qt::k_select_finish, lds)) return r;
   hipLaunchKernelGGL(qt::k_select_finish, dim3(L), dim3(1024), lds, h->stream, dw, N, L, W, (int)cap, n_total, dq, dout,
                      reinterpret_cast<int*>(dfl));
-  if (int r = fetch_out(h, dout, out, (size_t)L, flags)) return r;
-  if (int r = fetch_out(h, dfl, overflow, 1, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // R sorted runs, concatenated in `runs` (lengths: a HOST array, the launch geometry depends on them) -> out sorted.
 // Pairwise merge-path passes, ceil(log2 R) of them, ping-ponging between out and a scratch buffer.
 int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengths, int R, double* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (R < 1 || !run_lengths || !out) return fail(QT_ERR_ARG, "bad merge_sorted arguments");
   long long n = 0;
   for (int r = 0; r < R; ++r) {
@@ -1348,8 +1340,8 @@ int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengt
   if (!runs) return fail(QT_ERR_ARG, "bad merge_sorted arguments");
   const double* din;
   double* dout;
-  if (int r = stage_in(h, h->in0, runs, (size_t)n, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, out, (size_t)n, flags, &dout)) return r;
+  if (int r = c.in(runs, (size_t)n, &din)) return r;
+  if (int r = c.out(out, (size_t)n, &dout)) return r;
   std::vector<long long> len(run_lengths, run_lengths + R);
   int passes = 0;
   for (int m = R; m > 1; m = (m + 1) / 2) ++passes;
@@ -1381,14 +1373,14 @@ int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengt
       dst = (dst == dout) ? alt : dout;
     }
   }
-  if (int r = fetch_out(h, (const double*)dout, out, (size_t)n, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // ---- f2: stats.py:21-47 over a batch (MomentInterval, interval.py:59-110) ------------------------------------------------
 int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, const double* ns, const double* inv_matrix,
                     int rows, double n_trials, double* mean, double* var, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || S < 1 || K < 1 || rows < 1 || !(n_trials > 0.0) || !ns || !inv_matrix || (B > 0 && (!counts || !mean || !var)))
     return fail(QT_ERR_ARG, "bad moment_batch arguments");
   const long long M = (long long)S * K;
@@ -1397,14 +1389,14 @@ int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, 
   const int64_t* dc;
   const double *dns, *dp;
   double *dmean, *dvar;
-  if (int r = stage_in(h, h->in0, counts, (size_t)B * M, flags, &dc)) return r;
-  if (int r = stage_in(h, h->in1, ns, (size_t)S, flags, &dns)) return r;
-  if (int r = stage_in(h, h->out2, inv_matrix, (size_t)rows * M, flags, &dp)) return r;
-  if (int r = stage_out(h, h->out0, mean, (size_t)B, flags, &dmean)) return r;
-  if (int r = stage_out(h, h->out1, var, (size_t)B, flags, &dvar)) return r;
+  if (int r = c.in(counts, (size_t)B * M, &dc)) return r;
+  if (int r = c.in(ns, (size_t)S, &dns)) return r;
+  if (int r = c.in(inv_matrix, (size_t)rows * M, &dp)) return r;
+  if (int r = c.out(mean, (size_t)B, &dmean)) return r;
+  if (int r = c.out(var, (size_t)B, &dvar)) return r;
   // W = P^T P on the matrix cores ([M x rows] . [rows x M])
-  HIPCHK(h->out3.ensure((size_t)M * M * sizeof(double)));
-  double* dW = h->out3.as<double>();
+  HIPCHK(h->gram.ensure((size_t)M * M * sizeof(double)));
+  double* dW = h->gram.as<double>();
   hipLaunchKernelGGL(qt::k_gemm<0>, dim3((unsigned)((M + 15) / 16), (unsigned)((M + 15) / 16)), dim3(64), 0, h->stream, (int)M, (int)M,
                      rows, dp, (int)M, 1, dp, (int)M, 0, dW, (int)M);
   if (M <= 1024) {
@@ -1418,9 +1410,7 @@ int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, 
     if (int r = allow_big_lds(qt::k_moment_batch<1, 32>, lds)) return r;
     hipLaunchKernelGGL((qt::k_moment_batch<1, 32>), dim3(B), dim3(256), lds, h->stream, dc, B, S, K, dns, dW, n_trials, dmean, dvar);
   }
-  if (int r = fetch_out(h, dmean, mean, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dvar, var, (size_t)B, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 // ---- a4 / a12 / a16 host side: state.py:109-114, the draws of experiment() (qt_sampler.h) ---------
@@ -1465,18 +1455,19 @@ static int check_pvals(int period, int K, const int64_t* n, const double* pvals)
 int qt_device_multinomial(qt_handle_t* h, uint64_t seed, uint64_t first_row, long long rows, int period,
                           const int64_t* n, const double* pvals, int K, int64_t* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!n || !pvals || (rows > 0 && !out) || rows < 0 || period < 1 || K < 1)
     return fail(QT_ERR_ARG, "bad device_multinomial arguments");
   if (rows > (1LL << 40)) return fail(QT_ERR_UNSUPPORTED, "qt_device_multinomial draws at most 2^40 rows per call");
-  if (!(flags & QT_DEVICE_PTR))
+  if (!c.device())  // (device arrays are not read on the host)
     if (int r = check_pvals(period, K, n, pvals)) return r;
   if (rows == 0) return 0;
   const int64_t* dn;
   const double* dp;
   int64_t* dout;
-  if (int r = stage_in(h, h->in0, n, (size_t)period, flags, &dn)) return r;
-  if (int r = stage_in(h, h->in1, pvals, (size_t)period * K, flags, &dp)) return r;
-  if (int r = stage_out(h, h->out0, out, (size_t)rows * K, flags, &dout)) return r;
+  if (int r = c.in(n, (size_t)period, &dn)) return r;
+  if (int r = c.in(pvals, (size_t)period * K, &dp)) return r;
+  if (int r = c.out(out, (size_t)rows * K, &dout)) return r;
   // whole 64 x period blocks of rows per launch (a wavefront = one setting of 64 consecutive resamples); a launch covers at
   // most 2^30 threads -- HIP rejects grids of 2^32 threads and more -- so larger tables go out in chunks, each keyed by its
   // own first row: the table depends on (seed, global row) only
@@ -1488,8 +1479,7 @@ int qt_device_multinomial(qt_handle_t* h, uint64_t seed, uint64_t first_row, lon
     hipLaunchKernelGGL(qt_sampler::k_multinomial_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, seed,
                        first_row + (uint64_t)r0, nr, period, dn, dp, K, dout + (size_t)r0 * K);
   }
-  if (int r = fetch_out(h, (const int64_t*)dout, out, (size_t)rows * K, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 void qt_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out) { qt_sampler::philox4x32_10(ctr, key, out); }
@@ -1497,14 +1487,15 @@ void qt_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
 // ---- a5 for arbitrary matrices: routines.py:69-71 -------------------------------------------------
 int qt_left_inverse(qt_handle_t* h, const double* A, int rows, int cols, int is_complex, double* out, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!A || !out || rows < 1 || cols < 1) return fail(QT_ERR_ARG, "bad left_inverse arguments");
   if (rows < cols) return fail(QT_ERR_SINGULAR, "matrix has fewer rows (%d) than columns (%d)", rows, cols);
   const int W = is_complex ? 2 : 1;
   const size_t nel = (size_t)rows * cols * W;
   const double* dA;
   double* dout;
-  if (int r = stage_in(h, h->in0, A, nel, flags, &dA)) return r;
-  if (int r = stage_out(h, h->out0, out, nel, flags, &dout)) return r;
+  if (int r = c.in(A, nel, &dA)) return r;
+  if (int r = c.out(out, nel, &dout)) return r;
   DevBuf& aug = h->proc_aug;
   HIPCHK(aug.ensure((size_t)cols * 2 * cols * W * sizeof(double)));
   HIPCHK(h->info.ensure(sizeof(int)));
@@ -1523,9 +1514,8 @@ int qt_left_inverse(qt_handle_t* h, const double* A, int rows, int cols, int is_
   }
   int info = 0;
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (int r = fetch_out(h, dout, out, nel, flags)) return r;
-  HIPCHK(hipGetLastError());
-  QT_STREAM_SYNC(h);
+  if (int r = c.done()) return r;
+  if (c.device()) HIPCHK(hipStreamSynchronize(h->stream));  // (done() waits for host arrays only) the pivot report
   if (info != 0) return fail(QT_ERR_SINGULAR, "A^T A is singular (no pivot in column %d)", info - 1);
   return 0;
 }
@@ -1533,6 +1523,7 @@ int qt_left_inverse(qt_handle_t* h, const double* A, int rows, int cols, int is_
 // ---- process tomography: qt_process.h -------------------------------------------------------------
 int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (!in_states) return fail(QT_ERR_ARG, "null in_states");
   if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "process tomography supports n_qubits 1..3 in this release");
@@ -1549,8 +1540,7 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
     HIPCHK(hipMalloc(&ps.vs_pinv, (size_t)D * D * 2 * sizeof(double)));
     HIPCHK(hipMalloc(&ps.vp_pinv, (size_t)D * M * 2 * sizeof(double)));
     HIPCHK(hipMalloc(&ps.vp_pinvT, (size_t)M * D * 2 * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(ps.in_states, in_states, (size_t)D * D * 2 * sizeof(double),
-                          (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    if (int r = c.copy_in((double*)ps.in_states, in_states, (size_t)D * D * 2)) return r;
     hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->stream, h->nq, h->Aw.as<double>(),
                        M, (double*)ps.emats);
     int info[2] = {0, 0};
@@ -1565,7 +1555,7 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
                          D, d, 4, (double*)ps.vp_perm);
     }
     HIPCHK(hipGetLastError());
-    QT_STREAM_SYNC(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
     if (info[0] != 0) return fail(QT_ERR_SINGULAR, "input states do not span the operator space (column %d)", info[0] - 1);
     if (info[1] != 0) return fail(QT_ERR_SINGULAR, "POVM is not informationally complete (column %d)", info[1] - 1);
     ps.factored = true;
@@ -1579,8 +1569,7 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
   HIPCHK(hipMalloc(&ps.pinvT, R * C2 * 2 * sizeof(double)));
   HIPCHK(hipMalloc(&ps.aug, C2 * 2 * C2 * 2 * sizeof(double)));
   HIPCHK(h->info.ensure(sizeof(int)));
-  HIPCHK(hipMemcpyAsync(ps.in_states, in_states, (size_t)D * D * 2 * sizeof(double),
-                        (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  if (int r = c.copy_in((double*)ps.in_states, in_states, (size_t)D * D * 2)) return r;
   double *lifp = (double*)ps.lifp, *pinv = (double*)ps.pinv, *pinvT = (double*)ps.pinvT, *aug = (double*)ps.aug;
   // E_m = sum_k A'[m][k] P_k  (process.py:204: Qobj(povm_bloch).matrix)
   hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->stream, h->nq, h->Aw.as<double>(),
@@ -1618,7 +1607,7 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
                        1, (double*)ps.vp_perm);
   }
   HIPCHK(hipGetLastError());
-  QT_STREAM_SYNC(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "process design matrix is rank deficient (column %d): input states x POVM not complete", info - 1);
   if (factors && (finfo[0] != 0 || finfo[1] != 0)) {  // (cannot happen when the Kronecker product itself has full rank)
     (void)hipFree(ps.vp_perm);
@@ -1630,15 +1619,15 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
 
 int qt_process_get_operators(qt_handle_t* h, double* lifp_oper, double* lifp_oper_inv, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   if (h->proc.factored)
     return fail(QT_ERR_UNSUPPORTED, "at n = 3 the design matrix is kept Kronecker-factored (qt_process_get_factors); its dense "
                                     "form would be 2 x 906 MB");
-  const size_t bytes = (size_t)h->D * h->M * h->D * h->D * 2 * sizeof(double);
-  const hipMemcpyKind kind = (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (lifp_oper) HIPCHK(hipMemcpyAsync(lifp_oper, h->proc.lifp, bytes, kind, h->stream));
-  if (lifp_oper_inv) HIPCHK(hipMemcpyAsync(lifp_oper_inv, h->proc.pinv, bytes, kind, h->stream));
-  return finish(h, flags);
+  const size_t n = (size_t)h->D * h->M * h->D * h->D * 2;
+  if (int r = c.copy_out(lifp_oper, (const double*)h->proc.lifp, n)) return r;
+  if (int r = c.copy_out(lifp_oper_inv, (const double*)h->proc.pinv, n)) return r;
+  return c.done();
 }
 
 int qt_process_prefer_dense(qt_handle_t* h, int on) {
@@ -1649,19 +1638,20 @@ int qt_process_prefer_dense(qt_handle_t* h, int on) {
 
 int qt_process_get_factors(qt_handle_t* h, double* vs_pinv, double* vp_pinv, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   if (!h->proc.vs_pinv || !h->proc.vp_pinv)
     return fail(QT_ERR_UNSUPPORTED, "this set-up keeps the dense operator only (n = 1, or a POVM with M % 4 != 0 at n = 2): "
                                     "qt_process_get_operators");
-  const hipMemcpyKind kind = (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (vs_pinv) HIPCHK(hipMemcpyAsync(vs_pinv, h->proc.vs_pinv, (size_t)h->D * h->D * 2 * sizeof(double), kind, h->stream));
-  if (vp_pinv) HIPCHK(hipMemcpyAsync(vp_pinv, h->proc.vp_pinv, (size_t)h->D * h->M * 2 * sizeof(double), kind, h->stream));
-  return finish(h, flags);
+  if (int r = c.copy_out(vs_pinv, (const double*)h->proc.vs_pinv, (size_t)h->D * h->D * 2)) return r;
+  if (int r = c.copy_out(vp_pinv, (const double*)h->proc.vp_pinv, (size_t)h->D * h->M * 2)) return r;
+  return c.done();
 }
 
 int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double* choi, int32_t* iters, int32_t* status,
                   int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   if (B < 0 || (B > 0 && (!counts || !choi))) return fail(QT_ERR_ARG, "bad lifp_batch arguments");
   if (B == 0) return 0;
@@ -1669,10 +1659,10 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
   const int64_t* dc;
   double* dchoi;
   int32_t *dit, *dst;
-  if (int r = stage_in(h, h->in0, counts, (size_t)B * D * M, flags, &dc)) return r;
-  if (int r = stage_out(h, h->out0, choi, (size_t)B * D * D * 2, flags, &dchoi)) return r;
-  if (int r = stage_out(h, h->out1, iters, (size_t)B, flags, &dit)) return r;
-  if (int r = stage_out(h, h->out2, status, (size_t)B, flags, &dst)) return r;
+  if (int r = c.in(counts, (size_t)B * D * M, &dc)) return r;
+  if (int r = c.out(choi, (size_t)B * D * D * 2, &dchoi)) return r;
+  if (int r = c.out(iters, (size_t)B, &dit)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
   if (h->proc.factored) {  // n = 3: X = V_S^+ F V_P^+^T, two small products per process (qt_process64.h)
     if ((size_t)B * D > (size_t)1 << 26) return fail(QT_ERR_ARG, "batch too large");
     const int R = D * M;  // 13824: a multiple of 64, the pitch k_lifp_freq pads to
@@ -1704,11 +1694,7 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
       hipLaunchKernelGGL(qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, h->stream, (const double*)raw,
                          B, 0, 1000, 1e-12, dchoi, dit, dst, h->proc_ws.as<double>());
     }
-    if (int r = fetch_out(h, dchoi, choi, (size_t)B * D * D * 2, flags)) return r;
-    if (int r = fetch_out(h, dit, iters, (size_t)B, flags)) return r;
-    if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-    if (int r = finish(h, flags)) return r;
-    return count_bad(status, B, flags);
+    return c.done(status, B);
   }
   const size_t dyn = (size_t)D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
@@ -1787,16 +1773,13 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
     hipLaunchKernelGGL(qt::k_lifp_batch<16>, dim3(B), dim3(qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M,
                        (const double*)h->proc.pinvT, cptp, dchoi, dit, dst);
   }
-  if (int r = fetch_out(h, dchoi, choi, (size_t)B * D * D * 2, flags)) return r;
-  if (int r = fetch_out(h, dit, iters, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-  if (int r = finish(h, flags)) return r;
-  return count_bad(status, B, flags);
+  return c.done(status, B);
 }
 
 int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, double tol, int stop_rule, double* choi,
                   int32_t* iters, int32_t* status, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   if (B < 0 || (B > 0 && (!counts || !choi))) return fail(QT_ERR_ARG, "bad pgdb_batch arguments");
   if (stop_rule != 0 && stop_rule != 1) return fail(QT_ERR_ARG, "stop_rule must be 0 (reference) or 1 (converged)");
@@ -1806,10 +1789,10 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
   const int64_t* dc;
   double* dchoi;
   int32_t *dit, *dst;
-  if (int r = stage_in(h, h->in0, counts, (size_t)B * D * M, flags, &dc)) return r;
-  if (int r = stage_out(h, h->out0, choi, (size_t)B * D * D * 2, flags, &dchoi)) return r;
-  if (int r = stage_out(h, h->out1, iters, (size_t)B, flags, &dit)) return r;
-  if (int r = stage_out(h, h->out2, status, (size_t)B, flags, &dst)) return r;
+  if (int r = c.in(counts, (size_t)B * D * M, &dc)) return r;
+  if (int r = c.out(choi, (size_t)B * D * D * 2, &dchoi)) return r;
+  if (int r = c.out(iters, (size_t)B, &dit)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
   if (h->proc.factored) {  // n = 3: three launches per iteration over the batch, loop state on the device (qt_process64.h)
     using S = qt::Pgdb64;
     const size_t ne2 = (size_t)D * D * 2;
@@ -1836,15 +1819,11 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
                          n_active);
       int left = 0;
       HIPCHK(hipMemcpyAsync(&left, n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      QT_STREAM_SYNC(h);
+      HIPCHK(hipStreamSynchronize(h->stream));
       if (left <= 0) break;
     }
     HIPCHK(hipGetLastError());
-    if (int r = fetch_out(h, dchoi, choi, (size_t)B * D * D * 2, flags)) return r;
-    if (int r = fetch_out(h, dit, iters, (size_t)B, flags)) return r;
-    if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-    if (int r = finish(h, flags)) return r;
-    return count_bad(status, B, flags);
+    return c.done(status, B);
   }
   const size_t dyn = (size_t)4 * D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
@@ -1854,16 +1833,13 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
   else
     hipLaunchKernelGGL(qt::k_pgdb_batch<16>, dim3(B), dim3(qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M,
                        (const double*)h->proc.lifp, n_iter, tol, stop_rule, dchoi, dit, dst);
-  if (int r = fetch_out(h, dchoi, choi, (size_t)B * D * D * 2, flags)) return r;
-  if (int r = fetch_out(h, dit, iters, (size_t)B, flags)) return r;
-  if (int r = fetch_out(h, dst, status, (size_t)B, flags)) return r;
-  if (int r = finish(h, flags)) return r;
-  return count_bad(status, B, flags);
+  return c.done(status, B);
 }
 
 int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* choi_in, double* probas, double* grad,
                    double* projected, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   if (B < 0 || (B > 0 && (!counts || !choi_in))) return fail(QT_ERR_ARG, "bad pgdb_pieces arguments");
   if (!h->proc.factored) return fail(QT_ERR_UNSUPPORTED, "qt_pgdb_pieces inspects the factored (n = 3) iteration");
@@ -1873,8 +1849,8 @@ int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* c
   const size_t ne2 = (size_t)D * D * 2, wsd = S::ws_doubles(M);
   const int64_t* dc;
   const double* dcur;
-  if (int r = stage_in(h, h->in0, counts, (size_t)B * R, flags, &dc)) return r;
-  if (int r = stage_in(h, h->in1, choi_in, (size_t)B * ne2, flags, &dcur)) return r;
+  if (int r = c.in(counts, (size_t)B * R, &dc)) return r;
+  if (int r = c.in(choi_in, (size_t)B * ne2, &dcur)) return r;
   HIPCHK(h->ws_x.ensure((size_t)B * wsd * sizeof(double)));
   HIPCHK(h->ws_g.ensure((size_t)B * ne2 * sizeof(double)));
   HIPCHK(h->ws_f.ensure((size_t)B * ne2 * sizeof(double)));
@@ -1890,7 +1866,7 @@ int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* c
                      (const double*)h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), (int32_t*)nullptr,
                      (int32_t*)nullptr, h->proc_ws.as<double>());
   HIPCHK(hipGetLastError());
-  const hipMemcpyKind kind = (flags & QT_DEVICE_PTR) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const hipMemcpyKind kind = c.to_caller();
   const double* ws = h->ws_x.as<double>();
   if (probas)
     HIPCHK(hipMemcpy2DAsync(probas, (size_t)R * sizeof(double), ws + (size_t)2 * D * M, wsd * sizeof(double),
@@ -1898,13 +1874,14 @@ int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* c
   if (grad)
     HIPCHK(hipMemcpy2DAsync(grad, ne2 * sizeof(double), ws + (size_t)2 * D * M + 3 * (size_t)R, wsd * sizeof(double),
                             ne2 * sizeof(double), B, kind, h->stream));
-  if (projected) HIPCHK(hipMemcpyAsync(projected, h->ws_f.p, (size_t)B * ne2 * sizeof(double), kind, h->stream));
-  return finish(h, flags);
+  if (int r = c.copy_out(projected, h->ws_f.as<double>(), (size_t)B * ne2)) return r;
+  return c.done();
 }
 
 int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* choi_init, const double* deltas,
                     const double* uniforms, int T, double step, double* chain, int32_t* accepted, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   if (C < 0 || T < 0 || (C > 0 && T > 0 && (!counts || !choi_init || !deltas || !uniforms || !chain || !accepted)))
     return fail(QT_ERR_ARG, "bad mhmc_process arguments");
@@ -1915,12 +1892,12 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
   const double *dx, *dd, *du;
   double* dch;
   int32_t* dacc;
-  if (int r = stage_in(h, h->in0, counts, (size_t)C * D * M, flags, &dc)) return r;
-  if (int r = stage_in(h, h->in1, choi_init, (size_t)C * ne * 2, flags, &dx)) return r;
-  if (int r = stage_in(h, h->out2, deltas, (size_t)C * T * ne, flags, &dd)) return r;
-  if (int r = stage_in(h, h->out3, uniforms, (size_t)C * T, flags, &du)) return r;
-  if (int r = stage_out(h, h->out0, chain, (size_t)C * T * ne * 2, flags, &dch)) return r;
-  if (int r = stage_out(h, h->out1, accepted, (size_t)C * T, flags, &dacc)) return r;
+  if (int r = c.in(counts, (size_t)C * D * M, &dc)) return r;
+  if (int r = c.in(choi_init, (size_t)C * ne * 2, &dx)) return r;
+  if (int r = c.in(deltas, (size_t)C * T * ne, &dd)) return r;
+  if (int r = c.in(uniforms, (size_t)C * T, &du)) return r;
+  if (int r = c.out(chain, (size_t)C * T * ne * 2, &dch)) return r;
+  if (int r = c.out(accepted, (size_t)C * T, &dacc)) return r;
   if (h->proc.factored) {  // n = 3: three launches per step, the chain's state stays on the device (qt_process64.h)
     using S = qt::Pgdb64;
     const int nt = qt::Fwd64::tiles(M);
@@ -1951,9 +1928,7 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
                          (const double*)h->ws_f.as<double>(), du, x, fcur, dch, dacc);
     }
     HIPCHK(hipGetLastError());
-    if (int r = fetch_out(h, dch, chain, (size_t)C * T * ne * 2, flags)) return r;
-    if (int r = fetch_out(h, dacc, accepted, (size_t)C * T, flags)) return r;
-    return finish(h, flags);
+    return c.done();
   }
   const size_t dyn = (size_t)2 * D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
@@ -1963,14 +1938,13 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
   else
     hipLaunchKernelGGL(qt::k_mhmc_process<16>, dim3(C), dim3(qt::ProcWG<16>::NT), dyn, h->stream, dc, C, M,
                        (const double*)h->proc.lifp, dx, dd, du, T, step, dch, dacc);
-  if (int r = fetch_out(h, dch, chain, (size_t)C * T * ne * 2, flags)) return r;
-  if (int r = fetch_out(h, dacc, accepted, (size_t)C * T, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol, double* choi_out,
                           int32_t* iters, int flags) {
   QT_ENTER(h);
+  Call c(h, flags);
   if (B < 0 || (B > 0 && (!choi_in || !choi_out))) return fail(QT_ERR_ARG, "bad cptp_project arguments");
   if (mode < 0 || mode > 2) return fail(QT_ERR_ARG, "mode must be 0 (CPTP), 1 (TP) or 2 (CP)");
   if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "process tomography supports n_qubits 1..3 in this release");
@@ -1979,9 +1953,9 @@ int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode
   const double* din;
   double* dout;
   int32_t* dit;
-  if (int r = stage_in(h, h->in0, choi_in, (size_t)B * D * D * 2, flags, &din)) return r;
-  if (int r = stage_out(h, h->out0, choi_out, (size_t)B * D * D * 2, flags, &dout)) return r;
-  if (int r = stage_out(h, h->out1, iters, (size_t)B, flags, &dit)) return r;
+  if (int r = c.in(choi_in, (size_t)B * D * D * 2, &din)) return r;
+  if (int r = c.out(choi_out, (size_t)B * D * D * 2, &dout)) return r;
+  if (int r = c.out(iters, (size_t)B, &dit)) return r;
   if (D == 64) {
     if (int r = allow_big_lds(qt::k_cptp_project64, qt::Proc64::kLdsBytes)) return r;
     if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));  // Dykstra's p, q, y, x + the clip's input
@@ -1993,9 +1967,7 @@ int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode
   else
     hipLaunchKernelGGL(qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, h->stream, din, B, mode, n_iter, tol, dout, dit,
                        (int32_t*)nullptr);
-  if (int r = fetch_out(h, dout, choi_out, (size_t)B * D * D * 2, flags)) return r;
-  if (int r = fetch_out(h, dit, iters, (size_t)B, flags)) return r;
-  return finish(h, flags);
+  return c.done();
 }
 
 }  // extern "C"
