@@ -230,6 +230,25 @@ int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengt
 int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, const double* ns, const double* inv_matrix,
                     int rows, double n_trials, double* mean, double* var, int flags);
 
+/* ---- f3: quantpy/tomography/interval.py:268-335 (PolytopeStateInterval: 2 * n_points cvxopt `solvers.lp` calls) -----
+ * R x O dense linear programs that share one constraint matrix:
+ *     minimise C[o] . x  subject to  A x <= b[r],  x in R^N free          (r < R, o < O)
+ * A[M][N], C[O][N], b[R][M]; obj[R][O], x[R][O][N] (nullable: the final iterate), status[R][O] (qt_lp_status),
+ * iters[R][O] (nullable: interior-point iterations of both phases).  One workgroup per program: primal-dual interior
+ * point (Mehrotra predictor-corrector) on the normal matrix A^T diag(z / s) A, with a phase-1 program for a strictly
+ * feasible start (csrc/qt_lp.h).  A streams from L2 in row blocks: M is not limited by LDS.  N <= 64 (n <= 3 qubits:
+ * N = 4^n - 1), M >= N.  obj is +inf for INFEASIBLE, -inf for UNBOUNDED, NaN for NOT_CONVERGED.  When A is
+ * numerically rank deficient (a pivot of the Cholesky factor of A^T A below 1e-12 of its diagonal entry) every program
+ * reports NOT_CONVERGED.  Host-pointer calls return the number of programs whose status is not OPTIMAL. */
+enum qt_lp_status {
+  QT_LP_OPTIMAL = 0,       /* relative duality gap and scaled primal / dual residuals <= 1e-10 */
+  QT_LP_INFEASIBLE = 1,    /* no x satisfies A x <= b (phase 1 converged to t* >= 0)           */
+  QT_LP_UNBOUNDED = 2,     /* feasible iterates along which the objective diverges              */
+  QT_LP_NOT_CONVERGED = 3  /* iteration cap (100 per phase), non-finite value or Cholesky breakdown */
+};
+int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                     double* obj, double* x, int32_t* status, int32_t* iters, int flags);
+
 /* Metropolis-Hastings chains on the Cholesky parameters (mhmc.py:80-119 with `normalized_update`, used by
  * MHMCStateInterval, interval.py:735-750): C independent chains (the reference runs one), each on its
  * own counts[c][S][K]; x_init[C][D]; proposal increments deltas[C][T][D] and uniforms[C][T] drawn by the

@@ -17,6 +17,7 @@ QT_OPT_SHOTS_CHECK, QT_OPT_MLE_FUSED_MAX_WAVES = 1, 2  # qt_set_option
 # status codes (include/qtomo.h)
 QT_ERR_ARG, QT_ERR_STATE, QT_ERR_HIP, QT_ERR_SINGULAR, QT_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 TRIAL_OK, TRIAL_NOT_PD, TRIAL_LINESEARCH, TRIAL_MAXITER, TRIAL_NAN, TRIAL_SHOTS = 0, 1, 2, 3, 4, 5
+LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_NOT_CONVERGED = 0, 1, 2, 3  # qt_lp_status
 
 _c_int = ctypes.c_int
 _c_dbl = ctypes.c_double
@@ -64,6 +65,7 @@ SIGNATURES = {
     "qt_select_finish": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp, _vp, _vp, _c_int]),
     "qt_merge_sorted": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_moment_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_dbl, _vp, _vp, _c_int]),
+    "qt_lp_ineq_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
     "qt_legacy_multinomial": (_c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.c_longlong, _c_int, _vp, _vp, _c_int, _vp]),
     "qt_device_multinomial": (_c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_longlong, _c_int, _vp, _vp, _c_int, _vp,
                                        _c_int]),

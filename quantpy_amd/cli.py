@@ -5,8 +5,9 @@ confidence radii out.
 Input keys: `povm_matrix` (S, K, 4^n), `outcomes` (state: (S, K); process: (D, S, K)), `input_states`
 (process: D Bloch vectors), `conf_levels`; optional `target_state` / `target_process`.  Output keys:
 `state` / `process` (Bloch vector of the unconstrained linear-inversion estimate), `hs_radius`.
-The fidelity bounds the reference adds when a target is given come from a cvxopt SOCP
-(MomentFidelity*Interval) and are not produced; `hs_radius` is the same MomentInterval either way.
+With a `target_state` the state script adds `fidelity_min` / `fidelity_max` (MomentFidelityStateInterval, clipped to
+[0, 1] as reference scripts/state_interval.py:50-58 does) and takes `hs_radius` from that interval.  The process
+script's fidelity bounds (MomentFidelityProcessInterval) are not produced; its `hs_radius` is the MomentInterval's.
 """
 import json
 import sys
@@ -55,7 +56,15 @@ def state_interval(argv=None):
     tmg.results = results  # the setter derives the shots per setting from the counts
     output = {"state": list(tmg.point_estimate(physical=False).bloch)}
     if not args.no_ci:
-        _radius(qp, tmg, data, output, "target_state")
+        if "target_state" in data:
+            interval = qp.MomentFidelityStateInterval(tmg, target_state=qp.Qobj(data["target_state"]))
+            interval.setup()
+            (fidelity_min, fidelity_max), _ = interval(data["conf_levels"])
+            output["fidelity_min"] = list(np.maximum(fidelity_min, 0))
+            output["fidelity_max"] = list(np.minimum(fidelity_max, 1))
+            output["hs_radius"] = list(interval.cl_to_dist(data["conf_levels"]))
+        else:
+            _radius(qp, tmg, data, output, "target_state")
     _emit(output, args.output)
     return output
 

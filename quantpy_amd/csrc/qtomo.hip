@@ -14,6 +14,7 @@
 
 #include "../../include/qtomo.h"
 #include "qt_large.h"
+#include "qt_lp.h"
 #include "qt_ops.h"
 #include "qt_process.h"
 #include "qt_process64.h"
@@ -99,6 +100,7 @@ struct qt_handle {
   DevBuf stage[kStageBufs];
   DevBuf proc_aug, proc_ws;
   DevBuf gram;  // qt_moment_batch: P^T P
+  DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -1411,6 +1413,37 @@ int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, 
     hipLaunchKernelGGL((qt::k_moment_batch<1, 32>), dim3(B), dim3(256), lds, h->stream, dc, B, S, K, dns, dW, n_trials, dmean, dvar);
   }
   return c.done();
+}
+
+// ---- f3: interval.py:268-335, the LPs of PolytopeStateInterval (qt_lp.h) ---------------------------------------------
+int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                     double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (!A || !C || !b || !obj || !status) return fail(QT_ERR_ARG, "qt_lp_ineq_batch: null array");
+  if (N < 1 || M < N || O < 1 || R < 1) return fail(QT_ERR_ARG, "qt_lp_ineq_batch: bad sizes (M=%d N=%d O=%d R=%d)", M, N, O, R);
+  if (N > qt::kLpMaxN) return fail(QT_ERR_UNSUPPORTED, "qt_lp_ineq_batch supports up to %d variables (got %d)", qt::kLpMaxN, N);
+  const long long P = (long long)R * O;
+  if (P > (1LL << 30)) return fail(QT_ERR_ARG, "qt_lp_ineq_batch: too many programs (%lld)", P);
+  const double *dA, *dC, *db;
+  double *dobj, *dx;
+  int32_t *dst, *dit;
+  if (int r = c.in(A, (size_t)M * N, &dA)) return r;
+  if (int r = c.in(C, (size_t)O * N, &dC)) return r;
+  if (int r = c.in(b, (size_t)R * M, &db)) return r;
+  if (int r = c.out(obj, (size_t)P, &dobj)) return r;
+  if (int r = c.out(x, (size_t)P * N, &dx)) return r;
+  if (int r = c.out(status, (size_t)P, &dst)) return r;
+  if (int r = c.out(iters, (size_t)P, &dit)) return r;
+  // persistent workgroups: at most 2048, and at most 256 MB of workspace
+  const size_t per_wg = (size_t)qt::kLpWs * M * sizeof(double);
+  long long grid = P < 2048 ? P : 2048;
+  const long long by_ws = (long long)((256u << 20) / per_wg);
+  if (grid > by_ws) grid = by_ws > 0 ? by_ws : 1;
+  HIPCHK(h->lp_ws.ensure((size_t)grid * per_wg));
+  hipLaunchKernelGGL(qt::k_lp_ineq, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj, dx, dst,
+                     dit, h->lp_ws.as<double>());
+  return c.done(status, (int)P);
 }
 
 // ---- a4 / a12 / a16 host side: state.py:109-114, the draws of experiment() (qt_sampler.h) ---------

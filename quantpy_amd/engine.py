@@ -639,6 +639,25 @@ class Engine:
                                            _ptr(var), _capi.QT_HOST_PTR))
         return (mean[0], var[0]) if single else (mean, var)
 
+    # ---- f3: interval.py:268-335 -----------------------------------------------------------------------
+    def lp_ineq_batch(self, A, C, b, return_x=False):
+        """min C[o] . x subject to A x <= b[r] for every r, o (qt_lp_ineq_batch): A (M, N), C (O, N), b (R, M) ->
+        (obj (R, O), status (R, O), iters (R, O)[, x (R, O, N)]).  status: _capi.LP_* (obj +inf when infeasible, -inf
+        when unbounded, NaN when not converged).  N <= 64."""
+        a = _f64(A)
+        c = _f64(np.atleast_2d(C))
+        rhs = _f64(np.atleast_2d(b))
+        m, n = a.shape
+        o, r = c.shape[0], rhs.shape[0]
+        assert c.shape[1] == n and rhs.shape[1] == m
+        obj = np.empty((r, o))
+        status = np.empty((r, o), dtype=np.int32)
+        iters = np.empty((r, o), dtype=np.int32)
+        x = np.empty((r, o, n)) if return_x else None
+        self._chk(self.lib.qt_lp_ineq_batch(self._h, _ptr(a), m, n, _ptr(c), o, _ptr(rhs), r, _ptr(obj), _ptr(x),
+                                            _ptr(status), _ptr(iters), _capi.QT_HOST_PTR))
+        return (obj, status, iters, x) if return_x else (obj, status, iters)
+
     def sort_dev(self, x):
         """`x.sort()` in place for a float64 torch CUDA tensor (qt_sort_f64; NaN last like np.sort); asynchronous."""
         self._dev_call()

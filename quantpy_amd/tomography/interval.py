@@ -13,10 +13,15 @@ law.  Its one heavy step, the left inverse of the (state or process) design matr
 O(M^2) matrix form, batched over trials).
 
 `MHMCStateInterval` / `MHMCProcessInterval` run their chains on the GPU (qt_mhmc_state / qt_mhmc_process);
-`SugiyamaInterval` and `HolderInterval` are closed-form / compositions over those.  The four intervals that
-need cvxopt's SOCP / LP solvers (MomentFidelity{State,Process}Interval, Polytope{State,Process}Interval) are
-names that raise NotImplementedError: SURVEY.md section 2 row 11 puts them out of scope and the image has no
-cvxopt to validate against.
+`SugiyamaInterval` and `HolderInterval` are closed-form / compositions over those.
+
+The two state intervals the reference builds on cvxopt give fidelity bounds against a target state.
+`PolytopeStateInterval` (Kiktenko et al., arXiv:2109.04734; reference interval.py:268-335) solves its 2 * n_points
+linear programs, which share one constraint matrix, in ONE launch of the batched interior-point solver
+(qt_lp_ineq_batch).  `MomentFidelityStateInterval` (interval.py:113-160) poses one second-order cone program per
+confidence level whose optimum has a closed form (a linear objective over a ball cut by a hyperplane), so it needs no
+solver.  Their process counterparts (MomentFidelityProcessInterval, PolytopeProcessInterval) are still names that
+raise NotImplementedError.
 """
 from abc import ABC, abstractmethod
 from enum import Enum, auto
@@ -451,6 +456,169 @@ class HolderInterval(ConfidenceInterval):
             interval.setup()
 
 
+def count_confidence(delta, frequencies, n_measurements):
+    """Confidence level of the polytope of frequencies widened by `delta` (reference polytopes/utils.py:4-15): the
+    product over settings of max(1 - sum over outcomes of exp(-n_s KL(f || clip(f + delta))), 0), with the
+    divergence +inf where the clip reaches its top and the term 0 for a frequency of 1."""
+    eps = 1e-15
+    f = np.asarray(frequencies, dtype=np.float64)
+    shifted = np.clip(f + delta, eps, 1 - eps)
+    kl = f * np.log(f / shifted) + (1 - f) * np.log((1 - f) / (1 - shifted))
+    kl = np.where(shifted < 1 - eps, kl, np.inf)
+    eps_k = np.exp(-np.asarray(n_measurements)[:, None] * kl)
+    eps_k = np.where(np.abs(f - 1) < 2 * eps, 0, eps_k)
+    return np.prod(np.maximum(1 - np.sum(eps_k, axis=-1), 0))
+
+
+def count_delta(target_cl, frequencies, n_measurements):
+    """The widening whose confidence level is `target_cl` (reference polytopes/utils.py:18-27): bisection on
+    [1e-10, 1] down to a width of 1e-10, the left end moving while the level is below target + 1e-10; the last
+    midpoint is returned."""
+    left, right = 1e-10, 1.0
+    delta = None
+    while right - left > 1e-10:
+        delta = (left + right) / 2
+        if count_confidence(delta, frequencies, n_measurements) < target_cl + 1e-10:
+            left = delta
+        else:
+            right = delta
+    return delta
+
+
+def _state_only(interval, name):
+    if interval.mode == Mode.CHANNEL:
+        raise NotImplementedError(f"{name} works only for state tomography")
+
+
+def _objective_or_one(value, to_fidelity):
+    """The reference's `if not sol["primal objective"]: 1` (interval.py:146-153, :313-322): a missing optimum
+    (cvxopt's None for an infeasible or unbounded program) and an optimum of exactly 0.0 both give 1."""
+    value = np.asarray(value, dtype=np.float64)
+    return np.where(np.isfinite(value) & (value != 0.0), to_fidelity(value), 1.0)
+
+
+class MomentFidelityStateInterval(MomentInterval):
+    """Fidelity bounds with a target state from the moment interval's radii (reference interval.py:113-160).
+
+    For every level of a fixed 280-point grid the reference solves two SOCPs with cvxopt: minimise (maximise)
+    target.bloch . x over Bloch vectors x with x_0 = 1 / d and ||x - x_hat|| <= radius * sqrt(2 / d), x_hat being the
+    tomograph's (unconstrained) linear-inversion estimate.  That program is a linear objective over a ball cut by a
+    hyperplane, whose optimum is closed-form: c_0 / d + c' . x_hat' -+ rho ||c'|| with rho^2 = R^2 - (x_hat_0 - 1/d)^2
+    (primes drop index 0); an empty cut (rho^2 < 0) and an optimum of exactly 0.0 give 1, as the reference's
+    `if not sol["primal objective"]` does.  The bounds are not clipped to [0, 1] (the reference clips only in its
+    command-line script).
+
+    Deviation: a process tomograph raises NotImplementedError in __init__ (the reference fails later, in setup)."""
+
+    def __init__(self, tmg, distr_type="gamma", target_state=None):
+        super().__init__(tmg, distr_type=distr_type)
+        self.target_state = target_state
+        _state_only(self, "MomentFidelityStateInterval")
+
+    def __call__(self, conf_levels=None):
+        if conf_levels is None:
+            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
+        if not hasattr(self, "cl_to_dist_max"):
+            self.setup()
+        return (self.cl_to_dist_min(conf_levels), self.cl_to_dist_max(conf_levels)), conf_levels
+
+    @staticmethod
+    def levels():
+        """The reference's grid of confidence levels (interval.py:131)."""
+        return np.concatenate((np.arange(1e-7, 0.8, 0.01), np.linspace(0.8, 1 - 1e-7, 200)))
+
+    def setup(self):
+        super().setup()
+        tmg = self.tmg
+        if not hasattr(tmg, "reconstructed_state"):
+            tmg.point_estimate(physical=False)
+        if self.target_state is None:
+            self.target_state = tmg.reconstructed_state
+        dim = 2**tmg.state.n_qubits
+        conf_levels = self.levels()
+        radius = np.asarray(self.cl_to_dist(conf_levels), dtype=np.float64) * np.sqrt(2 / dim)
+        c = np.asarray(self.target_state.bloch, dtype=np.float64)
+        x_hat = np.asarray(tmg.reconstructed_state.bloch, dtype=np.float64)
+        rho2 = radius**2 - (x_hat[0] - 1 / dim) ** 2
+        rho = np.sqrt(np.maximum(rho2, 0.0))
+        centre = c[0] / dim + c[1:] @ x_hat[1:]
+        norm = np.linalg.norm(c[1:])
+        low = np.where(rho2 >= 0, centre - rho * norm, np.nan)     # min c . x
+        high = np.where(rho2 >= 0, -centre - rho * norm, np.nan)   # min -c . x
+        self.conf_levels = conf_levels
+        self.dist_min = _objective_or_one(low, lambda v: v * dim)
+        self.dist_max = _objective_or_one(high, lambda v: -v * dim)
+        self.cl_to_dist_min = interp1d(conf_levels, self.dist_min)
+        self.cl_to_dist_max = interp1d(conf_levels, self.dist_max)
+
+
+class PolytopeStateInterval(ConfidenceInterval):
+    """Fidelity bounds with a target state from a polytope of states (Kiktenko et al., arXiv:2109.04734; reference
+    interval.py:268-335).
+
+    For n_points widenings delta between count_delta(0) and count_delta(1 - 1e-7) the Bloch vectors whose outcome
+    probabilities lie within clip(f + delta) form a polytope A x <= b(delta); the fidelity bounds at confidence level
+    count_confidence(delta) are 1/d + d min(c . x) and 1/d - d min(-c . x) over it, c = target.bloch[1:].  The
+    reference makes 2 * n_points cvxopt `solvers.lp` calls; here all of them are one launch of the batched
+    interior-point solver (qt_lp_ineq_batch, n <= 3 qubits).  As in the reference an infeasible or unbounded program,
+    and an optimum of exactly 0.0 (always the case for c = 0, e.g. the maximally mixed target), give 1.  A program that
+    does not converge raises.  A POVM that is not informationally complete (rank of A below 4^n - 1) raises ValueError
+    before any launch, as cvxopt's `lp` does on such a G.
+
+    Deviation: a process tomograph raises NotImplementedError in __init__ (the reference raises it in setup)."""
+
+    def __init__(self, tmg, n_points=1000, target_state=None):
+        super().__init__(tmg, **_pop_hidden_keys(locals()))
+        _state_only(self, "PolytopeStateInterval")
+
+    def __call__(self, conf_levels=None):
+        if conf_levels is None:
+            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
+        if not hasattr(self, "cl_to_dist_max"):
+            self.setup()
+        return (self.cl_to_dist_min(conf_levels), self.cl_to_dist_max(conf_levels)), conf_levels
+
+    def programs(self):
+        """(A, b (n_points, M), c, deltas, frequencies) of the reference's LPs (interval.py:297-316)."""
+        tmg = self.tmg
+        n_qubits = tmg.state.n_qubits
+        if n_qubits > 3:
+            raise NotImplementedError(f"PolytopeStateInterval supports n <= 3 qubits (4^n - 1 <= 64 LP variables); "
+                                      f"got n = {n_qubits}")
+        dim = 2**n_qubits
+        shots = np.asarray(tmg.n_measurements, dtype=np.float64)
+        frequencies = np.clip(np.asarray(tmg.results) / shots[:, None], self.EPS, 1 - self.EPS)
+        povm = np.asarray(tmg.povm_matrix, dtype=np.float64)
+        weighted = np.reshape(povm * shots[:, None, None] / np.sum(shots), (-1, povm.shape[-1])) * povm.shape[0]
+        A = np.ascontiguousarray(weighted[:, 1:]) * dim
+        if np.linalg.matrix_rank(A) < A.shape[1]:
+            raise ValueError("Rank(A) < size(x): the POVM is not informationally complete")
+        c = np.asarray(self.target_state.bloch, dtype=np.float64)[1:]
+        deltas = np.linspace(count_delta(0, frequencies, shots), count_delta(1 - 1e-7, frequencies, shots), self.n_points)
+        b = np.clip(np.ravel(frequencies)[None, :] + deltas[:, None], self.EPS, 1 - self.EPS) - weighted[None, :, 0]
+        return A, b, c, deltas, frequencies
+
+    def setup(self):
+        tmg = self.tmg
+        if self.target_state is None:
+            self.target_state = tmg.state
+        dim = 2**tmg.state.n_qubits
+        A, b, c, deltas, frequencies = self.programs()
+        obj, status, iters = get_engine(tmg.state.n_qubits).lp_ineq_batch(A, np.stack([c, -c]), b)
+        from .. import _capi
+
+        bad = np.flatnonzero((status == _capi.LP_NOT_CONVERGED).any(axis=1))
+        if bad.size:
+            raise RuntimeError(f"the interior-point LP solver did not converge at delta index {bad[:8].tolist()}")
+        self.deltas, self.lp_status, self.lp_iters = deltas, status, iters
+        self.dist_min = _objective_or_one(obj[:, 0], lambda v: 1 / dim + v * dim)
+        self.dist_max = _objective_or_one(obj[:, 1], lambda v: 1 / dim - v * dim)
+        shots = np.asarray(tmg.n_measurements, dtype=np.float64)
+        self.conf_levels = np.array([count_confidence(d, frequencies, shots) for d in deltas])
+        self.cl_to_dist_min = interp1d(self.conf_levels, self.dist_min)
+        self.cl_to_dist_max = interp1d(self.conf_levels, self.dist_max)
+
+
 def _needs_cvxopt(name, lines):
     def __init__(self, *args, **kwargs):
         raise NotImplementedError(f"{name} (reference interval.py:{lines}) poses a cone / linear program for cvxopt; "
@@ -460,9 +628,7 @@ def _needs_cvxopt(name, lines):
                                               "__doc__": f"Placeholder: the reference's {name} needs cvxopt."})
 
 
-MomentFidelityStateInterval = _needs_cvxopt("MomentFidelityStateInterval", "113-160")
 MomentFidelityProcessInterval = _needs_cvxopt("MomentFidelityProcessInterval", "163-216")
-PolytopeStateInterval = _needs_cvxopt("PolytopeStateInterval", "268-335")
 PolytopeProcessInterval = _needs_cvxopt("PolytopeProcessInterval", "338-418")
 
 
