@@ -252,7 +252,7 @@ int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double
 /* Metropolis-Hastings chains on the Cholesky parameters (mhmc.py:80-119 with `normalized_update`, used by
  * MHMCStateInterval, interval.py:735-750): C independent chains (the reference runs one), each on its
  * own counts[c][S][K]; x_init[C][D]; proposal increments deltas[C][T][D] and uniforms[C][T] drawn by the
- * caller (host RNG, reference order); chain[C][T][D] = state after every step, accepted[C][T].  n <= 3. */
+ * caller (host RNG, reference order); chain[C][T][D] = state after every step, accepted[C][T].  n <= 5. */
 int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_init, const double* deltas,
                   const double* uniforms, int T, double step, double* chain, int32_t* accepted, int flags);
 

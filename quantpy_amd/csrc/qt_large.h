@@ -732,6 +732,42 @@ struct Large {
     __syncthreads();
     QT_STAMP(18);
   }
+
+  // ---- the NLL value alone: the forward half of nll_grad_inl, the same arithmetic in the same order (same bits of f).
+  // Kept beside it rather than factored out of it, so that the MLE kernels' code stays as it was.  No X / Y image is
+  // left for a backward pass; every thread returns the same f (bsum).
+  __device__ __forceinline__ static double nll_value_inl(const Ctx& c, double xt) {
+    double tr;
+    const cd m = build_llh(c, xt, tr);
+    cd* A = c.Aimg();
+    A[c.e] = cd{m.re / tr, m.im / tr};
+    __syncthreads();
+    const double* vec = c.vec();
+    (void)bloch_of(c, A);  // leaves the whole Bloch vector in vec (ends with a barrier)
+    double fpart = 0.0;
+    if (!c.pr.enabled) {  // dense operands: p = d A' b   (uniform per launch)
+      for (int m = c.t; m < c.M; m += NT) {
+        const double pe = row_dot_dense(c, c.AwT, m, vec) * d + 1e-10;
+        fpart += ((double)c.counts[m] / c.tot) * fast_log(pe);
+      }
+    } else {
+      const int R1 = c.pr.R1;
+      const double* in = vec;
+      for (int q = 1; q < NQ; ++q) {  // stages 1 .. n-1, stage n-1 in Y
+        const int lk = 2 * (NQ - q);
+        const int n_out = ipow(R1, q) << lk;
+        double* out = ((NQ - 1 - q) & 1) ? c.X() : c.Y();
+        stage<true>(c, c.tabT(), lk, n_out, in, out);
+        in = out;
+      }
+      for (int o = c.t; o < c.M; o += NT) {  // stage n fused with the likelihood terms
+        const double xn = stage_value<true>(c.tabT(), R1, stage_entry<true>(R1, 0, o), 1, in);
+        const double pe = xn * c.pr.wrowR[o] * d + 1e-10;
+        fpart += freq(c, o) * fast_log(pe);
+      }
+    }
+    return -bsum(c, fpart);
+  }
 };
 
 // =========================================================================================
@@ -1053,6 +1089,56 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
     if (nfev_out) nfev_out[b] = nfev;
     if (fun_out) fun_out[b] = fk;
     if (status_out) status_out[b] = status;
+  }
+}
+
+// k_mhmc_state (qt_small.h) at n = 4, 5: one workgroup per chain, thread t owns parameter x[t].  Step t:
+//   x' = (x + step * delta_t) / ||x + step * delta_t||,  alpha = exp(nll(x) - nll(x')),  accept iff u_t <= alpha.
+// chain[c][t][:] = the state AFTER step t, accepted[c][t] = 0 / 1.  The accept test reads only values every thread holds
+// bit for bit (f, fn from bsum) and u_t from one address, so the branch is uniform over the workgroup.
+template <int NQ>
+__global__ void __launch_bounds__(Large<NQ>::NT) k_mhmc_state_large(PovmView pv, const int64_t* __restrict__ counts, int C,
+                                                                    const double* __restrict__ x_init,
+                                                                    const double* __restrict__ deltas,
+                                                                    const double* __restrict__ uniforms, int T_steps,
+                                                                    double step, double* __restrict__ chain,
+                                                                    int32_t* __restrict__ accepted) {
+  using S = Large<NQ>;
+  constexpr int D = S::D;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int b = blockIdx.x;
+  if (b >= C) return;
+  typename S::Ctx c;
+  S::make_ctx(c, smem, pv, counts + (size_t)b * pv.M);
+  double x = x_init[(size_t)b * D + c.t];
+  double f = S::nll_value_inl(c, x);
+  const double* dl = deltas + (size_t)b * T_steps * D + c.t;
+  const double* un = uniforms + (size_t)b * T_steps;
+  double* out = chain + (size_t)b * T_steps * D + c.t;
+  for (int t = 0; t < T_steps; ++t) {
+    // the LDS base and the per-thread indices laundered through an empty asm every step, as in k_mle_large_bfgs: else
+    // hipcc hoists the loop-invariant LDS addresses of the evaluation out of the loop and spills them
+    typename S::Ctx ci = c;
+    {
+      int off = 0, v0 = 0;
+      asm volatile("" : "+s"(off));
+      ci.sm = c.sm + off;
+      asm volatile("" : "+v"(v0));
+      ci.t = c.t + v0, ci.i = c.i + v0, ci.j = c.j + v0, ci.e = c.e + v0;
+      ci.xm = c.xm + v0, ci.zm = c.zm + v0, ci.ny = c.ny + v0, ci.pi = c.pi + v0, ci.pj = c.pj + v0;
+    }
+    const double xp = fma(step, dl[(size_t)t * D], x);
+    const double nrm = sqrt(S::bsum(ci, xp * xp));
+    const double xn = xp / nrm;
+    const double fn = S::nll_value_inl(ci, xn);
+    const double alpha = exp(f - fn);
+    const bool acc = un[t] <= alpha;  // false for a NaN alpha, like the reference's comparison
+    if (acc) {
+      x = xn;
+      f = fn;
+    }
+    out[(size_t)t * D] = x;
+    if (c.t == 0) accepted[(size_t)b * T_steps + t] = acc ? 1 : 0;
   }
 }
 

@@ -1034,7 +1034,6 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
   if (int r = need_povm(h)) return r;
   if (C < 0 || T < 0 || (C > 0 && T > 0 && (!counts || !x_init || !deltas || !uniforms || !chain || !accepted)))
     return fail(QT_ERR_ARG, "bad mhmc_state arguments");
-  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "qt_mhmc_state supports n_qubits 1..3");
   if (C == 0 || T == 0) return 0;
   const int64_t* dc;
   const double *dx, *dd, *du;
@@ -1047,7 +1046,11 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
   if (int r = c.in(uniforms, (size_t)C * T, &du)) return r;
   if (int r = c.out(chain, nel, &dch)) return r;
   if (int r = c.out(accepted, (size_t)C * T, &dacc)) return r;
-  QT_LAUNCH_SMALL(qt::k_mhmc_state, h->M, C, (h->view(), dc, C, dx, dd, du, T, step, dch, dacc));
+  if (h->nq >= 4) {
+    QT_LAUNCH_LARGE(qt::k_mhmc_state_large, C, h->M, h->prod.R1, (h->view(), dc, C, dx, dd, du, T, step, dch, dacc));
+  } else {
+    QT_LAUNCH_SMALL(qt::k_mhmc_state, h->M, C, (h->view(), dc, C, dx, dd, du, T, step, dch, dacc));
+  }
   return c.done();
 }
 

@@ -509,7 +509,8 @@ class Engine:
 
     def mhmc_state(self, counts, x_init, deltas, uniforms, step):
         """Metropolis-Hastings chain(s) of mhmc.py on the Cholesky parameters: counts (S, K) or (C, S, K),
-        x_init (D,) / (C, D), deltas (T, D) / (C, T, D), uniforms (T,) / (C, T) -> (chain (.., T, D), accepted (.., T))."""
+        x_init (D,) / (C, D), deltas (T, D) / (C, T, D), uniforms (T,) / (C, T) -> (chain (.., T, D), accepted (.., T)).
+        n = 1 .. 5 qubits (k_mhmc_state, n = 4, 5: k_mhmc_state_large, one workgroup per chain)."""
         c, single = self._counts(counts)
         nchain = c.shape[0]
         x0 = _f64(x_init).reshape(nchain, self.D)

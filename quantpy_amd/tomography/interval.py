@@ -47,9 +47,10 @@ def _proposal_increments(dim):
     `multivariate_normal(mean=zeros(dim))` (mhmc.py / interval.py:735-738, :822-825) on np.random's global stream.
     That call ends in `RandomState.multivariate_normal`, which draws standard_normal((size, dim)) and multiplies by
     sqrt(s) v of svd(cov); for the identity covariance LAPACK returns s = 1, v = I exactly, so the product is the draws
-    themselves.  Up to dim 256 the reference's own call is made; above (three-qubit processes: dim 4096, where the
-    eigen-decomposition in the constructor and the SVD per call cost ~20 s each) the draws are taken directly -- the
-    n = 3 chains of tests/golden/mhmc3.npz, made by the reference through the full call, pin the equivalence."""
+    themselves.  Up to dim 256 the reference's own call is made; above (five-qubit states: dim 1024; three-qubit
+    processes: dim 4096, where the eigen-decomposition in the constructor and the SVD per call cost ~20 s each) the
+    draws are taken directly -- the n = 5 state chain of tests/golden/mhmc_large.npz and the n = 3 process chains of
+    tests/golden/mhmc3.npz, made by the reference through the full call, pin the equivalence."""
     if dim <= 256:
         from scipy.stats import multivariate_normal
 
@@ -335,7 +336,7 @@ class MHMCStateInterval(ConfidenceInterval):
     The random numbers are drawn here exactly as the reference draws them -- proposal increments from
     scipy's frozen `multivariate_normal(zeros(4^n))`, then `numpy.random.rand`, first for the burn-in,
     then for the samples -- and the chain itself (one likelihood evaluation per step, inherently serial)
-    runs in one launch of `qt_mhmc_state`."""
+    runs in one launch of `qt_mhmc_state`, for n = 1 .. 5 qubits (n = 4, 5: one workgroup per chain)."""
 
     def __init__(self, tmg, n_points=1000, step=0.01, burn_steps=1000, thinning=1, warm_start=False,
                  use_new_estimate=False, state=None, verbose=False):
