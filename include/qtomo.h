@@ -189,7 +189,9 @@ int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, in
 int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* centre, int B, double* dist, int flags);
 
 /* ---- a16: quantpy/tomography/interval.py:610-612 (and :683-685) -------------------------------- */
-/* `dist.sort()`: ascending in-place sort of n float64 values (radix sort on the device; NaN last). */
+/* `dist.sort()`: ascending in-place sort of n float64 values in np.sort's order (NaN last; bitonic in LDS up to 8192
+ * values, device radix sort above).  The output is np.sort's by value, with canonical bits: either zero is written as
+ * +0.0 and every NaN, whatever its sign and payload, as the quiet NaN 0x7ff8000000000000. */
 int qt_sort_f64(qt_handle_t* h, double* x, long long n, int flags);
 /* `interp1d(np.linspace(0, 1, n), sorted)(conf_levels)`: scipy's linear interp1d on real 1-D data is numpy.interp, and
  * these are its semantics on the grid x_i = i / (n - 1) -- cell x_j <= q < x_(j+1), a level ON a grid point returns
@@ -219,7 +221,8 @@ int qt_select_window(qt_handle_t* h, const double* sorted, long long n, const ui
 int qt_select_finish(qt_handle_t* h, const double* windows, int N, int L, int W, long long n_total, const double* conf_levels,
                      double* out, int32_t* overflow, int flags);
 /* R sorted runs stored back to back in runs (run_lengths[R]: always a HOST array) -> out: their merge in np.sort's
- * order (NaN last), by ceil(log2 R) merge-path passes.  out must not alias runs. */
+ * order (NaN last), by ceil(log2 R) merge-path passes.  out must not alias runs.  The values keep their bits; runs
+ * sorted by np.sort (zeros interleaved, NaNs of either sign last) merge like runs from qt_sort_f64. */
 int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengths, int R, double* out, int flags);
 
 /* ---- f2: quantpy/stats.py:21-47 over a batch of trials (MomentInterval, interval.py:59-110) ----------------------

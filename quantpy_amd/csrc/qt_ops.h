@@ -568,19 +568,37 @@ __global__ void __launch_bounds__(64) k_hs_dist(int d, const double* __restrict_
   }
 }
 
+// ---- the one sort key of the order-statistics path: np.sort's order ---------------------------------------------------
+// Order-preserving 64-bit key (sign-flipped IEEE bits) of the CANONICAL value: -0.0 gets +0.0's key, and every NaN,
+// whatever its sign and payload, the key of the quiet NaN 0x7ff8000000000000, 0xfff8000000000000: above +inf's
+// (0xfff0000000000000) and below ~0.  So np.sort's ties (the two zeros; all NaNs, last) are ties here too, a shard sorted
+// by np.sort is monotone in the keys, and no value has a sentinel key (0 / ~0 = "none" in k_select_*, ~0 = k_sort_small's
+// padding).  Formed from the bits; the comparisons below (key_le / key_lt) give the same order on the values, cheaper
+// than forming two keys.  The host restatement is _sort_keys in quantpy_amd/distributed.py.
+__device__ __forceinline__ unsigned long long sort_key(double v) {
+  unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned long long mag = b & 0x7fffffffffffffffull;
+  if (mag > 0x7ff0000000000000ull) return 0xfff8000000000000ull;  // NaN
+  if (mag == 0) b = 0;                                             // -0.0 -> +0.0
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// The value of a key (canonical: +0.0, and 0x7ff8000000000000 for the NaN key).
+__device__ __forceinline__ double key_value(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+// sort_key(a) <= sort_key(b) and sort_key(a) < sort_key(b) without forming keys: on non-NaN values the key order is IEEE
+// order with the two zeros equal, and a NaN is above everything else.  (IEEE comparisons: no -ffast-math here.)
+__device__ __forceinline__ bool key_le(double a, double b) { return b != b || a <= b; }
+__device__ __forceinline__ bool key_lt(double a, double b) { return a == a && (b != b || a < b); }
+
 // ---- a16: interval.py:610  dist.sort() for small n (<= 8192: every bootstrap the reference's defaults produce) ----
-// One workgroup, bitonic network in LDS on order-preserving 64-bit keys (sign-flipped IEEE bits: the order of a radix
-// sort, NaN last like np.sort).  A device radix sort is five launches for any n; this is one, ~10 us at n = 2048.
+// One workgroup, bitonic network in LDS on sort_key (np.sort's order, NaN last); the keys are written back, so the output
+// holds canonical values: +0.0 for either zero, 0x7ff8000000000000 for every NaN.  A device radix sort is five launches
+// for any n; this is one, ~10 us at n = 2048.
 __global__ void __launch_bounds__(1024) k_sort_small(double* __restrict__ x, int n, int npow2) {
   extern __shared__ unsigned long long keys[];
-  for (int e = threadIdx.x; e < npow2; e += blockDim.x) {
-    unsigned long long k = ~0ull;  // padding sorts behind everything
-    if (e < n) {
-      const unsigned long long b = (unsigned long long)__double_as_longlong(x[e]);
-      k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    }
-    keys[e] = k;
-  }
+  for (int e = threadIdx.x; e < npow2; e += blockDim.x)
+    keys[e] = e < n ? sort_key(x[e]) : ~0ull;  // padding sorts behind everything
   __syncthreads();
   for (int size = 2; size <= npow2; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -596,10 +614,16 @@ __global__ void __launch_bounds__(1024) k_sort_small(double* __restrict__ x, int
       __syncthreads();
     }
   }
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const unsigned long long k = keys[e];
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    x[e] = __longlong_as_double((long long)b);
+  for (int e = threadIdx.x; e < n; e += blockDim.x) x[e] = key_value(keys[e]);
+}
+
+// n > 8192 (qt_sort_f64's radix path): the same canonical values before hipcub::DeviceRadixSort, whose own float mapping
+// orders a NaN with the sign bit set first and gives the two zeros one digit (left interleaved).  Writes only what changes.
+__global__ void __launch_bounds__(256) k_sort_canonical(double* __restrict__ x, long long n) {
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x[e]), mag = b & 0x7fffffffffffffffull;
+    if (mag > 0x7ff0000000000000ull && b != 0x7ff8000000000000ull) x[e] = __longlong_as_double(0x7ff8000000000000LL);
+    else if (b == 0x8000000000000000ull) x[e] = 0.0;
   }
 }
 
@@ -675,32 +699,29 @@ __global__ void k_interp_sorted(const double* __restrict__ y, long long n, const
 //      (k_select_window);  all-gather [N][L][2 + W]
 //   4. the (k - sum below)-th smallest of the windows' union is the k-th of the sample (k_select_finish), then scipy's
 //      interpolation formula on the two values.
-// All comparisons are on the order-preserving 64-bit keys of the radix sort (NaN last, as np.sort has it).
-__device__ __forceinline__ unsigned long long sort_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-// number of keys <= k (UPPER = true) or < k (UPPER = false) in the sorted doubles a[0..n)
+// All comparisons are in sort_key's order (above: np.sort's, NaN last; the zeros one value, every NaN one value), made
+// by key_le / key_lt on the values themselves.
+// number of values whose key is <= sort_key(v) (UPPER = true) or < it (UPPER = false) in the sorted doubles a[0..n)
 template <bool UPPER, class Ptr>
-__device__ __forceinline__ long long count_sorted(Ptr a, long long n, unsigned long long k) {
+__device__ __forceinline__ long long count_sorted(Ptr a, long long n, double v) {
   long long lo = 0, hi = n;
   while (lo < hi) {
     const long long mid = (lo + hi) >> 1;
-    const unsigned long long m = sort_key(a[mid]);
-    if (UPPER ? (m <= k) : (m < k)) lo = mid + 1;
+    const double m = a[mid];
+    if (UPPER ? key_le(m, v) : key_lt(m, v)) lo = mid + 1;
     else hi = mid;
   }
   return lo;
 }
 
-// splitters[j] = sorted[j * stride] for j * stride < n, +inf-most key (NaN pattern ~0) behind; also resets the bracket
-// accumulators of the next step (lo_key[L] = 0 "none", hi_key[L] = ~0 "none") so that no separate memset is needed
+// splitters[j] = sorted[j * stride] for j * stride < n, padded behind with a NaN.  The padding is never a candidate nor
+// counted: k_select_bracket reads only rank r's first ceil(n_r / stride) splitters.
 __global__ void k_select_splitters(const double* __restrict__ sorted, long long n, long long stride, int P,
                                    double* __restrict__ splitters) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= P) return;
   const long long at = (long long)j * stride;
-  splitters[j] = at < n ? sorted[at] : __longlong_as_double(0x7fffffffffffffffLL);  // key ~0: behind everything
+  splitters[j] = at < n ? sorted[at] : __longlong_as_double(0x7fffffffffffffffLL);
 }
 
 __global__ void k_select_init(unsigned long long* __restrict__ lo_key, unsigned long long* __restrict__ hi_key, int L) {
@@ -721,11 +742,12 @@ __global__ void __launch_bounds__(256) k_select_bracket(const double* __restrict
   if (idx >= (long long)N * P) return;
   const int r0 = (int)(idx / P), j0 = (int)(idx % P);
   if ((long long)j0 * stride >= sizes[r0]) return;  // padding
-  const unsigned long long kv = sort_key(spl[idx]);
+  const double v = spl[idx];
+  const unsigned long long kv = sort_key(v);
   long long up = 0, low = 0;
   for (int r = 0; r < N; ++r) {
     const long long nr = sizes[r], pr = (nr + stride - 1) / stride;
-    const long long cnt = count_sorted<true>(spl + (size_t)r * P, pr, kv);
+    const long long cnt = count_sorted<true>(spl + (size_t)r * P, pr, v);
     const long long u = cnt * stride;
     up += u < nr ? u : nr;
     low += cnt > 0 ? (cnt - 1) * stride + 1 : 0;
@@ -748,8 +770,8 @@ __global__ void __launch_bounds__(256) k_select_window(const double* __restrict_
                                                        double* __restrict__ win) {
   const int l = blockIdx.x;
   const unsigned long long lk = lo_key[l], hk = hi_key[l];
-  const long long below = lk == 0ull ? 0 : count_sorted<true>(sorted, n, lk);
-  const long long upto = hk == ~0ull ? n : count_sorted<true>(sorted, n, hk);
+  const long long below = lk == 0ull ? 0 : count_sorted<true>(sorted, n, key_value(lk));
+  const long long upto = hk == ~0ull ? n : count_sorted<true>(sorted, n, key_value(hk));
   const long long w = upto - below;
   double* out = win + (size_t)l * (2 + W);
   if (threadIdx.x == 0) {
@@ -783,8 +805,9 @@ __global__ void __launch_bounds__(1024) k_select_finish(const double* __restrict
       const double* w = gw + ((size_t)r * L + l) * (2 + W);
       below += (long long)w[0];
       off[r] = tot;
-      if (w[1] > (double)W) flag[0] = 1;  // a clipped window: the caller takes the merge path
-      tot += w[1] > (double)W ? W : (int)w[1];
+      // a clipped window: the caller takes the merge path (w < 0 only from a shard that was not sorted: no LDS slot)
+      if (!(w[1] >= 0.0 && w[1] <= (double)W)) flag[0] = 1;
+      tot += w[1] > (double)W ? W : (w[1] > 0.0 ? (int)w[1] : 0);
     }
     off[N] = tot;
     s_below = below;
@@ -808,13 +831,13 @@ __global__ void __launch_bounds__(1024) k_select_finish(const double* __restrict
   }
   const long long t0 = k0 - s_below, t1 = k1 - s_below;
   for (int e = threadIdx.x; e < tot; e += blockDim.x) {
-    const unsigned long long kv = sort_key(cand[e]);
+    const double v = cand[e];
     long long lt = 0, le = 0;
     for (int r = 0; r < N; ++r) {
       const int o = off[r], cnt = (off[r + 1] > cap ? cap : off[r + 1]) - o;
       if (cnt <= 0) continue;
-      lt += count_sorted<false>(cand + o, cnt, kv);
-      le += count_sorted<true>(cand + o, cnt, kv);
+      lt += count_sorted<false>(cand + o, cnt, v);
+      le += count_sorted<true>(cand + o, cnt, v);
     }
     if (lt <= t0 && t0 < le) picked[0] = cand[e];  // (ties: equal values, any writer)
     if (lt <= t1 && t1 < le) picked[1] = cand[e];
@@ -946,14 +969,14 @@ __global__ void __launch_bounds__(256) k_merge_runs(const double* __restrict__ a
   long long lo = diag > nb ? diag - nb : 0, hi = diag < na ? diag : na;  // number taken from a
   while (lo < hi) {
     const long long mid = (lo + hi) >> 1;  // take mid from a, diag - mid from b: valid iff a[mid] > b[diag - mid - 1] fails
-    if (sort_key(a[mid]) <= sort_key(b[diag - mid - 1])) lo = mid + 1;
+    if (key_le(a[mid], b[diag - mid - 1])) lo = mid + 1;
     else hi = mid;
   }
   long long ia = lo, ib = diag - lo;
 #pragma unroll
   for (int e = 0; e < TILE; ++e) {
     if (diag + e >= total) break;
-    const bool take_a = ib >= nb || (ia < na && sort_key(a[ia]) <= sort_key(b[ib]));
+    const bool take_a = ib >= nb || (ia < na && key_le(a[ia], b[ib]));
     out[diag + e] = take_a ? a[ia++] : b[ib++];
   }
 }

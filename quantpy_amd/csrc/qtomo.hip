@@ -1223,6 +1223,8 @@ int qt_sort_f64(qt_handle_t* h, double* x, long long n, int flags) {
                        h->stream, dx, (int)n, np2);
     return c.done();
   }
+  const long long blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(qt::k_sort_canonical, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, h->stream, dx, n);
   HIPCHK(h->sort_alt.ensure((size_t)n * sizeof(double)));
   hipcub::DoubleBuffer<double> keys(dx, h->sort_alt.as<double>());
   size_t tmp_bytes = 0;

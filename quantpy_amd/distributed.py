@@ -130,10 +130,19 @@ def allgather_equal(x, force_collective=False):
 
 
 # ---- interval.py:610-612 for a sample whose shards stay on their ranks --------------------------------------------------
+_KEY_NAN = np.uint64(0xFFF8000000000000)  # every NaN's key: that of 0x7ff8000000000000, above +inf's, below ~0
+
+
 def _sort_keys(a):
-    """Order-preserving uint64 keys of float64 values: the order of np.sort / of the device radix sort (NaN last)."""
+    """Order-preserving uint64 keys of float64 values: the order of np.sort and of qt_sort_f64 (sort_key in
+    csrc/qt_ops.h).  -0.0 gets +0.0's key and every NaN, whatever its sign and payload, the one key _KEY_NAN (NaN last), so
+    a shard sorted by np.sort -- zeros interleaved, NaNs of both signs at the end -- is monotone in these keys, and no value
+    has a sentinel key (0 or ~0)."""
     b = np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-    return np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
+    mag = b & np.uint64(0x7FFFFFFFFFFFFFFF)
+    b = np.where(mag == 0, np.uint64(0), b)
+    k = np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
+    return np.where(mag > np.uint64(0x7FF0000000000000), _KEY_NAN, k)
 
 
 def interp_cell(n, q):
@@ -159,7 +168,7 @@ def interp_value(cell, q, yj, yj1):
     _, xj, xj1, exact = cell
     if exact:
         return yj
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         slope = (yj1 - yj) / (xj1 - xj)
         res = slope * (q - xj) + yj
         if np.isnan(res):

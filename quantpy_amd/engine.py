@@ -660,7 +660,8 @@ class Engine:
         return (obj, status, iters, x) if return_x else (obj, status, iters)
 
     def sort_dev(self, x):
-        """`x.sort()` in place for a float64 torch CUDA tensor (qt_sort_f64; NaN last like np.sort); asynchronous."""
+        """`x.sort()` in place for a float64 torch CUDA tensor (qt_sort_f64; NaN last like np.sort); asynchronous.  The
+        result is np.sort's by value, written canonically: -0.0 as +0.0 and every NaN as 0x7ff8000000000000."""
         self._dev_call()
         self._chk(self.lib.qt_sort_f64(self._h, _ptr(x), x.numel(), _capi.QT_DEVICE_PTR))
         return x
@@ -705,7 +706,8 @@ class Engine:
 
     def merge_sorted(self, runs, lengths, out=None):
         """Merge sorted runs stored back to back (np.sort's order, NaN last).  runs: float64 torch CUDA tensor (then `out`
-        likewise, asynchronous) or NumPy array (a new array is returned); lengths: host integers."""
+        likewise, asynchronous) or NumPy array (a new array is returned); lengths: host integers.  Values keep their bits:
+        the two zeros compare equal, as do all NaNs whatever their sign, so runs sorted by np.sort merge correctly."""
         ln = np.ascontiguousarray(lengths, dtype=np.int64)
         if _is_dev(runs):
             import torch
