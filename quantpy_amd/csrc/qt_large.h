@@ -217,7 +217,7 @@ struct Large {
     bool wide = false;
     uint32_t* cache = nullptr;
     // pv.extra > 0: offset (in doubles) of a 4 M-byte block behind everything else in the LDS allocation, sized by the host
-    // when it fits (QT_LAUNCH_LARGE_X)
+    // when it fits (large_plan in qtomo.hip)
     if (pv.extra > 0 && counts) cache = reinterpret_cast<uint32_t*>(smem + pv.extra);
     c.cnt = cache;
     // Per-setting totals for the shots check, from the values of the load pass itself: the K outcomes of a setting are K

@@ -25,7 +25,6 @@ struct ProcessState {
                              // columns are then the doubles of choi[b] in order); built for n = 2 only
   void* emats = nullptr;     // [M][d][d] complex POVM elements
   void* in_states = nullptr; // [D][d][d] complex
-  void* aug = nullptr;       // [D^2][2 D^2] complex Gauss-Jordan workspace
   void* pinv = nullptr;      // [D^2][D*M] complex
   // n = 3 (qt_process64.h): the design matrix stays Kronecker-factored -- left inverses of its two factors
   void* vs_pinv = nullptr;   // [D][D] complex: left inverse of V_S = [vec rho_s]
@@ -37,7 +36,7 @@ struct ProcessState {
   size_t cap_rows = 0;
   void release() {
     factored = false;
-    for (void** p : {&lifp, &pinvT, &pinvR, &emats, &in_states, &aug, &pinv, &vs_pinv, &vp_pinv, &vp_pinvT, &vp_perm}) {
+    for (void** p : {&lifp, &pinvT, &pinvR, &emats, &in_states, &pinv, &vs_pinv, &vp_pinv, &vp_pinvT, &vp_perm}) {
       if (*p) (void)hipFree(*p);
       *p = nullptr;
     }

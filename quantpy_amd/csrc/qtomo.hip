@@ -10,6 +10,7 @@
 
 #include <chrono>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/qtomo.h"
@@ -89,16 +90,17 @@ struct qt_handle {
   // left inverse (`pinv_ready`, compute_dense_pinv).
   bool povm_set = false, dense_ready = false, a_loaded = false, pinv_ready = false;
   int S = 0, K = 0, M = 0;
-  DevBuf A, AT, Aw, AwT, Pinv, PinvT, Ns, aug, info;
+  DevBuf A, AT, Aw, AwT, Pinv, PinvT, Ns, info;
   // packed row digits of the Kronecker assembly (k_povm_kron), cached per (S1, K1)
   DevBuf kron_dig;
   int kron_S1 = 0, kron_K1 = 0;
   // product-POVM (Kronecker) description, valid when prod.enabled
-  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd, pr_aug;
+  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd;
   qt::ProductView prod{};
   // staging for host-pointer calls: one buffer per array of a call, in the order the call registers them (Call)
   DevBuf stage[kStageBufs];
-  DevBuf proc_aug, proc_ws;
+  DevBuf aug;      // [cols][2 cols] Gauss-Jordan workspace of enqueue_left_inverse
+  DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project64)
   DevBuf gram;  // qt_moment_batch: P^T P
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   // MLE hand-off between k_mle_start and k_mle_bfgs
@@ -115,11 +117,11 @@ struct qt_handle {
   double ns_tot = 0.0;  // sum of the registered shots per setting
   bool check_shots = true;  // qt_set_option(QT_OPT_SHOTS_CHECK) / QTOMO_SKIP_SHOTS_CHECK=1 at qt_create
   int fused_max_waves = 1024;  // qt_set_option(QT_OPT_MLE_FUSED_MAX_WAVES): largest batch (in trial-waves) of k_mle_fused
-  int lds_extra = 0;  // per-trial extra LDS doubles of the launch being prepared (k_mle_bfgs); 0 otherwise
   double ns_max = 0.0;  // largest registered shot number (product POVMs): the n >= 4 count cache holds 32-bit counts
-  qt::PovmView view() const {
+  // the POVM as the estimator kernels read it; `extra` (PovmView::extra) comes with the launch's LDS size (Plan)
+  qt::PovmView view(int extra) const {
     return qt::PovmView{Aw.as<double>(), AwT.as<double>(), PinvT.as<double>(), M, prod, jtol2,
-                        check_shots ? Ns.as<double>() : nullptr, S, K, ns_tot, lds_extra};
+                        check_shots ? Ns.as<double>() : nullptr, S, K, ns_tot, extra};
   }
   // Jacobi stopping rule off^2 <= jtol2 * ||A||_F^2.  Measured on the C2 batch: the last sweep takes off^2
   // from > 1e-9 to < 1e-28 in one go, so no looser threshold saves a sweep without costing accuracy.
@@ -311,75 +313,87 @@ class Call {
 
 constexpr size_t kLdsLimit = 160 * 1024;  // LDS per CU on gfx950; one workgroup may use all of it
 
-// Dynamic LDS above the 64 KB default needs the kernel's attribute raised first.  (The n <= 3 kernels of qt_small.h
-// stream their dense operand from L2 -- dot_global -- and hold only per-trial scratch and the product-POVM tables there.)
-template <class K>
-int allow_big_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return 0;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)bytes);
-  if (e != hipSuccess) return fail(QT_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-  return 0;
-}
-
-// Launch KERNEL<n> (qt_small.h) for the handle's n = 1..3 over B_ trials.  LDS_ is the dynamic LDS size, an expression in
-// S_ = qt::Small<n>; ARGS is the parenthesised argument list.
-#define QT_LAUNCH_N(KERNEL, NQV, LDS_, B_, ARGS)                                                          \
-  do {                                                                                                    \
-    using S_ = qt::Small<NQV>;                                                                            \
-    const size_t lds_ = LDS_;                                                                             \
-    if (lds_ > kLdsLimit) return fail(QT_ERR_UNSUPPORTED, "POVM too large for the n<=3 kernels (%zu B of LDS)", lds_); \
-    if (int r_ = allow_big_lds(KERNEL<NQV>, lds_)) return r_;                                             \
-    const int grid_ = ((B_) + S_::TPB - 1) / S_::TPB;                                                     \
-    hipLaunchKernelGGL((KERNEL<NQV>), dim3(grid_), dim3(S_::NT), lds_, h->stream, QT_UNPACK ARGS);        \
-  } while (0)
-#define QT_LAUNCH_SMALL_LDS(KERNEL, LDS_, B_, ARGS)                                                         \
-  switch (h->nq) {                                                                                          \
-    case 1: QT_LAUNCH_N(KERNEL, 1, LDS_, B_, ARGS); break;                                                  \
-    case 2: QT_LAUNCH_N(KERNEL, 2, LDS_, B_, ARGS); break;                                                  \
-    case 3: QT_LAUNCH_N(KERNEL, 3, LDS_, B_, ARGS); break;                                                  \
-    default: return fail(QT_ERR_UNSUPPORTED, "estimators support n_qubits 1..3 in this release (got %d)", h->nq); \
+// Launch `kernel` on the handle's stream with `lds` bytes of dynamic LDS.  More than a CU has is refused; above the 64 KB
+// default the kernel's attribute is raised first.
+template <class... P, class... A>
+int launch(qt_handle_t* h, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A... args) {
+  if (lds > kLdsLimit) return fail(QT_ERR_UNSUPPORTED, "launch needs %zu B of LDS per workgroup (more than a CU has)", lds);
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(QT_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
   }
-#define QT_UNPACK(...) __VA_ARGS__
-// the estimators: per-trial scratch for an M_-row POVM (+ h->lds_extra) and the product-POVM tables
-#define QT_LAUNCH_SMALL(KERNEL, M_, B_, ARGS) \
-  QT_LAUNCH_SMALL_LDS(KERNEL, S_::lds_bytes(M_, h->prod.enabled ? h->prod.R1 : 0, h->lds_extra), B_, ARGS)
-// the Cholesky parametrisation, which reads no POVM: scratch only
-#define QT_LAUNCH_SMALL_NOPOVM(KERNEL, B_, ARGS) QT_LAUNCH_SMALL_LDS(KERNEL, S_::lds_bytes(0), B_, ARGS)
-
-// ---- n = 4, 5: workgroup-per-trial kernels (qt_large.h) ---------------------------------------------
-int compute_dense_pinv_fwd(qt_handle_t* h);
-// n >= 4: what the launch about to be made reads besides the factorised tables.  A plain tensor (qt_set_povm) has its
-// dense operands and left inverse already; a product POVM with unequal shots needs the dense left inverse for 'lin'.
-int prepare_large(qt_handle_t* h, bool needs_lin) {
-  if (h->prod.enabled && needs_lin && !h->prod.uniform && !h->pinv_ready) return compute_dense_pinv_fwd(h);
+  kernel<<<grid, block, lds, h->stream>>>(args...);
   return 0;
 }
-#define QT_LAUNCH_LARGE(KERNEL, B_, M_, R1_, ARGS) QT_LAUNCH_LARGE_X(KERNEL, B_, M_, R1_, 0, ARGS)
-// h->lds_extra (-> PovmView::extra) = offset in doubles, while ARGS (h->view()) is evaluated, of a block at the end of
-// the LDS allocation that holds a 32-bit copy of the trial's counts in R-order (Large::make_ctx): taken whenever it fits next to everything else and the registered
-// shots fit 32 bits.
-#define QT_LAUNCH_LARGE_X(KERNEL, B_, M_, R1_, XTRA_, ARGS)                                                 \
-  do {                                                                                                      \
-    if (h->nq == 4) {                                                                                       \
-      size_t lds_ = qt::Large<4>::lds_bytes(M_, R1_, XTRA_);                                                \
-      if (lds_ > kLdsLimit) return fail(QT_ERR_UNSUPPORTED, "POVM too large for LDS (%zu B)", lds_);         \
-      const bool cache_ = false; /* n = 4: measured slower with the cache (0.122 vs 0.101 ms per 1024 'mle') */ \
-      h->lds_extra = 0;                                                                                     \
-      if (int r_ = allow_big_lds(KERNEL<4>, lds_)) return r_;                                               \
-      hipLaunchKernelGGL((KERNEL<4>), dim3(B_), dim3(qt::Large<4>::NT), lds_, h->stream, QT_UNPACK ARGS);   \
-      h->lds_extra = 0;                                                                                     \
-    } else {                                                                                                \
-      size_t lds_ = qt::Large<5>::lds_bytes(M_, R1_, XTRA_);                                                \
-      if (lds_ > kLdsLimit) return fail(QT_ERR_UNSUPPORTED, "POVM too large for LDS (%zu B)", lds_);         \
-      const bool cache_ = h->prod.enabled && h->ns_max < 4294967296.0 && lds_ + 4 * (size_t)(M_) + 8 <= kLdsLimit; \
-      if (cache_) lds_ += 4 * (size_t)(M_) + 8;                                                             \
-      h->lds_extra = cache_ ? (int)((lds_ - 4 * (size_t)(M_) - 8) / 8) : 0;                                 \
-      if (int r_ = allow_big_lds(KERNEL<5>, lds_)) return r_;                                               \
-      hipLaunchKernelGGL((KERNEL<5>), dim3(B_), dim3(qt::Large<5>::NT), lds_, h->stream, QT_UNPACK ARGS);   \
-      h->lds_extra = 0;                                                                                     \
-    }                                                                                                       \
-  } while (0)
+
+// One launch of an estimator kernel (qt_small.h, qt_large.h): its geometry, its dynamic LDS, and the PovmView whose
+// `extra` field describes that LDS to the kernel.
+struct Plan {
+  dim3 grid, block;
+  size_t lds;
+  qt::PovmView pv;
+};
+template <class... P, class... A>
+int launch(qt_handle_t* h, void (*kernel)(P...), const Plan& p, A... args) {
+  return launch(h, kernel, p.grid, p.block, p.lds, args...);
+}
+
+// n = 1..3, B trials: Small<NQ>::TPB of them per workgroup, each with the scratch for an M-row POVM and `extra` doubles
+// behind it (PovmView::extra: k_mle_bfgs / k_mle_fused), and the tables of an R1-row one-qubit factor once per workgroup.
+// (These kernels stream their dense operand from L2 -- dot_global -- and hold no POVM in LDS.)
+template <int NQ>
+Plan small_plan(const qt_handle_t* h, int B, int M, int R1, int extra) {
+  using S = qt::Small<NQ>;
+  return {dim3((B + S::TPB - 1) / S::TPB), dim3(S::NT), S::lds_bytes(M, R1, extra), h->view(extra)};
+}
+
+// n = 4, 5, B trials, one per workgroup: LDS for an M-row POVM with an R1-row one-qubit factor and `max_iter` BFGS
+// iterations of two-loop scalars.  At n = 5 a 32-bit copy of the trial's counts in R-order (Large::make_ctx) goes behind
+// all that, PovmView::extra giving its offset in doubles, whenever it fits and the registered shots fit 32 bits.  (n = 4:
+// measured slower with the cache, 0.122 vs 0.101 ms per 1024 'mle'.)
+template <int NQ>
+Plan large_plan(const qt_handle_t* h, int B, int M, int R1, int max_iter) {
+  size_t lds = qt::Large<NQ>::lds_bytes(M, R1, max_iter);
+  int extra = 0;
+  const size_t cache = 4 * (size_t)M + 8;
+  if (NQ == 5 && h->prod.enabled && h->ns_max < 4294967296.0 && lds + cache <= kLdsLimit) {
+    extra = (int)(lds / 8);
+    lds += cache;
+  }
+  return {dim3(B), dim3(qt::Large<NQ>::NT), lds, h->view(extra)};
+}
+
+// An estimator over the handle's POVM.  `extra`: doubles per trial behind the scratch at n <= 3, BFGS iterations at n >= 4.
+template <int NQ>
+Plan povm_plan(const qt_handle_t* h, int B, int extra = 0) {
+  if constexpr (NQ <= 3) return small_plan<NQ>(h, B, h->M, h->prod.enabled ? h->prod.R1 : 0, extra);
+  else return large_plan<NQ>(h, B, h->M, h->prod.R1, extra);
+}
+
+// The Cholesky parametrisation, which reads no POVM: scratch only, and an empty PovmView.
+template <int NQ>
+Plan chol_plan(const qt_handle_t* h, int B) {
+  Plan p;
+  if constexpr (NQ <= 3) p = small_plan<NQ>(h, B, 0, 0, 0);
+  else p = large_plan<NQ>(h, B, 0, 1, 0);
+  p.pv = qt::PovmView{};
+  return p;
+}
+
+// f(std::integral_constant<int, n>()) for the handle's n: the kernels of qt_small.h (n <= 3) and qt_large.h (n = 4, 5)
+// are templates on it.
+template <class F>
+int by_nq(const qt_handle_t* h, F f) {
+  switch (h->nq) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    default: return fail(QT_ERR_UNSUPPORTED, "n_qubits %d", h->nq);
+  }
+}
 
 // In-place inverse of the n x n matrix in the left half of aug [n][2n]: one workgroup up to n = 127, the
 // chip-wide variant (qt_ops.h) beyond -- the 256 x 256 complex Gram matrix of 2-qubit process tomography takes
@@ -403,24 +417,311 @@ void launch_transpose(qt_handle_t* h, const double* in, int R, int C, double* ou
   hipLaunchKernelGGL(qt::k_transpose_tiled<W>, dim3((C + TS - 1) / TS, (R + TS - 1) / TS), dim3(256), 0, h->stream, in, R, C, out);
 }
 
-// out[cols][rows] = inv(A^T A) A^T of the complex A[rows][cols] (plain transposes, routines.py:69-71); all device
-// pointers, enqueued on the handle's stream; the pivot report lands in h->info (0 = regular).
-int enqueue_left_inverse_complex(qt_handle_t* h, const double* dA, int rows, int cols, double* dout) {
-  DevBuf& aug = h->proc_aug;
-  HIPCHK(aug.ensure((size_t)cols * 2 * cols * 2 * sizeof(double)));
+// out[cols][rows] = inv(A^T A) A^T of A[rows][cols], real (W = 1) or complex (W = 2; plain transposes, routines.py:69-71):
+// Gram GEMM, pivoted Gauss-Jordan in h->aug, GEMM, enqueued on the handle's stream; the pivot report lands in h->info
+// (0 = regular).  AT, when given, is A^T [cols][rows], read by the second GEMM in place of A.
+template <int W>
+int enqueue_left_inverse(qt_handle_t* h, const double* A, int rows, int cols, double* out, const double* AT = nullptr) {
+  constexpr int CPLX = W - 1;
+  HIPCHK(h->aug.ensure((size_t)cols * 2 * cols * W * sizeof(double)));
   HIPCHK(h->info.ensure(sizeof(int)));
-  double* g = aug.as<double>();
-  dim3 gg((cols + 15) / 16, (cols + 15) / 16), gp((rows + 15) / 16, (cols + 15) / 16);
-  hipLaunchKernelGGL(qt::k_gemm<1>, gg, dim3(64), 0, h->stream, cols, cols, rows, dA, cols, 1, dA, cols, 0, g, 2 * cols);
-  launch_gauss_jordan<1>(h, cols, g, h->info.as<int>());
-  hipLaunchKernelGGL(qt::k_gemm<1>, gp, dim3(64), 0, h->stream, cols, rows, cols, g + (size_t)cols * 2, 2 * cols, 0, dA, cols,
-                     1, dout, rows);
+  double* g = h->aug.as<double>();
+  hipLaunchKernelGGL(qt::k_gemm<CPLX>, dim3((cols + 15) / 16, (cols + 15) / 16), dim3(64), 0, h->stream, cols, cols, rows, A,
+                     cols, 1, A, cols, 0, g, 2 * cols);
+  launch_gauss_jordan<CPLX>(h, cols, g, h->info.as<int>());
+  hipLaunchKernelGGL(qt::k_gemm<CPLX>, dim3((rows + 15) / 16, (cols + 15) / 16), dim3(64), 0, h->stream, cols, rows, cols,
+                     g + (size_t)cols * W, 2 * cols, 0, AT ? AT : A, AT ? rows : cols, AT ? 0 : 1, out, rows);
   return 0;
 }
 
 int need_povm(qt_handle_t* h) {
   if (!h->povm_set) return fail(QT_ERR_STATE, "qt_set_povm has not been called on this handle");
   return 0;
+}
+
+// Row digits for k_povm_kron: row = s K + k with s = sum_q s_q S1^(n-1-q), k likewise; byte q = s_q K1 + k_q.
+int ensure_kron_digits(qt_handle_t* h, int S1, int K1) {
+  if (h->kron_S1 == S1 && h->kron_K1 == K1 && h->kron_dig.p) return 0;
+  const int n = h->nq;
+  long long S = 1, K = 1;
+  for (int q = 0; q < n; ++q) {
+    S *= S1;
+    K *= K1;
+  }
+  std::vector<unsigned long long> dig((size_t)(S * K));
+  for (long long s = 0; s < S; ++s)
+    for (long long k = 0; k < K; ++k) {
+      unsigned long long pack = 0;
+      long long sr = s, kr = k;
+      for (int q = n - 1; q >= 0; --q) {
+        pack |= (unsigned long long)((sr % S1) * K1 + (kr % K1)) << (8 * q);
+        sr /= S1;
+        kr /= K1;
+      }
+      dig[(size_t)(s * K + k)] = pack;
+    }
+  h->kron_S1 = h->kron_K1 = 0;
+  HIPCHK(h->kron_dig.ensure(dig.size() * sizeof(unsigned long long)));
+  HIPCHK(hipMemcpyAsync(h->kron_dig.p, dig.data(), dig.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // `dig` goes out of scope
+  h->kron_S1 = S1;
+  h->kron_K1 = K1;
+  return 0;
+}
+
+int launch_povm_kron(qt_handle_t* h, const double* dtable, int S1, int K1, double* dout) {
+  if (S1 * K1 > 255) return fail(QT_ERR_UNSUPPORTED, "one-qubit table with %d rows (> 255)", S1 * K1);
+  if (int r = ensure_kron_digits(h, S1, K1)) return r;
+  size_t total = (size_t)h->D;
+  for (int q = 0; q < h->nq; ++q) total *= (size_t)S1 * K1;
+  if ((total >> (2 * h->nq)) > ((size_t)1 << 31)) return fail(QT_ERR_UNSUPPORTED, "POVM tensor too large");
+  // >> 256 workgroups, each lane a 16-byte store per pass
+  hipLaunchKernelGGL(qt::k_povm_kron, dim3(grid_for(total / 2, 256, 4096)), dim3(256), 0, h->stream, h->nq, dtable, S1 * K1,
+                     h->kron_dig.as<unsigned long long>(), total, dout);
+  return 0;
+}
+
+// Dense operands A ([M][D]; the Kronecker power of the table for a product POVM), A^T, A', A'^T -- built when first
+// needed: Born kernel / dense estimators at n <= 3, process set-up, the dense left inverse.
+int ensure_dense(qt_handle_t* h) {
+  if (h->dense_ready) return 0;
+  const size_t bytes = (size_t)h->M * h->D * sizeof(double);
+  HIPCHK(h->A.ensure(bytes));
+  HIPCHK(h->AT.ensure(bytes));
+  HIPCHK(h->Aw.ensure(bytes));
+  HIPCHK(h->AwT.ensure(bytes));
+  if (!h->a_loaded) {
+    if (!h->pr_T.p || h->kron_S1 * h->kron_K1 == 0) return fail(QT_ERR_STATE, "no POVM tensor to build the dense operands from");
+    if (int r = launch_povm_kron(h, h->pr_T.as<double>(), h->kron_S1, h->kron_K1, h->A.as<double>())) return r;
+    h->a_loaded = true;
+  }
+  hipLaunchKernelGGL(qt::k_povm_setup, dim3((h->D + 63) / 64, (h->M + 63) / 64), dim3(256), 0, h->stream, h->A.as<double>(),
+                     h->Ns.as<double>(), h->ns_tot, h->K, h->M, h->D, h->AT.as<double>(), h->Aw.as<double>(),
+                     h->AwT.as<double>());
+  HIPCHK(hipGetLastError());
+  h->dense_ready = true;
+  return 0;
+}
+
+// Dense left inverse inv(A'^T A') A'^T of the cached weighted POVM.
+int compute_dense_pinv(qt_handle_t* h) {
+  if (int r = ensure_dense(h)) return r;
+  const int D = h->D, M = h->M;
+  const size_t bytes = (size_t)M * D * sizeof(double);
+  HIPCHK(h->Pinv.ensure(bytes));
+  HIPCHK(h->PinvT.ensure(bytes));
+  if (int r = enqueue_left_inverse<1>(h, h->Aw.as<double>(), M, D, h->Pinv.as<double>(), h->AwT.as<double>())) return r;
+  launch_transpose<1>(h, h->Pinv.as<double>(), D, M, h->PinvT.as<double>());
+  int info = 0;
+  HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (info != 0) return fail(QT_ERR_SINGULAR, "A^T A is singular (no pivot in column %d): POVM not informationally complete", info - 1);
+  h->pinv_ready = true;
+  return 0;
+}
+
+// n >= 4: what the launch about to be made reads besides the factorised tables.  A plain tensor (qt_set_povm) has its
+// dense operands and left inverse already; a product POVM with unequal shots needs the dense left inverse for 'lin'.
+int prepare_large(qt_handle_t* h, bool needs_lin) {
+  if (h->prod.enabled && needs_lin && !h->prod.uniform && !h->pinv_ready) return compute_dense_pinv(h);
+  return 0;
+}
+
+// Start of qt_set_povm / qt_set_povm_product: forget the previous POVM, record the shape.
+int begin_povm(qt_handle_t* h, int S, int K) {
+  const size_t M = (size_t)S * K;
+  if (M < (size_t)h->D) return fail(QT_ERR_SINGULAR, "POVM has %zu rows < D = %d: not informationally complete", M, h->D);
+  h->povm_set = false;
+  h->proc_set = false;
+  h->dense_ready = h->a_loaded = h->pinv_ready = false;
+  h->prod = qt::ProductView{};
+  h->S = S;
+  h->K = K;
+  h->M = (int)M;
+  HIPCHK(h->Ns.ensure(S * sizeof(double)));
+  HIPCHK(h->info.ensure(sizeof(int)));
+  return 0;
+}
+
+int check_pvals(int period, int K, const int64_t* n, const double* pvals) {
+  for (int s = 0; s < period; ++s) {
+    if (n[s] < 0) return fail(QT_ERR_ARG, "n < 0 in row %d", s);
+    // RandomState.multinomial's own checks (mtrand.pyx): every pval in [0, 1], and the leading K - 1 may not exceed 1
+    double head = 0.0, comp = 0.0;  // compensated sum, as NumPy's check has it
+    for (int j = 0; j < K; ++j) {
+      const double p = pvals[(size_t)s * K + j];
+      if (!(p >= 0.0 && p <= 1.0)) return fail(QT_ERR_ARG, "pvals < 0, pvals > 1 or pvals contains NaNs");
+      if (j == 0 && K > 1) head = p;
+      if (j > 0 && j < K - 1) {
+        const double y = p - comp, t = head + y;
+        comp = (t - head) - y;
+        head = t;
+      }
+    }
+    if (head > 1.0 + 1e-12) return fail(QT_ERR_ARG, "sum(pvals[:-1]) > 1.0");
+  }
+  return 0;
+}
+
+// a6 + a7 (+ a16 when `dist` is asked for): one body behind qt_lin_batch and qt_lin_dist_batch
+int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centre, double* rho,
+                   double* dist, double* bloch_out, int32_t* status, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = need_povm(h)) return r;
+  if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad lin_batch arguments");
+  if (B == 0) return 0;
+  const int64_t* dc;
+  const double* dcen;
+  double *drho, *dbl, *ddist;
+  int32_t* dst;
+  const size_t nel = (size_t)B * h->D;
+  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
+  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
+  if (int r = c.out(rho, nel * 2, &drho)) return r;
+  if (int r = c.out(bloch_out, nel, &dbl)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
+  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
+  const qt::EstOut eo{drho, dcen, ddist};
+  if (h->nq >= 4)
+    if (int r = prepare_large(h, true)) return r;
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        const Plan p = povm_plan<NQ>(h, B);
+        if constexpr (NQ <= 3) return launch(h, qt::k_lin_batch<NQ>, p, p.pv, dc, B, physical, eo, dbl, dst);
+        else return launch(h, qt::k_lin_large<NQ>, p, p.pv, dc, B, physical, eo, dbl, dst);
+      }))
+    return r;
+  return c.done(status, B);
+}
+
+// The per-trial arrays of an MLE batch; at(b0): those of the trials from b0 on (a null output stays null).
+struct MleArrays {
+  const int64_t* counts;
+  qt::EstOut eo;
+  int32_t *nit, *nfev;
+  double* fun;
+  int32_t* status;
+  double *x, *g, *f;  // the hand-off from k_mle_*start to k_mle_*bfgs
+  int32_t* act;
+  int M, D;
+  MleArrays at(int b0) const {
+    auto off = [b0](auto* p, size_t per) { return p ? p + (size_t)b0 * per : p; };
+    return {off(counts, M), {off(eo.rho, 2 * D), eo.centre, off(eo.dist, 1)}, off(nit, 1), off(nfev, 1), off(fun, 1),
+            off(status, 1), off(x, D), off(g, D), off(f, 1), off(act, 1), M, D};
+  }
+};
+
+// The split MLE pair: k_mle_start / k_mle_bfgs (qt_small.h) at n <= 3, k_mle_large_start / k_mle_large_bfgs (qt_large.h)
+// at n = 4, 5.
+template <int NQ>
+auto mle_split_kernels() {
+  if constexpr (NQ <= 3) return std::make_pair(qt::k_mle_start<NQ>, qt::k_mle_bfgs<NQ>);
+  else return std::make_pair(qt::k_mle_large_start<NQ>, qt::k_mle_large_bfgs<NQ>);
+}
+
+// a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch and qt_mle_dist_batch
+int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, const double* centre,
+                   double* rho, double* dist, int32_t* nit, int32_t* nfev, double* fun, int32_t* status, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = need_povm(h)) return r;
+  if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad mle_batch arguments");
+  if (init != QT_INIT_LIN && init != QT_INIT_MIXED) return fail(QT_ERR_ARG, "init must be QT_INIT_LIN or QT_INIT_MIXED");
+  if (max_iter < 0) return fail(QT_ERR_ARG, "max_iter < 0");
+  if (B == 0) return 0;
+  const int64_t* dc;
+  const double* dcen;
+  double *drho, *dfun, *ddist;
+  int32_t *dnit, *dnfev, *dst;
+  const size_t nel = (size_t)B * h->D;
+  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
+  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
+  if (int r = c.out(rho, nel * 2, &drho)) return r;
+  if (int r = c.out(nit, (size_t)B, &dnit)) return r;
+  if (int r = c.out(nfev, (size_t)B, &dnfev)) return r;
+  if (int r = c.out(fun, (size_t)B, &dfun)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
+  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
+  const qt::EstOut eo{drho, dcen, ddist};
+  if (h->nq >= 4) {
+    if (int r = prepare_large(h, init == QT_INIT_LIN)) return r;
+    if (max_iter > 4096) return fail(QT_ERR_UNSUPPORTED, "max_iter > 4096 is not supported for n_qubits >= 4");
+  }
+  // n = 3 keeps rho_i / alpha_i of every BFGS iteration in the trial's LDS (16 bytes per iteration and trial):
+  // the one-launch kernel (which also keeps 24 pairs there) up to 256 iterations, the split pair up to 2000
+  if (h->nq == 3 && max_iter > 2000)
+    return fail(QT_ERR_UNSUPPORTED, "max_iter > 2000 is not supported for n_qubits = 3 (LDS holds the two-loop scalars)");
+  const int mi = max_iter > 0 ? max_iter : 1;
+  return by_nq(h, [&](auto nq) -> int {
+    constexpr int NQ = decltype(nq)::value;
+    if constexpr (NQ <= 3) {
+      // up to one resident wave per SIMD (1024 trial-waves) the single fused launch wins; beyond that the
+      // 256-VGPR BFGS loop would cap occupancy for every trial, so the split pair is used
+      constexpr int TPW = qt::Small<NQ>::TPW;
+      if ((B + TPW - 1) / TPW <= h->fused_max_waves && !(NQ == 3 && max_iter > 256)) {
+        int extra = 0;
+        if (NQ == 3) {  // two-loop BFGS: line-search state, rho_i, alpha_i and the first pairs in LDS, later pairs in global
+          extra = qt::LineSearch::SLOTS + 2 * mi + qt::kFusedLdsPairs * 2 * h->D;
+          const int over = mi > qt::kFusedLdsPairs ? mi : 1;  // (indexed by pair number: rows below kFusedLdsPairs stay unused)
+          HIPCHK(h->hess.ensure((size_t)B * over * 2 * h->D * sizeof(double)));
+        }
+        const Plan p = povm_plan<NQ>(h, B, extra);
+        if (int r = launch(h, init == QT_INIT_LIN ? qt::k_mle_fused<NQ> : qt::k_mle_fused_mixed<NQ>, p, p.pv, dc, B, max_iter,
+                           tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>()))
+          return r;
+        return c.done(status, B);
+      }
+    }
+    HIPCHK(h->ws_x.ensure(nel * sizeof(double)));
+    HIPCHK(h->ws_g.ensure(nel * sizeof(double)));
+    HIPCHK(h->ws_f.ensure((size_t)B * sizeof(double)));
+    HIPCHK(h->ws_act.ensure((size_t)B * sizeof(int32_t)));
+    // BFGS history of the trials that iterate: 2 D doubles per iteration and trial (two-loop recursion), in chunks of
+    // <= 4 GiB.  (n = 1, 2 keep the 4 / 16-entry Hessian rows in registers: no workspace.)
+    int chunk = B;
+    if (NQ >= 3) {
+      const size_t per_trial = (size_t)mi * 2 * h->D * sizeof(double);
+      chunk = (int)(((size_t)4 << 30) / per_trial);
+      if (chunk < 1) chunk = 1;
+      if (chunk > B) chunk = B;
+      HIPCHK(h->hess.ensure((size_t)chunk * per_trial));
+    }
+    const MleArrays all{dc, eo, dnit, dnfev, dfun, dst, h->ws_x.as<double>(), h->ws_g.as<double>(), h->ws_f.as<double>(),
+                        h->ws_act.as<int32_t>(), h->M, h->D};
+    const auto [k_start, k_bfgs] = mle_split_kernels<NQ>();
+    // start point + first evaluation of every trial; then the BFGS loop of those that iterate, chunk by chunk, with
+    // rho_i, alpha_i (and at n = 3 the parked line-search state) in LDS
+    const Plan ps = povm_plan<NQ>(h, B);
+    if (int r = launch(h, k_start, ps, ps.pv, dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, all.x, all.g, all.f, all.act))
+      return r;
+    const int extra = NQ >= 4 ? max_iter : (NQ == 3 ? qt::LineSearch::SLOTS + 2 * mi : 0);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      const int nb = B - b0 < chunk ? B - b0 : chunk;
+      const MleArrays a = all.at(b0);
+      const Plan p = povm_plan<NQ>(h, nb, extra);
+      if (int r = launch(h, k_bfgs, p, p.pv, a.counts, nb, max_iter, tol, a.eo, a.nit, a.nfev, a.fun, a.status, a.x, a.g, a.f,
+                         a.act, h->hess.as<double>()))
+        return r;
+    }
+    return c.done(status, B);
+  });
+}
+
+// The n = 3 projection (qt_process64.h, k_cptp_project64) of B Choi matrices, one workgroup each, with Dykstra's p, q,
+// y, x and the clip's input in h->proc_ws -- except in mode 1 (TP only), which takes no workspace.
+int project64(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
+              int32_t* status) {
+  if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
+  return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, in, B, mode, n_iter, tol, out,
+                iters, status, h->proc_ws.as<double>());
+}
+
+// The n = 2 projection (qt_process_wave16.h, k_cptp_wave16): one wavefront per Choi matrix.
+int project16(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
+              int32_t* status) {
+  return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status);
 }
 
 }  // namespace
@@ -479,10 +780,10 @@ void qt_destroy(qt_handle_t* h) {
   if (!h) return;
   DeviceScope scope(h->device);
   (void)hipStreamSynchronize(h->stream);
-  for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_aug})
+  for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd})
     b->release();
-  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->aug, &h->info, &h->kron_dig, &h->proc_aug,
-                    &h->proc_ws, &h->gram, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
+  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws,
+                    &h->gram, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
   h->proc.release();
@@ -564,48 +865,6 @@ int qt_pauli_basis(qt_handle_t* h, double* out, int flags) {
   return c.done();
 }
 
-// Row digits for k_povm_kron: row = s K + k with s = sum_q s_q S1^(n-1-q), k likewise; byte q = s_q K1 + k_q.
-static int ensure_kron_digits(qt_handle_t* h, int S1, int K1) {
-  if (h->kron_S1 == S1 && h->kron_K1 == K1 && h->kron_dig.p) return 0;
-  const int n = h->nq;
-  long long S = 1, K = 1;
-  for (int q = 0; q < n; ++q) {
-    S *= S1;
-    K *= K1;
-  }
-  std::vector<unsigned long long> dig((size_t)(S * K));
-  for (long long s = 0; s < S; ++s)
-    for (long long k = 0; k < K; ++k) {
-      unsigned long long pack = 0;
-      long long sr = s, kr = k;
-      for (int q = n - 1; q >= 0; --q) {
-        pack |= (unsigned long long)((sr % S1) * K1 + (kr % K1)) << (8 * q);
-        sr /= S1;
-        kr /= K1;
-      }
-      dig[(size_t)(s * K + k)] = pack;
-    }
-  h->kron_S1 = h->kron_K1 = 0;
-  HIPCHK(h->kron_dig.ensure(dig.size() * sizeof(unsigned long long)));
-  HIPCHK(hipMemcpyAsync(h->kron_dig.p, dig.data(), dig.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));  // `dig` goes out of scope
-  h->kron_S1 = S1;
-  h->kron_K1 = K1;
-  return 0;
-}
-
-static int launch_povm_kron(qt_handle_t* h, const double* dtable, int S1, int K1, double* dout) {
-  if (S1 * K1 > 255) return fail(QT_ERR_UNSUPPORTED, "one-qubit table with %d rows (> 255)", S1 * K1);
-  if (int r = ensure_kron_digits(h, S1, K1)) return r;
-  size_t total = (size_t)h->D;
-  for (int q = 0; q < h->nq; ++q) total *= (size_t)S1 * K1;
-  if ((total >> (2 * h->nq)) > ((size_t)1 << 31)) return fail(QT_ERR_UNSUPPORTED, "POVM tensor too large");
-  // >> 256 workgroups, each lane a 16-byte store per pass
-  hipLaunchKernelGGL(qt::k_povm_kron, dim3(grid_for(total / 2, 256, 4096)), dim3(256), 0, h->stream, h->nq, dtable, S1 * K1,
-                     h->kron_dig.as<unsigned long long>(), total, dout);
-  return 0;
-}
-
 int qt_povm_kron(qt_handle_t* h, const double* povm1, int S1, int K1, double* out, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
@@ -622,75 +881,6 @@ int qt_povm_kron(qt_handle_t* h, const double* povm1, int S1, int K1, double* ou
   if (int r = c.out(out, n, &dout)) return r;
   if (int r = launch_povm_kron(h, din, S1, K1, dout)) return r;
   return c.done();
-}
-
-// Dense operands A ([M][D]; the Kronecker power of the table for a product POVM), A^T, A', A'^T -- built when first
-// needed: Born kernel / dense estimators at n <= 3, process set-up, the dense left inverse.
-static int ensure_dense(qt_handle_t* h) {
-  if (h->dense_ready) return 0;
-  const size_t bytes = (size_t)h->M * h->D * sizeof(double);
-  HIPCHK(h->A.ensure(bytes));
-  HIPCHK(h->AT.ensure(bytes));
-  HIPCHK(h->Aw.ensure(bytes));
-  HIPCHK(h->AwT.ensure(bytes));
-  if (!h->a_loaded) {
-    if (!h->pr_T.p || h->kron_S1 * h->kron_K1 == 0) return fail(QT_ERR_STATE, "no POVM tensor to build the dense operands from");
-    if (int r = launch_povm_kron(h, h->pr_T.as<double>(), h->kron_S1, h->kron_K1, h->A.as<double>())) return r;
-    h->a_loaded = true;
-  }
-  hipLaunchKernelGGL(qt::k_povm_setup, dim3((h->D + 63) / 64, (h->M + 63) / 64), dim3(256), 0, h->stream, h->A.as<double>(),
-                     h->Ns.as<double>(), h->ns_tot, h->K, h->M, h->D, h->AT.as<double>(), h->Aw.as<double>(),
-                     h->AwT.as<double>());
-  HIPCHK(hipGetLastError());
-  h->dense_ready = true;
-  return 0;
-}
-
-// Dense left inverse inv(A'^T A') A'^T of the cached weighted POVM (Gram GEMM, pivoted Gauss-Jordan, GEMM).
-static int compute_dense_pinv(qt_handle_t* h) {
-  if (int r = ensure_dense(h)) return r;
-  const int D = h->D, M = h->M;
-  const size_t bytes = (size_t)M * D * sizeof(double);
-  HIPCHK(h->Pinv.ensure(bytes));
-  HIPCHK(h->PinvT.ensure(bytes));
-  HIPCHK(h->aug.ensure((size_t)D * 2 * D * sizeof(double)));
-  double *dAw = h->Aw.as<double>(), *dAwT = h->AwT.as<double>();
-  double *dP = h->Pinv.as<double>(), *dPT = h->PinvT.as<double>(), *aug = h->aug.as<double>();
-  dim3 gg((D + 15) / 16, (D + 15) / 16);
-  hipLaunchKernelGGL(qt::k_gemm<0>, gg, dim3(64), 0, h->stream, D, D, M, dAw, D, 1, dAw, D, 0, aug, 2 * D);
-  launch_gauss_jordan<0>(h, D, aug, h->info.as<int>());
-  dim3 gp((M + 15) / 16, (D + 15) / 16);
-  hipLaunchKernelGGL(qt::k_gemm<0>, gp, dim3(64), 0, h->stream, D, M, D, aug + D, 2 * D, 0, dAwT, M, 0, dP, M);
-  launch_transpose<1>(h, dP, D, M, dPT);
-  int info = 0;
-  HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (info != 0) return fail(QT_ERR_SINGULAR, "A^T A is singular (no pivot in column %d): POVM not informationally complete", info - 1);
-  h->pinv_ready = true;
-  return 0;
-}
-
-}  // extern "C"
-namespace {
-int compute_dense_pinv_fwd(qt_handle_t* h) { return compute_dense_pinv(h); }
-}  // namespace
-extern "C" {
-
-// Start of qt_set_povm / qt_set_povm_product: forget the previous POVM, record the shape.
-static int begin_povm(qt_handle_t* h, int S, int K) {
-  const size_t M = (size_t)S * K;
-  if (M < (size_t)h->D) return fail(QT_ERR_SINGULAR, "POVM has %zu rows < D = %d: not informationally complete", M, h->D);
-  h->povm_set = false;
-  h->proc_set = false;
-  h->dense_ready = h->a_loaded = h->pinv_ready = false;
-  h->prod = qt::ProductView{};
-  h->S = S;
-  h->K = K;
-  h->M = (int)M;
-  HIPCHK(h->Ns.ensure(S * sizeof(double)));
-  HIPCHK(h->info.ensure(sizeof(int)));
-  return 0;
 }
 
 int qt_set_povm(qt_handle_t* h, const double* A, int S, int K, const double* Ns, int flags) {
@@ -751,15 +941,8 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
   // pinv of the one-qubit table, on the device: inv(T^T T) T^T  ([4][R1]) and its transpose
   HIPCHK(h->pr_P1.ensure((size_t)4 * R1 * sizeof(double)));
   HIPCHK(h->pr_P1T.ensure((size_t)4 * R1 * sizeof(double)));
-  HIPCHK(h->pr_aug.ensure((size_t)4 * 8 * sizeof(double)));
-  {
-    double *T = h->pr_T.as<double>(), *g = h->pr_aug.as<double>(), *P1 = h->pr_P1.as<double>();
-    hipLaunchKernelGGL(qt::k_gemm<0>, dim3(1, 1), dim3(64), 0, h->stream, 4, 4, R1, T, 4, 1, T, 4, 0, g, 8);
-    hipLaunchKernelGGL(qt::k_gauss_jordan<0>, dim3(1), dim3(1024), 0, h->stream, 4, g, h->info.as<int>());
-    hipLaunchKernelGGL(qt::k_gemm<0>, dim3((R1 + 15) / 16, 1), dim3(64), 0, h->stream, 4, R1, 4, g + 4, 8, 0, T, 4, 1, P1,
-                       R1);
-    launch_transpose<1>(h, P1, 4, R1, h->pr_P1T.as<double>());
-  }
+  if (int r = enqueue_left_inverse<1>(h, h->pr_T.as<double>(), R1, 4, h->pr_P1.as<double>())) return r;
+  launch_transpose<1>(h, h->pr_P1.as<double>(), 4, R1, h->pr_P1T.as<double>());
   // host-side index bookkeeping: R-order row map, shot weights, stage tables
   std::vector<int> rmap((size_t)M), fwd, bwd;
   std::vector<double> wrow((size_t)M);
@@ -851,7 +1034,8 @@ int qt_born_probs(qt_handle_t* h, const double* bloch, int B, double* p, int fla
   if (int r = c.in(bloch, (size_t)B * h->D, &din)) return r;
   if (int r = c.out(p, (size_t)B * h->M, &dout)) return r;
   if (h->nq >= 4 && h->prod.enabled) {  // factorised contraction, one workgroup per state
-    QT_LAUNCH_LARGE(qt::k_born_large, B, h->M, h->prod.R1, (h->view(), din, B, dout));
+    const Plan pl = h->nq == 4 ? povm_plan<4>(h, B) : povm_plan<5>(h, B);
+    if (int r = launch(h, h->nq == 4 ? qt::k_born_large<4> : qt::k_born_large<5>, pl, pl.pv, din, B, dout)) return r;
     return c.done();
   }
   if (int r = ensure_dense(h)) return r;
@@ -863,35 +1047,14 @@ int qt_born_probs(qt_handle_t* h, const double* bloch, int B, double* p, int fla
     // batched: the matrix-core kernel, one persistent 16-wave workgroup per CU (A^T lives in its LDS)
     int grid = (B + 16 * 16 - 1) / (16 * 16);
     if (grid > 256) grid = 256;
-    switch (h->D) {
-      case 4:
-        if (int r = allow_big_lds(qt::k_born_mfma<4>, at_bytes)) return r;
-        hipLaunchKernelGGL(qt::k_born_mfma<4>, dim3(grid), dim3(1024), at_bytes, h->stream, h->AT.as<double>(), h->M, Mp, h->d,
-                           din, B, dout);
-        break;
-      case 16:
-        if (int r = allow_big_lds(qt::k_born_mfma<16>, at_bytes)) return r;
-        hipLaunchKernelGGL(qt::k_born_mfma<16>, dim3(grid), dim3(1024), at_bytes, h->stream, h->AT.as<double>(), h->M, Mp, h->d,
-                           din, B, dout);
-        break;
-      default:
-        if (int r = allow_big_lds(qt::k_born_mfma<64>, at_bytes)) return r;
-        hipLaunchKernelGGL(qt::k_born_mfma<64>, dim3(grid), dim3(1024), at_bytes, h->stream, h->AT.as<double>(), h->M, Mp, h->d,
-                           din, B, dout);
-        break;
-    }
-  } else if (h->D <= 256) {
-    constexpr int TB = 8;
-    int gy = (B + TB - 1) / TB;
-    if (gy > 2048) gy = 2048;
-    hipLaunchKernelGGL(qt::k_born<TB>, dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream, h->AT.as<double>(),
-                       h->M, h->D, h->d, din, B, dout);
+    const auto kern = h->D == 4 ? qt::k_born_mfma<4> : (h->D == 16 ? qt::k_born_mfma<16> : qt::k_born_mfma<64>);
+    if (int r = launch(h, kern, dim3(grid), dim3(1024), at_bytes, h->AT.as<double>(), h->M, Mp, h->d, din, B, dout)) return r;
   } else {
-    constexpr int TB = 4;
+    const int TB = h->D <= 256 ? 8 : 4;  // states per workgroup
     int gy = (B + TB - 1) / TB;
     if (gy > 2048) gy = 2048;
-    hipLaunchKernelGGL(qt::k_born<TB>, dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream, h->AT.as<double>(),
-                       h->M, h->D, h->d, din, B, dout);
+    hipLaunchKernelGGL((TB == 8 ? qt::k_born<8> : qt::k_born<4>), dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream,
+                       h->AT.as<double>(), h->M, h->D, h->d, din, B, dout);
   }
   return c.done();
 }
@@ -924,35 +1087,6 @@ int qt_mat_from_bloch(qt_handle_t* h, const double* bloch, int B, double* mat, i
   return c.done();
 }
 
-// a6 + a7 (+ a16 when `dist` is asked for): one body behind qt_lin_batch and qt_lin_dist_batch
-static int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centre, double* rho,
-                          double* dist, double* bloch_out, int32_t* status, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (int r = need_povm(h)) return r;
-  if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad lin_batch arguments");
-  if (B == 0) return 0;
-  const int64_t* dc;
-  const double* dcen;
-  double *drho, *dbl, *ddist;
-  int32_t* dst;
-  const size_t nel = (size_t)B * h->D;
-  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
-  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
-  if (int r = c.out(rho, nel * 2, &drho)) return r;
-  if (int r = c.out(bloch_out, nel, &dbl)) return r;
-  if (int r = c.out(status, (size_t)B, &dst)) return r;
-  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
-  const qt::EstOut eo{drho, dcen, ddist};
-  if (h->nq >= 4) {
-    if (int r = prepare_large(h, true)) return r;
-    QT_LAUNCH_LARGE(qt::k_lin_large, B, h->M, h->prod.R1, (h->view(), dc, B, physical, eo, dbl, dst));
-  } else {
-    QT_LAUNCH_SMALL(qt::k_lin_batch, h->M, B, (h->view(), dc, B, physical, eo, dbl, dst));
-  }
-  return c.done(status, B);
-}
-
 int qt_lin_batch(qt_handle_t* h, const int64_t* counts, int B, int physical, double* rho, double* bloch_out,
                  int32_t* status, int flags) {
   if (B > 0 && !rho) return fail(QT_ERR_ARG, "bad lin_batch arguments");
@@ -977,12 +1111,13 @@ int qt_chol_param(qt_handle_t* h, const double* rho, int B, double* x, int32_t* 
   if (int r = c.in(rho, nel * 2, &din)) return r;
   if (int r = c.out(x, nel, &dx)) return r;
   if (int r = c.out(status, (size_t)B, &dst)) return r;
-  qt::PovmView pv{};
-  if (h->nq >= 4) {
-    QT_LAUNCH_LARGE(qt::k_chol_param_large, B, 0, 1, (pv, din, B, dx, dst));
-  } else {
-    QT_LAUNCH_SMALL_NOPOVM(qt::k_chol_param, B, (pv, din, B, dx, dst));
-  }
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        const Plan p = chol_plan<NQ>(h, B);
+        if constexpr (NQ <= 3) return launch(h, qt::k_chol_param<NQ>, p, p.pv, din, B, dx, dst);
+        else return launch(h, qt::k_chol_param_large<NQ>, p, p.pv, din, B, dx, dst);
+      }))
+    return r;
   return c.done(status, B);
 }
 
@@ -996,12 +1131,13 @@ int qt_chol_unparam(qt_handle_t* h, const double* x, int B, double* LLh, int fla
   const size_t nel = (size_t)B * h->D;
   if (int r = c.in(x, nel, &din)) return r;
   if (int r = c.out(LLh, nel * 2, &dout)) return r;
-  qt::PovmView pv{};
-  if (h->nq >= 4) {
-    QT_LAUNCH_LARGE(qt::k_chol_unparam_large, B, 0, 1, (pv, din, B, dout));
-  } else {
-    QT_LAUNCH_SMALL_NOPOVM(qt::k_chol_unparam, B, (pv, din, B, dout));
-  }
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        const Plan p = chol_plan<NQ>(h, B);
+        if constexpr (NQ <= 3) return launch(h, qt::k_chol_unparam<NQ>, p, p.pv, din, B, dout);
+        else return launch(h, qt::k_chol_unparam_large<NQ>, p, p.pv, din, B, dout);
+      }))
+    return r;
   return c.done();
 }
 
@@ -1019,11 +1155,13 @@ int qt_nll_batch(qt_handle_t* h, const double* x, const int64_t* counts, int B, 
   if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
   if (int r = c.out(f, (size_t)B, &df)) return r;
   if (int r = c.out(grad, nel, &dg)) return r;
-  if (h->nq >= 4) {
-    QT_LAUNCH_LARGE(qt::k_nll_large, B, h->M, h->prod.R1, (h->view(), dx, dc, B, df, dg));
-  } else {
-    QT_LAUNCH_SMALL(qt::k_nll_batch, h->M, B, (h->view(), dx, dc, B, df, dg));
-  }
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        const Plan p = povm_plan<NQ>(h, B);
+        if constexpr (NQ <= 3) return launch(h, qt::k_nll_batch<NQ>, p, p.pv, dx, dc, B, df, dg);
+        else return launch(h, qt::k_nll_large<NQ>, p, p.pv, dx, dc, B, df, dg);
+      }))
+    return r;
   return c.done();
 }
 
@@ -1046,122 +1184,14 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
   if (int r = c.in(uniforms, (size_t)C * T, &du)) return r;
   if (int r = c.out(chain, nel, &dch)) return r;
   if (int r = c.out(accepted, (size_t)C * T, &dacc)) return r;
-  if (h->nq >= 4) {
-    QT_LAUNCH_LARGE(qt::k_mhmc_state_large, C, h->M, h->prod.R1, (h->view(), dc, C, dx, dd, du, T, step, dch, dacc));
-  } else {
-    QT_LAUNCH_SMALL(qt::k_mhmc_state, h->M, C, (h->view(), dc, C, dx, dd, du, T, step, dch, dacc));
-  }
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        const Plan p = povm_plan<NQ>(h, C);
+        if constexpr (NQ <= 3) return launch(h, qt::k_mhmc_state<NQ>, p, p.pv, dc, C, dx, dd, du, T, step, dch, dacc);
+        else return launch(h, qt::k_mhmc_state_large<NQ>, p, p.pv, dc, C, dx, dd, du, T, step, dch, dacc);
+      }))
+    return r;
   return c.done();
-}
-
-// a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch and qt_mle_dist_batch
-static int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol,
-                          const double* centre, double* rho, double* dist, int32_t* nit, int32_t* nfev, double* fun,
-                          int32_t* status, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (int r = need_povm(h)) return r;
-  if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad mle_batch arguments");
-  if (init != QT_INIT_LIN && init != QT_INIT_MIXED) return fail(QT_ERR_ARG, "init must be QT_INIT_LIN or QT_INIT_MIXED");
-  if (max_iter < 0) return fail(QT_ERR_ARG, "max_iter < 0");
-  if (B == 0) return 0;
-  const int64_t* dc;
-  const double* dcen;
-  double *drho, *dfun, *ddist;
-  int32_t *dnit, *dnfev, *dst;
-  const size_t nel = (size_t)B * h->D;
-  if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
-  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
-  if (int r = c.out(rho, nel * 2, &drho)) return r;
-  if (int r = c.out(nit, (size_t)B, &dnit)) return r;
-  if (int r = c.out(nfev, (size_t)B, &dnfev)) return r;
-  if (int r = c.out(fun, (size_t)B, &dfun)) return r;
-  if (int r = c.out(status, (size_t)B, &dst)) return r;
-  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
-  const qt::EstOut eo{drho, dcen, ddist};
-  if (h->nq >= 4) {
-    if (int r = prepare_large(h, init == QT_INIT_LIN)) return r;
-    // BFGS history: 2 D doubles per iteration and trial, processed in chunks of <= 4 GiB
-    if (max_iter > 4096) return fail(QT_ERR_UNSUPPORTED, "max_iter > 4096 is not supported for n_qubits >= 4");
-    const size_t per_trial = (size_t)(max_iter > 0 ? max_iter : 1) * 2 * h->D * sizeof(double);
-    int chunk = (int)(((size_t)4 << 30) / per_trial);
-    if (chunk < 1) chunk = 1;
-    if (chunk > B) chunk = B;
-    HIPCHK(h->hess.ensure((size_t)chunk * per_trial));
-    HIPCHK(h->ws_x.ensure(nel * sizeof(double)));
-    HIPCHK(h->ws_g.ensure(nel * sizeof(double)));
-    HIPCHK(h->ws_f.ensure((size_t)B * sizeof(double)));
-    HIPCHK(h->ws_act.ensure((size_t)B * sizeof(int32_t)));
-    double *wx = h->ws_x.as<double>(), *wg = h->ws_g.as<double>(), *wf = h->ws_f.as<double>();
-    int32_t* wact = h->ws_act.as<int32_t>();
-    // start point + first evaluation of every trial; then the BFGS loop of those that iterate, chunk by chunk
-    QT_LAUNCH_LARGE(qt::k_mle_large_start, B, h->M, h->prod.R1,
-                    (h->view(), dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, wx, wg, wf, wact));
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-      const int nb = (B - b0 < chunk) ? B - b0 : chunk;
-      QT_LAUNCH_LARGE_X(qt::k_mle_large_bfgs, nb, h->M, h->prod.R1, max_iter,
-                        (h->view(), dc + (size_t)b0 * h->M, nb, max_iter, tol,
-                         qt::EstOut{drho ? drho + (size_t)b0 * h->D * 2 : nullptr, dcen, ddist ? ddist + b0 : nullptr},
-                         dnit ? dnit + b0 : nullptr, dnfev ? dnfev + b0 : nullptr, dfun ? dfun + b0 : nullptr,
-                         dst ? dst + b0 : nullptr, wx + (size_t)b0 * h->D, wg + (size_t)b0 * h->D, wf + b0, wact + b0,
-                         h->hess.as<double>()));
-    }
-  } else {
-    // up to one resident wave per SIMD (1024 trial-waves) the single fused launch wins; beyond that the
-    // 256-VGPR BFGS loop would cap occupancy for every trial, so the split pair is used
-    const int waves = (B + (64 / h->D > 0 ? 64 / h->D : 1) - 1) / (64 / h->D > 0 ? 64 / h->D : 1);
-    // n = 3 keeps rho_i / alpha_i of every BFGS iteration in the trial's LDS (16 bytes per iteration and trial):
-    // the one-launch kernel (which also keeps 24 pairs there) up to 256 iterations, the split pair up to 2000
-    if (h->nq == 3 && max_iter > 2000)
-      return fail(QT_ERR_UNSUPPORTED, "max_iter > 2000 is not supported for n_qubits = 3 (LDS holds the two-loop scalars)");
-    if (waves <= h->fused_max_waves && !(h->nq == 3 && max_iter > 256)) {
-      if (h->nq == 3) {  // two-loop BFGS: line-search state, rho_i, alpha_i and the first pairs in LDS, later pairs in global
-        const int mi = max_iter > 0 ? max_iter : 1;
-        h->lds_extra = qt::LineSearch::SLOTS + 2 * mi + qt::kFusedLdsPairs * 2 * h->D;
-        const int over = mi > qt::kFusedLdsPairs ? mi : 1;  // (indexed by pair number: rows below kFusedLdsPairs stay unused)
-        HIPCHK(h->hess.ensure((size_t)B * over * 2 * h->D * sizeof(double)));
-      }
-      if (init == QT_INIT_LIN) {
-        QT_LAUNCH_SMALL(qt::k_mle_fused, h->M, B,
-                        (h->view(), dc, B, max_iter, tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>()));
-      } else {
-        QT_LAUNCH_SMALL(qt::k_mle_fused_mixed, h->M, B,
-                        (h->view(), dc, B, max_iter, tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>()));
-      }
-      h->lds_extra = 0;
-    } else {
-      HIPCHK(h->ws_x.ensure(nel * sizeof(double)));
-      HIPCHK(h->ws_g.ensure(nel * sizeof(double)));
-      HIPCHK(h->ws_f.ensure((size_t)B * sizeof(double)));
-      HIPCHK(h->ws_act.ensure((size_t)B * sizeof(int32_t)));
-      double *wx = h->ws_x.as<double>(), *wg = h->ws_g.as<double>(), *wf = h->ws_f.as<double>();
-      int32_t* wact = h->ws_act.as<int32_t>();
-      QT_LAUNCH_SMALL(qt::k_mle_start, h->M, B,
-                      (h->view(), dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, wx, wg, wf, wact));
-      // BFGS history of the trials that iterate: 2 D doubles per iteration and trial (two-loop recursion), in
-      // chunks of <= 4 GiB; rho_i, alpha_i and the parked line-search state in LDS
-      int chunk = B;
-      if (h->nq == 3) {  // (n = 1, 2 keep the 4 / 16-entry Hessian rows in registers: no workspace)
-        const size_t per_trial = (size_t)(max_iter > 0 ? max_iter : 1) * 2 * h->D * sizeof(double);
-        chunk = (int)(((size_t)4 << 30) / per_trial);
-        if (chunk < 1) chunk = 1;
-        if (chunk > B) chunk = B;
-        HIPCHK(h->hess.ensure((size_t)chunk * per_trial));
-        h->lds_extra = qt::LineSearch::SLOTS + 2 * (max_iter > 0 ? max_iter : 1);
-      }
-      for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int nb = (B - b0 < chunk) ? B - b0 : chunk;
-        QT_LAUNCH_SMALL(qt::k_mle_bfgs, h->M, nb,
-                        (h->view(), dc + (size_t)b0 * h->M, nb, max_iter, tol,
-                         qt::EstOut{drho ? drho + (size_t)b0 * h->D * 2 : nullptr, dcen, ddist ? ddist + b0 : nullptr},
-                         dnit ? dnit + b0 : nullptr, dnfev ? dnfev + b0 : nullptr, dfun ? dfun + b0 : nullptr,
-                         dst ? dst + b0 : nullptr, wx + (size_t)b0 * h->D, wg + (size_t)b0 * h->D, wf + b0, wact + b0,
-                         h->hess.as<double>()));
-      }
-      h->lds_extra = 0;
-    }
-  }
-  return c.done(status, B);
 }
 
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
@@ -1326,9 +1356,9 @@ int qt_select_finish(qt_handle_t* h, const double* windows, int N, int L, int W,
   size_t cap = (size_t)N * W;
   if (cap > 16000) cap = 16000;  // 128 KB of LDS; a larger union raises the overflow flag (heavy ties: take the merge path)
   const size_t lds = cap * sizeof(double) + ((size_t)N + 2) * sizeof(int);
-  if (int r = allow_big_lds(qt::k_select_finish, lds)) return r;
-  hipLaunchKernelGGL(qt::k_select_finish, dim3(L), dim3(1024), lds, h->stream, dw, N, L, W, (int)cap, n_total, dq, dout,
-                     reinterpret_cast<int*>(dfl));
+  if (int r = launch(h, qt::k_select_finish, dim3(L), dim3(1024), lds, dw, N, L, W, (int)cap, n_total, dq, dout,
+                     reinterpret_cast<int*>(dfl)))
+    return r;
   return c.done();
 }
 
@@ -1406,17 +1436,10 @@ int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, 
   double* dW = h->gram.as<double>();
   hipLaunchKernelGGL(qt::k_gemm<0>, dim3((unsigned)((M + 15) / 16), (unsigned)((M + 15) / 16)), dim3(64), 0, h->stream, (int)M, (int)M,
                      rows, dp, (int)M, 1, dp, (int)M, 0, dW, (int)M);
-  if (M <= 1024) {
-    constexpr int T = 4;
-    const size_t lds = (size_t)2 * T * M * sizeof(double);
-    if (int r = allow_big_lds(qt::k_moment_batch<T, 4>, lds)) return r;
-    hipLaunchKernelGGL((qt::k_moment_batch<T, 4>), dim3((B + T - 1) / T), dim3(256), lds, h->stream, dc, B, S, K, dns, dW, n_trials,
-                       dmean, dvar);
-  } else {
-    const size_t lds = (size_t)2 * M * sizeof(double);
-    if (int r = allow_big_lds(qt::k_moment_batch<1, 32>, lds)) return r;
-    hipLaunchKernelGGL((qt::k_moment_batch<1, 32>), dim3(B), dim3(256), lds, h->stream, dc, B, S, K, dns, dW, n_trials, dmean, dvar);
-  }
+  const int T = M <= 1024 ? 4 : 1;  // trials per workgroup
+  if (int r = launch(h, T == 4 ? qt::k_moment_batch<4, 4> : qt::k_moment_batch<1, 32>, dim3((B + T - 1) / T), dim3(256),
+                     (size_t)2 * T * M * sizeof(double), dc, B, S, K, dns, dW, n_trials, dmean, dvar))
+    return r;
   return c.done();
 }
 
@@ -1452,8 +1475,6 @@ int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double
 }
 
 // ---- a4 / a12 / a16 host side: state.py:109-114, the draws of experiment() (qt_sampler.h) ---------
-static int check_pvals(int period, int K, const int64_t* n, const double* pvals);
-
 int qt_legacy_multinomial(uint32_t* mt_key, int* mt_pos, long long rows, int period, const int64_t* n,
                           const double* pvals, int K, int64_t* out) {
   if (!mt_key || !mt_pos || !n || !pvals || (rows > 0 && !out) || rows < 0 || period < 1 || K < 1)
@@ -1467,26 +1488,6 @@ int qt_legacy_multinomial(uint32_t* mt_key, int* mt_pos, long long rows, int per
     qt_sampler::legacy_multinomial(g, n[s], pvals + (size_t)s * K, K, out + (size_t)r * K, cache.data() + (size_t)s * K);
   }
   *mt_pos = g.pos;
-  return 0;
-}
-
-static int check_pvals(int period, int K, const int64_t* n, const double* pvals) {
-  for (int s = 0; s < period; ++s) {
-    if (n[s] < 0) return fail(QT_ERR_ARG, "n < 0 in row %d", s);
-    // RandomState.multinomial's own checks (mtrand.pyx): every pval in [0, 1], and the leading K - 1 may not exceed 1
-    double head = 0.0, comp = 0.0;  // compensated sum, as NumPy's check has it
-    for (int j = 0; j < K; ++j) {
-      const double p = pvals[(size_t)s * K + j];
-      if (!(p >= 0.0 && p <= 1.0)) return fail(QT_ERR_ARG, "pvals < 0, pvals > 1 or pvals contains NaNs");
-      if (j == 0 && K > 1) head = p;
-      if (j > 0 && j < K - 1) {
-        const double y = p - comp, t = head + y;
-        comp = (t - head) - y;
-        head = t;
-      }
-    }
-    if (head > 1.0 + 1e-12) return fail(QT_ERR_ARG, "sum(pvals[:-1]) > 1.0");
-  }
   return 0;
 }
 
@@ -1534,22 +1535,8 @@ int qt_left_inverse(qt_handle_t* h, const double* A, int rows, int cols, int is_
   double* dout;
   if (int r = c.in(A, nel, &dA)) return r;
   if (int r = c.out(out, nel, &dout)) return r;
-  DevBuf& aug = h->proc_aug;
-  HIPCHK(aug.ensure((size_t)cols * 2 * cols * W * sizeof(double)));
-  HIPCHK(h->info.ensure(sizeof(int)));
-  double* g = aug.as<double>();
-  dim3 gg((cols + 15) / 16, (cols + 15) / 16), gp((rows + 15) / 16, (cols + 15) / 16);
-  if (is_complex) {
-    hipLaunchKernelGGL(qt::k_gemm<1>, gg, dim3(64), 0, h->stream, cols, cols, rows, dA, cols, 1, dA, cols, 0, g, 2 * cols);
-    launch_gauss_jordan<1>(h, cols, g, h->info.as<int>());
-    hipLaunchKernelGGL(qt::k_gemm<1>, gp, dim3(64), 0, h->stream, cols, rows, cols, g + (size_t)cols * 2, 2 * cols, 0, dA,
-                       cols, 1, dout, rows);
-  } else {
-    hipLaunchKernelGGL(qt::k_gemm<0>, gg, dim3(64), 0, h->stream, cols, cols, rows, dA, cols, 1, dA, cols, 0, g, 2 * cols);
-    launch_gauss_jordan<0>(h, cols, g, h->info.as<int>());
-    hipLaunchKernelGGL(qt::k_gemm<0>, gp, dim3(64), 0, h->stream, cols, rows, cols, g + cols, 2 * cols, 0, dA, cols, 1,
-                       dout, rows);
-  }
+  if (int r = is_complex ? enqueue_left_inverse<2>(h, dA, rows, cols, dout) : enqueue_left_inverse<1>(h, dA, rows, cols, dout))
+    return r;
   int info = 0;
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (int r = c.done()) return r;
@@ -1582,9 +1569,9 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
     hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->stream, h->nq, h->Aw.as<double>(),
                        M, (double*)ps.emats);
     int info[2] = {0, 0};
-    if (int r = enqueue_left_inverse_complex(h, (const double*)ps.in_states, D, D, (double*)ps.vs_pinv)) return r;
+    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.in_states, D, D, (double*)ps.vs_pinv)) return r;
     HIPCHK(hipMemcpyAsync(&info[0], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (int r = enqueue_left_inverse_complex(h, (const double*)ps.emats, M, D, (double*)ps.vp_pinv)) return r;
+    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.emats, M, D, (double*)ps.vp_pinv)) return r;
     HIPCHK(hipMemcpyAsync(&info[1], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     launch_transpose<2>(h, (const double*)ps.vp_pinv, D, M, (double*)ps.vp_pinvT);
     if (M % 4 == 0) {  // the operand of k_lifp64 (the matrix-core path of qt_lifp_batch)
@@ -1605,21 +1592,15 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
   HIPCHK(hipMalloc(&ps.lifp, R * C2 * 2 * sizeof(double)));
   HIPCHK(hipMalloc(&ps.pinv, R * C2 * 2 * sizeof(double)));
   HIPCHK(hipMalloc(&ps.pinvT, R * C2 * 2 * sizeof(double)));
-  HIPCHK(hipMalloc(&ps.aug, C2 * 2 * C2 * 2 * sizeof(double)));
-  HIPCHK(h->info.ensure(sizeof(int)));
   if (int r = c.copy_in((double*)ps.in_states, in_states, (size_t)D * D * 2)) return r;
-  double *lifp = (double*)ps.lifp, *pinv = (double*)ps.pinv, *pinvT = (double*)ps.pinvT, *aug = (double*)ps.aug;
+  double *lifp = (double*)ps.lifp, *pinv = (double*)ps.pinv, *pinvT = (double*)ps.pinvT;
   // E_m = sum_k A'[m][k] P_k  (process.py:204: Qobj(povm_bloch).matrix)
   hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->stream, h->nq, h->Aw.as<double>(),
                      M, (double*)ps.emats);
   hipLaunchKernelGGL(qt::k_lifp_rows, dim3(grid_for(R * C2)), dim3(256), 0, h->stream, d, M, (const double*)ps.in_states,
                      (const double*)ps.emats, lifp);
   const int c2 = (int)C2, rr = (int)R;
-  dim3 gg((c2 + 15) / 16, (c2 + 15) / 16), gp((rr + 15) / 16, (c2 + 15) / 16);
-  hipLaunchKernelGGL(qt::k_gemm<1>, gg, dim3(64), 0, h->stream, c2, c2, rr, lifp, c2, 1, lifp, c2, 0, aug, 2 * c2);
-  launch_gauss_jordan<1>(h, c2, aug, h->info.as<int>());
-  hipLaunchKernelGGL(qt::k_gemm<1>, gp, dim3(64), 0, h->stream, c2, rr, c2, aug + (size_t)c2 * 2, 2 * c2, 0, lifp, c2, 1,
-                     pinv, rr);
+  if (int r = enqueue_left_inverse<2>(h, lifp, rr, c2, pinv)) return r;
   launch_transpose<2>(h, pinv, c2, rr, pinvT);
   if (h->nq == 2) {  // the batched GEMM of qt_lifp_batch reads the left inverse in row-major Choi order
     HIPCHK(hipMalloc(&ps.pinvR, R * C2 * 2 * sizeof(double)));
@@ -1636,9 +1617,9 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
     HIPCHK(hipMalloc(&ps.vp_pinv, (size_t)D * M * 2 * sizeof(double)));
     HIPCHK(hipMalloc(&ps.vp_pinvT, (size_t)M * D * 2 * sizeof(double)));
     HIPCHK(hipMalloc(&ps.vp_perm, (size_t)M * 32 * sizeof(double)));
-    if (int r = enqueue_left_inverse_complex(h, (const double*)ps.in_states, D, D, (double*)ps.vs_pinv)) return r;
+    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.in_states, D, D, (double*)ps.vs_pinv)) return r;
     HIPCHK(hipMemcpyAsync(&finfo[0], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (int r = enqueue_left_inverse_complex(h, (const double*)ps.emats, M, D, (double*)ps.vp_pinv)) return r;
+    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.emats, M, D, (double*)ps.vp_pinv)) return r;
     HIPCHK(hipMemcpyAsync(&finfo[1], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     launch_transpose<2>(h, (const double*)ps.vp_pinv, D, M, (double*)ps.vp_pinvT);
     hipLaunchKernelGGL(qt::k_vp_perm, dim3(grid_for((size_t)M * 32)), dim3(256), 0, h->stream, (const double*)ps.vp_pinvT, M, D, d,
@@ -1726,12 +1707,8 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
       hipLaunchKernelGGL(qt::k_lifp_kron_finish, dim3(B), dim3(256), 0, h->stream, (const double*)T,
                          (const double*)h->proc.vs_pinv, B, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit);
     }
-    if (cptp) {
-      if (int r = allow_big_lds(qt::k_cptp_project64, qt::Proc64::kLdsBytes)) return r;
-      HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));  // Dykstra's p, q, y, x + the clip's input
-      hipLaunchKernelGGL(qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, h->stream, (const double*)raw,
-                         B, 0, 1000, 1e-12, dchoi, dit, dst, h->proc_ws.as<double>());
-    }
+    if (cptp)
+      if (int r = project64(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
     return c.done(status, B);
   }
   const size_t dyn = (size_t)D * M * sizeof(double);
@@ -1739,10 +1716,7 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
   const int R = D * M, Rp = (R + 63) / 64 * 64;
   const size_t gemm_lds = ((size_t)Rp * 16 + 4 * 256) * sizeof(double);
   const size_t gemm_lds2 = ((size_t)Rp * 32 + 4 * 512) * sizeof(double);  // two column tiles per workgroup
-  if (D == 4) {
-    hipLaunchKernelGGL(qt::k_lifp_batch<4>, dim3(B), dim3(qt::ProcWG<4>::NT), dyn, h->stream, dc, B, M,
-                       (const double*)h->proc.pinvT, cptp, dchoi, dit, dst);
-  } else if (h->proc.vp_perm && !h->proc_dense) {
+  if (D == 16 && h->proc.vp_perm && !h->proc_dense) {
     // n = 2 through the Kronecker factors of the left inverse: one wavefront per process (qt_process.h, k_lifp16)
     double* raw = dchoi;
     if (cptp) {
@@ -1754,16 +1728,11 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
                                  // next process's counts in flight, and a workgroup stages V_P^+ once for all its processes
     const size_t lds = (size_t)M * 32 * sizeof(double);
     int32_t *st = cptp ? (int32_t*)nullptr : dst, *it0 = cptp ? (int32_t*)nullptr : dit;
-    if (M == 36)
-      hipLaunchKernelGGL(qt::k_lifp16<9>, dim3(grid), dim3(256), lds, h->stream, dc, B, M, (const double*)h->proc.vp_perm,
-                         (const double*)h->proc.vs_pinv, raw, st, it0);
-    else
-      hipLaunchKernelGGL(qt::k_lifp16<0>, dim3(grid), dim3(256), lds, h->stream, dc, B, M, (const double*)h->proc.vp_perm,
-                         (const double*)h->proc.vs_pinv, raw, st, it0);
+    hipLaunchKernelGGL((M == 36 ? qt::k_lifp16<9> : qt::k_lifp16<0>), dim3(grid), dim3(256), lds, h->stream, dc, B, M,
+                       (const double*)h->proc.vp_perm, (const double*)h->proc.vs_pinv, raw, st, it0);
     if (cptp)
-      hipLaunchKernelGGL(qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, h->stream, (const double*)raw, B, 0, 1000, 1e-12,
-                         dchoi, dit, dst);
-  } else if (B >= 256 && gemm_lds <= 152 * 1024) {
+      if (int r = project16(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
+  } else if (D == 16 && B >= 256 && gemm_lds <= 152 * 1024) {
     // many processes: frequencies, then one FP64 MFMA GEMM over the batch, then (cptp) the projection kernel
     constexpr int NE = 256;
     HIPCHK(h->ws_x.ensure(((size_t)B * Rp + 192) * sizeof(double)));  // [B][Rp] + the zeros k_lifp_freq appends
@@ -1780,36 +1749,30 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
     const int nblocks = (B + 63) / 64;
     const int passes = nblocks >= 64 ? 4 : (nblocks >= 32 ? 2 : 1);
     const int row_blocks = (nblocks + passes - 1) / passes;
+    const bool two = gemm_lds2 <= kLdsLimit;  // two column tiles per workgroup: half the re-reads of F (R <= 576)
+    auto kern = two ? qt::k_lifp_gemm<16, 2> : qt::k_lifp_gemm<16, 1>;
 #ifdef QT_PHASE_TIMING
-#define QT_GEMM_VARIANT(V)                                                                                                \
-  case V:                                                                                                                 \
-    if (int r = allow_big_lds(qt::k_lifp_gemm<16, 2, V>, gemm_lds2)) return r;                                             \
-    hipLaunchKernelGGL((qt::k_lifp_gemm<16, 2, V>), dim3(2 * NE / 32, row_blocks), dim3(512), gemm_lds2, h->stream, F, B, R, Rp, \
-                       (const double*)h->proc.pinvR, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit);  \
-    break;
-    if (gemm_lds2 <= kLdsLimit && g_host_diag != 0) {
-      switch (g_host_diag) {
-        QT_GEMM_VARIANT(1) QT_GEMM_VARIANT(2) QT_GEMM_VARIANT(3) QT_GEMM_VARIANT(4) QT_GEMM_VARIANT(7) QT_GEMM_VARIANT(8)
-        QT_GEMM_VARIANT(15)
-        default: return fail(QT_ERR_ARG, "no such diagnostic variant");
-      }
-    } else
-#endif
-    if (gemm_lds2 <= kLdsLimit) {  // two column tiles per workgroup: half the re-reads of F (R <= 576)
-      if (int r = allow_big_lds(qt::k_lifp_gemm<16, 2>, gemm_lds2)) return r;
-      hipLaunchKernelGGL((qt::k_lifp_gemm<16, 2>), dim3(2 * NE / 32, row_blocks), dim3(512), gemm_lds2, h->stream, F, B, R, Rp,
-                         (const double*)h->proc.pinvR, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit);
-    } else {
-      if (int r = allow_big_lds(qt::k_lifp_gemm<16, 1>, gemm_lds)) return r;
-      hipLaunchKernelGGL((qt::k_lifp_gemm<16, 1>), dim3(2 * NE / 16, row_blocks), dim3(512), gemm_lds, h->stream, F, B, R, Rp,
-                         (const double*)h->proc.pinvR, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit);
+    switch (two ? g_host_diag : 0) {  // profile build: a compile-time variant of the two-tile kernel (qt_debug_set_diag)
+      case 0: break;
+      case 1: kern = qt::k_lifp_gemm<16, 2, 1>; break;
+      case 2: kern = qt::k_lifp_gemm<16, 2, 2>; break;
+      case 3: kern = qt::k_lifp_gemm<16, 2, 3>; break;
+      case 4: kern = qt::k_lifp_gemm<16, 2, 4>; break;
+      case 7: kern = qt::k_lifp_gemm<16, 2, 7>; break;
+      case 8: kern = qt::k_lifp_gemm<16, 2, 8>; break;
+      case 15: kern = qt::k_lifp_gemm<16, 2, 15>; break;
+      default: return fail(QT_ERR_ARG, "no such diagnostic variant");
     }
+#endif
+    if (int r = launch(h, kern, dim3(2 * NE / (two ? 32 : 16), row_blocks), dim3(512), two ? gemm_lds2 : gemm_lds, F, B, R, Rp,
+                       (const double*)h->proc.pinvR, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit))
+      return r;
     if (cptp)
-      hipLaunchKernelGGL(qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, h->stream, (const double*)raw, B, 0, 1000, 1e-12,
-                         dchoi, dit, dst);
+      if (int r = project16(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
   } else {
-    hipLaunchKernelGGL(qt::k_lifp_batch<16>, dim3(B), dim3(qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M,
-                       (const double*)h->proc.pinvT, cptp, dchoi, dit, dst);
+    hipLaunchKernelGGL((D == 4 ? qt::k_lifp_batch<4> : qt::k_lifp_batch<16>), dim3(B),
+                       dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M, (const double*)h->proc.pinvT,
+                       cptp, dchoi, dit, dst);
   }
   return c.done(status, B);
 }
@@ -1837,24 +1800,20 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
     HIPCHK(h->ws_x.ensure((size_t)B * S::ws_doubles(M) * sizeof(double)));
     HIPCHK(h->ws_g.ensure((size_t)B * ne2 * sizeof(double)));  // trial points c - g / mu
     HIPCHK(h->ws_f.ensure((size_t)B * ne2 * sizeof(double)));  // their CPTP projections
-    HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
     HIPCHK(h->ws_act.ensure(((size_t)B * 4 + 4) * sizeof(int32_t)));
     int32_t* state = h->ws_act.as<int32_t>();
     int32_t* n_active = state + (size_t)B * 4;
-    if (int r = allow_big_lds(qt::k_cptp_project64, qt::Proc64::kLdsBytes)) return r;
-    if (int r = allow_big_lds(qt::k_pgdb64_grad, S::kLdsBytes)) return r;
-    if (int r = allow_big_lds(qt::k_pgdb64_step, S::kLdsBytes)) return r;
     const double *vs = (const double*)h->proc.in_states, *vp = (const double*)h->proc.emats;
     hipLaunchKernelGGL(qt::k_pgdb64_init, dim3(B), dim3(256), 0, h->stream, B, dchoi, state, dit, dst, n_active);
     for (int it = 0; it < n_iter; ++it) {
-      hipLaunchKernelGGL(qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, h->stream, dc, B, M, vs, vp, (const double*)dchoi,
-                         (const int32_t*)state, h->ws_x.as<double>(), h->ws_g.as<double>());
-      hipLaunchKernelGGL(qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, h->stream,
-                         (const double*)h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), (int32_t*)nullptr,
-                         (int32_t*)nullptr, h->proc_ws.as<double>());
-      hipLaunchKernelGGL(qt::k_pgdb64_step, dim3(B), dim3(S::NT), S::kLdsBytes, h->stream, dc, B, M, vs, vp,
+      if (int r = launch(h, qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, vs, vp, (const double*)dchoi,
+                         (const int32_t*)state, h->ws_x.as<double>(), h->ws_g.as<double>()))
+        return r;
+      if (int r = project64(h, h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr)) return r;
+      if (int r = launch(h, qt::k_pgdb64_step, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, vs, vp,
                          (const double*)h->ws_f.as<double>(), n_iter, tol, stop_rule, dchoi, state, h->ws_x.as<double>(), dit, dst,
-                         n_active);
+                         n_active))
+        return r;
       int left = 0;
       HIPCHK(hipMemcpyAsync(&left, n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
@@ -1865,12 +1824,9 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
   }
   const size_t dyn = (size_t)4 * D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-  if (D == 4)
-    hipLaunchKernelGGL(qt::k_pgdb_batch<4>, dim3(B), dim3(qt::ProcWG<4>::NT), dyn, h->stream, dc, B, M,
-                       (const double*)h->proc.lifp, n_iter, tol, stop_rule, dchoi, dit, dst);
-  else
-    hipLaunchKernelGGL(qt::k_pgdb_batch<16>, dim3(B), dim3(qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M,
-                       (const double*)h->proc.lifp, n_iter, tol, stop_rule, dchoi, dit, dst);
+  hipLaunchKernelGGL((D == 4 ? qt::k_pgdb_batch<4> : qt::k_pgdb_batch<16>), dim3(B),
+                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M, (const double*)h->proc.lifp,
+                     n_iter, tol, stop_rule, dchoi, dit, dst);
   return c.done(status, B);
 }
 
@@ -1892,17 +1848,13 @@ int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* c
   HIPCHK(h->ws_x.ensure((size_t)B * wsd * sizeof(double)));
   HIPCHK(h->ws_g.ensure((size_t)B * ne2 * sizeof(double)));
   HIPCHK(h->ws_f.ensure((size_t)B * ne2 * sizeof(double)));
-  HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
   HIPCHK(h->ws_act.ensure(((size_t)B * 4 + 4) * sizeof(int32_t)));
   int32_t* state = h->ws_act.as<int32_t>();
   HIPCHK(hipMemsetAsync(state, 0, ((size_t)B * 4 + 4) * sizeof(int32_t), h->stream));
-  if (int r = allow_big_lds(qt::k_cptp_project64, qt::Proc64::kLdsBytes)) return r;
-  if (int r = allow_big_lds(qt::k_pgdb64_grad, S::kLdsBytes)) return r;
-  hipLaunchKernelGGL(qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, h->stream, dc, B, M, (const double*)h->proc.in_states,
-                     (const double*)h->proc.emats, dcur, (const int32_t*)state, h->ws_x.as<double>(), h->ws_g.as<double>());
-  hipLaunchKernelGGL(qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, h->stream,
-                     (const double*)h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), (int32_t*)nullptr,
-                     (int32_t*)nullptr, h->proc_ws.as<double>());
+  if (int r = launch(h, qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, (const double*)h->proc.in_states,
+                     (const double*)h->proc.emats, dcur, (const int32_t*)state, h->ws_x.as<double>(), h->ws_g.as<double>()))
+    return r;
+  if (int r = project64(h, h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr)) return r;
   HIPCHK(hipGetLastError());
   const hipMemcpyKind kind = c.to_caller();
   const double* ws = h->ws_x.as<double>();
@@ -1943,25 +1895,22 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
     HIPCHK(h->ws_g.ensure((size_t)C * ne * 2 * sizeof(double)));     // proposals before the projection
     HIPCHK(h->ws_f.ensure((size_t)C * ne * 2 * sizeof(double)));     // ... and after it
     HIPCHK(h->hess.ensure((size_t)C * ne * 2 * sizeof(double)));     // the chains' current points
-    HIPCHK(h->proc_ws.ensure((size_t)C * qt::Proc64::kWsComplex * 2 * sizeof(double)));
-    if (int r = allow_big_lds(qt::k_cptp_project64, qt::Proc64::kLdsBytes)) return r;
-    if (int r = allow_big_lds(qt::k_fwd64_nll, qt::Fwd64::kLdsBytes)) return r;
     double *ws = h->ws_x.as<double>(), *fcur = ws + (size_t)C * S::ws_doubles(M), *fpart = fcur + C, *x = h->hess.as<double>();
     const double *vs = (const double*)h->proc.in_states, *vp = (const double*)h->proc.emats;
     HIPCHK(hipMemcpyAsync(x, dx, (size_t)C * ne * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     // the model and the NLL of a point: C x ceil(M / 16) workgroups on the matrix cores (k_fwd64_nll), then the accept test
-    hipLaunchKernelGGL(qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, h->stream, dc, C, M, vs, vp,
-                       (const double*)x, (const double*)nullptr, 0, fpart);
+    if (int r = launch(h, qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, C, M, vs, vp, (const double*)x,
+                       (const double*)nullptr, 0, fpart))
+      return r;
     hipLaunchKernelGGL(qt::k_mhmc64_decide, dim3(C), dim3(256), 0, h->stream, C, nt, T, -1, (const double*)fpart,
                        (const double*)nullptr, du, x, fcur, dch, dacc);
     for (int t = 0; t < T; ++t) {
       hipLaunchKernelGGL(qt::k_mhmc64_propose, dim3(C), dim3(256), 0, h->stream, C, T, t, step, (const double*)x, dd,
                          h->ws_g.as<double>());
-      hipLaunchKernelGGL(qt::k_cptp_project64, dim3(C), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, h->stream,
-                         (const double*)h->ws_g.as<double>(), C, 0, 1000, 1e-12, h->ws_f.as<double>(), (int32_t*)nullptr,
-                         (int32_t*)nullptr, h->proc_ws.as<double>());
-      hipLaunchKernelGGL(qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, h->stream, dc, C, M, vs, vp,
-                         (const double*)x, (const double*)h->ws_f.as<double>(), 1, fpart);
+      if (int r = project64(h, h->ws_g.as<double>(), C, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr)) return r;
+      if (int r = launch(h, qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, C, M, vs, vp, (const double*)x,
+                         (const double*)h->ws_f.as<double>(), 1, fpart))
+        return r;
       hipLaunchKernelGGL(qt::k_mhmc64_decide, dim3(C), dim3(256), 0, h->stream, C, nt, T, t, (const double*)fpart,
                          (const double*)h->ws_f.as<double>(), du, x, fcur, dch, dacc);
     }
@@ -1970,12 +1919,9 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
   }
   const size_t dyn = (size_t)2 * D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-  if (D == 4)
-    hipLaunchKernelGGL(qt::k_mhmc_process<4>, dim3(C), dim3(qt::ProcWG<4>::NT), dyn, h->stream, dc, C, M,
-                       (const double*)h->proc.lifp, dx, dd, du, T, step, dch, dacc);
-  else
-    hipLaunchKernelGGL(qt::k_mhmc_process<16>, dim3(C), dim3(qt::ProcWG<16>::NT), dyn, h->stream, dc, C, M,
-                       (const double*)h->proc.lifp, dx, dd, du, T, step, dch, dacc);
+  hipLaunchKernelGGL((D == 4 ? qt::k_mhmc_process<4> : qt::k_mhmc_process<16>), dim3(C),
+                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, h->stream, dc, C, M, (const double*)h->proc.lifp, dx,
+                     dd, du, T, step, dch, dacc);
   return c.done();
 }
 
@@ -1994,18 +1940,15 @@ int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode
   if (int r = c.in(choi_in, (size_t)B * D * D * 2, &din)) return r;
   if (int r = c.out(choi_out, (size_t)B * D * D * 2, &dout)) return r;
   if (int r = c.out(iters, (size_t)B, &dit)) return r;
-  if (D == 64) {
-    if (int r = allow_big_lds(qt::k_cptp_project64, qt::Proc64::kLdsBytes)) return r;
-    if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));  // Dykstra's p, q, y, x + the clip's input
-    hipLaunchKernelGGL(qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, h->stream, din, B, mode, n_iter,
-                       tol, dout, dit, (int32_t*)nullptr, h->proc_ws.as<double>());
-  } else if (D == 4)
+  int r = 0;
+  if (D == 64)
+    r = project64(h, din, B, mode, n_iter, tol, dout, dit, nullptr);
+  else if (D == 16)
+    r = project16(h, din, B, mode, n_iter, tol, dout, dit, nullptr);
+  else
     hipLaunchKernelGGL(qt::k_cptp_project<4>, dim3(B), dim3(qt::ProcWG<4>::NT), 0, h->stream, din, B, mode, n_iter, tol, dout,
                        dit);
-  else
-    hipLaunchKernelGGL(qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, h->stream, din, B, mode, n_iter, tol, dout, dit,
-                       (int32_t*)nullptr);
-  return c.done();
+  return r ? r : c.done();
 }
 
 }  // extern "C"

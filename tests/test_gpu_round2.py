@@ -321,6 +321,40 @@ def test_options_and_iteration_limits(oracle):
     eng.close()
 
 
+def test_refused_launch_leaves_the_engine_as_it_was(oracle):
+    """A launch refused for its LDS size changes nothing that later launches on the engine see.  n = 3 with a plain
+    POVM of M = 864 rows ('proj-set' four times over): at max_iter = 100 the fused MLE would need
+    4 x (2090 + 3304) x 8 B = 172.6 KB of LDS, more than a CU has, and is refused; 'lin' (4 x 2090 x 8 B = 66.9 KB)
+    and the two-loop MLE on the same engine then run and match a fresh engine bit for bit."""
+    import quantpy_amd as qp
+    from quantpy_amd import _capi
+
+    a = np.tile(np.asarray(qp.generate_measurement_matrix("proj-set", 3)), (4, 1, 1))
+    assert a.shape == (108, 8, 64)
+    rng = np.random.default_rng(6)
+    g = rng.standard_normal((8, 8)) + 1j * rng.standard_normal((8, 8))
+    rho = g @ g.conj().T
+    rho /= np.trace(rho)
+    np.random.seed(9)
+    counts = np.stack([oracle.sample_counts(a, oracle.bloch_from_matrix(rho), 200) for _ in range(3)])
+    eng, fresh = qp.Engine(3), qp.Engine(3)
+    for e in (eng, fresh):
+        e.set_povm(a, counts[0].sum(-1))
+    with pytest.raises(qp.EngineError) as ei:
+        eng.mle(counts, max_iter=100)
+    assert ei.value.code == _capi.QT_ERR_UNSUPPORTED
+    assert np.array_equal(eng.lin(counts), fresh.lin(counts))
+    for e in (eng, fresh):
+        e.set_option(_capi.QT_OPT_MLE_FUSED_MAX_WAVES, 0)
+    r, info = eng.mle(counts, max_iter=100, return_info=True)
+    r_fresh, info_fresh = fresh.mle(counts, max_iter=100, return_info=True)
+    assert np.array_equal(r, r_fresh)
+    for k in info_fresh:
+        assert np.array_equal(info[k], info_fresh[k]), k
+    eng.close()
+    fresh.close()
+
+
 def test_hs_dist_of_any_square_size_and_split_timer():
     """qt_hs_dist_dim (Choi matrices are 4^n x 4^n, not the handle's 2^n x 2^n) against the reference formula
     sqrt(|Tr((A - B)^2)|) / sqrt(2) (geometry.py:16-20), and the two halves of qt_timer_end."""
