@@ -252,6 +252,26 @@ enum qt_lp_status {
 int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                      double* obj, double* x, int32_t* status, int32_t* iters, int flags);
 
+/* ---- f4: quantpy/tomography/polytopes (the coverage study of arXiv:2109.04734, Fig. 1) over a batch of trials ------
+ * A trial is a count table counts[b][R][K] with shots[r] per setting (for a process the output tomographs are stacked,
+ * R = inputs x settings, and shots repeats the first tomograph's, as utils.py:11 broadcasts them);
+ * f = clip(counts / shots[r], 1e-15, 1 - 1e-15) (verification.py:30, :66).  Counts are not validated against the shots.
+ * Any R, K (csrc/qt_polytope.h picks the mapping from the shape alone, so splitting a batch over calls changes no bit);
+ * every entry of shots must be positive and finite (QT_ERR_ARG).  B = 0 returns 0 and writes nothing.
+ *
+ * qt_polytope_confidence: conf[b][q] = count_confidence(deltas[b][q], f_b, shots) (utils.py:4-13).
+ * qt_polytope_coverage: for every trial and level, delta = count_delta(levels[l], f_b, shots) (utils.py:16-27: 34
+ * bisection steps) and hit = min(bound - truth) > -1e-15 with bound = clip(f + delta, 1e-15, 1 - 1e-15) when clip_b != 0
+ * (test_qst, verification.py:33-34) and f + delta otherwise (test_qpt, verification.py:70-75); truth[R][K] = the true
+ * outcome probabilities A x + W[:, 0] (verification.py:17-25, :52-60).  Outputs, each nullable (not all three):
+ * deltas[B][L]; hits[B][L] (0 / 1); covered[L], to which the number of covering trials is ADDED (a study runs in chunks
+ * of trials).  hits and covered need truth. */
+int qt_polytope_confidence(qt_handle_t* h, const int64_t* counts, long long B, int R, int K, const double* shots,
+                           const double* deltas, int Q, double* conf, int flags);
+int qt_polytope_coverage(qt_handle_t* h, const int64_t* counts, long long B, int R, int K, const double* shots,
+                         const double* levels, int L, const double* truth, int clip_b, double* deltas, uint8_t* hits,
+                         long long* covered, int flags);
+
 /* Metropolis-Hastings chains on the Cholesky parameters (mhmc.py:80-119 with `normalized_update`, used by
  * MHMCStateInterval, interval.py:735-750): C independent chains (the reference runs one), each on its
  * own counts[c][S][K]; x_init[C][D]; proposal increments deltas[C][T][D] and uniforms[C][T] drawn by the

@@ -8,7 +8,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -17,6 +19,7 @@
 #include "qt_large.h"
 #include "qt_lp.h"
 #include "qt_ops.h"
+#include "qt_polytope.h"
 #include "qt_process.h"
 #include "qt_process64.h"
 #include "qt_process_wave16.h"
@@ -103,6 +106,7 @@ struct qt_handle {
   DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project64)
   DevBuf gram;  // qt_moment_batch: P^T P
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
+  DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -726,6 +730,76 @@ int project16(qt_handle_t* h, const double* in, int B, int mode, int n_iter, dou
 
 }  // namespace
 
+// ---- qt_polytope_confidence / qt_polytope_coverage: the mapping of a shape, argument checks ---------------------------
+namespace {
+
+struct PolyPlan {
+  bool wave = false;
+  int TS = 0, kshift = 0;  // wave teams
+  int NT = 0, mode = 0;    // workgroup per trial
+  qt::PolyShape sh{};
+  size_t lds = 0;
+};
+
+// The mapping is a function of the shape alone.  Workgroup mapping: G = the power of two <= min(K, 64) with the fewest
+// serial entries per lane, ceil(R G / NT) rounds of ceil(K / G) entries (the smallest such G).
+int poly_plan(int R, int K, PolyPlan* p) {
+  const long long RK = (long long)R * K;
+  if (RK > INT32_MAX) return fail(QT_ERR_UNSUPPORTED, "polytope kernels index a count table with 32 bits (R K = %lld)", RK);
+  const bool pow2 = (K & (K - 1)) == 0;
+  p->sh.R = R;
+  p->sh.K = K;
+  if (RK <= 64 && pow2) {
+    p->wave = true;
+    p->TS = 8;
+    while (p->TS < RK) p->TS *= 2;
+    while ((1 << p->kshift) < K) ++p->kshift;
+    return 0;
+  }
+  const size_t lds_f = (size_t)(RK + 16) * sizeof(double);
+  p->mode = lds_f <= kLdsLimit ? qt::POLY_LDS : qt::POLY_GLOBAL;
+  p->NT = RK <= 1024 ? 64 : RK <= 4096 ? 256 : 1024;
+  p->lds = p->mode == qt::POLY_LDS ? lds_f : 16 * sizeof(double);
+  long long best = -1;
+  for (int G = 1, s = 0; G <= 64 && G <= K; G *= 2, ++s) {
+    const long long cost = (((long long)R * G + p->NT - 1) / p->NT) * ((K + G - 1) / G);
+    if (best < 0 || cost < best) {
+      best = cost;
+      p->sh.G = G;
+      p->sh.gshift = s;
+    }
+  }
+  return 0;
+}
+
+// Every shot number positive and finite, checked on the host before any launch.  Device arrays are read back (R doubles)
+// once the handle's stream has finished whatever produces them.
+int poly_check_shots(qt_handle_t* h, Call& c, const double* shots, int R, const char* fn) {
+  std::vector<double> v;
+  if (c.device()) HIPCHK(hipStreamSynchronize(h->stream));
+  if (int r = c.read(v, shots, (size_t)R)) return r;
+  for (int i = 0; i < R; ++i)
+    if (!(v[i] > 0.0) || !std::isfinite(v[i]))
+      return fail(QT_ERR_ARG, "%s: shots[%d] = %g is not a positive finite number", fn, i, v[i]);
+  return 0;
+}
+
+template <class Wave, class Wg>
+int poly_dispatch(const PolyPlan& p, Wave wave, Wg wg) {
+  if (p.wave) return wave();
+  using Lds = std::integral_constant<int, qt::POLY_LDS>;
+  if (p.mode == qt::POLY_GLOBAL) return wg(std::integral_constant<int, 1024>{}, std::integral_constant<int, qt::POLY_GLOBAL>{});
+  if (p.NT == 64) return wg(std::integral_constant<int, 64>{}, Lds{});
+  if (p.NT == 256) return wg(std::integral_constant<int, 256>{}, Lds{});
+  return wg(std::integral_constant<int, 1024>{}, Lds{});
+}
+
+constexpr long long kPolyMaxGrid = 1 << 20;  // workgroups of the per-trial mapping (each strides over the batch)
+// one call: at most 2^31 - 1 workgroups of wave teams (>= 4 pairs each) and counts that a size_t of bytes can hold
+constexpr long long kPolyMaxUnits = 1LL << 32, kPolyMaxCounts = 1LL << 44;
+
+}  // namespace
+
 extern "C" {
 
 int qt_version(void) { return 100; }
@@ -783,7 +857,7 @@ void qt_destroy(qt_handle_t* h) {
   for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd})
     b->release();
   for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws,
-                    &h->gram, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
+                    &h->gram, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
   h->proc.release();
@@ -1472,6 +1546,95 @@ int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double
   hipLaunchKernelGGL(qt::k_lp_ineq, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj, dx, dst,
                      dit, h->lp_ws.as<double>());
   return c.done(status, (int)P);
+}
+
+// ---- f4: polytopes/utils.py:4-27, verification.py:9-78 over a batch of trials (qt_polytope.h) -------------------------
+int qt_polytope_confidence(qt_handle_t* h, const int64_t* counts, long long B, int R, int K, const double* shots,
+                           const double* deltas, int Q, double* conf, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (B < 0 || R < 1 || K < 1 || Q < 1 || !shots || (B > 0 && (!counts || !deltas || !conf)))
+    return fail(QT_ERR_ARG, "qt_polytope_confidence: null array or bad sizes (B=%lld R=%d K=%d Q=%d)", B, R, K, Q);
+  PolyPlan p;
+  if (int r = poly_plan(R, K, &p)) return r;
+  if (int r = poly_check_shots(h, c, shots, R, "qt_polytope_confidence")) return r;
+  if (B == 0) return 0;
+  const long long RK = (long long)R * K;
+  if (B > kPolyMaxUnits / Q || B > kPolyMaxCounts / RK)
+    return fail(QT_ERR_UNSUPPORTED, "qt_polytope_confidence: B x Q = %lld x %d (R K = %lld) is too large for one call", B, Q, RK);
+  const long long units = B * Q, wave_grid = p.wave ? (units + 4 * (64 / p.TS) - 1) / (4 * (64 / p.TS)) : 0;
+  const int64_t* dc;
+  const double *dn, *dd;
+  double* dconf;
+  if (int r = c.in(counts, (size_t)(B * RK), &dc)) return r;
+  if (int r = c.in(shots, (size_t)R, &dn)) return r;
+  if (int r = c.in(deltas, (size_t)units, &dd)) return r;
+  if (int r = c.out(conf, (size_t)units, &dconf)) return r;
+  const int rl = poly_dispatch(
+      p,
+      [&] {
+        return launch(h, qt::k_polytope_confidence_wave, dim3((unsigned)wave_grid), dim3(256), 0, dc, B, R, K, p.kshift, p.TS,
+                      dn, dd, Q, dconf);
+      },
+      [&](auto nt, auto mode) {
+        constexpr int NT = decltype(nt)::value, MODE = decltype(mode)::value;
+        return launch(h, qt::k_polytope_confidence<NT, MODE>, dim3((unsigned)std::min(B, kPolyMaxGrid)), dim3(NT), p.lds, dc, B,
+                      p.sh, dn, dd, Q, dconf);
+      });
+  if (rl) return rl;
+  return c.done();
+}
+
+int qt_polytope_coverage(qt_handle_t* h, const int64_t* counts, long long B, int R, int K, const double* shots,
+                         const double* levels, int L, const double* truth, int clip_b, double* deltas, uint8_t* hits,
+                         long long* covered, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (B < 0 || R < 1 || K < 1 || L < 1 || !shots || !levels || (B > 0 && !counts) || (!deltas && !hits && !covered) ||
+      ((hits || covered) && !truth))
+    return fail(QT_ERR_ARG, "qt_polytope_coverage: null array or bad sizes (B=%lld R=%d K=%d L=%d)", B, R, K, L);
+  PolyPlan p;
+  if (int r = poly_plan(R, K, &p)) return r;
+  if (int r = poly_check_shots(h, c, shots, R, "qt_polytope_coverage")) return r;
+  if (B == 0) return 0;
+  const long long RK = (long long)R * K;
+  if (B > kPolyMaxUnits / L || B > kPolyMaxCounts / RK)
+    return fail(QT_ERR_UNSUPPORTED, "qt_polytope_coverage: B x L = %lld x %d (R K = %lld) is too large for one call", B, L, RK);
+  const long long units = B * L, wave_grid = p.wave ? (units + 4 * (64 / p.TS) - 1) / (4 * (64 / p.TS)) : 0;
+  const int64_t* dc;
+  const double *dn, *dl, *dt;
+  double* dd;
+  uint8_t* dh;
+  long long* dcov = nullptr;
+  if (int r = c.in(counts, (size_t)(B * RK), &dc)) return r;
+  if (int r = c.in(shots, (size_t)R, &dn)) return r;
+  if (int r = c.in(levels, (size_t)L, &dl)) return r;
+  if (int r = c.in(truth, (size_t)RK, &dt)) return r;
+  if (int r = c.out(deltas, (size_t)units, &dd)) return r;
+  if (int r = c.out(hits, (size_t)units, &dh)) return r;
+  if (covered) {
+    if (int r = c.inout(covered, (size_t)L, &dcov)) return r;
+    if (!dh) {
+      HIPCHK(h->poly_ws.ensure((size_t)units));
+      dh = h->poly_ws.as<uint8_t>();
+    }
+  }
+  const int rl = poly_dispatch(
+      p,
+      [&] {
+        return launch(h, qt::k_polytope_coverage_wave, dim3((unsigned)wave_grid), dim3(256), 0, dc, B, R, K, p.kshift, p.TS, dn,
+                      dl, L, dt, clip_b, dd, dh);
+      },
+      [&](auto nt, auto mode) {
+        constexpr int NT = decltype(nt)::value, MODE = decltype(mode)::value;
+        return launch(h, qt::k_polytope_coverage<NT, MODE>, dim3((unsigned)std::min(B, kPolyMaxGrid)), dim3(NT), p.lds, dc, B,
+                      p.sh, dn, dl, L, dt, clip_b, dd, dh);
+      });
+  if (rl) return rl;
+  // one workgroup per level counts its column of hits and adds it to covered[l]: no contended atomics
+  if (covered)
+    if (int r = launch(h, qt::k_polytope_count, dim3(L), dim3(256), 0, (const uint8_t*)dh, B, L, dcov)) return r;
+  return c.done();
 }
 
 // ---- a4 / a12 / a16 host side: state.py:109-114, the draws of experiment() (qt_sampler.h) ---------

@@ -659,6 +659,91 @@ class Engine:
                                             _ptr(status), _ptr(iters), _capi.QT_HOST_PTR))
         return (obj, status, iters, x) if return_x else (obj, status, iters)
 
+    # ---- f4: polytopes/utils.py, verification.py ---------------------------------------------------------
+    @staticmethod
+    def _polytope_tables(counts, shots):
+        """counts (B, R, K) / (B, D, S, K) (NumPy or an int64 torch CUDA tensor), shots (R,) or (S,) (repeated over the
+        leading table axes, as utils.py:11 broadcasts them) -> (counts, B, R, K, shots (R,) float64 on the host)."""
+        if not _is_dev(counts):
+            counts = _i64(counts)
+        if counts.ndim < 3:
+            raise ValueError("counts must be (trials, settings, outcomes) or (trials, inputs, settings, outcomes)")
+        b, k = int(counts.shape[0]), int(counts.shape[-1])
+        r = 1
+        for s in counts.shape[1:-1]:
+            r *= int(s)
+        shots = _f64(np.atleast_1d(shots))
+        if shots.ndim != 1 or shots.size == 0 or r % shots.size:
+            raise ValueError("one shot number per setting")
+        return counts, b, r, k, _f64(np.tile(shots, r // shots.size))
+
+    def polytope_confidence(self, counts, shots, deltas):
+        """count_confidence (reference polytopes/utils.py:4-13) of every trial at every widening
+        (qt_polytope_confidence): counts (B, R, K) or (B, D, S, K), shots (R,) or (S,), deltas (B, Q) or (Q,) (the same
+        for every trial) -> conf (B, Q)."""
+        c, b, r, k, n = self._polytope_tables(counts, shots)
+        if _is_dev(c):
+            raise TypeError("polytope_confidence takes NumPy arrays")
+        d = _f64(deltas)
+        if d.ndim == 1:
+            d = _f64(np.broadcast_to(d, (b, d.size)))
+        assert d.ndim == 2 and d.shape[0] == b
+        conf = np.empty(d.shape)
+        self._chk(self.lib.qt_polytope_confidence(self._h, _ptr(c), b, r, k, _ptr(n), _ptr(d), d.shape[1], _ptr(conf),
+                                                  _capi.QT_HOST_PTR))
+        return conf
+
+    def polytope_coverage(self, counts, shots, levels, truth=None, clip_b=True, return_deltas=False, return_hits=False,
+                          covered=None):
+        """The coverage study of the confidence polytope over a batch of trials (qt_polytope_coverage; reference
+        polytopes/verification.py): delta = count_delta(level) per (trial, level) and, with `truth` (R K true outcome
+        probabilities), whether the polytope widened by delta holds the truth (clip_b: test_qst's clipped bound; False:
+        test_qpt's).  -> covered (L,) int64, the number of covering trials per level (None without truth); then
+        deltas (B, L) and hits (B, L) bool where asked for.  `covered`: an int64 array from earlier chunks to add to.
+        counts may be an int64 torch CUDA tensor (the device sampler's): the trials then never visit the host."""
+        c, b, r, k, n = self._polytope_tables(counts, shots)
+        lv = _f64(np.atleast_1d(levels))
+        n_lv = lv.size
+        if truth is None and (return_hits or covered is not None):
+            raise ValueError("hits and covered need the true outcome probabilities")
+        return_deltas = return_deltas or truth is None  # without truth the deltas are all there is to return
+        t = None if truth is None else _f64(np.ravel(truth))
+        if t is not None and t.size != r * k:
+            raise ValueError("truth must hold one probability per table entry")
+        cov = None
+        if t is not None:
+            cov = np.zeros(n_lv, dtype=np.int64) if covered is None else np.ascontiguousarray(covered, dtype=np.int64).copy()
+            assert cov.shape == (n_lv,)
+        if _is_dev(c):
+            import torch
+
+            self._dev_call()
+            dev = c.device
+            assert c.dtype == torch.int64 and c.is_contiguous()
+            to = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
+            n_d, lv_d, t_d, cov_d = to(n), to(lv), to(t), to(cov)
+            dl_d = torch.empty((b, n_lv), dtype=torch.float64, device=dev) if return_deltas else None
+            h_d = torch.empty((b, n_lv), dtype=torch.uint8, device=dev) if return_hits else None
+            self._chk(self.lib.qt_polytope_coverage(self._h, _ptr(c), b, r, k, _ptr(n_d), _ptr(lv_d), n_lv, _ptr(t_d),
+                                                    int(bool(clip_b)), _ptr(dl_d), _ptr(h_d), _ptr(cov_d), _capi.QT_DEVICE_PTR))
+            self.sync()
+            cov = None if cov_d is None else cov_d.cpu().numpy()
+            dl = None if dl_d is None else dl_d.cpu().numpy()
+            hits = None if h_d is None else h_d.cpu().numpy()
+        else:
+            dl = np.empty((b, n_lv)) if return_deltas else None
+            hits = np.empty((b, n_lv), dtype=np.uint8) if return_hits else None
+            self._chk(self.lib.qt_polytope_coverage(self._h, _ptr(c), b, r, k, _ptr(n), _ptr(lv), n_lv, _ptr(t),
+                                                    int(bool(clip_b)), _ptr(dl), _ptr(hits), _ptr(cov), _capi.QT_HOST_PTR))
+        if t is None:
+            return dl
+        res = (cov,)
+        if return_deltas:
+            res += (dl,)
+        if return_hits:
+            res += (hits.astype(bool),)
+        return res[0] if len(res) == 1 else res
+
     def sort_dev(self, x):
         """`x.sort()` in place for a float64 torch CUDA tensor (qt_sort_f64; NaN last like np.sort); asynchronous.  The
         result is np.sort's by value, written canonically: -0.0 as +0.0 and every NaN as 0x7ff8000000000000."""
