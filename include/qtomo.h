@@ -252,6 +252,17 @@ enum qt_lp_status {
 int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                      double* obj, double* x, int32_t* status, int32_t* iters, int flags);
 
+/* The same programs, arguments, statuses and return value for 1 <= N <= 255 (csrc/qt_lp_large.h): the polytope of a
+ * two-qubit process (reference interval.py:338-418, N = 16^2 - 16 = 240) and of a four-qubit state (N = 255).  The
+ * normal matrix (up to 256 x 256) lives in a per-workgroup slice of a global workspace (0.5 MB + 7 M doubles per
+ * workgroup, at most 256 MB in all) and is factored by a blocked Cholesky in which a pivot not above 1e-11 of its
+ * diagonal entry of H is replaced by that entry: without this the iteration breaks down on most polytope programs of
+ * this size shortly before it converges.  N > 255 is QT_ERR_UNSUPPORTED, and so is an M whose seven M-vectors do not
+ * fit the 256 MB beside one normal matrix (M > 4.7 million).  For N <= 64 both entry points accept the
+ * program; their results agree to the solver's tolerance, not bit for bit (the sums run in another order). */
+int qt_lp_ineq_large_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                           double* obj, double* x, int32_t* status, int32_t* iters, int flags);
+
 /* ---- f4: quantpy/tomography/polytopes (the coverage study of arXiv:2109.04734, Fig. 1) over a batch of trials ------
  * A trial is a count table counts[b][R][K] with shots[r] per setting (for a process the output tomographs are stacked,
  * R = inputs x settings, and shots repeats the first tomograph's, as utils.py:11 broadcasts them);

@@ -18,6 +18,7 @@
 #include "../../include/qtomo.h"
 #include "qt_large.h"
 #include "qt_lp.h"
+#include "qt_lp_large.h"
 #include "qt_ops.h"
 #include "qt_polytope.h"
 #include "qt_process.h"
@@ -106,6 +107,7 @@ struct qt_handle {
   DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project64)
   DevBuf gram;  // qt_moment_batch: P^T P
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
+  DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
@@ -1545,6 +1547,41 @@ int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double
   HIPCHK(h->lp_ws.ensure((size_t)grid * per_wg));
   hipLaunchKernelGGL(qt::k_lp_ineq, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj, dx, dst,
                      dit, h->lp_ws.as<double>());
+  return c.done(status, (int)P);
+}
+
+// The same programs for 65 ... 255 variables (qt_lp_large.h): the normal matrix lives in the workspace, not in LDS.
+int qt_lp_ineq_large_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                           double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (!A || !C || !b || !obj || !status) return fail(QT_ERR_ARG, "qt_lp_ineq_large_batch: null array");
+  if (N < 1 || M < N || O < 1 || R < 1)
+    return fail(QT_ERR_ARG, "qt_lp_ineq_large_batch: bad sizes (M=%d N=%d O=%d R=%d)", M, N, O, R);
+  if (N > qt::kLgMaxN)
+    return fail(QT_ERR_UNSUPPORTED, "qt_lp_ineq_large_batch supports up to %d variables (got %d)", qt::kLgMaxN, N);
+  const long long P = (long long)R * O;
+  if (P > (1LL << 30)) return fail(QT_ERR_ARG, "qt_lp_ineq_large_batch: too many programs (%lld)", P);
+  const double *dA, *dC, *db;
+  double *dobj, *dx;
+  int32_t *dst, *dit;
+  if (int r = c.in(A, (size_t)M * N, &dA)) return r;
+  if (int r = c.in(C, (size_t)O * N, &dC)) return r;
+  if (int r = c.in(b, (size_t)R * M, &db)) return r;
+  if (int r = c.out(obj, (size_t)P, &dobj)) return r;
+  if (int r = c.out(x, (size_t)P * N, &dx)) return r;
+  if (int r = c.out(status, (size_t)P, &dst)) return r;
+  if (int r = c.out(iters, (size_t)P, &dit)) return r;
+  // persistent workgroups: at most 2048, and at most 256 MB of workspace (about 0.6 MB each: about 400 workgroups)
+  const size_t per_wg = (qt::kLgHDoubles + (size_t)qt::kLgWs * M) * sizeof(double);
+  long long grid = P < 2048 ? P : 2048;
+  const long long by_ws = (long long)((256u << 20) / per_wg);
+  if (by_ws < 1)
+    return fail(QT_ERR_UNSUPPORTED, "qt_lp_ineq_large_batch: M = %d needs more than 256 MB of workspace per program", M);
+  if (grid > by_ws) grid = by_ws;
+  HIPCHK(h->lp_large_ws.ensure((size_t)grid * per_wg));
+  hipLaunchKernelGGL(qt::k_lp_ineq_large, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj,
+                     dx, dst, dit, h->lp_large_ws.as<double>());
   return c.done(status, (int)P);
 }
 

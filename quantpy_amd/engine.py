@@ -645,6 +645,32 @@ class Engine:
         """min C[o] . x subject to A x <= b[r] for every r, o (qt_lp_ineq_batch): A (M, N), C (O, N), b (R, M) ->
         (obj (R, O), status (R, O), iters (R, O)[, x (R, O, N)]).  status: _capi.LP_* (obj +inf when infeasible, -inf
         when unbounded, NaN when not converged).  N <= 64."""
+        return self._lp_call(self.lib.qt_lp_ineq_batch, A, C, b, return_x)
+
+    def lp_ineq_large_batch(self, A, C, b, return_x=False):
+        """lp_ineq_batch for 1 <= N <= 255 variables (qt_lp_ineq_large_batch): the same arguments and results.  The
+        normal matrix lives in global memory, the sums run in another order and a vanishing Cholesky pivot is replaced
+        instead of ending the program, so at N <= 64 the two agree to the solver's tolerance, not bit for bit."""
+        return self._lp_call(self.lib.qt_lp_ineq_large_batch, A, C, b, return_x)
+
+    def _lp_ineq_by_size(self, A, C, b, return_x=False):
+        """The LP kernel for this number of variables -> (lp_ineq_batch's tuple, resolved).  N <= 64 keeps
+        lp_ineq_batch and its bits; a right-hand side with a program that it leaves NOT_CONVERGED (its plain Cholesky
+        breaks down near a degenerate optimum, e.g. the polytope programs of a pure target state) is solved again by
+        lp_ineq_large_batch, whose factorisation replaces a vanishing pivot, and takes that kernel's results for all
+        its objectives.  resolved (R,) bool marks those right-hand sides (all True above 64 variables: the large
+        kernel solved everything)."""
+        rhs = _f64(np.atleast_2d(b))
+        if np.shape(A)[1] > 64:
+            return self.lp_ineq_large_batch(A, C, rhs, return_x), np.ones(rhs.shape[0], dtype=bool)
+        res = self.lp_ineq_batch(A, C, rhs, return_x)
+        resolved = (res[1] == _capi.LP_NOT_CONVERGED).any(axis=1)
+        if resolved.any():
+            for old, new in zip(res, self.lp_ineq_large_batch(A, C, rhs[resolved], return_x)):
+                old[resolved] = new
+        return res, resolved
+
+    def _lp_call(self, fn, A, C, b, return_x):
         a = _f64(A)
         c = _f64(np.atleast_2d(C))
         rhs = _f64(np.atleast_2d(b))
@@ -655,8 +681,8 @@ class Engine:
         status = np.empty((r, o), dtype=np.int32)
         iters = np.empty((r, o), dtype=np.int32)
         x = np.empty((r, o, n)) if return_x else None
-        self._chk(self.lib.qt_lp_ineq_batch(self._h, _ptr(a), m, n, _ptr(c), o, _ptr(rhs), r, _ptr(obj), _ptr(x),
-                                            _ptr(status), _ptr(iters), _capi.QT_HOST_PTR))
+        self._chk(fn(self._h, _ptr(a), m, n, _ptr(c), o, _ptr(rhs), r, _ptr(obj), _ptr(x), _ptr(status), _ptr(iters),
+                     _capi.QT_HOST_PTR))
         return (obj, status, iters, x) if return_x else (obj, status, iters)
 
     # ---- f4: polytopes/utils.py, verification.py ---------------------------------------------------------

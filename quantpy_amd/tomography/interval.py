@@ -568,9 +568,14 @@ class PolytopeStateInterval(ConfidenceInterval):
 
     Deviation: a process tomograph raises NotImplementedError in __init__ (the reference raises it in setup)."""
 
+    _MAX_QUBITS, _MAX_VARIABLES = 3, 64  # polytopes.StateFidelityInterval goes to n = 4 on the second LP kernel
+
     def __init__(self, tmg, n_points=1000, target_state=None):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
-        _state_only(self, "PolytopeStateInterval")
+        _state_only(self, type(self).__name__)
+
+    def _lp(self, A, C, b):
+        return get_engine(self.tmg.state.n_qubits).lp_ineq_batch(A, C, b)
 
     def __call__(self, conf_levels=None):
         if conf_levels is None:
@@ -583,9 +588,9 @@ class PolytopeStateInterval(ConfidenceInterval):
         """(A, b (n_points, M), c, deltas, frequencies) of the reference's LPs (interval.py:297-316)."""
         tmg = self.tmg
         n_qubits = tmg.state.n_qubits
-        if n_qubits > 3:
-            raise NotImplementedError(f"PolytopeStateInterval supports n <= 3 qubits (4^n - 1 <= 64 LP variables); "
-                                      f"got n = {n_qubits}")
+        if n_qubits > self._MAX_QUBITS:
+            raise NotImplementedError(f"{type(self).__name__} supports n <= {self._MAX_QUBITS} qubits (4^n - 1 <= "
+                                      f"{self._MAX_VARIABLES} LP variables); got n = {n_qubits}")
         dim = 2**n_qubits
         shots = np.asarray(tmg.n_measurements, dtype=np.float64)
         frequencies = np.clip(np.asarray(tmg.results) / shots[:, None], self.EPS, 1 - self.EPS)
@@ -605,7 +610,7 @@ class PolytopeStateInterval(ConfidenceInterval):
             self.target_state = tmg.state
         dim = 2**tmg.state.n_qubits
         A, b, c, deltas, frequencies = self.programs()
-        obj, status, iters = get_engine(tmg.state.n_qubits).lp_ineq_batch(A, np.stack([c, -c]), b)
+        obj, status, iters = self._lp(A, np.stack([c, -c]), b)
         from .. import _capi
 
         bad = np.flatnonzero((status == _capi.LP_NOT_CONVERGED).any(axis=1))
@@ -620,17 +625,19 @@ class PolytopeStateInterval(ConfidenceInterval):
         self.cl_to_dist_max = interp1d(self.conf_levels, self.dist_max)
 
 
-def _needs_cvxopt(name, lines):
+def _needs_cvxopt(name, lines, see=""):
     def __init__(self, *args, **kwargs):
         raise NotImplementedError(f"{name} (reference interval.py:{lines}) poses a cone / linear program for cvxopt; "
-                                  "that solver is outside the tomography hot path and is not provided")
+                                  f"that solver is outside the tomography hot path and is not provided{see}")
 
     return type(name, (ConfidenceInterval,), {"__init__": __init__, "setup": lambda self: None,
-                                              "__doc__": f"Placeholder: the reference's {name} needs cvxopt."})
+                                              "__doc__": f"Placeholder: the reference's {name} needs cvxopt{see or '.'}"})
 
 
 MomentFidelityProcessInterval = _needs_cvxopt("MomentFidelityProcessInterval", "163-216")
-PolytopeProcessInterval = _needs_cvxopt("PolytopeProcessInterval", "338-418")
+PolytopeProcessInterval = _needs_cvxopt(
+    "PolytopeProcessInterval", "338-418",
+    ".  The same fidelity bounds, from the batched GPU LP solver, are quantpy_amd.tomography.polytopes.ProcessFidelityInterval.")
 
 
 class MHMCProcessInterval(ConfidenceInterval):
