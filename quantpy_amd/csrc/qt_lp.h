@@ -16,6 +16,9 @@
 // by the workspace (six M-vectors per workgroup: s, z, r_p and three temporaries, in global memory).  Every loop has a
 // bound: at most kLpCap iterations per phase, Cholesky and the row passes over fixed ranges.  Every branch that
 // contains a barrier depends only on values that are uniform over the workgroup (block reductions, LDS).
+//
+// The iteration (lp_phase) and the per-workgroup driver (lp_run) are templates: k_lp_ineq_large (qt_lp_large.h, up to
+// 255 variables) runs the same text on its own primitives.  A kernel supplies one struct of primitives (LpSmall here).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,7 +32,6 @@ constexpr int kLpMaxN = 64;  // variables; phase 1 adds t
 constexpr int kLpLD = 66;    // LDS row stride of the normal matrix (n <= 65)
 constexpr int kLpRB = 32;    // rows of A per LDS block while forming H
 constexpr int kLpCap = 100;  // iterations per phase
-constexpr int kLpWs = 6;     // M-vectors of global workspace per workgroup
 
 enum { LP_OPTIMAL = 0, LP_INFEASIBLE = 1, LP_UNBOUNDED = 2, LP_NOT_CONVERGED = 3, LP_FEASIBLE = 4 /* phase 1 only */ };
 
@@ -62,11 +64,11 @@ __device__ inline void lp_reduce(double (&v)[K], double* red) {
                : (red[k] + red[K + k]) + (red[2 * K + k] + red[3 * K + k]);
 }
 
-// a_i . y over the first N columns (+ the phase-1 column, which is -1 in every row)
-__device__ inline double lp_row_dot(const double* __restrict__ a, int N, const double* y, bool p1) {
+// a_i . y over the first N columns (the caller adds the phase-1 column, which is -1 in every row)
+__device__ inline double lp_row_dot(const double* __restrict__ a, int N, const double* y) {
   double acc = 0.0;
   for (int j = 0; j < N; ++j) acc = fma(a[j], y[j], acc);
-  return p1 ? acc - y[N] : acc;
+  return acc;
 }
 
 // sh.u[j] = sum_i A[i][j] v[i] (j < N), sh.u[N] = sum_i v[i]; v is global, written by other threads before the call
@@ -89,7 +91,7 @@ __device__ inline void lp_colsum(LpShared& sh, const double* __restrict__ A, int
 }
 
 // H = A^T diag(w) A for the first N columns, register-tiled 4 x 4 per thread over LDS row blocks of A
-__device__ inline void lp_normal(LpShared& sh, const double* __restrict__ A, int M, int N, const double* w) {
+__device__ __noinline__ void lp_normal(LpShared& sh, const double* __restrict__ A, int M, int N, const double* w) {
   const int t = threadIdx.x, tj = t >> 4, tk = t & 15;
   double acc[4][4] = {};
   for (int r0 = 0; r0 < M; r0 += kLpRB) {
@@ -163,19 +165,68 @@ __device__ inline void lp_ratio(double x, double dx, double* amin) {
   if (dx < 0.0) *amin = fmin(*amin, -x / dx);
 }
 
-// One phase of the interior-point method.  In: sh.y[0..n) (n = N + p1), sh.c[0..n), s, z (global, this LP's rows).
+// What differs between the kernels that run lp_phase / lp_run below is one struct P per kernel.  It holds A, M, N and
+// vec (the six M-vectors s, z, r_p, w, w2, w3 of this workgroup's workspace), names the kernel's LDS block (Shared: y,
+// dy, rd, u, c, red and what the primitives need) and supplies
+//   ws_doubles(M)         doubles of global workspace per workgroup,
+//   matvec(v), av(i, v)   make A v available / (A v)_i for the v of the last matvec, over the first N columns,
+//   colsum(sh, v, p1)     sh.u[j] = (A^T v)_j, and sh.u[N] = sum v (read in phase 1 only),
+//   factor(sh, w, p1)     H = A^T diag(w) A with the phase-1 border, then its Cholesky factor; false on a breakdown,
+//   full_rank(sh, w)      the same for the rank test: no border, a pivot below 1e-12 of its diagonal entry is a breakdown,
+//   solve(sh, n, v)       v <- H^{-1} v with the last factor.
+// The LDS block is an argument of its own, from the kernel down, and not a member: the compiler then knows in every
+// primitive that it is LDS, also in the ones it keeps as functions.  The members are forced inline (the struct never
+// exists in memory), and so are lp_phase and lp_run; lp_normal, lg_normal and lg_solve are kept out of line, which is
+// what the inliner chose before it was told: their register tiles are not live across the iteration.
+// k_lp_ineq's: the normal matrix in LDS, (A v)_i computed where it is read (no M-vector for it).
+struct LpSmall {
+  using Shared = LpShared;
+  const double* __restrict__ A;
+  int M, N;
+  double* vec;
+
+  __host__ __device__ static size_t ws_doubles(int M) { return (size_t)6 * M; }
+  __device__ LpSmall(const double* A, int M, int N, double* ws) : A(A), M(M), N(N), vec(ws) {}
+  __device__ __forceinline__ void matvec(const double*) const {}
+  __device__ __forceinline__ double av(int i, const double* v) const { return lp_row_dot(A + (size_t)i * N, N, v); }
+  __device__ __forceinline__ void colsum(LpShared& sh, const double* v, bool) const { lp_colsum(sh, A, M, N, v); }
+  __device__ __forceinline__ void normal(LpShared& sh, const double* w, bool p1) const {
+    const int t = threadIdx.x;
+    __syncthreads();  // w was written by other threads
+    lp_normal(sh, A, M, N, w);
+    if (p1) {
+      lp_colsum(sh, A, M, N, w);
+      if (t < N) sh.H[N * kLpLD + t] = -sh.u[t];
+      if (t == 64) sh.H[N * kLpLD + N] = sh.u[N];
+      __syncthreads();
+    }
+  }
+  __device__ __forceinline__ bool factor(LpShared& sh, const double* w, bool p1) const {
+    normal(sh, w, p1);
+    return lp_cholesky(sh, N + (p1 ? 1 : 0), 0.0);
+  }
+  __device__ __forceinline__ bool full_rank(LpShared& sh, const double* w) const {
+    normal(sh, w, false);
+    return lp_cholesky(sh, N, 1e-12);
+  }
+  __device__ __forceinline__ void solve(LpShared& sh, int n, double* v) const { lp_solve(sh, n, v); }
+};
+
+// One phase of the interior-point method, for both kernels: every tolerance and test of the method is here and in
+// lp_run, nowhere else in device code.  In: sh.y[0..n) (n = N + p1), sh.c[0..n), s, z (global, this LP's rows).
 // Returns LP_FEASIBLE (phase 1: x strictly feasible), LP_INFEASIBLE (phase 1 converged), LP_OPTIMAL, LP_UNBOUNDED or
-// LP_NOT_CONVERGED.
-__device__ int lp_phase(LpShared& sh, const double* __restrict__ A, int M, int N, bool p1, const double* __restrict__ b,
-                        double* s, double* z, double* rp, double* w, double* w2, double* w3, double amax, double bn,
-                        double cn, int* iters) {
+// LP_NOT_CONVERGED.  On LP_FEASIBLE the last matvec was of sh.y.
+template <class P>
+__device__ __forceinline__ int lp_phase(typename P::Shared& sh, const P& p, bool p1, const double* __restrict__ b, double amax, double bn, double cn, int* iters) {
   constexpr double kTol = 1e-10;
-  const int t = threadIdx.x, n = N + (p1 ? 1 : 0);
+  const int t = threadIdx.x, M = p.M, N = p.N, n = N + (p1 ? 1 : 0);
+  double *s = p.vec, *z = s + M, *rp = z + M, *w = rp + M, *w2 = w + M, *w3 = w2 + M;
   for (int it = 0; it < kLpCap; ++it) {
     // ---- residuals and stopping tests
+    p.matvec(sh.y);
     double sums[2] = {0.0, 0.0}, maxs[2] = {0.0, -INFINITY};  // s.z, sum z | max|r_p|, max(A x - b)
     for (int i = t; i < M; i += kLpNT) {
-      const double ax = lp_row_dot(A + (size_t)i * N, N, sh.y, false);  // phase 2 starts from s = b - ax, bit for bit
+      const double ax = p.av(i, sh.y);  // phase 2 starts from s = b - ax, bit for bit
       const double r = (p1 ? ax - sh.y[N] : ax) + s[i] - b[i];
       rp[i] = r;
       sums[0] = fma(s[i], z[i], sums[0]);
@@ -185,7 +236,7 @@ __device__ int lp_phase(LpShared& sh, const double* __restrict__ A, int M, int N
     }
     lp_reduce<2, false>(sums, sh.red);
     lp_reduce<2, true>(maxs, sh.red);
-    lp_colsum(sh, A, M, N, z);
+    p.colsum(sh, z, p1);
     double ynorm = 0.0, pobj = 0.0, dres = 0.0;
     for (int j = 0; j < n; ++j) {
       ynorm += fabs(sh.y[j]);
@@ -209,27 +260,21 @@ __device__ int lp_phase(LpShared& sh, const double* __restrict__ A, int M, int N
 
     // ---- normal matrix and its factor
     for (int i = t; i < M; i += kLpNT) w[i] = z[i] / s[i];
-    __syncthreads();
-    lp_normal(sh, A, M, N, w);
-    if (p1) {
-      lp_colsum(sh, A, M, N, w);
-      if (t < N) sh.H[N * kLpLD + t] = -sh.u[t];
-      if (t == 64) sh.H[N * kLpLD + N] = sh.u[N];
-      __syncthreads();
-    }
-    if (!lp_cholesky(sh, n, 0.0)) return LP_NOT_CONVERGED;
+    if (!p.factor(sh, w, p1)) return LP_NOT_CONVERGED;
 
     // ---- predictor: r_sz = s z
     for (int i = t; i < M; i += kLpNT) w[i] = z[i] - z[i] * rp[i] / s[i];
-    lp_colsum(sh, A, M, N, w);
+    p.colsum(sh, w, p1);
     if (t < n) sh.dy[t] = -sh.rd[t] + (t < N ? sh.u[t] : -sh.u[N]);
     __syncthreads();
-    lp_solve(sh, n, sh.dy);
+    p.solve(sh, n, sh.dy);
+    p.matvec(sh.dy);
     double al[2] = {-1.0, -1.0};  // -(largest primal / dual step), as a max
     {
       double ap = INFINITY, ad = INFINITY;
       for (int i = t; i < M; i += kLpNT) {
-        const double ds = -rp[i] - lp_row_dot(A + (size_t)i * N, N, sh.dy, p1);
+        const double ady = p.av(i, sh.dy);
+        const double ds = -rp[i] - (p1 ? ady - sh.dy[N] : ady);
         const double dz = -z[i] - z[i] * ds / s[i];
         w2[i] = ds;
         w3[i] = dz;
@@ -251,14 +296,16 @@ __device__ int lp_phase(LpShared& sh, const double* __restrict__ A, int M, int N
       w2[i] = rsz;
       w[i] = (rsz - z[i] * rp[i]) / s[i];
     }
-    lp_colsum(sh, A, M, N, w);
+    p.colsum(sh, w, p1);
     if (t < n) sh.dy[t] = -sh.rd[t] + (t < N ? sh.u[t] : -sh.u[N]);
     __syncthreads();
-    lp_solve(sh, n, sh.dy);
+    p.solve(sh, n, sh.dy);
+    p.matvec(sh.dy);
     {
       double ap = INFINITY, ad = INFINITY;
       for (int i = t; i < M; i += kLpNT) {
-        const double ds = -rp[i] - lp_row_dot(A + (size_t)i * N, N, sh.dy, p1);
+        const double ady = p.av(i, sh.dy);
+        const double ds = -rp[i] - (p1 ? ady - sh.dy[N] : ady);
         const double dz = (-w2[i] - z[i] * ds) / s[i];
         rp[i] = ds;
         w3[i] = dz;
@@ -280,26 +327,23 @@ __device__ int lp_phase(LpShared& sh, const double* __restrict__ A, int M, int N
   return LP_NOT_CONVERGED;
 }
 
-// grid: persistent workgroups over the R * O programs; ws: gridDim.x * kLpWs * M doubles
-__global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A, int M, int N,
-                                                   const double* __restrict__ C, int O, const double* __restrict__ bb,
-                                                   int R, double* __restrict__ obj, double* __restrict__ xout,
-                                                   int32_t* __restrict__ status, int32_t* __restrict__ iters,
-                                                   double* __restrict__ ws) {
-  __shared__ LpShared sh;
-  const int t = threadIdx.x;
-  double* s = ws + (size_t)blockIdx.x * kLpWs * M;
-  double *z = s + M, *rp = z + M, *w = rp + M, *w2 = w + M, *w3 = w2 + M;
+// One workgroup of either kernel, persistent over the R * O programs: rank test, then for every program the phase-1
+// start, the hand-over to phase 2 and the write-out.
+template <class P>
+__device__ __forceinline__ void lp_run(typename P::Shared& sh, const P& p, const double* __restrict__ C, int O, const double* __restrict__ bb, int R,
+                       double* __restrict__ obj, double* __restrict__ xout, int32_t* __restrict__ status,
+                       int32_t* __restrict__ iters) {
+  const int t = threadIdx.x, M = p.M, N = p.N;
+  const double* __restrict__ A = p.A;
+  double *s = p.vec, *z = s + M, *w = z + 2 * M;
   // max |A|: the scale of the rounding in A y and A^T z
   double amax[1] = {0.0};
   for (size_t e = t; e < (size_t)M * N; e += kLpNT) amax[0] = fmax(amax[0], fabs(A[e]));
   lp_reduce<1, true>(amax, sh.red);
   // rank test, once: a pivot of the Cholesky factor of A^T A below 1e-12 of its diagonal entry (cond(A) above ~1e6)
-  // is a breakdown, and every program of the batch reports NOT_CONVERGED
+  // is a breakdown, and every program of the batch reports NOT_CONVERGED (no pivot is replaced here: that would hide it)
   for (int i = t; i < M; i += kLpNT) w[i] = 1.0;
-  __syncthreads();
-  lp_normal(sh, A, M, N, w);
-  const bool full_rank = lp_cholesky(sh, N, 1e-12);
+  const bool full_rank = p.full_rank(sh, w);
   for (int lp = blockIdx.x; lp < R * O; lp += gridDim.x) {
     const int r = lp / O, o = lp % O;
     const double* b = bb + (size_t)r * M;
@@ -324,13 +368,13 @@ __global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A,
       z[i] = 1.0 / M;
     }
     __syncthreads();
-    if (full_rank) st = lp_phase(sh, A, M, N, true, b, s, z, rp, w, w2, w3, amax[0], bn, 1.0, &it);
+    if (full_rank) st = lp_phase(sh, p, true, b, amax[0], bn, 1.0, &it);
     if (st == LP_FEASIBLE) {
-      // phase 2 from the strictly feasible x: s = b - A x, z = mean(s) / s
+      // phase 2 from the strictly feasible x: s = b - A x (the A x of phase 1's last matvec), z = mean(s) / s
       double cm[1] = {0.0}, ssum[1] = {0.0};
       for (int j = t; j < N; j += kLpNT) cm[0] = fmax(cm[0], fabs(c[j]));
       for (int i = t; i < M; i += kLpNT) {
-        s[i] = b[i] - lp_row_dot(A + (size_t)i * N, N, sh.y, false);
+        s[i] = b[i] - p.av(i, sh.y);
         ssum[0] += s[i];
       }
       lp_reduce<1, true>(cm, sh.red);
@@ -339,7 +383,7 @@ __global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A,
       for (int i = t; i < M; i += kLpNT) z[i] = smean / s[i];
       if (t < N) sh.c[t] = c[t];
       __syncthreads();
-      st = lp_phase(sh, A, M, N, false, b, s, z, rp, w, w2, w3, amax[0], bn, fmax(1.0, cm[0]), &it);
+      st = lp_phase(sh, p, false, b, amax[0], bn, fmax(1.0, cm[0]), &it);
     }
     if (t == 0) {
       double val = NAN;
@@ -358,6 +402,16 @@ __global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A,
     if (xout && t < N) xout[(size_t)lp * N + t] = sh.y[t];
     __syncthreads();  // sh.y / sh.c are rewritten by the next program
   }
+}
+
+// grid: persistent workgroups over the R * O programs; ws: gridDim.x * LpSmall::ws_doubles(M) doubles
+__global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A, int M, int N,
+                                                   const double* __restrict__ C, int O, const double* __restrict__ bb,
+                                                   int R, double* __restrict__ obj, double* __restrict__ xout,
+                                                   int32_t* __restrict__ status, int32_t* __restrict__ iters,
+                                                   double* __restrict__ ws) {
+  __shared__ LpShared sh;
+  lp_run(sh, LpSmall(A, M, N, ws + blockIdx.x * LpSmall::ws_doubles(M)), C, O, bb, R, obj, xout, status, iters);
 }
 
 }  // namespace qt

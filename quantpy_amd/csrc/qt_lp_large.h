@@ -3,10 +3,9 @@
 //     for r < R, o < O:  minimise C[o] . x  subject to  A x <= b[r],  x in R^N free   (N <= 255, any M >= N)
 //
 // The programs are the process polytope of PolytopeProcessInterval at n = 2 (reference interval.py:338-418; A is
-// 576 x 240 with 'sic' inputs and 'proj-set') and the state polytope at n = 4 (1296 x 255).  The iteration is qt_lp.h's,
-// statement for statement: Mehrotra predictor-corrector on the normal equations, phase 1 on min t, A x - t 1 <= b up to
-// the first strictly feasible x, the same stopping, Farkas and unbounded tests, kLpCap iterations per phase.  What is
-// different:
+// 576 x 240 with 'sic' inputs and 'proj-set') and the state polytope at n = 4 (1296 x 255).  The iteration and the
+// per-workgroup driver are qt_lp.h's lp_phase and lp_run, the same text for both kernels; this file holds the primitives
+// they run on here and the struct (LpLarge) that hands them over.  What the primitives do differently:
 //
 //   * The normal matrix (n x n, n <= 256 with the phase-1 column) does not fit LDS.  It lives in this workgroup's slice
 //     of a global workspace (512 KB: it stays in L2 / Infinity Cache), row stride kLgLD.
@@ -40,7 +39,6 @@ constexpr int kLgLD = 256;        // row stride of the normal matrix in global m
 constexpr int kLgRB = 16;         // rows of A per LDS block while forming H
 constexpr int kLgNB = 32;         // Cholesky panel width
 constexpr int kLgDS = kLgNB + 1;  // LDS row stride of a panel / diagonal block
-constexpr int kLgWs = 7;          // M-vectors of global workspace per workgroup (after the normal matrix)
 constexpr double kLgPivot = 1e-11;  // a pivot not above this fraction of its diagonal entry is replaced
 constexpr size_t kLgHDoubles = (size_t)kLgLD * kLgLD;
 
@@ -181,7 +179,7 @@ __device__ inline void lg_normal_pass(LgShared& sh, const double* __restrict__ A
 #undef QT_LG_FMA
 #undef QT_LG_OUT
 
-__device__ inline void lg_normal(LgShared& sh, const double* __restrict__ A, int M, int N, bool p1, const double* w,
+__device__ __noinline__ void lg_normal(LgShared& sh, const double* __restrict__ A, int M, int N, bool p1, const double* w,
                                  double* __restrict__ H) {
   const int n = N + (p1 ? 1 : 0);
   lg_normal_pass<0>(sh, A, M, N, n, p1, w, H);
@@ -282,7 +280,7 @@ __device__ inline bool lg_cholesky(LgShared& sh, double* H, int n, double rel, b
 }
 
 // v <- (L L^T)^{-1} v for the factor in H; v is in LDS, written before the caller's last barrier
-__device__ inline void lg_solve(LgShared& sh, const double* H, int n, double* v) {
+__device__ __noinline__ void lg_solve(LgShared& sh, const double* H, int n, double* v) {
   const int t = threadIdx.x, lane = t & 63;
   const int nblk = (n + kLgNB - 1) / kLgNB;
   for (int kb = 0; kb < nblk; ++kb) {
@@ -337,195 +335,43 @@ __device__ inline void lg_solve(LgShared& sh, const double* H, int n, double* v)
   }
 }
 
-// One phase of the interior-point method: lp_phase of qt_lp.h on the primitives above.  ax is the seventh M-vector.
-__device__ int lg_phase(LgShared& sh, const double* __restrict__ A, int M, int N, bool p1, const double* __restrict__ b,
-                        double* H, double* s, double* z, double* rp, double* w, double* w2, double* w3, double* ax,
-                        double amax, double bn, double cn, int* iters) {
-  constexpr double kTol = 1e-10;
-  const int t = threadIdx.x, n = N + (p1 ? 1 : 0);
-  for (int it = 0; it < kLpCap; ++it) {
-    // ---- residuals and stopping tests
-    lg_matvec(A, M, N, sh.y, ax);
-    __syncthreads();
-    double sums[2] = {0.0, 0.0}, maxs[2] = {0.0, -INFINITY};  // s.z, sum z | max|r_p|, max(A x - b)
-    for (int i = t; i < M; i += kLpNT) {
-      const double r = (p1 ? ax[i] - sh.y[N] : ax[i]) + s[i] - b[i];
-      rp[i] = r;
-      sums[0] = fma(s[i], z[i], sums[0]);
-      sums[1] += z[i];
-      maxs[0] = fmax(maxs[0], fabs(r));
-      maxs[1] = fmax(maxs[1], ax[i] - b[i]);
-    }
-    lp_reduce<2, false>(sums, sh.red);
-    lp_reduce<2, true>(maxs, sh.red);
-    lg_colsum(sh, A, M, N, z, p1);
-    double ynorm = 0.0, pobj = 0.0, dres = 0.0;
-    for (int j = 0; j < n; ++j) {
-      ynorm += fabs(sh.y[j]);
-      pobj = fma(sh.c[j], sh.y[j], pobj);
-      const double rdj = (j < N ? sh.u[j] : -sh.u[N]) + sh.c[j];
-      dres = fmax(dres, fabs(rdj));
-    }
-    __syncthreads();
-    if (t < n) sh.rd[t] = (t < N ? sh.u[t] : -sh.u[N]) + sh.c[t];
-    __syncthreads();
-    *iters += 1;
-    const double gap = sums[0], mu = gap / M;
-    const double pres = maxs[0] / fmax(bn, amax * ynorm), dres_s = dres / fmax(cn, amax * sums[1]);
-    if (!isfinite(gap) || !isfinite(pres) || !isfinite(dres_s) || !isfinite(pobj)) return LP_NOT_CONVERGED;
-    if (p1 && maxs[1] < 0.0) return LP_FEASIBLE;
-    if (pres <= kTol && dres_s <= kTol && gap <= kTol * fmax(1.0, fabs(pobj))) return p1 ? LP_INFEASIBLE : LP_OPTIMAL;
-    if (p1 && pres <= kTol && dres_s <= kTol && pobj - gap > 1e-9 * fmax(1.0, fabs(pobj))) return LP_INFEASIBLE;
-    if (!p1 && pres <= 1e-8 && pobj < -1e10 * cn * bn) return LP_UNBOUNDED;
+// k_lp_ineq_large's primitives for lp_phase / lp_run (see LpSmall): the normal matrix at the head of the workgroup's
+// workspace, A v through a seventh M-vector behind the six of the iteration.
+struct LpLarge {
+  using Shared = LgShared;
+  const double* __restrict__ A;
+  int M, N;
+  double *H, *vec, *ax;
 
-    // ---- normal matrix and its factor
-    for (int i = t; i < M; i += kLpNT) w[i] = z[i] / s[i];
-    lg_normal(sh, A, M, N, p1, w, H);  // its first barrier orders the writes of w
-    if (!lg_cholesky(sh, H, n, kLgPivot, true)) return LP_NOT_CONVERGED;
-
-    // ---- predictor: r_sz = s z
-    for (int i = t; i < M; i += kLpNT) w[i] = z[i] - z[i] * rp[i] / s[i];
-    lg_colsum(sh, A, M, N, w, p1);
-    if (t < n) sh.dy[t] = -sh.rd[t] + (t < N ? sh.u[t] : -sh.u[N]);
-    __syncthreads();
-    lg_solve(sh, H, n, sh.dy);
-    lg_matvec(A, M, N, sh.dy, ax);
-    __syncthreads();
-    double al[2] = {-1.0, -1.0};  // -(largest primal / dual step), as a max
-    {
-      double ap = INFINITY, ad = INFINITY;
-      for (int i = t; i < M; i += kLpNT) {
-        const double ds = -rp[i] - (p1 ? ax[i] - sh.dy[N] : ax[i]);
-        const double dz = -z[i] - z[i] * ds / s[i];
-        w2[i] = ds;
-        w3[i] = dz;
-        lp_ratio(s[i], ds, &ap);
-        lp_ratio(z[i], dz, &ad);
-      }
-      al[0] = -fmin(1.0, ap);
-      al[1] = -fmin(1.0, ad);
-    }
-    lp_reduce<2, true>(al, sh.red);
-    double muaff[1] = {0.0};
-    for (int i = t; i < M; i += kLpNT) muaff[0] = fma(s[i] - al[0] * w2[i], z[i] - al[1] * w3[i], muaff[0]);
-    lp_reduce<1, false>(muaff, sh.red);
-    const double ratio = muaff[0] / M / mu, sigma_mu = ratio * ratio * ratio * mu;
-
-    // ---- corrector: r_sz = s z + ds_aff dz_aff - sigma mu  (kept in w2)
-    for (int i = t; i < M; i += kLpNT) {
-      const double rsz = s[i] * z[i] + w2[i] * w3[i] - sigma_mu;
-      w2[i] = rsz;
-      w[i] = (rsz - z[i] * rp[i]) / s[i];
-    }
-    lg_colsum(sh, A, M, N, w, p1);
-    if (t < n) sh.dy[t] = -sh.rd[t] + (t < N ? sh.u[t] : -sh.u[N]);
-    __syncthreads();
-    lg_solve(sh, H, n, sh.dy);
-    lg_matvec(A, M, N, sh.dy, ax);
-    __syncthreads();
-    {
-      double ap = INFINITY, ad = INFINITY;
-      for (int i = t; i < M; i += kLpNT) {
-        const double ds = -rp[i] - (p1 ? ax[i] - sh.dy[N] : ax[i]);
-        const double dz = (-w2[i] - z[i] * ds) / s[i];
-        rp[i] = ds;
-        w3[i] = dz;
-        lp_ratio(s[i], ds, &ap);
-        lp_ratio(z[i], dz, &ad);
-      }
-      al[0] = -ap;
-      al[1] = -ad;
-    }
-    lp_reduce<2, true>(al, sh.red);
-    const double ap = fmin(1.0, -0.99 * al[0]), ad = fmin(1.0, -0.99 * al[1]);
-    for (int i = t; i < M; i += kLpNT) {
-      s[i] = fma(ap, rp[i], s[i]);
-      z[i] = fma(ad, w3[i], z[i]);
-    }
-    if (t < n) sh.y[t] = fma(ap, sh.dy[t], sh.y[t]);
+  __host__ __device__ static size_t ws_doubles(int M) { return kLgHDoubles + (size_t)7 * M; }
+  __device__ LpLarge(const double* A, int M, int N, double* ws)
+      : A(A), M(M), N(N), H(ws), vec(ws + kLgHDoubles), ax(vec + (size_t)6 * M) {}
+  __device__ __forceinline__ void matvec(const double* v) const {
+    lg_matvec(A, M, N, v, ax);
     __syncthreads();
   }
-  return LP_NOT_CONVERGED;
-}
+  // phase 2 starts from the ax that phase 1's last matvec(sh.y) left here
+  __device__ __forceinline__ double av(int i, const double*) const { return ax[i]; }
+  __device__ __forceinline__ void colsum(LgShared& sh, const double* v, bool p1) const { lg_colsum(sh, A, M, N, v, p1); }
+  __device__ __forceinline__ bool factor(LgShared& sh, const double* w, bool p1) const {
+    lg_normal(sh, A, M, N, p1, w, H);  // its first barrier orders the writes of w
+    return lg_cholesky(sh, H, N + (p1 ? 1 : 0), kLgPivot, true);
+  }
+  __device__ __forceinline__ bool full_rank(LgShared& sh, const double* w) const {
+    lg_normal(sh, A, M, N, false, w, H);
+    return lg_cholesky(sh, H, N, 1e-12, false);
+  }
+  __device__ __forceinline__ void solve(LgShared& sh, int n, double* v) const { lg_solve(sh, H, n, v); }
+};
 
-// grid: persistent workgroups over the R * O programs; ws: gridDim.x * (kLgHDoubles + kLgWs * M) doubles
+// grid: persistent workgroups over the R * O programs; ws: gridDim.x * LpLarge::ws_doubles(M) doubles
 __global__ void __launch_bounds__(kLpNT) k_lp_ineq_large(const double* __restrict__ A, int M, int N,
                                                          const double* __restrict__ C, int O,
                                                          const double* __restrict__ bb, int R, double* __restrict__ obj,
                                                          double* __restrict__ xout, int32_t* __restrict__ status,
                                                          int32_t* __restrict__ iters, double* __restrict__ ws) {
   __shared__ LgShared sh;
-  const int t = threadIdx.x;
-  double* H = ws + (size_t)blockIdx.x * (kLgHDoubles + (size_t)kLgWs * M);
-  double* s = H + kLgHDoubles;
-  double *z = s + M, *rp = z + M, *w = rp + M, *w2 = w + M, *w3 = w2 + M, *ax = w3 + M;
-  // max |A|: the scale of the rounding in A y and A^T z
-  double amax[1] = {0.0};
-  for (size_t e = t; e < (size_t)M * N; e += kLpNT) amax[0] = fmax(amax[0], fabs(A[e]));
-  lp_reduce<1, true>(amax, sh.red);
-  // rank test, once: a pivot of the Cholesky factor of A^T A below 1e-12 of its diagonal entry is a breakdown, and
-  // every program of the batch reports NOT_CONVERGED (no pivot is replaced here: that would hide it)
-  for (int i = t; i < M; i += kLpNT) w[i] = 1.0;
-  lg_normal(sh, A, M, N, false, w, H);
-  const bool full_rank = lg_cholesky(sh, H, N, 1e-12, false);
-  for (int lp = blockIdx.x; lp < R * O; lp += gridDim.x) {
-    const int r = lp / O, o = lp % O;
-    const double* b = bb + (size_t)r * M;
-    const double* c = C + (size_t)o * N;
-    double bm[2] = {0.0, -INFINITY};  // max |b|, max(-b)
-    for (int i = t; i < M; i += kLpNT) {
-      bm[0] = fmax(bm[0], fabs(b[i]));
-      bm[1] = fmax(bm[1], -b[i]);
-    }
-    lp_reduce<2, true>(bm, sh.red);
-    const double bn = fmax(1.0, bm[0]);
-    int it = 0;
-    int st = LP_NOT_CONVERGED;
-    // phase 1 from x = 0, t0 = max(-b, 0) + 1: s = b + t0 >= 1, z = 1 / M (the dual's sum z = 1 holds)
-    const double t0 = fmax(bm[1], 0.0) + 1.0;
-    if (t <= N) {
-      sh.y[t] = (t == N) ? t0 : 0.0;
-      sh.c[t] = (t == N) ? 1.0 : 0.0;
-    }
-    for (int i = t; i < M; i += kLpNT) {
-      s[i] = b[i] + t0;
-      z[i] = 1.0 / M;
-    }
-    __syncthreads();
-    if (full_rank) st = lg_phase(sh, A, M, N, true, b, H, s, z, rp, w, w2, w3, ax, amax[0], bn, 1.0, &it);
-    if (st == LP_FEASIBLE) {
-      // phase 2 from the strictly feasible x (its A x is still in ax): s = b - A x, z = mean(s) / s
-      double cm[1] = {0.0}, ssum[1] = {0.0};
-      for (int j = t; j < N; j += kLpNT) cm[0] = fmax(cm[0], fabs(c[j]));
-      for (int i = t; i < M; i += kLpNT) {
-        s[i] = b[i] - ax[i];
-        ssum[0] += s[i];
-      }
-      lp_reduce<1, true>(cm, sh.red);
-      lp_reduce<1, false>(ssum, sh.red);
-      const double smean = ssum[0] / M;
-      for (int i = t; i < M; i += kLpNT) z[i] = smean / s[i];
-      if (t < N) sh.c[t] = c[t];
-      __syncthreads();
-      st = lg_phase(sh, A, M, N, false, b, H, s, z, rp, w, w2, w3, ax, amax[0], bn, fmax(1.0, cm[0]), &it);
-    }
-    if (t == 0) {
-      double val = NAN;
-      if (st == LP_OPTIMAL) {
-        val = 0.0;
-        for (int j = 0; j < N; ++j) val = fma(c[j], sh.y[j], val);
-      } else if (st == LP_INFEASIBLE) {
-        val = INFINITY;
-      } else if (st == LP_UNBOUNDED) {
-        val = -INFINITY;
-      }
-      obj[lp] = val;
-      status[lp] = st;
-      if (iters) iters[lp] = it;
-    }
-    if (xout && t < N) xout[(size_t)lp * N + t] = sh.y[t];
-    __syncthreads();  // sh.y / sh.c are rewritten by the next program
-  }
+  lp_run(sh, LpLarge(A, M, N, ws + blockIdx.x * LpLarge::ws_doubles(M)), C, O, bb, R, obj, xout, status, iters);
 }
 
 }  // namespace qt

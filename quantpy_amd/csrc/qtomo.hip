@@ -1519,16 +1519,21 @@ int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, 
   return c.done();
 }
 
-// ---- f3: interval.py:268-335, the LPs of PolytopeStateInterval (qt_lp.h) ---------------------------------------------
-int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
-                     double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
+// ---- f3: interval.py:268-335, the LPs of PolytopeStateInterval (qt_lp.h, qt_lp_large.h) --------------------------------
+// Both LP entries: `name` for the messages, at most max_n variables, per_wg bytes of workspace per workgroup in `ws`.
+// The large entry refuses a workgroup's workspace above 256 MB (refuse_ws); the small one then runs one workgroup.
+using LpKernel = void (*)(const double*, int, int, const double*, int, const double*, int, double*, double*, int32_t*,
+                          int32_t*, double*);
+static int lp_ineq_entry(qt_handle_t* h, const char* name, int max_n, size_t per_wg, bool refuse_ws, DevBuf qt_handle_t::*ws,
+                         LpKernel kernel, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                         double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
-  if (!A || !C || !b || !obj || !status) return fail(QT_ERR_ARG, "qt_lp_ineq_batch: null array");
-  if (N < 1 || M < N || O < 1 || R < 1) return fail(QT_ERR_ARG, "qt_lp_ineq_batch: bad sizes (M=%d N=%d O=%d R=%d)", M, N, O, R);
-  if (N > qt::kLpMaxN) return fail(QT_ERR_UNSUPPORTED, "qt_lp_ineq_batch supports up to %d variables (got %d)", qt::kLpMaxN, N);
+  if (!A || !C || !b || !obj || !status) return fail(QT_ERR_ARG, "%s: null array", name);
+  if (N < 1 || M < N || O < 1 || R < 1) return fail(QT_ERR_ARG, "%s: bad sizes (M=%d N=%d O=%d R=%d)", name, M, N, O, R);
+  if (N > max_n) return fail(QT_ERR_UNSUPPORTED, "%s supports up to %d variables (got %d)", name, max_n, N);
   const long long P = (long long)R * O;
-  if (P > (1LL << 30)) return fail(QT_ERR_ARG, "qt_lp_ineq_batch: too many programs (%lld)", P);
+  if (P > (1LL << 30)) return fail(QT_ERR_ARG, "%s: too many programs (%lld)", name, P);
   const double *dA, *dC, *db;
   double *dobj, *dx;
   int32_t *dst, *dit;
@@ -1539,50 +1544,30 @@ int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double
   if (int r = c.out(x, (size_t)P * N, &dx)) return r;
   if (int r = c.out(status, (size_t)P, &dst)) return r;
   if (int r = c.out(iters, (size_t)P, &dit)) return r;
-  // persistent workgroups: at most 2048, and at most 256 MB of workspace
-  const size_t per_wg = (size_t)qt::kLpWs * M * sizeof(double);
+  // persistent workgroups: at most 2048, and at most 256 MB of workspace (the large kernel takes about 0.6 MB each:
+  // about 400 workgroups)
   long long grid = P < 2048 ? P : 2048;
   const long long by_ws = (long long)((256u << 20) / per_wg);
+  if (by_ws < 1 && refuse_ws)
+    return fail(QT_ERR_UNSUPPORTED, "%s: M = %d needs more than 256 MB of workspace per program", name, M);
   if (grid > by_ws) grid = by_ws > 0 ? by_ws : 1;
-  HIPCHK(h->lp_ws.ensure((size_t)grid * per_wg));
-  hipLaunchKernelGGL(qt::k_lp_ineq, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj, dx, dst,
-                     dit, h->lp_ws.as<double>());
+  HIPCHK((h->*ws).ensure((size_t)grid * per_wg));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj, dx, dst, dit,
+                     (h->*ws).as<double>());
   return c.done(status, (int)P);
+}
+
+int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                     double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
+  return lp_ineq_entry(h, "qt_lp_ineq_batch", qt::kLpMaxN, qt::LpSmall::ws_doubles(M) * sizeof(double), false, &qt_handle_t::lp_ws,
+                       qt::k_lp_ineq, A, M, N, C, O, b, R, obj, x, status, iters, flags);
 }
 
 // The same programs for 65 ... 255 variables (qt_lp_large.h): the normal matrix lives in the workspace, not in LDS.
 int qt_lp_ineq_large_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                            double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (!A || !C || !b || !obj || !status) return fail(QT_ERR_ARG, "qt_lp_ineq_large_batch: null array");
-  if (N < 1 || M < N || O < 1 || R < 1)
-    return fail(QT_ERR_ARG, "qt_lp_ineq_large_batch: bad sizes (M=%d N=%d O=%d R=%d)", M, N, O, R);
-  if (N > qt::kLgMaxN)
-    return fail(QT_ERR_UNSUPPORTED, "qt_lp_ineq_large_batch supports up to %d variables (got %d)", qt::kLgMaxN, N);
-  const long long P = (long long)R * O;
-  if (P > (1LL << 30)) return fail(QT_ERR_ARG, "qt_lp_ineq_large_batch: too many programs (%lld)", P);
-  const double *dA, *dC, *db;
-  double *dobj, *dx;
-  int32_t *dst, *dit;
-  if (int r = c.in(A, (size_t)M * N, &dA)) return r;
-  if (int r = c.in(C, (size_t)O * N, &dC)) return r;
-  if (int r = c.in(b, (size_t)R * M, &db)) return r;
-  if (int r = c.out(obj, (size_t)P, &dobj)) return r;
-  if (int r = c.out(x, (size_t)P * N, &dx)) return r;
-  if (int r = c.out(status, (size_t)P, &dst)) return r;
-  if (int r = c.out(iters, (size_t)P, &dit)) return r;
-  // persistent workgroups: at most 2048, and at most 256 MB of workspace (about 0.6 MB each: about 400 workgroups)
-  const size_t per_wg = (qt::kLgHDoubles + (size_t)qt::kLgWs * M) * sizeof(double);
-  long long grid = P < 2048 ? P : 2048;
-  const long long by_ws = (long long)((256u << 20) / per_wg);
-  if (by_ws < 1)
-    return fail(QT_ERR_UNSUPPORTED, "qt_lp_ineq_large_batch: M = %d needs more than 256 MB of workspace per program", M);
-  if (grid > by_ws) grid = by_ws;
-  HIPCHK(h->lp_large_ws.ensure((size_t)grid * per_wg));
-  hipLaunchKernelGGL(qt::k_lp_ineq_large, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj,
-                     dx, dst, dit, h->lp_large_ws.as<double>());
-  return c.done(status, (int)P);
+  return lp_ineq_entry(h, "qt_lp_ineq_large_batch", qt::kLgMaxN, qt::LpLarge::ws_doubles(M) * sizeof(double), true,
+                       &qt_handle_t::lp_large_ws, qt::k_lp_ineq_large, A, M, N, C, O, b, R, obj, x, status, iters, flags);
 }
 
 // ---- f4: polytopes/utils.py:4-27, verification.py:9-78 over a batch of trials (qt_polytope.h) -------------------------

@@ -20,6 +20,8 @@ import numpy as np
 
 OPTIMAL, INFEASIBLE, UNBOUNDED, NOT_CONVERGED, FEASIBLE = 0, 1, 2, 3, 4  # qt_lp_status; FEASIBLE: phase 1 only
 LARGE_PIVOT = 1e-11  # kLgPivot of csrc/qt_lp_large.h
+# The constants of phase() below (tol, cap, the 1e-9 Farkas margin, the 1e-8 / -1e10 unbounded test) are those of
+# lp_phase in csrc/qt_lp.h (kTol, kLpCap and the literals beside them), the one place where both kernels have them.
 
 
 def _max_step(x, dx):
