@@ -6,7 +6,7 @@
 // reduction in place of the DPP butterfly.  What changes is where things live:
 //   * LDS (<= 160 KB): L, the broadcast vector, and two overlaid work regions X / Y that hold the
 //     stages of the factorised POVM contraction (R-order, see qt_small.h) and, outside of it, the
-//     Jacobi images A / V and the gradient matrix.  At n = 5 with 'proj-set' (M = 6^5 = 7776):
+//     images of the eigenvalue clip and the gradient matrix.  At n = 5 with 'proj-set' (M = 6^5 = 7776):
 //     X = 7776, Y = 5184 doubles -> 127 KB.  Frequencies are not stored: they are re-read from the
 //     counts (int64, gathered through the R-order row map) when needed.
 //   * The BFGS inverse Hessian is never formed.  A dense D x D f64 H (8 MB per trial at n = 5) had to be
@@ -26,7 +26,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qt_jacobi_wg.h"
 #include "qt_linesearch.h"
 #include "qt_signclip_wg.h"
 #include "qt_small.h"
@@ -50,9 +49,7 @@ struct Large {
   static constexpr int oVec = oL + MAT;        // [D]
   static constexpr int oLam = oVec + D;        // [d]
   static constexpr int oRed = oLam + d;        // [32] reduction scratch
-  static constexpr bool kJacobiClip = false;   // a7 through the cyclic Jacobi eigensolver instead of the sign-function clip
-  static constexpr int oRot = oRed + 32;       // Jacobi rotations of this round and the next: 2 x (cos [d], w [d] complex)
-  static constexpr int oLs = oRot + (kJacobiClip ? 6 * d : 0);  // line-search state parked across an evaluation
+  static constexpr int oLs = oRed + 32;        // line-search state parked across an evaluation
   static constexpr int oTab = oLs + LineSearch::SLOTS;  // tabT [R1][4], tabP [R1][4]
   __host__ __device__ static int x_doubles(int M) { return (M > MAT ? M : MAT) + (M & 1); }
   __host__ __device__ static int y_doubles(int M, int R1) {
@@ -496,22 +493,14 @@ struct Large {
     return r;
   }
 
-  // ---- a7: eigenvalue clip U max(v, eps) U^dagger / Tr.  Default: through the matrix sign function on the FP64 matrix
-  // cores (qt_signclip_wg.h; three d x d images: the Y overlay, the L region -- which holds nothing live here, the
-  // factorisation that called us has failed -- and the X overlay).  kJacobiClip selects the cyclic Jacobi
-  // eigensolver of qt_jacobi_wg.h instead (the version before round 2; kept for cross-checks).
+  // ---- a7: eigenvalue clip U max(v, eps) U^dagger / Tr through the matrix sign function on the FP64 matrix cores
+  // (qt_signclip_wg.h; three d x d images: the Y overlay, the L region -- which holds nothing live here, the
+  // factorisation that called us has failed -- and the X overlay).
   __device__ static cd psd_project(const Ctx& c, cd a, double eps) {
-    if constexpr (kJacobiClip) {
-      using J = JacobiWG<d, NT, true>;
-      static_assert(J::LDV == LD, "the eigenvector image uses the pitch of the other d x d images");
-      const typename J::Lds o{(int)(c.Y() - c.sm), oL, oRot, (int)(c.X() - c.sm), oLam, oRed};
-      return J::clip(c.t, a, eps, c.sm, o, true);
-    } else {
-      using SC = SignClipWG<d, NT>;
-      static_assert(SC::P == LD, "the images use the pitch of the other d x d images");
-      const typename SC::Lds o{(int)(c.Y() - c.sm), oL, (int)(c.X() - c.sm), oRed};
-      return SC::clip(c.t, a, eps, c.sm, o, true);
-    }
+    using SC = SignClipWG<d, NT>;
+    static_assert(SC::P == LD, "the images use the pitch of the other d x d images");
+    const typename SC::Lds o{(int)(c.Y() - c.sm), oL, (int)(c.X() - c.sm), oRed};
+    return SC::clip(c.t, a, eps, c.sm, o, true);
   }
 
   // ---- a8: Cholesky (image in the A overlay, factor in L) ------------------------------------------

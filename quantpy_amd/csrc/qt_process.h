@@ -6,12 +6,12 @@
 //
 // One workgroup reconstructs one process: thread (r, c) owns element C[r][c] of the DC x DC Choi
 // matrix (DC = 4^n: 4 or 16; DC = 64 has its own layout, qt_process64.h) through the whole Dykstra loop; the TP step is a partial-trace
-// reduction in LDS, the CP step a parallel-order Jacobi eigensolver in LDS.
+// reduction in LDS, the CP step the sign-function clip of qt_signclip_wg.h (DC = 16) or a round-robin Jacobi eigensolver
+// in LDS (DC = 4).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qt_jacobi_wg.h"
 #include "qt_signclip_wg.h"
 #include "qt_ops.h"    // v4f64
 #include "qt_small.h"  // gsum
@@ -108,15 +108,13 @@ struct ProcWG {
   // reads of the Jacobi rounds and of the rebuild fall on two banks (8-way conflicts).
   static constexpr int LDC = DC + 1;
   static constexpr int NEP = DC * LDC;
-  // The CP step's eigensolver: DC = 16 uses the workgroup Jacobi of qt_jacobi_wg.h (one thread per element, one
-  // barrier per round) in its own LDS block `jac`; DC = 4 (16 active threads of one wavefront) keeps the small
-  // round-robin version below with the v* / r* / o* arrays.
-  static constexpr bool kWgJacobi = DC == 16;
-  static constexpr bool kSignClipCP = true;  // false: the workgroup Jacobi eigensolver (the version before round 2)
-  using JW = JacobiWG<kWgJacobi ? DC : 16, kWgJacobi ? NE : 256, false>;
-  static constexpr int oJimg0 = 0, oJimg1 = oJimg0 + 2 * NE, oJrot = oJimg1 + 2 * NE, oJv = oJrot + 6 * DC,
-                       oJlam = oJv + 2 * DC * (DC + 1), oJred = oJlam + DC, kJacDoubles = oJred + 32;
-  static constexpr int NEV = kWgJacobi ? 2 : NEP;  // eigenvector images of the small version
+  // The CP step's eigenvalue clip: DC = 16 runs the sign-function clip of qt_signclip_wg.h (one thread per element) in
+  // its own LDS block `clip`; DC = 4 (16 active threads of one wavefront) keeps the small round-robin Jacobi eigensolver
+  // below with the v* / r* / o* arrays.
+  // `clip`: three 16 x 17 complex images + 32 doubles of reduction scratch = 1664 doubles, inside the 1712 the block has
+  // always had -- so the LDS size of every ProcWG<16> kernel, and the place of the dynamic LDS behind it, stay as measured.
+  static constexpr int kClipDoubles = 1712;
+  static constexpr int NEV = DC == 16 ? 2 : NEP;  // eigenvector images of the small version
   struct Sh {
     double are[NEP], aim[NEP];   // work matrix
     double tre[NEP], tim[NEP];   // column-rotated matrix
@@ -125,7 +123,7 @@ struct ProcWG {
     double red[16];
     double red6[6 * ((NT + 63) / 64)];
     double rre[DQ * DQ], rim[DQ * DQ];  // reduced (input-space) matrix of the TP step
-    alignas(16) double jac[kWgJacobi ? kJacDoubles : 2];
+    alignas(16) double clip[DC == 16 ? kClipDoubles : 2];
   };
 
   __device__ __forceinline__ static int partner(int i, int r) {
@@ -138,10 +136,7 @@ struct ProcWG {
 
   // CP projection (process.py:270-277): eigh on the lower triangle, clip at eps, rebuild.
   // (re, im) = this thread's element (i, j); returns the projected element.
-  // warm (DC = 16): in / out -- set when this call's eigensolve may start from the eigenvectors a previous call left
-  // in `jac`, and set by a call that ran the eigensolver (see JacobiWG::clip)
-  __device__ static void cp_project(Sh& sh, bool act, int i, int j, double& re, double& im, double eps,
-                                    bool* warm = nullptr) {
+  __device__ static void cp_project(Sh& sh, bool act, int i, int j, double& re, double& im, double eps) {
     const int e = i * LDC + j;
     // Hermitian completion from the lower triangle, like LAPACK's zheevd with uplo = 'L'
     if (act) {
@@ -206,25 +201,14 @@ struct ProcWG {
         return;
       }
     }
-    if constexpr (kWgJacobi && kSignClipCP) {
-      // eigenvalue clip through the matrix sign function on the FP64 matrix cores (qt_signclip_wg.h): three 16 x 17
-      // complex images + reduction scratch inside the `jac` block
-      // (default at d = 16: four real products on two wavefronts.  Three products on ONE wavefront, rotated over the SIMDs of
-      //  co-resident workgroups -- SignClipWG<DC, NE, true> -- measured slower here: CP step 43 -> 49 us per 1024, 4.4 -> 5.1 k
-      //  clocks per iteration step: a d = 16 step is bound by the latency of its one wavefront's chain, not by the matrix pipe)
+    if constexpr (DC == 16) {
+      // eigenvalue clip through the matrix sign function on the FP64 matrix cores (qt_signclip_wg.h, its default product
+      // form at d = 16: DESIGN.md section 4.4 has the other one measured here)
       using SC = SignClipWG<DC, NE>;
-      static_assert(3 * 2 * DC * SC::P + 32 <= kJacDoubles, "the sign-clip images fit the Jacobi block");
+      static_assert(3 * 2 * DC * SC::P + 32 <= kClipDoubles, "the sign-clip images and scratch fit their block");
       const typename SC::Lds o{0, 2 * DC * SC::P, 4 * DC * SC::P, 6 * DC * SC::P};
-      const cd out = SC::clip(threadIdx.x, cd{ar, ai}, eps, sh.jac, o, false);
+      const cd out = SC::clip(threadIdx.x, cd{ar, ai}, eps, sh.clip, o, false);
       __syncthreads();
-      re = out.re;
-      im = out.im;
-      return;
-    } else if constexpr (kWgJacobi) {
-      const typename JW::Lds o{oJimg0, oJimg1, oJrot, oJv, oJlam, oJred};
-      const cd out = JW::clip(threadIdx.x, cd{ar, ai}, eps, sh.jac, o, false, warm && *warm);
-      if (warm) *warm = true;
-      __syncthreads();  // the caller goes on to overwrite the a* / t* images; nothing of `jac` is read after this
       re = out.re;
       im = out.im;
       return;
@@ -364,9 +348,6 @@ struct ProcWG {
   __device__ static int dykstra(Sh& sh, bool act, int i, int j, double& xr, double& xi, int n_iter, double tol) {
     double pr = 0.0, pim = 0.0, qr = 0.0, qi = 0.0, yr = 0.0, yi = 0.0;
     int it = 0;
-    // successive CP steps see nearly the same matrix: from the second eigensolve on, start from the eigenvectors
-    // of the previous one (2-3 sweeps instead of ~7); every Dykstra run starts cold, so rounding in V cannot pile up
-    bool warm = false;
     for (; it < n_iter; ++it) {
       double tr_ = xr + pr, ti_ = xi + pim;
       tp_project(sh, act, i, j, tr_, ti_);
@@ -374,7 +355,7 @@ struct ProcWG {
       yr += ydr;
       yi += ydi;
       double cr = yr + qr, ci = yi + qi;
-      cp_project(sh, act, i, j, cr, ci, 1e-12, &warm);
+      cp_project(sh, act, i, j, cr, ci, 1e-12);
       const double xdr = cr - xr, xdi = ci - xi;
       xr += xdr;
       xi += xdi;

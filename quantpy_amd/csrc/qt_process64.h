@@ -88,7 +88,7 @@ struct Proc64 {
   };
 
   // This wavefront's share of A B into registers: c[0..3] its tile, c[4..7] its half of a split tile (wavefronts 0..3); no
-  // barrier inside.  THREE real products per complex tile (round 3, as SignClipWG::tile_product at d = 32): P1 = Ar Br,
+  // barrier inside.  THREE real products per complex tile (round 3, as ThreeProducts::tile_product of qt_signclip_wg.h): P1 = Ar Br,
   // P2 = Ai Bi, P3 = (Ar + Ai)(Br + Bi), C = (P1 - P2) + i (P3 - P1 - P2) -- the step is bound by the throughput of the FP64
   // matrix pipe, and the three (six) accumulator chains are independent.
   __device__ __forceinline__ static void tiles(const cd* A, const cd* B, const Work& wk, cd (&c)[EPT]) {
@@ -270,7 +270,7 @@ struct Proc64 {
     const double nrm2 = wsum(red, n2);
     if (!(nrm2 > 0.0)) {  // the zero matrix (or NaN input): every eigenvalue is clipped to eps
 #pragma unroll
-      for (int r = 0; r < EPT; ++r) a[r] = cd{nrm2 == 0.0 ? (e[r] == et[r] ? eps : 0.0) : nrm2, 0.0};
+      for (int r = 0; r < EPT; ++r) a[r] = sign_clip_degenerate(nrm2, e[r] == et[r], eps);
       return 0;
     }
     const double scale = 1.0 / sqrt(nrm2);
@@ -280,8 +280,9 @@ struct Proc64 {
       X[e[r]] = cd{a[r].re * scale, a[r].im * scale};
     }
     __syncthreads();
-    bool lifting = true;
-    int ns_left = 12, steps = 0;
+    using Sched = SignSchedule<24>;  // (3^24 = 2.8e11: what is still unlifted after 24 lifting steps is below 1e-11 ||A||)
+    Sched sched;
+    int steps = 0;
     const Work wk(m.tid);  // (derived from the caller's re-derived thread index: see dykstra)
     const int wave = m.tid >> 6;
     // A step (round 3: EVERY product Hermitian, three barriers where there were six, a lifting polynomial of degree 5).
@@ -304,7 +305,7 @@ struct Proc64 {
     // measuring the stragglers only) and slope 3 at 0; slope 3.2 is where the invariant interval [0, 1.26] is lost.  It
     // grows an unlifted eigenvalue by 3.0 for 9 tile products where 1.9 x - 0.9 x^3 (round 2) took 6 for 1.9.
     auto keep = [](cd*, int, int) {};
-    for (int k = 0; k < 64; ++k) {  // every exit condition is workgroup-uniform (identical bits in every thread)
+    for (int k = 0; k < Sched::kMaxSteps; ++k) {  // every exit condition is workgroup-uniform (identical bits in every thread)
       double rs = product(X, X, Y, wk, sm, keep);  // (image 1 is idle: the last product ended behind a barrier)
       rs = gsum<64>(rs);
       if ((m.tid & 63) == 0) red[wave] = rs;
@@ -312,10 +313,10 @@ struct Proc64 {
       double res = 0.0;
 #pragma unroll
       for (int w = 0; w < NW; ++w) res += red[w];
-      if (lifting && (res < 0.5 || k >= 24)) lifting = false;  // (3^24 = 2.8e11: what is still unlifted then is below 1e-11 ||A||)
-      const bool last = !lifting && (res < 1e-14 || --ns_left <= 0);
-      double alpha = 1.5, beta = -0.5;
-      if (lifting) {  // uniform.  W' = -3.25 Y + 1.25 Y Y over Y (its own tile re-read: cheaper than registers kept alive)
+      const bool last = sched.last_step(res, k);
+      double alpha = Sched::kNsAlpha, beta = Sched::kNsBeta;
+      // (lifting here is the quintic above, not the schedule's cubic: only the decision is shared)
+      if (sched.lifting) {  // uniform.  W' = -3.25 Y + 1.25 Y Y over Y (its own tile re-read: cheaper than registers kept alive)
         (void)product(Y, Y, Y, wk, sm, [&](cd* c, int row0, int col0) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -335,7 +336,7 @@ struct Proc64 {
       });
       __syncthreads();
       ++steps;
-      if (last || !(res == res)) break;
+      if (last) break;
     }
     // S = sign(A) sits in X.  R = (A + A S) / 2 + eps (I - S) / 2
     cd s[EPT];
@@ -351,11 +352,7 @@ struct Proc64 {
     __syncthreads();
     cd out[EPT];
 #pragma unroll
-    for (int r = 0; r < EPT; ++r) {
-      const cd as = Y[e[r]];
-      out[r] = cd{0.5 * (a[r].re + as.re) + 0.5 * eps * ((e[r] == et[r] ? 1.0 : 0.0) - s[r].re),
-                  0.5 * (a[r].im + as.im) - 0.5 * eps * s[r].im};
-    }
+    for (int r = 0; r < EPT; ++r) out[r] = sign_clip_epilogue(a[r], Y[e[r]], s[r], e[r] == et[r], eps);
     __syncthreads();  // everybody has its elements of A S
 #pragma unroll
     for (int r = 0; r < EPT; ++r) Y[e[r]] = out[r];

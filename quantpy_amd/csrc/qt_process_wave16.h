@@ -21,8 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qt_ops.h"    // v4f64
-#include "qt_small.h"  // cd, gsum, wave_sync, readlane_f64
+#include "qt_ops.h"          // v4f64
+#include "qt_signclip_wg.h"  // SignSchedule, sign_clip_degenerate, sign_clip_epilogue
+#include "qt_small.h"        // cd, gsum, wave_sync, readlane_f64
 
 namespace qt {
 
@@ -165,17 +166,17 @@ struct ProcWave16 {
     const double nrm2 = gsum<64>(n2);
     if (!(nrm2 > 0.0)) {  // the zero matrix (or NaN input): every eigenvalue is clipped to eps
 #pragma unroll
-      for (int r = 0; r < 4; ++r) a[r] = cd{nrm2 == 0.0 ? (L.i(r) == L.r16 ? eps : 0.0) : nrm2, 0.0};
+      for (int r = 0; r < 4; ++r) a[r] = sign_clip_degenerate(nrm2, L.i(r) == L.r16, eps);
       return 0;
     }
     const double scale = 1.0 / sqrt(nrm2);
     cd x[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) x[r] = cd{a[r].re * scale, a[r].im * scale};
-    bool lifting = true;
-    int ns_left = 12, steps = 0;
+    SignSchedule<40> sched;
+    int steps = 0;
     QT_STAMP(26);  // (profile build, scripts/phase_timing_cptp.py)
-    for (int k = 0; k < 64; ++k) {  // every exit condition is wave-uniform (gsum returns identical bits)
+    for (int k = 0; k < sched.kMaxSteps; ++k) {  // every exit condition is wave-uniform (gsum returns identical bits)
       QT_STAMP_VAL(25, (long long)(k + 1));
       cd y[4];
       mul_h(x, x, y);
@@ -186,15 +187,14 @@ struct ProcWave16 {
         rs += dr * dr + y[r].im * y[r].im;
       }
       const double res = gsum<64>(rs);
-      if (lifting && (res < 0.5 || k >= 40)) lifting = false;
-      const bool last = !lifting && (res < 1e-14 || --ns_left <= 0);
-      const double alpha = lifting ? 2.0 : 1.5, beta = lifting ? -1.0 : -0.5;
+      const bool last = sched.last_step(res, k);
+      const double alpha = sched.alpha(), beta = sched.beta();
       cd xy[4];
       mul_h(x, y, xy);
 #pragma unroll
       for (int r = 0; r < 4; ++r) x[r] = cd{fma(beta, xy[r].re, alpha * x[r].re), fma(beta, xy[r].im, alpha * x[r].im)};
       ++steps;
-      if (last || !(res == res)) break;
+      if (last) break;
       if ((k & 3) == 3) hermitian_part(L, x);
     }
     QT_STAMP(27);
@@ -202,9 +202,7 @@ struct ProcWave16 {
     cd as[4];
     mul_h(a, x, as);
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      a[r] = cd{0.5 * (a[r].re + as[r].re) + 0.5 * eps * ((L.i(r) == L.r16 ? 1.0 : 0.0) - x[r].re),
-                0.5 * (a[r].im + as[r].im) - 0.5 * eps * x[r].im};
+    for (int r = 0; r < 4; ++r) a[r] = sign_clip_epilogue(a[r], as[r], x[r], L.i(r) == L.r16, eps);
     hermitian_part(L, a);
 #pragma unroll
     for (int r = 0; r < 4; ++r)

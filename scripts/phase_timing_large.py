@@ -63,7 +63,4 @@ for label, sel in (("PD", ~nonpd), ("non-PD", nonpd)):
         prev = np.where(have, cur, prev)
 
 if nonpd.any():
-    q = p[nonpd][:8]
-    print("Jacobi off^2/nrm^2 (x 1e30) at the start of each sweep, first non-PD trials:")
-    for row in q:
-        print("   ", [f"{v / 1e30:.1e}" for v in row[20:32] if v != 0])
+    print("steps of the sign-function clip, first non-PD trials:", p[nonpd][:8, 25].tolist())
