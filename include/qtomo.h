@@ -78,9 +78,15 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
 /* Per-handle switches.  QT_OPT_SHOTS_CHECK (default 1): compare every trial's per-setting totals with the Ns of
  * qt_set_povm (QT_TRIAL_SHOTS).  QT_OPT_MLE_FUSED_MAX_WAVES (default 1024): batches of up to this many trial-wavefronts
  * (n <= 3) run the MLE as one launch with the BFGS inverse Hessian in registers; larger ones as a start launch plus a
- * BFGS launch in two-loop form (0 = always the latter).  Both forms compute scipy's iterates. */
-enum qt_option { QT_OPT_SHOTS_CHECK = 1, QT_OPT_MLE_FUSED_MAX_WAVES = 2 };
+ * BFGS launch in two-loop form (0 = always the latter).  Both forms compute scipy's iterates.
+ * QT_OPT_PAIRED_STAGES (default 1): at n <= 3 a six-row one-qubit table whose rows 2a, 2a+1 are exactly zero outside
+ * columns 0 and a+1 ('proj-set', 'proj' and their pseudo-inverses) runs contraction stages that skip those zeros;
+ * 0 forces the dense-table stages.  Both give the same bits, the sign of a zero excepted. */
+enum qt_option { QT_OPT_SHOTS_CHECK = 1, QT_OPT_MLE_FUSED_MAX_WAVES = 2, QT_OPT_PAIRED_STAGES = 3 };
 int qt_set_option(qt_handle_t* h, int option, double value);
+/* Which one-qubit tables of the current product POVM have that shape: bit 0 = T, bit 1 = pinv(T) as computed on the
+ * device (0 without a product POVM and at n >= 4; independent of QT_OPT_PAIRED_STAGES). */
+int qt_get_paired_tables(qt_handle_t* h);
 /* hipEvent timers on the handle's stream: begin, ..., end -> elapsed milliseconds */
 int qt_timer_begin(qt_handle_t* h);
 int qt_timer_end(qt_handle_t* h, double* elapsed_ms);

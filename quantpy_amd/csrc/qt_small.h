@@ -263,6 +263,12 @@ struct ProductView {
   int uniform;          // all N_s equal
   double wuni;          // the common weight
   int enabled;
+  // A six-row table whose rows 2a, 2a+1 are zero outside columns 0 and a+1 (the six-projector POVMs 'proj-set' and
+  // 'proj', and their pseudo-inverses) is "paired": half of every stage's terms are fma(0, x, acc).  The n <= 3
+  // stages then skip them (same terms, same order: same bits) and take the coefficients from here instead of LDS.
+  int pairedT, pairedP;  // T / pinv(T)^T has that shape and QT_OPT_PAIRED_STAGES is on (n <= 3 only)
+  double cT[12], cP[12];  // (u_r, v_r) = (tab[r][0], tab[r][r / 2 + 1]), r = 0 .. 5: the bits of T and P1T
+  const int* last;       // [M] stage-n entries of a paired T: in0 | axis << 8 | (4 r + a + 1) << 16
 };
 
 struct PovmView {
@@ -423,8 +429,15 @@ struct Small {
         t1[e] = pv.pr.T[e];
         t1[4 * r1 + e] = pv.pr.P1T[e];
       }
-      for (int e = threadIdx.x; e < nf; e += NT) tabs[e] = pv.pr.fwd[e];
-      for (int e = threadIdx.x; e < nb; e += NT) tabs[nf + e] = pv.pr.bwd[e];
+      // paired tables index their stages in closed form: only stage n of the forward pass keeps a table (M <= nf
+      // entries, in the place of the forward tables)
+      if (pv.pr.pairedT) {
+        for (int e = threadIdx.x; e < pv.M; e += NT) tabs[e] = pv.pr.last[e];
+      } else {
+        for (int e = threadIdx.x; e < nf; e += NT) tabs[e] = pv.pr.fwd[e];
+      }
+      if (!(pv.pr.pairedT && pv.pr.pairedP))
+        for (int e = threadIdx.x; e < nb; e += NT) tabs[nf + e] = pv.pr.bwd[e];
       for (int e = threadIdx.x; e < pv.M; e += NT) {
         tabs[nf + nb + e] = pv.pr.rmap[e];
         wrow[e] = pv.pr.wrowR[e];
@@ -753,14 +766,72 @@ struct Small {
   __device__ __forceinline__ static double stage_last(const Ctx& c, const double* tb, const int* tab, const double* in) {
     return stage_value<false, R1C>(tb, c.pv.pr.R1, tab[c.l], 1 << (2 * (NQ - 1)), in);
   }
-  // Backward pass from Y_n (R-order, in `yn`) to the lane's Y_0[k = l]; tb = tabT (A^T y) or tabP (A^+ f).
+  // ---- the same stages for a paired table (ProductView::pairedT / pairedP, R1 = 6) ----------------------------
+  // Row r = 2a, 2a+1 of such a table is (u_r, 0 .. v_r .. 0) with v_r in column a+1, so a forward output has two
+  // terms and a backward output two (k = a+1) or six (k = 0).  The terms that are left are those of stage_value in
+  // its order, with coefficients of the same bits (ProductView::cT / cP): what is dropped is fma(0, x, acc) = acc,
+  // so the results agree bit for bit, the sign of a zero excepted.  A stage works on its bases
+  // (r_1 .. r_(q-1), k_rest), one per lane and indexed in closed form: 6^(q-1) 4^(n-q) <= G of them.
+  __device__ __forceinline__ static int paired_bases(int q) { return ipow(6, q - 1) << (2 * (NQ - q)); }
+  // forward stage q < n: the base's four inputs make its six outputs
+  __device__ __forceinline__ static void paired_forward(const Ctx& c, int q, const double* in, double* out) {
+    const int lk = 2 * (NQ - q), Kq = 1 << lk;
+    if (c.l < paired_bases(q)) {
+      const int rpre = c.l >> lk, krest = c.l & (Kq - 1);
+      const double* ib = in + ((rpre * 4) << lk) + krest;
+      double* ob = out + ((rpre * 6) << lk) + krest;
+      const double x0 = ib[0];
+      const double xa[3] = {ib[Kq], ib[2 * Kq], ib[3 * Kq]};
+#pragma unroll
+      for (int r = 0; r < 6; ++r) ob[r * Kq] = fma(c.pv.pr.cT[2 * r + 1], xa[r >> 1], c.pv.pr.cT[2 * r] * x0);
+    }
+    wave_sync();
+  }
+  // backward stage q >= 2: the base's six inputs make its four outputs
+  template <bool PINV>
+  __device__ __forceinline__ static void paired_backward(const Ctx& c, int q, const double* in, double* out) {
+    const int lk = 2 * (NQ - q), Kq = 1 << lk;
+    if (c.l < paired_bases(q)) {
+      const int rpre = c.l >> lk, krest = c.l & (Kq - 1);
+      const double* ib = in + ((rpre * 6) << lk) + krest;
+      double* ob = out + ((rpre * 4) << lk) + krest;
+      double y[6], acc = 0.0;
+#pragma unroll
+      for (int t = 0; t < 6; ++t) y[t] = ib[t * Kq];
+#pragma unroll
+      for (int t = 0; t < 6; ++t) acc = fma(PINV ? c.pv.pr.cP[2 * t] : c.pv.pr.cT[2 * t], y[t], acc);
+      ob[0] = acc;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double v0 = PINV ? c.pv.pr.cP[4 * a + 1] : c.pv.pr.cT[4 * a + 1];
+        const double v1 = PINV ? c.pv.pr.cP[4 * a + 3] : c.pv.pr.cT[4 * a + 3];
+        ob[(a + 1) * Kq] = fma(v1, y[2 * a + 1], v0 * y[2 * a]);
+      }
+    }
+    wave_sync();
+  }
+
+  // Backward pass from Y_n (R-order, in `yn`) to the lane's Y_0[k = l]; PINV: with pinv(T) (A^+ f), else T (A^T y).
   // Intermediates ping-pong between bufB and rbuf; `yn` itself is only read.
-  __device__ static double prod_backward(const Ctx& c, const double* tb, const double* yn) {
+  template <bool PINV>
+  __device__ static double prod_backward(const Ctx& c, const double* yn) {
     const int R1 = c.pv.pr.R1;
+    const double* tb = PINV ? c.tabP() : c.tabT();
     const int* tab = c.tbwd;
     const double* in = yn;
     double* bufs[2] = {c.bufB(), c.rbuf()};
     int which = 0;
+    if (PINV ? c.pv.pr.pairedP : c.pv.pr.pairedT) {
+#pragma unroll
+      for (int q = NQ; q >= 2; --q) {
+        paired_backward<PINV>(c, q, in, bufs[which]);
+        in = bufs[which];
+        which ^= 1;
+      }
+      // stage 1 keeps its shape (one output per lane, the table column from LDS); its entry is (k_rest, k_1)
+      const int lk = 2 * (NQ - 1);
+      return stage_value<false, 6>(tb, 6, (c.l & ((1 << lk) - 1)) | (c.l >> lk) << 16, 1 << lk, in);
+    }
 #pragma unroll
     for (int q = NQ; q >= 2; --q) {
       const int stride = 1 << (2 * (NQ - q));             // 4^(n-q)
@@ -774,6 +845,42 @@ struct Small {
     if (R1 == 6) return stage_last<6>(c, tb, tab, in);
     if (R1 == 4) return stage_last<4>(c, tb, tab, in);
     return stage_last<0>(c, tb, tab, in);
+  }
+  // Forward stage n fused with the log-likelihood terms: p = d w (.) X_n + 1e-10, the lane's share of
+  // sum freq log p (returned), and Y_n = w (.) freq / p into `rb` (A'^T r = K^T (w (.) r)).  Two outputs per pass
+  // so that their LDS round trips (table entry -> operands) overlap; the second of a pair is a recomputation of
+  // the first when the row count runs out, and is not stored.
+  // PAIRED (ProductView::pairedT): a row keeps its lane -- the order of the sum over rows is part of the value's
+  // bits -- and reads its two non-zero coefficients and their operands through the entries of ProductView::last.
+  // UNI: equal shots, every row weight is wuni (the same division as wrowR[m]).
+  template <bool PAIRED, bool UNI>
+  __device__ __forceinline__ static double stage_n_log(const Ctx& c, const int* tab, const double* in, const double* fr,
+                                                       double* rb) {
+    const double* tb = c.tabT();
+    auto x_of = [&](int ent) {
+      if (!PAIRED) return stage_value<true>(tb, c.pv.pr.R1, ent, 1, in);
+      const int vi = ent >> 16;
+      return fma(tb[vi], in[(ent >> 8) & 0xff], tb[vi & ~3] * in[ent & 0xff]);
+    };
+    double fpart = 0.0;
+    for (int o = c.l; o < c.M; o += 2 * G) {
+      const int o2 = o + G;
+      const bool two = o2 < c.M;
+      const int oo = two ? o2 : o;
+      const int e0 = tab[o], e1 = tab[oo];
+      const double x0 = x_of(e0), x1 = x_of(e1);
+      const double w0 = UNI ? c.pv.pr.wuni : c.twrow[o], w1 = UNI ? c.pv.pr.wuni : c.twrow[oo];
+      const double f0 = fr[o], f1 = fr[oo];
+      const double p0 = x0 * w0 * d + 1e-10, p1 = x1 * w1 * d + 1e-10;
+      const double l0 = fast_log(p0), l1 = fast_log(p1);
+      fpart += f0 * l0;
+      rb[o] = w0 * f0 * recip_nr(p0);
+      if (two) {
+        fpart += f1 * l1;
+        rb[o2] = w1 * f1 * recip_nr(p1);
+      }
+    }
+    return fpart;
   }
   // sum_m Op[m][lane] * vec[m]   (lane = column)
   __device__ __forceinline__ static double col_dot(const Ctx& c, const double* g_rowmajor, const double* vec) {
@@ -789,7 +896,7 @@ struct Small {
     if (c.prod()) {
       if (c.pv.pr.uniform) {
         // pinv(w K) = pinv(T)^(x n) / w : the same backward pass with pinv(T) instead of T
-        bloch_l = prod_backward(c, c.tabP(), c.freq()) / (c.pv.pr.wuni * d);
+        bloch_l = prod_backward<true>(c, c.freq()) / (c.pv.pr.wuni * d);
       } else {  // unequal shots per setting: dense left inverse, rows visited in R-order
         double acc = 0.0;
         for (int m = 0; m < c.M; ++m) acc = fma(c.pv.PinvT[(size_t)c.trmap[m] * D + c.l], c.freq()[m], acc);
@@ -1159,6 +1266,7 @@ struct Small {
     double wl;
     if (c.prod()) {
       const int R1 = c.pv.pr.R1;
+      const bool paired = c.pv.pr.pairedT != 0;
       const int* tab = c.tfwd;
       const double* in = vec;
 #pragma unroll
@@ -1166,37 +1274,23 @@ struct Small {
         const int stride = 1 << (2 * (NQ - q));
         const int n_out = ipow(R1, q) * stride;
         double* out = ((NQ - 1 - q) & 1) ? rb : c.bufB();
-        stage<true>(c, c.tabT(), tab, n_out, stride, in, out);
-        tab += n_out;
+        if (paired) {
+          paired_forward(c, q, in, out);
+        } else {
+          stage<true>(c, c.tabT(), tab, n_out, stride, in, out);
+          tab += n_out;
+        }
         in = out;
       }
       QT_STAMP(14);
-      // stage n fused with the log-likelihood terms, two outputs per pass so that their LDS round trips
-      // (table entry -> operands) overlap; the second of a pair is a recomputation of the first when the
-      // row count runs out, and is not stored
-      for (int o = c.l; o < c.M; o += 2 * G) {
-        const int o2 = o + G;
-        const bool two = o2 < c.M;
-        const int oo = two ? o2 : o;
-        const int e0 = tab[o], e1 = tab[oo];
-        const double x0 = stage_value<true>(c.tabT(), R1, e0, 1, in);
-        const double x1 = stage_value<true>(c.tabT(), R1, e1, 1, in);
-        const double w0 = c.twrow[o], w1 = c.twrow[oo];
-        const double f0 = fr[o], f1 = fr[oo];
-        const double p0 = x0 * w0 * d + 1e-10, p1 = x1 * w1 * d + 1e-10;
-        const double l0 = fast_log(p0), l1 = fast_log(p1);
-        fpart += f0 * l0;
-        rb[o] = w0 * f0 * recip_nr(p0);  // Y_n = w (.) r : A'^T r = K^T (w (.) r)
-        if (two) {
-          fpart += f1 * l1;
-          rb[o2] = w1 * f1 * recip_nr(p1);
-        }
-      }
+      if (!paired) fpart = stage_n_log<false, false>(c, tab, in, fr, rb);
+      else if (c.pv.pr.uniform) fpart = stage_n_log<true, true>(c, tab, in, fr, rb);
+      else fpart = stage_n_log<true, false>(c, tab, in, fr, rb);
       f = -gsum<G>(fpart);
       wave_sync();
       QT_STAMP(15);
       if (!want_grad) return;  // (uniform) the Metropolis chain only needs the value
-      wl = prod_backward(c, c.tabT(), rb);
+      wl = prod_backward<false>(c, rb);
       QT_STAMP(16);
     } else {
       for (int m0 = 0; m0 < c.M; m0 += G) {

@@ -99,7 +99,7 @@ struct qt_handle {
   DevBuf kron_dig;
   int kron_S1 = 0, kron_K1 = 0;
   // product-POVM (Kronecker) description, valid when prod.enabled
-  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd;
+  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd, pr_last;
   qt::ProductView prod{};
   // staging for host-pointer calls: one buffer per array of a call, in the order the call registers them (Call)
   DevBuf stage[kStageBufs];
@@ -124,10 +124,15 @@ struct qt_handle {
   bool check_shots = true;  // qt_set_option(QT_OPT_SHOTS_CHECK) / QTOMO_SKIP_SHOTS_CHECK=1 at qt_create
   int fused_max_waves = 1024;  // qt_set_option(QT_OPT_MLE_FUSED_MAX_WAVES): largest batch (in trial-waves) of k_mle_fused
   double ns_max = 0.0;  // largest registered shot number (product POVMs): the n >= 4 count cache holds 32-bit counts
+  bool paired_stages = true;  // qt_set_option(QT_OPT_PAIRED_STAGES): let paired tables take their own stages (n <= 3)
+  int paired_tables = 0;      // what qt_set_povm_product found: bit 0 = T is paired, bit 1 = pinv(T)^T is
   // the POVM as the estimator kernels read it; `extra` (PovmView::extra) comes with the launch's LDS size (Plan)
   qt::PovmView view(int extra) const {
-    return qt::PovmView{Aw.as<double>(), AwT.as<double>(), PinvT.as<double>(), M, prod, jtol2,
-                        check_shots ? Ns.as<double>() : nullptr, S, K, ns_tot, extra};
+    qt::PovmView v{Aw.as<double>(), AwT.as<double>(), PinvT.as<double>(), M, prod, jtol2,
+                   check_shots ? Ns.as<double>() : nullptr, S, K, ns_tot, extra};
+    v.pr.pairedT = paired_stages ? paired_tables & 1 : 0;
+    v.pr.pairedP = paired_stages ? (paired_tables >> 1) & 1 : 0;
+    return v;
   }
   // Jacobi stopping rule off^2 <= jtol2 * ||A||_F^2.  Measured on the C2 batch: the last sweep takes off^2
   // from > 1e-9 to < 1e-28 in one go, so no looser threshold saves a sweep without costing accuracy.
@@ -542,6 +547,7 @@ int begin_povm(qt_handle_t* h, int S, int K) {
   h->proc_set = false;
   h->dense_ready = h->a_loaded = h->pinv_ready = false;
   h->prod = qt::ProductView{};
+  h->paired_tables = 0;
   h->S = S;
   h->K = K;
   h->M = (int)M;
@@ -856,7 +862,7 @@ void qt_destroy(qt_handle_t* h) {
   if (!h) return;
   DeviceScope scope(h->device);
   (void)hipStreamSynchronize(h->stream);
-  for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd})
+  for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_last})
     b->release();
   for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws,
                     &h->gram, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
@@ -898,8 +904,14 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
       if (!(value >= 0.0 && value <= 1048576.0)) return fail(QT_ERR_ARG, "QT_OPT_MLE_FUSED_MAX_WAVES out of range");
       h->fused_max_waves = (int)value;
       return 0;
+    case QT_OPT_PAIRED_STAGES: h->paired_stages = value != 0.0; return 0;
     default: return fail(QT_ERR_ARG, "unknown option %d", option);
   }
+}
+
+int qt_get_paired_tables(qt_handle_t* h) {
+  QT_ENTER(h);
+  return h->povm_set && h->prod.enabled ? h->paired_tables : 0;
 }
 
 int qt_timer_begin(qt_handle_t* h) {
@@ -1066,11 +1078,42 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
   HIPCHK(hipMemcpyAsync(h->pr_wrow.p, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->pr_fwd.p, fwd.data(), fwd.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->pr_bwd.p, bwd.data(), bwd.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  // A paired table (ProductView::pairedT) at n <= 3: the entries of forward stage n, row by row in R-order
+  // (in0 = 4 r_pre, axis = in0 + a + 1, and the place 4 r + a + 1 of v_r in the table).  pinv(T)^T is classified
+  // below on the values the kernels read, i.e. on the device's result, with no tolerance.
+  const bool try_paired = n <= 3 && R1 == 6;
+  auto is_paired = [](const double* tab) {  // [6][4]
+    for (int r = 0; r < 6; ++r)
+      for (int k = 1; k < 4; ++k)
+        if (k != r / 2 + 1 && tab[r * 4 + k] != 0.0) return false;
+    return true;
+  };
+  const bool pairedT = try_paired && is_paired(t1.data());
+  if (pairedT) {
+    std::vector<int> last((size_t)M);
+    for (long long o = 0; o < M; ++o) {
+      const int rpre = (int)(o / 6), r = (int)(o % 6), a = r / 2;
+      last[(size_t)o] = (4 * rpre) | (4 * rpre + a + 1) << 8 | (4 * r + a + 1) << 16;
+    }
+    HIPCHK(h->pr_last.ensure(last.size() * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(h->pr_last.p, last.data(), last.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  }
   int info = 0;
+  double p1t[24] = {};
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (try_paired) HIPCHK(hipMemcpyAsync(p1t, h->pr_P1T.p, sizeof(p1t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "the one-qubit table is not informationally complete");
+  const bool pairedP = try_paired && is_paired(p1t);
+  for (int r = 0; r < 6 && try_paired; ++r) {
+    h->prod.cT[2 * r] = t1[r * 4];
+    h->prod.cT[2 * r + 1] = t1[r * 4 + r / 2 + 1];
+    h->prod.cP[2 * r] = p1t[r * 4];
+    h->prod.cP[2 * r + 1] = p1t[r * 4 + r / 2 + 1];
+  }
+  h->prod.last = h->pr_last.as<int>();
+  h->paired_tables = (pairedT ? 1 : 0) | (pairedP ? 2 : 0);
   h->prod.T = h->pr_T.as<double>();
   h->prod.P1T = h->pr_P1T.as<double>();
   h->prod.wrowR = h->pr_wrow.as<double>();

@@ -179,8 +179,15 @@ class Engine:
 
     def set_option(self, option, value):
         """qt_set_option: _capi.QT_OPT_SHOTS_CHECK (0 / 1), _capi.QT_OPT_MLE_FUSED_MAX_WAVES (0 = always the split,
-        two-loop BFGS path)."""
+        two-loop BFGS path), _capi.QT_OPT_PAIRED_STAGES (0 = the dense-table contraction stages for every one-qubit
+        table, 1 = the zero-skipping stages where `paired_tables` says so; the same bits either way)."""
         self._chk(self.lib.qt_set_option(self._h, int(option), float(value)))
+
+    @property
+    def paired_tables(self):
+        """Bit 0: the one-qubit table of the current product POVM is paired (six rows, rows 2a and 2a+1 exactly zero
+        outside columns 0 and a+1); bit 1: so is its pseudo-inverse as the device computed it.  0 at n >= 4."""
+        return self._chk(self.lib.qt_get_paired_tables(self._h))
 
     def timer_begin(self):
         self._chk(self.lib.qt_timer_begin(self._h))
