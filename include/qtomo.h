@@ -81,12 +81,17 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
  * BFGS launch in two-loop form (0 = always the latter).  Both forms compute scipy's iterates.
  * QT_OPT_PAIRED_STAGES (default 1): at n <= 3 a six-row one-qubit table whose rows 2a, 2a+1 are exactly zero outside
  * columns 0 and a+1 ('proj-set', 'proj' and their pseudo-inverses) runs contraction stages that skip those zeros;
- * 0 forces the dense-table stages.  Both give the same bits, the sign of a zero excepted. */
-enum qt_option { QT_OPT_SHOTS_CHECK = 1, QT_OPT_MLE_FUSED_MAX_WAVES = 2, QT_OPT_PAIRED_STAGES = 3 };
+ * 0 forces the dense-table stages.  Both give the same bits, the sign of a zero excepted.
+ * QT_OPT_MLE_SPECIALISE (default 1): at n <= 3 the MLE kernels have a second instantiation compiled for the shape of
+ * every built-in six-projector run ('proj-set': both tables paired and QT_OPT_PAIRED_STAGES on, equal shots per
+ * setting, QT_OPT_SHOTS_CHECK on); 0 forces the generic instantiation.  Both give the same bits. */
+enum qt_option { QT_OPT_SHOTS_CHECK = 1, QT_OPT_MLE_FUSED_MAX_WAVES = 2, QT_OPT_PAIRED_STAGES = 3, QT_OPT_MLE_SPECIALISE = 4 };
 int qt_set_option(qt_handle_t* h, int option, double value);
 /* Which one-qubit tables of the current product POVM have that shape: bit 0 = T, bit 1 = pinv(T) as computed on the
  * device (0 without a product POVM and at n >= 4; independent of QT_OPT_PAIRED_STAGES). */
 int qt_get_paired_tables(qt_handle_t* h);
+/* 1 if the last qt_mle_batch / qt_mle_dist_batch launch took the specialised instantiation, else 0. */
+int qt_get_mle_specialised(qt_handle_t* h);
 /* hipEvent timers on the handle's stream: begin, ..., end -> elapsed milliseconds */
 int qt_timer_begin(qt_handle_t* h);
 int qt_timer_end(qt_handle_t* h, double* elapsed_ms);

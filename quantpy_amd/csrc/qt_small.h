@@ -287,6 +287,30 @@ struct PovmView {
   int extra = 0;  // extra doubles of per-trial LDS behind the scratch (k_mle_bfgs: line-search state + two-loop scalars)
 };
 
+// What the specialised MLE kernels (template parameter GENERIC = false, n <= 3) take instead of a PovmView.  They are
+// compiled for ONE launch-uniform shape, that of every built-in six-projector run: a product POVM with R1 = 6 rows
+// made of three two-outcome settings (so K = d outcomes per setting, M = 6^n <= 4 G rows), both one-qubit tables
+// paired, equal shots per setting, the shots check on.  Nothing else of the POVM is read, so nothing else is passed:
+// the PovmView is 0x1b8 bytes of kernel arguments, most of them dead on this path and all of them live in SGPRs.
+// `image` is built once by qt_set_povm_product, in device memory: the workgroup's LDS table block in its final layout
+// (Small::image_chunks(M) 16-byte chunks: the stage-n entries `last`[M], padded to a multiple of four, then T [6][4]
+// and pinv(T)^T [6][4]) followed by rinv[M].
+struct SpecArgs {
+  const void* image;
+  const double* Ns;  // [S] registered shots per setting
+  double ns_tot, wuni, jtol2;
+  int M, extra;
+  double cT[12], cP[12];  // ProductView::cT / cP
+};
+template <bool GENERIC>
+struct MleArgs {
+  using type = PovmView;
+};
+template <>
+struct MleArgs<false> {
+  using type = SpecArgs;
+};
+
 // t_s / total == N_s / ns_tot, compared as cross products of integer-valued doubles (exact below 2^53; a few
 // ulp of slack beyond that -- one stray count out of N_s < 1e14 is still seen)
 __device__ __forceinline__ bool shots_match(double t_s, double total, double n_s, double ns_tot) {
@@ -393,7 +417,75 @@ struct Small {
     __device__ __forceinline__ const double* tabP() const { return ptab; }  // [R1][4]
     __device__ __forceinline__ bool prod() const { return pv.pr.enabled != 0; }
     __device__ __forceinline__ double* extra() const { return sm + trial_doubles(M, pv.pr.enabled ? pv.pr.R1 : 0); }  // [pv.extra]
+    // the launch-uniform facts, read at run time here and compile-time constants in CtxS
+    static constexpr bool kGeneric = true;
+    __device__ __forceinline__ int R1() const { return pv.pr.R1; }
+    __device__ __forceinline__ bool uniform() const { return pv.pr.uniform != 0; }
+    __device__ __forceinline__ bool pairedT() const { return pv.pr.pairedT != 0; }
+    __device__ __forceinline__ bool pairedP() const { return pv.pr.pairedP != 0; }
+    __device__ __forceinline__ double wuni() const { return pv.pr.wuni; }
+    __device__ __forceinline__ double jtol2() const { return pv.jtol2; }
+    __device__ __forceinline__ double cT(int k) const { return pv.pr.cT[k]; }
+    __device__ __forceinline__ double cP(int k) const { return pv.pr.cP[k]; }
   };
+  // The context of the specialised kernels (SpecArgs): the same roles, the shape known to the compiler.  The table
+  // block holds the image of SpecArgs::image and nothing else; the trial scratch keeps the generic layout and offset.
+  struct CtxS {
+    int l, i, j, e;
+    double* sm;
+    const int* tfwd;            // `last`: the stage-n entries
+    const double *ttab, *ptab;  // T [6][4], pinv(T)^T [6][4]
+    int M, Mp;
+    SpecArgs a;
+    int xm, zm, ny;
+    int pi, pj, pkind;
+    int src_re, src_im;
+    int bslot;  // n = 3: where bloch_of's lane (x, z) leaves its value, pauli_index(x, z)
+    // The 12 + 12 coefficients of the paired stages.  k_mle_start / k_mle_bfgs (held to 128 / 168 VGPRs) keep them as
+    // scalars: without the PovmView they fit the SGPR file.  k_mle_fused does not get them to fit -- its BFGS loop and
+    // the f64 literals of fast_log are scalars too, and the register allocator's answer was to spill all 24 at the top
+    // of nll_grad and restore them lane by lane in front of every stage (158 v_readlane per evaluation) -- but it runs
+    // one wave per SIMD with ~75 VGPRs to spare: there they are pinned in vector registers (make_ctx<true>), where an
+    // FMA reads them at no cost.
+    double kT[12], kP[12];
+    __device__ __forceinline__ cd* A() const { return reinterpret_cast<cd*>(sm + oA); }
+    __device__ __forceinline__ cd* Bm() const { return reinterpret_cast<cd*>(sm + oB); }
+    __device__ __forceinline__ cd* V() const { return reinterpret_cast<cd*>(sm + v_offset(M, 6)); }
+    __device__ __forceinline__ double* vec() const { return sm + oVec; }
+    __device__ __forceinline__ double* lam() const { return sm + oLam; }
+    __device__ __forceinline__ double* rbuf() const { return sm + oM; }
+    __device__ __forceinline__ double* freq() const { return sm + oM + Mp; }
+    __device__ __forceinline__ double* bufB() const { return sm + oM + 2 * Mp; }
+    __device__ __forceinline__ const double* tabT() const { return ttab; }
+    __device__ __forceinline__ const double* tabP() const { return ptab; }
+    __device__ __forceinline__ double* extra() const { return sm + trial_doubles(M, 6); }  // [a.extra]
+    static constexpr bool kGeneric = false;
+    __device__ __forceinline__ static constexpr bool prod() { return true; }
+    __device__ __forceinline__ static constexpr int R1() { return 6; }
+    __device__ __forceinline__ static constexpr bool uniform() { return true; }
+    __device__ __forceinline__ static constexpr bool pairedT() { return true; }
+    __device__ __forceinline__ static constexpr bool pairedP() { return true; }
+    __device__ __forceinline__ double wuni() const { return a.wuni; }
+    __device__ __forceinline__ double jtol2() const { return a.jtol2; }
+    __device__ __forceinline__ double cT(int k) const { return kT[k]; }
+    __device__ __forceinline__ double cP(int k) const { return kP[k]; }
+  };
+  __device__ __forceinline__ static double pin_vgpr(double x) {  // the value, in a vector register from here on
+    asm volatile("" : "+v"(x));
+    return x;
+  }
+  template <bool GENERIC, class = void>
+  struct CtxOf {
+    using type = Ctx;
+  };
+  template <class X>
+  struct CtxOf<false, X> {
+    using type = CtxS;
+  };
+  // 16-byte chunks of the table image (SpecArgs::image): `last` padded to four entries, then the two one-qubit tables
+  __host__ __device__ static int image_last_ints(int M) { return (M + 3) & ~3; }
+  // (M = 6^n <= 216: at most 78 chunks, one per thread of the workgroup)
+  __host__ __device__ static int image_chunks(int M) { return image_last_ints(M) / 4 + 2 * 24 / 2; }
 
   // Trial handled by this lane's group; *live = false for the padding groups of the last block.
   __device__ __forceinline__ static int trial_index(int B, bool* live) {
@@ -510,7 +602,8 @@ struct Small {
   __device__ __forceinline__ static cd wht_step(cd s, cd p, bool upper) {
     return upper ? cd{p.re - s.re, p.im - s.im} : cd{s.re + p.re, s.im + p.im};
   }
-  __device__ static double bloch_of(const Ctx& c, const cd* m) {
+  template <class C>
+  __device__ static double bloch_of(const C& c, const cd* m) {
     if constexpr (NQ == 3) {
       const int x = c.i, r = c.j, lane = threadIdx.x & 63;
       const cd e = m[r * LD + (r ^ x)];
@@ -523,7 +616,8 @@ struct Small {
       // pauli_index(x, z): digit bits (hi, lo) = (z_q, x_q ^ z_q) = spread(x) ^ 3 spread(z)
       const int sx = (x & 1) | ((x & 2) << 1) | ((x & 4) << 2), sz = (z & 1) | ((z & 2) << 1) | ((z & 4) << 2);
       double* vec = c.vec();
-      vec[sx ^ (3 * sz)] = v;
+      if constexpr (C::kGeneric) vec[sx ^ (3 * sz)] = v;
+      else vec[c.bslot] = v;  // the same index, a lane constant computed once (make_ctx)
       wave_sync();
       const double mine = vec[c.l];
       wave_sync();
@@ -575,7 +669,8 @@ struct Small {
     using type = MatTab<L...>;
   };
   static_assert(NQ <= 3, "the packed table holds d <= 8 terms of 8 bits");
-  __device__ static cd matrix_of(const Ctx& c, const double* v) {
+  template <class C>
+  __device__ static cd matrix_of(const C& c, const double* v) {
     using Tab = typename MakeMatTab<D>::type;
     const uint64_t pack = Tab::v[c.l];
     cd s{0.0, 0.0};
@@ -599,6 +694,8 @@ struct Small {
     int64_t v[4];
     double ns[4];  // N_s of the settings rows l + q G belong to (segmented check) or of setting s = lane (ns[0])
     bool ok, seg;  // seg: K in {2, 4, 8, 16} divides G -- the K outcomes of a setting sit in K neighbouring lanes
+    int ri[4];     // specialised kernels: the R-order slots of the rows l + q G (rinv)
+    uint4 img;     // ... and this thread's 16-byte chunk of the workgroup's table image
   };
   __device__ __forceinline__ static void prefetch_counts(Prefetch& pf, const int64_t* counts, const PovmView& pv) {
     const int l = (threadIdx.x & 63) % G, M = pv.M, K = pv.K;
@@ -703,6 +800,120 @@ struct Small {
     return (votes & mine) == 0ull;
   }
 
+  // ---- prologue of the specialised kernels (SpecArgs, CtxS) -------------------------------------
+  // Everything a trial reads from memory is requested in ONE batch at the top of the kernel: this thread's chunk of
+  // the table image (L2), the counts of its rows (the only cold read), their R-order slots and their settings' N_s.
+  // make_ctx then has one wait, one ds_write_b128 per thread and the workgroup barrier; the generic body stages its
+  // tables in three load -> wait -> write loops, each an exposed L2 round trip of a lone wave.
+  __device__ __forceinline__ static void prefetch_counts(Prefetch& pf, const int64_t* counts, const SpecArgs& a) {
+    const int l = (threadIdx.x & 63) % G, M = a.M, nch = image_chunks(M), t = threadIdx.x;
+    const uint4* img = reinterpret_cast<const uint4*>(a.image);
+    const int* rinv = reinterpret_cast<const int*>(img + nch);
+    pf.img = img[t < nch ? t : nch - 1];
+    pf.ok = pf.seg = true;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int m = l + q * G, mc = m < M ? m : M - 1;
+      pf.v[q] = counts[mc];
+      pf.ri[q] = rinv[mc];
+      pf.ns[q] = a.Ns[mc >> NQ];  // K = d outcomes per setting
+    }
+  }
+  template <bool VCOEF = false>
+  __device__ static void make_ctx(CtxS& c, double* smem_block, const SpecArgs& a, const Prefetch& pf) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    c.l = lane % G;
+    const int slot = wave * TPW + lane / G;
+    c.i = c.l / d;
+    c.j = c.l % d;
+    c.e = c.i * LD + c.j;
+    c.M = a.M;
+    c.Mp = (a.M + 1) & ~1;
+    c.a = a;
+    if ((int)threadIdx.x < image_chunks(a.M)) reinterpret_cast<uint4*>(smem_block)[threadIdx.x] = pf.img;
+    c.tfwd = reinterpret_cast<const int*>(smem_block);
+    c.ttab = smem_block + image_last_ints(a.M) / 2;
+    c.ptab = c.ttab + 24;
+    c.sm = smem_block + table_doubles(a.M, 6) + slot * (trial_doubles(a.M, 6) + a.extra);
+    if (c.l == 0) c.sm[oVec + D] = 0.0;
+    __syncthreads();
+    // lane constants, without loops or branches
+    int xm = 0, zm = 0, ny = 0;
+#pragma unroll
+    for (int b = 0; b < NQ; ++b) {
+      const int dig = (c.l >> (2 * b)) & 3;
+      xm |= (dig == 1 || dig == 2) << b;
+      zm |= (dig >= 2) << b;
+      ny += dig == 2;
+    }
+    c.xm = xm;
+    c.zm = zm;
+    c.ny = ny & 3;
+    // parameter l: diagonal (l, l), then the T real and the T imaginary parts in the order of np.tril_indices(d, -1);
+    // row ii of entry t is the number of triangular numbers k (k - 1) / 2 <= t, k = 1 .. d - 1
+    const bool diag = c.l < d, imag = c.l >= d + T;
+    const int t = c.l - d - (imag ? T : 0);
+    int ii = 1;
+#pragma unroll
+    for (int k = 2; k < d; ++k) ii += t >= (k * (k - 1)) / 2;
+    c.pkind = diag ? 0 : imag ? 2 : 1;
+    c.pi = diag ? c.l : ii;
+    c.pj = diag ? c.l : t - (ii * (ii - 1)) / 2;
+    const int tt = (c.i * (c.i - 1)) / 2 + c.j;
+    c.src_re = c.i == c.j ? c.i : c.i > c.j ? d + tt : D;
+    c.src_im = c.i > c.j ? d + T + tt : D;
+    // bloch_of (n = 3): lane (x, z) = (i, j) holds the value of Pauli string pauli_index(x, z) = spread(x) ^ 3 spread(z)
+    const int sx = (c.i & 1) | ((c.i & 2) << 1) | ((c.i & 4) << 2), sz = (c.j & 1) | ((c.j & 2) << 1) | ((c.j & 4) << 2);
+    c.bslot = sx ^ (3 * sz);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      c.kT[k] = VCOEF ? pin_vgpr(a.cT[k]) : a.cT[k];
+      c.kP[k] = VCOEF ? pin_vgpr(a.cP[k]) : a.cP[k];
+    }
+  }
+  // the butterfly of gsum<G> from stride KK on: for values already summed over aligned groups of KK lanes
+  template <int KK>
+  __device__ __forceinline__ static double gsum_above(double v) {
+    if (KK < 2) v += dpp_f64<0xB1>(v);
+    if (KK < 4) v += dpp_f64<0x4E>(v);
+    if (G >= 8 && KK < 8) v += dpp_f64<0x141>(v);
+    if (G >= 16 && KK < 16) v += dpp_f64<0x140>(v);
+    if (G == 64) {
+      v += dpp_f64<0x142, 0xA>(v);
+      v += dpp_f64<0x143, 0xC>(v);
+      v = readlane_f64(v, 63);
+    }
+    return v;
+  }
+  // load_freq of the specialised shape.  A lane knows the R-order slot of each of its rows (Prefetch::ri), so the
+  // frequency goes straight there: no parking of the counts in rbuf and no raw[trmap[m]] (two dependent LDS reads)
+  // to fetch them back.  The total is the sum of the per-setting sums the shots check forms anyway, continued over the
+  // settings: every partial sum is an integer-valued double below 2^53, so any order gives the bits of gsum<G>(part).
+  __device__ static bool load_freq(const CtxS& c, const Prefetch& pf) {
+    double dv[4], st[4];
+    bool valid[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      valid[q] = c.l + q * G < c.M;
+      dv[q] = valid[q] ? (double)pf.v[q] : 0.0;
+      st[q] = segsum_c<d>(dv[q]);
+    }
+    const double total = gsum_above<d>((st[0] + st[1]) + (st[2] + st[3]));
+    const double inv = 1.0 / total;
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bad |= valid[q] & !shots_match(st[q], total, pf.ns[q], c.a.ns_tot);
+    double* fq = c.freq();
+    double* dummy = c.rbuf();  // rows beyond M: one slot of a buffer nobody reads before writing it
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *(valid[q] ? fq + pf.ri[q] : dummy) = dv[q] * inv;
+    const unsigned long long votes = __builtin_amdgcn_ballot_w64(bad);
+    const int lane = threadIdx.x & 63;
+    const unsigned long long mine = (G == 64) ? ~0ull : (((1ull << (G & 63)) - 1ull) << (lane / G * G));
+    wave_sync();
+    return (votes & mine) == 0ull;
+  }
+
   // ---- factorised contractions for product POVMs -----------------------------------------------
   __device__ __forceinline__ static int ipow(int b, int e) {
     int r = 1;
@@ -739,10 +950,10 @@ struct Small {
     return acc;
   }
   // All outputs of a stage, two per lane and pass so that their reads overlap.
-  template <bool FWD, int R1C>
-  __device__ __forceinline__ static void stage_run(const Ctx& c, const double* tb, const int* tab, int n_out, int stride,
+  template <bool FWD, int R1C, class C>
+  __device__ __forceinline__ static void stage_run(const C& c, const double* tb, const int* tab, int n_out, int stride,
                                                    const double* in, double* out) {
-    const int R1 = c.pv.pr.R1;
+    const int R1 = c.R1();
     for (int o = c.l; o < n_out; o += 2 * G) {
       const int o2 = o + G;
       const bool two = o2 < n_out;
@@ -753,18 +964,18 @@ struct Small {
       if (two) out[o2] = v1;
     }
   }
-  template <bool FWD>
-  __device__ static void stage(const Ctx& c, const double* tb, const int* tab, int n_out, int stride, const double* in,
+  template <bool FWD, class C>
+  __device__ static void stage(const C& c, const double* tb, const int* tab, int n_out, int stride, const double* in,
                                double* out) {
     if (FWD) stage_run<true, 0>(c, tb, tab, n_out, stride, in, out);
-    else if (c.pv.pr.R1 == 6) stage_run<false, 6>(c, tb, tab, n_out, stride, in, out);
-    else if (c.pv.pr.R1 == 4) stage_run<false, 4>(c, tb, tab, n_out, stride, in, out);
+    else if (c.R1() == 6) stage_run<false, 6>(c, tb, tab, n_out, stride, in, out);
+    else if (c.R1() == 4) stage_run<false, 4>(c, tb, tab, n_out, stride, in, out);
     else stage_run<false, 0>(c, tb, tab, n_out, stride, in, out);
     wave_sync();
   }
-  template <int R1C>
-  __device__ __forceinline__ static double stage_last(const Ctx& c, const double* tb, const int* tab, const double* in) {
-    return stage_value<false, R1C>(tb, c.pv.pr.R1, tab[c.l], 1 << (2 * (NQ - 1)), in);
+  template <int R1C, class C>
+  __device__ __forceinline__ static double stage_last(const C& c, const double* tb, const int* tab, const double* in) {
+    return stage_value<false, R1C>(tb, c.R1(), tab[c.l], 1 << (2 * (NQ - 1)), in);
   }
   // ---- the same stages for a paired table (ProductView::pairedT / pairedP, R1 = 6) ----------------------------
   // Row r = 2a, 2a+1 of such a table is (u_r, 0 .. v_r .. 0) with v_r in column a+1, so a forward output has two
@@ -774,7 +985,8 @@ struct Small {
   // (r_1 .. r_(q-1), k_rest), one per lane and indexed in closed form: 6^(q-1) 4^(n-q) <= G of them.
   __device__ __forceinline__ static int paired_bases(int q) { return ipow(6, q - 1) << (2 * (NQ - q)); }
   // forward stage q < n: the base's four inputs make its six outputs
-  __device__ __forceinline__ static void paired_forward(const Ctx& c, int q, const double* in, double* out) {
+  template <class C>
+  __device__ __forceinline__ static void paired_forward(const C& c, int q, const double* in, double* out) {
     const int lk = 2 * (NQ - q), Kq = 1 << lk;
     if (c.l < paired_bases(q)) {
       const int rpre = c.l >> lk, krest = c.l & (Kq - 1);
@@ -783,13 +995,13 @@ struct Small {
       const double x0 = ib[0];
       const double xa[3] = {ib[Kq], ib[2 * Kq], ib[3 * Kq]};
 #pragma unroll
-      for (int r = 0; r < 6; ++r) ob[r * Kq] = fma(c.pv.pr.cT[2 * r + 1], xa[r >> 1], c.pv.pr.cT[2 * r] * x0);
+      for (int r = 0; r < 6; ++r) ob[r * Kq] = fma(c.cT(2 * r + 1), xa[r >> 1], c.cT(2 * r) * x0);
     }
     wave_sync();
   }
   // backward stage q >= 2: the base's six inputs make its four outputs
-  template <bool PINV>
-  __device__ __forceinline__ static void paired_backward(const Ctx& c, int q, const double* in, double* out) {
+  template <bool PINV, class C>
+  __device__ __forceinline__ static void paired_backward(const C& c, int q, const double* in, double* out) {
     const int lk = 2 * (NQ - q), Kq = 1 << lk;
     if (c.l < paired_bases(q)) {
       const int rpre = c.l >> lk, krest = c.l & (Kq - 1);
@@ -799,12 +1011,12 @@ struct Small {
 #pragma unroll
       for (int t = 0; t < 6; ++t) y[t] = ib[t * Kq];
 #pragma unroll
-      for (int t = 0; t < 6; ++t) acc = fma(PINV ? c.pv.pr.cP[2 * t] : c.pv.pr.cT[2 * t], y[t], acc);
+      for (int t = 0; t < 6; ++t) acc = fma(PINV ? c.cP(2 * t) : c.cT(2 * t), y[t], acc);
       ob[0] = acc;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        const double v0 = PINV ? c.pv.pr.cP[4 * a + 1] : c.pv.pr.cT[4 * a + 1];
-        const double v1 = PINV ? c.pv.pr.cP[4 * a + 3] : c.pv.pr.cT[4 * a + 3];
+        const double v0 = PINV ? c.cP(4 * a + 1) : c.cT(4 * a + 1);
+        const double v1 = PINV ? c.cP(4 * a + 3) : c.cT(4 * a + 3);
         ob[(a + 1) * Kq] = fma(v1, y[2 * a + 1], v0 * y[2 * a]);
       }
     }
@@ -813,15 +1025,13 @@ struct Small {
 
   // Backward pass from Y_n (R-order, in `yn`) to the lane's Y_0[k = l]; PINV: with pinv(T) (A^+ f), else T (A^T y).
   // Intermediates ping-pong between bufB and rbuf; `yn` itself is only read.
-  template <bool PINV>
-  __device__ static double prod_backward(const Ctx& c, const double* yn) {
-    const int R1 = c.pv.pr.R1;
+  template <bool PINV, class C>
+  __device__ static double prod_backward(const C& c, const double* yn) {
     const double* tb = PINV ? c.tabP() : c.tabT();
-    const int* tab = c.tbwd;
     const double* in = yn;
     double* bufs[2] = {c.bufB(), c.rbuf()};
     int which = 0;
-    if (PINV ? c.pv.pr.pairedP : c.pv.pr.pairedT) {
+    if (PINV ? c.pairedP() : c.pairedT()) {
 #pragma unroll
       for (int q = NQ; q >= 2; --q) {
         paired_backward<PINV>(c, q, in, bufs[which]);
@@ -832,19 +1042,25 @@ struct Small {
       const int lk = 2 * (NQ - 1);
       return stage_value<false, 6>(tb, 6, (c.l & ((1 << lk) - 1)) | (c.l >> lk) << 16, 1 << lk, in);
     }
+    if constexpr (C::kGeneric) {
+      const int R1 = c.R1();
+      const int* tab = c.tbwd;
 #pragma unroll
-    for (int q = NQ; q >= 2; --q) {
-      const int stride = 1 << (2 * (NQ - q));             // 4^(n-q)
-      const int n_out = ipow(R1, q - 1) * 4 * stride;
-      stage<false>(c, tb, tab, n_out, stride, in, bufs[which]);
-      tab += n_out;
-      in = bufs[which];
-      which ^= 1;
+      for (int q = NQ; q >= 2; --q) {
+        const int stride = 1 << (2 * (NQ - q));             // 4^(n-q)
+        const int n_out = ipow(R1, q - 1) * 4 * stride;
+        stage<false>(c, tb, tab, n_out, stride, in, bufs[which]);
+        tab += n_out;
+        in = bufs[which];
+        which ^= 1;
+      }
+      // stage 1: D outputs, one per lane
+      if (R1 == 6) return stage_last<6>(c, tb, tab, in);
+      if (R1 == 4) return stage_last<4>(c, tb, tab, in);
+      return stage_last<0>(c, tb, tab, in);
+    } else {
+      return 0.0;  // (not reached: both tables of the specialised shape are paired)
     }
-    // stage 1: D outputs, one per lane
-    if (R1 == 6) return stage_last<6>(c, tb, tab, in);
-    if (R1 == 4) return stage_last<4>(c, tb, tab, in);
-    return stage_last<0>(c, tb, tab, in);
   }
   // Forward stage n fused with the log-likelihood terms: p = d w (.) X_n + 1e-10, the lane's share of
   // sum freq log p (returned), and Y_n = w (.) freq / p into `rb` (A'^T r = K^T (w (.) r)).  Two outputs per pass
@@ -853,14 +1069,18 @@ struct Small {
   // PAIRED (ProductView::pairedT): a row keeps its lane -- the order of the sum over rows is part of the value's
   // bits -- and reads its two non-zero coefficients and their operands through the entries of ProductView::last.
   // UNI: equal shots, every row weight is wuni (the same division as wrowR[m]).
-  template <bool PAIRED, bool UNI>
-  __device__ __forceinline__ static double stage_n_log(const Ctx& c, const int* tab, const double* in, const double* fr,
+  template <bool PAIRED, bool UNI, class C>
+  __device__ __forceinline__ static double stage_n_log(const C& c, const int* tab, const double* in, const double* fr,
                                                        double* rb) {
     const double* tb = c.tabT();
     auto x_of = [&](int ent) {
-      if (!PAIRED) return stage_value<true>(tb, c.pv.pr.R1, ent, 1, in);
+      if (!PAIRED) return stage_value<true>(tb, c.R1(), ent, 1, in);
       const int vi = ent >> 16;
       return fma(tb[vi], in[(ent >> 8) & 0xff], tb[vi & ~3] * in[ent & 0xff]);
+    };
+    auto w_of = [&](int o) {
+      if constexpr (UNI) return c.wuni();
+      else return c.twrow[o];
     };
     double fpart = 0.0;
     for (int o = c.l; o < c.M; o += 2 * G) {
@@ -869,7 +1089,7 @@ struct Small {
       const int oo = two ? o2 : o;
       const int e0 = tab[o], e1 = tab[oo];
       const double x0 = x_of(e0), x1 = x_of(e1);
-      const double w0 = UNI ? c.pv.pr.wuni : c.twrow[o], w1 = UNI ? c.pv.pr.wuni : c.twrow[oo];
+      const double w0 = w_of(o), w1 = w_of(oo);
       const double f0 = fr[o], f1 = fr[oo];
       const double p0 = x0 * w0 * d + 1e-10, p1 = x1 * w1 * d + 1e-10;
       const double l0 = fast_log(p0), l1 = fast_log(p1);
@@ -883,20 +1103,25 @@ struct Small {
     return fpart;
   }
   // sum_m Op[m][lane] * vec[m]   (lane = column)
-  __device__ __forceinline__ static double col_dot(const Ctx& c, const double* g_rowmajor, const double* vec) {
+  template <class C>
+  __device__ __forceinline__ static double col_dot(const C& c, const double* g_rowmajor, const double* vec) {
     return dot_global<16>(g_rowmajor, D, (unsigned)c.l, vec, c.M);
   }
   // sum_k Op[row][k] * vec[k]    (lane = row), g_transposed = [D][M]
-  __device__ __forceinline__ static double row_dot(const Ctx& c, const double* g_transposed, int row, const double* vec) {
+  template <class C>
+  __device__ __forceinline__ static double row_dot(const C& c, const double* g_transposed, int row, const double* vec) {
     return dot_global<(D < 16 ? D : 16)>(g_transposed, (size_t)c.M, (unsigned)row, vec, D);
   }
 
   // ---- a6: linear inversion (operand PinvT).  Returns lane's element of rho; vec() = Bloch vector.
-  __device__ static cd lin_invert(const Ctx& c, double& bloch_l) {
-    if (c.prod()) {
-      if (c.pv.pr.uniform) {
+  template <class C>
+  __device__ static cd lin_invert(const C& c, double& bloch_l) {
+    if constexpr (!C::kGeneric) {
+      bloch_l = prod_backward<true>(c, c.freq()) / (c.wuni() * d);
+    } else if (c.prod()) {
+      if (c.uniform()) {
         // pinv(w K) = pinv(T)^(x n) / w : the same backward pass with pinv(T) instead of T
-        bloch_l = prod_backward<true>(c, c.freq()) / (c.pv.pr.wuni * d);
+        bloch_l = prod_backward<true>(c, c.freq()) / (c.wuni() * d);
       } else {  // unequal shots per setting: dense left inverse, rows visited in R-order
         double acc = 0.0;
         for (int m = 0; m < c.M; ++m) acc = fma(c.pv.PinvT[(size_t)c.trmap[m] * D + c.l], c.freq()[m], acc);
@@ -918,7 +1143,8 @@ struct Small {
   // round is ONE LDS round trip: the lanes publish A and V, then each lane reads the two 2x2
   // blocks that define the rotations of its column pair {j, j^r} and row pair {i, i^r} together
   // with its three partner elements, and applies A' = J^dagger A J, V' = V J in registers.
-  __device__ static cd psd_project(const Ctx& c, cd a, double eps) {
+  template <class C>
+  __device__ static cd psd_project(const C& c, cd a, double eps) {
     const int i = c.i, j = c.j;
     cd* Ai = c.A();
     cd* Vi = c.V();
@@ -927,7 +1153,7 @@ struct Small {
     const double nrm = gsum<G>(a.re * a.re + a.im * a.im);  // Frobenius norm: invariant
     for (int sweep = 0; sweep < 20; ++sweep) {
       const double off = gsum<G>(i != j ? a.re * a.re + a.im * a.im : 0.0);
-      if (__all(!(off > c.pv.jtol2 * nrm))) break;
+      if (__all(!(off > c.jtol2() * nrm))) break;
 #pragma unroll 1
       for (int r = 1; r < d; ++r) {
         Ai[c.e] = a;
@@ -987,8 +1213,8 @@ struct Small {
   // skips ~3 k of its ~39 k clocks (the launch ends with its slowest wave, and those are the clipped trials); a
   // positive definite one throws the inverse away, ~1.5 k clocks it had to spare.  Same arithmetic, same bits, as the
   // loop in lift_single_negative.  *spec_inv = this lane's element of the inverse (garbage unless kneg = d - 1).
-  template <bool SPEC = false>
-  __device__ static double cholesky_param(const Ctx& c, cd a, int& ok, int* neg_out = nullptr, int* kneg_out = nullptr,
+  template <bool SPEC = false, class C>
+  __device__ static double cholesky_param(const C& c, cd a, int& ok, int* neg_out = nullptr, int* kneg_out = nullptr,
                                           cd* spec_inv = nullptr) {
     cd* A = c.A();
     cd* L = c.Bm();
@@ -1073,7 +1299,8 @@ struct Small {
   // lam_1 = Tr(A N) < eps, and ||A N - lam_1 N||_F <= 1e-13 ||A||_F.  Returns false (caller runs the
   // Jacobi eigensolver on the untouched input) on a slow ratio, a positive lam, or a failed check.
   // `inverse`: the lane's element of A^{-1} when the caller already has it (cholesky_param<true>, kneg = d - 1).
-  __device__ static bool lift_single_negative(const Ctx& c, cd r, int kneg, double eps, cd& out,
+  template <class C>
+  __device__ static bool lift_single_negative(const C& c, cd r, int kneg, double eps, cd& out,
                                               const cd* inverse = nullptr) {
     static_assert(G == 64, "one trial per wavefront: the flags below are wave-uniform");
     cd* Ai = c.A();
@@ -1162,8 +1389,8 @@ struct Small {
   // definite (its Cholesky factorisation runs through) no eigenvalue is below the clip, so
   // U max(v, 1e-15) U^dagger is the input itself (to rounding) and only the trace division is left.
   // Returns the projected element; if `xl` is non-null also the Cholesky parameter of the result.
-  template <bool SPEC = false>
-  __device__ static cd make_feasible(const Ctx& c, cd r, double* xl, int* ok_out, double* lscale_out = nullptr) {
+  template <bool SPEC = false, class C>
+  __device__ static cd make_feasible(const C& c, cd r, double* xl, int* ok_out, double* lscale_out = nullptr) {
     int ok, neg, kneg;
     cd spec_inv{0.0, 0.0};
     double x = cholesky_param<SPEC && G == 64>(c, r, ok, &neg, &kneg, &spec_inv);
@@ -1210,7 +1437,8 @@ struct Small {
   }
 
   // x (one parameter per lane) -> L in Bm(), returns lane's element of L L^dagger and t = Tr.
-  __device__ static cd build_llh(const Ctx& c, double xl, double& tr) {
+  template <class C>
+  __device__ static cd build_llh(const C& c, double xl, double& tr) {
     double* vx = c.vec();
     cd* L = c.Bm();
     vx[c.l] = xl;
@@ -1237,7 +1465,8 @@ struct Small {
     cd rho;         // this lane's element of the normalised start matrix
     double lscale;  // L(x) = lscale * Bm()
   };
-  __device__ static void nll_grad(const Ctx& c, double xl, double& f, double& gl, cd* rho_l = nullptr,
+  template <class C>
+  __device__ static void nll_grad(const C& c, double xl, double& f, double& gl, cd* rho_l = nullptr,
                                   bool want_grad = true, const StartPoint* start = nullptr) {
     double tr;
     QT_STAMP(11);
@@ -1265,8 +1494,8 @@ struct Small {
     double* rb = c.rbuf();
     double wl;
     if (c.prod()) {
-      const int R1 = c.pv.pr.R1;
-      const bool paired = c.pv.pr.pairedT != 0;
+      const int R1 = c.R1();
+      const bool paired = c.pairedT() != 0;
       const int* tab = c.tfwd;
       const double* in = vec;
 #pragma unroll
@@ -1276,23 +1505,27 @@ struct Small {
         double* out = ((NQ - 1 - q) & 1) ? rb : c.bufB();
         if (paired) {
           paired_forward(c, q, in, out);
-        } else {
+        } else if constexpr (C::kGeneric) {
           stage<true>(c, c.tabT(), tab, n_out, stride, in, out);
           tab += n_out;
         }
         in = out;
       }
       QT_STAMP(14);
-      if (!paired) fpart = stage_n_log<false, false>(c, tab, in, fr, rb);
-      else if (c.pv.pr.uniform) fpart = stage_n_log<true, true>(c, tab, in, fr, rb);
-      else fpart = stage_n_log<true, false>(c, tab, in, fr, rb);
+      if constexpr (!C::kGeneric) {
+        fpart = stage_n_log<true, true>(c, tab, in, fr, rb);
+      } else {
+        if (!paired) fpart = stage_n_log<false, false>(c, tab, in, fr, rb);
+        else if (c.uniform()) fpart = stage_n_log<true, true>(c, tab, in, fr, rb);
+        else fpart = stage_n_log<true, false>(c, tab, in, fr, rb);
+      }
       f = -gsum<G>(fpart);
       wave_sync();
       QT_STAMP(15);
       if (!want_grad) return;  // (uniform) the Metropolis chain only needs the value
       wl = prod_backward<false>(c, rb);
       QT_STAMP(16);
-    } else {
+    } else if constexpr (C::kGeneric) {
       for (int m0 = 0; m0 < c.M; m0 += G) {
         const int mm = m0 + c.l;
         if (mm < c.M) {
@@ -1337,7 +1570,8 @@ struct Small {
   // sqrt(|Tr((R - C)^2)|) / sqrt(2) for the matrix R held one element (i, j) per lane (geometry.py:16-20):
   // Tr(Delta Delta) = sum_ij Delta_ij Delta_ji, the transposed element fetched from lane (j, i) of the group.
   // Executed by every lane of the wavefront (DPP reductions); every lane of a group returns the same bits.
-  __device__ __forceinline__ static double hs_to_centre(const Ctx& c, cd r, const double* __restrict__ centre) {
+  template <class C>
+  __device__ __forceinline__ static double hs_to_centre(const C& c, cd r, const double* __restrict__ centre) {
     const double2 cc = *reinterpret_cast<const double2*>(centre + 2 * c.l);
     const cd dl{r.re - cc.x, r.im - cc.y};
     const int src = (int)(threadIdx.x & 63) - c.l + c.j * d + c.i;
@@ -1350,7 +1584,8 @@ struct Small {
   }
   // Result of trial b: element (i, j) = r.  `store` = this lane's group owns a live trial; the distance is computed by
   // all lanes (o.dist is uniform over the launch), only the stores are masked.
-  __device__ __forceinline__ static void emit(const Ctx& c, const EstOut& o, int b, bool store, cd r) {
+  template <class C>
+  __device__ __forceinline__ static void emit(const C& c, const EstOut& o, int b, bool store, cd r) {
     if (o.dist) {
       const double v = hs_to_centre(c, r, o.centre);
       if (store && c.l == 0) o.dist[b] = v;
@@ -1465,8 +1700,8 @@ __global__ void __launch_bounds__(256) k_nll_batch(PovmView pv, const double* __
 // Held to four wavefronts per SIMD (128 VGPRs): the saturated batches run four workgroups per CU, and one
 // register more -- the EstOut pointers of round 3 made it 129 -- takes a workgroup off every CU (measured: 0.372 -> 0.416 ms
 // per 65 536 trials).
-template <int NQ>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_mle_start(PovmView pv, const int64_t* __restrict__ counts, int B, int init,
+template <int NQ, bool GENERIC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_mle_start(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int init,
                                                    int max_iter, double gtol, EstOut rho,
                                                    int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                    double* __restrict__ fun_out, int32_t* __restrict__ status_out,
@@ -1475,14 +1710,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   using S = Small<NQ>;
   constexpr int D = S::D, G = S::G, d = S::d;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::Ctx c;
+  typename S::template CtxOf<GENERIC>::type c;
   bool live;
   const int b = S::trial_index(B, &live);
   const int bb = live ? b : B - 1;
   typename S::Prefetch pf;
   S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
-  S::make_ctx(c, smem, pv);
-  const bool shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
+  bool shots_ok;
+  if constexpr (GENERIC) {
+    S::make_ctx(c, smem, pv);
+    shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
+  } else {
+    S::make_ctx(c, smem, pv, pf);
+    shots_ok = S::load_freq(c, pf);
+  }
   int ok;
   double xk;
   typename S::StartPoint sp;
@@ -1529,8 +1770,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
 // meet gtol.  One (value, gradient) evaluation per loop pass; the line search is the state machine of
 // qt_linesearch.h; the inverse Hessian is one row per lane in registers.  `mine` marks the groups that
 // iterate; the others idle through the evaluations on finite dummy values.
-template <int NQ>
-__device__ __forceinline__ void bfgs_iterate(const typename Small<NQ>::Ctx& c, bool mine, double xk, double gk,
+template <int NQ, class C>
+__device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, double gk,
                                              double fk, int b, int max_iter, double gtol, EstOut rho,
                                              int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                              double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
@@ -1671,8 +1912,8 @@ __device__ __forceinline__ void bfgs_iterate(const typename Small<NQ>::Ctx& c, b
 // (tests/test_gpu_state.py runs the reference's 70 golden trials through both).
 // LP > 0 (k_mle_fused: one workgroup per CU, LDS to spare): the first LP pairs stay in the trial's LDS and only later
 // ones go to the global workspace -- a lone wave would otherwise wait out an L2 round trip per block of pairs.
-template <int NQ, int LP = 0>
-__device__ __forceinline__ void bfgs_iterate_2l(const typename Small<NQ>::Ctx& c, bool mine, double xk, double gk,
+template <int NQ, int LP = 0, class C>
+__device__ __forceinline__ void bfgs_iterate_2l(const C& c, bool mine, double xk, double gk,
                                                 double fk, int b, int max_iter, double gtol, EstOut rho,
                                                 int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                 double* __restrict__ fun_out, int32_t* __restrict__ status_out,
@@ -1804,8 +2045,8 @@ __device__ __forceinline__ void bfgs_iterate_2l(const typename Small<NQ>::Ctx& c
 #define QT_BFGS_WAVES 2  // waves per SIMD the BFGS kernel is compiled for; measured at B = 65 536 (15-iteration trials): 3 waves
                          // (<= 168 VGPRs, 18 spilled) 5.29 ms, 2 waves (205 VGPRs, no scratch) 5.39 ms -- instruction-bound either way
 #endif
-template <int NQ>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFGS_WAVES))) k_mle_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B, int max_iter,
+template <int NQ, bool GENERIC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFGS_WAVES))) k_mle_bfgs(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
                                                   double gtol, EstOut rho, int32_t* __restrict__ nit_out,
                                                   int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                   int32_t* __restrict__ status_out, const double* __restrict__ ws_x,
@@ -1818,10 +2059,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFG
   const bool mine = live && ws_active[b] != 0;
   if (!__syncthreads_or(mine)) return;  // nothing left to iterate in this workgroup
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::Ctx c;
-  S::make_ctx(c, smem, pv);
+  typename S::template CtxOf<GENERIC>::type c;
   const int bb = live ? b : B - 1;
-  S::load_freq(c, counts + (size_t)bb * pv.M);
+  if constexpr (GENERIC) {
+    S::make_ctx(c, smem, pv);
+    S::load_freq(c, counts + (size_t)bb * pv.M);
+  } else {
+    typename S::Prefetch pf;
+    S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
+    S::make_ctx(c, smem, pv, pf);
+    S::load_freq(c, pf);
+  }
   // inactive trials of a live wave idle through the loop on dummy finite values
   const double xk = mine ? ws_x[(size_t)b * D + c.l] : (c.l < S::d ? 1.0 : 0.0);
   const double gk = mine ? ws_g[(size_t)b * D + c.l] : 0.0;
@@ -1839,8 +2087,8 @@ constexpr int kFusedLdsPairs = 24;  // (s, y) pairs of k_mle_fused<3> kept in LD
 // a10 in ONE launch, for batches small enough that its 256-VGPR footprint (two waves per SIMD) is no
 // handicap: start point, first evaluation and -- for the waves that still hold an open trial -- the BFGS
 // loop.  Saves the second launch (2.5-4 us when nothing iterates, ~10 % of a 1000-trial step).
-template <int NQ>
-__device__ __forceinline__ void mle_fused_body(const PovmView& pv, const int64_t* __restrict__ counts, int B, int init,
+template <int NQ, bool GENERIC>
+__device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::type& pv, const int64_t* __restrict__ counts, int B, int init,
                                                int max_iter, double gtol, EstOut rho,
                                                int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                double* __restrict__ fun_out, int32_t* __restrict__ status_out,
@@ -1848,15 +2096,22 @@ __device__ __forceinline__ void mle_fused_body(const PovmView& pv, const int64_t
   using S = Small<NQ>;
   constexpr int D = S::D, G = S::G, d = S::d;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::Ctx c;
+  typename S::template CtxOf<GENERIC>::type c;
   bool live;
   const int b = S::trial_index(B, &live);
   const int bb = live ? b : B - 1;
   typename S::Prefetch pf;
   S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
-  S::make_ctx(c, smem, pv);
-  QT_STAMP(0);
-  const bool shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
+  bool shots_ok;
+  if constexpr (GENERIC) {
+    S::make_ctx(c, smem, pv);
+    QT_STAMP(0);
+    shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
+  } else {
+    S::template make_ctx<true>(c, smem, pv, pf);
+    QT_STAMP(0);
+    shots_ok = S::load_freq(c, pf);
+  }
   QT_STAMP(1);
   int ok;
   double xk;
@@ -1916,20 +2171,20 @@ __device__ __forceinline__ void mle_fused_body(const PovmView& pv, const int64_t
 // Two entry points over the same body: the fully mixed start (`init = 'mixed'`: every trial iterates, ~10x the duration)
 // runs under its own kernel name, so that a profiler's per-kernel average of k_mle_fused is the average of the
 // 'lin'-start launches (bench.py's timed steps) and not a mixture with the iterating side measurements.
-template <int NQ>
-__global__ void __launch_bounds__(256) k_mle_fused(PovmView pv, const int64_t* __restrict__ counts, int B, int max_iter,
+template <int NQ, bool GENERIC>
+__global__ void __launch_bounds__(256) k_mle_fused(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
                                                    double gtol, EstOut rho, int32_t* __restrict__ nit_out,
                                                    int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                    int32_t* __restrict__ status_out, double* __restrict__ pairs) {
-  mle_fused_body<NQ>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ, GENERIC>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
-template <int NQ>
-__global__ void __launch_bounds__(256) k_mle_fused_mixed(PovmView pv, const int64_t* __restrict__ counts, int B,
+template <int NQ, bool GENERIC>
+__global__ void __launch_bounds__(256) k_mle_fused_mixed(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B,
                                                          int max_iter, double gtol, EstOut rho,
                                                          int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                          double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                          double* __restrict__ pairs) {
-  mle_fused_body<NQ>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ, GENERIC>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 
 // Metropolis-Hastings chain on the Cholesky parameters (reference mhmc.py:80-119 with

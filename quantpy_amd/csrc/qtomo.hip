@@ -99,7 +99,7 @@ struct qt_handle {
   DevBuf kron_dig;
   int kron_S1 = 0, kron_K1 = 0;
   // product-POVM (Kronecker) description, valid when prod.enabled
-  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd, pr_last;
+  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd, pr_last, pr_image;
   qt::ProductView prod{};
   // staging for host-pointer calls: one buffer per array of a call, in the order the call registers them (Call)
   DevBuf stage[kStageBufs];
@@ -126,6 +126,25 @@ struct qt_handle {
   double ns_max = 0.0;  // largest registered shot number (product POVMs): the n >= 4 count cache holds 32-bit counts
   bool paired_stages = true;  // qt_set_option(QT_OPT_PAIRED_STAGES): let paired tables take their own stages (n <= 3)
   int paired_tables = 0;      // what qt_set_povm_product found: bit 0 = T is paired, bit 1 = pinv(T)^T is
+  // qt_set_option(QT_OPT_MLE_SPECIALISE): let an eligible POVM take the specialised MLE kernels (GENERIC = false, n <= 3)
+  bool mle_specialise = true;
+  bool image_ready = false;    // pr_image holds the table image of the current POVM (built when both tables are paired)
+  bool last_mle_spec = false;  // which instantiation the last MLE launch took (qt_get_mle_specialised)
+  // The shape the specialised kernels are compiled for (qt::SpecArgs): three two-outcome settings per qubit (R1 = 6,
+  // K = d, M = 6^n <= 4 G and the segmented shots check), both tables paired and their stages on, equal shots, the
+  // shots check on.  Everything else -- 'sic', 'proj4', 'proj', unequal shots, plain arrays -- takes the generic body.
+  bool spec_eligible() const {
+    return mle_specialise && nq <= 3 && povm_set && prod.enabled && prod.R1 == 6 && K == d && paired_stages &&
+           paired_tables == 3 && image_ready && prod.uniform && check_shots;
+  }
+  qt::SpecArgs spec_args(int extra) const {
+    qt::SpecArgs a{pr_image.p, Ns.as<double>(), ns_tot, prod.wuni, jtol2, M, extra, {}, {}};
+    for (int k = 0; k < 12; ++k) {
+      a.cT[k] = prod.cT[k];
+      a.cP[k] = prod.cP[k];
+    }
+    return a;
+  }
   // the POVM as the estimator kernels read it; `extra` (PovmView::extra) comes with the launch's LDS size (Plan)
   qt::PovmView view(int extra) const {
     qt::PovmView v{Aw.as<double>(), AwT.as<double>(), PinvT.as<double>(), M, prod, jtol2,
@@ -548,6 +567,7 @@ int begin_povm(qt_handle_t* h, int S, int K) {
   h->dense_ready = h->a_loaded = h->pinv_ready = false;
   h->prod = qt::ProductView{};
   h->paired_tables = 0;
+  h->image_ready = false;
   h->S = S;
   h->K = K;
   h->M = (int)M;
@@ -627,10 +647,16 @@ struct MleArrays {
 
 // The split MLE pair: k_mle_start / k_mle_bfgs (qt_small.h) at n <= 3, k_mle_large_start / k_mle_large_bfgs (qt_large.h)
 // at n = 4, 5.
-template <int NQ>
+template <int NQ, bool GENERIC>
 auto mle_split_kernels() {
-  if constexpr (NQ <= 3) return std::make_pair(qt::k_mle_start<NQ>, qt::k_mle_bfgs<NQ>);
+  if constexpr (NQ <= 3) return std::make_pair(qt::k_mle_start<NQ, GENERIC>, qt::k_mle_bfgs<NQ, GENERIC>);
   else return std::make_pair(qt::k_mle_large_start<NQ>, qt::k_mle_large_bfgs<NQ>);
+}
+// The POVM argument of an n <= 3 MLE kernel: the PovmView of the plan, or the slim struct of the specialised instantiation.
+template <bool GENERIC>
+auto mle_povm_arg(const qt_handle_t* h, const Plan& p) {
+  if constexpr (GENERIC) return p.pv;
+  else return h->spec_args(p.pv.extra);
 }
 
 // a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch and qt_mle_dist_batch
@@ -666,6 +692,7 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
   if (h->nq == 3 && max_iter > 2000)
     return fail(QT_ERR_UNSUPPORTED, "max_iter > 2000 is not supported for n_qubits = 3 (LDS holds the two-loop scalars)");
   const int mi = max_iter > 0 ? max_iter : 1;
+  h->last_mle_spec = h->spec_eligible();
   return by_nq(h, [&](auto nq) -> int {
     constexpr int NQ = decltype(nq)::value;
     if constexpr (NQ <= 3) {
@@ -680,9 +707,12 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
           HIPCHK(h->hess.ensure((size_t)B * over * 2 * h->D * sizeof(double)));
         }
         const Plan p = povm_plan<NQ>(h, B, extra);
-        if (int r = launch(h, init == QT_INIT_LIN ? qt::k_mle_fused<NQ> : qt::k_mle_fused_mixed<NQ>, p, p.pv, dc, B, max_iter,
-                           tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>()))
-          return r;
+        auto fused = [&](auto generic) {
+          constexpr bool GEN = decltype(generic)::value;
+          return launch(h, init == QT_INIT_LIN ? qt::k_mle_fused<NQ, GEN> : qt::k_mle_fused_mixed<NQ, GEN>, p,
+                        mle_povm_arg<GEN>(h, p), dc, B, max_iter, tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>());
+        };
+        if (int r = h->last_mle_spec ? fused(std::false_type()) : fused(std::true_type())) return r;
         return c.done(status, B);
       }
     }
@@ -702,22 +732,27 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
     }
     const MleArrays all{dc, eo, dnit, dnfev, dfun, dst, h->ws_x.as<double>(), h->ws_g.as<double>(), h->ws_f.as<double>(),
                         h->ws_act.as<int32_t>(), h->M, h->D};
-    const auto [k_start, k_bfgs] = mle_split_kernels<NQ>();
     // start point + first evaluation of every trial; then the BFGS loop of those that iterate, chunk by chunk, with
     // rho_i, alpha_i (and at n = 3 the parked line-search state) in LDS
-    const Plan ps = povm_plan<NQ>(h, B);
-    if (int r = launch(h, k_start, ps, ps.pv, dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, all.x, all.g, all.f, all.act))
-      return r;
-    const int extra = NQ >= 4 ? max_iter : (NQ == 3 ? qt::LineSearch::SLOTS + 2 * mi : 0);
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-      const int nb = B - b0 < chunk ? B - b0 : chunk;
-      const MleArrays a = all.at(b0);
-      const Plan p = povm_plan<NQ>(h, nb, extra);
-      if (int r = launch(h, k_bfgs, p, p.pv, a.counts, nb, max_iter, tol, a.eo, a.nit, a.nfev, a.fun, a.status, a.x, a.g, a.f,
-                         a.act, h->hess.as<double>()))
+    auto split = [&](auto generic) -> int {
+      constexpr bool GEN = decltype(generic)::value || NQ >= 4;
+      const auto [k_start, k_bfgs] = mle_split_kernels<NQ, GEN>();
+      const Plan ps = povm_plan<NQ>(h, B);
+      if (int r = launch(h, k_start, ps, mle_povm_arg<GEN>(h, ps), dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, all.x,
+                         all.g, all.f, all.act))
         return r;
-    }
-    return c.done(status, B);
+      const int extra = NQ >= 4 ? max_iter : (NQ == 3 ? qt::LineSearch::SLOTS + 2 * mi : 0);
+      for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = B - b0 < chunk ? B - b0 : chunk;
+        const MleArrays a = all.at(b0);
+        const Plan p = povm_plan<NQ>(h, nb, extra);
+        if (int r = launch(h, k_bfgs, p, mle_povm_arg<GEN>(h, p), a.counts, nb, max_iter, tol, a.eo, a.nit, a.nfev, a.fun,
+                           a.status, a.x, a.g, a.f, a.act, h->hess.as<double>()))
+          return r;
+      }
+      return c.done(status, B);
+    };
+    return h->last_mle_spec ? split(std::false_type()) : split(std::true_type());
   });
 }
 
@@ -905,6 +940,7 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
       h->fused_max_waves = (int)value;
       return 0;
     case QT_OPT_PAIRED_STAGES: h->paired_stages = value != 0.0; return 0;
+    case QT_OPT_MLE_SPECIALISE: h->mle_specialise = value != 0.0; return 0;
     default: return fail(QT_ERR_ARG, "unknown option %d", option);
   }
 }
@@ -912,6 +948,11 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
 int qt_get_paired_tables(qt_handle_t* h) {
   QT_ENTER(h);
   return h->povm_set && h->prod.enabled ? h->paired_tables : 0;
+}
+
+int qt_get_mle_specialised(qt_handle_t* h) {
+  QT_ENTER(h);
+  return h->last_mle_spec ? 1 : 0;
 }
 
 int qt_timer_begin(qt_handle_t* h) {
@@ -1114,6 +1155,23 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
   }
   h->prod.last = h->pr_last.as<int>();
   h->paired_tables = (pairedT ? 1 : 0) | (pairedP ? 2 : 0);
+  if (pairedT && pairedP && K == (1 << n)) {
+    // The table image of the specialised MLE kernels (qt::SpecArgs::image): the workgroup's LDS table block in its
+    // final layout -- `last` padded to four entries, T, pinv(T)^T as the device computed it -- and rinv behind it.
+    const int nl = (int)((M + 3) & ~3LL);
+    std::vector<int> image((size_t)nl + 2 * 48 + (size_t)M, 0);
+    for (long long o = 0; o < M; ++o) {
+      const int rpre = (int)(o / 6), r = (int)(o % 6), a = r / 2;
+      image[(size_t)o] = (4 * rpre) | (4 * rpre + a + 1) << 8 | (4 * r + a + 1) << 16;
+    }
+    memcpy(image.data() + nl, t1.data(), 24 * sizeof(double));
+    memcpy(image.data() + nl + 48, p1t, 24 * sizeof(double));
+    memcpy(image.data() + nl + 96, rinv.data(), (size_t)M * sizeof(int));
+    HIPCHK(h->pr_image.ensure(image.size() * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(h->pr_image.p, image.data(), image.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->image_ready = true;
+  }
   h->prod.T = h->pr_T.as<double>();
   h->prod.P1T = h->pr_P1T.as<double>();
   h->prod.wrowR = h->pr_wrow.as<double>();

@@ -180,7 +180,9 @@ class Engine:
     def set_option(self, option, value):
         """qt_set_option: _capi.QT_OPT_SHOTS_CHECK (0 / 1), _capi.QT_OPT_MLE_FUSED_MAX_WAVES (0 = always the split,
         two-loop BFGS path), _capi.QT_OPT_PAIRED_STAGES (0 = the dense-table contraction stages for every one-qubit
-        table, 1 = the zero-skipping stages where `paired_tables` says so; the same bits either way)."""
+        table, 1 = the zero-skipping stages where `paired_tables` says so; the same bits either way),
+        _capi.QT_OPT_MLE_SPECIALISE (0 = the generic MLE kernels for every POVM, 1 = the instantiation compiled for the
+        six-projector shape where the POVM has it, see `mle_specialised`; the same bits either way)."""
         self._chk(self.lib.qt_set_option(self._h, int(option), float(value)))
 
     @property
@@ -188,6 +190,12 @@ class Engine:
         """Bit 0: the one-qubit table of the current product POVM is paired (six rows, rows 2a and 2a+1 exactly zero
         outside columns 0 and a+1); bit 1: so is its pseudo-inverse as the device computed it.  0 at n >= 4."""
         return self._chk(self.lib.qt_get_paired_tables(self._h))
+
+    @property
+    def mle_specialised(self):
+        """True if the last `mle` / `mle_dist` launch took the MLE kernels specialised on the POVM's shape (n <= 3:
+        'proj-set' with equal shots per setting, paired stages and the shots check on), False if the generic ones."""
+        return bool(self._chk(self.lib.qt_get_mle_specialised(self._h)))
 
     def timer_begin(self):
         self._chk(self.lib.qt_timer_begin(self._h))
