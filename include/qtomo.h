@@ -240,9 +240,21 @@ int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengt
  * mean[b], var[b] of ||P (f_b - p)||^2 under multinomial noise, f_b[s][k] = counts[b][s][k] / ns[s] (interval.py:73,
  * :82), n_trials = the shots per setting (interval.py:89: n_measurements[0]), weights W = P^T P with
  * P = inv_matrix[rows][S*K] (the left inverse of the design matrix / dim, interval.py:75-87; W is formed on the matrix
- * cores).  For process tomography S = (input states) x (settings).  S * K <= 8192. */
+ * cores).  For process tomography S = (input states) x (settings).  Up to S * K = 8192 rows one workgroup keeps the
+ * frequencies of its trials in LDS; above that the counts are turned into frequencies first and take the kernels of
+ * qt_moment_freq_batch (a three-qubit process with 'proj-set' has 64 x 216 = 13 824 rows).  S * K <= 32 768, where W
+ * takes 8 GiB (QT_ERR_UNSUPPORTED beyond). */
 int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, const double* ns, const double* inv_matrix,
                     int rows, double n_trials, double* mean, double* var, int flags);
+/* The same moments from frequencies given directly, freq[B][S*K]: the reference forms results / n_measurements[:, None]
+ * in floating point (interval.py:70-90) and its sums (stats.py:21-47) take any real frequencies, e.g. expected counts
+ * N p that are not integers.  W is split over the grid by columns (whole settings, or pieces of one when K > 256) and by
+ * runs of settings; the workgroups' partial sums are added in a fixed order by a second kernel, without atomics: the
+ * same input gives the same bits on every call, and a trial the same bits alone and in a batch.  LDS does not grow
+ * with S, K or S * K; any S >= 1 and K >= 1 with S * K <= 32 768.  Fed counts / ns it returns the bits of
+ * qt_moment_batch above 8192 rows; at or below, the two sum in different orders. */
+int qt_moment_freq_batch(qt_handle_t* h, const double* freq, int B, int S, int K, const double* inv_matrix, int rows,
+                         double n_trials, double* mean, double* var, int flags);
 
 /* ---- f3: quantpy/tomography/interval.py:268-335 (PolytopeStateInterval: 2 * n_points cvxopt `solvers.lp` calls) -----
  * R x O dense linear programs that share one constraint matrix:

@@ -67,6 +67,7 @@ SIGNATURES = {
     "qt_select_finish": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp, _vp, _vp, _c_int]),
     "qt_merge_sorted": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_moment_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_dbl, _vp, _vp, _c_int]),
+    "qt_moment_freq_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_dbl, _vp, _vp, _c_int]),
     "qt_lp_ineq_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
     "qt_lp_ineq_large_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
     "qt_polytope_confidence": (_c_int, [_vp, _vp, ctypes.c_longlong, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int]),

@@ -956,6 +956,174 @@ __global__ void __launch_bounds__(256) k_moment_batch(const int64_t* __restrict_
   }
 }
 
+// ---- f2 at any M: the same five sums from frequencies, with LDS that does not grow with M ---------------------------------
+// k_moment_cols splits W three ways over the grid.  blockIdx.x takes kMomentT trials (they share every read of W; trials
+// past B carry f = 0).  blockIdx.y is a column block of at most 256 columns, one per thread: with K <= 256 it owns
+// `spb` = 256 / K WHOLE settings b (the last block of a row of blocks owns the remainder), so that Q_ab, which is squared,
+// is complete inside the block; with K > 256 (`pieces` = ceil(K / 256) > 1) it owns one piece of one setting and writes
+// its partial Q_ab for every a to `qpart`[trial][a][b][piece], which k_moment_finish adds up in piece order before it
+// squares.  blockIdx.z is a run of `spr` settings a, i.e. the rows a K .. (a + spr) K of W: every one of the five sums is
+// a sum over a (W_cc f_c is taken by the first run only).  The geometry depends on (S, K) alone, never on B, so a trial
+// gives the same bits alone and in a batch.  Per block: f of 256 rows at a time in LDS (read back as a broadcast: f[r] is
+// the same for every lane), U[a][c] in a register while the K rows of setting a go by, U[a][c] f_c into one of two LDS
+// buffers (one barrier per setting) for the segment sums, eight lanes per segment with a fixed butterfly.  Each block
+// leaves five partial sums per trial in `part`[trial][gridDim.y * gridDim.z][5]; k_moment_finish adds them in block order
+// and applies the formula above.  No atomics.  LDS: 8 + 16 KB whatever M, S and K are; the entry point bounds
+// S K <= kMomentMaxRows (the W allocation), and S needs no array of its own.
+constexpr int kMomentT = 4, kMomentCols = 256, kMomentRows = 256, kMomentSub = 8, kMomentMaxRows = 32768;
+
+__global__ void __launch_bounds__(256) k_counts_to_freq(const int64_t* __restrict__ counts, long long total, int S, int K,
+                                                        const double* __restrict__ ns, double* __restrict__ freq) {
+  const long long M = (long long)S * K;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
+    freq[e] = (double)counts[e] / ns[(e % M) / K];
+}
+
+__global__ void __launch_bounds__(256) k_moment_cols(const double* __restrict__ freq, int B, int S, int K,
+                                                     const double* __restrict__ W, int spb, int pieces, int spr,
+                                                     double* __restrict__ part, double* __restrict__ qpart) {
+  constexpr int T = kMomentT, CB = kMomentCols, RB = kMomentRows, SUB = kMomentSub;
+  __shared__ double fs[T][RB];
+  __shared__ double prod[2][T][CB];
+  __shared__ double red[4][5 * T];
+  const int M = S * K, tid = threadIdx.x;
+  const int b0 = blockIdx.x * T, cb = blockIdx.y, rc = blockIdx.z;
+  int bfirst, piece = 0, c0, nseg, seglen;  // the block's columns: nseg segments of seglen columns from c0 on
+  if (pieces == 1) {
+    bfirst = cb * spb;
+    nseg = min(spb, S - bfirst);
+    seglen = K;
+    c0 = bfirst * K;
+  } else {
+    bfirst = cb / pieces;
+    piece = cb % pieces;
+    nseg = 1;
+    seglen = min(CB, K - piece * CB);
+    c0 = bfirst * K + piece * CB;
+  }
+  const bool own = tid < nseg * seglen;
+  const int c = c0 + (own ? tid : 0);
+  double fc[T], u[T], uuf[T], ww[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    fc[t] = own && b0 + t < B ? freq[(size_t)(b0 + t) * M + c] : 0.0;
+    u[t] = uuf[t] = ww[t] = 0.0;
+  }
+  // segment sums: lanes 8 g .. 8 g + 7 take (segment, trial) pair g, g + 32, ...; 32 % T == 0, so a thread's trial is fixed
+  const int sub = tid % SUB, tq = (tid / SUB) % T;
+  double q2 = 0.0, trq = 0.0;  // of trial tq
+  const int a0 = rc * spr, a1 = min(S, a0 + spr), rend = a1 * K;
+  int a = a0, left = K, buf = 0;
+  for (int r0 = a0 * K; r0 < rend; r0 += RB) {
+    const int nr = min(RB, rend - r0);
+    __syncthreads();
+    for (int e = tid; e < T * RB; e += 256) {
+      const int t = e / RB, j = e % RB;
+      fs[t][j] = j < nr && b0 + t < B ? freq[(size_t)(b0 + t) * M + r0 + j] : 0.0;
+    }
+    __syncthreads();
+    for (int j = 0; j < nr;) {
+      const int run = min(left, nr - j);  // rows of setting a in this row block
+      if (own) {
+        const double* wp = W + (size_t)(r0 + j) * M + c;
+#pragma unroll 4
+        for (int i = 0; i < run; ++i) {
+          const double w = wp[(size_t)i * M], w2 = w * w;
+#pragma unroll
+          for (int t = 0; t < T; ++t) {
+            const double fr = fs[t][j + i];
+            u[t] = fma(fr, w, u[t]);
+            ww[t] = fma(fr, w2, ww[t]);
+          }
+        }
+      }
+      j += run;
+      left -= run;
+      if (left > 0) continue;
+      // setting a is complete: U[a][c] f_c, then Q_ab (or this piece of it) for the block's segments
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        const double uf = u[t] * fc[t];
+        uuf[t] = fma(u[t], uf, uuf[t]);
+        prod[buf][t][tid] = uf;
+        u[t] = 0.0;
+      }
+      __syncthreads();  // (the other buffer is written next: one barrier per setting)
+      for (int e0 = 0; e0 < nseg * T * SUB; e0 += 256) {
+        const int s = (e0 + tid) / (T * SUB);
+        double q = 0.0;
+        if (s < nseg) {
+          const double* p = &prod[buf][tq][s * seglen];
+          for (int jj = sub; jj < seglen; jj += SUB) q += p[jj];
+        }
+        q += __shfl_xor(q, 1);
+        q += __shfl_xor(q, 2);
+        q += __shfl_xor(q, 4);
+        if (sub == 0 && s < nseg) {
+          if (pieces == 1) {
+            q2 = fma(q, q, q2);
+            if (bfirst + s == a) trq += q;
+          } else if (b0 + tq < B) {
+            qpart[(((size_t)(b0 + tq) * S + a) * S + bfirst) * pieces + piece] = q;
+          }
+        }
+      }
+      buf ^= 1;
+      ++a;
+      left = K;
+    }
+  }
+  const double wd = own && rc == 0 ? W[(size_t)c * M + c] : 0.0;
+  // five sums per trial over the workgroup
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    double v[5] = {uuf[t], ww[t] * fc[t], wd * fc[t], t == tq ? q2 : 0.0, t == tq ? trq : 0.0};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      v[k] = gsum<64>(v[k]);
+      if ((tid & 63) == 0) red[tid >> 6][5 * t + k] = v[k];
+    }
+  }
+  __syncthreads();
+  if (tid < 5 * T && b0 + tid / 5 < B) {
+    const size_t nblk = (size_t)gridDim.y * gridDim.z, blk = (size_t)cb * gridDim.z + rc;
+    part[((size_t)(b0 + tid / 5) * nblk + blk) * 5 + tid % 5] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  }
+}
+
+// One wavefront per trial: the blocks' partial sums in block order (lane l takes blocks l, l + 64, ...), the Q_ab that
+// k_moment_cols left in pieces (pieces > 1), and the closing formula of k_moment_batch.
+__global__ void __launch_bounds__(64) k_moment_finish(const double* __restrict__ part, int nblk,
+                                                      const double* __restrict__ qpart, int S, int pieces,
+                                                      double n_trials, double* __restrict__ mean,
+                                                      double* __restrict__ var) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = lane; i < nblk; i += 64) {
+    const double* p = part + ((size_t)b * nblk + i) * 5;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] += p[k];
+  }
+  if (pieces > 1) {
+    for (int e = lane; e < S * S; e += 64) {
+      const double* p = qpart + ((size_t)b * S * S + e) * pieces;
+      double q = 0.0;
+      for (int i = 0; i < pieces; ++i) q += p[i];
+      v[3] = fma(q, q, v[3]);
+      if (e / S == e % S) v[4] += q;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) v[k] = gsum<64>(v[k]);
+  if (lane == 0) {
+    const double s_uuf = v[0], s_wwf = v[1], t_d = v[2], s_q2 = v[3], tr_q = v[4];
+    const double first = (t_d - tr_q) / n_trials;
+    const double second = ((tr_q - t_d) * (tr_q - t_d) + 2.0 * s_q2 - 4.0 * s_uuf + 2.0 * s_wwf) / (n_trials * n_trials);
+    mean[b] = first;
+    var[b] = second - first * first;
+  }
+}
+
 // ---- merge of two adjacent sorted runs (gather of sorted shards -> the sorted sample; np.sort's order, NaN last) ------
 // in[0..na) and in[na..na+nb) sorted -> out[0..na+nb): every thread owns TILE consecutive outputs, finds its start on
 // the merge path by a binary search over the diagonal, then merges sequentially.  Stable (ties: first run first).

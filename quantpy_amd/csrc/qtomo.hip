@@ -106,6 +106,7 @@ struct qt_handle {
   DevBuf aug;      // [cols][2 cols] Gauss-Jordan workspace of enqueue_left_inverse
   DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project64)
   DevBuf gram;  // qt_moment_batch: P^T P
+  DevBuf moment_freq, moment_part, moment_qpart;  // k_moment_cols: counts / ns, the blocks' partial sums, Q_ab in pieces
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
@@ -900,7 +901,7 @@ void qt_destroy(qt_handle_t* h) {
   for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_last})
     b->release();
   for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws,
-                    &h->gram, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
+                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
   h->proc.release();
@@ -1591,6 +1592,48 @@ int qt_merge_sorted(qt_handle_t* h, const double* runs, const int64_t* run_lengt
 }
 
 // ---- f2: stats.py:21-47 over a batch (MomentInterval, interval.py:59-110) ------------------------------------------------
+// W = P^T P on the matrix cores ([M x rows] . [rows x M]), in h->gram
+static int moment_gram(qt_handle_t* h, const double* dp, int rows, long long M, double** dW) {
+  HIPCHK(h->gram.ensure((size_t)M * M * sizeof(double)));
+  *dW = h->gram.as<double>();
+  hipLaunchKernelGGL(qt::k_gemm<0>, dim3((unsigned)((M + 15) / 16), (unsigned)((M + 15) / 16)), dim3(64), 0, h->stream, (int)M, (int)M,
+                     rows, dp, (int)M, 1, dp, (int)M, 0, *dW, (int)M);
+  return 0;
+}
+
+// The moments of B trials from their frequencies in device memory, at any M (k_moment_cols, k_moment_finish).  The grid
+// over W -- column blocks of whole settings (or pieces of one, K > 256) x runs of settings -- aims at about 1024 blocks
+// per group of trials and at least 64 rows per block, and is a function of (S, K) alone.  256 trials per launch pair bound
+// the workspace (40 B per block and trial, 8 S^2 ceil(K / 256) B per trial for K > 256).
+static int moment_from_freq(qt_handle_t* h, const double* dfreq, int B, int S, int K, const double* dW, double n_trials,
+                            double* dmean, double* dvar) {
+  const int CB = qt::kMomentCols, T = qt::kMomentT;
+  const int pieces = K <= CB ? 1 : (K + CB - 1) / CB, spb = K <= CB ? CB / K : 0;
+  const int ncb = pieces == 1 ? (S + spb - 1) / spb : S * pieces;
+  const int runs = std::min(S, std::max(1, 1024 / ncb));
+  const int spr = std::min(S, std::max((S + runs - 1) / runs, (64 + K - 1) / K)), nrc = (S + spr - 1) / spr;
+  const size_t nblk = (size_t)ncb * nrc, M = (size_t)S * K, per_q = pieces > 1 ? (size_t)S * S * pieces : 0;
+  const int chunk = std::min(B, 256);
+  HIPCHK(h->moment_part.ensure(chunk * nblk * 5 * sizeof(double)));
+  HIPCHK(h->moment_qpart.ensure(chunk * per_q * sizeof(double)));
+  double *part = h->moment_part.as<double>(), *qpart = h->moment_qpart.as<double>();
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = std::min(chunk, B - b0);
+    if (int r = launch(h, qt::k_moment_cols, dim3((nb + T - 1) / T, ncb, nrc), dim3(256), 0, dfreq + b0 * M, nb, S, K, dW, spb,
+                       pieces, spr, part, qpart))
+      return r;
+    if (int r = launch(h, qt::k_moment_finish, dim3(nb), dim3(64), 0, (const double*)part, (int)nblk, (const double*)qpart, S,
+                       pieces, n_trials, dmean + b0, dvar + b0))
+      return r;
+  }
+  return 0;
+}
+
+static int moment_too_large(long long M) {
+  return fail(QT_ERR_UNSUPPORTED, "the moment entries support up to %d POVM rows (got %lld: W = P^T P would take %.1f GiB)",
+              qt::kMomentMaxRows, M, (double)M * (double)M * 8.0 / 1073741824.0);
+}
+
 int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, const double* ns, const double* inv_matrix,
                     int rows, double n_trials, double* mean, double* var, int flags) {
   QT_ENTER(h);
@@ -1598,25 +1641,49 @@ int qt_moment_batch(qt_handle_t* h, const int64_t* counts, int B, int S, int K, 
   if (B < 0 || S < 1 || K < 1 || rows < 1 || !(n_trials > 0.0) || !ns || !inv_matrix || (B > 0 && (!counts || !mean || !var)))
     return fail(QT_ERR_ARG, "bad moment_batch arguments");
   const long long M = (long long)S * K;
-  if (M > 8192) return fail(QT_ERR_UNSUPPORTED, "qt_moment_batch supports up to 8192 POVM rows (got %lld)", M);
+  if (M > qt::kMomentMaxRows) return moment_too_large(M);
   if (B == 0) return 0;
   const int64_t* dc;
   const double *dns, *dp;
-  double *dmean, *dvar;
+  double *dmean, *dvar, *dW;
   if (int r = c.in(counts, (size_t)B * M, &dc)) return r;
   if (int r = c.in(ns, (size_t)S, &dns)) return r;
   if (int r = c.in(inv_matrix, (size_t)rows * M, &dp)) return r;
   if (int r = c.out(mean, (size_t)B, &dmean)) return r;
   if (int r = c.out(var, (size_t)B, &dvar)) return r;
-  // W = P^T P on the matrix cores ([M x rows] . [rows x M])
-  HIPCHK(h->gram.ensure((size_t)M * M * sizeof(double)));
-  double* dW = h->gram.as<double>();
-  hipLaunchKernelGGL(qt::k_gemm<0>, dim3((unsigned)((M + 15) / 16), (unsigned)((M + 15) / 16)), dim3(64), 0, h->stream, (int)M, (int)M,
-                     rows, dp, (int)M, 1, dp, (int)M, 0, dW, (int)M);
-  const int T = M <= 1024 ? 4 : 1;  // trials per workgroup
-  if (int r = launch(h, T == 4 ? qt::k_moment_batch<4, 4> : qt::k_moment_batch<1, 32>, dim3((B + T - 1) / T), dim3(256),
-                     (size_t)2 * T * M * sizeof(double), dc, B, S, K, dns, dW, n_trials, dmean, dvar))
-    return r;
+  if (int r = moment_gram(h, dp, rows, M, &dW)) return r;
+  if (M <= 8192) {  // f and U f of whole trials in LDS
+    const int T = M <= 1024 ? 4 : 1;  // trials per workgroup
+    if (int r = launch(h, T == 4 ? qt::k_moment_batch<4, 4> : qt::k_moment_batch<1, 32>, dim3((B + T - 1) / T), dim3(256),
+                       (size_t)2 * T * M * sizeof(double), dc, B, S, K, dns, (const double*)dW, n_trials, dmean, dvar))
+      return r;
+  } else {
+    const long long total = (long long)B * M;
+    HIPCHK(h->moment_freq.ensure((size_t)total * sizeof(double)));
+    double* dfreq = h->moment_freq.as<double>();
+    if (int r = launch(h, qt::k_counts_to_freq, dim3(grid_for((size_t)total)), dim3(256), 0, dc, total, S, K, dns, dfreq)) return r;
+    if (int r = moment_from_freq(h, dfreq, B, S, K, dW, n_trials, dmean, dvar)) return r;
+  }
+  return c.done();
+}
+
+int qt_moment_freq_batch(qt_handle_t* h, const double* freq, int B, int S, int K, const double* inv_matrix, int rows,
+                         double n_trials, double* mean, double* var, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (B < 0 || S < 1 || K < 1 || rows < 1 || !(n_trials > 0.0) || !inv_matrix || (B > 0 && (!freq || !mean || !var)))
+    return fail(QT_ERR_ARG, "bad moment_freq_batch arguments");
+  const long long M = (long long)S * K;
+  if (M > qt::kMomentMaxRows) return moment_too_large(M);
+  if (B == 0) return 0;
+  const double *df, *dp;
+  double *dmean, *dvar, *dW;
+  if (int r = c.in(freq, (size_t)B * M, &df)) return r;
+  if (int r = c.in(inv_matrix, (size_t)rows * M, &dp)) return r;
+  if (int r = c.out(mean, (size_t)B, &dmean)) return r;
+  if (int r = c.out(var, (size_t)B, &dvar)) return r;
+  if (int r = moment_gram(h, dp, rows, M, &dW)) return r;
+  if (int r = moment_from_freq(h, df, B, S, K, dW, n_trials, dmean, dvar)) return r;
   return c.done();
 }
 

@@ -639,10 +639,16 @@ class Engine:
     # ---- f2: stats.py:21-47 ------------------------------------------------------------------------
     def moments(self, counts, n_meas, inv_matrix):
         """Mean and variance of the squared weighted l2 error of the frequencies under multinomial noise
-        (qt_moment_batch; reference stats.py l2_mean / l2_variance with the weights of interval.py:88).
+        (reference stats.py l2_mean / l2_variance with the weights of interval.py:88).
         counts (B, S, K) or (S, K); n_meas (S,) shots per setting; inv_matrix (rows, S*K) = left inverse of the design
-        matrix / dim.  -> (mean, var), each (B,) or scalars."""
-        c = _i64(counts)
+        matrix / dim.  -> (mean, var), each (B,) or scalars.  Integer-valued counts go to qt_moment_batch; real-valued
+        ones (the reference takes any `results`, e.g. expected counts N p) to qt_moment_freq_batch as the frequencies
+        counts / n_meas[:, None] (interval.py:82)."""
+        c = np.asarray(counts)
+        if not (np.issubdtype(c.dtype, np.integer) or np.all(np.equal(np.mod(c, 1), 0))):
+            ns = np.broadcast_to(np.asarray(n_meas, dtype=np.float64), (c.shape[-2],))
+            return self.moments_freq(c / ns[:, None], ns[0], inv_matrix)
+        c = _i64(c)
         single = c.ndim == 2
         if single:
             c = c[None]
@@ -653,6 +659,21 @@ class Engine:
         mean, var = np.empty(b), np.empty(b)
         self._chk(self.lib.qt_moment_batch(self._h, _ptr(c), b, s, k, _ptr(ns), _ptr(p), p.shape[0], float(ns[0]), _ptr(mean),
                                            _ptr(var), _capi.QT_HOST_PTR))
+        return (mean[0], var[0]) if single else (mean, var)
+
+    def moments_freq(self, freq, n_trials, inv_matrix):
+        """`moments` from frequencies given directly (qt_moment_freq_batch): freq (B, S, K) or (S, K), n_trials the shots
+        per setting of the closing formula (interval.py:89: n_measurements[0])."""
+        f = _f64(freq)
+        single = f.ndim == 2
+        if single:
+            f = f[None]
+        b, s, k = f.shape
+        p = _f64(np.asarray(inv_matrix).reshape(np.asarray(inv_matrix).shape[0], -1))
+        assert p.shape[1] == s * k
+        mean, var = np.empty(b), np.empty(b)
+        self._chk(self.lib.qt_moment_freq_batch(self._h, _ptr(f), b, s, k, _ptr(p), p.shape[0], float(n_trials), _ptr(mean),
+                                                _ptr(var), _capi.QT_HOST_PTR))
         return (mean[0], var[0]) if single else (mean, var)
 
     # ---- f3: interval.py:268-335 -----------------------------------------------------------------------

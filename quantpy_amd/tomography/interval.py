@@ -100,7 +100,8 @@ class MomentInterval(ConfidenceInterval):
     distr_type : 'gamma' (default) | 'norm' | 'exp'.
 
     Both heavy steps run on the GPU: the left inverse of the design matrix (qt_left_inverse: MFMA Gram, pivoted
-    Gauss-Jordan) and the moment sums of stats.py:21-47 (qt_moment_batch).  `radii_batch` evaluates the interval for
+    Gauss-Jordan) and the moment sums of stats.py:21-47 (qt_moment_batch; qt_moment_freq_batch when `results` are not
+    integers, which the reference accepts; a three-qubit process, 13 824 POVM rows, included).  `radii_batch` evaluates the interval for
     a whole batch of count tensors of the same experiment in one launch -- the coverage study of
     notebooks/Verification.ipynb (10 000 trials per state) is that call."""
 
