@@ -331,10 +331,11 @@ class Engine:
             choi, iters = choi[0], iters[0]
         return (choi, iters) if return_iters else choi
 
-    def pgdb(self, counts, n_iter=1000, tol=1e-10, stop="reference", return_iters=False):
+    def pgdb(self, counts, n_iter=1000, tol=1e-10, stop="reference", return_iters=False, return_status=False):
         """'pgdb' of process.py:291-308 on counts (B, D, S, K) or (D, S, K) -> Choi.  stop='reference'
         keeps the reference's loop exit (it returns the point before the first improving step),
-        stop='converged' accepts steps until the NLL decrease falls below `tol`."""
+        stop='converged' accepts steps until the NLL decrease falls below `tol`.  return_iters / return_status append
+        the per-trial iteration counts / status codes (_capi.TRIAL_*), in that order."""
         if stop not in ("reference", "converged"):
             raise ValueError("stop must be 'reference' or 'converged'")
         c = _i64(counts)
@@ -347,33 +348,42 @@ class Engine:
         self._chk(self.lib.qt_pgdb_batch(self._h, _ptr(c), b, int(n_iter), float(tol), 0 if stop == "reference" else 1,
                                          _ptr(choi), _ptr(iters), _ptr(status), _capi.QT_HOST_PTR))
         if single:
-            choi, iters = choi[0], iters[0]
-        return (choi, iters) if return_iters else choi
+            choi, iters, status = choi[0], iters[0], status[0]
+        res = (choi,) + ((iters,) if return_iters else ()) + ((status,) if return_status else ())
+        return res[0] if len(res) == 1 else res
 
     def pgdb_pieces(self, counts, choi):
-        """One 'pgdb' iteration's pieces at `choi` (n = 3, qt_pgdb_pieces): (probas (D*M,), grad (D, D) laid out like
-        the Choi matrix, P_CPTP(choi - grad / mu) (D, D))."""
-        c = _i64(counts).reshape(1, self.D, self.S, self.K)
-        x = _c128(choi).reshape(1, self.D, self.D)
-        probas = np.empty((1, c[0].size))
-        grad = np.empty((1, self.D, self.D), dtype=np.complex128)
-        proj = np.empty((1, self.D, self.D), dtype=np.complex128)
-        self._chk(self.lib.qt_pgdb_pieces(self._h, _ptr(c), 1, _ptr(x), _ptr(probas), _ptr(grad), _ptr(proj), _capi.QT_HOST_PTR))
-        return probas[0], grad[0], proj[0]
+        """One 'pgdb' iteration's pieces at `choi` (n = 3, qt_pgdb_pieces): counts (D, S, K) and choi (D, D) ->
+        (probas (D*M,), grad (D, D) laid out like the Choi matrix, P_CPTP(choi - grad / mu) (D, D)); counts
+        (B, D, S, K) and choi (B, D, D) -> the same with a leading B."""
+        c = _i64(counts)
+        single = c.ndim == 3
+        c = c.reshape(-1, self.D, self.S, self.K)
+        b = c.shape[0]
+        x = _c128(choi).reshape(b, self.D, self.D)
+        probas = np.empty((b, c[0].size))
+        grad = np.empty((b, self.D, self.D), dtype=np.complex128)
+        proj = np.empty((b, self.D, self.D), dtype=np.complex128)
+        self._chk(self.lib.qt_pgdb_pieces(self._h, _ptr(c), b, _ptr(x), _ptr(probas), _ptr(grad), _ptr(proj), _capi.QT_HOST_PTR))
+        return (probas[0], grad[0], proj[0]) if single else (probas, grad, proj)
 
     def mhmc_process(self, counts, choi_init, deltas, uniforms, step):
-        """Metropolis-Hastings chain of MHMCProcessInterval: counts (D, S, K), choi_init (D, D), deltas
-        (T, D*D) real (column-stacked index), uniforms (T,) -> (chain (T, D, D) complex, accepted (T,))."""
-        c = _i64(counts).reshape(1, self.D, self.S, self.K)
-        x0 = _c128(choi_init).reshape(1, self.D, self.D)
-        dl = _f64(deltas).reshape(1, -1, self.D * self.D)
+        """Metropolis-Hastings chain(s) of MHMCProcessInterval: counts (D, S, K) or (C, D, S, K), choi_init (D, D) /
+        (C, D, D), deltas (T, D*D) / (C, T, D*D) real (column-stacked index), uniforms (T,) / (C, T) ->
+        (chain (.., T, D, D) complex, accepted (.., T))."""
+        c = _i64(counts)
+        single = c.ndim == 3
+        c = c.reshape(-1, self.D, self.S, self.K)
+        nchain = c.shape[0]
+        x0 = _c128(choi_init).reshape(nchain, self.D, self.D)
+        dl = _f64(deltas).reshape(nchain, -1, self.D * self.D)
         t = dl.shape[1]
-        un = _f64(uniforms).reshape(1, t)
-        chain = np.empty((1, t, self.D, self.D), dtype=np.complex128)
-        acc = np.zeros((1, t), dtype=np.int32)
-        self._chk(self.lib.qt_mhmc_process(self._h, _ptr(c), 1, _ptr(x0), _ptr(dl), _ptr(un), t, float(step), _ptr(chain),
-                                           _ptr(acc), _capi.QT_HOST_PTR))
-        return chain[0], acc[0]
+        un = _f64(uniforms).reshape(nchain, t)
+        chain = np.empty((nchain, t, self.D, self.D), dtype=np.complex128)
+        acc = np.zeros((nchain, t), dtype=np.int32)
+        self._chk(self.lib.qt_mhmc_process(self._h, _ptr(c), nchain, _ptr(x0), _ptr(dl), _ptr(un), t, float(step),
+                                           _ptr(chain), _ptr(acc), _capi.QT_HOST_PTR))
+        return (chain[0], acc[0]) if single else (chain, acc)
 
     def lifp_dev(self, counts, choi, cptp=True, iters=None, status=None):
         self._dev_call()

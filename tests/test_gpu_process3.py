@@ -132,12 +132,15 @@ def test_n3_process_without_counts_is_nan_and_alone(g3):
     assert iters[0] == int(g3["Q0_dykstra_iters"]) and iters[2] == int(g3["Q1_dykstra_iters"])
 
 
-@pytest.mark.parametrize("nq", [3, 2])
+@pytest.mark.parametrize("nq", [3, 2, 1])
 def test_cptp_projection_regimes_against_eigh_dykstra(oracle, nq):
-    """k_cptp_project64 (n = 3) and k_cptp_wave16 (n = 2: one wavefront per process, the matrix in the registers of the
-    matrix-core tile) on Choi matrices the fixtures do not reach -- already CPTP, CP but not TP, TP but far from CP,
+    """k_cptp_project64 (n = 3), k_cptp_wave16 (n = 2: one wavefront per process, the matrix in the registers of the
+    matrix-core tile) and k_cptp_project<4> (n = 1: the Cholesky short cut and the round-robin Jacobi CP step of
+    ProcWG<4>) on Choi matrices the fixtures do not reach -- already CPTP, CP but not TP, TP but far from CP,
     a unitary channel (rank one) with noise, large noise -- against a NumPy Dykstra loop with eigh (process.py:237-278;
-    its TP step checked once against the oracle's operator form): same iteration counts, Choi to 1e-9."""
+    its TP step checked once against the oracle's operator form): same iteration counts, Choi to 1e-9.  The counts
+    rest on the NumPy loop not stopping within rounding of `tol`; for the n = 1 cases (seed 4) its last criterion is
+    below 3e-16 and the one before it above 1e-6."""
     import quantpy_amd as qp
 
     d = 2**nq
@@ -407,3 +410,42 @@ def test_n2_cp_step_on_rank_deficient_and_tiny_spectra():
         w, u = np.linalg.eigh(a)
         want = (u * np.maximum(w, 1e-12)) @ u.conj().T
         assert np.abs(r - want).max() < 3e-12 * max(np.linalg.norm(a), 1.0) + 1e-12, np.abs(r - want).max()
+
+
+def test_n1_cp_step_on_rank_deficient_and_tiny_spectra():
+    """The 4 x 4 CP step (k_cptp_project<4>: ProcWG<4>::cp_project, Cholesky short cut or round-robin Jacobi) on the
+    families of spectra test_n2_cp_step_on_rank_deficient_and_tiny_spectra and test_n3_cp_step_on_hard_spectra give the
+    larger ones: exact zeros (the Choi matrix of a unitary channel, rank one; a rank-2 matrix), eigenvalues at 1e-13 ..
+    1e-8 of the norm on both sides of zero, negative definite, a multiple of the identity, a degenerate pair -- against
+    the eigh clip (process.py:270-277) under the bound of the n = 2 test."""
+    import quantpy_amd as qp
+
+    rng = np.random.default_rng(41)
+    g = rng.standard_normal((4, 4)) + 1j * rng.standard_normal((4, 4))
+    q, _ = np.linalg.qr(g)
+    u2, _ = np.linalg.qr(rng.standard_normal((2, 2)) + 1j * rng.standard_normal((2, 2)))
+    v = u2.T.reshape(-1)
+    mats = {"unitary channel (rank one)": np.outer(v, v.conj())}  # Choi matrix of rho -> U rho U^dagger
+    spectra = {
+        "rank 2 (exact zeros)": [0.0, 0.0, -0.7, 1.0],
+        "tiny, both signs": [1e-13, -1e-11, 1e-8, 1.0],
+        "tiny, both signs, mirrored": [-1e-13, 1e-11, -1e-8, 1.0],
+        "tiny positive (positive definite)": [1e-13, 1e-11, 1e-9, 1.0],
+        "one dominant eigenvalue, bulk +-1e-7": [1.0, -1e-7, 1e-7, -1e-7],
+        "negative definite": [-0.1, -0.4, -0.7, -1.0],
+        "-0.3 I": [-0.3, -0.3, -0.3, -0.3],
+        "+0.3 I": [0.3, 0.3, 0.3, 0.3],
+        "degenerate pair, positive": [0.5, 0.5, -0.2, 1.0],
+        "degenerate pair, clipped": [-0.5, -0.5, 0.2, 1.0],
+    }
+    for name, ev in spectra.items():
+        a = (q * np.array(ev)) @ q.conj().T
+        mats[name] = (a + a.conj().T) / 2
+    mats["zero matrix"] = np.zeros((4, 4), dtype=np.complex128)
+    batch = np.stack(list(mats.values()))
+    got = qp.get_engine(1).cptp_project(batch, mode="cp")
+    for name, a, r in zip(mats, batch, got):
+        w, u = np.linalg.eigh(a)
+        want = (u * np.maximum(w, 1e-12)) @ u.conj().T
+        err = np.abs(r - want).max()
+        assert err < 3e-12 * max(np.linalg.norm(a), 1.0) + 1e-12, (name, err)
