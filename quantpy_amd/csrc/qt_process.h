@@ -18,32 +18,6 @@
 
 namespace qt {
 
-struct ProcessState {
-  void* lifp = nullptr;      // [D*M][D^2] complex design matrix
-  void* pinvT = nullptr;     // [D*M][D^2] complex: transpose of its left inverse
-  void* pinvR = nullptr;     // the same with each row's D^2 entries in ROW-major Choi order (k_lifp_gemm's operand: its product
-                             // columns are then the doubles of choi[b] in order); built for n = 2 only
-  void* emats = nullptr;     // [M][d][d] complex POVM elements
-  void* in_states = nullptr; // [D][d][d] complex
-  void* pinv = nullptr;      // [D^2][D*M] complex
-  // n = 3 (qt_process64.h): the design matrix stays Kronecker-factored -- left inverses of its two factors
-  void* vs_pinv = nullptr;   // [D][D] complex: left inverse of V_S = [vec rho_s]
-  void* vp_pinv = nullptr;   // [D][M] complex: left inverse of V_P = [vec E_m] (index e d + b)
-  void* vp_pinvT = nullptr;  // [M][D] complex: its transpose, the right-hand operand of T = F V_P^+^T
-  void* vp_perm = nullptr;   // [groups][M][32] real: the same, 16 columns (re | im) per group in the order k_lifp64 (n = 3:
-                             // 4 groups) / k_lifp16 (n = 2: 1 group) store them; M % 4 == 0 only
-  bool factored = false;
-  size_t cap_rows = 0;
-  void release() {
-    factored = false;
-    for (void** p : {&lifp, &pinvT, &pinvR, &emats, &in_states, &pinv, &vs_pinv, &vp_pinv, &vp_pinvT, &vp_perm}) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
-    cap_rows = 0;
-  }
-};
-
 // lifp[(s*M + m)][col*d^2 + row] = rho_s[a][c] * E_m[e][b],  row = a*d + b, col = c*d + e
 __global__ void k_lifp_rows(int d, int M, const double* __restrict__ in_states, const double* __restrict__ emats,
                             double* __restrict__ lifp) {

@@ -679,8 +679,18 @@ __global__ void __launch_bounds__(256) k_lifp64(const int64_t* __restrict__ coun
 struct Pgdb64 {
   static constexpr int DC = 64, d = 8, NT = 256, P = DC + 1, NE = DC * DC;
   static constexpr size_t kLdsBytes = ((size_t)2 * DC * P + 64) * sizeof(double);
-  // per-process workspace, in doubles: Y[64][M] complex | p[R] | q[R] | w[R] | g[64][64] complex (Choi layout)
-  __host__ __device__ static size_t ws_doubles(int M) { return (size_t)2 * DC * M + 3 * (size_t)DC * M + 2 * NE; }
+  // per-process workspace, in doubles: Y[64][M] complex | p[R] | q[R] | w[R] | g[64][64] complex (Choi layout), R = 64 M
+  __host__ __device__ static size_t ws_doubles(int M) { return (size_t)5 * DC * M + 2 * NE; }
+  struct Ws {  // process b's block of the workspace `ws`
+    double* base;
+    size_t R;
+    __host__ __device__ Ws(double* ws, int b, int M) : base(ws + (size_t)b * ws_doubles(M)), R((size_t)DC * M) {}
+    __host__ __device__ cd* Y() const { return reinterpret_cast<cd*>(base); }
+    __host__ __device__ double* p() const { return base + 2 * R; }
+    __host__ __device__ double* q() const { return base + 3 * R; }
+    __host__ __device__ double* w() const { return base + 4 * R; }
+    __host__ __device__ cd* g() const { return reinterpret_cast<cd*>(base + 5 * R); }
+  };
 
   __device__ static double bsum(double* red, double v) {  // identical bits in every thread
     v = gsum<64>(v);
@@ -898,11 +908,9 @@ __global__ void __launch_bounds__(Pgdb64::NT) k_pgdb64_grad(const int64_t* __res
   using S = Pgdb64;
   const int R = S::DC * M;
   cd* X = reinterpret_cast<cd*>(smp);
-  double* wsb = ws + (size_t)b * S::ws_doubles(M);
-  cd* Y = reinterpret_cast<cd*>(wsb);
-  double* p = wsb + (size_t)2 * S::DC * M;
-  double* w = p + 2 * (size_t)R;
-  cd* g = reinterpret_cast<cd*>(w + R);
+  const S::Ws wsb(ws, b, M);
+  cd *Y = wsb.Y(), *g = wsb.g();
+  double *p = wsb.p(), *w = wsb.w();
   const cd* cur = reinterpret_cast<const cd*>(choi) + (size_t)b * S::NE;
   const cd *VS = reinterpret_cast<const cd*>(vs), *VP = reinterpret_cast<const cd*>(vp);
   S::load_x(cur, X);
@@ -928,11 +936,11 @@ __global__ void __launch_bounds__(Pgdb64::NT) k_pgdb64_step(const int64_t* __res
   const int R = S::DC * M;
   cd* X = reinterpret_cast<cd*>(smp);
   double* red = smp + 2 * S::DC * S::P;
-  double* wsb = ws + (size_t)b * S::ws_doubles(M);
-  cd* Y = reinterpret_cast<cd*>(wsb);
-  const double* p = wsb + (size_t)2 * S::DC * M;
-  double* q = wsb + (size_t)2 * S::DC * M + R;
-  const cd* g = reinterpret_cast<const cd*>(wsb + (size_t)2 * S::DC * M + 3 * (size_t)R);
+  const S::Ws wsb(ws, b, M);
+  cd* Y = wsb.Y();
+  const double* p = wsb.p();
+  double* q = wsb.q();
+  const cd* g = wsb.g();
   cd* cur = reinterpret_cast<cd*>(choi) + (size_t)b * S::NE;
   const cd* pr = reinterpret_cast<const cd*>(proj) + (size_t)b * S::NE;
   const cd *VS = reinterpret_cast<const cd*>(vs), *VP = reinterpret_cast<const cd*>(vp);

@@ -76,6 +76,31 @@ struct DevBuf {
 
 constexpr int kStageBufs = 8;  // arrays one host-pointer call may stage (qt_mle_batch: counts, centre and six outputs)
 
+// What qt_process_setup keeps of the design matrix L (rows vec(rho_s (x) E_m^T)).  n <= 2 keeps it dense (`lifp` ..
+// `pinvR`); n = 3 keeps only the left inverses of its Kronecker factors (qt_process64.h: `factored`); n = 2 builds those
+// next to the dense form when the POVM allows (`factors` without `factored`).
+struct ProcessState {
+  DevBuf in_states;  // [D][d][d] complex
+  DevBuf emats;      // [M][d][d] complex POVM elements
+  DevBuf lifp;       // [D*M][D^2] complex design matrix
+  DevBuf pinv;       // [D^2][D*M] complex: its left inverse
+  DevBuf pinvT;      // [D*M][D^2] complex: the transpose of that
+  DevBuf pinvR;      // the same with each row's D^2 entries in ROW-major Choi order (k_lifp_gemm's operand: its product
+                     // columns are then the doubles of choi[b] in order); built for n = 2 only
+  DevBuf vs_pinv;    // [D][D] complex: left inverse of V_S = [vec rho_s]
+  DevBuf vp_pinv;    // [D][M] complex: left inverse of V_P = [vec E_m] (index e d + b)
+  DevBuf vp_pinvT;   // [M][D] complex: its transpose, the right-hand operand of T = F V_P^+^T
+  DevBuf vp_perm;    // [groups][M][32] real: the same, 16 columns (re | im) per group in the order k_lifp64 (n = 3:
+                     // 4 groups) / k_lifp16 (n = 2: 1 group) store them
+  bool factored = false;  // the dense form was not built: the factors are all there is
+  bool factors = false;   // vs_pinv, vp_pinv, vp_pinvT hold regular left inverses
+  bool perm = false;      // ... and vp_perm their permuted copy: qt_lifp_batch takes the matrix-core kernels
+  void release() {
+    factored = factors = perm = false;
+    for (DevBuf* b : {&in_states, &emats, &lifp, &pinv, &pinvT, &pinvR, &vs_pinv, &vp_pinv, &vp_pinvT, &vp_perm}) b->release();
+  }
+};
+
 }  // namespace
 
 struct qt_handle {
@@ -104,7 +129,7 @@ struct qt_handle {
   // staging for host-pointer calls: one buffer per array of a call, in the order the call registers them (Call)
   DevBuf stage[kStageBufs];
   DevBuf aug;      // [cols][2 cols] Gauss-Jordan workspace of enqueue_left_inverse
-  DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project64)
+  DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project)
   DevBuf gram;  // qt_moment_batch: P^T P
   DevBuf moment_freq, moment_part, moment_qpart;  // k_moment_cols: counts / ns, the blocks' partial sums, Q_ab in pieces
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
@@ -117,8 +142,8 @@ struct qt_handle {
   // radix-sort double buffer + temporary storage (qt_sort_f64)
   DevBuf sort_alt, sort_tmp;
   // process tomography
-  qt::ProcessState proc;
-  bool proc_set = false;
+  ProcessState proc;
+  bool proc_set = false;  // `proc` describes the current POVM: a set-up succeeded after the last qt_set_povm
   bool proc_dense = false;  // qt_process_prefer_dense: qt_lifp_batch multiplies by the dense left inverse where it has a choice
 
   double ns_tot = 0.0;  // sum of the registered shots per setting
@@ -757,19 +782,62 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
   });
 }
 
-// The n = 3 projection (qt_process64.h, k_cptp_project64) of B Choi matrices, one workgroup each, with Dykstra's p, q,
-// y, x and the clip's input in h->proc_ws -- except in mode 1 (TP only), which takes no workspace.
-int project64(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
-              int32_t* status) {
-  if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
-  return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, in, B, mode, n_iter, tol, out,
-                iters, status, h->proc_ws.as<double>());
+// The projection (mode 0: CPTP by Dykstra's alternation, 1: TP, 2: CP) of B Choi matrices by the kernel for the handle's
+// size.  n = 3: k_cptp_project64 (qt_process64.h), one workgroup each, with Dykstra's p, q, y, x and the clip's input in
+// h->proc_ws -- except in mode 1, which takes no workspace.  n = 2: k_cptp_wave16 (qt_process_wave16.h), one wavefront
+// each.  n = 1: k_cptp_project<4> (qt_process.h), one workgroup each.  `iters` and `status` may be null.
+int project(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
+            int32_t* status) {
+  if (h->D == 64) {
+    if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
+    return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, in, B, mode, n_iter, tol, out,
+                  iters, status, h->proc_ws.as<double>());
+  }
+  if (h->D == 16) return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status);
+  return launch(h, qt::k_cptp_project<4>, dim3(B), dim3(qt::ProcWG<4>::NT), 0, in, B, mode, n_iter, tol, out, iters, status);
 }
 
-// The n = 2 projection (qt_process_wave16.h, k_cptp_wave16): one wavefront per Choi matrix.
-int project16(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
-              int32_t* status) {
-  return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status);
+// The Kronecker factors of the left inverse, L^+ = Pi (V_S^+ (x) V_P^+), from proc.in_states and proc.emats: V_S^+, V_P^+,
+// its transpose and, with `groups` > 0, the permuted operand of the matrix-core kernels (k_lifp64: 4 groups, k_lifp16: 1).
+// Enqueued on the handle's stream; the two pivot reports are in info[0] (V_S) and info[1] (V_P) once it has been waited for.
+int enqueue_factors(qt_handle_t* h, int groups, int info[2]) {
+  ProcessState& ps = h->proc;
+  const int d = h->d, D = h->D, M = h->M;
+  HIPCHK(ps.vs_pinv.ensure((size_t)D * D * 2 * sizeof(double)));
+  HIPCHK(ps.vp_pinv.ensure((size_t)D * M * 2 * sizeof(double)));
+  HIPCHK(ps.vp_pinvT.ensure((size_t)M * D * 2 * sizeof(double)));
+  if (groups) HIPCHK(ps.vp_perm.ensure((size_t)groups * M * 32 * sizeof(double)));
+  if (int r = enqueue_left_inverse<2>(h, ps.in_states.as<double>(), D, D, ps.vs_pinv.as<double>())) return r;
+  HIPCHK(hipMemcpyAsync(&info[0], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (int r = enqueue_left_inverse<2>(h, ps.emats.as<double>(), M, D, ps.vp_pinv.as<double>())) return r;
+  HIPCHK(hipMemcpyAsync(&info[1], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  launch_transpose<2>(h, ps.vp_pinv.as<double>(), D, M, ps.vp_pinvT.as<double>());
+  if (groups)
+    return launch(h, qt::k_vp_perm, dim3(grid_for((size_t)groups * M * 32)), dim3(256), 0, ps.vp_pinvT.as<double>(), M, D, d,
+                  groups, ps.vp_perm.as<double>());
+  return 0;
+}
+
+// Scratch of the n = 3 'pgdb' iteration over B processes: the per-process workspace (qt::Pgdb64::Ws) in ws_x, the trial
+// points c - g / mu in ws_g, their CPTP projections in ws_f, the loop state {iteration, stopped, NaN seen, -} per
+// process and the count of running processes in ws_act.
+int pgdb64_scratch(qt_handle_t* h, int B) {
+  const size_t ne2 = (size_t)h->D * h->D * 2;
+  HIPCHK(h->ws_x.ensure((size_t)B * qt::Pgdb64::ws_doubles(h->M) * sizeof(double)));
+  HIPCHK(h->ws_g.ensure((size_t)B * ne2 * sizeof(double)));
+  HIPCHK(h->ws_f.ensure((size_t)B * ne2 * sizeof(double)));
+  HIPCHK(h->ws_act.ensure(((size_t)B * 4 + 4) * sizeof(int32_t)));
+  return 0;
+}
+
+// The first two launches of an iteration at the points `cur`: model, weights and gradient into the workspace, then the
+// projection of the trial points (ws_g -> ws_f).
+int pgdb64_trial(qt_handle_t* h, const int64_t* counts, int B, const double* cur) {
+  using S = qt::Pgdb64;
+  if (int r = launch(h, qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, counts, B, h->M, h->proc.in_states.as<double>(),
+                     h->proc.emats.as<double>(), cur, h->ws_act.as<int32_t>(), h->ws_x.as<double>(), h->ws_g.as<double>()))
+    return r;
+  return project(h, h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr);
 }
 
 }  // namespace
@@ -1909,82 +1977,50 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
   if (int r = ensure_dense(h)) return r;
   const int d = h->d, D = h->D, M = h->M;
   const size_t C2 = (size_t)D * D, R = (size_t)D * M;
-  qt::ProcessState& ps = h->proc;
+  ProcessState& ps = h->proc;
   ps.release();
-  if (h->nq == 3) {
-    // Kronecker-factored design matrix (qt_process64.h): L = (V_S (x) V_P) Pi^T, L^+ = Pi (V_S^+ (x) V_P^+)
-    HIPCHK(hipMalloc(&ps.in_states, (size_t)D * D * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.emats, (size_t)M * D * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.vs_pinv, (size_t)D * D * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.vp_pinv, (size_t)D * M * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.vp_pinvT, (size_t)M * D * 2 * sizeof(double)));
-    if (int r = c.copy_in((double*)ps.in_states, in_states, (size_t)D * D * 2)) return r;
-    hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->stream, h->nq, h->Aw.as<double>(),
-                       M, (double*)ps.emats);
-    int info[2] = {0, 0};
-    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.in_states, D, D, (double*)ps.vs_pinv)) return r;
-    HIPCHK(hipMemcpyAsync(&info[0], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.emats, M, D, (double*)ps.vp_pinv)) return r;
-    HIPCHK(hipMemcpyAsync(&info[1], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    launch_transpose<2>(h, (const double*)ps.vp_pinv, D, M, (double*)ps.vp_pinvT);
-    if (M % 4 == 0) {  // the operand of k_lifp64 (the matrix-core path of qt_lifp_batch)
-      HIPCHK(hipMalloc(&ps.vp_perm, (size_t)4 * M * 32 * sizeof(double)));
-      hipLaunchKernelGGL(qt::k_vp_perm, dim3(grid_for((size_t)4 * M * 32)), dim3(256), 0, h->stream, (const double*)ps.vp_pinvT, M,
-                         D, d, 4, (double*)ps.vp_perm);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (info[0] != 0) return fail(QT_ERR_SINGULAR, "input states do not span the operator space (column %d)", info[0] - 1);
-    if (info[1] != 0) return fail(QT_ERR_SINGULAR, "POVM is not informationally complete (column %d)", info[1] - 1);
-    ps.factored = true;
-    h->proc_set = true;
-    return 0;
-  }
-  HIPCHK(hipMalloc(&ps.in_states, (size_t)D * D * 2 * sizeof(double)));
-  HIPCHK(hipMalloc(&ps.emats, (size_t)M * D * 2 * sizeof(double)));
-  HIPCHK(hipMalloc(&ps.lifp, R * C2 * 2 * sizeof(double)));
-  HIPCHK(hipMalloc(&ps.pinv, R * C2 * 2 * sizeof(double)));
-  HIPCHK(hipMalloc(&ps.pinvT, R * C2 * 2 * sizeof(double)));
-  if (int r = c.copy_in((double*)ps.in_states, in_states, (size_t)D * D * 2)) return r;
-  double *lifp = (double*)ps.lifp, *pinv = (double*)ps.pinv, *pinvT = (double*)ps.pinvT;
+  HIPCHK(ps.in_states.ensure((size_t)D * D * 2 * sizeof(double)));
+  HIPCHK(ps.emats.ensure((size_t)M * D * 2 * sizeof(double)));
+  if (int r = c.copy_in(ps.in_states.as<double>(), in_states, (size_t)D * D * 2)) return r;
   // E_m = sum_k A'[m][k] P_k  (process.py:204: Qobj(povm_bloch).matrix)
-  hipLaunchKernelGGL(qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->stream, h->nq, h->Aw.as<double>(),
-                     M, (double*)ps.emats);
-  hipLaunchKernelGGL(qt::k_lifp_rows, dim3(grid_for(R * C2)), dim3(256), 0, h->stream, d, M, (const double*)ps.in_states,
-                     (const double*)ps.emats, lifp);
-  const int c2 = (int)C2, rr = (int)R;
-  if (int r = enqueue_left_inverse<2>(h, lifp, rr, c2, pinv)) return r;
-  launch_transpose<2>(h, pinv, c2, rr, pinvT);
-  if (h->nq == 2) {  // the batched GEMM of qt_lifp_batch reads the left inverse in row-major Choi order
-    HIPCHK(hipMalloc(&ps.pinvR, R * C2 * 2 * sizeof(double)));
-    hipLaunchKernelGGL(qt::k_choi_order_rows, dim3(grid_for(R * C2)), dim3(256), 0, h->stream, (const double*)pinvT, R, D,
-                       (double*)ps.pinvR);
-  }
+  if (int r = launch(h, qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->nq, h->Aw.as<double>(), M,
+                     ps.emats.as<double>()))
+    return r;
+  // n = 3 keeps the Kronecker-factored design matrix only (qt_process64.h): L = (V_S (x) V_P) Pi^T, L^+ = Pi (V_S^+ (x) V_P^+).
+  // n = 2 builds the factors too where k_lifp16 can take them (qt_process.h): what qt_lifp_batch multiplies by; the dense
+  // operators stay for qt_process_get_operators, 'pgdb' and the process chain.
+  const bool factored = h->nq == 3;
+  const bool factors = factored || (h->nq == 2 && M % 4 == 0 && (size_t)M * 32 * sizeof(double) <= 64 * 1024);
   int info = 0, finfo[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  const bool factors = h->nq == 2 && M % 4 == 0 && (size_t)M * 32 * sizeof(double) <= 64 * 1024;
-  if (factors) {
-    // the Kronecker factors of the left inverse (qt_process.h, k_lifp16): what qt_lifp_batch multiplies by at n = 2; the
-    // dense operators above stay for qt_process_get_operators, 'pgdb' and the process chain
-    HIPCHK(hipMalloc(&ps.vs_pinv, (size_t)D * D * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.vp_pinv, (size_t)D * M * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.vp_pinvT, (size_t)M * D * 2 * sizeof(double)));
-    HIPCHK(hipMalloc(&ps.vp_perm, (size_t)M * 32 * sizeof(double)));
-    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.in_states, D, D, (double*)ps.vs_pinv)) return r;
-    HIPCHK(hipMemcpyAsync(&finfo[0], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (int r = enqueue_left_inverse<2>(h, (const double*)ps.emats, M, D, (double*)ps.vp_pinv)) return r;
-    HIPCHK(hipMemcpyAsync(&finfo[1], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    launch_transpose<2>(h, (const double*)ps.vp_pinv, D, M, (double*)ps.vp_pinvT);
-    hipLaunchKernelGGL(qt::k_vp_perm, dim3(grid_for((size_t)M * 32)), dim3(256), 0, h->stream, (const double*)ps.vp_pinvT, M, D, d,
-                       1, (double*)ps.vp_perm);
+  if (!factored) {
+    HIPCHK(ps.lifp.ensure(R * C2 * 2 * sizeof(double)));
+    HIPCHK(ps.pinv.ensure(R * C2 * 2 * sizeof(double)));
+    HIPCHK(ps.pinvT.ensure(R * C2 * 2 * sizeof(double)));
+    double *lifp = ps.lifp.as<double>(), *pinv = ps.pinv.as<double>(), *pinvT = ps.pinvT.as<double>();
+    if (int r = launch(h, qt::k_lifp_rows, dim3(grid_for(R * C2)), dim3(256), 0, d, M, ps.in_states.as<double>(),
+                       ps.emats.as<double>(), lifp))
+      return r;
+    if (int r = enqueue_left_inverse<2>(h, lifp, (int)R, (int)C2, pinv)) return r;
+    launch_transpose<2>(h, pinv, (int)C2, (int)R, pinvT);
+    if (h->nq == 2) {  // the batched GEMM of qt_lifp_batch reads the left inverse in row-major Choi order
+      HIPCHK(ps.pinvR.ensure(R * C2 * 2 * sizeof(double)));
+      if (int r = launch(h, qt::k_choi_order_rows, dim3(grid_for(R * C2)), dim3(256), 0, pinvT, R, D, ps.pinvR.as<double>()))
+        return r;
+    }
+    HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   }
+  if (factors)  // the permuted operand of k_lifp64 / k_lifp16 (the matrix-core paths of qt_lifp_batch) wants M % 4 == 0
+    if (int r = enqueue_factors(h, M % 4 ? 0 : (factored ? 4 : 1), finfo)) return r;
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "process design matrix is rank deficient (column %d): input states x POVM not complete", info - 1);
-  if (factors && (finfo[0] != 0 || finfo[1] != 0)) {  // (cannot happen when the Kronecker product itself has full rank)
-    (void)hipFree(ps.vp_perm);
-    ps.vp_perm = nullptr;
-  }
+  if (factored && finfo[0] != 0) return fail(QT_ERR_SINGULAR, "input states do not span the operator space (column %d)", finfo[0] - 1);
+  if (factored && finfo[1] != 0) return fail(QT_ERR_SINGULAR, "POVM is not informationally complete (column %d)", finfo[1] - 1);
+  ps.factored = factored;
+  ps.factors = factors && finfo[0] == 0 && finfo[1] == 0;
+  ps.perm = ps.factors && M % 4 == 0;
+  if (factors && !ps.factors)  // n = 2 goes on with the dense form alone (cannot happen when the Kronecker product has full rank)
+    for (DevBuf* b : {&ps.vs_pinv, &ps.vp_pinv, &ps.vp_pinvT, &ps.vp_perm}) b->release();
   h->proc_set = true;
   return 0;
 }
@@ -1997,8 +2033,8 @@ int qt_process_get_operators(qt_handle_t* h, double* lifp_oper, double* lifp_ope
     return fail(QT_ERR_UNSUPPORTED, "at n = 3 the design matrix is kept Kronecker-factored (qt_process_get_factors); its dense "
                                     "form would be 2 x 906 MB");
   const size_t n = (size_t)h->D * h->M * h->D * h->D * 2;
-  if (int r = c.copy_out(lifp_oper, (const double*)h->proc.lifp, n)) return r;
-  if (int r = c.copy_out(lifp_oper_inv, (const double*)h->proc.pinv, n)) return r;
+  if (int r = c.copy_out(lifp_oper, h->proc.lifp.as<const double>(), n)) return r;
+  if (int r = c.copy_out(lifp_oper_inv, h->proc.pinv.as<const double>(), n)) return r;
   return c.done();
 }
 
@@ -2012,11 +2048,11 @@ int qt_process_get_factors(qt_handle_t* h, double* vs_pinv, double* vp_pinv, int
   QT_ENTER(h);
   Call c(h, flags);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
-  if (!h->proc.vs_pinv || !h->proc.vp_pinv)
+  if (!h->proc.factors)
     return fail(QT_ERR_UNSUPPORTED, "this set-up keeps the dense operator only (n = 1, or a POVM with M % 4 != 0 at n = 2): "
                                     "qt_process_get_operators");
-  if (int r = c.copy_out(vs_pinv, (const double*)h->proc.vs_pinv, (size_t)h->D * h->D * 2)) return r;
-  if (int r = c.copy_out(vp_pinv, (const double*)h->proc.vp_pinv, (size_t)h->D * h->M * 2)) return r;
+  if (int r = c.copy_out(vs_pinv, h->proc.vs_pinv.as<const double>(), (size_t)h->D * h->D * 2)) return r;
+  if (int r = c.copy_out(vp_pinv, h->proc.vp_pinv.as<const double>(), (size_t)h->D * h->M * 2)) return r;
   return c.done();
 }
 
@@ -2028,6 +2064,7 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
   if (B < 0 || (B > 0 && (!counts || !choi))) return fail(QT_ERR_ARG, "bad lifp_batch arguments");
   if (B == 0) return 0;
   const int D = h->D, M = h->M;
+  const ProcessState& ps = h->proc;
   const int64_t* dc;
   double* dchoi;
   int32_t *dit, *dst;
@@ -2035,98 +2072,102 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
   if (int r = c.out(choi, (size_t)B * D * D * 2, &dchoi)) return r;
   if (int r = c.out(iters, (size_t)B, &dit)) return r;
   if (int r = c.out(status, (size_t)B, &dst)) return r;
-  if (h->proc.factored) {  // n = 3: X = V_S^+ F V_P^+^T, two small products per process (qt_process64.h)
+  // 1. The path.  R doubles of frequencies per process, Rp with the pitch k_lifp_freq pads to (at n = 3 R is a multiple
+  // of 64 already and the factored GEMM reads the rows unpadded).
+  const int R = D * M, Rp = ps.factored ? R : (R + 63) / 64 * 64;
+  const size_t dyn = (size_t)D * M * sizeof(double);
+  const size_t gemm_lds = ((size_t)Rp * 16 + 4 * 256) * sizeof(double);
+  const size_t gemm_lds2 = ((size_t)Rp * 32 + 4 * 512) * sizeof(double);  // two column tiles per workgroup
+  enum { kLifp64, kKronGemm, kLifp16, kDenseGemm, kFused } path;
+  if (ps.factored) {  // n = 3: X = V_S^+ F V_P^+^T, two small products per process (qt_process64.h)
     if ((size_t)B * D > (size_t)1 << 26) return fail(QT_ERR_ARG, "batch too large");
-    const int R = D * M;  // 13824: a multiple of 64, the pitch k_lifp_freq pads to
-    double* raw = dchoi;
-    if (cptp) {
-      HIPCHK(h->ws_f.ensure((size_t)B * D * D * 2 * sizeof(double)));
-      raw = h->ws_f.as<double>();
-    }
-    if (h->proc.vp_perm) {  // M % 4 == 0: both products of a process in one kernel on the matrix cores
-      hipLaunchKernelGGL(qt::k_lifp64, dim3(4 * B), dim3(256), 0, h->stream, dc, B, M, (const double*)h->proc.vp_perm,
-                         (const double*)h->proc.vs_pinv, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit);
-    } else {
-      HIPCHK(h->ws_x.ensure(((size_t)B * R + 192) * sizeof(double)));
+    path = ps.perm ? kLifp64 : kKronGemm;
+  } else {
+    if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
+    if (D == 16 && ps.perm && !h->proc_dense) path = kLifp16;
+    else if (D == 16 && B >= 256 && gemm_lds <= 152 * 1024) path = kDenseGemm;
+    else path = kFused;  // k_lifp_batch: the one kernel that projects by itself
+  }
+  // 2. The linear inversion into `raw`: the caller's array, or -- when a projection follows -- a workspace; the projection
+  // then reports iters and status, and the inversion gets neither.
+  const bool then_project = cptp && path != kFused;
+  double* raw = dchoi;
+  int32_t *rst = dst, *rit = dit;
+  if (then_project) {
+    HIPCHK(h->ws_f.ensure((size_t)B * D * D * 2 * sizeof(double)));
+    raw = h->ws_f.as<double>();
+    rst = rit = nullptr;
+  }
+  double* F = nullptr;  // [B][Rp] frequencies (+ the zeros k_lifp_freq appends) of the two GEMM paths
+  if (path == kKronGemm || path == kDenseGemm) {
+    HIPCHK(h->ws_x.ensure(((size_t)B * Rp + 192) * sizeof(double)));
+    F = h->ws_x.as<double>();
+    if (int r = launch(h, qt::k_lifp_freq, dim3((B * D + 15) / 16), dim3(256), 0, dc, B * D, M, D, Rp, F)) return r;
+  }
+  switch (path) {
+    case kLifp64:  // M % 4 == 0: both products of a process in one kernel on the matrix cores
+      if (int r = launch(h, qt::k_lifp64, dim3(4 * B), dim3(256), 0, dc, B, M, ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(),
+                         raw, rst, rit))
+        return r;
+      break;
+    case kKronGemm: {
       HIPCHK(h->ws_g.ensure((size_t)B * D * D * 2 * sizeof(double)));
-      double *F = h->ws_x.as<double>(), *T = h->ws_g.as<double>();
-      hipLaunchKernelGGL(qt::k_lifp_freq, dim3((B * D + 15) / 16), dim3(256), 0, h->stream, dc, B * D, M, D, R, F);
+      double* T = h->ws_g.as<double>();
       // T[(b, s)][beta] = sum_m F[(b, s)][m] V_P^+[beta][m]: real x complex = a real GEMM with 2 D interleaved columns
       for (int b0 = 0; b0 < B; b0 += 8192) {  // (grid.y <= 65535 row tiles)
         const int nb = B - b0 < 8192 ? B - b0 : 8192;
-        hipLaunchKernelGGL(qt::k_gemm<0>, dim3(2 * D / 16, (nb * D + 15) / 16), dim3(64), 0, h->stream, nb * D, 2 * D, M,
-                           F + (size_t)b0 * R, M, 0, (const double*)h->proc.vp_pinvT, 2 * D, 0, T + (size_t)b0 * D * D * 2, 2 * D);
+        if (int r = launch(h, qt::k_gemm<0>, dim3(2 * D / 16, (nb * D + 15) / 16), dim3(64), 0, nb * D, 2 * D, M, F + (size_t)b0 * R,
+                           M, 0, ps.vp_pinvT.as<double>(), 2 * D, 0, T + (size_t)b0 * D * D * 2, 2 * D))
+          return r;
       }
-      hipLaunchKernelGGL(qt::k_lifp_kron_finish, dim3(B), dim3(256), 0, h->stream, (const double*)T,
-                         (const double*)h->proc.vs_pinv, B, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit);
+      if (int r = launch(h, qt::k_lifp_kron_finish, dim3(B), dim3(256), 0, T, ps.vs_pinv.as<double>(), B, raw, rst, rit)) return r;
+      break;
     }
-    if (cptp)
-      if (int r = project64(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
-    return c.done(status, B);
-  }
-  const size_t dyn = (size_t)D * M * sizeof(double);
-  if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-  const int R = D * M, Rp = (R + 63) / 64 * 64;
-  const size_t gemm_lds = ((size_t)Rp * 16 + 4 * 256) * sizeof(double);
-  const size_t gemm_lds2 = ((size_t)Rp * 32 + 4 * 512) * sizeof(double);  // two column tiles per workgroup
-  if (D == 16 && h->proc.vp_perm && !h->proc_dense) {
-    // n = 2 through the Kronecker factors of the left inverse: one wavefront per process (qt_process.h, k_lifp16)
-    double* raw = dchoi;
-    if (cptp) {
-      HIPCHK(h->ws_g.ensure((size_t)B * 256 * 2 * sizeof(double)));
-      raw = h->ws_g.as<double>();
-    }
-    int grid = (B + 3) / 4;
-    if (grid > 768) grid = 768;  // three resident workgroups per CU (166 VGPRs): the wavefronts stride over the batch with the
-                                 // next process's counts in flight, and a workgroup stages V_P^+ once for all its processes
-    const size_t lds = (size_t)M * 32 * sizeof(double);
-    int32_t *st = cptp ? (int32_t*)nullptr : dst, *it0 = cptp ? (int32_t*)nullptr : dit;
-    hipLaunchKernelGGL((M == 36 ? qt::k_lifp16<9> : qt::k_lifp16<0>), dim3(grid), dim3(256), lds, h->stream, dc, B, M,
-                       (const double*)h->proc.vp_perm, (const double*)h->proc.vs_pinv, raw, st, it0);
-    if (cptp)
-      if (int r = project16(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
-  } else if (D == 16 && B >= 256 && gemm_lds <= 152 * 1024) {
-    // many processes: frequencies, then one FP64 MFMA GEMM over the batch, then (cptp) the projection kernel
-    constexpr int NE = 256;
-    HIPCHK(h->ws_x.ensure(((size_t)B * Rp + 192) * sizeof(double)));  // [B][Rp] + the zeros k_lifp_freq appends
-    double* F = h->ws_x.as<double>();
-    double* raw = dchoi;
-    if (cptp) {
-      HIPCHK(h->ws_g.ensure((size_t)B * NE * 2 * sizeof(double)));
-      raw = h->ws_g.as<double>();
-    }
-    hipLaunchKernelGGL(qt::k_lifp_freq, dim3((B * D + 15) / 16), dim3(256), 0, h->stream, dc, B * D, M, D, Rp, F);
-    // 4 groups of 16 processes per workgroup pass (x 2 halves of K).  A workgroup keeps its operand slice for up
-    // to 4 passes once there are enough blocks to fill the chip anyway (measured: B = 1024 best with 1-2 passes,
-    // 26 M/s; B = 8192 with 4, 38 M/s against 35 M/s with 1)
-    const int nblocks = (B + 63) / 64;
-    const int passes = nblocks >= 64 ? 4 : (nblocks >= 32 ? 2 : 1);
-    const int row_blocks = (nblocks + passes - 1) / passes;
-    const bool two = gemm_lds2 <= kLdsLimit;  // two column tiles per workgroup: half the re-reads of F (R <= 576)
-    auto kern = two ? qt::k_lifp_gemm<16, 2> : qt::k_lifp_gemm<16, 1>;
+    case kLifp16:  // n = 2 through the Kronecker factors of the left inverse: one wavefront per process (qt_process.h).
+      // At most 768 workgroups, three resident per CU (166 VGPRs): the wavefronts stride over the batch with the next
+      // process's counts in flight, and a workgroup stages V_P^+ once for all its processes
+      if (int r = launch(h, M == 36 ? qt::k_lifp16<9> : qt::k_lifp16<0>, dim3(std::min((B + 3) / 4, 768)), dim3(256),
+                         (size_t)M * 32 * sizeof(double), dc, B, M, ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(), raw, rst, rit))
+        return r;
+      break;
+    case kDenseGemm: {  // many processes: frequencies, then one FP64 MFMA GEMM over the batch
+      constexpr int NE = 256;
+      // 4 groups of 16 processes per workgroup pass (x 2 halves of K).  A workgroup keeps its operand slice for up
+      // to 4 passes once there are enough blocks to fill the chip anyway (measured: B = 1024 best with 1-2 passes,
+      // 26 M/s; B = 8192 with 4, 38 M/s against 35 M/s with 1)
+      const int nblocks = (B + 63) / 64;
+      const int passes = nblocks >= 64 ? 4 : (nblocks >= 32 ? 2 : 1);
+      const int row_blocks = (nblocks + passes - 1) / passes;
+      const bool two = gemm_lds2 <= kLdsLimit;  // two column tiles per workgroup: half the re-reads of F (R <= 576)
+      auto kern = two ? qt::k_lifp_gemm<16, 2> : qt::k_lifp_gemm<16, 1>;
 #ifdef QT_PHASE_TIMING
-    switch (two ? g_host_diag : 0) {  // profile build: a compile-time variant of the two-tile kernel (qt_debug_set_diag)
-      case 0: break;
-      case 1: kern = qt::k_lifp_gemm<16, 2, 1>; break;
-      case 2: kern = qt::k_lifp_gemm<16, 2, 2>; break;
-      case 3: kern = qt::k_lifp_gemm<16, 2, 3>; break;
-      case 4: kern = qt::k_lifp_gemm<16, 2, 4>; break;
-      case 7: kern = qt::k_lifp_gemm<16, 2, 7>; break;
-      case 8: kern = qt::k_lifp_gemm<16, 2, 8>; break;
-      case 15: kern = qt::k_lifp_gemm<16, 2, 15>; break;
-      default: return fail(QT_ERR_ARG, "no such diagnostic variant");
-    }
+      switch (two ? g_host_diag : 0) {  // profile build: a compile-time variant of the two-tile kernel (qt_debug_set_diag)
+        case 0: break;
+        case 1: kern = qt::k_lifp_gemm<16, 2, 1>; break;
+        case 2: kern = qt::k_lifp_gemm<16, 2, 2>; break;
+        case 3: kern = qt::k_lifp_gemm<16, 2, 3>; break;
+        case 4: kern = qt::k_lifp_gemm<16, 2, 4>; break;
+        case 7: kern = qt::k_lifp_gemm<16, 2, 7>; break;
+        case 8: kern = qt::k_lifp_gemm<16, 2, 8>; break;
+        case 15: kern = qt::k_lifp_gemm<16, 2, 15>; break;
+        default: return fail(QT_ERR_ARG, "no such diagnostic variant");
+      }
 #endif
-    if (int r = launch(h, kern, dim3(2 * NE / (two ? 32 : 16), row_blocks), dim3(512), two ? gemm_lds2 : gemm_lds, F, B, R, Rp,
-                       (const double*)h->proc.pinvR, raw, cptp ? (int32_t*)nullptr : dst, cptp ? (int32_t*)nullptr : dit))
-      return r;
-    if (cptp)
-      if (int r = project16(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
-  } else {
-    hipLaunchKernelGGL((D == 4 ? qt::k_lifp_batch<4> : qt::k_lifp_batch<16>), dim3(B),
-                       dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M, (const double*)h->proc.pinvT,
-                       cptp, dchoi, dit, dst);
+      if (int r = launch(h, kern, dim3(2 * NE / (two ? 32 : 16), row_blocks), dim3(512), two ? gemm_lds2 : gemm_lds, F, B, R, Rp,
+                         ps.pinvR.as<double>(), raw, rst, rit))
+        return r;
+      break;
+    }
+    case kFused:
+      if (int r = launch(h, D == 4 ? qt::k_lifp_batch<4> : qt::k_lifp_batch<16>, dim3(B),
+                         dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, B, M, ps.pinvT.as<double>(), cptp, dchoi,
+                         dit, dst))
+        return r;
+      break;
   }
+  // 3. The projection, where the path left it to do.
+  if (then_project)
+    if (int r = project(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
   return c.done(status, B);
 }
 
@@ -2149,23 +2190,14 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
   if (int r = c.out(status, (size_t)B, &dst)) return r;
   if (h->proc.factored) {  // n = 3: three launches per iteration over the batch, loop state on the device (qt_process64.h)
     using S = qt::Pgdb64;
-    const size_t ne2 = (size_t)D * D * 2;
-    HIPCHK(h->ws_x.ensure((size_t)B * S::ws_doubles(M) * sizeof(double)));
-    HIPCHK(h->ws_g.ensure((size_t)B * ne2 * sizeof(double)));  // trial points c - g / mu
-    HIPCHK(h->ws_f.ensure((size_t)B * ne2 * sizeof(double)));  // their CPTP projections
-    HIPCHK(h->ws_act.ensure(((size_t)B * 4 + 4) * sizeof(int32_t)));
-    int32_t* state = h->ws_act.as<int32_t>();
-    int32_t* n_active = state + (size_t)B * 4;
-    const double *vs = (const double*)h->proc.in_states, *vp = (const double*)h->proc.emats;
-    hipLaunchKernelGGL(qt::k_pgdb64_init, dim3(B), dim3(256), 0, h->stream, B, dchoi, state, dit, dst, n_active);
+    if (int r = pgdb64_scratch(h, B)) return r;
+    int32_t *state = h->ws_act.as<int32_t>(), *n_active = state + (size_t)B * 4;
+    if (int r = launch(h, qt::k_pgdb64_init, dim3(B), dim3(256), 0, B, dchoi, state, dit, dst, n_active)) return r;
     for (int it = 0; it < n_iter; ++it) {
-      if (int r = launch(h, qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, vs, vp, (const double*)dchoi,
-                         (const int32_t*)state, h->ws_x.as<double>(), h->ws_g.as<double>()))
-        return r;
-      if (int r = project64(h, h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr)) return r;
-      if (int r = launch(h, qt::k_pgdb64_step, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, vs, vp,
-                         (const double*)h->ws_f.as<double>(), n_iter, tol, stop_rule, dchoi, state, h->ws_x.as<double>(), dit, dst,
-                         n_active))
+      if (int r = pgdb64_trial(h, dc, B, dchoi)) return r;
+      if (int r = launch(h, qt::k_pgdb64_step, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, h->proc.in_states.as<double>(),
+                         h->proc.emats.as<double>(), h->ws_f.as<double>(), n_iter, tol, stop_rule, dchoi, state,
+                         h->ws_x.as<double>(), dit, dst, n_active))
         return r;
       int left = 0;
       HIPCHK(hipMemcpyAsync(&left, n_active, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -2177,9 +2209,10 @@ int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, doub
   }
   const size_t dyn = (size_t)4 * D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-  hipLaunchKernelGGL((D == 4 ? qt::k_pgdb_batch<4> : qt::k_pgdb_batch<16>), dim3(B),
-                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, h->stream, dc, B, M, (const double*)h->proc.lifp,
-                     n_iter, tol, stop_rule, dchoi, dit, dst);
+  if (int r = launch(h, D == 4 ? qt::k_pgdb_batch<4> : qt::k_pgdb_batch<16>, dim3(B),
+                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, B, M, h->proc.lifp.as<double>(), n_iter, tol,
+                     stop_rule, dchoi, dit, dst))
+    return r;
   return c.done(status, B);
 }
 
@@ -2193,31 +2226,23 @@ int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* c
   if (B == 0) return 0;
   using S = qt::Pgdb64;
   const int D = h->D, M = h->M, R = D * M;
-  const size_t ne2 = (size_t)D * D * 2, wsd = S::ws_doubles(M);
+  const size_t ne2 = (size_t)D * D * 2;
   const int64_t* dc;
   const double* dcur;
   if (int r = c.in(counts, (size_t)B * R, &dc)) return r;
   if (int r = c.in(choi_in, (size_t)B * ne2, &dcur)) return r;
-  HIPCHK(h->ws_x.ensure((size_t)B * wsd * sizeof(double)));
-  HIPCHK(h->ws_g.ensure((size_t)B * ne2 * sizeof(double)));
-  HIPCHK(h->ws_f.ensure((size_t)B * ne2 * sizeof(double)));
-  HIPCHK(h->ws_act.ensure(((size_t)B * 4 + 4) * sizeof(int32_t)));
-  int32_t* state = h->ws_act.as<int32_t>();
-  HIPCHK(hipMemsetAsync(state, 0, ((size_t)B * 4 + 4) * sizeof(int32_t), h->stream));
-  if (int r = launch(h, qt::k_pgdb64_grad, dim3(B), dim3(S::NT), S::kLdsBytes, dc, B, M, (const double*)h->proc.in_states,
-                     (const double*)h->proc.emats, dcur, (const int32_t*)state, h->ws_x.as<double>(), h->ws_g.as<double>()))
-    return r;
-  if (int r = project64(h, h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr)) return r;
+  if (int r = pgdb64_scratch(h, B)) return r;
+  HIPCHK(hipMemsetAsync(h->ws_act.p, 0, ((size_t)B * 4 + 4) * sizeof(int32_t), h->stream));  // no process has stopped
+  if (int r = pgdb64_trial(h, dc, B, dcur)) return r;
   HIPCHK(hipGetLastError());
-  const hipMemcpyKind kind = c.to_caller();
-  const double* ws = h->ws_x.as<double>();
+  // p and g of every process's block, strided by the block, into the caller's dense arrays
+  const S::Ws ws(h->ws_x.as<double>(), 0, M);
+  const size_t pitch = S::ws_doubles(M) * sizeof(double);
   if (probas)
-    HIPCHK(hipMemcpy2DAsync(probas, (size_t)R * sizeof(double), ws + (size_t)2 * D * M, wsd * sizeof(double),
-                            (size_t)R * sizeof(double), B, kind, h->stream));
-  if (grad)
-    HIPCHK(hipMemcpy2DAsync(grad, ne2 * sizeof(double), ws + (size_t)2 * D * M + 3 * (size_t)R, wsd * sizeof(double),
-                            ne2 * sizeof(double), B, kind, h->stream));
-  if (int r = c.copy_out(projected, h->ws_f.as<double>(), (size_t)B * ne2)) return r;
+    HIPCHK(hipMemcpy2DAsync(probas, (size_t)R * sizeof(double), ws.p(), pitch, (size_t)R * sizeof(double), B, c.to_caller(),
+                            h->stream));
+  if (grad) HIPCHK(hipMemcpy2DAsync(grad, ne2 * sizeof(double), ws.g(), pitch, ne2 * sizeof(double), B, c.to_caller(), h->stream));
+  if (int r = c.copy_out(projected, h->ws_f.as<const double>(), (size_t)B * ne2)) return r;
   return c.done();
 }
 
@@ -2241,40 +2266,36 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
   if (int r = c.in(uniforms, (size_t)C * T, &du)) return r;
   if (int r = c.out(chain, (size_t)C * T * ne * 2, &dch)) return r;
   if (int r = c.out(accepted, (size_t)C * T, &dacc)) return r;
-  if (h->proc.factored) {  // n = 3: three launches per step, the chain's state stays on the device (qt_process64.h)
-    using S = qt::Pgdb64;
+  if (h->proc.factored) {  // n = 3: four launches per step, the chain's state stays on the device (qt_process64.h)
     const int nt = qt::Fwd64::tiles(M);
-    HIPCHK(h->ws_x.ensure(((size_t)C * S::ws_doubles(M) + C + (size_t)C * nt) * sizeof(double)));
+    HIPCHK(h->ws_x.ensure(((size_t)C + (size_t)C * nt) * sizeof(double)));  // the points' NLLs and their pieces per row tile
     HIPCHK(h->ws_g.ensure((size_t)C * ne * 2 * sizeof(double)));     // proposals before the projection
     HIPCHK(h->ws_f.ensure((size_t)C * ne * 2 * sizeof(double)));     // ... and after it
     HIPCHK(h->hess.ensure((size_t)C * ne * 2 * sizeof(double)));     // the chains' current points
-    double *ws = h->ws_x.as<double>(), *fcur = ws + (size_t)C * S::ws_doubles(M), *fpart = fcur + C, *x = h->hess.as<double>();
-    const double *vs = (const double*)h->proc.in_states, *vp = (const double*)h->proc.emats;
+    double *fcur = h->ws_x.as<double>(), *fpart = fcur + C, *x = h->hess.as<double>();
+    double *trial = h->ws_g.as<double>(), *proj = h->ws_f.as<double>();
+    const double *vs = h->proc.in_states.as<double>(), *vp = h->proc.emats.as<double>(), *none = nullptr;
     HIPCHK(hipMemcpyAsync(x, dx, (size_t)C * ne * 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     // the model and the NLL of a point: C x ceil(M / 16) workgroups on the matrix cores (k_fwd64_nll), then the accept test
-    if (int r = launch(h, qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, C, M, vs, vp, (const double*)x,
-                       (const double*)nullptr, 0, fpart))
+    if (int r = launch(h, qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, C, M, vs, vp, x, none, 0, fpart))
       return r;
-    hipLaunchKernelGGL(qt::k_mhmc64_decide, dim3(C), dim3(256), 0, h->stream, C, nt, T, -1, (const double*)fpart,
-                       (const double*)nullptr, du, x, fcur, dch, dacc);
+    if (int r = launch(h, qt::k_mhmc64_decide, dim3(C), dim3(256), 0, C, nt, T, -1, fpart, none, du, x, fcur, dch, dacc)) return r;
     for (int t = 0; t < T; ++t) {
-      hipLaunchKernelGGL(qt::k_mhmc64_propose, dim3(C), dim3(256), 0, h->stream, C, T, t, step, (const double*)x, dd,
-                         h->ws_g.as<double>());
-      if (int r = project64(h, h->ws_g.as<double>(), C, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr)) return r;
-      if (int r = launch(h, qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, C, M, vs, vp, (const double*)x,
-                         (const double*)h->ws_f.as<double>(), 1, fpart))
+      if (int r = launch(h, qt::k_mhmc64_propose, dim3(C), dim3(256), 0, C, T, t, step, x, dd, trial)) return r;
+      if (int r = project(h, trial, C, 0, 1000, 1e-12, proj, nullptr, nullptr)) return r;
+      if (int r = launch(h, qt::k_fwd64_nll, dim3(C * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, C, M, vs, vp, x, proj, 1, fpart))
         return r;
-      hipLaunchKernelGGL(qt::k_mhmc64_decide, dim3(C), dim3(256), 0, h->stream, C, nt, T, t, (const double*)fpart,
-                         (const double*)h->ws_f.as<double>(), du, x, fcur, dch, dacc);
+      if (int r = launch(h, qt::k_mhmc64_decide, dim3(C), dim3(256), 0, C, nt, T, t, fpart, proj, du, x, fcur, dch, dacc)) return r;
     }
     HIPCHK(hipGetLastError());
     return c.done();
   }
   const size_t dyn = (size_t)2 * D * M * sizeof(double);
   if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-  hipLaunchKernelGGL((D == 4 ? qt::k_mhmc_process<4> : qt::k_mhmc_process<16>), dim3(C),
-                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, h->stream, dc, C, M, (const double*)h->proc.lifp, dx,
-                     dd, du, T, step, dch, dacc);
+  if (int r = launch(h, D == 4 ? qt::k_mhmc_process<4> : qt::k_mhmc_process<16>, dim3(C),
+                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, C, M, h->proc.lifp.as<double>(), dx, dd, du, T,
+                     step, dch, dacc))
+    return r;
   return c.done();
 }
 
@@ -2293,15 +2314,8 @@ int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode
   if (int r = c.in(choi_in, (size_t)B * D * D * 2, &din)) return r;
   if (int r = c.out(choi_out, (size_t)B * D * D * 2, &dout)) return r;
   if (int r = c.out(iters, (size_t)B, &dit)) return r;
-  int r = 0;
-  if (D == 64)
-    r = project64(h, din, B, mode, n_iter, tol, dout, dit, nullptr);
-  else if (D == 16)
-    r = project16(h, din, B, mode, n_iter, tol, dout, dit, nullptr);
-  else
-    hipLaunchKernelGGL(qt::k_cptp_project<4>, dim3(B), dim3(qt::ProcWG<4>::NT), 0, h->stream, din, B, mode, n_iter, tol, dout,
-                       dit);
-  return r ? r : c.done();
+  if (int r = project(h, din, B, mode, n_iter, tol, dout, dit, nullptr)) return r;
+  return c.done();
 }
 
 }  // extern "C"
