@@ -117,20 +117,38 @@ __device__ __forceinline__ double gsum(double v) {
   }
   return v;
 }
-// Maximum of non-negative values (every caller passes fabs(.)); a NaN anywhere wins.  The rows a
-// row_bcast step leaves out read 0, which is neutral for such inputs.
+// "Does `pred` hold in any lane of this lane's group": one ballot and a mask (the whole wave at G = 64).  Executed by
+// every lane of the wavefront.
+template <int G>
+__device__ __forceinline__ bool group_any(bool pred) {
+  const unsigned long long votes = __builtin_amdgcn_ballot_w64(pred);
+  if (G == 64) return votes != 0ull;
+  const int lane = threadIdx.x & 63;
+  return (votes & (((1ull << (G & 63)) - 1ull) << (lane / G * G))) != 0ull;
+}
+// v_max_f64 as it stands: of a NaN and a number it returns the number.  (fmax() in C++ makes the compiler put a
+// canonicalising v_max_f64 v, v, v in front of the operand that comes out of a DPP move -- one extra instruction per
+// level of the butterfly below: 49 instead of 42 for gmax<64>, against 63 for the compare-and-select form.)
+__device__ __forceinline__ double max_f64(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// Maximum of non-negative values (every caller passes fabs(.)); a NaN anywhere wins: the butterfly itself passes over
+// NaNs, one ballot finds them.  The rows a row_bcast step leaves out read 0, which is neutral for such inputs.
 template <int G>
 __device__ __forceinline__ double gmax(double v) {
-  v = nanmax(v, dpp_f64<0xB1>(v));
-  v = nanmax(v, dpp_f64<0x4E>(v));
-  if (G >= 8) v = nanmax(v, dpp_f64<0x141>(v));
-  if (G >= 16) v = nanmax(v, dpp_f64<0x140>(v));
+  const bool nan = group_any<G>(v != v);
+  v = max_f64(v, dpp_f64<0xB1>(v));
+  v = max_f64(v, dpp_f64<0x4E>(v));
+  if (G >= 8) v = max_f64(v, dpp_f64<0x141>(v));
+  if (G >= 16) v = max_f64(v, dpp_f64<0x140>(v));
   if (G == 64) {
-    v = nanmax(v, dpp_f64<0x142, 0xA>(v));
-    v = nanmax(v, dpp_f64<0x143, 0xC>(v));
+    v = max_f64(v, dpp_f64<0x142, 0xA>(v));
+    v = max_f64(v, dpp_f64<0x143, 0xC>(v));
     v = readlane_f64(v, 63);
   }
-  return v;
+  return nan ? __builtin_nan("") : v;
 }
 
 // log(x) and 1/x for the likelihood terms.  The OCML log is correctly rounded through ~85 FP64
@@ -143,6 +161,7 @@ __device__ __forceinline__ double recip_nr(double x) {  // 1/x to ~1 ulp: hardwa
   r = fma(r, fma(-x, r, 1.0), r);
   return fma(r, fma(-x, r, 1.0), r);
 }
+__device__ __forceinline__ bool log_is_regular(double x) { return x > 0.0 && x < 1.7e308; }  // fast_log's main branch
 __device__ __forceinline__ double fast_log(double x) {
   if (!(x > 0.0) || !(x < 1.7e308)) return x == 0.0 ? -__builtin_huge_val() : (x > 0.0 ? x : __builtin_nan(""));
   double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
@@ -1062,6 +1081,16 @@ struct Small {
       return 0.0;  // (not reached: both tables of the specialised shape are paired)
     }
   }
+  // One term of sum freq log p: the eager form (stage_n_log) and the deferred one (deferred_value) both accumulate
+  // through this expression, so that both contract to the same fma.
+  __device__ __forceinline__ static void add_log_term(double& fpart, double f, double l) { fpart += f * l; }
+  // What a deferred first evaluation keeps per lane: p of its rows (two per pass of stage_n_log over the 6^n rows of
+  // the specialised shape) and whether any valid row is outside fast_log's regular branch.
+  static constexpr int kLogPasses = ((NQ == 1 ? 6 : NQ == 2 ? 36 : 216) + 2 * G - 1) / (2 * G);
+  struct DeferredValue {
+    double p[2 * kLogPasses];
+    bool special;
+  };
   // Forward stage n fused with the log-likelihood terms: p = d w (.) X_n + 1e-10, the lane's share of
   // sum freq log p (returned), and Y_n = w (.) freq / p into `rb` (A'^T r = K^T (w (.) r)).  Two outputs per pass
   // so that their LDS round trips (table entry -> operands) overlap; the second of a pair is a recomputation of
@@ -1069,9 +1098,13 @@ struct Small {
   // PAIRED (ProductView::pairedT): a row keeps its lane -- the order of the sum over rows is part of the value's
   // bits -- and reads its two non-zero coefficients and their operands through the entries of ProductView::last.
   // UNI: equal shots, every row weight is wuni (the same division as wrowR[m]).
-  template <bool PAIRED, bool UNI, class C>
+  // DEFER (specialised kernels, first evaluation of a trial): no logarithms; the p of this lane's rows are kept in
+  // `dv` for deferred_value, with the flag "a valid row would take fast_log's special-case branch".  p and rb[] are
+  // formed by the same statements either way.  The specialised shape has M = 6^n rows, so the passes are counted at
+  // compile time and p[] stays in registers.
+  template <bool PAIRED, bool UNI, bool DEFER = false, class C>
   __device__ __forceinline__ static double stage_n_log(const C& c, const int* tab, const double* in, const double* fr,
-                                                       double* rb) {
+                                                       double* rb, DeferredValue* dv = nullptr) {
     const double* tb = c.tabT();
     auto x_of = [&](int ent) {
       if (!PAIRED) return stage_value<true>(tb, c.R1(), ent, 1, in);
@@ -1083,7 +1116,8 @@ struct Small {
       else return c.twrow[o];
     };
     double fpart = 0.0;
-    for (int o = c.l; o < c.M; o += 2 * G) {
+    bool special = false;
+    auto pass = [&](int o, int s) {
       const int o2 = o + G;
       const bool two = o2 < c.M;
       const int oo = two ? o2 : o;
@@ -1092,15 +1126,64 @@ struct Small {
       const double w0 = w_of(o), w1 = w_of(oo);
       const double f0 = fr[o], f1 = fr[oo];
       const double p0 = x0 * w0 * d + 1e-10, p1 = x1 * w1 * d + 1e-10;
-      const double l0 = fast_log(p0), l1 = fast_log(p1);
-      fpart += f0 * l0;
+      if constexpr (DEFER) {
+        dv->p[2 * s] = p0;
+        dv->p[2 * s + 1] = p1;
+        special |= !log_is_regular(p0);
+      } else {
+        const double l0 = fast_log(p0), l1 = fast_log(p1);
+        add_log_term(fpart, f0, l0);
+        if (two) add_log_term(fpart, f1, l1);
+      }
       rb[o] = w0 * f0 * recip_nr(p0);
       if (two) {
-        fpart += f1 * l1;
+        if constexpr (DEFER) special |= !log_is_regular(p1);
         rb[o2] = w1 * f1 * recip_nr(p1);
       }
+    };
+    if constexpr (DEFER) {
+#pragma unroll
+      for (int s = 0; s < kLogPasses; ++s) {
+        const int o = c.l + s * 2 * G;
+        dv->p[2 * s] = dv->p[2 * s + 1] = 1.0;
+        if (o < c.M) pass(o, s);
+      }
+      dv->special = special;
+    } else {
+      for (int o = c.l; o < c.M; o += 2 * G) pass(o, 0);
     }
     return fpart;
+  }
+  // -sum freq log p of a deferred first evaluation: the terms of stage_n_log in its row order, through the same
+  // add_log_term.  Executed by every lane of the wavefront; freq[] is still what stage_n_log read.
+  template <class C>
+  __device__ __forceinline__ static double deferred_value(const C& c, const DeferredValue& dv) {
+    const double* fr = c.freq();
+    double fpart = 0.0;
+#pragma unroll
+    for (int s = 0; s < kLogPasses; ++s) {
+      const int o = c.l + s * 2 * G;
+      if (o < c.M) {
+        const int o2 = o + G;
+        const bool two = o2 < c.M;
+        const double f0 = fr[o], f1 = fr[two ? o2 : o];
+        const double l0 = fast_log(dv.p[2 * s]), l1 = fast_log(dv.p[2 * s + 1]);
+        add_log_term(fpart, f0, l0);
+        if (two) add_log_term(fpart, f1, l1);
+      }
+    }
+    return -gsum<G>(fpart);
+  }
+  // The value of a deferred first evaluation where something reads it: `wanted` (the trial goes on to BFGS, or the
+  // caller asked for `fun`) or a p outside fast_log's regular branch, where the value may be a NaN and status 4 asks.
+  // Decided per wavefront: every lane runs the reduction or none does.  Otherwise 0: with every p positive and
+  // finite the value is no NaN unless a frequency is one, and then the gradient norm is a NaN as well.
+  template <class C>
+  __device__ __forceinline__ static double value_if_needed(const C& c, const DeferredValue& dv, bool wanted) {
+    if (!__any(wanted || dv.special)) return 0.0;
+    const double f = deferred_value(c, dv);
+    QT_STAMP(19);
+    return f;
   }
   // sum_m Op[m][lane] * vec[m]   (lane = column)
   template <class C>
@@ -1395,14 +1478,23 @@ struct Small {
     cd spec_inv{0.0, 0.0};
     double x = cholesky_param<SPEC && G == 64>(c, r, ok, &neg, &kneg, &spec_inv);
     QT_STAMP(3);
-    const double tr = gsum<G>(c.i == c.j ? r.re : 0.0);
-    cd out{r.re / tr, r.im / tr};
-    // 1 / sqrt(tr) for the Cholesky parameters of r / tr: hardware seed + Newton (~1 ulp) instead of an IEEE sqrt and
+    // The positive-definite epilogue: r / tr, and the Cholesky parameters of r / tr through
+    // 1 / sqrt(tr): hardware seed + Newton (~1 ulp) instead of an IEEE sqrt and
     // an IEEE division (~60 instructions on the critical path); tr = 1 up to the noise of the linear inversion
-    const double rst = tr > 0.0 ? fast_rsqrt(tr) : 1.0 / sqrt(tr);
-    x = x * rst;  // L of r/tr
-    double lscale = rst;  // Bm() holds the factor of r, not of r/tr
-    if (!__all(ok)) {
+    cd out{0.0, 0.0};
+    double lscale = 1.0;
+    auto pd_epilogue = [&]() {
+      const double tr = gsum<G>(c.i == c.j ? r.re : 0.0);
+      out = cd{r.re / tr, r.im / tr};
+      const double rst = tr > 0.0 ? fast_rsqrt(tr) : 1.0 / sqrt(tr);
+      x = x * rst;   // L of r/tr
+      lscale = rst;  // Bm() holds the factor of r, not of r/tr
+    };
+    // One trial per wave: `ok` is wave-uniform and a clipped trial replaces all of it, so it is formed only for the
+    // trials that keep it.  Several trials per wave: the groups differ, every lane runs it ahead of the branch.
+    const bool all_pd = __all(ok);
+    if (G < 64 || all_pd || (!xl && lscale_out)) pd_epilogue();
+    if (!all_pd) {
       cd proj;
       bool lifted = false;
       if constexpr (G == 64) {  // one trial per wave: neg / kneg are the same in every lane
@@ -1465,9 +1557,11 @@ struct Small {
     cd rho;         // this lane's element of the normalised start matrix
     double lscale;  // L(x) = lscale * Bm()
   };
-  template <class C>
+  // DEFER (specialised kernels only): `f` is left alone; `dv` receives what deferred_value needs to form it later.
+  template <bool DEFER = false, class C>
   __device__ static void nll_grad(const C& c, double xl, double& f, double& gl, cd* rho_l = nullptr,
-                                  bool want_grad = true, const StartPoint* start = nullptr) {
+                                  bool want_grad = true, const StartPoint* start = nullptr, DeferredValue* dv = nullptr) {
+    static_assert(!DEFER || !C::kGeneric, "the deferred value needs the compile-time row count of the specialised shape");
     double tr;
     QT_STAMP(11);
     cd m;
@@ -1512,14 +1606,16 @@ struct Small {
         in = out;
       }
       QT_STAMP(14);
-      if constexpr (!C::kGeneric) {
+      if constexpr (DEFER) {
+        stage_n_log<true, true, true>(c, tab, in, fr, rb, dv);
+      } else if constexpr (!C::kGeneric) {
         fpart = stage_n_log<true, true>(c, tab, in, fr, rb);
       } else {
         if (!paired) fpart = stage_n_log<false, false>(c, tab, in, fr, rb);
         else if (c.uniform()) fpart = stage_n_log<true, true>(c, tab, in, fr, rb);
         else fpart = stage_n_log<true, false>(c, tab, in, fr, rb);
       }
-      f = -gsum<G>(fpart);
+      if constexpr (!DEFER) f = -gsum<G>(fpart);
       wave_sync();
       QT_STAMP(15);
       if (!want_grad) return;  // (uniform) the Metropolis chain only needs the value
@@ -1738,16 +1834,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   }
   double fk, gk;
   cd rho_l;  // L L^dagger / Tr at x_k: what the trial returns if BFGS does not move
-  S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
+  [[maybe_unused]] typename S::DeferredValue dv;
+  if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
+  else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
   const double gnorm = gmax<G>(fabs(gk));
   const bool iterate = shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
+  if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
   int status = 0;
   if (!shots_ok) status = 5;
   else if (!ok) status = 1;
   else if (!iterate) {
-    const double xn = gmax<G>(fabs(xk));
+    const bool xnan = group_any<G>(xk != xk);
     if (0 >= max_iter) status = 3;
-    else if (gnorm != gnorm || fk != fk || xn != xn) status = 4;
+    else if (gnorm != gnorm || fk != fk || xnan) status = 4;
   }
   S::emit(c, rho, b, live, rho_l);
   if (live) {
@@ -2129,19 +2228,22 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   QT_STAMP(8);
   double fk, gk;
   cd rho_l;
-  S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
+  [[maybe_unused]] typename S::DeferredValue dv;
+  if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
+  else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
   const double gnorm = gmax<G>(fabs(gk));
   QT_STAMP(9);
   const bool iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
+  if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
   S::emit(c, rho, b, live && !iterate, rho_l);  // (trials that iterate are written at the end of the loop)
   if (!iterate) {
     int status = 0;
     if (!shots_ok) status = 5;
     else if (!ok) status = 1;
     else {
-      const double xn = gmax<G>(fabs(xk));
+      const bool xnan = group_any<G>(xk != xk);
       if (0 >= max_iter) status = 3;
-      else if (gnorm != gnorm || fk != fk || xn != xn) status = 4;
+      else if (gnorm != gnorm || fk != fk || xnan) status = 4;
     }
     if (live) {
       if (c.l == 0) {
