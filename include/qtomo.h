@@ -84,8 +84,17 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
  * 0 forces the dense-table stages.  Both give the same bits, the sign of a zero excepted.
  * QT_OPT_MLE_SPECIALISE (default 1): at n <= 3 the MLE kernels have a second instantiation compiled for the shape of
  * every built-in six-projector run ('proj-set': both tables paired and QT_OPT_PAIRED_STAGES on, equal shots per
- * setting, QT_OPT_SHOTS_CHECK on); 0 forces the generic instantiation.  Both give the same bits. */
-enum qt_option { QT_OPT_SHOTS_CHECK = 1, QT_OPT_MLE_FUSED_MAX_WAVES = 2, QT_OPT_PAIRED_STAGES = 3, QT_OPT_MLE_SPECIALISE = 4 };
+ * setting, QT_OPT_SHOTS_CHECK on); 0 forces the generic instantiation.  Both give the same bits.
+ * QT_OPT_LIFP_DIST_SLICE (default 0): qt_lifp_dist_batch runs its batch in slices of this many processes, so that the
+ * workspaces that follow the batch stay bounded; 0, or more than 128 MB of Choi matrices (2048 processes at n = 3,
+ * 32 768 at n = 2), takes that bound.  The same bits whatever the slice. */
+enum qt_option {
+  QT_OPT_SHOTS_CHECK = 1,
+  QT_OPT_MLE_FUSED_MAX_WAVES = 2,
+  QT_OPT_PAIRED_STAGES = 3,
+  QT_OPT_MLE_SPECIALISE = 4,
+  QT_OPT_LIFP_DIST_SLICE = 5
+};
 int qt_set_option(qt_handle_t* h, int option, double value);
 /* Which one-qubit tables of the current product POVM have that shape: bit 0 = T, bit 1 = pinv(T) as computed on the
  * device (0 without a product POVM and at n >= 4; independent of QT_OPT_PAIRED_STAGES). */
@@ -336,6 +345,15 @@ int qt_process_prefer_dense(qt_handle_t* h, int on);
  * projection of process.py:231-257 (n_iter <= 1000, stop 1e-12); iters[B] (nullable) */
 int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double* choi, int32_t* iters,
                   int32_t* status, int flags);
+/* The resample loop of the process bootstrap (interval.py:673-682) in one pass: qt_lifp_batch, and
+ * dist[B] = hs_dst(Choi_b, centre) as qt_hs_dist_dim computes it (sqrt(|sum_ij D_ij D_ji|) / sqrt(2), no conjugation, 0
+ * below 1e-15), for centre[D][D][2] (need not be Hermitian).  choi is NULLABLE: without it no matrix leaves the device.
+ * With it, choi / iters / status are bit-identical to qt_lifp_batch's.  n <= 2 on the default paths forms the distance
+ * in the kernel that holds the matrix (the order of its D^2-term sum is then that kernel's); every other path stores
+ * the matrices (in a handle workspace when choi is null, a slice at a time: QT_OPT_LIFP_DIST_SLICE) and runs
+ * qt_hs_dist_dim's kernel on them: the same bits as the two calls. */
+int qt_lifp_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, const double* centre, double* choi,
+                       double* dist, int32_t* iters, int32_t* status, int flags);
 /* 'pgdb' (process.py:291-308): projected gradient descent with backtracking from the fully mixed Choi
  * matrix, raw counts as weights, every arithmetic quirk of the reference kept (see qt_process.h).
  * stop_rule 0 = the reference's loop exit (leaves at the first step that lowers the NLL by more than

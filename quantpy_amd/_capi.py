@@ -13,6 +13,7 @@ QT_INIT_LIN = 0
 QT_INIT_MIXED = 1
 QT_STREAM_LEGACY = 1  # qt_set_stream: the legacy default ("null") stream
 QT_OPT_SHOTS_CHECK, QT_OPT_MLE_FUSED_MAX_WAVES, QT_OPT_PAIRED_STAGES, QT_OPT_MLE_SPECIALISE = 1, 2, 3, 4  # qt_set_option
+QT_OPT_LIFP_DIST_SLICE = 5  # processes per slice of qt_lifp_dist_batch (0: the library's byte bound)
 
 # status codes (include/qtomo.h)
 QT_ERR_ARG, QT_ERR_STATE, QT_ERR_HIP, QT_ERR_SINGULAR, QT_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
@@ -83,6 +84,7 @@ SIGNATURES = {
     "qt_process_get_factors": (_c_int, [_vp, _vp, _vp, _c_int]),
     "qt_process_prefer_dense": (_c_int, [_vp, _c_int]),
     "qt_lifp_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int]),
+    "qt_lifp_dist_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int]),
     "qt_pgdb_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _c_int, _vp, _vp, _vp, _c_int]),
     "qt_mhmc_process": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_dbl, _vp, _vp, _c_int]),
     "qt_cptp_project_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_int]),

@@ -363,7 +363,8 @@ template <int DC>
 __global__ void __launch_bounds__(ProcWG<DC>::NT, 4) k_lifp_batch(const int64_t* __restrict__ counts, int B, int M,
                                                               const double* __restrict__ pinvT, int cptp,
                                                               double* __restrict__ choi, int32_t* __restrict__ iters,
-                                                              int32_t* __restrict__ status) {
+                                                              int32_t* __restrict__ status,
+                                                              const double* __restrict__ centre, double* __restrict__ dist) {
   using W = ProcWG<DC>;
   __shared__ typename W::Sh sh;
   extern __shared__ double sfreq[];  // [DC * M]
@@ -408,7 +409,20 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 4) k_lifp_batch(const int64_t*
   __syncthreads();
   int it = 0;
   if (cptp) it = W::dykstra(sh, act, i, j, xr, xi, 1000, 1e-12);
-  if (act) {
+  if constexpr (DC == 4) {
+    // hs_dst(C, centre) as k_hs_dist forms it, the 16 elements in the first 16 lanes of the one wavefront: Delta_ji by a
+    // shuffle.  (uniform over the launch; DC = 16 callers pass null and run k_hs_dist on the stored matrices)
+    if (dist) {
+      cd dl{0.0, 0.0};
+      if (act) dl = cd{xr - centre[2 * tid], xi - centre[2 * tid + 1]};
+      const int src = act ? j * DC + i : tid;
+      const cd t = hs_term(dl, cd{__shfl(dl.re, src), __shfl(dl.im, src)});
+      const double sr = gsum<64>(t.re), si = gsum<64>(t.im);
+      const double v = sqrt(hypot(sr, si)) / sqrt(2.0);
+      if (tid == 0) dist[b] = v < 1e-15 ? 0.0 : v;
+    }
+  }
+  if (act && choi) {
     double* out = choi + ((size_t)b * W::NE + tid) * 2;
     out[0] = xr;
     out[1] = xi;
@@ -834,9 +848,10 @@ template <int KSC>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_lifp16(const int64_t* __restrict__ counts, int B, int M,
                                                 const double* __restrict__ vp_perm, const double* __restrict__ vs_pinv,
                                                 double* __restrict__ choi, int32_t* __restrict__ status,
-                                                int32_t* __restrict__ iters) {
-  constexpr int DC = 16;
-  extern __shared__ double s_vp[];  // [M][32]
+                                                int32_t* __restrict__ iters, const double* __restrict__ centre,
+                                                double* __restrict__ dist) {
+  constexpr int DC = 16, PT = DC + 1;
+  extern __shared__ __attribute__((aligned(16))) double s_vp[];  // [M][32]; with `dist`: + [4 wavefronts][16][PT] complex
   for (int k = threadIdx.x; k < M * 32; k += 256) s_vp[k] = vp_perm[k];
   const int lane = threadIdx.x & 63, r16 = lane & 15, kq = lane >> 4, w = threadIdx.x >> 6;
   cd va[4];  // A operand of the second product: V_S^+[alpha = r16][s = 4 r + kq]
@@ -896,15 +911,44 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
       xi1 = __builtin_amdgcn_mfma_f64_16x16x4f64(va[r].re, ti, xi1, 0, 0, 0);
       xi2 = __builtin_amdgcn_mfma_f64_16x16x4f64(va[r].im, tr, xi2, 0, 0, 0);
     }
-    cd* out = reinterpret_cast<cd*>(choi) + (size_t)b * DC * DC;
     const int e = r16 & 3, bb = r16 >> 2;
     bool nan = false;
+    cd x[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int alpha = kq + 4 * r, a = alpha >> 2, c = alpha & 3;
-      const cd x{xr1[r] + xr2[r], xi1[r] + xi2[r]};
-      out[(a * 4 + bb) * DC + c * 4 + e] = x;
-      nan = nan || !(x.re == x.re);
+      x[r] = cd{xr1[r] + xr2[r], xi1[r] + xi2[r]};
+      nan = nan || !(x[r].re == x[r].re);
+    }
+    // register r holds Choi element (row, col) = (4 r + bb, 4 kq + e)   (alpha = kq + 4 r = 4 a + c: a = r, c = kq)
+    if (choi) {
+      cd* out = reinterpret_cast<cd*>(choi) + (size_t)b * DC * DC;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[(r * 4 + bb) * DC + kq * 4 + e] = x[r];
+    }
+    if (dist) {  // (uniform over the launch) hs_dst(X, centre) as k_hs_dist forms it, Delta^T through this wavefront's scratch
+      cd* T = reinterpret_cast<cd*>(s_vp + M * 32) + w * DC * PT;
+      const cd* cen = reinterpret_cast<const cd*>(centre);
+      cd dl[4];
+      wave_sync();  // (the reads of the process before are done)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = r * 4 + bb, col = kq * 4 + e;
+        const cd c = cen[row * DC + col];
+        dl[r] = cd{x[r].re - c.re, x[r].im - c.im};
+        T[row * PT + col] = dl[r];
+      }
+      wave_sync();
+      double sr = 0.0, si = 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const cd t = hs_term(dl[r], T[(kq * 4 + e) * PT + r * 4 + bb]);
+        sr += t.re;
+        si += t.im;
+      }
+      sr = gsum<64>(sr);
+      si = gsum<64>(si);
+      const double v = sqrt(hypot(sr, si)) / sqrt(2.0);
+      if (lane == 0) dist[b] = v < 1e-15 ? 0.0 : v;
     }
     const bool any = __any(nan);  // (an input state without counts: NaN frequencies, process.py:285)
     if (lane == 0) {

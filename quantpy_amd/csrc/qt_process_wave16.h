@@ -219,6 +219,30 @@ struct ProcWave16 {
     return clip(L, a, eps);
   }
 
+  // sqrt(|Tr((X - C)^2)|) / sqrt(2) (geometry.py:16-20) of the matrix in the registers and the row-major `centre`:
+  // Tr(Delta Delta) = sum_ij Delta_ij Delta_ji, Delta^T through the transpose scratch; the terms and the final
+  // expression are k_hs_dist's (hs_term), the order of the 256-term sum is this layout's.  Every lane returns the same bits.
+  __device__ __forceinline__ static double hs_to_centre(const Lane& L, const cd (&x)[4], const cd* __restrict__ centre) {
+    cd dl[4], dt[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const cd c = centre[L.i(r) * DC + L.r16];
+      dl[r] = cd{x[r].re - c.re, x[r].im - c.im};
+    }
+    transpose(L, dl, dt);
+    double sr = 0.0, si = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const cd t = hs_term(dl[r], dt[r]);
+      sr += t.re;
+      si += t.im;
+    }
+    sr = gsum<64>(sr);
+    si = gsum<64>(si);
+    const double v = sqrt(hypot(sr, si)) / sqrt(2.0);
+    return v < 1e-15 ? 0.0 : v;
+  }
+
   // Dykstra alternation (process.py:237-257); returns the iteration count
   __device__ __forceinline__ static int dykstra(const Lane& L, cd (&x)[4], int n_iter, double tol) {
     cd p[4], q[4], y[4];
@@ -268,10 +292,13 @@ struct ProcWave16 {
   }
 };
 
-// mode 0: Dykstra CPTP, 1: TP only, 2: CP only; in / out [B][16][16] complex, row-major; one wavefront per process
+// mode 0: Dykstra CPTP, 1: TP only, 2: CP only; in / out [B][16][16] complex, row-major; one wavefront per process.
+// `dist` (uniform over the launch; null: none) takes hs_dst(projected matrix, centre) per process, formed on the registers
+// (ProcWave16::hs_to_centre); `out` may then be null: no matrix leaves the kernel (qt_lifp_dist_batch).
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_cptp_wave16(const double* __restrict__ in, int B, int mode, int n_iter, double tol,
                                                      double* __restrict__ out, int32_t* __restrict__ iters,
-                                                     int32_t* __restrict__ status) {
+                                                     int32_t* __restrict__ status, const double* __restrict__ centre,
+                                                     double* __restrict__ dist) {
   __shared__ cd scratch[4 * ProcWave16::kLdsComplexPerWave];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + w;
@@ -287,9 +314,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
   else if (mode == 1) ProcWave16::tp_project(L, x);
   else it = ProcWave16::cp_project(L, x, 1e-12);
   QT_STAMP(1);
-  cd* dst = reinterpret_cast<cd*>(out) + (size_t)b * 256;
+  if (dist) {
+    const double v = ProcWave16::hs_to_centre(L, x, reinterpret_cast<const cd*>(centre));
+    if (lane == 0) dist[b] = v;
+  }
+  if (out) {
+    cd* dst = reinterpret_cast<cd*>(out) + (size_t)b * 256;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) dst[L.i(r) * 16 + L.r16] = x[r];
+    for (int r = 0; r < 4; ++r) dst[L.i(r) * 16 + L.r16] = x[r];
+  }
   if (lane == 0) {
     if (iters) iters[b] = it;
     if (status) status[b] = (x[0].re == x[0].re) ? 0 : 4;

@@ -130,6 +130,7 @@ struct qt_handle {
   DevBuf stage[kStageBufs];
   DevBuf aug;      // [cols][2 cols] Gauss-Jordan workspace of enqueue_left_inverse
   DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project)
+  DevBuf lifp_dist_ws;  // qt_lifp_dist_batch without `choi`: one slice's Choi matrices, where k_hs_dist reads them
   DevBuf gram;  // qt_moment_batch: P^T P
   DevBuf moment_freq, moment_part, moment_qpart;  // k_moment_cols: counts / ns, the blocks' partial sums, Q_ab in pieces
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
@@ -149,6 +150,7 @@ struct qt_handle {
   double ns_tot = 0.0;  // sum of the registered shots per setting
   bool check_shots = true;  // qt_set_option(QT_OPT_SHOTS_CHECK) / QTOMO_SKIP_SHOTS_CHECK=1 at qt_create
   int fused_max_waves = 1024;  // qt_set_option(QT_OPT_MLE_FUSED_MAX_WAVES): largest batch (in trial-waves) of k_mle_fused
+  int lifp_dist_slice = 0;  // qt_set_option(QT_OPT_LIFP_DIST_SLICE): processes per slice of qt_lifp_dist_batch (0: the byte bound's)
   double ns_max = 0.0;  // largest registered shot number (product POVMs): the n >= 4 count cache holds 32-bit counts
   bool paired_stages = true;  // qt_set_option(QT_OPT_PAIRED_STAGES): let paired tables take their own stages (n <= 3)
   int paired_tables = 0;      // what qt_set_povm_product found: bit 0 = T is paired, bit 1 = pinv(T)^T is
@@ -786,14 +788,16 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
 // size.  n = 3: k_cptp_project64 (qt_process64.h), one workgroup each, with Dykstra's p, q, y, x and the clip's input in
 // h->proc_ws -- except in mode 1, which takes no workspace.  n = 2: k_cptp_wave16 (qt_process_wave16.h), one wavefront
 // each.  n = 1: k_cptp_project<4> (qt_process.h), one workgroup each.  `iters` and `status` may be null.
+// n = 2 only: `dist` (with `centre`) takes hs_dst(projected matrix, centre) from the same launch, and `out` may then be null.
 int project(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
-            int32_t* status) {
+            int32_t* status, const double* centre = nullptr, double* dist = nullptr) {
   if (h->D == 64) {
     if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
     return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, in, B, mode, n_iter, tol, out,
                   iters, status, h->proc_ws.as<double>());
   }
-  if (h->D == 16) return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status);
+  if (h->D == 16)
+    return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status, centre, dist);
   return launch(h, qt::k_cptp_project<4>, dim3(B), dim3(qt::ProcWG<4>::NT), 0, in, B, mode, n_iter, tol, out, iters, status);
 }
 
@@ -912,6 +916,187 @@ constexpr long long kPolyMaxUnits = 1LL << 32, kPolyMaxCounts = 1LL << 44;
 
 }  // namespace
 
+// ---- a11: the Choi linear inversion behind qt_lifp_batch and qt_lifp_dist_batch -----------------------------------
+namespace {
+
+// How qt_lifp_batch / qt_lifp_dist_batch reconstruct: chosen once per call from the WHOLE batch, so that the slices of
+// a call all take the path (and give the bits) of the unsliced one.
+enum LifpPath { kLifp64, kKronGemm, kLifp16, kDenseGemm, kFused };
+
+int lifp_path(qt_handle_t* h, int B, LifpPath* path) {
+  const ProcessState& ps = h->proc;
+  const int D = h->D, M = h->M;
+  const int R = D * M, Rp = ps.factored ? R : (R + 63) / 64 * 64;
+  const size_t gemm_lds = ((size_t)Rp * 16 + 4 * 256) * sizeof(double);
+  if (ps.factored) {  // n = 3: X = V_S^+ F V_P^+^T, two small products per process (qt_process64.h)
+    if ((size_t)B * D > (size_t)1 << 26) return fail(QT_ERR_ARG, "batch too large");
+    *path = ps.perm ? kLifp64 : kKronGemm;
+  } else {
+    if ((size_t)D * M * sizeof(double) > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
+    if (D == 16 && ps.perm && !h->proc_dense) *path = kLifp16;
+    else if (D == 16 && B >= 256 && gemm_lds <= 152 * 1024) *path = kDenseGemm;
+    else *path = kFused;  // k_lifp_batch: the one kernel that projects by itself
+  }
+  return 0;
+}
+
+// The writers that form hs_dst(Choi, centre) on the matrix they hold (k_cptp_wave16: n = 2 where a projection launch
+// follows the inversion; k_lifp16: n = 2 without the projection; k_lifp_batch<4>: n = 1); every other one -- all of
+// n = 3, k_lifp_gemm without the projection, k_lifp_batch<16> -- stores the matrices and k_hs_dist reads them.
+bool lifp_dist_in_kernel(const qt_handle_t* h, LifpPath path, int cptp) {
+  return h->D == 4 || (h->D == 16 && (path == kLifp16 || (cptp && path != kFused)));
+}
+
+// Linear inversion (+ projection) of B processes on device arrays along `path`; `dist` non-null (only where
+// lifp_dist_in_kernel): the distances to `centre` from the same launches, and `dchoi` may then be null.
+int lifp_launch(qt_handle_t* h, LifpPath path, const int64_t* dc, int B, int cptp, const double* centre, double* dchoi,
+                double* dist, int32_t* dit, int32_t* dst) {
+  const int D = h->D, M = h->M;
+  const ProcessState& ps = h->proc;
+  // R doubles of frequencies per process, Rp with the pitch k_lifp_freq pads to (at n = 3 R is a multiple of 64 already
+  // and the factored GEMM reads the rows unpadded).
+  const int R = D * M, Rp = ps.factored ? R : (R + 63) / 64 * 64;
+  const size_t dyn = (size_t)D * M * sizeof(double);
+  const size_t gemm_lds = ((size_t)Rp * 16 + 4 * 256) * sizeof(double);
+  const size_t gemm_lds2 = ((size_t)Rp * 32 + 4 * 512) * sizeof(double);  // two column tiles per workgroup
+  // The linear inversion into `raw`: the caller's array, or -- when a projection follows -- a workspace; the projection
+  // then reports iters, status and the distance, and the inversion gets none of them.
+  const bool then_project = cptp && path != kFused;
+  double *raw = dchoi, *rdist = dist;
+  int32_t *rst = dst, *rit = dit;
+  if (then_project) {
+    HIPCHK(h->ws_f.ensure((size_t)B * D * D * 2 * sizeof(double)));
+    raw = h->ws_f.as<double>();
+    rst = rit = nullptr;
+    rdist = nullptr;
+  }
+  double* F = nullptr;  // [B][Rp] frequencies (+ the zeros k_lifp_freq appends) of the two GEMM paths
+  if (path == kKronGemm || path == kDenseGemm) {
+    HIPCHK(h->ws_x.ensure(((size_t)B * Rp + 192) * sizeof(double)));
+    F = h->ws_x.as<double>();
+    if (int r = launch(h, qt::k_lifp_freq, dim3((B * D + 15) / 16), dim3(256), 0, dc, B * D, M, D, Rp, F)) return r;
+  }
+  switch (path) {
+    case kLifp64:  // M % 4 == 0: both products of a process in one kernel on the matrix cores
+      if (int r = launch(h, qt::k_lifp64, dim3(4 * B), dim3(256), 0, dc, B, M, ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(),
+                         raw, rst, rit))
+        return r;
+      break;
+    case kKronGemm: {
+      HIPCHK(h->ws_g.ensure((size_t)B * D * D * 2 * sizeof(double)));
+      double* T = h->ws_g.as<double>();
+      // T[(b, s)][beta] = sum_m F[(b, s)][m] V_P^+[beta][m]: real x complex = a real GEMM with 2 D interleaved columns
+      for (int b0 = 0; b0 < B; b0 += 8192) {  // (grid.y <= 65535 row tiles)
+        const int nb = B - b0 < 8192 ? B - b0 : 8192;
+        if (int r = launch(h, qt::k_gemm<0>, dim3(2 * D / 16, (nb * D + 15) / 16), dim3(64), 0, nb * D, 2 * D, M, F + (size_t)b0 * R,
+                           M, 0, ps.vp_pinvT.as<double>(), 2 * D, 0, T + (size_t)b0 * D * D * 2, 2 * D))
+          return r;
+      }
+      if (int r = launch(h, qt::k_lifp_kron_finish, dim3(B), dim3(256), 0, T, ps.vs_pinv.as<double>(), B, raw, rst, rit)) return r;
+      break;
+    }
+    case kLifp16: {  // n = 2 through the Kronecker factors of the left inverse: one wavefront per process (qt_process.h).
+      // At most 768 workgroups, three resident per CU (166 VGPRs): the wavefronts stride over the batch with the next
+      // process's counts in flight, and a workgroup stages V_P^+ once for all its processes.  The distance takes a
+      // 16 x 17 complex transpose scratch per wavefront behind V_P^+
+      const size_t lds = (size_t)M * 32 * sizeof(double) + (rdist ? 4 * 16 * 17 * 2 * sizeof(double) : 0);
+      if (int r = launch(h, M == 36 ? qt::k_lifp16<9> : qt::k_lifp16<0>, dim3(std::min((B + 3) / 4, 768)), dim3(256), lds, dc, B, M,
+                         ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(), raw, rst, rit, centre, rdist))
+        return r;
+      break;
+    }
+    case kDenseGemm: {  // many processes: frequencies, then one FP64 MFMA GEMM over the batch
+      constexpr int NE = 256;
+      // 4 groups of 16 processes per workgroup pass (x 2 halves of K).  A workgroup keeps its operand slice for up
+      // to 4 passes once there are enough blocks to fill the chip anyway (measured: B = 1024 best with 1-2 passes,
+      // 26 M/s; B = 8192 with 4, 38 M/s against 35 M/s with 1)
+      const int nblocks = (B + 63) / 64;
+      const int passes = nblocks >= 64 ? 4 : (nblocks >= 32 ? 2 : 1);
+      const int row_blocks = (nblocks + passes - 1) / passes;
+      const bool two = gemm_lds2 <= kLdsLimit;  // two column tiles per workgroup: half the re-reads of F (R <= 576)
+      auto kern = two ? qt::k_lifp_gemm<16, 2> : qt::k_lifp_gemm<16, 1>;
+#ifdef QT_PHASE_TIMING
+      switch (two ? g_host_diag : 0) {  // profile build: a compile-time variant of the two-tile kernel (qt_debug_set_diag)
+        case 0: break;
+        case 1: kern = qt::k_lifp_gemm<16, 2, 1>; break;
+        case 2: kern = qt::k_lifp_gemm<16, 2, 2>; break;
+        case 3: kern = qt::k_lifp_gemm<16, 2, 3>; break;
+        case 4: kern = qt::k_lifp_gemm<16, 2, 4>; break;
+        case 7: kern = qt::k_lifp_gemm<16, 2, 7>; break;
+        case 8: kern = qt::k_lifp_gemm<16, 2, 8>; break;
+        case 15: kern = qt::k_lifp_gemm<16, 2, 15>; break;
+        default: return fail(QT_ERR_ARG, "no such diagnostic variant");
+      }
+#endif
+      if (int r = launch(h, kern, dim3(2 * NE / (two ? 32 : 16), row_blocks), dim3(512), two ? gemm_lds2 : gemm_lds, F, B, R, Rp,
+                         ps.pinvR.as<double>(), raw, rst, rit))
+        return r;
+      break;
+    }
+    case kFused:
+      if (int r = launch(h, D == 4 ? qt::k_lifp_batch<4> : qt::k_lifp_batch<16>, dim3(B),
+                         dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, B, M, ps.pinvT.as<double>(), cptp, dchoi,
+                         dit, dst, centre, dist))
+        return r;
+      break;
+  }
+  // The projection, where the path left it to do.
+  if (then_project)
+    if (int r = project(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst, centre, dist)) return r;
+  return 0;
+}
+
+// Both entry points.  `with_dist` false: qt_lifp_batch.  Otherwise the batch runs in slices (QT_OPT_LIFP_DIST_SLICE) that bound
+// every workspace whose size follows the batch: the raw inversion a projection reads, and -- where k_hs_dist forms the
+// distance and the caller wants no matrices -- the matrices themselves.
+int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B, int cptp, const double* centre, double* choi,
+                    double* dist, int32_t* iters, int32_t* status, int flags, const char* fn) {
+  QT_ENTER(h);
+  Call c(h, flags, fn);
+  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+  if (B < 0 || (B > 0 && (!counts || (with_dist ? !centre || !dist : !choi)))) return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
+  if (B == 0) return 0;
+  if (!with_dist) dist = nullptr;
+  const int D = h->D, M = h->M;
+  const size_t ne2 = (size_t)D * D * 2;
+  const int64_t* dc;
+  const double* dcen;
+  double *dchoi, *ddist;
+  int32_t *dit, *dst;
+  if (int r = c.in(counts, (size_t)B * D * M, &dc)) return r;
+  if (int r = c.in(centre, dist ? ne2 : 0, &dcen)) return r;
+  if (int r = c.out(choi, (size_t)B * ne2, &dchoi)) return r;
+  if (int r = c.out(dist, (size_t)B, &ddist)) return r;
+  if (int r = c.out(iters, (size_t)B, &dit)) return r;
+  if (int r = c.out(status, (size_t)B, &dst)) return r;
+  LifpPath path;
+  if (int r = lifp_path(h, B, &path)) return r;
+  if (!dist) {
+    if (int r = lifp_launch(h, path, dc, B, cptp, nullptr, dchoi, nullptr, dit, dst)) return r;
+    return c.done(status, B);
+  }
+  constexpr size_t kSliceBytes = (size_t)128 << 20;  // of Choi matrices: 2048 processes at n = 3, 32 768 at n = 2
+  const int cap = (int)(kSliceBytes / (ne2 * sizeof(double)));
+  const int slice = h->lifp_dist_slice > 0 && h->lifp_dist_slice < cap ? h->lifp_dist_slice : cap;
+  const bool in_kernel = lifp_dist_in_kernel(h, path, cptp);
+  for (int b0 = 0; b0 < B; b0 += slice) {
+    const int nb = B - b0 < slice ? B - b0 : slice;
+    double* m = dchoi ? dchoi + (size_t)b0 * ne2 : nullptr;
+    if (!in_kernel && !m) {
+      HIPCHK(h->lifp_dist_ws.ensure((size_t)nb * ne2 * sizeof(double)));
+      m = h->lifp_dist_ws.as<double>();
+    }
+    if (int r = lifp_launch(h, path, dc + (size_t)b0 * D * M, nb, cptp, dcen, m, in_kernel ? ddist + b0 : nullptr,
+                            dit ? dit + b0 : nullptr, dst ? dst + b0 : nullptr))
+      return r;
+    if (!in_kernel)
+      if (int r = launch(h, qt::k_hs_dist, dim3(nb), dim3(64), 0, D, (const double*)m, dcen, nb, ddist + b0)) return r;
+  }
+  return c.done(status, B);
+}
+
+}  // namespace
+
 extern "C" {
 
 int qt_version(void) { return 100; }
@@ -968,7 +1153,7 @@ void qt_destroy(qt_handle_t* h) {
   (void)hipStreamSynchronize(h->stream);
   for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_last})
     b->release();
-  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws,
+  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws,
                     &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
@@ -1010,6 +1195,10 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
       return 0;
     case QT_OPT_PAIRED_STAGES: h->paired_stages = value != 0.0; return 0;
     case QT_OPT_MLE_SPECIALISE: h->mle_specialise = value != 0.0; return 0;
+    case QT_OPT_LIFP_DIST_SLICE:
+      if (!(value >= 0.0 && value <= 16777216.0)) return fail(QT_ERR_ARG, "QT_OPT_LIFP_DIST_SLICE out of range");
+      h->lifp_dist_slice = (int)value;
+      return 0;
     default: return fail(QT_ERR_ARG, "unknown option %d", option);
   }
 }
@@ -2058,117 +2247,12 @@ int qt_process_get_factors(qt_handle_t* h, double* vs_pinv, double* vp_pinv, int
 
 int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double* choi, int32_t* iters, int32_t* status,
                   int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
-  if (B < 0 || (B > 0 && (!counts || !choi))) return fail(QT_ERR_ARG, "bad lifp_batch arguments");
-  if (B == 0) return 0;
-  const int D = h->D, M = h->M;
-  const ProcessState& ps = h->proc;
-  const int64_t* dc;
-  double* dchoi;
-  int32_t *dit, *dst;
-  if (int r = c.in(counts, (size_t)B * D * M, &dc)) return r;
-  if (int r = c.out(choi, (size_t)B * D * D * 2, &dchoi)) return r;
-  if (int r = c.out(iters, (size_t)B, &dit)) return r;
-  if (int r = c.out(status, (size_t)B, &dst)) return r;
-  // 1. The path.  R doubles of frequencies per process, Rp with the pitch k_lifp_freq pads to (at n = 3 R is a multiple
-  // of 64 already and the factored GEMM reads the rows unpadded).
-  const int R = D * M, Rp = ps.factored ? R : (R + 63) / 64 * 64;
-  const size_t dyn = (size_t)D * M * sizeof(double);
-  const size_t gemm_lds = ((size_t)Rp * 16 + 4 * 256) * sizeof(double);
-  const size_t gemm_lds2 = ((size_t)Rp * 32 + 4 * 512) * sizeof(double);  // two column tiles per workgroup
-  enum { kLifp64, kKronGemm, kLifp16, kDenseGemm, kFused } path;
-  if (ps.factored) {  // n = 3: X = V_S^+ F V_P^+^T, two small products per process (qt_process64.h)
-    if ((size_t)B * D > (size_t)1 << 26) return fail(QT_ERR_ARG, "batch too large");
-    path = ps.perm ? kLifp64 : kKronGemm;
-  } else {
-    if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-    if (D == 16 && ps.perm && !h->proc_dense) path = kLifp16;
-    else if (D == 16 && B >= 256 && gemm_lds <= 152 * 1024) path = kDenseGemm;
-    else path = kFused;  // k_lifp_batch: the one kernel that projects by itself
-  }
-  // 2. The linear inversion into `raw`: the caller's array, or -- when a projection follows -- a workspace; the projection
-  // then reports iters and status, and the inversion gets neither.
-  const bool then_project = cptp && path != kFused;
-  double* raw = dchoi;
-  int32_t *rst = dst, *rit = dit;
-  if (then_project) {
-    HIPCHK(h->ws_f.ensure((size_t)B * D * D * 2 * sizeof(double)));
-    raw = h->ws_f.as<double>();
-    rst = rit = nullptr;
-  }
-  double* F = nullptr;  // [B][Rp] frequencies (+ the zeros k_lifp_freq appends) of the two GEMM paths
-  if (path == kKronGemm || path == kDenseGemm) {
-    HIPCHK(h->ws_x.ensure(((size_t)B * Rp + 192) * sizeof(double)));
-    F = h->ws_x.as<double>();
-    if (int r = launch(h, qt::k_lifp_freq, dim3((B * D + 15) / 16), dim3(256), 0, dc, B * D, M, D, Rp, F)) return r;
-  }
-  switch (path) {
-    case kLifp64:  // M % 4 == 0: both products of a process in one kernel on the matrix cores
-      if (int r = launch(h, qt::k_lifp64, dim3(4 * B), dim3(256), 0, dc, B, M, ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(),
-                         raw, rst, rit))
-        return r;
-      break;
-    case kKronGemm: {
-      HIPCHK(h->ws_g.ensure((size_t)B * D * D * 2 * sizeof(double)));
-      double* T = h->ws_g.as<double>();
-      // T[(b, s)][beta] = sum_m F[(b, s)][m] V_P^+[beta][m]: real x complex = a real GEMM with 2 D interleaved columns
-      for (int b0 = 0; b0 < B; b0 += 8192) {  // (grid.y <= 65535 row tiles)
-        const int nb = B - b0 < 8192 ? B - b0 : 8192;
-        if (int r = launch(h, qt::k_gemm<0>, dim3(2 * D / 16, (nb * D + 15) / 16), dim3(64), 0, nb * D, 2 * D, M, F + (size_t)b0 * R,
-                           M, 0, ps.vp_pinvT.as<double>(), 2 * D, 0, T + (size_t)b0 * D * D * 2, 2 * D))
-          return r;
-      }
-      if (int r = launch(h, qt::k_lifp_kron_finish, dim3(B), dim3(256), 0, T, ps.vs_pinv.as<double>(), B, raw, rst, rit)) return r;
-      break;
-    }
-    case kLifp16:  // n = 2 through the Kronecker factors of the left inverse: one wavefront per process (qt_process.h).
-      // At most 768 workgroups, three resident per CU (166 VGPRs): the wavefronts stride over the batch with the next
-      // process's counts in flight, and a workgroup stages V_P^+ once for all its processes
-      if (int r = launch(h, M == 36 ? qt::k_lifp16<9> : qt::k_lifp16<0>, dim3(std::min((B + 3) / 4, 768)), dim3(256),
-                         (size_t)M * 32 * sizeof(double), dc, B, M, ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(), raw, rst, rit))
-        return r;
-      break;
-    case kDenseGemm: {  // many processes: frequencies, then one FP64 MFMA GEMM over the batch
-      constexpr int NE = 256;
-      // 4 groups of 16 processes per workgroup pass (x 2 halves of K).  A workgroup keeps its operand slice for up
-      // to 4 passes once there are enough blocks to fill the chip anyway (measured: B = 1024 best with 1-2 passes,
-      // 26 M/s; B = 8192 with 4, 38 M/s against 35 M/s with 1)
-      const int nblocks = (B + 63) / 64;
-      const int passes = nblocks >= 64 ? 4 : (nblocks >= 32 ? 2 : 1);
-      const int row_blocks = (nblocks + passes - 1) / passes;
-      const bool two = gemm_lds2 <= kLdsLimit;  // two column tiles per workgroup: half the re-reads of F (R <= 576)
-      auto kern = two ? qt::k_lifp_gemm<16, 2> : qt::k_lifp_gemm<16, 1>;
-#ifdef QT_PHASE_TIMING
-      switch (two ? g_host_diag : 0) {  // profile build: a compile-time variant of the two-tile kernel (qt_debug_set_diag)
-        case 0: break;
-        case 1: kern = qt::k_lifp_gemm<16, 2, 1>; break;
-        case 2: kern = qt::k_lifp_gemm<16, 2, 2>; break;
-        case 3: kern = qt::k_lifp_gemm<16, 2, 3>; break;
-        case 4: kern = qt::k_lifp_gemm<16, 2, 4>; break;
-        case 7: kern = qt::k_lifp_gemm<16, 2, 7>; break;
-        case 8: kern = qt::k_lifp_gemm<16, 2, 8>; break;
-        case 15: kern = qt::k_lifp_gemm<16, 2, 15>; break;
-        default: return fail(QT_ERR_ARG, "no such diagnostic variant");
-      }
-#endif
-      if (int r = launch(h, kern, dim3(2 * NE / (two ? 32 : 16), row_blocks), dim3(512), two ? gemm_lds2 : gemm_lds, F, B, R, Rp,
-                         ps.pinvR.as<double>(), raw, rst, rit))
-        return r;
-      break;
-    }
-    case kFused:
-      if (int r = launch(h, D == 4 ? qt::k_lifp_batch<4> : qt::k_lifp_batch<16>, dim3(B),
-                         dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, B, M, ps.pinvT.as<double>(), cptp, dchoi,
-                         dit, dst))
-        return r;
-      break;
-  }
-  // 3. The projection, where the path left it to do.
-  if (then_project)
-    if (int r = project(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst)) return r;
-  return c.done(status, B);
+  return lifp_batch_impl(h, false, counts, B, cptp, nullptr, choi, nullptr, iters, status, flags, __func__);
+}
+
+int qt_lifp_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, const double* centre, double* choi,
+                       double* dist, int32_t* iters, int32_t* status, int flags) {
+  return lifp_batch_impl(h, true, counts, B, cptp, centre, choi, dist, iters, status, flags, __func__);
 }
 
 int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, double tol, int stop_rule, double* choi,

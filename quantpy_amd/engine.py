@@ -182,7 +182,8 @@ class Engine:
         two-loop BFGS path), _capi.QT_OPT_PAIRED_STAGES (0 = the dense-table contraction stages for every one-qubit
         table, 1 = the zero-skipping stages where `paired_tables` says so; the same bits either way),
         _capi.QT_OPT_MLE_SPECIALISE (0 = the generic MLE kernels for every POVM, 1 = the instantiation compiled for the
-        six-projector shape where the POVM has it, see `mle_specialised`; the same bits either way)."""
+        six-projector shape where the POVM has it, see `mle_specialised`; the same bits either way),
+        _capi.QT_OPT_LIFP_DIST_SLICE (processes per slice of `lifp_dist`; 0 = the library's 128 MB bound)."""
         self._chk(self.lib.qt_set_option(self._h, int(option), float(value)))
 
     @property
@@ -389,6 +390,27 @@ class Engine:
         self._dev_call()
         self._chk(self.lib.qt_lifp_batch(self._h, _ptr(counts), counts.shape[0], int(bool(cptp)), _ptr(choi), _ptr(iters),
                                          _ptr(status), _capi.QT_DEVICE_PTR))
+
+    def lifp_dist(self, counts, centre, cptp=True, return_info=False):
+        """hs_dst(lifp(counts_b), centre) for every process in ONE pass (qt_lifp_dist_batch: the Choi matrices are not
+        written).  counts (B, D, S, K), centre (D, D) -> (B,) float64; return_info appends dict(iters, status)."""
+        c = _i64(counts).reshape(-1, self.D, self.S, self.K)
+        b = c.shape[0]
+        cen = _c128(centre)
+        assert cen.shape == (self.D, self.D)
+        dist = np.empty(b)
+        iters = np.zeros(b, dtype=np.int32)
+        status = np.zeros(b, dtype=np.int32)
+        self._chk(self.lib.qt_lifp_dist_batch(self._h, _ptr(c), b, int(bool(cptp)), _ptr(cen), None, _ptr(dist), _ptr(iters),
+                                              _ptr(status), _capi.QT_HOST_PTR))
+        return (dist, dict(iters=iters, status=status)) if return_info else dist
+
+    def lifp_dist_dev(self, counts, centre, dist, cptp=True, choi=None, iters=None, status=None):
+        """device-pointer form: counts int64 (B, D, S, K), centre complex128 (D, D), dist float64 (B,) torch CUDA
+        tensors; choi complex128 (B, D, D) optional (then what `lifp_dev` writes, bit for bit)"""
+        self._dev_call()
+        self._chk(self.lib.qt_lifp_dist_batch(self._h, _ptr(counts), counts.shape[0], int(bool(cptp)), _ptr(centre),
+                                              _ptr(choi), _ptr(dist), _ptr(iters), _ptr(status), _capi.QT_DEVICE_PTR))
 
     def cptp_project(self, choi, mode="cptp", n_iter=1000, tol=1e-12, return_iters=False):
         """mode 'cptp' (Dykstra) | 'tp' | 'cp' on Choi matrices (B, D, D) / (D, D)."""

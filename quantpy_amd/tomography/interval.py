@@ -170,7 +170,37 @@ class MomentInterval(ConfidenceInterval):
         return np.sqrt(distr.ppf(np.asarray(conf_levels, dtype=np.float64)[None, :])) * self._alpha(dim)
 
 
-class BootstrapStateInterval(ConfidenceInterval):
+class _ShardedBootstrap:
+    """What the one-pass bootstraps keep of their resamples: `boot_dist` and `boot_counts`, plain attributes on the
+    two-pass paths, fetched from where `_setup_fused` left them on first use otherwise."""
+
+    @property
+    def boot_dist(self):
+        """The distances in resample order, on the host (all-gathered on first use when the ranks hold shards)."""
+        if getattr(self, "_boot_dist", None) is None and getattr(self, "_dist_shard", None) is not None:
+            self._boot_dist = qdist.allgather_device(self._dist_shard, self.n_points).cpu().numpy()
+        return getattr(self, "_boot_dist", None)
+
+    @boot_dist.setter
+    def boot_dist(self, value):
+        self._boot_dist, self._dist_shard = value, None
+
+    @property
+    def boot_counts(self):
+        """Every resample's counts on the host.  sampler='device': this rank's shard only (rows lo .. hi of the table),
+        fetched when somebody reads it -- from the device tensor that holds it (states), or, where the shard was drawn
+        and consumed chunk by chunk (processes), drawn again from the same Philox streams."""
+        source = getattr(self, "_boot_counts_device", None)
+        if getattr(self, "_boot_counts_host", None) is None and source is not None:
+            self._boot_counts_host = source() if callable(source) else source.cpu().numpy()
+        return getattr(self, "_boot_counts_host", None)
+
+    @boot_counts.setter
+    def boot_counts(self, value):
+        self._boot_counts_host, self._boot_counts_device = value, None
+
+
+class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
     """Parametric bootstrap around `state` (default: the tomograph's reconstructed state) with the
     tomograph's own POVM and shots; distances tmg.dst(resampled estimate, state)."""
 
@@ -281,29 +311,6 @@ class BootstrapStateInterval(ConfidenceInterval):
         self._boot_dist = None
         self.sample = qdist.ShardedSample(dist, self.n_points, engine=eng)
         self.cl_to_dist = _SampleInterp(self.sample)
-
-    @property
-    def boot_dist(self):
-        """The distances in resample order, on the host (all-gathered on first use when the ranks hold shards)."""
-        if getattr(self, "_boot_dist", None) is None and getattr(self, "_dist_shard", None) is not None:
-            self._boot_dist = qdist.allgather_device(self._dist_shard, self.n_points).cpu().numpy()
-        return getattr(self, "_boot_dist", None)
-
-    @boot_dist.setter
-    def boot_dist(self, value):
-        self._boot_dist, self._dist_shard = value, None
-
-    @property
-    def boot_counts(self):
-        """Every resample's counts on the host.  sampler='device': this rank's shard only (rows lo .. hi of the table),
-        fetched when somebody reads it."""
-        if getattr(self, "_boot_counts_host", None) is None and getattr(self, "_boot_counts_device", None) is not None:
-            self._boot_counts_host = self._boot_counts_device.cpu().numpy()
-        return getattr(self, "_boot_counts_host", None)
-
-    @boot_counts.setter
-    def boot_counts(self, value):
-        self._boot_counts_host, self._boot_counts_device = value, None
 
 
 class _SampleInterp:
@@ -697,12 +704,20 @@ class MHMCProcessInterval(ConfidenceInterval):
         self.cl_to_dist = interp1d(conf_levels, dist)
 
 
-class BootstrapProcessInterval(ConfidenceInterval):
+class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
     """Parametric bootstrap of a process tomography around `channel` (default: the reconstructed
-    channel): resampled counts for every input state, batched Choi reconstruction."""
+    channel): resampled counts for every input state, batched Choi reconstruction.
+
+    method='lifp' with the Hilbert-Schmidt distance runs in one pass per rank (`_setup_fused`); with sampler='device'
+    the counts then never leave the GPU: `boot_counts` is this rank's shard, drawn again from the same streams when it
+    is read.  `chunk` (keyword-only) overrides how many resamples of the shard are drawn and reconstructed at a time
+    (default: 256 MB of counts); the draws and distances do not depend on it."""
+
+    _CHUNK_BYTES = 256 << 20
 
     def __init__(self, tmg, n_points=1000, method="lifp", cptp=True, tol=1e-10, channel=None,
-                 states_est_method="lin", states_physical=True, states_init="lin", sampler="numpy", seed=None):
+                 states_est_method="lin", states_physical=True, states_init="lin", sampler="numpy", seed=None, *,
+                 chunk=None):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
 
     def setup(self):
@@ -717,6 +732,9 @@ class BootstrapProcessInterval(ConfidenceInterval):
                                                   states_init=self.states_init, cptp=self.cptp)
         boot = tmg.__class__(self.channel, tmg.input_states, tmg.dst)
         shots, povm = tmg.tomographs[0].n_measurements, tmg.tomographs[0].povm_matrix
+        if self.n_points and tmg.dst is hs_dst and self.method == "lifp":
+            self._setup_fused(boot, shots, povm)
+            return
         counts = qdist.broadcast_array(boot.experiment_batch(shots, povm=povm, repeats=self.n_points,
                                                              sampler=self.sampler, seed=self.seed))
         self.boot_counts = counts
@@ -735,3 +753,83 @@ class BootstrapProcessInterval(ConfidenceInterval):
 
         self.boot_dist = qdist.sharded_map(counts, reconstruct)
         self._finish(self.boot_dist)
+
+    def _setup_fused(self, boot, shots, povm):
+        """The loop of interval.py:673-682 for 'lifp' and the Hilbert-Schmidt distance as this rank's shard of it, the way
+        BootstrapStateInterval._setup_fused runs the state loop: the shard's counts go to (sampler='numpy': drawn on
+        np.random's stream on rank 0, broadcast) or are drawn in (sampler='device': row (resample * 4^n + input) * S +
+        setting of the table keyed by that global index, `ProcessTomograph.experiment_batch`'s keying, so each rank
+        draws only its own rows) HBM, qt_lifp_dist_batch reconstructs them and writes the distance to `channel` -- 8
+        bytes per resample leave the kernels, no Choi matrices -- and the sorted shard stays where it is behind a
+        `ShardedSample`.  The device sampler's shard is drawn and consumed `chunk` resamples at a time in one count
+        buffer; rows being keyed globally, the chunking changes no draw.  As in the reference's loop, `cptp` is passed
+        on and `tol` is not."""
+        import torch
+
+        from ..sampling import resolve_seed
+
+        rank, world = qdist.world()
+        lo, hi = qdist.shard_bounds(self.n_points)
+        if self.sampler == "numpy":
+            if self.seed is not None:  # (every rank: what draw_counts tells rank 0)
+                raise ValueError("sampler='numpy' draws from np.random's global stream: seed it with np.random.seed")
+            if rank == 0:
+                host = boot.experiment_batch(shots, povm=povm, repeats=self.n_points)
+            else:
+                povm_matrix, shots_set, probas = boot._experiment_tables(shots, povm)
+                host = np.empty((self.n_points, len(boot.tomographs), povm_matrix.shape[0], probas.shape[1]), dtype=np.int64)
+            host = qdist.broadcast_array(host)
+            self.boot_counts = host
+            n_in, n_set, n_out = host.shape[1:]
+        elif self.sampler == "device":
+            povm_matrix, shots_set, probas = boot._experiment_tables(shots, povm)
+            n_in = len(boot.tomographs)
+            n_set, n_out = probas.shape[0] // n_in, probas.shape[1]
+            if not (np.all(probas >= 0) and np.all(probas[:, :-1].sum(1) <= 1.0 + 1e-12)):
+                raise ValueError("sum(pvals[:-1]) > 1.0")
+            seed = resolve_seed(self.seed)
+            if world > 1:  # one Philox key for the whole table: rank 0's
+                seed = int(qdist.broadcast_array(np.array([seed], dtype=np.uint64).view(np.int64)).view(np.uint64)[0])
+            shots_rows = np.tile(np.asarray(shots_set).astype(np.int64), n_in)
+        else:
+            raise ValueError(f"sampler must be 'numpy' or 'device', not {self.sampler!r}")
+        if not hasattr(boot.tomographs[0], "povm_matrix"):  # (no experiment_batch on this rank) what the engine's set-up reads
+            for t in boot.tomographs:
+                t.povm_matrix, t.n_measurements = povm_matrix, np.asarray(shots_set)
+        eng = boot._engine()
+        dev = torch.device("cuda", eng.device)
+        rows = n_in * n_set  # table rows per resample
+        dist = torch.empty(hi - lo, dtype=torch.float64, device=dev)
+        status = torch.zeros(hi - lo, dtype=torch.int32, device=dev)
+        centre = torch.from_numpy(np.ascontiguousarray(self.channel.choi.matrix, dtype=np.complex128)).to(dev)
+        if self.sampler == "numpy":
+            if hi > lo:
+                counts = torch.from_numpy(np.ascontiguousarray(host[lo:hi])).to(dev)
+                eng.lifp_dist_dev(counts, centre, dist, cptp=self.cptp, status=status)
+        else:
+            chunk = int(self.chunk) if self.chunk else max(1, self._CHUNK_BYTES // (rows * n_out * 8))
+            chunk = max(1, min(chunk, hi - lo))
+            n_d, p_d = torch.from_numpy(shots_rows).to(dev), torch.from_numpy(np.ascontiguousarray(probas)).to(dev)
+            buf = torch.empty((chunk, n_in, n_set, n_out), dtype=torch.int64, device=dev)
+            for c0 in range(lo, hi, chunk):  # one stream: a chunk's draw waits for the reconstruction before it
+                counts = buf[: min(chunk, hi - c0)]
+                eng.device_multinomial(n_d, p_d, counts.shape[0] * rows, seed, first_row=c0 * rows, out=counts)
+                eng.lifp_dist_dev(counts, centre, dist[c0 - lo: c0 - lo + counts.shape[0]], cptp=self.cptp,
+                                  status=status[c0 - lo: c0 - lo + counts.shape[0]])
+            self._boot_counts_host = None
+            self._boot_counts_device = lambda: (
+                eng.device_multinomial(shots_rows, probas, (hi - lo) * rows, seed, first_row=lo * rows) if hi > lo else
+                np.empty((0, n_out), dtype=np.int64)).reshape(hi - lo, n_in, n_set, n_out)
+        eng.sync()
+        bad = np.array([int(torch.any(status != 0).item())])
+        if world > 1:  # every rank raises, or none
+            bad = qdist.allgather_equal(bad).max(axis=0)
+        if bad[0]:
+            raise ValueError("a resampled process has no finite Choi matrix (an input state without counts)")
+        if self.sampler == "device" and world == 1:  # the tomographs are left as the last experiment() would leave them
+            for t, last in zip(boot.tomographs, counts[-1].cpu().numpy()):
+                t.results = last
+        self._dist_shard = dist.clone()  # resample order (boot_dist); the sample below is sorted in place
+        self._boot_dist = None
+        self.sample = qdist.ShardedSample(dist, self.n_points, engine=eng)
+        self.cl_to_dist = _SampleInterp(self.sample)

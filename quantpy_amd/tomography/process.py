@@ -67,16 +67,21 @@ class ProcessTomograph:
         """Counts (repeats, n_inputs, S, K) of `repeats` successive `experiment(n_measurements, povm)` calls, drawn in
         one call in the same order on the same global stream (resample, input state, setting: the loop of reference
         interval.py:673-676).  Leaves the tomographs as the last of those calls would."""
-        self.tomographs = [StateTomograph(self.channel.transform(state)) for state in self.input_basis.elements]
-        first = self.tomographs[0]
-        povm_matrix, shots = first._experiment_arguments(n_measurements, povm)
-        probas = np.concatenate([born_probabilities(povm_matrix, tmg.state.bloch) for tmg in self.tomographs])
+        povm_matrix, shots, probas = self._experiment_tables(n_measurements, povm)
         n_in, n_set = len(self.tomographs), povm_matrix.shape[0]
         counts = draw_counts(np.tile(shots, n_in), probas, repeats, sampler, seed).reshape(repeats, n_in, n_set, -1)
         if repeats:
             for tmg, last in zip(self.tomographs, counts[-1]):
                 tmg.povm_matrix, tmg.results, tmg.n_measurements = povm_matrix, last, np.asarray(shots)
         return counts
+
+    def _experiment_tables(self, n_measurements, povm):
+        """Fresh output tomographs, and what the sampler draws for them:
+        (povm_matrix, shots (S,), probas (n_inputs * S, K)) -- row input * S + setting of one resample's table."""
+        self.tomographs = [StateTomograph(self.channel.transform(state)) for state in self.input_basis.elements]
+        povm_matrix, shots = self.tomographs[0]._experiment_arguments(n_measurements, povm)
+        probas = np.concatenate([born_probabilities(povm_matrix, tmg.state.bloch) for tmg in self.tomographs])
+        return povm_matrix, shots, probas
 
     @property
     def results(self):
