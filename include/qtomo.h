@@ -87,13 +87,17 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
  * setting, QT_OPT_SHOTS_CHECK on); 0 forces the generic instantiation.  Both give the same bits.
  * QT_OPT_LIFP_DIST_SLICE (default 0): qt_lifp_dist_batch runs its batch in slices of this many processes, so that the
  * workspaces that follow the batch stay bounded; 0, or more than 128 MB of Choi matrices (2048 processes at n = 3,
- * 32 768 at n = 2), takes that bound.  The same bits whatever the slice. */
+ * 32 768 at n = 2), takes that bound.  The same bits whatever the slice.
+ * QT_OPT_MLE_HELPER_WAVE (default 1): at n = 3 the one-launch MLE from the 'lin' start (product POVM, batches within
+ * QT_OPT_MLE_FUSED_MAX_WAVES) gives every trial a helper wavefront, which factorises a clipped trial's projected
+ * matrix beside its first evaluation; 0 launches the kernel without helpers.  Both give the same bits. */
 enum qt_option {
   QT_OPT_SHOTS_CHECK = 1,
   QT_OPT_MLE_FUSED_MAX_WAVES = 2,
   QT_OPT_PAIRED_STAGES = 3,
   QT_OPT_MLE_SPECIALISE = 4,
-  QT_OPT_LIFP_DIST_SLICE = 5
+  QT_OPT_LIFP_DIST_SLICE = 5,
+  QT_OPT_MLE_HELPER_WAVE = 6
 };
 int qt_set_option(qt_handle_t* h, int option, double value);
 /* Which one-qubit tables of the current product POVM have that shape: bit 0 = T, bit 1 = pinv(T) as computed on the
@@ -101,6 +105,8 @@ int qt_set_option(qt_handle_t* h, int option, double value);
 int qt_get_paired_tables(qt_handle_t* h);
 /* 1 if the last qt_mle_batch / qt_mle_dist_batch launch took the specialised instantiation, else 0. */
 int qt_get_mle_specialised(qt_handle_t* h);
+/* 1 if the last qt_mle_batch / qt_mle_dist_batch launch was the kernel with helper wavefronts, else 0. */
+int qt_get_mle_helper_wave(qt_handle_t* h);
 /* hipEvent timers on the handle's stream: begin, ..., end -> elapsed milliseconds */
 int qt_timer_begin(qt_handle_t* h);
 int qt_timer_end(qt_handle_t* h, double* elapsed_ms);

@@ -14,6 +14,7 @@ QT_INIT_MIXED = 1
 QT_STREAM_LEGACY = 1  # qt_set_stream: the legacy default ("null") stream
 QT_OPT_SHOTS_CHECK, QT_OPT_MLE_FUSED_MAX_WAVES, QT_OPT_PAIRED_STAGES, QT_OPT_MLE_SPECIALISE = 1, 2, 3, 4  # qt_set_option
 QT_OPT_LIFP_DIST_SLICE = 5  # processes per slice of qt_lifp_dist_batch (0: the library's byte bound)
+QT_OPT_MLE_HELPER_WAVE = 6  # n = 3 one-launch MLE, 'lin' start: a helper wavefront per trial (0: the kernel without)
 
 # status codes (include/qtomo.h)
 QT_ERR_ARG, QT_ERR_STATE, QT_ERR_HIP, QT_ERR_SINGULAR, QT_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
@@ -36,6 +37,7 @@ SIGNATURES = {
     "qt_set_option": (_c_int, [_vp, _c_int, _c_dbl]),
     "qt_get_paired_tables": (_c_int, [_vp]),
     "qt_get_mle_specialised": (_c_int, [_vp]),
+    "qt_get_mle_helper_wave": (_c_int, [_vp]),
     "qt_timer_begin": (_c_int, [_vp]),
     "qt_timer_end": (_c_int, [_vp, ctypes.POINTER(_c_dbl)]),
     "qt_timer_stop": (_c_int, [_vp]),

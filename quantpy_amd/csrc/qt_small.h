@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "qt_linesearch.h"
 
 namespace qt {
@@ -438,6 +440,7 @@ struct Small {
     __device__ __forceinline__ double* extra() const { return sm + trial_doubles(M, pv.pr.enabled ? pv.pr.R1 : 0); }  // [pv.extra]
     // the launch-uniform facts, read at run time here and compile-time constants in CtxS
     static constexpr bool kGeneric = true;
+    static constexpr bool kHelper = false;  // (WithHelper)
     __device__ __forceinline__ int R1() const { return pv.pr.R1; }
     __device__ __forceinline__ bool uniform() const { return pv.pr.uniform != 0; }
     __device__ __forceinline__ bool pairedT() const { return pv.pr.pairedT != 0; }
@@ -479,6 +482,7 @@ struct Small {
     __device__ __forceinline__ const double* tabP() const { return ptab; }
     __device__ __forceinline__ double* extra() const { return sm + trial_doubles(M, 6); }  // [a.extra]
     static constexpr bool kGeneric = false;
+    static constexpr bool kHelper = false;
     __device__ __forceinline__ static constexpr bool prod() { return true; }
     __device__ __forceinline__ static constexpr int R1() { return 6; }
     __device__ __forceinline__ static constexpr bool uniform() { return true; }
@@ -868,16 +872,7 @@ struct Small {
     c.xm = xm;
     c.zm = zm;
     c.ny = ny & 3;
-    // parameter l: diagonal (l, l), then the T real and the T imaginary parts in the order of np.tril_indices(d, -1);
-    // row ii of entry t is the number of triangular numbers k (k - 1) / 2 <= t, k = 1 .. d - 1
-    const bool diag = c.l < d, imag = c.l >= d + T;
-    const int t = c.l - d - (imag ? T : 0);
-    int ii = 1;
-#pragma unroll
-    for (int k = 2; k < d; ++k) ii += t >= (k * (k - 1)) / 2;
-    c.pkind = diag ? 0 : imag ? 2 : 1;
-    c.pi = diag ? c.l : ii;
-    c.pj = diag ? c.l : t - (ii * (ii - 1)) / 2;
+    param_owner(c.l, c.pi, c.pj, c.pkind);
     const int tt = (c.i * (c.i - 1)) / 2 + c.j;
     c.src_re = c.i == c.j ? c.i : c.i > c.j ? d + tt : D;
     c.src_im = c.i > c.j ? d + T + tt : D;
@@ -1372,6 +1367,143 @@ struct Small {
     return x;
   }
 
+  // ---- k_mle_fused_hw (n = 3): the hand-off between a trial's wavefront and its helper wavefront on the same SIMD.
+  // A clipped trial's second Cholesky sweep (cholesky_param of the projected matrix) and the front of its first
+  // nll_grad are independent; the helper runs the sweep while the trial's wave runs the front.  Everything goes through
+  // the first doubles of the trial's LDS pair store (bfgs_iterate_2l's `lp`, which nothing touches before the BFGS loop):
+  // the helper's working image, the parameters it returns, and the words `task`, `done`, `ok`.  Data first, then the
+  // flag: release stores and acquire loads at workgroup scope, no workgroup barrier -- the four trials of a workgroup
+  // stay uncoupled.  Every wait is a counted loop; whoever runs out of polls leaves:
+  //   helper: polls `task` (kUnset until the trial's wave knows its class); kNone -> exit; kSweep -> claims the task
+  //           (compare-and-swap kSweep -> kClaimed), runs the sweep (L into the trial's Bm(), which the front of an
+  //           evaluation with a StartPoint does not touch), writes x and ok, then done = 1.
+  //   trial:  publishes kNone (positive definite, Jacobi path, short cut refused) or the projected matrix and kSweep;
+  //           at the end of the front it polls `done`.  Out of polls: it takes the task back (compare-and-swap
+  //           kSweep -> kRevoked: a helper that has not claimed it never will) and runs k_mle_fused's serial path.  If the
+  //           helper had claimed it, the helper is inside straight-line code that waits for nobody, and a second,
+  //           much longer count covers that sweep many times over.
+  struct HelperLink {
+    enum : int { kNone = 0, kSweep = 1, kUnset = 2, kClaimed = 3, kRevoked = 4 };
+    // polls (each an LDS read and an s_sleep): the helper's wait covers the longest path to the verdict (~20 k clocks)
+    // several hundred times, the trial's first wait the helper's ~2.5 k-clock sweep likewise
+    static constexpr int kHelperPolls = 1 << 15, kWaitPolls = 1 << 12, kClaimedPolls = 1 << 16;
+    double* base;  // [MAT] image, [D] x, then the three words
+    int pending;   // trial's wave: the projected matrix is with the helper (wave-uniform)
+    __device__ __forceinline__ static constexpr int doubles() { return MAT + D + 2; }
+    __device__ __forceinline__ cd* image() const { return reinterpret_cast<cd*>(base); }
+    __device__ __forceinline__ double* x() const { return base + MAT; }
+    __device__ __forceinline__ int* task() const { return reinterpret_cast<int*>(base + MAT + D); }
+    __device__ __forceinline__ int* done() const { return task() + 1; }
+    __device__ __forceinline__ int* ok() const { return task() + 2; }
+    __device__ __forceinline__ static void publish(int* w, int v) {  // after this wave's data writes
+      wave_sync();
+      if ((threadIdx.x & 63) == 0) __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ static int peek(const int* w) {
+      return __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    }
+    __device__ __forceinline__ static bool claim(int* w, int to) {  // kSweep -> `to`, by one lane; the same answer in all
+      int won = 0;
+      if ((threadIdx.x & 63) == 0) {
+        int expect = kSweep;
+        won = __hip_atomic_compare_exchange_strong(w, &expect, to, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      return __builtin_amdgcn_readfirstlane(won) != 0;
+    }
+    template <int SLEEP>
+    __device__ __forceinline__ static int poll(const int* w, int idle, int polls) {  // the word once it is not `idle`
+      int v = idle;
+#pragma unroll 1
+      for (int n = 0; n < polls; ++n) {
+        v = peek(w);
+        if (v != idle) break;
+        __builtin_amdgcn_s_sleep(SLEEP);
+      }
+      return v;
+    }
+    // trial's wave, before the workgroup barrier of make_ctx
+    __device__ __forceinline__ void reset() {
+      pending = 0;
+      if ((threadIdx.x & 63) == 0) {
+        *task() = kUnset;
+        *done() = 0;
+      }
+    }
+    __device__ __forceinline__ void none() const { publish(task(), kNone); }
+    __device__ __forceinline__ void give(int e, cd proj) {
+      image()[e] = proj;
+      publish(task(), kSweep);
+      pending = 1;
+    }
+    // trial's wave: the helper's parameters; false = they did not come and the helper will not write any more
+    // (or, after a claimed task and the long count, has stopped making progress)
+    __device__ __forceinline__ bool collect(int l, double& xl, int& okl) const {
+      if (poll<1>(done(), 0, kWaitPolls) == 0) {
+        if (claim(task(), kRevoked)) return false;
+        if (poll<1>(done(), 0, kClaimedPolls) == 0) return false;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      xl = x()[l];
+      okl = *ok();
+      return true;
+    }
+  };
+  // What the helper wavefront knows of its lane: the matrix element and the Cholesky parameter it owns (make_ctx).
+  // cholesky_param's view of its images: A() is the helper's own, Bm() the trial's.
+  struct CtxH {
+    int l, i, j, e, pi, pj, pkind;
+    cd *image, *factor;
+    __device__ __forceinline__ cd* A() const { return image; }
+    __device__ __forceinline__ cd* Bm() const { return factor; }
+    __device__ __forceinline__ cd* V() const { return nullptr; }  // (the speculative inverse is not the helper's)
+  };
+  // What nll_grad<.., LATE> got from the helper: `got` = it came (otherwise x is a finite stand-in and the caller
+  // evaluates again from the top), the parameter of this lane, and whether the matrix was positive definite.
+  struct LateX {
+    bool got;
+    double x;
+    int ok;
+  };
+  // The context of a trial's wavefront in k_mle_fused_hw: that of k_mle_fused, and the link to its helper.
+  template <class Base>
+  struct WithHelper : Base {
+    HelperLink* link;
+    LateX* late;  // nll_grad<.., LATE>
+    static constexpr bool kHelper = true;
+  };
+  __device__ __forceinline__ static void param_owner(int l, int& pi, int& pj, int& pkind) {
+    // parameter l: diagonal (l, l), then the T real and the T imaginary parts in the order of np.tril_indices(d, -1);
+    // row ii of entry t is the number of triangular numbers k (k - 1) / 2 <= t, k = 1 .. d - 1
+    const bool diag = l < d, imag = l >= d + T;
+    const int t = l - d - (imag ? T : 0);
+    int ii = 1;
+#pragma unroll
+    for (int k = 2; k < d; ++k) ii += t >= (k * (k - 1)) / 2;
+    pkind = diag ? 0 : imag ? 2 : 1;
+    pi = diag ? l : ii;
+    pj = diag ? l : t - (ii * (ii - 1)) / 2;
+  }
+  __device__ static void helper_wave(const HelperLink& k, cd* L) {
+    static_assert(G == 64, "one trial per wavefront");
+    if (HelperLink::template poll<2>(k.task(), HelperLink::kUnset, HelperLink::kHelperPolls) != HelperLink::kSweep) return;
+    if (!HelperLink::claim(k.task(), HelperLink::kClaimed)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    CtxH c;
+    c.l = threadIdx.x & 63;
+    c.i = c.l / d;
+    c.j = c.l % d;
+    c.e = c.i * LD + c.j;
+    param_owner(c.l, c.pi, c.pj, c.pkind);
+    c.image = k.image();
+    c.factor = L;
+    int ok2;
+    const double x2 = cholesky_param(c, c.image[c.e], ok2);
+    k.x()[c.l] = x2;
+    if (c.l == 0) *k.ok() = ok2;  // (wave-uniform: the pivots are read from their lanes)
+    HelperLink::publish(k.done(), 1);
+  }
+
   // ---- a7, short cut for exactly ONE negative eigenvalue (lam_1 < 0 < lam_2 <= ...):
   //   U max(v, eps) U^dagger = A + (eps - lam_1) v_1 v_1^dagger,
   // so only the projector N = v_1 v_1^dagger is needed.  M = A^{-1} (Gauss-Jordan, pivot order with
@@ -1472,6 +1604,9 @@ struct Small {
   // definite (its Cholesky factorisation runs through) no eigenvalue is below the clip, so
   // U max(v, 1e-15) U^dagger is the input itself (to rounding) and only the trace division is left.
   // Returns the projected element; if `xl` is non-null also the Cholesky parameter of the result.
+  // C::kHelper (k_mle_fused_hw): the trial's helper wavefront is told the class as soon as it is known, and a lifted
+  // trial leaves its second factorisation to it: the projected matrix comes back with c.link->pending set, *xl and
+  // *ok_out are not written (HelperLink::collect has them later) and *lscale_out = 1.
   template <bool SPEC = false, class C>
   __device__ static cd make_feasible(const C& c, cd r, double* xl, int* ok_out, double* lscale_out = nullptr) {
     int ok, neg, kneg;
@@ -1493,6 +1628,9 @@ struct Small {
     // One trial per wave: `ok` is wave-uniform and a clipped trial replaces all of it, so it is formed only for the
     // trials that keep it.  Several trials per wave: the groups differ, every lane runs it ahead of the branch.
     const bool all_pd = __all(ok);
+    if constexpr (C::kHelper) {
+      if (all_pd) c.link->none();
+    }
     if (G < 64 || all_pd || (!xl && lscale_out)) pd_epilogue();
     if (!all_pd) {
       cd proj;
@@ -1504,8 +1642,18 @@ struct Small {
                        (int)lift_single_negative(c, r, kn, 1e-15, proj, SPEC && kn == d - 1 ? &spec_inv : nullptr)) != 0;
         }
       }
+      if constexpr (C::kHelper) {
+        if (!lifted) c.link->none();  // the Jacobi path, or the short cut refused
+      }
       if (!lifted) proj = psd_project(c, r, 1e-15);  // whole wave runs it; PD trials keep their shortcut
       QT_STAMP(6);
+      if constexpr (C::kHelper) {
+        if (lifted) {
+          c.link->give(c.e, proj);
+          if (lscale_out) *lscale_out = 1.0;
+          return proj;
+        }
+      }
       int ok2 = 1;
       double x2 = xl ? cholesky_param(c, proj, ok2) : 0.0;
       if (lifted && xl && !__all(ok2 || ok)) {
@@ -1558,14 +1706,19 @@ struct Small {
     double lscale;  // L(x) = lscale * Bm()
   };
   // DEFER (specialised kernels only): `f` is left alone; `dv` receives what deferred_value needs to form it later.
-  template <bool DEFER = false, class C>
+  // LATE (with `start`; k_mle_fused_hw): the parameters are not known yet.  Everything up to the gradient matrix reads
+  // only start->rho; x is first needed for Tr = sum x^2 behind it, and the trial's helper wavefront has it by then
+  // (HelperLink::collect, LateX).
+  template <bool DEFER = false, class C, bool LATE = false>
   __device__ static void nll_grad(const C& c, double xl, double& f, double& gl, cd* rho_l = nullptr,
                                   bool want_grad = true, const StartPoint* start = nullptr, DeferredValue* dv = nullptr) {
     static_assert(!DEFER || !C::kGeneric, "the deferred value needs the compile-time row count of the specialised shape");
     double tr;
     QT_STAMP(11);
     cd m;
-    if (start) {
+    if constexpr (LATE) {
+      m = start->rho;  // (not read: rho_e below is start->rho)
+    } else if (start) {
       tr = gsum<G>(xl * xl);
       m = cd{start->rho.re * tr, start->rho.im * tr};
     } else {
@@ -1641,6 +1794,15 @@ struct Small {
     wave_sync();
     cd g = matrix_of(c, vec);
     QT_STAMP(17);
+    if constexpr (LATE) {
+      LateX& lx = *c.late;
+      lx.x = 1.0;
+      lx.ok = 0;
+      lx.got = c.link->collect(c.l, lx.x, lx.ok);
+      xl = lx.x;
+      tr = gsum<G>(xl * xl);
+      QT_STAMP(25);
+    }
     g.re = -g.re;
     g.im = -g.im;
     if (c.i == c.j) g.re -= tr_g_rho;
@@ -2186,7 +2348,10 @@ constexpr int kFusedLdsPairs = 24;  // (s, y) pairs of k_mle_fused<3> kept in LD
 // a10 in ONE launch, for batches small enough that its 256-VGPR footprint (two waves per SIMD) is no
 // handicap: start point, first evaluation and -- for the waves that still hold an open trial -- the BFGS
 // loop.  Saves the second launch (2.5-4 us when nothing iterates, ~10 % of a 1000-trial step).
-template <int NQ, bool GENERIC>
+// HW (k_mle_fused_hw, n = 3, 'lin' start): launched with blocks of 256 x 2 threads.  threadIdx.y = 0 are the four
+// trial wavefronts, exactly as without HW; threadIdx.y = 1 are their helpers (Small::HelperLink), wavefront 4 + t on
+// the SIMD of wavefront t and with the same threadIdx.x, hence the same trial and the same LDS slot.
+template <int NQ, bool GENERIC, bool HW = false>
 __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::type& pv, const int64_t* __restrict__ counts, int B, int init,
                                                int max_iter, double gtol, EstOut rho,
                                                int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
@@ -2195,7 +2360,27 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   using S = Small<NQ>;
   constexpr int D = S::D, G = S::G, d = S::d;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::template CtxOf<GENERIC>::type c;
+  using Ctx = typename S::template CtxOf<GENERIC>::type;
+  std::conditional_t<HW, typename S::template WithHelper<Ctx>, Ctx> c;
+  [[maybe_unused]] typename S::HelperLink link;
+  [[maybe_unused]] typename S::LateX late{false, 0.0, 0};
+  if constexpr (HW) {
+    static_assert(NQ == 3, "one trial per wavefront");
+    static_assert(S::HelperLink::doubles() <= kFusedLdsPairs * 2 * D, "the hand-off lives in the LDS pair store");
+    int r1 = 6;  // the product POVM's one-qubit rows (the generic body is launched with HW only for a product POVM)
+    if constexpr (GENERIC) r1 = pv.pr.R1;
+    const int per_trial = S::trial_doubles(pv.M, r1);
+    double* sm = smem + S::table_doubles(pv.M, r1) + (threadIdx.x >> 6) * (per_trial + pv.extra);
+    link.base = sm + per_trial + LineSearch::SLOTS + 2 * max_iter;  // bfgs_iterate_2l's `lp`
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.y) != 0) {
+      __syncthreads();  // the workgroup barrier of make_ctx, behind which `task` and `done` are set up
+      S::helper_wave(link, reinterpret_cast<cd*>(sm + S::oB));
+      return;
+    }
+    link.reset();
+    c.link = &link;
+    c.late = &late;
+  }
   bool live;
   const int b = S::trial_index(B, &live);
   const int bb = live ? b : B - 1;
@@ -2215,11 +2400,13 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   int ok;
   double xk;
   typename S::StartPoint sp;
+  [[maybe_unused]] cd lin;
   if (init == 0) {
     double bl;
-    const cd lin = S::lin_invert(c, bl);
+    lin = S::lin_invert(c, bl);
     QT_STAMP(2);
-    sp.rho = S::template make_feasible<true>(c, lin, &xk, &ok, &sp.lscale);  // one wave per SIMD: speculative inverse (cholesky_param)
+    // one wave per SIMD (HW: beside a helper that sleeps): speculative inverse (cholesky_param)
+    sp.rho = S::template make_feasible<true>(c, lin, &xk, &ok, &sp.lscale);
   } else {
     sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
     sp.lscale = 1.0;
@@ -2229,8 +2416,30 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   double fk, gk;
   cd rho_l;
   [[maybe_unused]] typename S::DeferredValue dv;
-  if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
-  else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
+  bool evaluate = true;
+  if constexpr (HW) {
+    if (__builtin_amdgcn_readfirstlane(link.pending)) {
+      // the front of the evaluation beside the helper's factorisation of sp.rho; x arrives where Tr is formed
+      if constexpr (GENERIC) S::template nll_grad<false, decltype(c), true>(c, 0.0, fk, gk, &rho_l, true, &sp);
+      else S::template nll_grad<true, decltype(c), true>(c, 0.0, fk, gk, &rho_l, true, &sp, &dv);
+      xk = late.x;
+      ok = late.ok;
+      // Nothing came, or the short cut left something non-positive behind (make_feasible): the serial path, as
+      // without a helper, and the evaluation again from the top.  (One trial per wave: both facts are wave-uniform.)
+      const bool got = __builtin_amdgcn_readfirstlane((int)late.got) != 0;
+      if (!got) xk = S::cholesky_param(c, sp.rho, ok);
+      ok = __builtin_amdgcn_readfirstlane(ok);
+      evaluate = !got || !ok;
+      if (!ok) {
+        sp.rho = S::psd_project(c, lin, 1e-15);
+        xk = S::cholesky_param(c, sp.rho, ok);
+      }
+    }
+  }
+  if (evaluate) {
+    if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
+    else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
+  }
   const double gnorm = gmax<G>(fabs(gk));
   QT_STAMP(9);
   const bool iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
@@ -2287,6 +2496,16 @@ __global__ void __launch_bounds__(256) k_mle_fused_mixed(typename MleArgs<GENERI
                                                          double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                          double* __restrict__ pairs) {
   mle_fused_body<NQ, GENERIC>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+}
+
+// The 'lin' start with a helper wavefront per trial (mle_fused_body<.., HW>): blocks of 256 x 2 threads, the grid and
+// the LDS layout of k_mle_fused.  Two waves per SIMD: the 256 registers of the body are what a wave can have.
+template <int NQ, bool GENERIC>
+__global__ void __launch_bounds__(512) k_mle_fused_hw(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
+                                                      double gtol, EstOut rho, int32_t* __restrict__ nit_out,
+                                                      int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
+                                                      int32_t* __restrict__ status_out, double* __restrict__ pairs) {
+  mle_fused_body<NQ, GENERIC, true>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 
 // Metropolis-Hastings chain on the Cholesky parameters (reference mhmc.py:80-119 with

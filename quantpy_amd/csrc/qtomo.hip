@@ -158,6 +158,9 @@ struct qt_handle {
   bool mle_specialise = true;
   bool image_ready = false;    // pr_image holds the table image of the current POVM (built when both tables are paired)
   bool last_mle_spec = false;  // which instantiation the last MLE launch took (qt_get_mle_specialised)
+  // qt_set_option(QT_OPT_MLE_HELPER_WAVE): let the one-launch 'lin' start at n = 3 run k_mle_fused_hw (a helper wavefront per trial)
+  bool mle_helper_wave = true;
+  bool last_mle_helper = false;  // whether the last MLE launch was k_mle_fused_hw (qt_get_mle_helper_wave)
   // The shape the specialised kernels are compiled for (qt::SpecArgs): three two-outcome settings per qubit (R1 = 6,
   // K = d, M = 6^n <= 4 G and the segmented shots check), both tables paired and their stages on, equal shots, the
   // shots check on.  Everything else -- 'sic', 'proj4', 'proj', unequal shots, plain arrays -- takes the generic body.
@@ -721,6 +724,7 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
     return fail(QT_ERR_UNSUPPORTED, "max_iter > 2000 is not supported for n_qubits = 3 (LDS holds the two-loop scalars)");
   const int mi = max_iter > 0 ? max_iter : 1;
   h->last_mle_spec = h->spec_eligible();
+  h->last_mle_helper = false;
   return by_nq(h, [&](auto nq) -> int {
     constexpr int NQ = decltype(nq)::value;
     if constexpr (NQ <= 3) {
@@ -734,9 +738,18 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
           const int over = mi > qt::kFusedLdsPairs ? mi : 1;  // (indexed by pair number: rows below kFusedLdsPairs stay unused)
           HIPCHK(h->hess.ensure((size_t)B * over * 2 * h->D * sizeof(double)));
         }
-        const Plan p = povm_plan<NQ>(h, B, extra);
+        Plan p = povm_plan<NQ>(h, B, extra);
         auto fused = [&](auto generic) {
           constexpr bool GEN = decltype(generic)::value;
+          if constexpr (NQ == 3) {
+            // the generic body meets its helpers at the barrier behind the product POVM's tables
+            if (h->mle_helper_wave && init == QT_INIT_LIN && p.pv.pr.enabled) {
+              h->last_mle_helper = true;
+              p.block = dim3(qt::Small<NQ>::NT, 2);  // y = 1: the helper wavefronts
+              return launch(h, qt::k_mle_fused_hw<NQ, GEN>, p, mle_povm_arg<GEN>(h, p), dc, B, max_iter, tol, eo, dnit, dnfev,
+                            dfun, dst, h->hess.as<double>());
+            }
+          }
           return launch(h, init == QT_INIT_LIN ? qt::k_mle_fused<NQ, GEN> : qt::k_mle_fused_mixed<NQ, GEN>, p,
                         mle_povm_arg<GEN>(h, p), dc, B, max_iter, tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>());
         };
@@ -1195,6 +1208,7 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
       return 0;
     case QT_OPT_PAIRED_STAGES: h->paired_stages = value != 0.0; return 0;
     case QT_OPT_MLE_SPECIALISE: h->mle_specialise = value != 0.0; return 0;
+    case QT_OPT_MLE_HELPER_WAVE: h->mle_helper_wave = value != 0.0; return 0;
     case QT_OPT_LIFP_DIST_SLICE:
       if (!(value >= 0.0 && value <= 16777216.0)) return fail(QT_ERR_ARG, "QT_OPT_LIFP_DIST_SLICE out of range");
       h->lifp_dist_slice = (int)value;
@@ -1211,6 +1225,11 @@ int qt_get_paired_tables(qt_handle_t* h) {
 int qt_get_mle_specialised(qt_handle_t* h) {
   QT_ENTER(h);
   return h->last_mle_spec ? 1 : 0;
+}
+
+int qt_get_mle_helper_wave(qt_handle_t* h) {
+  QT_ENTER(h);
+  return h->last_mle_helper ? 1 : 0;
 }
 
 int qt_timer_begin(qt_handle_t* h) {

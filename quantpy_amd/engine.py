@@ -183,7 +183,10 @@ class Engine:
         table, 1 = the zero-skipping stages where `paired_tables` says so; the same bits either way),
         _capi.QT_OPT_MLE_SPECIALISE (0 = the generic MLE kernels for every POVM, 1 = the instantiation compiled for the
         six-projector shape where the POVM has it, see `mle_specialised`; the same bits either way),
-        _capi.QT_OPT_LIFP_DIST_SLICE (processes per slice of `lifp_dist`; 0 = the library's 128 MB bound)."""
+        _capi.QT_OPT_LIFP_DIST_SLICE (processes per slice of `lifp_dist`; 0 = the library's 128 MB bound),
+        _capi.QT_OPT_MLE_HELPER_WAVE (n = 3, one-launch `mle` / `mle_dist` from the 'lin' start: 1 = a helper wavefront
+        per trial factorises a clipped trial's projected matrix beside its first evaluation, 0 = the kernel without
+        helpers, see `mle_helper_wave`; the same bits either way)."""
         self._chk(self.lib.qt_set_option(self._h, int(option), float(value)))
 
     @property
@@ -197,6 +200,11 @@ class Engine:
         """True if the last `mle` / `mle_dist` launch took the MLE kernels specialised on the POVM's shape (n <= 3:
         'proj-set' with equal shots per setting, paired stages and the shots check on), False if the generic ones."""
         return bool(self._chk(self.lib.qt_get_mle_specialised(self._h)))
+
+    @property
+    def mle_helper_wave(self):
+        """True if the last `mle` / `mle_dist` launch was the one-launch kernel with a helper wavefront per trial."""
+        return bool(self._chk(self.lib.qt_get_mle_helper_wave(self._h)))
 
     def timer_begin(self):
         self._chk(self.lib.qt_timer_begin(self._h))
