@@ -89,8 +89,9 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
  * workspaces that follow the batch stay bounded; 0, or more than 128 MB of Choi matrices (2048 processes at n = 3,
  * 32 768 at n = 2), takes that bound.  The same bits whatever the slice.
  * QT_OPT_MLE_HELPER_WAVE (default 1): at n = 3 the one-launch MLE from the 'lin' start (product POVM, batches within
- * QT_OPT_MLE_FUSED_MAX_WAVES) gives every trial a helper wavefront, which factorises a clipped trial's projected
- * matrix beside its first evaluation; 0 launches the kernel without helpers.  Both give the same bits. */
+ * QT_OPT_MLE_FUSED_MAX_WAVES) gives every trial a helper wavefront, which lifts the trial's linear-inversion matrix
+ * on speculation beside the first Cholesky sweep and, where the sweep asks for the lift, hands the clipped matrix over
+ * and factorises it beside the first evaluation; 0 launches the kernel without helpers.  Both give the same bits. */
 enum qt_option {
   QT_OPT_SHOTS_CHECK = 1,
   QT_OPT_MLE_FUSED_MAX_WAVES = 2,

@@ -14,7 +14,7 @@ QT_INIT_MIXED = 1
 QT_STREAM_LEGACY = 1  # qt_set_stream: the legacy default ("null") stream
 QT_OPT_SHOTS_CHECK, QT_OPT_MLE_FUSED_MAX_WAVES, QT_OPT_PAIRED_STAGES, QT_OPT_MLE_SPECIALISE = 1, 2, 3, 4  # qt_set_option
 QT_OPT_LIFP_DIST_SLICE = 5  # processes per slice of qt_lifp_dist_batch (0: the library's byte bound)
-QT_OPT_MLE_HELPER_WAVE = 6  # n = 3 one-launch MLE, 'lin' start: a helper wavefront per trial (0: the kernel without)
+QT_OPT_MLE_HELPER_WAVE = 6  # n = 3 one-launch MLE, 'lin' start: a helper wavefront per trial lifts on speculation (0: the kernel without)
 
 # status codes (include/qtomo.h)
 QT_ERR_ARG, QT_ERR_STATE, QT_ERR_HIP, QT_ERR_SINGULAR, QT_ERR_UNSUPPORTED = -1, -2, -3, -4, -5

@@ -33,16 +33,19 @@ namespace qt {
 // -DQT_PHASE_TIMING (lib/libqtomo_prof.so); the product library carries none of this.
 #ifdef QT_PHASE_TIMING
 __device__ long long* g_qt_prof = nullptr;  // [waves][32]
+// One row per wavefront of threadIdx.y = 0; the helper wavefronts of k_mle_fused_hw (threadIdx.y = 1) have theirs behind
+// those of the whole grid, in the same order.
+#define QT_PROF_ROW \
+  ((size_t)(blockIdx.x + threadIdx.y * gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6))
 #define QT_STAMP(slot)                                                                                   \
   do {                                                                                                   \
     if (g_qt_prof && (threadIdx.x & 63) == 0)                                                            \
-      g_qt_prof[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32 + (slot)] =           \
-          (long long)__builtin_readcyclecounter();                                                       \
+      g_qt_prof[QT_PROF_ROW * 32 + (slot)] = (long long)__builtin_readcyclecounter();                    \
   } while (0)
 #define QT_STAMP_VAL(slot, val)                                                                          \
   do {                                                                                                   \
     if (g_qt_prof && (threadIdx.x & 63) == 0)                                                            \
-      g_qt_prof[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32 + (slot)] = (val);    \
+      g_qt_prof[QT_PROF_ROW * 32 + (slot)] = (val);                                                      \
   } while (0)
 #else
 #define QT_STAMP(slot) do {} while (0)
@@ -441,6 +444,9 @@ struct Small {
     // the launch-uniform facts, read at run time here and compile-time constants in CtxS
     static constexpr bool kGeneric = true;
     static constexpr bool kHelper = false;  // (WithHelper)
+    // (CtxH: the helper wavefront's lift can be called off; a trial's own never is)
+    __device__ __forceinline__ static constexpr int verdict_load() { return 0; }
+    __device__ __forceinline__ static constexpr bool abandoned(int) { return false; }
     __device__ __forceinline__ int R1() const { return pv.pr.R1; }
     __device__ __forceinline__ bool uniform() const { return pv.pr.uniform != 0; }
     __device__ __forceinline__ bool pairedT() const { return pv.pr.pairedT != 0; }
@@ -483,6 +489,8 @@ struct Small {
     __device__ __forceinline__ double* extra() const { return sm + trial_doubles(M, 6); }  // [a.extra]
     static constexpr bool kGeneric = false;
     static constexpr bool kHelper = false;
+    __device__ __forceinline__ static constexpr int verdict_load() { return 0; }
+    __device__ __forceinline__ static constexpr bool abandoned(int) { return false; }
     __device__ __forceinline__ static constexpr bool prod() { return true; }
     __device__ __forceinline__ static constexpr int R1() { return 6; }
     __device__ __forceinline__ static constexpr bool uniform() { return true; }
@@ -1291,6 +1299,7 @@ struct Small {
   // skips ~3 k of its ~39 k clocks (the launch ends with its slowest wave, and those are the clipped trials); a
   // positive definite one throws the inverse away, ~1.5 k clocks it had to spare.  Same arithmetic, same bits, as the
   // loop in lift_single_negative.  *spec_inv = this lane's element of the inverse (garbage unless kneg = d - 1).
+  // (k_mle_fused_hw runs the plain sweep: there the trial's helper wavefront speculates, see HelperLink.)
   template <bool SPEC = false, class C>
   __device__ static double cholesky_param(const C& c, cd a, int& ok, int* neg_out = nullptr, int* kneg_out = nullptr,
                                           cd* spec_inv = nullptr) {
@@ -1368,33 +1377,50 @@ struct Small {
   }
 
   // ---- k_mle_fused_hw (n = 3): the hand-off between a trial's wavefront and its helper wavefront on the same SIMD.
-  // A clipped trial's second Cholesky sweep (cholesky_param of the projected matrix) and the front of its first
-  // nll_grad are independent; the helper runs the sweep while the trial's wave runs the front.  Everything goes through
-  // the first doubles of the trial's LDS pair store (bfgs_iterate_2l's `lp`, which nothing touches before the BFGS loop):
-  // the helper's working image, the parameters it returns, and the words `task`, `done`, `ok`.  Data first, then the
-  // flag: release stores and acquire loads at workgroup scope, no workgroup barrier -- the four trials of a workgroup
-  // stay uncoupled.  Every wait is a counted loop; whoever runs out of polls leaves:
-  //   helper: polls `task` (kUnset until the trial's wave knows its class); kNone -> exit; kSweep -> claims the task
-  //           (compare-and-swap kSweep -> kClaimed), runs the sweep (L into the trial's Bm(), which the front of an
-  //           evaluation with a StartPoint does not touch), writes x and ok, then done = 1.
-  //   trial:  publishes kNone (positive definite, Jacobi path, short cut refused) or the projected matrix and kSweep;
-  //           at the end of the front it polls `done`.  Out of polls: it takes the task back (compare-and-swap
-  //           kSweep -> kRevoked: a helper that has not claimed it never will) and runs k_mle_fused's serial path.  If the
-  //           helper had claimed it, the helper is inside straight-line code that waits for nobody, and a second,
-  //           much longer count covers that sweep many times over.
+  // Between lin_invert and the lifted matrix a clipped trial is one serial chain (first Cholesky sweep, Gauss-Jordan
+  // inverse, squarings, certificate), and nothing of the lift needs the sweep except the knowledge that the lift is
+  // wanted.  So the helper runs lift_single_negative in natural pivot order on EVERY trial, speculatively, from the
+  // moment the linear-inversion matrix exists, while the trial's wave runs the plain sweep; the verdict of the sweep
+  // then lets the helper go on or sends it home.  After "go" the helper hands the lifted matrix over and runs the
+  // second Cholesky sweep of it while the trial's wave runs the front of the first nll_grad on it (the two are
+  // independent).  Everything goes through the first doubles of the trial's LDS pair store (bfgs_iterate_2l's `lp`,
+  // which nothing touches before the BFGS loop): the helper's two images, the parameters it returns and the words
+  // below.  Data first, then the flag: release stores and acquire loads at workgroup scope, no workgroup barrier --
+  // the four trials of a workgroup stay uncoupled.  Every wait is a counted loop; whoever runs out of polls leaves:
+  //   trial:  `task` = kSpec with its matrix in image(0), as soon as lin_invert is done.  After its sweep, `verdict`:
+  //           kAbort (positive definite: it never waits; or a class the natural-order lift does not serve: wrong
+  //           pivot, several negative pivots -- today's serial code on its own wave) or kGo (one negative pivot, the
+  //           last).  After kGo it polls `lifted`: kLifted -> the matrix is in result(), the front of the evaluation
+  //           runs on it and collect() has x and ok behind it; kRefused -> the eigensolver on its own wave (the lift on
+  //           its own wave would refuse with the same bits).  Out of polls: it takes the verdict back (compare-and-swap
+  //           kGo -> kRevoked: a helper that has not claimed it never will) and runs the serial path.  If the helper
+  //           had claimed it, the helper is inside straight-line code that waits for nobody, and a second, much longer
+  //           count covers that many times over.
+  //   helper: polls `task`; on kSpec runs the lift on its own images, looking at `verdict` once per squaring
+  //           (CtxH::abandoned) and leaving on anything but "none yet" or kGo.  At the end it waits for the verdict,
+  //           claims kGo (-> kClaimed), publishes kRefused and leaves, or the matrix and kLifted; then the sweep (L
+  //           into the trial's Bm(), which the front of an evaluation with a StartPoint does not touch), x, ok, done.
+  //           During the speculation it writes nothing outside this region.  Wherever it leaves, `gone` = 1 is its last
+  //           write: the trial's wave acquires it before the BFGS loop writes the first pair over this region.
   struct HelperLink {
-    enum : int { kNone = 0, kSweep = 1, kUnset = 2, kClaimed = 3, kRevoked = 4 };
-    // polls (each an LDS read and an s_sleep): the helper's wait covers the longest path to the verdict (~20 k clocks)
-    // several hundred times, the trial's first wait the helper's ~2.5 k-clock sweep likewise
-    static constexpr int kHelperPolls = 1 << 15, kWaitPolls = 1 << 12, kClaimedPolls = 1 << 16;
-    double* base;  // [MAT] image, [D] x, then the three words
-    int pending;   // trial's wave: the projected matrix is with the helper (wave-uniform)
-    __device__ __forceinline__ static constexpr int doubles() { return MAT + D + 2; }
-    __device__ __forceinline__ cd* image() const { return reinterpret_cast<cd*>(base); }
-    __device__ __forceinline__ double* x() const { return base + MAT; }
-    __device__ __forceinline__ int* task() const { return reinterpret_cast<int*>(base + MAT + D); }
-    __device__ __forceinline__ int* done() const { return task() + 1; }
-    __device__ __forceinline__ int* ok() const { return task() + 2; }
+    enum : int { kUnset = 0, kSpec = 1 };                                    // task
+    enum : int { kPending = 0, kGo = 1, kAbort = 2, kClaimed = 3, kRevoked = 4 };  // verdict
+    enum : int { kNothing = 0, kLifted = 1, kRefused = 2 };                  // lifted
+    // polls (each an LDS read and an s_sleep): the helper's waits cover the longest path to the verdict (~20 k clocks)
+    // several hundred times, the trial's first wait the helper's ~11 k-clock chain likewise
+    static constexpr int kHelperPolls = 1 << 15, kWaitPolls = 1 << 14, kClaimedPolls = 1 << 16;
+    double* base;  // [2][MAT] images, [D] x, then the words
+    int pending;   // trial's wave: the lifted matrix came from the helper, which is factorising it (wave-uniform)
+    __device__ __forceinline__ static constexpr int doubles() { return 2 * MAT + D + 3; }
+    __device__ __forceinline__ cd* image(int k) const { return reinterpret_cast<cd*>(base + k * MAT); }
+    __device__ __forceinline__ cd* result() const { return image(1); }  // (the lift's second image is free by then)
+    __device__ __forceinline__ double* x() const { return base + 2 * MAT; }
+    __device__ __forceinline__ int* task() const { return reinterpret_cast<int*>(base + 2 * MAT + D); }
+    __device__ __forceinline__ int* verdict() const { return task() + 1; }
+    __device__ __forceinline__ int* lifted() const { return task() + 2; }
+    __device__ __forceinline__ int* done() const { return task() + 3; }
+    __device__ __forceinline__ int* gone() const { return task() + 4; }
+    __device__ __forceinline__ int* ok() const { return task() + 5; }
     __device__ __forceinline__ static void publish(int* w, int v) {  // after this wave's data writes
       wave_sync();
       if ((threadIdx.x & 63) == 0) __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1402,10 +1428,10 @@ struct Small {
     __device__ __forceinline__ static int peek(const int* w) {
       return __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
     }
-    __device__ __forceinline__ static bool claim(int* w, int to) {  // kSweep -> `to`, by one lane; the same answer in all
+    __device__ __forceinline__ static bool claim(int* w, int from, int to) {  // by one lane; the same answer in all
       int won = 0;
       if ((threadIdx.x & 63) == 0) {
-        int expect = kSweep;
+        int expect = from;
         won = __hip_atomic_compare_exchange_strong(w, &expect, to, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
       }
@@ -1427,36 +1453,70 @@ struct Small {
       pending = 0;
       if ((threadIdx.x & 63) == 0) {
         *task() = kUnset;
+        *verdict() = kPending;
+        *lifted() = kNothing;
         *done() = 0;
+        *gone() = 0;
       }
     }
-    __device__ __forceinline__ void none() const { publish(task(), kNone); }
-    __device__ __forceinline__ void give(int e, cd proj) {
-      image()[e] = proj;
-      publish(task(), kSweep);
-      pending = 1;
+    __device__ __forceinline__ void speculate(int e, cd lin) const {
+      image(0)[e] = lin;
+      publish(task(), kSpec);
     }
-    // trial's wave: the helper's parameters; false = they did not come and the helper will not write any more
-    // (or, after a claimed task and the long count, has stopped making progress)
+    __device__ __forceinline__ void decide(bool go) const { publish(verdict(), go ? kGo : kAbort); }
+    // trial's wave, after decide(true): kLifted = this lane's element of the lifted matrix is in `proj` and the helper
+    // is factorising it; kRefused = the lift ran and declined; kNothing = nothing came and nothing will (or, after a
+    // claimed verdict and the long count, the helper has stopped making progress)
+    __device__ __forceinline__ int await_lift(int e, cd& proj) {
+      int v = poll<1>(lifted(), kNothing, kWaitPolls);
+      if (v == kNothing) {
+        if (claim(verdict(), kGo, kRevoked)) return kNothing;
+        v = poll<1>(lifted(), kNothing, kClaimedPolls);
+        if (v == kNothing) return kNothing;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      if (v == kLifted) {
+        proj = result()[e];
+        pending = 1;
+      }
+      return v;
+    }
+    // trial's wave: the helper's parameters; false = they did not come (the helper claimed the verdict before it
+    // published the matrix and waits for nobody behind that: the long count covers its sweep many times over)
     __device__ __forceinline__ bool collect(int l, double& xl, int& okl) const {
-      if (poll<1>(done(), 0, kWaitPolls) == 0) {
-        if (claim(task(), kRevoked)) return false;
-        if (poll<1>(done(), 0, kClaimedPolls) == 0) return false;
-      }
+      if (poll<1>(done(), 0, kClaimedPolls) == 0) return false;
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
       xl = x()[l];
       okl = *ok();
       return true;
     }
+    // trial's wave, before the first (s, y) pair goes into the LDS pair store: the helper has left this region.  In any
+    // normal run that was thousands of clocks ago and this is one LDS read.  The wait is bounded like every other: after
+    // 2^16 polls without an answer the trial's wave goes on and writes its pairs unsynchronised (a helper that has not
+    // left by then has stopped making progress; its region is the first pairs', and nothing reads what it wrote).
+    __device__ __forceinline__ void await_gone() const {
+      poll<1>(gone(), 0, kClaimedPolls);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
   };
   // What the helper wavefront knows of its lane: the matrix element and the Cholesky parameter it owns (make_ctx).
-  // cholesky_param's view of its images: A() is the helper's own, Bm() the trial's.
+  // Its view of the images: A() and V() are its own, Bm() is the trial's (cholesky_param leaves L there).
   struct CtxH {
     int l, i, j, e, pi, pj, pkind;
-    cd *image, *factor;
+    cd *image, *second, *factor;
+    const int* verdict;
     __device__ __forceinline__ cd* A() const { return image; }
     __device__ __forceinline__ cd* Bm() const { return factor; }
-    __device__ __forceinline__ cd* V() const { return nullptr; }  // (the speculative inverse is not the helper's)
+    __device__ __forceinline__ cd* V() const { return second; }
+    // lift_single_negative on speculation: the word is loaded with a batch of LDS reads the lift issues anyway and
+    // looked at behind them, so a look costs an issue slot and a scalar compare, not an LDS round trip
+    __device__ __forceinline__ int verdict_load() const {
+      return __hip_atomic_load(verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ static bool abandoned(int v) {
+      v = __builtin_amdgcn_readfirstlane(v);
+      return v != HelperLink::kPending && v != HelperLink::kGo;
+    }
   };
   // What nll_grad<.., LATE> got from the helper: `got` = it came (otherwise x is a finite stand-in and the caller
   // evaluates again from the top), the parameter of this lane, and whether the matrix was positive definite.
@@ -1485,23 +1545,44 @@ struct Small {
     pj = diag ? l : t - (ii * (ii - 1)) / 2;
   }
   __device__ static void helper_wave(const HelperLink& k, cd* L) {
+    helper_work(k, L);
+    HelperLink::publish(k.gone(), 1);
+  }
+  __device__ static void helper_work(const HelperLink& k, cd* L) {
     static_assert(G == 64, "one trial per wavefront");
-    if (HelperLink::template poll<2>(k.task(), HelperLink::kUnset, HelperLink::kHelperPolls) != HelperLink::kSweep) return;
-    if (!HelperLink::claim(k.task(), HelperLink::kClaimed)) return;
+    if (HelperLink::template poll<2>(k.task(), HelperLink::kUnset, HelperLink::kHelperPolls) != HelperLink::kSpec) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    QT_STAMP(0);
     CtxH c;
     c.l = threadIdx.x & 63;
     c.i = c.l / d;
     c.j = c.l % d;
     c.e = c.i * LD + c.j;
     param_owner(c.l, c.pi, c.pj, c.pkind);
-    c.image = k.image();
+    c.image = k.image(0);
+    c.second = k.image(1);
     c.factor = L;
+    c.verdict = k.verdict();
+    cd proj{0.0, 0.0};
+    const bool lifted =
+        __builtin_amdgcn_readfirstlane((int)lift_single_negative(c, c.image[c.e], d - 1, 1e-15, proj, nullptr)) != 0;
+    QT_STAMP(6);
+    // (an abandoned lift finds its kAbort here at the first look)
+    if (HelperLink::template poll<1>(k.verdict(), HelperLink::kPending, HelperLink::kHelperPolls) != HelperLink::kGo) return;
+    QT_STAMP(7);
+    if (!HelperLink::claim(k.verdict(), HelperLink::kGo, HelperLink::kClaimed)) return;
+    if (!lifted) {
+      HelperLink::publish(k.lifted(), HelperLink::kRefused);
+      return;
+    }
+    k.result()[c.e] = proj;
+    HelperLink::publish(k.lifted(), HelperLink::kLifted);
     int ok2;
-    const double x2 = cholesky_param(c, c.image[c.e], ok2);
+    const double x2 = cholesky_param(c, proj, ok2);
     k.x()[c.l] = x2;
     if (c.l == 0) *k.ok() = ok2;  // (wave-uniform: the pivots are read from their lanes)
     HelperLink::publish(k.done(), 1);
+    QT_STAMP(8);
   }
 
   // ---- a7, short cut for exactly ONE negative eigenvalue (lam_1 < 0 < lam_2 <= ...):
@@ -1514,6 +1595,8 @@ struct Small {
   // lam_1 = Tr(A N) < eps, and ||A N - lam_1 N||_F <= 1e-13 ||A||_F.  Returns false (caller runs the
   // Jacobi eigensolver on the untouched input) on a slow ratio, a positive lam, or a failed check.
   // `inverse`: the lane's element of A^{-1} when the caller already has it (cholesky_param<true>, kneg = d - 1).
+  // One function for the trial's wavefront and for the helper wavefront of k_mle_fused_hw, which runs it before anybody
+  // knows whether it is wanted and returns false as soon as C::abandoned says it is not (HelperLink).
   template <class C>
   __device__ static bool lift_single_negative(const C& c, cd r, int kneg, double eps, cd& out,
                                               const cd* inverse = nullptr) {
@@ -1551,6 +1634,7 @@ struct Small {
     for (int k = 1; k <= 7 && !done; ++k) {
       Ai[c.e] = b;
       wave_sync();
+      [[maybe_unused]] const int verdict = c.verdict_load();  // (helper wavefront: ahead of the reads below, looked at behind them)
       cd n{0.0, 0.0}, n2{0.0, 0.0};  // even / odd terms: two dependency chains per component
 #pragma unroll
       for (int q = 0; q < d; q += 2) {
@@ -1565,10 +1649,14 @@ struct Small {
       }
       n = cadd(n, n2);
       wave_sync();
+      if (c.abandoned(verdict)) return false;  // helper wavefront: the trial has no use for this lift
       const double pur = gsum<G>(n.re * n.re + n.im * n.im);
       b = cscale(n, fast_rsqrt(pur));
       const double defect = 1.0 - pur;  // ~ 2 (sigma_2 / sigma_1)^(2^(k+1))
       QT_STAMP_VAL(20, k);
+#ifdef QT_PHASE_TIMING
+      if (k <= 5) QT_STAMP(25 + k);
+#endif
       if (certified) done = true;
       else if (defect < 1e-7) certified = true;
       else if (k == 3 && !(defect < 0.05)) return false;  // ratio > ~0.8: the eigensolver is cheaper
@@ -1604,9 +1692,11 @@ struct Small {
   // definite (its Cholesky factorisation runs through) no eigenvalue is below the clip, so
   // U max(v, 1e-15) U^dagger is the input itself (to rounding) and only the trace division is left.
   // Returns the projected element; if `xl` is non-null also the Cholesky parameter of the result.
-  // C::kHelper (k_mle_fused_hw): the trial's helper wavefront is told the class as soon as it is known, and a lifted
-  // trial leaves its second factorisation to it: the projected matrix comes back with c.link->pending set, *xl and
-  // *ok_out are not written (HelperLink::collect has them later) and *lscale_out = 1.
+  // C::kHelper (k_mle_fused_hw; SPEC is off there): the trial's helper wavefront, which has been lifting `r` on
+  // speculation since before the sweep, is told the verdict as soon as it is known.  One negative pivot, the last: the
+  // lifted matrix is the helper's, and so is its factorisation: it comes back with c.link->pending set, *xl and
+  // *ok_out are not written (HelperLink::collect has them later) and *lscale_out = 1.  Every other class runs as
+  // without a helper, on this wave.
   template <bool SPEC = false, class C>
   __device__ static cd make_feasible(const C& c, cd r, double* xl, int* ok_out, double* lscale_out = nullptr) {
     int ok, neg, kneg;
@@ -1628,32 +1718,38 @@ struct Small {
     // One trial per wave: `ok` is wave-uniform and a clipped trial replaces all of it, so it is formed only for the
     // trials that keep it.  Several trials per wave: the groups differ, every lane runs it ahead of the branch.
     const bool all_pd = __all(ok);
+    [[maybe_unused]] bool go = false;
     if constexpr (C::kHelper) {
-      if (all_pd) c.link->none();
+      go = kLiftSingleNegative && !all_pd && __builtin_amdgcn_readfirstlane(neg) == 1 &&
+           __builtin_amdgcn_readfirstlane(kneg) == d - 1;
+      c.link->decide(go);
     }
     if (G < 64 || all_pd || (!xl && lscale_out)) pd_epilogue();
     if (!all_pd) {
       cd proj;
       bool lifted = false;
+      [[maybe_unused]] bool refused = false;  // by the helper: the same arithmetic on this wave would refuse again
+      if constexpr (C::kHelper) {
+        if (go) {
+          const int came = c.link->await_lift(c.e, proj);
+          QT_STAMP(31);
+          if (came == HelperLink::kLifted) {
+            QT_STAMP(6);
+            if (lscale_out) *lscale_out = 1.0;
+            return proj;
+          }
+          refused = came == HelperLink::kRefused;
+        }
+      }
       if constexpr (G == 64) {  // one trial per wave: neg / kneg are the same in every lane
-        if (kLiftSingleNegative && __builtin_amdgcn_readfirstlane(neg) == 1) {
+        if (kLiftSingleNegative && !refused && __builtin_amdgcn_readfirstlane(neg) == 1) {
           const int kn = __builtin_amdgcn_readfirstlane(kneg);
           lifted = __builtin_amdgcn_readfirstlane(
                        (int)lift_single_negative(c, r, kn, 1e-15, proj, SPEC && kn == d - 1 ? &spec_inv : nullptr)) != 0;
         }
       }
-      if constexpr (C::kHelper) {
-        if (!lifted) c.link->none();  // the Jacobi path, or the short cut refused
-      }
       if (!lifted) proj = psd_project(c, r, 1e-15);  // whole wave runs it; PD trials keep their shortcut
       QT_STAMP(6);
-      if constexpr (C::kHelper) {
-        if (lifted) {
-          c.link->give(c.e, proj);
-          if (lscale_out) *lscale_out = 1.0;
-          return proj;
-        }
-      }
       int ok2 = 1;
       double x2 = xl ? cholesky_param(c, proj, ok2) : 0.0;
       if (lifted && xl && !__all(ok2 || ok)) {
@@ -2405,8 +2501,10 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     double bl;
     lin = S::lin_invert(c, bl);
     QT_STAMP(2);
-    // one wave per SIMD (HW: beside a helper that sleeps): speculative inverse (cholesky_param)
-    sp.rho = S::template make_feasible<true>(c, lin, &xk, &ok, &sp.lscale);
+    // one wave per SIMD: the speculative inverse rides along in the sweep (cholesky_param<SPEC>); HW: the helper
+    // wavefront speculates, through the whole lift, and the sweep here is the plain one
+    if constexpr (HW) link.speculate(c.e, lin);
+    sp.rho = S::template make_feasible<!HW>(c, lin, &xk, &ok, &sp.lscale);
   } else {
     sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
     sp.lscale = 1.0;
@@ -2419,7 +2517,7 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   bool evaluate = true;
   if constexpr (HW) {
     if (__builtin_amdgcn_readfirstlane(link.pending)) {
-      // the front of the evaluation beside the helper's factorisation of sp.rho; x arrives where Tr is formed
+      // the front of the evaluation beside the helper's factorisation of sp.rho (its lift); x arrives where Tr is formed
       if constexpr (GENERIC) S::template nll_grad<false, decltype(c), true>(c, 0.0, fk, gk, &rho_l, true, &sp);
       else S::template nll_grad<true, decltype(c), true>(c, 0.0, fk, gk, &rho_l, true, &sp, &dv);
       xk = late.x;
@@ -2472,6 +2570,7 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   }
   // n = 3: two-loop form, the first kFusedLdsPairs (s, y) pairs in LDS (the 64 x 64 inverse Hessian took 128 VGPRs per lane
   // and ~460 AGPR moves per iteration); n = 1, 2: the 4 / 16-entry Hessian rows stay in registers
+  if constexpr (HW) link.await_gone();  // the hand-off region is the front of the LDS pair store
   if constexpr (NQ == 3)
     bfgs_iterate_2l<NQ, kFusedLdsPairs>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out,
                                               status_out, pairs);

@@ -158,7 +158,8 @@ struct qt_handle {
   bool mle_specialise = true;
   bool image_ready = false;    // pr_image holds the table image of the current POVM (built when both tables are paired)
   bool last_mle_spec = false;  // which instantiation the last MLE launch took (qt_get_mle_specialised)
-  // qt_set_option(QT_OPT_MLE_HELPER_WAVE): let the one-launch 'lin' start at n = 3 run k_mle_fused_hw (a helper wavefront per trial)
+  // qt_set_option(QT_OPT_MLE_HELPER_WAVE): let the one-launch 'lin' start at n = 3 run k_mle_fused_hw (a helper wavefront
+  // per trial, which runs the single-negative lift on speculation and a lifted trial's second Cholesky sweep)
   bool mle_helper_wave = true;
   bool last_mle_helper = false;  // whether the last MLE launch was k_mle_fused_hw (qt_get_mle_helper_wave)
   // The shape the specialised kernels are compiled for (qt::SpecArgs): three two-outcome settings per qubit (R1 = 6,

@@ -185,8 +185,9 @@ class Engine:
         six-projector shape where the POVM has it, see `mle_specialised`; the same bits either way),
         _capi.QT_OPT_LIFP_DIST_SLICE (processes per slice of `lifp_dist`; 0 = the library's 128 MB bound),
         _capi.QT_OPT_MLE_HELPER_WAVE (n = 3, one-launch `mle` / `mle_dist` from the 'lin' start: 1 = a helper wavefront
-        per trial factorises a clipped trial's projected matrix beside its first evaluation, 0 = the kernel without
-        helpers, see `mle_helper_wave`; the same bits either way)."""
+        per trial clips the linear-inversion matrix on speculation beside the first Cholesky sweep and factorises the
+        result beside the first evaluation, 0 = the kernel without helpers, see `mle_helper_wave`; the same bits either
+        way)."""
         self._chk(self.lib.qt_set_option(self._h, int(option), float(value)))
 
     @property

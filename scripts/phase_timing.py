@@ -26,18 +26,26 @@ eng = qp.get_engine(n, device=0)
 eng.set_povm(povm, shots)
 cd_ = torch.from_numpy(counts).cuda()
 out = torch.empty((B, d, d), dtype=torch.complex128, device="cuda")
-prof = torch.zeros((B + 8, 32), dtype=torch.int64, device="cuda")
+ROWS = B + 8  # one per trial wavefront (whole workgroups); k_mle_fused_hw's helper wavefronts stamp the rows behind them
+prof = torch.zeros((2 * ROWS, 32), dtype=torch.int64, device="cuda")
 eng.lib.qt_debug_set_prof.argtypes = [ctypes.c_void_p]
 assert eng.lib.qt_debug_set_prof(prof.data_ptr()) == 0
 names = {0: "start", 1: "load_freq", 2: "lin_invert", 3: "cholesky #1", 4: "gauss-jordan inverse", 5: "squarings",
          6: "lift tail / jacobi", 7: "cholesky #2", 8: "make_feasible end", 9: "nll_grad end + gnorm", 10: "store",
          11: "(nll) entry", 12: "(nll) build L L^H", 13: "(nll) bloch_of", 14: "(nll) fwd stages 1..n-1",
          15: "(nll) stage n + log", 16: "(nll) backward stages", 17: "(nll) matrix_of", 18: "(nll) Gt L + tail", 19: "deferred value",
-         25: "(nll) wait for helper"}
+         25: "(nll) wait for helper", 31: "wait for the lifted matrix"}
 # 9 closes the first evaluation and its gradient norm; 19 is stamped only by the waves that form the deferred value
 # (a trial that iterates, a caller that asks for `fun`, a p outside the logarithm's regular range); 25 only by the
-# clipped trials of k_mle_fused_hw, whose "cholesky #2" runs in the helper wavefront (the helpers stamp nothing)
-ORDER = [1, 2, 3, 4, 5, 6, 7, 8, 11, 12, 13, 14, 15, 16, 17, 25, 18, 9, 19, 10]
+# clipped trials of k_mle_fused_hw, whose lift and "cholesky #2" run in the helper wavefront; 31 closes their wait for
+# the lifted matrix, which starts at the verdict behind "cholesky #1"
+ORDER = [1, 2, 3, 31, 4, 5, 6, 7, 8, 11, 12, 13, 14, 15, 16, 17, 25, 18, 9, 19, 10]
+# A helper wavefront's stamps, in clocks since ITS TRIAL's start: slot 0 = the speculation starts (the matrix is there),
+# 4 = inverse done, 26 .. 30 = squarings 1 .. 5, 5 = squarings done, 6 = lift over (tail done, refused or called off),
+# 7 = verdict "go" seen, 8 = second sweep done and published
+HELPER = [(0, "speculation starts"), (4, "inverse done"), (26, "squaring 1"), (27, "squaring 2"), (28, "squaring 3"),
+          (29, "squaring 4"), (30, "squaring 5"), (5, "squarings done"), (6, "lift over"), (7, "verdict go seen"),
+          (8, "sweep done")]
 
 
 def mle(helper):
@@ -54,13 +62,16 @@ for name, fn in (("k_lin_batch", lambda: eng.lin_dev(cd_, out, physical=True)), 
     eng.timer_begin()
     fn()
     ms = eng.timer_end()
-    p = prof.cpu().numpy()[:B]
+    both = prof.cpu().numpy()
+    # the helpers' rows start behind the rows of the whole grid: B rounded up to whole workgroups of four trials
+    p, ph = both[:B], both[(B + 3) // 4 * 4:][:B]
     span = (p.max(1) - p[:, 0])
     nonpd = p[:, 6] > 0
     print(f"== {name}: {ms * 1e3:.1f} us for {B} trials; slowest wave {span.max()} clk, {nonpd.sum()} non-PD trials")
     if nonpd.any():
-        ks = p[nonpd, 20]
-        sq = p[nonpd, 5] - p[nonpd, 4]
+        src = ph if ph[nonpd, 20].any() else p  # k_mle_fused_hw: the squarings run in the helper wavefronts
+        ks = src[nonpd, 20]
+        sq = src[nonpd, 5] - src[nonpd, 4]
         for k in np.unique(ks):
             print(f"  squarings = {k}: {np.sum(ks == k)} waves, phase mean {sq[ks == k].mean():.0f} max {sq[ks == k].max()} clk")
     for label, sel in (("PD trials", ~nonpd), ("non-PD trials", nonpd)):
@@ -77,3 +88,18 @@ for name, fn in (("k_lin_batch", lambda: eng.lin_dev(cd_, out, physical=True)), 
             dt = (cur - prev)[have]
             print(f"    {names[s]:24s} mean {dt.mean():8.0f}  max {dt.max():8.0f} clk  ({have.sum()} waves)")
             prev = np.where(have, cur, prev)
+    if ph.any():
+        for label, sel in (("PD trials", ~nonpd), ("non-PD trials", nonpd)):
+            print(f"  helper wavefronts of the {label} (clocks since the trial's start):")
+            for slot, what in HELPER:
+                have = sel & (ph[:, slot] > 0)
+                if have.any():
+                    at = (ph[:, slot] - p[:, 0])[have]
+                    print(f"    {what:24s} mean {at.mean():8.0f}  max {at.max():8.0f} clk  ({have.sum()} waves)")
+        # the trial's stamps on the same scale, for the clipped trials: verdict, matrix received, helper's x received
+        for slot, what in ((2, "lin_invert done"), (3, "verdict (cholesky #1 done)"), (31, "lifted matrix received"),
+                           (17, "front of nll_grad done"), (25, "helper's x received")):
+            have = nonpd & (p[:, slot] > 0)
+            if have.any():
+                at = (p[:, slot] - p[:, 0])[have]
+                print(f"  trial wavefront, non-PD: {what:28s} mean {at.mean():8.0f}  max {at.max():8.0f} clk")
