@@ -89,9 +89,11 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
  * workspaces that follow the batch stay bounded; 0, or more than 128 MB of Choi matrices (2048 processes at n = 3,
  * 32 768 at n = 2), takes that bound.  The same bits whatever the slice.
  * QT_OPT_MLE_HELPER_WAVE (default 1): at n = 3 the one-launch MLE from the 'lin' start (product POVM, batches within
- * QT_OPT_MLE_FUSED_MAX_WAVES) gives every trial a helper wavefront, which lifts the trial's linear-inversion matrix
- * on speculation beside the first Cholesky sweep and, where the sweep asks for the lift, hands the clipped matrix over
- * and factorises it beside the first evaluation; 0 launches the kernel without helpers.  Both give the same bits. */
+ * QT_OPT_MLE_FUSED_MAX_WAVES) gives every trial a twin wavefront, which reads the trial's counts itself, forms the same
+ * linear-inversion matrix and lifts it on speculation beside the first Cholesky sweep; where the sweep asks for the
+ * lift, the twin keeps the clipped matrix and goes on as the trial (evaluation, outputs, BFGS loop) while the first
+ * wavefront factorises that matrix for it.  The launch keeps 16 instead of 24 BFGS pairs per trial in LDS, and where
+ * its layout does not fit a CU's LDS the kernel without twins runs; 0 launches that kernel.  Both give the same bits. */
 enum qt_option {
   QT_OPT_SHOTS_CHECK = 1,
   QT_OPT_MLE_FUSED_MAX_WAVES = 2,

@@ -413,6 +413,13 @@ struct Small {
   __host__ __device__ static size_t lds_bytes(int M, int R1 = 0, int extra = 0) {
     return ((size_t)table_doubles(M, R1) + (size_t)TPB * (trial_doubles(M, R1) + extra)) * sizeof(double);
   }
+  // k_mle_fused_hw: behind that, one more scratch (without `extra`) per trial, for its twin wavefront
+  __host__ __device__ static int twin_offset(int M, int R1, int extra) {
+    return table_doubles(M, R1) + TPB * (trial_doubles(M, R1) + extra);
+  }
+  __host__ __device__ static size_t lds_bytes_twin(int M, int R1, int extra) {
+    return lds_bytes(M, R1, extra) + (size_t)TPB * trial_doubles(M, R1) * sizeof(double);
+  }
 
   // ---- per-lane context ---------------------------------------------------------------
   struct Ctx {
@@ -526,7 +533,10 @@ struct Small {
     return b;
   }
 
-  __device__ static void make_ctx(Ctx& c, double* smem_block, const PovmView& pv) {
+  // TWIN (k_mle_fused_hw): the workgroup has a second wavefront per trial (`twin` != 0, wave-uniform), which comes
+  // through here like the first, leaves the staging of the tables to it, and gets a scratch of its own (twin_offset).
+  template <bool TWIN = false>
+  __device__ static void make_ctx(Ctx& c, double* smem_block, const PovmView& pv, [[maybe_unused]] int twin = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     c.l = lane % G;
     const int slot = wave * TPW + lane / G;
@@ -548,26 +558,29 @@ struct Small {
     c.ptab = t1 + 4 * r1;
     if (r1 > 0) {  // every thread of the workgroup comes through here once, before anything else
       const int nf = fwd_ints(r1), nb = bwd_ints(r1);
-      for (int e = threadIdx.x; e < 4 * r1; e += NT) {
-        t1[e] = pv.pr.T[e];
-        t1[4 * r1 + e] = pv.pr.P1T[e];
-      }
-      // paired tables index their stages in closed form: only stage n of the forward pass keeps a table (M <= nf
-      // entries, in the place of the forward tables)
-      if (pv.pr.pairedT) {
-        for (int e = threadIdx.x; e < pv.M; e += NT) tabs[e] = pv.pr.last[e];
-      } else {
-        for (int e = threadIdx.x; e < nf; e += NT) tabs[e] = pv.pr.fwd[e];
-      }
-      if (!(pv.pr.pairedT && pv.pr.pairedP))
-        for (int e = threadIdx.x; e < nb; e += NT) tabs[nf + e] = pv.pr.bwd[e];
-      for (int e = threadIdx.x; e < pv.M; e += NT) {
-        tabs[nf + nb + e] = pv.pr.rmap[e];
-        wrow[e] = pv.pr.wrowR[e];
+      if (!(TWIN && twin)) {
+        for (int e = threadIdx.x; e < 4 * r1; e += NT) {
+          t1[e] = pv.pr.T[e];
+          t1[4 * r1 + e] = pv.pr.P1T[e];
+        }
+        // paired tables index their stages in closed form: only stage n of the forward pass keeps a table (M <= nf
+        // entries, in the place of the forward tables)
+        if (pv.pr.pairedT) {
+          for (int e = threadIdx.x; e < pv.M; e += NT) tabs[e] = pv.pr.last[e];
+        } else {
+          for (int e = threadIdx.x; e < nf; e += NT) tabs[e] = pv.pr.fwd[e];
+        }
+        if (!(pv.pr.pairedT && pv.pr.pairedP))
+          for (int e = threadIdx.x; e < nb; e += NT) tabs[nf + e] = pv.pr.bwd[e];
+        for (int e = threadIdx.x; e < pv.M; e += NT) {
+          tabs[nf + nb + e] = pv.pr.rmap[e];
+          wrow[e] = pv.pr.wrowR[e];
+        }
       }
       __syncthreads();
     }
     c.sm = smem_block + table_doubles(pv.M, r1) + slot * (trial_doubles(pv.M, r1) + pv.extra);
+    if (TWIN && twin) c.sm = smem_block + twin_offset(pv.M, r1, pv.extra) + slot * trial_doubles(pv.M, r1);
     int xm = 0, zm = 0, ny = 0;
 #pragma unroll
     for (int b = 0; b < NQ; ++b) {
@@ -850,8 +863,9 @@ struct Small {
       pf.ns[q] = a.Ns[mc >> NQ];  // K = d outcomes per setting
     }
   }
-  template <bool VCOEF = false>
-  __device__ static void make_ctx(CtxS& c, double* smem_block, const SpecArgs& a, const Prefetch& pf) {
+  template <bool VCOEF = false, bool TWIN = false>
+  __device__ static void make_ctx(CtxS& c, double* smem_block, const SpecArgs& a, const Prefetch& pf,
+                                  [[maybe_unused]] int twin = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     c.l = lane % G;
     const int slot = wave * TPW + lane / G;
@@ -861,11 +875,12 @@ struct Small {
     c.M = a.M;
     c.Mp = (a.M + 1) & ~1;
     c.a = a;
-    if ((int)threadIdx.x < image_chunks(a.M)) reinterpret_cast<uint4*>(smem_block)[threadIdx.x] = pf.img;
+    if (!(TWIN && twin) && (int)threadIdx.x < image_chunks(a.M)) reinterpret_cast<uint4*>(smem_block)[threadIdx.x] = pf.img;
     c.tfwd = reinterpret_cast<const int*>(smem_block);
     c.ttab = smem_block + image_last_ints(a.M) / 2;
     c.ptab = c.ttab + 24;
     c.sm = smem_block + table_doubles(a.M, 6) + slot * (trial_doubles(a.M, 6) + a.extra);
+    if (TWIN && twin) c.sm = smem_block + twin_offset(a.M, 6, a.extra) + slot * trial_doubles(a.M, 6);
     if (c.l == 0) c.sm[oVec + D] = 0.0;
     __syncthreads();
     // lane constants, without loops or branches
@@ -1376,51 +1391,61 @@ struct Small {
     return x;
   }
 
-  // ---- k_mle_fused_hw (n = 3): the hand-off between a trial's wavefront and its helper wavefront on the same SIMD.
+  // ---- k_mle_fused_hw (n = 3): the hand-off between a trial's wavefront and its twin wavefront on the same SIMD.
   // Between lin_invert and the lifted matrix a clipped trial is one serial chain (first Cholesky sweep, Gauss-Jordan
   // inverse, squarings, certificate), and nothing of the lift needs the sweep except the knowledge that the lift is
-  // wanted.  So the helper runs lift_single_negative in natural pivot order on EVERY trial, speculatively, from the
-  // moment the linear-inversion matrix exists, while the trial's wave runs the plain sweep; the verdict of the sweep
-  // then lets the helper go on or sends it home.  After "go" the helper hands the lifted matrix over and runs the
-  // second Cholesky sweep of it while the trial's wave runs the front of the first nll_grad on it (the two are
-  // independent).  Everything goes through the first doubles of the trial's LDS pair store (bfgs_iterate_2l's `lp`,
-  // which nothing touches before the BFGS loop): the helper's two images, the parameters it returns and the words
-  // below.  Data first, then the flag: release stores and acquire loads at workgroup scope, no workgroup barrier --
-  // the four trials of a workgroup stay uncoupled.  Every wait is a counted loop; whoever runs out of polls leaves:
-  //   trial:  `task` = kSpec with its matrix in image(0), as soon as lin_invert is done.  After its sweep, `verdict`:
+  // wanted.  So the twin (the "helper" below) runs lift_single_negative in natural pivot order on EVERY trial,
+  // speculatively, while the trial's wave runs the plain sweep; the verdict of the sweep then lets it go on or sends
+  // it home.  The twin is given nothing: it reads the trial's counts itself and runs load_freq and lin_invert on a
+  // scratch of its own (behind the scratches of the workgroup's four trials), so the matrix it lifts is in its own
+  // registers, bit for bit the trial's, at the moment the trial's sweep starts, and the lift's two images are the A()
+  // and V() of that scratch.  After "go" the twin KEEPS the lifted matrix in its registers and goes on as the trial --
+  // first evaluation, outputs, BFGS loop, all on its own context -- and the wave on threadIdx.y = 0 becomes the
+  // helper: it receives the matrix and runs the second Cholesky sweep of it (L into the twin's Bm()) while the twin
+  // runs the front of the first nll_grad (the two are independent).  One wave owns a trial's outputs; the
+  // compare-and-swap on `verdict` decides which (strictly so as long as no count runs out: see await_lift for the
+  // one branch behind a claimed verdict where both waves would go on as the trial).  In the names and comments of
+  // HelperLink, "the trial's wave" is the wave on threadIdx.y = 0 up to kLifted and the twin behind it, and "the
+  // helper" is the other one: the role swaps with the ownership.  What crosses between the waves goes through the first doubles of the
+  // trial's LDS pair store (bfgs_iterate_2l's `lp`, which nothing touches before the BFGS loop): the lifted matrix,
+  // the parameters of the sweep and the words below.
+  // Data first, then the flag: release stores and acquire loads at workgroup scope, no workgroup barrier besides the
+  // one of make_ctx -- the four trials of a workgroup stay uncoupled.  Every wait is a counted loop; whoever runs out
+  // of polls leaves:
+  //   trial:  after its sweep, `verdict`:
   //           kAbort (positive definite: it never waits; or a class the natural-order lift does not serve: wrong
   //           pivot, several negative pivots -- today's serial code on its own wave) or kGo (one negative pivot, the
-  //           last).  After kGo it polls `lifted`: kLifted -> the matrix is in result(), the front of the evaluation
-  //           runs on it and collect() has x and ok behind it; kRefused -> the eigensolver on its own wave (the lift on
-  //           its own wave would refuse with the same bits).  Out of polls: it takes the verdict back (compare-and-swap
-  //           kGo -> kRevoked: a helper that has not claimed it never will) and runs the serial path.  If the helper
-  //           had claimed it, the helper is inside straight-line code that waits for nobody, and a second, much longer
-  //           count covers that many times over.
-  //   helper: polls `task`; on kSpec runs the lift on its own images, looking at `verdict` once per squaring
-  //           (CtxH::abandoned) and leaving on anything but "none yet" or kGo.  At the end it waits for the verdict,
-  //           claims kGo (-> kClaimed), publishes kRefused and leaves, or the matrix and kLifted; then the sweep (L
-  //           into the trial's Bm(), which the front of an evaluation with a StartPoint does not touch), x, ok, done.
-  //           During the speculation it writes nothing outside this region.  Wherever it leaves, `gone` = 1 is its last
-  //           write: the trial's wave acquires it before the BFGS loop writes the first pair over this region.
+  //           last).  After kGo it polls `lifted`: kLifted -> the matrix is in result() and the trial is the twin's:
+  //           this wave runs sweep_for (second sweep, L into the twin's Bm(), which the front of an evaluation with a
+  //           StartPoint does not touch; x, ok, done), publishes `gone` and leaves without writing an output;
+  //           kRefused -> it stays the trial and runs the eigensolver on its own wave (the lift on its own wave would
+  //           refuse with the same bits).  Out of polls: it takes the verdict back (compare-and-swap kGo -> kRevoked: a
+  //           twin that has not claimed it never will) and runs the serial path.  If the twin had claimed it, the twin
+  //           is inside straight-line code that waits for nobody, and a second, much longer count covers that many
+  //           times over.
+  //   twin:   runs the lift on its own images, looking at `verdict` once per squaring (CtxH::abandoned) and leaving on
+  //           anything but "none yet" or kGo.  At the end it waits for the verdict, claims kGo (-> kClaimed), publishes
+  //           kRefused and leaves, or the matrix and kLifted (twin_lift); then it is the trial: nll_grad<.., LATE> with
+  //           collect() behind the front, and if x does not come or ok = 0, today's fallbacks on its own wave and its
+  //           own `lin`.  Before that it writes nothing outside its own scratch.
+  //   `gone` = 1 is the last write of whichever wave leaves; the wave that owns the trial acquires it before the BFGS
+  //   loop writes the first pair over this region.
   struct HelperLink {
-    enum : int { kUnset = 0, kSpec = 1 };                                    // task
     enum : int { kPending = 0, kGo = 1, kAbort = 2, kClaimed = 3, kRevoked = 4 };  // verdict
     enum : int { kNothing = 0, kLifted = 1, kRefused = 2 };                  // lifted
     // polls (each an LDS read and an s_sleep): the helper's waits cover the longest path to the verdict (~20 k clocks)
     // several hundred times, the trial's first wait the helper's ~11 k-clock chain likewise
     static constexpr int kHelperPolls = 1 << 15, kWaitPolls = 1 << 14, kClaimedPolls = 1 << 16;
-    double* base;  // [2][MAT] images, [D] x, then the words
-    int pending;   // trial's wave: the lifted matrix came from the helper, which is factorising it (wave-uniform)
-    __device__ __forceinline__ static constexpr int doubles() { return 2 * MAT + D + 3; }
-    __device__ __forceinline__ cd* image(int k) const { return reinterpret_cast<cd*>(base + k * MAT); }
-    __device__ __forceinline__ cd* result() const { return image(1); }  // (the lift's second image is free by then)
-    __device__ __forceinline__ double* x() const { return base + 2 * MAT; }
-    __device__ __forceinline__ int* task() const { return reinterpret_cast<int*>(base + 2 * MAT + D); }
-    __device__ __forceinline__ int* verdict() const { return task() + 1; }
-    __device__ __forceinline__ int* lifted() const { return task() + 2; }
-    __device__ __forceinline__ int* done() const { return task() + 3; }
-    __device__ __forceinline__ int* gone() const { return task() + 4; }
-    __device__ __forceinline__ int* ok() const { return task() + 5; }
+    double* base;  // [MAT] the lifted matrix, [D] x, then the words
+    int pending;   // the lifted matrix is the twin's: the twin evaluates it, the other wave factorises it (wave-uniform)
+    __device__ __forceinline__ static constexpr int doubles() { return MAT + D + 3; }
+    __device__ __forceinline__ cd* result() const { return reinterpret_cast<cd*>(base); }
+    __device__ __forceinline__ double* x() const { return base + MAT; }
+    __device__ __forceinline__ int* verdict() const { return reinterpret_cast<int*>(base + MAT + D); }
+    __device__ __forceinline__ int* lifted() const { return verdict() + 1; }
+    __device__ __forceinline__ int* done() const { return verdict() + 2; }
+    __device__ __forceinline__ int* gone() const { return verdict() + 3; }
+    __device__ __forceinline__ int* ok() const { return verdict() + 4; }
     __device__ __forceinline__ static void publish(int* w, int v) {  // after this wave's data writes
       wave_sync();
       if ((threadIdx.x & 63) == 0) __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1448,25 +1473,25 @@ struct Small {
       }
       return v;
     }
-    // trial's wave, before the workgroup barrier of make_ctx
+    // trial's wave, before the workgroup barrier of make_ctx (every launch sets its words up: nothing is left over)
     __device__ __forceinline__ void reset() {
       pending = 0;
       if ((threadIdx.x & 63) == 0) {
-        *task() = kUnset;
         *verdict() = kPending;
         *lifted() = kNothing;
         *done() = 0;
         *gone() = 0;
       }
     }
-    __device__ __forceinline__ void speculate(int e, cd lin) const {
-      image(0)[e] = lin;
-      publish(task(), kSpec);
-    }
     __device__ __forceinline__ void decide(bool go) const { publish(verdict(), go ? kGo : kAbort); }
     // trial's wave, after decide(true): kLifted = this lane's element of the lifted matrix is in `proj` and the helper
     // is factorising it; kRefused = the lift ran and declined; kNothing = nothing came and nothing will (or, after a
-    // claimed verdict and the long count, the helper has stopped making progress)
+    // claimed verdict and the long count, the helper has stopped making progress).  That last case is the one place
+    // where ownership rests on a bounded wait and not on the compare-and-swap: the twin has claimed and, if it is still
+    // alive, will publish kLifted and go on as the trial while this wave runs the serial path as the trial too; both
+    // would then write the trial's outputs and pairs (the same values, but unsynchronised).  The twin's stretch between
+    // its claim and its publish is a store and a release, set against 2^16 polls; as with await_gone, a twin that has
+    // not answered by then has stopped making progress.  No test forces it.
     __device__ __forceinline__ int await_lift(int e, cd& proj) {
       int v = poll<1>(lifted(), kNothing, kWaitPolls);
       if (v == kNothing) {
@@ -1499,8 +1524,8 @@ struct Small {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
   };
-  // What the helper wavefront knows of its lane: the matrix element and the Cholesky parameter it owns (make_ctx).
-  // Its view of the images: A() and V() are its own, Bm() is the trial's (cholesky_param leaves L there).
+  // The twin's view of the images behind lin_invert: A() and V() are those of its own scratch, Bm() is the trial's
+  // (cholesky_param leaves L there).  The lane constants are those of its trial context (make_ctx).
   struct CtxH {
     int l, i, j, e, pi, pj, pkind;
     cd *image, *second, *factor;
@@ -1529,7 +1554,9 @@ struct Small {
   template <class Base>
   struct WithHelper : Base {
     HelperLink* link;
-    LateX* late;  // nll_grad<.., LATE>
+    LateX* late;    // nll_grad<.., LATE>
+    double* xtra;   // the trial's `extra` doubles: behind the trial's scratch, for the twin too (whose own scratch has none)
+    __device__ __forceinline__ double* extra() const { return xtra; }
     static constexpr bool kHelper = true;
   };
   __device__ __forceinline__ static void param_owner(int l, int& pi, int& pj, int& pkind) {
@@ -1544,45 +1571,56 @@ struct Small {
     pi = diag ? l : ii;
     pj = diag ? l : t - (ii * (ii - 1)) / 2;
   }
-  __device__ static void helper_wave(const HelperLink& k, cd* L) {
-    helper_work(k, L);
-    HelperLink::publish(k.gone(), 1);
-  }
-  __device__ static void helper_work(const HelperLink& k, cd* L) {
+  // The twin behind lin_invert: `t` its own trial context, `lin` its own linear-inversion matrix.  True: it has lifted,
+  // claimed the verdict and published the lifted matrix, whose element of this lane is `proj` -- from here on it IS the
+  // trial (it holds the counts' frequencies, the context and the matrix) and the wave on threadIdx.y = 0 is its helper
+  // (sweep_for).  False: it leaves, and the caller publishes `gone`.
+  template <class C>
+  __device__ static bool twin_lift(const C& t, const HelperLink& k, cd lin, cd& proj) {
     static_assert(G == 64, "one trial per wavefront");
-    if (HelperLink::template poll<2>(k.task(), HelperLink::kUnset, HelperLink::kHelperPolls) != HelperLink::kSpec) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    QT_STAMP(0);
-    CtxH c;
-    c.l = threadIdx.x & 63;
-    c.i = c.l / d;
-    c.j = c.l % d;
-    c.e = c.i * LD + c.j;
-    param_owner(c.l, c.pi, c.pj, c.pkind);
-    c.image = k.image(0);
-    c.second = k.image(1);
-    c.factor = L;
-    c.verdict = k.verdict();
-    cd proj{0.0, 0.0};
-    const bool lifted =
-        __builtin_amdgcn_readfirstlane((int)lift_single_negative(c, c.image[c.e], d - 1, 1e-15, proj, nullptr)) != 0;
+    CtxH c = side_ctx(t, k, t.Bm());
+    proj = cd{0.0, 0.0};
+    const bool lifted = __builtin_amdgcn_readfirstlane((int)lift_single_negative(c, lin, d - 1, 1e-15, proj, nullptr)) != 0;
     QT_STAMP(6);
     // (an abandoned lift finds its kAbort here at the first look)
-    if (HelperLink::template poll<1>(k.verdict(), HelperLink::kPending, HelperLink::kHelperPolls) != HelperLink::kGo) return;
+    if (HelperLink::template poll<1>(k.verdict(), HelperLink::kPending, HelperLink::kHelperPolls) != HelperLink::kGo) return false;
     QT_STAMP(7);
-    if (!HelperLink::claim(k.verdict(), HelperLink::kGo, HelperLink::kClaimed)) return;
+    if (!HelperLink::claim(k.verdict(), HelperLink::kGo, HelperLink::kClaimed)) return false;
     if (!lifted) {
       HelperLink::publish(k.lifted(), HelperLink::kRefused);
-      return;
+      return false;
     }
     k.result()[c.e] = proj;
     HelperLink::publish(k.lifted(), HelperLink::kLifted);
+    return true;
+  }
+  // The wave on threadIdx.y = 0 after kLifted: the second Cholesky sweep of the lifted matrix, on its own A(), with L
+  // going into the twin's Bm() `L` (the front of the twin's evaluation does not touch it); then x, ok, done.
+  template <class C>
+  __device__ static void sweep_for(const C& t, const HelperLink& k, cd proj, cd* L) {
+    CtxH c = side_ctx(t, k, L);
     int ok2;
     const double x2 = cholesky_param(c, proj, ok2);
     k.x()[c.l] = x2;
     if (c.l == 0) *k.ok() = ok2;  // (wave-uniform: the pivots are read from their lanes)
     HelperLink::publish(k.done(), 1);
-    QT_STAMP(8);
+    QT_STAMP(7);
+  }
+  template <class C>
+  __device__ __forceinline__ static CtxH side_ctx(const C& t, const HelperLink& k, cd* L) {
+    CtxH c;
+    c.l = t.l;
+    c.i = t.i;
+    c.j = t.j;
+    c.e = t.e;
+    c.pi = t.pi;
+    c.pj = t.pj;
+    c.pkind = t.pkind;
+    c.image = t.A();
+    c.second = t.V();
+    c.factor = L;
+    c.verdict = k.verdict();
+    return c;
   }
 
   // ---- a7, short cut for exactly ONE negative eigenvalue (lam_1 < 0 < lam_2 <= ...):
@@ -2440,13 +2478,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFG
 }
 
 constexpr int kFusedLdsPairs = 24;  // (s, y) pairs of k_mle_fused<3> kept in LDS: 24 KB per trial, 4 trials per workgroup
+// ... and of k_mle_fused_hw<3>, whose workgroup also holds a scratch per twin wavefront: 16 KB per trial.  (Where a pair
+// lives changes no bit of the iteration.)
+constexpr int kFusedHwLdsPairs = 16;
 
 // a10 in ONE launch, for batches small enough that its 256-VGPR footprint (two waves per SIMD) is no
 // handicap: start point, first evaluation and -- for the waves that still hold an open trial -- the BFGS
 // loop.  Saves the second launch (2.5-4 us when nothing iterates, ~10 % of a 1000-trial step).
 // HW (k_mle_fused_hw, n = 3, 'lin' start): launched with blocks of 256 x 2 threads.  threadIdx.y = 0 are the four
-// trial wavefronts, exactly as without HW; threadIdx.y = 1 are their helpers (Small::HelperLink), wavefront 4 + t on
-// the SIMD of wavefront t and with the same threadIdx.x, hence the same trial and the same LDS slot.
+// trial wavefronts, exactly as without HW; threadIdx.y = 1 are their twins (Small::HelperLink), wavefront 4 + t on
+// the SIMD of wavefront t and with the same threadIdx.x, hence the same trial.  A twin runs the same prologue on the
+// same counts with a scratch of its own (make_ctx<.., TWIN>) and parts from the trial's wave behind lin_invert.
 template <int NQ, bool GENERIC, bool HW = false>
 __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::type& pv, const int64_t* __restrict__ counts, int B, int init,
                                                int max_iter, double gtol, EstOut rho,
@@ -2460,21 +2502,25 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   std::conditional_t<HW, typename S::template WithHelper<Ctx>, Ctx> c;
   [[maybe_unused]] typename S::HelperLink link;
   [[maybe_unused]] typename S::LateX late{false, 0.0, 0};
+  [[maybe_unused]] int twin = 0;               // HW: this wavefront is a twin (wave-uniform)
+  [[maybe_unused]] double* trial_sm = nullptr;  // HW: the scratch of the trial (a twin's own is c.sm)
   if constexpr (HW) {
     static_assert(NQ == 3, "one trial per wavefront");
-    static_assert(S::HelperLink::doubles() <= kFusedLdsPairs * 2 * D, "the hand-off lives in the LDS pair store");
+    static_assert(S::HelperLink::doubles() <= kFusedHwLdsPairs * 2 * D, "the hand-off lives in the LDS pair store");
     int r1 = 6;  // the product POVM's one-qubit rows (the generic body is launched with HW only for a product POVM)
     if constexpr (GENERIC) r1 = pv.pr.R1;
     const int per_trial = S::trial_doubles(pv.M, r1);
-    double* sm = smem + S::table_doubles(pv.M, r1) + (threadIdx.x >> 6) * (per_trial + pv.extra);
-    link.base = sm + per_trial + LineSearch::SLOTS + 2 * max_iter;  // bfgs_iterate_2l's `lp`
-    if (__builtin_amdgcn_readfirstlane((int)threadIdx.y) != 0) {
-      __syncthreads();  // the workgroup barrier of make_ctx, behind which `task` and `done` are set up
-      S::helper_wave(link, reinterpret_cast<cd*>(sm + S::oB));
-      return;
-    }
-    link.reset();
+    trial_sm = smem + S::table_doubles(pv.M, r1) + (threadIdx.x >> 6) * (per_trial + pv.extra);
+    link.base = trial_sm + per_trial + LineSearch::SLOTS + 2 * max_iter;  // bfgs_iterate_2l's `lp`
+    twin = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
+    link.pending = 0;
+    if (!twin) link.reset();  // (in front of the workgroup barrier of make_ctx: the twin finds its words set up)
+    // The twin is the younger wave of its SIMD and loses the arbitration by age, and it carries the chain the launch
+    // waits for (a clipped trial's prologue, lift and evaluation); the older wave has thousands of clocks to spare in
+    // every class.  Once, for the whole kernel.  (Measured: profiles/mle_twin_wave_headline_ab.txt.)
+    if (twin) __builtin_amdgcn_s_setprio(1);
     c.link = &link;
+    c.xtra = trial_sm + per_trial;
     c.late = &late;
   }
   bool live;
@@ -2484,11 +2530,11 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
   bool shots_ok;
   if constexpr (GENERIC) {
-    S::make_ctx(c, smem, pv);
+    S::template make_ctx<HW>(c, smem, pv, twin);
     QT_STAMP(0);
     shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
   } else {
-    S::template make_ctx<true>(c, smem, pv, pf);
+    S::template make_ctx<true, HW>(c, smem, pv, pf, twin);
     QT_STAMP(0);
     shots_ok = S::load_freq(c, pf);
   }
@@ -2501,10 +2547,33 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     double bl;
     lin = S::lin_invert(c, bl);
     QT_STAMP(2);
-    // one wave per SIMD: the speculative inverse rides along in the sweep (cholesky_param<SPEC>); HW: the helper
-    // wavefront speculates, through the whole lift, and the sweep here is the plain one
-    if constexpr (HW) link.speculate(c.e, lin);
-    sp.rho = S::template make_feasible<!HW>(c, lin, &xk, &ok, &sp.lscale);
+    // one wave per SIMD: the speculative inverse rides along in the sweep (cholesky_param<SPEC>); HW: the twin
+    // wavefront, which holds the same `lin`, speculates, through the whole lift, and the sweep here is the plain one
+    bool feasible = false;
+    if constexpr (HW) {
+      if (twin) {
+        // lifted, claimed and published: the matrix stays in these registers and this wave goes on as the trial
+        if (!S::twin_lift(c, link, lin, sp.rho)) {
+          S::HelperLink::publish(link.gone(), 1);
+          return;
+        }
+        sp.lscale = 1.0;
+        link.pending = 1;
+        feasible = true;
+      }
+    }
+    if (!feasible) sp.rho = S::template make_feasible<!HW>(c, lin, &xk, &ok, &sp.lscale);
+    if constexpr (HW) {
+      if (!twin && __builtin_amdgcn_readfirstlane(link.pending)) {
+        // the twin owns the trial from here: factorise its matrix for it and leave, writing no output
+        int r1 = 6;
+        if constexpr (GENERIC) r1 = pv.pr.R1;
+        double* twin_sm = smem + S::twin_offset(pv.M, r1, pv.extra) + (threadIdx.x >> 6) * S::trial_doubles(pv.M, r1);
+        S::sweep_for(c, link, sp.rho, reinterpret_cast<cd*>(twin_sm + S::oB));
+        S::HelperLink::publish(link.gone(), 1);
+        return;
+      }
+    }
   } else {
     sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
     sp.lscale = 1.0;
@@ -2572,7 +2641,7 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   // and ~460 AGPR moves per iteration); n = 1, 2: the 4 / 16-entry Hessian rows stay in registers
   if constexpr (HW) link.await_gone();  // the hand-off region is the front of the LDS pair store
   if constexpr (NQ == 3)
-    bfgs_iterate_2l<NQ, kFusedLdsPairs>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out,
+    bfgs_iterate_2l<NQ, HW ? kFusedHwLdsPairs : kFusedLdsPairs>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out,
                                               status_out, pairs);
   else
     bfgs_iterate<NQ>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
@@ -2597,8 +2666,9 @@ __global__ void __launch_bounds__(256) k_mle_fused_mixed(typename MleArgs<GENERI
   mle_fused_body<NQ, GENERIC>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 
-// The 'lin' start with a helper wavefront per trial (mle_fused_body<.., HW>): blocks of 256 x 2 threads, the grid and
-// the LDS layout of k_mle_fused.  Two waves per SIMD: the 256 registers of the body are what a wave can have.
+// The 'lin' start with a twin wavefront per trial (mle_fused_body<.., HW>): blocks of 256 x 2 threads, the grid of
+// k_mle_fused, its LDS layout with kFusedHwLdsPairs pairs and the twins' scratches behind it (Small::lds_bytes_twin).
+// Two waves per SIMD: the 256 registers of the body are what a wave can have.
 template <int NQ, bool GENERIC>
 __global__ void __launch_bounds__(512) k_mle_fused_hw(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
                                                       double gtol, EstOut rho, int32_t* __restrict__ nit_out,

@@ -734,19 +734,28 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
       constexpr int TPW = qt::Small<NQ>::TPW;
       if ((B + TPW - 1) / TPW <= h->fused_max_waves && !(NQ == 3 && max_iter > 256)) {
         int extra = 0;
+        bool helper = false;
+        size_t lds_hw = 0;  // k_mle_fused_hw's dynamic LDS: computed once, for the fit check and for the launch
         if (NQ == 3) {  // two-loop BFGS: line-search state, rho_i, alpha_i and the first pairs in LDS, later pairs in global
-          extra = qt::LineSearch::SLOTS + 2 * mi + qt::kFusedLdsPairs * 2 * h->D;
-          const int over = mi > qt::kFusedLdsPairs ? mi : 1;  // (indexed by pair number: rows below kFusedLdsPairs stay unused)
+          const int state = qt::LineSearch::SLOTS + 2 * mi;
+          // k_mle_fused_hw (the generic body meets its twins at the barrier behind the product POVM's tables) keeps fewer
+          // pairs in LDS and a scratch per twin wavefront behind the trials'; where that does not fit, k_mle_fused runs
+          const int extra_hw = state + qt::kFusedHwLdsPairs * 2 * h->D;
+          lds_hw = qt::Small<3>::lds_bytes_twin(h->M, h->prod.R1, extra_hw);
+          helper = h->mle_helper_wave && init == QT_INIT_LIN && h->prod.enabled && lds_hw <= kLdsLimit;
+          const int lds_pairs = helper ? qt::kFusedHwLdsPairs : qt::kFusedLdsPairs;
+          extra = state + lds_pairs * 2 * h->D;
+          const int over = mi > lds_pairs ? mi : 1;  // (indexed by pair number: rows below lds_pairs stay unused)
           HIPCHK(h->hess.ensure((size_t)B * over * 2 * h->D * sizeof(double)));
         }
         Plan p = povm_plan<NQ>(h, B, extra);
         auto fused = [&](auto generic) {
           constexpr bool GEN = decltype(generic)::value;
           if constexpr (NQ == 3) {
-            // the generic body meets its helpers at the barrier behind the product POVM's tables
-            if (h->mle_helper_wave && init == QT_INIT_LIN && p.pv.pr.enabled) {
+            if (helper) {
               h->last_mle_helper = true;
-              p.block = dim3(qt::Small<NQ>::NT, 2);  // y = 1: the helper wavefronts
+              p.block = dim3(qt::Small<NQ>::NT, 2);  // y = 1: the twin wavefronts
+              p.lds = lds_hw;
               return launch(h, qt::k_mle_fused_hw<NQ, GEN>, p, mle_povm_arg<GEN>(h, p), dc, B, max_iter, tol, eo, dnit, dnfev,
                             dfun, dst, h->hess.as<double>());
             }

@@ -26,7 +26,7 @@ eng = qp.get_engine(n, device=0)
 eng.set_povm(povm, shots)
 cd_ = torch.from_numpy(counts).cuda()
 out = torch.empty((B, d, d), dtype=torch.complex128, device="cuda")
-ROWS = B + 8  # one per trial wavefront (whole workgroups); k_mle_fused_hw's helper wavefronts stamp the rows behind them
+ROWS = B + 8  # one per trial wavefront (whole workgroups); k_mle_fused_hw's twin wavefronts stamp the rows behind them
 prof = torch.zeros((2 * ROWS, 32), dtype=torch.int64, device="cuda")
 eng.lib.qt_debug_set_prof.argtypes = [ctypes.c_void_p]
 assert eng.lib.qt_debug_set_prof(prof.data_ptr()) == 0
@@ -36,16 +36,20 @@ names = {0: "start", 1: "load_freq", 2: "lin_invert", 3: "cholesky #1", 4: "gaus
          15: "(nll) stage n + log", 16: "(nll) backward stages", 17: "(nll) matrix_of", 18: "(nll) Gt L + tail", 19: "deferred value",
          25: "(nll) wait for helper", 31: "wait for the lifted matrix"}
 # 9 closes the first evaluation and its gradient norm; 19 is stamped only by the waves that form the deferred value
-# (a trial that iterates, a caller that asks for `fun`, a p outside the logarithm's regular range); 25 only by the
-# clipped trials of k_mle_fused_hw, whose lift and "cholesky #2" run in the helper wavefront; 31 closes their wait for
-# the lifted matrix, which starts at the verdict behind "cholesky #1"
+# (a trial that iterates, a caller that asks for `fun`, a p outside the logarithm's regular range).  k_mle_fused_hw:
+# a clipped trial's first wave stamps 31 when the lifted matrix has arrived (its wait starts at the verdict behind
+# "cholesky #1") and 7 when its sweep for the twin is done; everything behind that is in the twin's row (HELPER below)
 ORDER = [1, 2, 3, 31, 4, 5, 6, 7, 8, 11, 12, 13, 14, 15, 16, 17, 25, 18, 9, 19, 10]
-# A helper wavefront's stamps, in clocks since ITS TRIAL's start: slot 0 = the speculation starts (the matrix is there),
-# 4 = inverse done, 26 .. 30 = squarings 1 .. 5, 5 = squarings done, 6 = lift over (tail done, refused or called off),
-# 7 = verdict "go" seen, 8 = second sweep done and published
-HELPER = [(0, "speculation starts"), (4, "inverse done"), (26, "squaring 1"), (27, "squaring 2"), (28, "squaring 3"),
+# A twin wavefront's stamps, in clocks since ITS TRIAL's start: slot 0 = its own start (behind the barrier of make_ctx),
+# 1 = its load_freq done, 2 = its lin_invert done: the inverse starts (the matrix is in its registers), 4 = inverse done,
+# 26 .. 30 = squarings 1 .. 5, 5 = squarings done, 6 = lift over (tail done, refused or called off), 7 = verdict "go"
+# seen, 8 = lifted matrix published: from here the twin owns the trial and stamps the trial's slots (17 front of
+# nll_grad, 25 x received from the other wave, 18, 9, 10) in its own row.  The second sweep's end is slot 7 of the FIRST
+# wave's row (sweep_for).
+HELPER = [(0, "twin starts"), (1, "own load_freq done"), (2, "own lin_invert done"), (4, "inverse done"), (26, "squaring 1"), (27, "squaring 2"), (28, "squaring 3"),
           (29, "squaring 4"), (30, "squaring 5"), (5, "squarings done"), (6, "lift over"), (7, "verdict go seen"),
-          (8, "sweep done")]
+          (8, "matrix published, owns the trial"), (17, "front of nll_grad done"), (25, "x received"), (18, "nll_grad done"),
+          (9, "gnorm"), (10, "store")]
 
 
 def mle(helper):
@@ -90,16 +94,18 @@ for name, fn in (("k_lin_batch", lambda: eng.lin_dev(cd_, out, physical=True)), 
             prev = np.where(have, cur, prev)
     if ph.any():
         for label, sel in (("PD trials", ~nonpd), ("non-PD trials", nonpd)):
-            print(f"  helper wavefronts of the {label} (clocks since the trial's start):")
+            print(f"  twin wavefronts of the {label} (clocks since the trial's start):")
             for slot, what in HELPER:
                 have = sel & (ph[:, slot] > 0)
                 if have.any():
                     at = (ph[:, slot] - p[:, 0])[have]
                     print(f"    {what:24s} mean {at.mean():8.0f}  max {at.max():8.0f} clk  ({have.sum()} waves)")
-        # the trial's stamps on the same scale, for the clipped trials: verdict, matrix received, helper's x received
+        # the trial's stamps on the same scale, for the clipped trials: verdict, matrix received, sweep for the twin done
         for slot, what in ((2, "lin_invert done"), (3, "verdict (cholesky #1 done)"), (31, "lifted matrix received"),
-                           (17, "front of nll_grad done"), (25, "helper's x received")):
+                           (7, "sweep for the twin done")):
             have = nonpd & (p[:, slot] > 0)
             if have.any():
                 at = (p[:, slot] - p[:, 0])[have]
                 print(f"  trial wavefront, non-PD: {what:28s} mean {at.mean():8.0f}  max {at.max():8.0f} clk")
+        owns = ph[:, 10] > 0
+        print(f"  {owns.sum()} twins own their trial's outputs; slowest of them {(ph[owns].max(1) - p[owns, 0]).max() if owns.any() else 0} clk")
