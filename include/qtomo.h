@@ -211,6 +211,23 @@ int qt_mle_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int init, in
                       const double* centre, double* rho, double* dist, int32_t* nit, int32_t* nfev, double* fun,
                       int32_t* status, int flags);
 
+/* ---- the bootstrap coverage study, quantpy/metrics.py:125-144 (get_CL_list_state with interval='boot'): every trial t of
+ * the study resamples around ITS OWN point estimate, so a batch of resamples has a centre per trial ----------------------
+ * qt_lin_dist_batch / qt_mle_dist_batch with a table centres[G][d][d][2]: dist[b] = hs_dst(estimate_b, centres[b % G]).
+ * The batch is resample-major, counts[r * G + t] = resample r of trial t -- the order qt_device_multinomial writes with
+ * period = G * S and the Born probabilities of the G estimates as pvals.  G >= 1 (else QT_ERR_ARG); G = 1 is
+ * qt_lin_dist_batch / qt_mle_dist_batch.  Everything else -- rho NULLABLE, the outputs, status -- as in those. */
+int qt_lin_dist_group_batch(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centres, int G,
+                            double* rho, double* dist, int32_t* status, int flags);
+int qt_mle_dist_group_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol,
+                            const double* centres, int G, double* rho, double* dist, int32_t* nit, int32_t* nfev,
+                            double* fun, int32_t* status, int flags);
+/* metrics.py:140-144, `np.where(delta > distances)` for every trial of a chunk of whole resamples: dist[B] as the two
+ * entries above write it (B = R * G, else QT_ERR_ARG), thresholds[G] = delta_t;  hits[g] += #{ r : thresholds[g] >
+ * dist[r * G + g] }, int64.  The comparison is strict, so a NaN distance never counts.  `hits` ACCUMULATES (zero it before
+ * the first chunk): integer adds, so the totals do not depend on how the resamples are chunked. */
+int qt_group_hits(qt_handle_t* h, const double* dist, int B, int G, const double* thresholds, int64_t* hits, int flags);
+
 /* ---- a16: quantpy/geometry.py:5-20 hs_dst --------------------------------------------------- */
 /* dist[b] = sqrt(|Tr((rho_b - centre)^2)|) / sqrt(2), set to 0 below 1e-15 */
 int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, int B, double* dist, int flags);

@@ -6,7 +6,7 @@ StateTomograph / ProcessTomograph / Bootstrap*Interval whose estimators are HIP 
 libqtomo.so (include/qtomo.h).  There is no CPU estimator: without the library or a GPU the
 estimators raise `EngineUnavailable`.
 """
-from . import basis, channel, engine, operator, qobj  # noqa: F401
+from . import basis, channel, engine, metrics, operator, qobj  # noqa: F401
 from ._capi import EngineUnavailable  # noqa: F401
 from .base_quantum import BaseQuantum  # noqa: F401
 from .channel import Channel  # noqa: F401

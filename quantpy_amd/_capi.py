@@ -59,6 +59,10 @@ SIGNATURES = {
     "qt_mle_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _vp, _c_int]),
     "qt_mle_dist_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int]),
     "qt_mhmc_state": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_dbl, _vp, _vp, _c_int]),
+    "qt_lin_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_int]),
+    "qt_mle_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _c_int]),
+    "qt_group_hits": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _c_int]),
     "qt_hs_dist_batch": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_hs_dist_dim": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_sort_f64": (_c_int, [_vp, _vp, ctypes.c_longlong, _c_int]),

@@ -147,7 +147,7 @@ struct Large {
   // which no estimator reads after its last build_llh).  Called by every thread of the workgroup.
   __device__ static void emit(const Ctx& c, const EstOut& o, int b, cd r) {
     if (o.dist) {  // uniform over the launch
-      const double2 cc = *reinterpret_cast<const double2*>(o.centre + 2 * c.t);
+      const double2 cc = *reinterpret_cast<const double2*>(o.centre_of(b, 2 * D) + 2 * c.t);
       const cd dl{r.re - cc.x, r.im - cc.y};
       cd* L = c.L();
       __syncthreads();

@@ -568,6 +568,35 @@ __global__ void __launch_bounds__(64) k_hs_dist(int d, const double* __restrict_
   }
 }
 
+// ---- the counting step of the bootstrap coverage study: metrics.py:140-144, `np.where(delta > distances)` per trial ----
+// dist[R][G] (resample-major, as the grouped estimators write it), thr[G]:  hits[g] += #{ r : thr[g] > dist[r][g] }.  The
+// comparison is strict and IEEE, so a NaN distance (or threshold) never counts.
+// A workgroup reads tiles of rp rows x cw columns (cw = min(G, 256), rp = 256 / cw): consecutive threads read consecutive
+// doubles of a row -- and of the following rows where G < 256, so that a small G still fills the loads -- and blockIdx.y
+// takes slices of `rows` rows each, so that a large R with a small G still fills the device.  Every thread counts one
+// column in a register, the rp counts of a column meet in LDS, and one 64-bit atomic add per column and workgroup goes to
+// `hits`: integer adds, the same result in whatever order, and `hits` keeps accumulating over the caller's chunks.
+__global__ void __launch_bounds__(256) k_group_hits(const double* __restrict__ dist, int R, int G, int rows,
+                                                    const double* __restrict__ thr, unsigned long long* __restrict__ hits) {
+  __shared__ unsigned long long part[256];
+  const int cw = G < 256 ? G : 256, rp = 256 / cw;
+  const int t = threadIdx.x, col = blockIdx.x * cw + t % cw, r_off = t / cw;
+  const long long r0 = (long long)blockIdx.y * rows;
+  const long long r1 = r0 + rows < R ? r0 + rows : R;
+  unsigned long long n = 0;
+  if (r_off < rp && col < G) {
+    const double th = thr[col];
+    for (long long r = r0 + r_off; r < r1; r += rp) n += th > dist[(size_t)r * G + col] ? 1 : 0;
+  }
+  part[t] = n;
+  __syncthreads();
+  if (t < cw && col < G) {
+    unsigned long long s = 0;
+    for (int k = 0; k < rp; ++k) s += part[k * cw + t];
+    if (s) atomicAdd(hits + col, s);
+  }
+}
+
 // ---- the one sort key of the order-statistics path: np.sort's order ---------------------------------------------------
 // Order-preserving 64-bit key (sign-flipped IEEE bits) of the CANONICAL value: -0.0 gets +0.0's key, and every NaN,
 // whatever its sign and payload, the key of the quiet NaN 0x7ff8000000000000, 0xfff8000000000000: above +inf's

@@ -345,10 +345,21 @@ __device__ __forceinline__ bool shots_match(double t_s, double total, double n_s
 // Where an estimator leaves a trial's result: the density matrix and / or -- the body of the bootstrap loop,
 // interval.py:600-609, `dist[i] = dst(point_estimate(...), state)` -- its Hilbert-Schmidt distance (geometry.py:16-20) to
 // `centre`.  With `dist` set and `rho` null a resample costs 8 bytes of HBM writes instead of 16 d^2 and no second pass.
+// A table of G centres serves the nested bootstrap of the coverage study (metrics.py:125-144), where every trial of the
+// study has its own point estimate: the batch is then [resample][trial] and trial b is measured against centre (g0 + b) % G
+// (g0: the group of the launch's first trial, for a launch that starts inside the batch).  G == 1 is the single centre and
+// takes no modulo.
 struct EstOut {
   double* rho;           // [B][d][d][2], or nullptr when only the distance is wanted
-  const double* centre;  // [d][d][2], read when dist != nullptr
+  const double* centre;  // [G][d][d][2], read when dist != nullptr
   double* dist;          // [B], or nullptr
+  int G = 1;             // centres in the table (launch-uniform)
+  int g0 = 0;            // group of trial 0 of this launch, < G
+  // The centre of trial b, dd doubles each.  Reduced for every b >= 0, so the lane groups that pad the last workgroup
+  // (b >= B, stores masked) read inside the table too.
+  __device__ __forceinline__ const double* centre_of(int b, int dd) const {
+    return G > 1 ? centre + (size_t)((unsigned)(g0 + b) % (unsigned)G) * dd : centre;
+  }
 };
 
 template <int NQ>
@@ -1979,7 +1990,7 @@ struct Small {
   template <class C>
   __device__ __forceinline__ static void emit(const C& c, const EstOut& o, int b, bool store, cd r) {
     if (o.dist) {
-      const double v = hs_to_centre(c, r, o.centre);
+      const double v = hs_to_centre(c, r, o.centre_of(b, 2 * D));  // b: this lane group's trial
       if (store && c.l == 0) o.dist[b] = v;
     }
     if (store && o.rho) {

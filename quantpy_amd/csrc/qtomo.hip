@@ -74,7 +74,7 @@ struct DevBuf {
   }
 };
 
-constexpr int kStageBufs = 8;  // arrays one host-pointer call may stage (qt_mle_batch: counts, centre and six outputs)
+constexpr int kStageBufs = 8;  // arrays one host-pointer call may stage (qt_mle_batch: counts, centres and six outputs)
 
 // What qt_process_setup keeps of the design matrix L (rows vec(rho_s (x) E_m^T)).  n <= 2 keeps it dense (`lifp` ..
 // `pinvR`); n = 3 keeps only the left inverses of its Kronecker factors (qt_process64.h: `factored`); n = 2 builds those
@@ -628,13 +628,14 @@ int check_pvals(int period, int K, const int64_t* n, const double* pvals) {
   return 0;
 }
 
-// a6 + a7 (+ a16 when `dist` is asked for): one body behind qt_lin_batch and qt_lin_dist_batch
-int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centre, double* rho,
+// a6 + a7 (+ a16 when `dist` is asked for): one body behind qt_lin_batch, qt_lin_dist_batch and qt_lin_dist_group_batch.
+// `centre` holds G matrices; trial b is measured against centre b % G (qt::EstOut).
+int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centre, int G, double* rho,
                    double* dist, double* bloch_out, int32_t* status, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
   if (int r = need_povm(h)) return r;
-  if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad lin_batch arguments");
+  if (B < 0 || G < 1 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad lin_batch arguments");
   if (B == 0) return 0;
   const int64_t* dc;
   const double* dcen;
@@ -642,12 +643,12 @@ int lin_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int physical, c
   int32_t* dst;
   const size_t nel = (size_t)B * h->D;
   if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
-  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
+  if (int r = c.in(centre, (size_t)G * h->D * 2, &dcen)) return r;
   if (int r = c.out(rho, nel * 2, &drho)) return r;
   if (int r = c.out(bloch_out, nel, &dbl)) return r;
   if (int r = c.out(status, (size_t)B, &dst)) return r;
   if (int r = c.out(dist, (size_t)B, &ddist)) return r;
-  const qt::EstOut eo{drho, dcen, ddist};
+  const qt::EstOut eo{drho, dcen, ddist, G, 0};
   if (h->nq >= 4)
     if (int r = prepare_large(h, true)) return r;
   if (int r = by_nq(h, [&](auto nq) {
@@ -672,7 +673,8 @@ struct MleArrays {
   int M, D;
   MleArrays at(int b0) const {
     auto off = [b0](auto* p, size_t per) { return p ? p + (size_t)b0 * per : p; };
-    return {off(counts, M), {off(eo.rho, 2 * D), eo.centre, off(eo.dist, 1)}, off(nit, 1), off(nfev, 1), off(fun, 1),
+    return {off(counts, M), {off(eo.rho, 2 * D), eo.centre, off(eo.dist, 1), eo.G, (int)((eo.g0 + (long long)b0) % eo.G)},
+            off(nit, 1), off(nfev, 1), off(fun, 1),
             off(status, 1), off(x, D), off(g, D), off(f, 1), off(act, 1), M, D};
   }
 };
@@ -691,13 +693,14 @@ auto mle_povm_arg(const qt_handle_t* h, const Plan& p) {
   else return h->spec_args(p.pv.extra);
 }
 
-// a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch and qt_mle_dist_batch
-int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, const double* centre,
+// a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch, qt_mle_dist_batch and qt_mle_dist_group_batch.
+// `centre` holds G matrices; trial b is measured against centre b % G (qt::EstOut).
+int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, const double* centre, int G,
                    double* rho, double* dist, int32_t* nit, int32_t* nfev, double* fun, int32_t* status, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
   if (int r = need_povm(h)) return r;
-  if (B < 0 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad mle_batch arguments");
+  if (B < 0 || G < 1 || (B > 0 && (!counts || (!rho && !dist) || (dist && !centre)))) return fail(QT_ERR_ARG, "bad mle_batch arguments");
   if (init != QT_INIT_LIN && init != QT_INIT_MIXED) return fail(QT_ERR_ARG, "init must be QT_INIT_LIN or QT_INIT_MIXED");
   if (max_iter < 0) return fail(QT_ERR_ARG, "max_iter < 0");
   if (B == 0) return 0;
@@ -707,14 +710,14 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
   int32_t *dnit, *dnfev, *dst;
   const size_t nel = (size_t)B * h->D;
   if (int r = c.in(counts, (size_t)B * h->M, &dc)) return r;
-  if (int r = c.in(centre, (size_t)h->D * 2, &dcen)) return r;
+  if (int r = c.in(centre, (size_t)G * h->D * 2, &dcen)) return r;
   if (int r = c.out(rho, nel * 2, &drho)) return r;
   if (int r = c.out(nit, (size_t)B, &dnit)) return r;
   if (int r = c.out(nfev, (size_t)B, &dnfev)) return r;
   if (int r = c.out(fun, (size_t)B, &dfun)) return r;
   if (int r = c.out(status, (size_t)B, &dst)) return r;
   if (int r = c.out(dist, (size_t)B, &ddist)) return r;
-  const qt::EstOut eo{drho, dcen, ddist};
+  const qt::EstOut eo{drho, dcen, ddist, G, 0};
   if (h->nq >= 4) {
     if (int r = prepare_large(h, init == QT_INIT_LIN)) return r;
     if (max_iter > 4096) return fail(QT_ERR_UNSUPPORTED, "max_iter > 4096 is not supported for n_qubits >= 4");
@@ -1554,13 +1557,19 @@ int qt_mat_from_bloch(qt_handle_t* h, const double* bloch, int B, double* mat, i
 int qt_lin_batch(qt_handle_t* h, const int64_t* counts, int B, int physical, double* rho, double* bloch_out,
                  int32_t* status, int flags) {
   if (B > 0 && !rho) return fail(QT_ERR_ARG, "bad lin_batch arguments");
-  return lin_batch_impl(h, counts, B, physical, nullptr, rho, nullptr, bloch_out, status, flags);
+  return lin_batch_impl(h, counts, B, physical, nullptr, 1, rho, nullptr, bloch_out, status, flags);
 }
 
 int qt_lin_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centre, double* rho,
                       double* dist, int32_t* status, int flags) {
   if (B > 0 && (!dist || !centre)) return fail(QT_ERR_ARG, "bad lin_dist_batch arguments");
-  return lin_batch_impl(h, counts, B, physical, centre, rho, dist, nullptr, status, flags);
+  return lin_batch_impl(h, counts, B, physical, centre, 1, rho, dist, nullptr, status, flags);
+}
+
+int qt_lin_dist_group_batch(qt_handle_t* h, const int64_t* counts, int B, int physical, const double* centres, int G,
+                            double* rho, double* dist, int32_t* status, int flags) {
+  if (G < 1 || (B > 0 && (!dist || !centres))) return fail(QT_ERR_ARG, "bad lin_dist_group_batch arguments");
+  return lin_batch_impl(h, counts, B, physical, centres, G, rho, dist, nullptr, status, flags);
 }
 
 int qt_chol_param(qt_handle_t* h, const double* rho, int B, double* x, int32_t* status, int flags) {
@@ -1661,14 +1670,46 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
                  int32_t* nit, int32_t* nfev, double* fun, int32_t* status, int flags) {
   if (B > 0 && !rho) return fail(QT_ERR_ARG, "bad mle_batch arguments");
-  return mle_batch_impl(h, counts, B, init, max_iter, tol, nullptr, rho, nullptr, nit, nfev, fun, status, flags);
+  return mle_batch_impl(h, counts, B, init, max_iter, tol, nullptr, 1, rho, nullptr, nit, nfev, fun, status, flags);
 }
 
 int qt_mle_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol,
                       const double* centre, double* rho, double* dist, int32_t* nit, int32_t* nfev, double* fun,
                       int32_t* status, int flags) {
   if (B > 0 && (!dist || !centre)) return fail(QT_ERR_ARG, "bad mle_dist_batch arguments");
-  return mle_batch_impl(h, counts, B, init, max_iter, tol, centre, rho, dist, nit, nfev, fun, status, flags);
+  return mle_batch_impl(h, counts, B, init, max_iter, tol, centre, 1, rho, dist, nit, nfev, fun, status, flags);
+}
+
+int qt_mle_dist_group_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol,
+                            const double* centres, int G, double* rho, double* dist, int32_t* nit, int32_t* nfev,
+                            double* fun, int32_t* status, int flags) {
+  if (G < 1 || (B > 0 && (!dist || !centres))) return fail(QT_ERR_ARG, "bad mle_dist_group_batch arguments");
+  return mle_batch_impl(h, counts, B, init, max_iter, tol, centres, G, rho, dist, nit, nfev, fun, status, flags);
+}
+
+// metrics.py:140-144 for a chunk of whole resamples: hits[g] += #{ r : thresholds[g] > dist[r][g] } (k_group_hits)
+int qt_group_hits(qt_handle_t* h, const double* dist, int B, int G, const double* thresholds, int64_t* hits, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (B < 0 || G < 1 || B % G != 0 || !thresholds || !hits || (B > 0 && !dist))
+    return fail(QT_ERR_ARG, "bad group_hits arguments (B = %d must be a multiple of G = %d)", B, G);
+  if (B == 0) return 0;
+  const double *dd, *dthr;
+  int64_t* dhits;
+  if (int r = c.in(dist, (size_t)B, &dd)) return r;
+  if (int r = c.in(thresholds, (size_t)G, &dthr)) return r;
+  if (int r = c.inout(hits, (size_t)G, &dhits)) return r;
+  // column tiles of min(G, 256) x slices of rows: about 2048 workgroups at the most, at least eight passes per slice
+  const int R = B / G, cw = G < 256 ? G : 256, rp = 256 / cw, gx = (G + cw - 1) / cw;
+  int slices = 2048 / gx;
+  if (slices < 1) slices = 1;
+  int rows = (R + slices - 1) / slices;
+  if (rows < 8 * rp) rows = 8 * rp;
+  const int gy = (R + rows - 1) / rows;
+  if (int r = launch(h, qt::k_group_hits, dim3(gx, gy), dim3(256), 0, dd, R, G, rows, dthr,
+                     reinterpret_cast<unsigned long long*>(dhits)))
+    return r;
+  return c.done();
 }
 
 int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, int B, double* dist, int flags) {

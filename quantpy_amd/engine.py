@@ -506,8 +506,15 @@ class Engine:
         return dist
 
     def lin_dist_dev(self, counts, centre, dist, physical=True, rho=None, status=None):
-        """device-pointer form: centre complex128 (d, d), dist float64 (B,) torch CUDA tensors; rho optional"""
+        """device-pointer form: centre complex128 (d, d), dist float64 (B,) torch CUDA tensors; rho optional.
+        A centre table (G, d, d) measures trial b against centre[b % G] (qt_lin_dist_group_batch: resample-major batches
+        of the bootstrap coverage study, metrics.get_CL_list_state)."""
         self._dev_call()
+        if centre.dim() == 3:
+            self._chk(self.lib.qt_lin_dist_group_batch(self._h, _ptr(counts), counts.shape[0], int(bool(physical)),
+                                                       _ptr(centre), centre.shape[0], _ptr(rho), _ptr(dist), _ptr(status),
+                                                       _capi.QT_DEVICE_PTR))
+            return
         self._chk(self.lib.qt_lin_dist_batch(self._h, _ptr(counts), counts.shape[0], int(bool(physical)), _ptr(centre),
                                              _ptr(rho), _ptr(dist), _ptr(status), _capi.QT_DEVICE_PTR))
 
@@ -605,7 +612,16 @@ class Engine:
 
     def mle_dist_dev(self, counts, centre, dist, init="lin", max_iter=100, tol=1e-3, rho=None, nit=None, nfev=None,
                      fun=None, status=None):
+        """device-pointer form of mle_dist; a centre table (G, d, d) measures trial b against centre[b % G]
+        (qt_mle_dist_group_batch), as in lin_dist_dev"""
         self._dev_call()
+        if centre.dim() == 3:
+            self._chk(self.lib.qt_mle_dist_group_batch(self._h, _ptr(counts), counts.shape[0],
+                                                       _capi.QT_INIT_LIN if init == "lin" else _capi.QT_INIT_MIXED,
+                                                       int(max_iter), float(tol), _ptr(centre), centre.shape[0], _ptr(rho),
+                                                       _ptr(dist), _ptr(nit), _ptr(nfev), _ptr(fun), _ptr(status),
+                                                       _capi.QT_DEVICE_PTR))
+            return
         self._chk(self.lib.qt_mle_dist_batch(self._h, _ptr(counts), counts.shape[0],
                                              _capi.QT_INIT_LIN if init == "lin" else _capi.QT_INIT_MIXED, int(max_iter),
                                              float(tol), _ptr(centre), _ptr(rho), _ptr(dist), _ptr(nit), _ptr(nfev),
@@ -646,6 +662,23 @@ class Engine:
         self._chk(self.lib.qt_device_multinomial(self._h, seed, first_row, rows, pvals.shape[0], _ptr(n), _ptr(pvals),
                                                  pvals.shape[-1], _ptr(counts), _capi.QT_HOST_PTR))
         return counts
+
+    def group_hits(self, dist, thresholds, hits):
+        """metrics.py:140-144 for a chunk of whole resamples: hits[g] += #{ r : thresholds[g] > dist[r, g] } (qt_group_hits,
+        strict comparison: a NaN distance never counts).  dist float64 (R * G,), thresholds float64 (G,), hits int64 (G,):
+        torch CUDA tensors, or NumPy arrays (`hits` is then updated in place too).  `hits` accumulates over calls."""
+        if _is_dev(dist):
+            self._dev_call()
+            flags = _capi.QT_DEVICE_PTR
+            assert thresholds.is_contiguous() and hits.is_contiguous() and dist.is_contiguous()
+            b, g = dist.numel(), hits.numel()
+        else:
+            flags = _capi.QT_HOST_PTR
+            dist, thresholds = _f64(dist), _f64(thresholds)
+            assert isinstance(hits, np.ndarray) and hits.dtype == np.int64 and hits.flags.c_contiguous
+            b, g = dist.size, hits.size
+        self._chk(self.lib.qt_group_hits(self._h, _ptr(dist), b, g, _ptr(thresholds), _ptr(hits), flags))
+        return hits
 
     def hs_dist_dev(self, rho, centre, out):
         self._dev_call()

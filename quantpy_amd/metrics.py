@@ -1,0 +1,203 @@
+"""Coverage studies of the confidence intervals (reference quantpy/metrics.py:8-147, 150-319).
+
+`get_CL_list_state` / `get_CL_list_channel` run `n_iter` experiments, build an interval for each, read the confidence
+level at which the truth leaves it (metrics.py:140-144) and return the sorted levels: a calibrated interval gives the
+uniform distribution.  The reference states the study as a Python loop over trials (and calls tomograph methods it no
+longer has); here the trials are one batch.
+
+interval='boot' (states, Hilbert-Schmidt distance, method_boot 'lin' / 'mle') is the nested bootstrap: every trial t
+resamples `n_points` times around ITS OWN point estimate.  The resamples are laid out resample-major, row
+(r * n_iter + t) of a chunk = resample r of trial t, which is the order `qt_device_multinomial` writes with
+period = n_iter * S and the Born probabilities of the n_iter estimates as its table; one grouped launch family
+(`qt_lin_dist_group_batch` / `qt_mle_dist_group_batch`: trial b against centre b % n_iter) reconstructs a chunk of whole
+resamples and writes its distances, and `qt_group_hits` adds, per trial, how many of them lie below that trial's distance
+to the truth.  Counts and distances never leave HBM; 8 * n_iter bytes come back.
+
+interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with the same rule.
+"""
+import numpy as np
+
+from . import distributed as qdist
+from .geometry import hs_dst
+from .sampling import SAMPLERS, resolve_seed
+from .tomography.interval import BootstrapProcessInterval, MomentInterval
+from .tomography.process import ProcessTomograph
+from .tomography.state import StateTomograph
+
+_INTERVALS = ("gamma", "boot", "mhmc")
+_CHUNK_BYTES = BootstrapProcessInterval._CHUNK_BYTES  # counts of one chunk of resamples
+
+
+def levels_from_hits(hits, n_points):
+    """metrics.py:140-144 on a sorted raw sample of `n_points` distances with CLs = np.linspace(0, 1, n_points): with
+    hits = #{ i : delta > distances[i] } (the sample is sorted and a NaN, sorted last, is never below delta, so the last
+    such index is hits - 1) the level is CLs[hits - 1], and 0 when nothing lies below delta."""
+    hits = np.asarray(hits, dtype=np.int64)
+    cls = np.linspace(0, 1, n_points)
+    return np.where(hits > 0, cls[np.maximum(hits, 1) - 1], 0.0)
+
+
+def _levels_from_radii(delta, radii, cls):
+    """The same rule on tabulated radii (n_iter, n_points): CLs[last index with delta > radius], else 0."""
+    below = delta[:, None] > radii
+    last = below.shape[1] - 1 - np.argmax(below[:, ::-1], axis=1)
+    return np.where(below.any(axis=1), cls[last], 0.0), below.sum(axis=1)
+
+
+def _check_arguments(interval, dst, n_iter, n_points, sampler, boot_methods, method_boot):
+    if interval not in _INTERVALS:
+        raise ValueError("Incorrect value for argument `interval`.")
+    if interval == "mhmc":
+        raise NotImplementedError("interval='mhmc' (a chain per trial) is not implemented; supported: 'gamma'"
+                                  + (", 'boot'" if boot_methods else ""))
+    if interval == "boot" and not boot_methods:
+        raise NotImplementedError("interval='boot' is not implemented for processes; supported: 'gamma'")
+    if not (dst == "hs" or dst is hs_dst):
+        raise NotImplementedError("only the Hilbert-Schmidt distance (dst='hs') is supported")
+    if interval == "boot" and method_boot not in boot_methods:
+        raise NotImplementedError(f"interval='boot' supports method_boot in {boot_methods}, not {method_boot!r}")
+    if int(n_iter) < 1 or int(n_points) < 1:
+        raise ValueError("n_iter and n_points must be positive")
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, not {sampler!r}")
+
+
+def _shared_seed(seed):
+    """resolve_seed(seed), rank 0's on every rank."""
+    key = resolve_seed(seed)
+    if qdist.world()[1] > 1:
+        key = int(qdist.broadcast_array(np.array([key], dtype=np.uint64).view(np.int64)).view(np.uint64)[0])
+    return key
+
+
+def _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, keyed):
+    """(counts of the n_iter experiments, the resolved seed), the same on every rank: rank 0's stream (sampler='numpy',
+    np.random's in the reference's order; the seed is resolved behind the draws, and only when `keyed` resamples will
+    need it) or rank 0's Philox key (sampler='device')."""
+    if sampler == "device":
+        key = _shared_seed(seed)
+        return tmg.experiment_batch(n_measurements, povm, repeats=n_iter, sampler="device", seed=key), key
+    counts = tmg.experiment_batch(n_measurements, povm, repeats=n_iter)
+    if qdist.world()[1] > 1:
+        counts = qdist.broadcast_array(counts)
+    return counts, (_shared_seed(seed) if keyed else None)
+
+
+def _result(levels, return_details, **details):
+    if return_details:
+        return dict(levels=levels, **details)
+    return np.sort(levels)
+
+
+def get_CL_list_state(state, n_iter=1000, n_points=1000, interval="gamma", n_measurements=1000, method="lin",
+                      method_boot="lin", dst="hs", povm="proj-set", physical=True, init="lin", tol=1e-3, max_iter=100,
+                      step=0.01, burn_steps=1000, thinning=1, verbose=True, *, sampler="device", seed=None, chunk=None,
+                      return_details=False):
+    """Conducts `n_iter` experiments, constructs a confidence interval for each, computes the confidence level that
+    corresponds to the distance between the target state and the point estimate, and returns the sorted levels
+    (reference metrics.py:8-147; parameters as there).
+
+    interval : 'gamma' -- `MomentInterval.radii_batch` at np.linspace(0, 1, n_points);
+               'boot'  -- bootstrap around each trial's point estimate, `n_points` resamples reconstructed with
+               `method_boot` in ('lin', 'mle') (`physical`, `init`, `tol`, `max_iter` as in BootstrapStateInterval), for
+               dst='hs'.  'mhmc', other distances and other `method_boot` raise NotImplementedError.
+    verbose is accepted and ignored: there is no loop to show.
+
+    Keyword-only extensions
+    sampler : 'device' (default) | 'numpy' -- how the TRIAL counts are drawn: on the GPU from Philox streams keyed by
+        `seed`, or on np.random's global stream in the reference's order (`seed` then only keys the resamples).
+    seed : 64-bit key; None takes one from np.random's stream (after the trial counts, with sampler='numpy').
+    chunk : resamples per launch family of 'boot' (default: as many whole resamples as 256 MB of counts hold).
+    return_details : return a dict of per-trial `counts`, `estimates`, `delta`, `hits`, `levels` in TRIAL order and
+        `seed`, the key of the resamples, instead of the sorted levels.
+
+    The resamples of 'boot' always come from the device sampler: trial t's probabilities depend on its estimate, so the
+    nested loop has no reference stream to reproduce.  Keying: Philox key (resolve_seed(seed) + 1) mod 2^64, and row
+    (r * n_iter + t) * S + s for setting s of resample r of trial t (S settings) -- a multinomial(n_measurements[s],
+    clip(born_probs(estimate_t), 0, 1)[s]).  The table therefore depends neither on `chunk` nor on the number of ranks;
+    with several ranks each takes `shard_bounds(n_points)` of the resamples, the hits are summed, and every rank returns
+    the same list.  The level of trial t is np.linspace(0, 1, n_points)[hits_t - 1] (0 when hits_t == 0), hits_t the
+    number of resampled distances strictly below delta_t (`levels_from_hits`)."""
+    _check_arguments(interval, dst, n_iter, n_points, sampler, ("lin", "mle"), method_boot)
+    n_iter, n_points = int(n_iter), int(n_points)
+    tmg = StateTomograph(state, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, interval == "boot")
+    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
+    if info is not None and np.any(info["status"] == 1):
+        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
+    eng = tmg._engine()
+    delta = eng.hs_dist(rho, state.matrix)
+    if interval == "gamma":
+        cls = np.linspace(0, 1, n_points)
+        levels, hits = _levels_from_radii(delta, MomentInterval(tmg).radii_batch(counts, cls), cls)
+        return _result(levels, return_details, counts=counts, estimates=rho, delta=delta, hits=hits, seed=None)
+    key = (base + 1) & (2**64 - 1)
+    hits = _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk)
+    return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
+                   seed=key)
+
+
+def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk):
+    """hits[t] = #{ r < n_points : delta_t > hs_dst(estimate(resample r of trial t), estimate_t) }, this rank's shard of
+    the resamples chunk by chunk on the device, summed over the ranks."""
+    import torch
+
+    from . import _capi
+
+    n_iter = rho.shape[0]
+    n_set, n_out = eng.S, eng.K
+    dev = torch.device("cuda", eng.device)
+    pvals = np.clip(eng.born_probs(eng.bloch_from_matrix(rho)), 0, 1).reshape(n_iter * n_set, n_out)
+    p_d = torch.from_numpy(pvals).to(dev)
+    n_d = torch.from_numpy(np.tile(np.asarray(tmg.n_measurements).astype(np.int64), n_iter)).to(dev)
+    centres = torch.from_numpy(np.ascontiguousarray(rho, dtype=np.complex128)).to(dev)
+    thr = torch.from_numpy(np.ascontiguousarray(delta, dtype=np.float64)).to(dev)
+    hits = torch.zeros(n_iter, dtype=torch.int64, device=dev)
+    per_resample = n_iter * n_set * n_out * 8
+    chunk = int(chunk) if chunk else max(1, _CHUNK_BYTES // per_resample)
+    chunk = max(1, min(chunk, (2**31 - 1) // n_iter))  # the batch size of a launch is a 32-bit int
+    lo, hi = qdist.shard_bounds(n_points)
+    chunk = min(chunk, max(hi - lo, 1))
+    counts = torch.empty((chunk * n_iter, n_set, n_out), dtype=torch.int64, device=dev)
+    dist = torch.empty(chunk * n_iter, dtype=torch.float64, device=dev)
+    status = torch.zeros(chunk * n_iter, dtype=torch.int32, device=dev)
+    bad = torch.zeros(2, dtype=torch.bool, device=dev)
+    for r0 in range(lo, hi, chunk):
+        b = min(chunk, hi - r0) * n_iter
+        eng.device_multinomial(n_d, p_d, b * n_set, key, first_row=r0 * n_iter * n_set, out=counts[:b])
+        if method_boot == "lin":
+            eng.lin_dist_dev(counts[:b], centres, dist[:b], physical=physical, status=status[:b])
+        else:
+            eng.mle_dist_dev(counts[:b], centres, dist[:b], init=init, max_iter=max_iter, tol=tol, status=status[:b])
+        eng.group_hits(dist[:b], thr, hits)
+        bad |= torch.stack([(status[:b] == 1).any(), (status[:b] == _capi.TRIAL_SHOTS).any()])
+    eng.sync()
+    bad = bad.cpu().numpy().astype(np.int64)
+    hits = hits.cpu().numpy()
+    if qdist.world()[1] > 1:  # every rank raises, or none
+        bad = qdist.allgather_equal(bad).max(axis=0)
+        hits = qdist.allgather_equal(hits).sum(0)
+    if bad[0]:
+        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
+    if bad[1]:
+        raise ValueError("per-setting totals of a trial do not match the registered shots")
+    return hits
+
+
+def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n_measurements=1000, method="lifp",
+                        method_boot="lifp", dst="hs", povm="proj-set", input_states="proj4", cptp=True, tol=1e-3,
+                        states_physical=True, states_init="lin", states_est_method="lin", states_est_method_boot="lin",
+                        step=0.01, burn_steps=1000, thinning=1, verbose=True, *, sampler="device", seed=None,
+                        return_details=False):
+    """The same study for a channel and its Choi matrix (reference metrics.py:150-319; parameters as there), for
+    interval='gamma': the process form of `MomentInterval.radii_batch` at np.linspace(0, 1, n_points).  'boot' and
+    'mhmc' raise NotImplementedError.  `sampler`, `seed`, `return_details` as in `get_CL_list_state`."""
+    _check_arguments(interval, dst, n_iter, n_points, sampler, (), method_boot)
+    n_iter, n_points = int(n_iter), int(n_points)
+    tmg = ProcessTomograph(channel, input_states, "hs")
+    counts, _ = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, False)
+    choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
+    delta = tmg._engine().hs_dist(choi, channel.choi.matrix)
+    cls = np.linspace(0, 1, n_points)
+    levels, hits = _levels_from_radii(delta, MomentInterval(tmg).radii_batch(counts, cls), cls)
+    return _result(levels, return_details, counts=counts, estimates=choi, delta=delta, hits=hits, seed=None)
