@@ -380,6 +380,18 @@ int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double
  * qt_hs_dist_dim's kernel on them: the same bits as the two calls. */
 int qt_lifp_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, const double* centre, double* choi,
                        double* dist, int32_t* iters, int32_t* status, int flags);
+/* The bootstrap coverage study for processes (quantpy/metrics.py:282-316: every trial t bootstraps around ITS OWN Choi
+ * estimate): qt_lifp_dist_batch with a table centres[G][D][D][2], dist[b] = hs_dst(Choi_b, centres[b % G]).  The batch is
+ * resample-major, counts[r * G + t] = resample r of trial t -- the order qt_device_multinomial writes with
+ * period = G * D * S and qt_process_born_probs' table as pvals.  G >= 1 (else QT_ERR_ARG); G = 1 is qt_lifp_dist_batch.
+ * Everything else -- choi NULLABLE, iters, status, the choice of path from the whole batch, the slices -- as there. */
+int qt_lifp_dist_group_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, const double* centres, int G, double* choi,
+                             double* dist, int32_t* iters, int32_t* status, int flags);
+/* The outcome probabilities of G channels given by their Choi matrices choi[G][D][D][2], on the D input states of
+ * qt_process_setup (requires qt_set_povm* and qt_process_setup):
+ *   p[G][D][S][K] = clip(Born(povm, E_g(rho_i)), 0, 1),   E_g(rho) = Tr_in[(rho^T (x) I) C_g]  (channel.py: Channel.transform)
+ * Row (g * D + i) * S + s is one multinomial's pvals: the table qt_device_multinomial reads with period = G * D * S. */
+int qt_process_born_probs(qt_handle_t* h, const double* choi, int G, double* p, int flags);
 /* 'pgdb' (process.py:291-308): projected gradient descent with backtracking from the fully mixed Choi
  * matrix, raw counts as weights, every arithmetic quirk of the reference kept (see qt_process.h).
  * stop_rule 0 = the reference's loop exit (leaves at the first step that lowers the NLL by more than

@@ -62,6 +62,8 @@ SIGNATURES = {
     "qt_lin_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_int]),
     "qt_mle_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _c_int]),
+    "qt_lifp_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
+    "qt_process_born_probs": (_c_int, [_vp, _vp, _c_int, _vp, _c_int]),
     "qt_group_hits": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _c_int]),
     "qt_hs_dist_batch": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_hs_dist_dim": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _vp, _c_int]),

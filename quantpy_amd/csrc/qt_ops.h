@@ -543,11 +543,13 @@ __global__ void k_mat_from_bloch(int nq, const double* __restrict__ bloch, int B
 }
 
 // ---- a16: geometry.py:16-20, one wavefront per trial -----------------------------------------
-__global__ void __launch_bounds__(64) k_hs_dist(int d, const double* __restrict__ rho, const double* __restrict__ centre,
-                                                int B, double* __restrict__ dist) {
+// `centres` holds G matrices; trial b (= the workgroup) is measured against centre (g0 + b) % G (centre_of, qt_small.h).
+__global__ void __launch_bounds__(64) k_hs_dist(int d, const double* __restrict__ rho, const double* __restrict__ centres,
+                                                int G, int g0, int B, double* __restrict__ dist) {
   const int b = blockIdx.x;
   if (b >= B) return;
   const double* r = rho + (size_t)b * d * d * 2;
+  const double* centre = centre_of(centres, G, g0, b, 2 * d * d);
   double sr = 0.0, si = 0.0;
   for (int e = threadIdx.x; e < d * d; e += 64) {
     const int i = e / d, j = e % d;
@@ -565,6 +567,14 @@ __global__ void __launch_bounds__(64) k_hs_dist(int d, const double* __restrict_
   if (threadIdx.x == 0) {
     const double v = sqrt(hypot(sr, si)) / sqrt(2.0);
     dist[b] = v < 1e-15 ? 0.0 : v;
+  }
+}
+
+// np.clip(p, 0, 1) in place (a NaN stays a NaN): the `pvals` of the bootstrap's resampling tables
+__global__ void __launch_bounds__(256) k_clip01(double* __restrict__ p, size_t n) {
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    const double v = p[t];
+    p[t] = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
   }
 }
 

@@ -364,7 +364,8 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 4) k_lifp_batch(const int64_t*
                                                               const double* __restrict__ pinvT, int cptp,
                                                               double* __restrict__ choi, int32_t* __restrict__ iters,
                                                               int32_t* __restrict__ status,
-                                                              const double* __restrict__ centre, double* __restrict__ dist) {
+                                                              const double* __restrict__ centres, int G, int g0,
+                                                              double* __restrict__ dist) {
   using W = ProcWG<DC>;
   __shared__ typename W::Sh sh;
   extern __shared__ double sfreq[];  // [DC * M]
@@ -413,6 +414,7 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 4) k_lifp_batch(const int64_t*
     // hs_dst(C, centre) as k_hs_dist forms it, the 16 elements in the first 16 lanes of the one wavefront: Delta_ji by a
     // shuffle.  (uniform over the launch; DC = 16 callers pass null and run k_hs_dist on the stored matrices)
     if (dist) {
+      const double* centre = centre_of(centres, G, g0, b, 2 * W::NE);  // (b: the workgroup)
       cd dl{0.0, 0.0};
       if (act) dl = cd{xr - centre[2 * tid], xi - centre[2 * tid + 1]};
       const int src = act ? j * DC + i : tid;
@@ -848,8 +850,8 @@ template <int KSC>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_lifp16(const int64_t* __restrict__ counts, int B, int M,
                                                 const double* __restrict__ vp_perm, const double* __restrict__ vs_pinv,
                                                 double* __restrict__ choi, int32_t* __restrict__ status,
-                                                int32_t* __restrict__ iters, const double* __restrict__ centre,
-                                                double* __restrict__ dist) {
+                                                int32_t* __restrict__ iters, const double* __restrict__ centres,
+                                                int G, int g0, double* __restrict__ dist) {
   constexpr int DC = 16, PT = DC + 1;
   extern __shared__ __attribute__((aligned(16))) double s_vp[];  // [M][32]; with `dist`: + [4 wavefronts][16][PT] complex
   for (int k = threadIdx.x; k < M * 32; k += 256) s_vp[k] = vp_perm[k];
@@ -927,7 +929,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
     }
     if (dist) {  // (uniform over the launch) hs_dst(X, centre) as k_hs_dist forms it, Delta^T through this wavefront's scratch
       cd* T = reinterpret_cast<cd*>(s_vp + M * 32) + w * DC * PT;
-      const cd* cen = reinterpret_cast<const cd*>(centre);
+      // process b's centre: b is the same in the whole wavefront, so the table index stays in scalar registers
+      const cd* cen = reinterpret_cast<const cd*>(centre_of(centres, G, g0, __builtin_amdgcn_readfirstlane(b), 2 * DC * DC));
       cd dl[4];
       wave_sync();  // (the reads of the process before are done)
 #pragma unroll
@@ -955,6 +958,32 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
       if (status) status[b] = any ? 4 : 0;
       if (iters) iters[b] = 0;
     }
+  }
+}
+
+// ---- channel.py:89-91, the Choi branch of Channel.transform, for G channels x D input states -------------------------
+// choi[G][D][D] complex (D = d^2, row a d + b: input index a, output index b), in_states[D][d][d] complex:
+//   out[g][i][b][e] = E_g(rho_i)[b][e] = Tr_in[(rho_i^T (x) I) C_g][b][e] = sum_{a, c} rho_i[a][c] C_g[a d + b][c d + e].
+// One thread per output element (n = total elements, G D d^2), e fastest: a wavefront reads runs of d consecutive Choi
+// entries.  Feeds the Bloch / Born kernels of qt_process_born_probs; not a hot path (16 D^2 bytes read per channel, once per
+// study).
+__global__ void __launch_bounds__(256) k_choi_apply(int d, const double* __restrict__ choi, const double* __restrict__ in_states,
+                                                    size_t n, double* __restrict__ out) {
+  const int D = d * d;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    const int e = (int)(t % d), b = (int)(t / d % d), i = (int)(t / D % D);
+    const size_t g = t / D / D;
+    const cd* C = reinterpret_cast<const cd*>(choi) + g * D * D;
+    const cd* rho = reinterpret_cast<const cd*>(in_states) + (size_t)i * D;
+    double sr = 0.0, si = 0.0;
+    for (int a = 0; a < d; ++a)
+      for (int c = 0; c < d; ++c) {
+        const cd r = rho[a * d + c], x = C[(size_t)(a * d + b) * D + c * d + e];
+        sr += r.re * x.re - r.im * x.im;
+        si += r.re * x.im + r.im * x.re;
+      }
+    out[2 * t] = sr;
+    out[2 * t + 1] = si;
   }
 }
 

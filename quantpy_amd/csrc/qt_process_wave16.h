@@ -293,12 +293,12 @@ struct ProcWave16 {
 };
 
 // mode 0: Dykstra CPTP, 1: TP only, 2: CP only; in / out [B][16][16] complex, row-major; one wavefront per process.
-// `dist` (uniform over the launch; null: none) takes hs_dst(projected matrix, centre) per process, formed on the registers
-// (ProcWave16::hs_to_centre); `out` may then be null: no matrix leaves the kernel (qt_lifp_dist_batch).
+// `dist` (uniform over the launch; null: none) takes hs_dst(projected matrix, centre (g0 + b) % G of `centres`) per process,
+// formed on the registers (ProcWave16::hs_to_centre); `out` may then be null: no matrix leaves the kernel (qt_lifp_dist_batch).
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_cptp_wave16(const double* __restrict__ in, int B, int mode, int n_iter, double tol,
                                                      double* __restrict__ out, int32_t* __restrict__ iters,
-                                                     int32_t* __restrict__ status, const double* __restrict__ centre,
-                                                     double* __restrict__ dist) {
+                                                     int32_t* __restrict__ status, const double* __restrict__ centres,
+                                                     int G, int g0, double* __restrict__ dist) {
   __shared__ cd scratch[4 * ProcWave16::kLdsComplexPerWave];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + w;
@@ -315,6 +315,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
   else it = ProcWave16::cp_project(L, x, 1e-12);
   QT_STAMP(1);
   if (dist) {
+    // process b's centre: b is the same in the whole wavefront, so the table index stays in scalar registers
+    const double* centre = centre_of(centres, G, g0, __builtin_amdgcn_readfirstlane(b), 2 * 256);
     const double v = ProcWave16::hs_to_centre(L, x, reinterpret_cast<const cd*>(centre));
     if (lane == 0) dist[b] = v;
   }

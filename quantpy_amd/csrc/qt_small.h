@@ -349,6 +349,11 @@ __device__ __forceinline__ bool shots_match(double t_s, double total, double n_s
 // study has its own point estimate: the batch is then [resample][trial] and trial b is measured against centre (g0 + b) % G
 // (g0: the group of the launch's first trial, for a launch that starts inside the batch).  G == 1 is the single centre and
 // takes no modulo.
+// Centre (g0 + b) % G of a table of G matrices of dd doubles each.  Defined for every b >= 0.
+__device__ __forceinline__ const double* centre_of(const double* centres, int G, int g0, int b, int dd) {
+  return G > 1 ? centres + (size_t)((unsigned)(g0 + b) % (unsigned)G) * dd : centres;
+}
+
 struct EstOut {
   double* rho;           // [B][d][d][2], or nullptr when only the distance is wanted
   const double* centre;  // [G][d][d][2], read when dist != nullptr
@@ -358,7 +363,7 @@ struct EstOut {
   // The centre of trial b, dd doubles each.  Reduced for every b >= 0, so the lane groups that pad the last workgroup
   // (b >= B, stores masked) read inside the table too.
   __device__ __forceinline__ const double* centre_of(int b, int dd) const {
-    return G > 1 ? centre + (size_t)((unsigned)(g0 + b) % (unsigned)G) * dd : centre;
+    return qt::centre_of(centre, G, g0, b, dd);
   }
 };
 

@@ -130,6 +130,7 @@ struct qt_handle {
   DevBuf stage[kStageBufs];
   DevBuf aug;      // [cols][2 cols] Gauss-Jordan workspace of enqueue_left_inverse
   DevBuf proc_ws;  // k_cptp_project64: Dykstra's p, q, y, x and the clip's input (project)
+  DevBuf born_ws;       // qt_process_born_probs: the output states E_g(rho_i) and, behind them, their Bloch vectors
   DevBuf lifp_dist_ws;  // qt_lifp_dist_batch without `choi`: one slice's Choi matrices, where k_hs_dist reads them
   DevBuf gram;  // qt_moment_batch: P^T P
   DevBuf moment_freq, moment_part, moment_qpart;  // k_moment_cols: counts / ns, the blocks' partial sums, Q_ab in pieces
@@ -814,16 +815,17 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
 // size.  n = 3: k_cptp_project64 (qt_process64.h), one workgroup each, with Dykstra's p, q, y, x and the clip's input in
 // h->proc_ws -- except in mode 1, which takes no workspace.  n = 2: k_cptp_wave16 (qt_process_wave16.h), one wavefront
 // each.  n = 1: k_cptp_project<4> (qt_process.h), one workgroup each.  `iters` and `status` may be null.
-// n = 2 only: `dist` (with `centre`) takes hs_dst(projected matrix, centre) from the same launch, and `out` may then be null.
+// n = 2 only: `dist` (with the table `centres` of G matrices, process b against centre (g0 + b) % G) takes hs_dst(projected
+// matrix, centre) from the same launch, and `out` may then be null.
 int project(qt_handle_t* h, const double* in, int B, int mode, int n_iter, double tol, double* out, int32_t* iters,
-            int32_t* status, const double* centre = nullptr, double* dist = nullptr) {
+            int32_t* status, const double* centres = nullptr, int G = 1, int g0 = 0, double* dist = nullptr) {
   if (h->D == 64) {
     if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
     return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, in, B, mode, n_iter, tol, out,
                   iters, status, h->proc_ws.as<double>());
   }
   if (h->D == 16)
-    return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status, centre, dist);
+    return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status, centres, G, g0, dist);
   return launch(h, qt::k_cptp_project<4>, dim3(B), dim3(qt::ProcWG<4>::NT), 0, in, B, mode, n_iter, tol, out, iters, status);
 }
 
@@ -868,6 +870,33 @@ int pgdb64_trial(qt_handle_t* h, const int64_t* counts, int B, const double* cur
                      h->proc.emats.as<double>(), cur, h->ws_act.as<int32_t>(), h->ws_x.as<double>(), h->ws_g.as<double>()))
     return r;
   return project(h, h->ws_g.as<double>(), B, 0, 1000, 1e-12, h->ws_f.as<double>(), nullptr, nullptr);
+}
+
+// a5 on device arrays, the launches behind qt_born_probs and qt_process_born_probs: p[B][M] from bloch[B][D]
+int born_launch(qt_handle_t* h, const double* din, int B, double* dout) {
+  if (h->nq >= 4 && h->prod.enabled) {  // factorised contraction, one workgroup per state
+    const Plan pl = h->nq == 4 ? povm_plan<4>(h, B) : povm_plan<5>(h, B);
+    return launch(h, h->nq == 4 ? qt::k_born_large<4> : qt::k_born_large<5>, pl, pl.pv, din, B, dout);
+  }
+  if (int r = ensure_dense(h)) return r;
+  const int gx = (h->M + 255) / 256;
+  int Mp = (h->M + 15) & ~15;
+  if ((Mp & 31) != 16) Mp += 16;  // LDS pitch: 16 mod 32 doubles (see k_born_mfma)
+  const size_t at_bytes = (size_t)h->D * Mp * sizeof(double);
+  if (h->D <= 64 && at_bytes <= 128 * 1024 && B >= 4096) {
+    // batched: the matrix-core kernel, one persistent 16-wave workgroup per CU (A^T lives in its LDS)
+    int grid = (B + 16 * 16 - 1) / (16 * 16);
+    if (grid > 256) grid = 256;
+    const auto kern = h->D == 4 ? qt::k_born_mfma<4> : (h->D == 16 ? qt::k_born_mfma<16> : qt::k_born_mfma<64>);
+    if (int r = launch(h, kern, dim3(grid), dim3(1024), at_bytes, h->AT.as<double>(), h->M, Mp, h->d, din, B, dout)) return r;
+  } else {
+    const int TB = h->D <= 256 ? 8 : 4;  // states per workgroup
+    int gy = (B + TB - 1) / TB;
+    if (gy > 2048) gy = 2048;
+    hipLaunchKernelGGL((TB == 8 ? qt::k_born<8> : qt::k_born<4>), dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream,
+                       h->AT.as<double>(), h->M, h->D, h->d, din, B, dout);
+  }
+  return 0;
 }
 
 }  // namespace
@@ -974,9 +1003,10 @@ bool lifp_dist_in_kernel(const qt_handle_t* h, LifpPath path, int cptp) {
 }
 
 // Linear inversion (+ projection) of B processes on device arrays along `path`; `dist` non-null (only where
-// lifp_dist_in_kernel): the distances to `centre` from the same launches, and `dchoi` may then be null.
-int lifp_launch(qt_handle_t* h, LifpPath path, const int64_t* dc, int B, int cptp, const double* centre, double* dchoi,
-                double* dist, int32_t* dit, int32_t* dst) {
+// lifp_dist_in_kernel): the distances from the same launches, process b to centre (g0 + b) % G of the table `centre`
+// (qt::centre_of), and `dchoi` may then be null.
+int lifp_launch(qt_handle_t* h, LifpPath path, const int64_t* dc, int B, int cptp, const double* centre, int G, int g0,
+                double* dchoi, double* dist, int32_t* dit, int32_t* dst) {
   const int D = h->D, M = h->M;
   const ProcessState& ps = h->proc;
   // R doubles of frequencies per process, Rp with the pitch k_lifp_freq pads to (at n = 3 R is a multiple of 64 already
@@ -1027,7 +1057,7 @@ int lifp_launch(qt_handle_t* h, LifpPath path, const int64_t* dc, int B, int cpt
       // 16 x 17 complex transpose scratch per wavefront behind V_P^+
       const size_t lds = (size_t)M * 32 * sizeof(double) + (rdist ? 4 * 16 * 17 * 2 * sizeof(double) : 0);
       if (int r = launch(h, M == 36 ? qt::k_lifp16<9> : qt::k_lifp16<0>, dim3(std::min((B + 3) / 4, 768)), dim3(256), lds, dc, B, M,
-                         ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(), raw, rst, rit, centre, rdist))
+                         ps.vp_perm.as<double>(), ps.vs_pinv.as<double>(), raw, rst, rit, centre, G, g0, rdist))
         return r;
       break;
     }
@@ -1062,25 +1092,27 @@ int lifp_launch(qt_handle_t* h, LifpPath path, const int64_t* dc, int B, int cpt
     case kFused:
       if (int r = launch(h, D == 4 ? qt::k_lifp_batch<4> : qt::k_lifp_batch<16>, dim3(B),
                          dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, B, M, ps.pinvT.as<double>(), cptp, dchoi,
-                         dit, dst, centre, dist))
+                         dit, dst, centre, G, g0, dist))
         return r;
       break;
   }
   // The projection, where the path left it to do.
   if (then_project)
-    if (int r = project(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst, centre, dist)) return r;
+    if (int r = project(h, raw, B, 0, 1000, 1e-12, dchoi, dit, dst, centre, G, g0, dist)) return r;
   return 0;
 }
 
-// Both entry points.  `with_dist` false: qt_lifp_batch.  Otherwise the batch runs in slices (QT_OPT_LIFP_DIST_SLICE) that bound
+// The three entry points.  `with_dist` false: qt_lifp_batch.  Otherwise `centre` holds G matrices, process b is measured
+// against centre b % G (qt_lifp_dist_batch: G = 1), and the batch runs in slices (QT_OPT_LIFP_DIST_SLICE) that bound
 // every workspace whose size follows the batch: the raw inversion a projection reads, and -- where k_hs_dist forms the
 // distance and the caller wants no matrices -- the matrices themselves.
-int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B, int cptp, const double* centre, double* choi,
-                    double* dist, int32_t* iters, int32_t* status, int flags, const char* fn) {
+int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B, int cptp, const double* centre, int G,
+                    double* choi, double* dist, int32_t* iters, int32_t* status, int flags, const char* fn) {
   QT_ENTER(h);
   Call c(h, flags, fn);
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
-  if (B < 0 || (B > 0 && (!counts || (with_dist ? !centre || !dist : !choi)))) return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
+  if (B < 0 || G < 1 || (B > 0 && (!counts || (with_dist ? !centre || !dist : !choi))))
+    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
   if (B == 0) return 0;
   if (!with_dist) dist = nullptr;
   const int D = h->D, M = h->M;
@@ -1090,7 +1122,7 @@ int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B
   double *dchoi, *ddist;
   int32_t *dit, *dst;
   if (int r = c.in(counts, (size_t)B * D * M, &dc)) return r;
-  if (int r = c.in(centre, dist ? ne2 : 0, &dcen)) return r;
+  if (int r = c.in(centre, dist ? (size_t)G * ne2 : 0, &dcen)) return r;
   if (int r = c.out(choi, (size_t)B * ne2, &dchoi)) return r;
   if (int r = c.out(dist, (size_t)B, &ddist)) return r;
   if (int r = c.out(iters, (size_t)B, &dit)) return r;
@@ -1098,7 +1130,7 @@ int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B
   LifpPath path;
   if (int r = lifp_path(h, B, &path)) return r;
   if (!dist) {
-    if (int r = lifp_launch(h, path, dc, B, cptp, nullptr, dchoi, nullptr, dit, dst)) return r;
+    if (int r = lifp_launch(h, path, dc, B, cptp, nullptr, 1, 0, dchoi, nullptr, dit, dst)) return r;
     return c.done(status, B);
   }
   constexpr size_t kSliceBytes = (size_t)128 << 20;  // of Choi matrices: 2048 processes at n = 3, 32 768 at n = 2
@@ -1107,16 +1139,17 @@ int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B
   const bool in_kernel = lifp_dist_in_kernel(h, path, cptp);
   for (int b0 = 0; b0 < B; b0 += slice) {
     const int nb = B - b0 < slice ? B - b0 : slice;
+    const int g0 = b0 % G;  // the group of the slice's first process
     double* m = dchoi ? dchoi + (size_t)b0 * ne2 : nullptr;
     if (!in_kernel && !m) {
       HIPCHK(h->lifp_dist_ws.ensure((size_t)nb * ne2 * sizeof(double)));
       m = h->lifp_dist_ws.as<double>();
     }
-    if (int r = lifp_launch(h, path, dc + (size_t)b0 * D * M, nb, cptp, dcen, m, in_kernel ? ddist + b0 : nullptr,
+    if (int r = lifp_launch(h, path, dc + (size_t)b0 * D * M, nb, cptp, dcen, G, g0, m, in_kernel ? ddist + b0 : nullptr,
                             dit ? dit + b0 : nullptr, dst ? dst + b0 : nullptr))
       return r;
     if (!in_kernel)
-      if (int r = launch(h, qt::k_hs_dist, dim3(nb), dim3(64), 0, D, (const double*)m, dcen, nb, ddist + b0)) return r;
+      if (int r = launch(h, qt::k_hs_dist, dim3(nb), dim3(64), 0, D, (const double*)m, dcen, G, g0, nb, ddist + b0)) return r;
   }
   return c.done(status, B);
 }
@@ -1179,7 +1212,7 @@ void qt_destroy(qt_handle_t* h) {
   (void)hipStreamSynchronize(h->stream);
   for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_last})
     b->release();
-  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws,
+  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
                     &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
@@ -1500,29 +1533,7 @@ int qt_born_probs(qt_handle_t* h, const double* bloch, int B, double* p, int fla
   double* dout;
   if (int r = c.in(bloch, (size_t)B * h->D, &din)) return r;
   if (int r = c.out(p, (size_t)B * h->M, &dout)) return r;
-  if (h->nq >= 4 && h->prod.enabled) {  // factorised contraction, one workgroup per state
-    const Plan pl = h->nq == 4 ? povm_plan<4>(h, B) : povm_plan<5>(h, B);
-    if (int r = launch(h, h->nq == 4 ? qt::k_born_large<4> : qt::k_born_large<5>, pl, pl.pv, din, B, dout)) return r;
-    return c.done();
-  }
-  if (int r = ensure_dense(h)) return r;
-  const int gx = (h->M + 255) / 256;
-  int Mp = (h->M + 15) & ~15;
-  if ((Mp & 31) != 16) Mp += 16;  // LDS pitch: 16 mod 32 doubles (see k_born_mfma)
-  const size_t at_bytes = (size_t)h->D * Mp * sizeof(double);
-  if (h->D <= 64 && at_bytes <= 128 * 1024 && B >= 4096) {
-    // batched: the matrix-core kernel, one persistent 16-wave workgroup per CU (A^T lives in its LDS)
-    int grid = (B + 16 * 16 - 1) / (16 * 16);
-    if (grid > 256) grid = 256;
-    const auto kern = h->D == 4 ? qt::k_born_mfma<4> : (h->D == 16 ? qt::k_born_mfma<16> : qt::k_born_mfma<64>);
-    if (int r = launch(h, kern, dim3(grid), dim3(1024), at_bytes, h->AT.as<double>(), h->M, Mp, h->d, din, B, dout)) return r;
-  } else {
-    const int TB = h->D <= 256 ? 8 : 4;  // states per workgroup
-    int gy = (B + TB - 1) / TB;
-    if (gy > 2048) gy = 2048;
-    hipLaunchKernelGGL((TB == 8 ? qt::k_born<8> : qt::k_born<4>), dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream,
-                       h->AT.as<double>(), h->M, h->D, h->d, din, B, dout);
-  }
+  if (int r = born_launch(h, din, B, dout)) return r;
   return c.done();
 }
 
@@ -1722,7 +1733,7 @@ int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, in
   if (int r = c.in(rho, (size_t)B * h->D * 2, &dr)) return r;
   if (int r = c.in(centre, (size_t)h->D * 2, &dcn)) return r;
   if (int r = c.out(dist, (size_t)B, &dd)) return r;
-  hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, h->d, dr, dcn, B, dd);
+  hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, h->d, dr, dcn, 1, 0, B, dd);
   return c.done();
 }
 
@@ -1738,7 +1749,7 @@ int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* cen
   if (int r = c.in(rho, (size_t)B * ne * 2, &dr)) return r;
   if (int r = c.in(centre, ne * 2, &dcn)) return r;
   if (int r = c.out(dist, (size_t)B, &dd)) return r;
-  hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, dim, dr, dcn, B, dd);
+  hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, dim, dr, dcn, 1, 0, B, dd);
   return c.done();
 }
 
@@ -2317,12 +2328,46 @@ int qt_process_get_factors(qt_handle_t* h, double* vs_pinv, double* vp_pinv, int
 
 int qt_lifp_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, double* choi, int32_t* iters, int32_t* status,
                   int flags) {
-  return lifp_batch_impl(h, false, counts, B, cptp, nullptr, choi, nullptr, iters, status, flags, __func__);
+  return lifp_batch_impl(h, false, counts, B, cptp, nullptr, 1, choi, nullptr, iters, status, flags, __func__);
 }
 
 int qt_lifp_dist_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, const double* centre, double* choi,
                        double* dist, int32_t* iters, int32_t* status, int flags) {
-  return lifp_batch_impl(h, true, counts, B, cptp, centre, choi, dist, iters, status, flags, __func__);
+  return lifp_batch_impl(h, true, counts, B, cptp, centre, 1, choi, dist, iters, status, flags, __func__);
+}
+
+int qt_lifp_dist_group_batch(qt_handle_t* h, const int64_t* counts, int B, int cptp, const double* centres, int G, double* choi,
+                             double* dist, int32_t* iters, int32_t* status, int flags) {
+  return lifp_batch_impl(h, true, counts, B, cptp, centres, G, choi, dist, iters, status, flags, __func__);
+}
+
+// The resampling table of the process bootstrap: output states (k_choi_apply), their Bloch vectors and the Born rule by the
+// kernels of qt_bloch_from_mat / qt_born_probs on the handle's workspace, then the clip np.random.multinomial's pvals get.
+int qt_process_born_probs(qt_handle_t* h, const double* choi, int G, double* p, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = need_povm(h)) return r;
+  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+  if (G < 0 || (G > 0 && (!choi || !p))) return fail(QT_ERR_ARG, "bad process_born_probs arguments");
+  if (G == 0) return 0;
+  const int D = h->D, M = h->M;
+  if ((long long)G * D > INT32_MAX / 2) return fail(QT_ERR_ARG, "batch too large");
+  const int B = G * D;  // output states
+  const size_t ne2 = (size_t)D * D * 2, nmat = (size_t)B * D * 2, np = (size_t)B * M;
+  const double* dchoi;
+  double* dp;
+  if (int r = c.in(choi, (size_t)G * ne2, &dchoi)) return r;
+  if (int r = c.out(p, np, &dp)) return r;
+  HIPCHK(h->born_ws.ensure((nmat + (size_t)B * D) * sizeof(double)));
+  double *mat = h->born_ws.as<double>(), *bloch = mat + nmat;
+  if (int r = launch(h, qt::k_choi_apply, dim3(grid_for((size_t)B * D)), dim3(256), 0, h->d, dchoi, h->proc.in_states.as<double>(),
+                     (size_t)B * D, mat))
+    return r;
+  if (int r = launch(h, qt::k_bloch_from_mat, dim3(grid_for((size_t)B * D)), dim3(256), 0, h->nq, (const double*)mat, B, bloch))
+    return r;
+  if (int r = born_launch(h, bloch, B, dp)) return r;
+  if (int r = launch(h, qt::k_clip01, dim3(grid_for(np)), dim3(256), 0, dp, np)) return r;
+  return c.done();
 }
 
 int qt_pgdb_batch(qt_handle_t* h, const int64_t* counts, int B, int n_iter, double tol, int stop_rule, double* choi,

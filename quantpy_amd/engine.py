@@ -402,24 +402,58 @@ class Engine:
 
     def lifp_dist(self, counts, centre, cptp=True, return_info=False):
         """hs_dst(lifp(counts_b), centre) for every process in ONE pass (qt_lifp_dist_batch: the Choi matrices are not
-        written).  counts (B, D, S, K), centre (D, D) -> (B,) float64; return_info appends dict(iters, status)."""
+        written).  counts (B, D, S, K), centre (D, D) -> (B,) float64; return_info appends dict(iters, status).
+        A centre table (G, D, D) measures process b against centre[b % G] (qt_lifp_dist_group_batch: the resample-major
+        batches of metrics.get_CL_list_channel_boot)."""
         c = _i64(counts).reshape(-1, self.D, self.S, self.K)
         b = c.shape[0]
         cen = _c128(centre)
-        assert cen.shape == (self.D, self.D)
+        assert cen.shape[-2:] == (self.D, self.D) and cen.ndim in (2, 3)
         dist = np.empty(b)
         iters = np.zeros(b, dtype=np.int32)
         status = np.zeros(b, dtype=np.int32)
-        self._chk(self.lib.qt_lifp_dist_batch(self._h, _ptr(c), b, int(bool(cptp)), _ptr(cen), None, _ptr(dist), _ptr(iters),
-                                              _ptr(status), _capi.QT_HOST_PTR))
+        if cen.ndim == 3:
+            self._chk(self.lib.qt_lifp_dist_group_batch(self._h, _ptr(c), b, int(bool(cptp)), _ptr(cen), cen.shape[0], None,
+                                                        _ptr(dist), _ptr(iters), _ptr(status), _capi.QT_HOST_PTR))
+        else:
+            self._chk(self.lib.qt_lifp_dist_batch(self._h, _ptr(c), b, int(bool(cptp)), _ptr(cen), None, _ptr(dist),
+                                                  _ptr(iters), _ptr(status), _capi.QT_HOST_PTR))
         return (dist, dict(iters=iters, status=status)) if return_info else dist
 
     def lifp_dist_dev(self, counts, centre, dist, cptp=True, choi=None, iters=None, status=None):
         """device-pointer form: counts int64 (B, D, S, K), centre complex128 (D, D), dist float64 (B,) torch CUDA
-        tensors; choi complex128 (B, D, D) optional (then what `lifp_dev` writes, bit for bit)"""
+        tensors; choi complex128 (B, D, D) optional (then what `lifp_dev` writes, bit for bit).  A centre table
+        (G, D, D) measures process b against centre[b % G] (qt_lifp_dist_group_batch), as in lin_dist_dev."""
         self._dev_call()
+        if centre.dim() == 3:
+            self._chk(self.lib.qt_lifp_dist_group_batch(self._h, _ptr(counts), counts.shape[0], int(bool(cptp)), _ptr(centre),
+                                                        centre.shape[0], _ptr(choi), _ptr(dist), _ptr(iters), _ptr(status),
+                                                        _capi.QT_DEVICE_PTR))
+            return
         self._chk(self.lib.qt_lifp_dist_batch(self._h, _ptr(counts), counts.shape[0], int(bool(cptp)), _ptr(centre),
                                               _ptr(choi), _ptr(dist), _ptr(iters), _ptr(status), _capi.QT_DEVICE_PTR))
+
+    def process_born_probs(self, choi, out=None):
+        """Outcome probabilities of the channels with Choi matrices `choi` (G, D, D) on the input states of
+        `process_setup`: (G, D, S, K) float64, clip(Born(povm, E_g(rho_i)), 0, 1) with E_g the Choi branch of
+        Channel.transform (qt_process_born_probs) -- the `pvals` table of the process bootstrap, row (g * D + i) * S + s.
+        NumPy in, NumPy out; a complex128 torch CUDA tensor in, `out` (float64 CUDA tensor, allocated when None) out."""
+        if _is_dev(choi):
+            self._dev_call()
+            assert choi.is_contiguous() and tuple(choi.shape[1:]) == (self.D, self.D)
+            g = choi.shape[0]
+            if out is None:
+                import torch
+
+                out = torch.empty((g, self.D, self.S, self.K), dtype=torch.float64, device=choi.device)
+            assert out.is_contiguous() and out.numel() == g * self.D * self.M
+            self._chk(self.lib.qt_process_born_probs(self._h, _ptr(choi), g, _ptr(out), _capi.QT_DEVICE_PTR))
+            return out
+        c = _c128(choi).reshape(-1, self.D, self.D)
+        p = np.empty((c.shape[0], self.D, self.S, self.K)) if out is None else out
+        assert p.dtype == np.float64 and p.flags.c_contiguous and p.size == c.shape[0] * self.D * self.M
+        self._chk(self.lib.qt_process_born_probs(self._h, _ptr(c), c.shape[0], _ptr(p), _capi.QT_HOST_PTR))
+        return p
 
     def cptp_project(self, choi, mode="cptp", n_iter=1000, tol=1e-12, return_iters=False):
         """mode 'cptp' (Dykstra) | 'tp' | 'cp' on Choi matrices (B, D, D) / (D, D)."""

@@ -51,7 +51,8 @@ def _check_arguments(interval, dst, n_iter, n_points, sampler, boot_methods, met
         raise NotImplementedError("interval='mhmc' (a chain per trial) is not implemented; supported: 'gamma'"
                                   + (", 'boot'" if boot_methods else ""))
     if interval == "boot" and not boot_methods:
-        raise NotImplementedError("interval='boot' is not implemented for processes; supported: 'gamma'")
+        raise NotImplementedError("interval='boot' is not implemented by get_CL_list_channel (supported: 'gamma'); the "
+                                  "bootstrap study of a channel is get_CL_list_channel_boot")
     if not (dst == "hs" or dst is hs_dst):
         raise NotImplementedError("only the Hilbert-Schmidt distance (dst='hs') is supported")
     if interval == "boot" and method_boot not in boot_methods:
@@ -145,43 +146,70 @@ def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init,
     from . import _capi
 
     n_iter = rho.shape[0]
-    n_set, n_out = eng.S, eng.K
-    dev = torch.device("cuda", eng.device)
-    pvals = np.clip(eng.born_probs(eng.bloch_from_matrix(rho)), 0, 1).reshape(n_iter * n_set, n_out)
-    p_d = torch.from_numpy(pvals).to(dev)
-    n_d = torch.from_numpy(np.tile(np.asarray(tmg.n_measurements).astype(np.int64), n_iter)).to(dev)
-    centres = torch.from_numpy(np.ascontiguousarray(rho, dtype=np.complex128)).to(dev)
-    thr = torch.from_numpy(np.ascontiguousarray(delta, dtype=np.float64)).to(dev)
-    hits = torch.zeros(n_iter, dtype=torch.int64, device=dev)
-    per_resample = n_iter * n_set * n_out * 8
-    chunk = int(chunk) if chunk else max(1, _CHUNK_BYTES // per_resample)
-    chunk = max(1, min(chunk, (2**31 - 1) // n_iter))  # the batch size of a launch is a 32-bit int
-    lo, hi = qdist.shard_bounds(n_points)
-    chunk = min(chunk, max(hi - lo, 1))
-    counts = torch.empty((chunk * n_iter, n_set, n_out), dtype=torch.int64, device=dev)
-    dist = torch.empty(chunk * n_iter, dtype=torch.float64, device=dev)
-    status = torch.zeros(chunk * n_iter, dtype=torch.int32, device=dev)
-    bad = torch.zeros(2, dtype=torch.bool, device=dev)
-    for r0 in range(lo, hi, chunk):
-        b = min(chunk, hi - r0) * n_iter
-        eng.device_multinomial(n_d, p_d, b * n_set, key, first_row=r0 * n_iter * n_set, out=counts[:b])
+    pvals = np.clip(eng.born_probs(eng.bloch_from_matrix(rho)), 0, 1).reshape(n_iter * eng.S, eng.K)
+
+    def measure(counts, centres, dist, status):
         if method_boot == "lin":
-            eng.lin_dist_dev(counts[:b], centres, dist[:b], physical=physical, status=status[:b])
+            eng.lin_dist_dev(counts, centres, dist, physical=physical, status=status)
         else:
-            eng.mle_dist_dev(counts[:b], centres, dist[:b], init=init, max_iter=max_iter, tol=tol, status=status[:b])
-        eng.group_hits(dist[:b], thr, hits)
-        bad |= torch.stack([(status[:b] == 1).any(), (status[:b] == _capi.TRIAL_SHOTS).any()])
-    eng.sync()
-    bad = bad.cpu().numpy().astype(np.int64)
-    hits = hits.cpu().numpy()
-    if qdist.world()[1] > 1:  # every rank raises, or none
-        bad = qdist.allgather_equal(bad).max(axis=0)
-        hits = qdist.allgather_equal(hits).sum(0)
+            eng.mle_dist_dev(counts, centres, dist, init=init, max_iter=max_iter, tol=tol, status=status)
+
+    hits, bad = _chunked_hits(eng, rho, (eng.S, eng.K), pvals, tmg.n_measurements, delta, n_points, key, chunk, measure,
+                              lambda status: torch.stack([(status == 1).any(), (status == _capi.TRIAL_SHOTS).any()]))
     if bad[0]:
         raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
     if bad[1]:
         raise ValueError("per-setting totals of a trial do not match the registered shots")
     return hits
+
+
+def _chunked_hits(eng, centres, trial_shape, pvals, shots, delta, n_points, key, chunk, measure, flags):
+    """The chunk loop of both nested bootstraps.  `centres` (n_iter, ., .) are the trials' estimates, one trial's counts
+    have shape `trial_shape` = (..., S, K), `pvals` is the table of the n_iter estimates (rows of K) and `shots` the (S,)
+    totals of a setting.  This rank's `shard_bounds(n_points)` of the resamples runs in chunks of whole resamples through
+    one count buffer: `device_multinomial` (row r * rows-per-resample + ... of the table keyed by `key`),
+    `measure(counts, centres, dist, status)` -- a grouped launch family on device tensors -- and `group_hits` against
+    `delta`.  `flags(status)` gives a bool tensor of the error conditions seen in a chunk.  Returns (hits (n_iter,)
+    summed over the ranks, flags OR-ed over chunks and ranks): every rank raises, or none."""
+    import torch
+
+    n_iter = centres.shape[0]
+    n_out = trial_shape[-1]
+    rows = int(np.prod(trial_shape[:-1])) * n_iter  # table rows per resample of all trials
+    dev = torch.device("cuda", eng.device)
+    p_d = torch.from_numpy(np.ascontiguousarray(pvals, dtype=np.float64).reshape(rows, n_out)).to(dev)
+    shots = np.atleast_1d(np.asarray(shots)).astype(np.int64)
+    n_d = torch.from_numpy(np.tile(shots, rows // len(shots))).to(dev)
+    centres = torch.from_numpy(np.ascontiguousarray(centres, dtype=np.complex128)).to(dev)
+    thr = torch.from_numpy(np.ascontiguousarray(delta, dtype=np.float64)).to(dev)
+    hits = torch.zeros(n_iter, dtype=torch.int64, device=dev)
+    per_resample = rows * n_out * 8
+    chunk = int(chunk) if chunk else max(1, _CHUNK_BYTES // per_resample)
+    # The batch size of a launch is a 32-bit int.  (A caller's `chunk` is otherwise taken as given: the count buffer
+    # is chunk * per_resample bytes, and only the default is held to _CHUNK_BYTES.)
+    chunk = max(1, min(chunk, (2**31 - 1) // n_iter))
+    lo, hi = qdist.shard_bounds(n_points)
+    chunk = min(chunk, max(hi - lo, 1))
+    counts = torch.empty((chunk * n_iter,) + tuple(trial_shape), dtype=torch.int64, device=dev)
+    dist = torch.empty(chunk * n_iter, dtype=torch.float64, device=dev)
+    status = torch.zeros(chunk * n_iter, dtype=torch.int32, device=dev)
+    bad = None
+    for r0 in range(lo, hi, chunk):
+        b = min(chunk, hi - r0) * n_iter
+        eng.device_multinomial(n_d, p_d, (b // n_iter) * rows, key, first_row=r0 * rows, out=counts[:b])
+        measure(counts[:b], centres, dist[:b], status[:b])
+        eng.group_hits(dist[:b], thr, hits)
+        seen = flags(status[:b])
+        bad = seen if bad is None else bad | seen
+    eng.sync()
+    if bad is None:  # (a rank without resamples)
+        bad = torch.zeros_like(flags(status[:0]))
+    bad = bad.cpu().numpy().astype(np.int64)
+    hits = hits.cpu().numpy()
+    if qdist.world()[1] > 1:  # every rank raises, or none
+        bad = qdist.allgather_equal(bad).max(axis=0)
+        hits = qdist.allgather_equal(hits).sum(0)
+    return hits, bad
 
 
 def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n_measurements=1000, method="lifp",
@@ -191,7 +219,8 @@ def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n
                         return_details=False):
     """The same study for a channel and its Choi matrix (reference metrics.py:150-319; parameters as there), for
     interval='gamma': the process form of `MomentInterval.radii_batch` at np.linspace(0, 1, n_points).  'boot' and
-    'mhmc' raise NotImplementedError.  `sampler`, `seed`, `return_details` as in `get_CL_list_state`."""
+    'mhmc' raise NotImplementedError; the bootstrap study of a channel is `get_CL_list_channel_boot`.  `sampler`, `seed`,
+    `return_details` as in `get_CL_list_state`."""
     _check_arguments(interval, dst, n_iter, n_points, sampler, (), method_boot)
     n_iter, n_points = int(n_iter), int(n_points)
     tmg = ProcessTomograph(channel, input_states, "hs")
@@ -201,3 +230,43 @@ def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n
     cls = np.linspace(0, 1, n_points)
     levels, hits = _levels_from_radii(delta, MomentInterval(tmg).radii_batch(counts, cls), cls)
     return _result(levels, return_details, counts=counts, estimates=choi, delta=delta, hits=hits, seed=None)
+
+
+def get_CL_list_channel_boot(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",
+                             input_states="proj4", cptp=True, states_init="lin", states_est_method="lin", *,
+                             sampler="device", seed=None, chunk=None, return_details=False):
+    """The interval='boot', method_boot='lifp', dst='hs' branch of the reference's get_CL_list_channel
+    (metrics.py:282-316; parameters as there): `n_iter` process tomographies, each bootstrapped with `n_points` resamples
+    around ITS OWN Choi estimate; the level of trial t is the one at which the true Choi matrix leaves its interval.
+    Returns the sorted levels.  (`get_CL_list_channel(interval='boot')` keeps its refusal; this is the study's name.)
+
+    The trials are formed as in `get_CL_list_channel`: `point_estimate_batch(counts, method=method, ...)` with its default
+    cptp=True, as the reference's loop calls it; `cptp` is what the RESAMPLES are reconstructed with ('lifp', `tol` not
+    passed: BootstrapProcessInterval's loop).  `sampler`, `seed`, `chunk`, `return_details` as in `get_CL_list_state`.
+
+    Keying of the resamples (always the device sampler): Philox key (resolve_seed(seed) + 1) mod 2^64, and row
+    ((r * n_iter + t) * D + i) * S + s for setting s of input state i of resample r of trial t (D = 4^n input states, S
+    settings) -- a multinomial(n_measurements[s], `Engine.process_born_probs`(estimates)[t, i, s]).  The table depends
+    neither on `chunk` nor on the number of ranks; each rank takes `shard_bounds(n_points)` of the resamples, the hits are
+    summed and every rank returns the same list.  A chunk of whole resamples is one `device_multinomial`, one
+    `qt_lifp_dist_group_batch` (process b against centre b % n_iter) and one `qt_group_hits`; the level of trial t is
+    `levels_from_hits`: np.linspace(0, 1, n_points)[hits_t - 1], hits_t the resampled distances strictly below delta_t."""
+    _check_arguments("boot", "hs", n_iter, n_points, sampler, ("lifp",), "lifp")
+    n_iter, n_points = int(n_iter), int(n_points)
+    tmg = ProcessTomograph(channel, input_states, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
+    choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
+    eng = tmg._engine()
+    delta = eng.hs_dist(choi, channel.choi.matrix)
+    key = (base + 1) & (2**64 - 1)
+    pvals = eng.process_born_probs(choi)
+
+    def measure(resamples, centres, dist, status):
+        eng.lifp_dist_dev(resamples, centres, dist, cptp=cptp, status=status)
+
+    hits, bad = _chunked_hits(eng, choi, (eng.D, eng.S, eng.K), pvals, tmg.tomographs[0].n_measurements, delta, n_points,
+                              key, chunk, measure, lambda status: (status != 0).any().reshape(1))
+    if bad[0]:
+        raise ValueError("a resampled process has no finite Choi matrix (an input state without counts)")
+    return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
+                   seed=key)
