@@ -348,6 +348,31 @@ int qt_polytope_coverage(qt_handle_t* h, const int64_t* counts, long long B, int
 int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_init, const double* deltas,
                   const double* uniforms, int T, double step, double* chain, int32_t* accepted, int flags);
 
+/* The random numbers of such a chain drawn on the device, defined by index (csrc/qt_sampler.h: mhmc_draw).  Global step
+ * j of global chain c (j counts the burn-in steps first, then the sampling steps) owns the Philox4x32-10 stream
+ * (key = seed, row = c, substream = 1 + j): counter {q, c low, c high, 1 + j}; substream 0 is qt_device_multinomial's.
+ * Block q < D/2 (words w0..w3) holds the increments of parameters 2q and 2q + 1 by Box-Muller,
+ *   u1 = u53(w0, w1), u2 = u53(w2, w3), r = sqrt(-2 log(1 - u1)), delta[2q] = r cos(2 pi u2), delta[2q + 1] = r sin(2 pi u2),
+ * with u53(a, b) = ((a >> 5) 2^26 + (b >> 6)) / 2^53, and block q = D/2 the step's uniform u53(w0, w1).  Every number is
+ * a pure function of (seed, c, j, index): no launch, batch position, rank count or lane enters it.  This keying is ABI,
+ * like the row keying of qt_device_multinomial.  n <= 3 (n = 4, 5: QT_ERR_UNSUPPORTED); C = 0 or T = 0 returns 0.
+ *
+ * qt_mhmc_draws: deltas[C][T][D], uniforms[C][T] of chains first_chain .. first_chain+C-1, steps first_step ..
+ * first_step+T-1 (first_step + T >= 2^32 - 1: QT_ERR_ARG) -- what qt_mhmc_state needs to run the same chain. */
+int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
+                  double* deltas, double* uniforms, int flags);
+
+/* C chains, chain i on counts[i][S][K] from x_init[i][D] (qt_chol_param of centres[i]), numbers as above for global
+ * chain first_chain + i.  After the burn-in, post-burn step s is kept when s % thinning == 0 (mhmc.py:80-84): of the
+ * kept states,  hits[i] = #{ thresholds[i] > hs_dst(unparam(x), centres[i]) }  (strict: a NaN never counts; unparam as
+ * qt_chol_unparam, the distance as qt_hs_dist_dim), accepted[i] = accepted post-burn steps; dist[C][n_points] NULLABLE =
+ * the kept distances in chain order.  centres[C][d][d][2], thresholds[C].  The steps are those of qt_mhmc_state (one
+ * device function).  burn_steps >= 0, n_points >= 0, thinning >= 1 and burn_steps + n_points * thinning < 2^32 - 1, else
+ * QT_ERR_ARG; n = 4, 5: QT_ERR_UNSUPPORTED; C = 0 returns 0 without a launch. */
+int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
+                       const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                       int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags);
+
 /* ---- a11-a15: quantpy/tomography/process.py -------------------------------------------------- */
 /* Process tomography of an n-qubit channel (handle created with n_qubits = n; n <= 3: 'lifp', the projections and
  * what builds on them ('states', the bootstrap), 'pgdb' and the process chain all run for n <= 3; at n = 3 through the

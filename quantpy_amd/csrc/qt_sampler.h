@@ -60,10 +60,15 @@ inline uint32_t mt_next(Mt19937& g) {
 inline uint32_t Mt19937::next() { return mt_next(*this); }
 
 // the legacy 53-bit double: 27 high bits of one word, 26 of the next
+QT_SAMPLER_HD inline double u53_words(uint32_t w0, uint32_t w1) {
+  const int32_t a = (int32_t)(w0 >> 5), b = (int32_t)(w1 >> 6);
+  return (a * 67108864.0 + b) / 9007199254740992.0;
+}
 template <class G>
 QT_SAMPLER_HD inline double uniform53(G& g) {
-  const int32_t a = (int32_t)(g.next() >> 5), b = (int32_t)(g.next() >> 6);
-  return (a * 67108864.0 + b) / 9007199254740992.0;
+  const uint32_t w0 = g.next();
+  const uint32_t w1 = g.next();
+  return u53_words(w0, w1);
 }
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): a keyed
@@ -272,7 +277,41 @@ QT_SAMPLER_HD inline void philox_multinomial_row(uint64_t seed, uint64_t global_
   o[K - 1] = dn > 0 ? dn : 0;
 }
 
+// The random numbers of a Metropolis-Hastings chain, defined by index (qt_mhmc_draws / qt_mhmc_state_hits): step j of
+// chain c owns the Philox stream (seed, row = c, substream = 1 + j) -- substream 0 is the multinomial sampler's -- and
+// reads it by block, not in order: block q < D/2 (ctr[0] = q, words w0..w3) holds the pair of increments 2q, 2q + 1,
+//   u1 = u53(w0, w1),  u2 = u53(w2, w3),  r = sqrt(-2 log(1 - u1)),  delta[2q] = r cos(2 pi u2),  delta[2q + 1] = r sin(2 pi u2)
+// (Box-Muller; u53 = u53_words, the 53-bit double of uniform53), and block q = D/2 the step's uniform u53(w0, w1).
+// `l` < D: the increment of parameter l; l == D: the uniform.  A pure function of (seed, c, j, l): whoever computes it,
+// on the host or on any lane of any launch, gets the same number (the libm / device math functions agree to a few ulp
+// in the increments; the uniforms are exact).
+QT_SAMPLER_HD inline double mhmc_draw(uint64_t seed, uint64_t chain, uint32_t step, int D, int l) {
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  const uint32_t ctr[4] = {(uint32_t)(l >> 1), (uint32_t)chain, (uint32_t)(chain >> 32), 1u + step};
+  uint32_t w[4];
+  philox4x32_10(ctr, key, w);
+  const double u1 = u53_words(w[0], w[1]);
+  if (l == D) return u1;
+  const double r = sqrt(-2.0 * log(1.0 - u1));
+  const double phi = 6.283185307179586 * u53_words(w[2], w[3]);
+  return r * ((l & 1) ? sin(phi) : cos(phi));
+}
+
 #if defined(__HIPCC__)
+// deltas[C][T][D] and uniforms[C][T] of chains first_chain .. and steps first_step .. : one thread per number, through
+// mhmc_draw (the table the fused chain kernel never writes: for tests, and for feeding qt_mhmc_state)
+__global__ void __launch_bounds__(256) k_mhmc_draws(uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T, int D,
+                                                    double* __restrict__ deltas, double* __restrict__ uniforms) {
+  const size_t total = (size_t)C * T * (D + 1);
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const int l = (int)(t % (size_t)(D + 1));
+    const size_t cs = t / (size_t)(D + 1);  // c * T + s
+    const double v = mhmc_draw(seed, first_chain + cs / T, first_step + (uint32_t)(cs % T), D, l);
+    if (l == D) uniforms[cs] = v;
+    else deltas[cs * D + l] = v;
+  }
+}
+
 // Opt-in device sampler: row r (= resample r / period, setting r % period) is drawn by one thread from its own Philox
 // stream (seed, first_row + r), so the counts of a row depend on nothing but (seed, global row index, n, p): any
 // split of the rows over launches or ranks gives the same table.  out is [rows][K] int64, what the estimators read.

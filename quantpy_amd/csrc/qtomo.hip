@@ -1678,6 +1678,68 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
   return c.done();
 }
 
+// The two entries of the chain whose numbers are drawn on the device (qt_sampler::mhmc_draw): n <= 3
+static int mhmc_device_nq(const qt_handle_t* h, const char* fn) {
+  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 1..3 (got %d): the device-drawn chain has no n = 4, 5 kernel", fn, h->nq);
+  return 0;
+}
+
+int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T, double* deltas,
+                  double* uniforms, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = mhmc_device_nq(h, "qt_mhmc_draws")) return r;
+  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad mhmc_draws arguments");
+  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "qt_mhmc_draws: steps beyond 2^32 - 2");
+  if (C == 0 || T == 0) return 0;
+  double *dd, *du;
+  const size_t ct = (size_t)C * T;
+  if (int r = c.out(deltas, ct * h->D, &dd)) return r;
+  if (int r = c.out(uniforms, ct, &du)) return r;
+  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (h->D + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain,
+                     C, first_step, T, h->D, dd, du))
+    return r;
+  return c.done();
+}
+
+int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
+                       const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                       int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = mhmc_device_nq(h, "qt_mhmc_state_hits")) return r;
+  if (int r = need_povm(h)) return r;
+  if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
+      (C > 0 && (!counts || !centres || !x_init || !thresholds || !hits || !accepted)))
+    return fail(QT_ERR_ARG, "bad mhmc_state_hits arguments");
+  if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
+    return fail(QT_ERR_ARG, "qt_mhmc_state_hits: burn_steps + n_points * thinning must be below 2^32 - 1");
+  if (C == 0) return 0;
+  const int64_t* dc;
+  const double *dcen, *dx, *dthr;
+  int64_t *dh, *da;
+  double* ddist;
+  if (int r = c.in(counts, (size_t)C * h->M, &dc)) return r;
+  if (int r = c.in(centres, (size_t)C * h->D * 2, &dcen)) return r;
+  if (int r = c.in(x_init, (size_t)C * h->D, &dx)) return r;
+  if (int r = c.in(thresholds, (size_t)C, &dthr)) return r;
+  if (int r = c.out(hits, (size_t)C, &dh)) return r;
+  if (int r = c.out(accepted, (size_t)C, &da)) return r;
+  if (int r = c.out(dist, (size_t)C * n_points, &ddist)) return r;
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if constexpr (NQ <= 3) {
+          const Plan p = povm_plan<NQ>(h, C);
+          return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, dc, C, dcen, dx, dthr, seed, first_chain, (uint32_t)burn_steps,
+                        (uint32_t)n_points, (uint32_t)thinning, step, dh, da, ddist);
+        } else {
+          return 0;  // (refused above)
+        }
+      }))
+    return r;
+  return c.done();
+}
+
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
                  int32_t* nit, int32_t* nfev, double* fun, int32_t* status, int flags) {
   if (B > 0 && !rho) return fail(QT_ERR_ARG, "bad mle_batch arguments");

@@ -620,6 +620,63 @@ class Engine:
                                          _ptr(chain), _ptr(acc), _capi.QT_HOST_PTR))
         return (chain[0], acc[0]) if single else (chain, acc)
 
+    def mhmc_draws(self, seed, chains, steps, first_chain=0, first_step=0, out=None):
+        """The random numbers of `chains` Metropolis-Hastings chains drawn on the GPU (qt_mhmc_draws): (deltas
+        (chains, steps, D), uniforms (chains, steps)) of global chains first_chain .. and global steps first_step ..,
+        each number a function of (seed, chain, step, index) alone (include/qtomo.h states the formula) -- what
+        `mhmc_state` needs to run the chain of `mhmc_state_hits`.  NumPy arrays, or `out` = (deltas, uniforms) float64
+        torch CUDA tensors of those shapes, filled in stream order.  n <= 3."""
+        chains, steps = int(chains), int(steps)
+        if out is not None:
+            self._dev_call()
+            deltas, uniforms = out
+            assert deltas.numel() == chains * steps * self.D and uniforms.numel() == chains * steps
+            flags = _capi.QT_DEVICE_PTR
+        else:
+            deltas, uniforms = np.empty((chains, steps, self.D)), np.empty((chains, steps))
+            flags = _capi.QT_HOST_PTR
+        self._chk(self.lib.qt_mhmc_draws(self._h, int(seed), int(first_chain), chains, int(first_step), steps, _ptr(deltas),
+                                         _ptr(uniforms), flags))
+        return deltas, uniforms
+
+    def mhmc_state_hits(self, counts, centres, x_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain=0,
+                        return_dist=False):
+        """One Metropolis-Hastings chain per trial with its random numbers drawn on the device and nothing of the chain
+        stored (qt_mhmc_state_hits): chain i runs on counts[i] from x_init[i] (`chol_param(centres[i])`) with the numbers
+        of global chain first_chain + i (`mhmc_draws`), `burn_steps` steps and then n_points * thinning of which every
+        `thinning`-th state, from the first, is kept.  Returns (hits, accepted): hits[i] = the kept states whose
+        Hilbert-Schmidt distance to centres[i] lies strictly below thresholds[i], accepted[i] = the accepted post-burn
+        steps; with return_dist also the kept distances (C, n_points).  counts (C, S, K), centres (C, d, d) complex,
+        x_init (C, D), thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in stream order).
+        n <= 3."""
+        if _is_dev(counts):
+            import torch
+
+            self._dev_call()
+            flags = _capi.QT_DEVICE_PTR
+            nchain = counts.shape[0]
+            assert all(t.is_contiguous() for t in (counts, centres, x_init, thresholds))
+            assert counts.dtype == torch.int64 and centres.dtype == torch.complex128
+            assert x_init.dtype == torch.float64 and thresholds.dtype == torch.float64
+            assert centres.numel() == nchain * self.D and x_init.numel() == nchain * self.D and thresholds.numel() == nchain
+            hits = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
+            acc = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
+            dist = torch.empty((nchain, int(n_points)), dtype=torch.float64, device=counts.device) if return_dist else None
+        else:
+            flags = _capi.QT_HOST_PTR
+            counts = _i64(counts).reshape(-1, self.S, self.K)
+            nchain = counts.shape[0]
+            centres = _c128(centres).reshape(nchain, self.d, self.d)
+            x_init = _f64(x_init).reshape(nchain, self.D)
+            thresholds = _f64(thresholds).reshape(nchain)
+            hits = np.zeros(nchain, dtype=np.int64)
+            acc = np.zeros(nchain, dtype=np.int64)
+            dist = np.empty((nchain, int(n_points))) if return_dist else None
+        self._chk(self.lib.qt_mhmc_state_hits(self._h, _ptr(counts), nchain, _ptr(centres), _ptr(x_init), _ptr(thresholds),
+                                              int(seed), int(first_chain), int(burn_steps), int(n_points), int(thinning),
+                                              float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags))
+        return (hits, acc, dist) if return_dist else (hits, acc)
+
     def mle_dev(self, counts, rho, init="lin", max_iter=100, tol=1e-3, nit=None, nfev=None, fun=None, status=None):
         self._dev_call()
         self._chk(self.lib.qt_mle_batch(self._h, _ptr(counts), counts.shape[0],

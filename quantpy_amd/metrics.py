@@ -14,6 +14,10 @@ resamples and writes its distances, and `qt_group_hits` adds, per trial, how man
 to the truth.  Counts and distances never leave HBM; 8 * n_iter bytes come back.
 
 interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with the same rule.
+
+`get_CL_list_state_mhmc` is the reference's interval='mhmc' branch for states: one Metropolis-Hastings chain per trial, all
+of them in one launch that draws its own random numbers and returns, per trial, the hits and the accepted steps
+(`qt_mhmc_state_hits`).
 """
 import numpy as np
 
@@ -26,6 +30,7 @@ from .tomography.state import StateTomograph
 
 _INTERVALS = ("gamma", "boot", "mhmc")
 _CHUNK_BYTES = BootstrapProcessInterval._CHUNK_BYTES  # counts of one chunk of resamples
+_PD_FLOOR = 1e-13  # get_CL_list_state_mhmc: an estimate starts a chain when estimate - _PD_FLOOR * 1 has a Cholesky factor
 
 
 def levels_from_hits(hits, n_points):
@@ -48,8 +53,9 @@ def _check_arguments(interval, dst, n_iter, n_points, sampler, boot_methods, met
     if interval not in _INTERVALS:
         raise ValueError("Incorrect value for argument `interval`.")
     if interval == "mhmc":
-        raise NotImplementedError("interval='mhmc' (a chain per trial) is not implemented; supported: 'gamma'"
-                                  + (", 'boot'" if boot_methods else ""))
+        raise NotImplementedError("interval='mhmc' (a chain per trial) is not implemented here; supported: 'gamma'"
+                                  + (", 'boot'" if boot_methods else "")
+                                  + "; the chain study of a state is get_CL_list_state_mhmc")
     if interval == "boot" and not boot_methods:
         raise NotImplementedError("interval='boot' is not implemented by get_CL_list_channel (supported: 'gamma'); the "
                                   "bootstrap study of a channel is get_CL_list_channel_boot")
@@ -136,6 +142,69 @@ def get_CL_list_state(state, n_iter=1000, n_points=1000, interval="gamma", n_mea
     hits = _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
                    seed=key)
+
+
+def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=1000, method="lin", povm="proj-set", init="lin",
+                           tol=1e-3, max_iter=100, step=0.01, burn_steps=1000, thinning=1, *, sampler="device", seed=None,
+                           return_details=False):
+    """The interval='mhmc', dst='hs' branch of the reference's get_CL_list_state (metrics.py:125-144; parameters as
+    there): `n_iter` experiments, for each a Metropolis-Hastings chain of the likelihood on the Cholesky parameters around
+    ITS OWN point estimate (MHMCStateInterval: `burn_steps` steps, then n_points * thinning of which every `thinning`-th
+    state is a sample), and the level at which the true state leaves the interval of the sampled distances.  Returns the
+    sorted levels.  (`get_CL_list_state(interval='mhmc')` keeps its refusal; this is the study's name.)
+
+    All chains of this rank's `shard_bounds(n_iter)` run in ONE launch (`Engine.mhmc_state_hits`): the proposal increments
+    and uniforms are drawn on the device, the distance of every sample to the trial's estimate is formed where the state
+    is held and compared with delta_t = hs_dst(estimate_t, state); per trial, the number of hits and of accepted steps come
+    back.  Keying: Philox key (resolve_seed(seed) + 1) mod 2^64, chain = trial index t, step = burn-in first, then the
+    sampling steps (include/qtomo.h: qt_mhmc_draws) -- the numbers of a trial depend neither on the number of ranks nor on
+    its place in a batch, and never on np.random: the reference's stream is not reproduced.  The level of trial t is
+    `levels_from_hits(hits_t, n_points)`.
+
+    The chain starts at the Cholesky factor of the estimate, so an estimate that is not positive definite raises
+    np.linalg.LinAlgError (on every rank), where the reference fails in scipy.linalg.cholesky.  The study is stricter than
+    that call and than MHMCStateInterval, which start a chain wherever the factorisation goes through (`chol_param` status
+    0): it asks for a factor of estimate - `_PD_FLOOR` * 1 (one more `chol_param` of the batch), that is, for a smallest
+    eigenvalue above 1e-13.  The clipped 'lin' estimates of a rank-deficient state (a pure state, say) are such trials:
+    the clip leaves them eigenvalues of 1e-15, which a factorisation in double precision takes or refuses by the sign of
+    a rounding error.  (1e-13 is the size below which `qt_chol_param` stops trusting a pivot: a hundred times the clip,
+    and far below the eigenvalues of an estimate of a full-rank state.)  Use a mixed state, or method='mle' on one.
+
+    `sampler`, `seed`, `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the
+    accepted post-burn steps / (n_points * thinning), the reference's definition."""
+    _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
+    n_iter, n_points, burn_steps, thinning = int(n_iter), int(n_points), int(burn_steps), int(thinning)
+    if thinning < 1:
+        raise ValueError("thinning must be a positive integer")
+    if burn_steps < 0:
+        raise ValueError("burn_steps must not be negative")
+    if burn_steps + n_points * thinning >= 2**32 - 1:
+        raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
+    tmg = StateTomograph(state, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
+    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
+    if info is not None and np.any(info["status"] == 1):
+        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
+    eng = tmg._engine()
+    delta = eng.hs_dist(rho, state.matrix)
+    x0, status = eng.chol_param(rho)
+    # ... and none for the estimate less the floor: its smallest eigenvalue is not above _PD_FLOOR (a NaN is refused too)
+    _, shifted = eng.chol_param(rho - _PD_FLOOR * np.eye(rho.shape[-1]))
+    bad = (status != 0) | (shifted != 0)
+    if np.any(bad):  # (the same estimates on every rank: all raise, or none)
+        raise np.linalg.LinAlgError(f"the estimate of trial {int(np.flatnonzero(bad)[0])} is not positive definite: "
+                                    "no Cholesky factor to start its chain from")
+    key = (base + 1) & (2**64 - 1)
+    lo, hi = qdist.shard_bounds(n_iter)
+    both = np.zeros((2, n_iter), dtype=np.int64)
+    if hi > lo:
+        both[0, lo:hi], both[1, lo:hi] = eng.mhmc_state_hits(counts[lo:hi], rho[lo:hi], x0[lo:hi], delta[lo:hi], key,
+                                                             burn_steps, n_points, thinning, step, first_chain=lo)
+    if qdist.world()[1] > 1:
+        both = qdist.allgather_equal(both).sum(0)
+    hits, accepted = both
+    return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
+                   seed=key, acceptance_rate=accepted / (n_points * thinning))
 
 
 def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk):
