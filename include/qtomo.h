@@ -437,6 +437,35 @@ int qt_pgdb_pieces(qt_handle_t* h, const int64_t* counts, int B, const double* c
  * chain[C][T][D][D][2] = Choi matrix after every step, accepted[C][T]. */
 int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* choi_init, const double* deltas,
                     const double* uniforms, int T, double step, double* chain, int32_t* accepted, int flags);
+
+/* The random numbers of such a chain drawn on the device: the definition stated at qt_mhmc_draws with the vector length
+ * D replaced by D^2 (D = 4^n, the Choi vector has D^2 real increments).  Global step j of global chain c owns the
+ * Philox4x32-10 stream (key = seed, row = c, substream = 1 + j), counter {q, c low, c high, 1 + j}: block q < D^2/2 holds
+ * the increments of the column-stacked entries 2q and 2q + 1 (Box-Muller, as there), block q = D^2/2 the step's uniform
+ * u53(w0, w1).  This keying is ABI.  A state chain (qt_mhmc_draws) and a process chain with the same (seed, chain) read
+ * overlapping Philox blocks -- blocks q < D/2 of a step are the same words in both, and the state chain's uniform is the
+ * u1 of the process chain's block D/2 -- so their numbers are NOT independent: never run both under one key (the studies
+ * of metrics do not: each derives its key from its own seed and runs one kind of chain).
+ * Both entries need qt_set_povm* and qt_process_setup, and n <= 2 (n = 3, whose chain is four launches per step:
+ * QT_ERR_UNSUPPORTED before any launch).
+ *
+ * qt_mhmc_process_draws: the numbers of qt_mhmc_process_hits written out, deltas[C][T][D*D], uniforms[C][T] of chains
+ * first_chain .. first_chain+C-1, steps first_step .. first_step+T-1 (first_step + T >= 2^32 - 1: QT_ERR_ARG; C = 0 or
+ * T = 0 returns 0) -- what qt_mhmc_process needs to run the same chain. */
+int qt_mhmc_process_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
+                          double* deltas, double* uniforms, int flags);
+/* C chains, chain i on counts[i][D][S][K] from choi_init[i][D][D][2], numbers as above for global chain first_chain + i,
+ * the steps those of qt_mhmc_process (one device function).  After the burn-in, post-burn step s is kept when
+ * s % thinning == 0 (mhmc.py:80-84).  Of the kept states X,
+ *   hits[i] = #{ thresholds[i] > hs_dst(Re(X), centres[i]) }   (strict: a NaN never counts),
+ * the distance of the REAL PART (mhmc.py:66 stores the samples in a real array) formed as qt_hs_dist_dim forms it:
+ * Delta = Re(X) - centre, sqrt(|sum_ij Delta_ij Delta_ji|) / sqrt(2), 0 below 1e-15.  accepted[i] = accepted post-burn
+ * steps; dist[C][n_points] NULLABLE = the kept distances in chain order.  centres[C][D][D][2], thresholds[C].
+ * burn_steps >= 0, n_points >= 0, thinning >= 1 and burn_steps + n_points * thinning < 2^32 - 1, else QT_ERR_ARG;
+ * C = 0 returns 0 without a launch. */
+int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
+                         const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                         int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags);
 /* projections alone (process.py:231-278): mode 0 = CPTP (Dykstra), 1 = TP, 2 = CP */
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol,
                           double* choi_out, int32_t* iters, int flags);

@@ -98,6 +98,9 @@ SIGNATURES = {
     "qt_lifp_dist_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int]),
     "qt_pgdb_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _c_int, _vp, _vp, _vp, _c_int]),
     "qt_mhmc_process": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_dbl, _vp, _vp, _c_int]),
+    "qt_mhmc_process_draws": (_c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _c_int, ctypes.c_uint32, _c_int, _vp, _vp, _c_int]),
+    "qt_mhmc_process_hits": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _c_int, _c_int, _c_int,
+                                      _c_dbl, _vp, _vp, _vp, _c_int]),
     "qt_cptp_project_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_int]),
 }
 

@@ -564,36 +564,31 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_pgdb_batch(const int64_t*
 //   x' = P_CPTP(x + step * delta_t)      (delta real, added entry by entry to the column-stacked vector)
 // and accepts iff u_t <= exp(nll(x) - nll(x')), nll = -sum n log(A x + 1e-12) (process.py:310-314; the
 // complex logarithm enters through its real part, as NumPy orders complex numbers by it).
-// One workgroup per chain; chain_out[c][t] = Choi matrix (row-major) after step t.
+// One workgroup per chain.  ProcChain is what a chain's workgroup holds besides its point: the LDS of the projection, the
+// column-stacked image of a matrix (cre, cim), the raw counts and the model's probabilities (cnt, pr: dynamic LDS), and
+// this thread's element (i, j) with its place v_own in the column-stacked vector.
 template <int DC>
-__global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process(const int64_t* __restrict__ counts, int C, int M,
-                                                                const double* __restrict__ lifp,
-                                                                const double* __restrict__ choi_init,
-                                                                const double* __restrict__ deltas,
-                                                                const double* __restrict__ uniforms, int T_steps,
-                                                                double step, double* __restrict__ chain_out,
-                                                                int32_t* __restrict__ accepted) {
+struct ProcChain {
   using W = ProcWG<DC>;
-  constexpr int NE = W::NE, NT = W::NT, NW = NT / 64;
-  __shared__ typename W::Sh sh;
-  __shared__ double cre[NE], cim[NE];
-  extern __shared__ double dynsh[];  // cnt[R] | p[R]
-  const int R = DC * M;
-  double* cnt = dynsh;
-  double* pr = cnt + R;
-  const int b = blockIdx.x;
-  if (b >= C) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool act = tid < NE;
-  const int i = tid / DC, j = tid % DC;
-  const int v_own = j * DC + i;
-  for (int r = tid; r < R; r += NT) cnt[r] = (double)counts[(size_t)b * R + r];
-  double xr = 0.0, xi = 0.0;
-  if (act) {
-    xr = choi_init[((size_t)b * NE + tid) * 2];
-    xi = choi_init[((size_t)b * NE + tid) * 2 + 1];
+  static constexpr int NE = W::NE, NT = W::NT, NW = NT / 64;
+  typename W::Sh& sh;
+  double *cre, *cim;  // [NE], index v
+  double *cnt, *pr;   // [R]
+  const double* __restrict__ lifp;
+  int R, tid, i, j, v_own;
+  bool act;
+
+  __device__ __forceinline__ ProcChain(typename W::Sh& sh_, double* cre_, double* cim_, double* dynsh, const double* lifp_, int M)
+      : sh(sh_), cre(cre_), cim(cim_), cnt(dynsh), pr(dynsh + DC * M), lifp(lifp_), R(DC * M), tid(threadIdx.x),
+        i(threadIdx.x / DC), j(threadIdx.x % DC), v_own((threadIdx.x % DC) * DC + threadIdx.x / DC), act(threadIdx.x < NE) {}
+
+  __device__ __forceinline__ void load_counts(const int64_t* __restrict__ counts_b) const {
+    for (int r = tid; r < R; r += NT) cnt[r] = (double)counts_b[r];
   }
-  auto nll_of = [&](double er, double ei) {  // nll of the matrix whose element (i, j) this thread passes in
+
+  // nll of the matrix whose element (i, j) this thread passes in
+  __device__ __forceinline__ double nll_of(double er, double ei) const {
+    const int lane = tid & 63, wave = tid >> 6;
     __syncthreads();
     if (act) {
       cre[v_own] = er;
@@ -611,25 +606,148 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process(const int64_
     double part = 0.0;
     for (int r = tid; r < R; r += NT) part += cnt[r] * log(fabs(pr[r] + 1e-12));
     return -block_sum<NT>(part, sh.red);
-  };
-  double f = nll_of(xr, xi);
-  for (int t = 0; t < T_steps; ++t) {
+  }
+
+  // One step, the one body of both kernels below.  delta: the increment of this thread's entry (read by active threads
+  // only); uniform(): the step's u, asked for behind the projection and the NLL, so that a kernel which draws it does
+  // not carry it through them.  (xr, xi), f: the point and its NLL, replaced on acceptance.  Executed by every thread.
+  template <class U>
+  __device__ __forceinline__ bool step(double step, double delta, U&& uniform, double& xr, double& xi, double& f) const {
     double pr_ = xr, pi_ = xi;
-    if (act) pr_ += step * deltas[((size_t)b * T_steps + t) * NE + v_own];
+    if (act) pr_ += step * delta;
     W::dykstra(sh, act, i, j, pr_, pi_, 1000, 1e-12);
     const double fn = nll_of(pr_, pi_);
-    const bool acc = uniforms[(size_t)b * T_steps + t] <= exp(f - fn);
+    const bool acc = uniform() <= exp(f - fn);
     if (acc) {
       xr = pr_;
       xi = pi_;
       f = fn;
     }
+    return acc;
+  }
+
+  // hs_dst(Re(X), centre) as k_hs_dist forms it from the real parts of a chain state (mhmc.py:66 keeps the samples in a
+  // real array): Delta = Re(X) - centre, sqrt(|sum_ij Delta_ij Delta_ji|) / sqrt(2), 0 below 1e-15.  xr = this thread's
+  // Re(X_ij); X_ji comes through the column-stacked image.  Every thread returns the same bits.
+  __device__ __forceinline__ double real_part_dist(double xr, const double* __restrict__ centre) const {
+    __syncthreads();
+    if (act) cre[v_own] = xr;
+    __syncthreads();
+    double two[2] = {0.0, 0.0};
+    if (act) {
+      const cd dl{xr - centre[2 * tid], 0.0 - centre[2 * tid + 1]};
+      const cd dt{cre[tid] - centre[2 * v_own], 0.0 - centre[2 * v_own + 1]};  // cre[tid]: element (j, i)
+      const cd t = hs_term(dl, dt);
+      two[0] = t.re;
+      two[1] = t.im;
+    }
+    block_sums<NT, 2>(two, sh.red6);
+    const double v = sqrt(hypot(two[0], two[1])) / sqrt(2.0);
+    return v < 1e-15 ? 0.0 : v;
+  }
+};
+
+// The increments and the uniforms read from memory: chain_out[c][t] = Choi matrix (row-major) after step t,
+// accepted[c][t] = 0 / 1.
+template <int DC>
+__global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process(const int64_t* __restrict__ counts, int C, int M,
+                                                                const double* __restrict__ lifp,
+                                                                const double* __restrict__ choi_init,
+                                                                const double* __restrict__ deltas,
+                                                                const double* __restrict__ uniforms, int T_steps,
+                                                                double step, double* __restrict__ chain_out,
+                                                                int32_t* __restrict__ accepted) {
+  using W = ProcWG<DC>;
+  constexpr int NE = W::NE;
+  __shared__ typename W::Sh sh;
+  __shared__ double cre[NE], cim[NE];
+  extern __shared__ double dynsh[];  // cnt[R] | p[R]
+  const int b = blockIdx.x;
+  if (b >= C) return;
+  const ProcChain<DC> c(sh, cre, cim, dynsh, lifp, M);
+  const int tid = c.tid;
+  const bool act = c.act;
+  c.load_counts(counts + (size_t)b * c.R);
+  double xr = 0.0, xi = 0.0;
+  if (act) {
+    xr = choi_init[((size_t)b * NE + tid) * 2];
+    xi = choi_init[((size_t)b * NE + tid) * 2 + 1];
+  }
+  double f = c.nll_of(xr, xi);
+  for (int t = 0; t < T_steps; ++t) {
+    const double dl = act ? deltas[((size_t)b * T_steps + t) * NE + c.v_own] : 0.0;
+    const bool acc = c.step(step, dl, [&] { return uniforms[(size_t)b * T_steps + t]; }, xr, xi, f);
     if (act) {
       double* out = chain_out + (((size_t)b * T_steps + t) * NE + tid) * 2;
       out[0] = xr;
       out[1] = xi;
     }
     if (tid == 0) accepted[(size_t)b * T_steps + t] = acc ? 1 : 0;
+  }
+}
+
+// The chain of the coverage study (metrics.get_CL_list_channel_mhmc): the same steps on numbers the threads draw themselves
+// (qt_sampler::mhmc_draw with vector length NE: thread (i, j) the increment of its entry v = j DC + i, index NE the step's
+// uniform; global chain first_chain + b, global step = burn-in steps first, then the n_points * thinning sampling steps),
+// and of the chain only three numbers per chain leave the workgroup.  Post-burn step s is kept when s % thinning == 0
+// (mhmc.py:80-84); on a kept step the workgroup forms the distance of the REAL PART of its point to centres[b]
+// (real_part_dist):
+//   hits[b] = #{ kept : thresholds[b] > distance }  (strict: a NaN never counts),  accepted[b] = accepted post-burn steps,
+//   dist[b][k] (nullable) = the distance of kept state k.
+// Every thread counts (the decisions are uniform over the workgroup); thread 0 stores.
+template <int DC>
+__global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process_hits(const int64_t* __restrict__ counts, int C, int M,
+                                                                     const double* __restrict__ lifp,
+                                                                     const double* __restrict__ choi_init,
+                                                                     const double* __restrict__ centres,
+                                                                     const double* __restrict__ thresholds, uint64_t seed,
+                                                                     uint64_t first_chain, uint32_t burn_steps,
+                                                                     uint32_t n_points, uint32_t thinning, double step,
+                                                                     int64_t* __restrict__ hits, int64_t* __restrict__ accepted,
+                                                                     double* __restrict__ dist) {
+  using W = ProcWG<DC>;
+  constexpr int NE = W::NE;
+  __shared__ typename W::Sh sh;
+  __shared__ double cre[NE], cim[NE];
+  extern __shared__ double dynsh[];  // cnt[R] | p[R]
+  const int b = blockIdx.x;
+  if (b >= C) return;
+  const ProcChain<DC> c(sh, cre, cim, dynsh, lifp, M);
+  const int tid = c.tid;
+  const bool act = c.act;
+  c.load_counts(counts + (size_t)b * c.R);
+  double xr = 0.0, xi = 0.0;
+  if (act) {
+    xr = choi_init[((size_t)b * NE + tid) * 2];
+    xi = choi_init[((size_t)b * NE + tid) * 2 + 1];
+  }
+  double f = c.nll_of(xr, xi);
+  const uint64_t gc = first_chain + (uint64_t)b;
+  const double* centre = centres + (size_t)b * NE * 2;
+  const double thr = thresholds[b];
+  auto one_step = [&](uint32_t jglob) {
+    const double dl = act ? qt_sampler::mhmc_draw(seed, gc, jglob, NE, c.v_own) : 0.0;
+    return c.step(step, dl, [&] { return qt_sampler::mhmc_draw(seed, gc, jglob, NE, NE); }, xr, xi, f);
+  };
+  uint32_t j = 0;
+  for (; j < burn_steps; ++j) one_step(j);
+  int64_t n_hit = 0, n_acc = 0;
+  uint32_t kept = 0, to_keep = 0;              // to_keep: steps until the next kept one
+  const uint32_t total = n_points * thinning;  // (< 2^32 - 1 with the burn-in: checked by the entry)
+  for (uint32_t s = 0; s < total; ++s, ++j) {
+    n_acc += one_step(j);
+    if (to_keep == 0) {  // (launch-uniform)
+      const double v = c.real_part_dist(xr, centre);
+      n_hit += thr > v;
+      if (dist && tid == 0) dist[(size_t)b * n_points + kept] = v;
+      ++kept;
+      to_keep = thinning;
+    }
+    --to_keep;
+  }
+  if (tid == 0) {
+    hits[b] = n_hit;
+    accepted[b] = n_acc;
   }
 }
 

@@ -2560,6 +2560,72 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
   return c.done();
 }
 
+// The two entries of the process chain whose numbers are drawn on the device (qt_sampler::mhmc_draw with vector length
+// D^2): n <= 2, the one-workgroup chain of qt_process.h
+static int mhmc_process_device_nq(const qt_handle_t* h, const char* fn) {
+  if (h->nq > 2)
+    return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 1..2 (got %d): the device-drawn process chain has no n = 3 kernel", fn,
+                h->nq);
+  return 0;
+}
+
+int qt_mhmc_process_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
+                          double* deltas, double* uniforms, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = mhmc_process_device_nq(h, "qt_mhmc_process_draws")) return r;
+  if (int r = need_povm(h)) return r;
+  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad mhmc_process_draws arguments");
+  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "qt_mhmc_process_draws: steps beyond 2^32 - 2");
+  if (C == 0 || T == 0) return 0;
+  double *dd, *du;
+  const size_t ct = (size_t)C * T;
+  const int ne = h->D * h->D;
+  if (int r = c.out(deltas, ct * ne, &dd)) return r;
+  if (int r = c.out(uniforms, ct, &du)) return r;
+  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (ne + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain, C,
+                     first_step, T, ne, dd, du))
+    return r;
+  return c.done();
+}
+
+int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
+                         const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                         int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (int r = mhmc_process_device_nq(h, "qt_mhmc_process_hits")) return r;
+  if (int r = need_povm(h)) return r;
+  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+  if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
+      (C > 0 && (!counts || !centres || !choi_init || !thresholds || !hits || !accepted)))
+    return fail(QT_ERR_ARG, "bad mhmc_process_hits arguments");
+  if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
+    return fail(QT_ERR_ARG, "qt_mhmc_process_hits: burn_steps + n_points * thinning must be below 2^32 - 1");
+  if (C == 0) return 0;
+  const int D = h->D, M = h->M;
+  const size_t ne = (size_t)D * D;
+  const size_t dyn = (size_t)2 * D * M * sizeof(double);
+  if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
+  const int64_t* dc;
+  const double *dcen, *dx, *dthr;
+  int64_t *dh, *da;
+  double* ddist;
+  if (int r = c.in(counts, (size_t)C * D * M, &dc)) return r;
+  if (int r = c.in(centres, (size_t)C * ne * 2, &dcen)) return r;
+  if (int r = c.in(choi_init, (size_t)C * ne * 2, &dx)) return r;
+  if (int r = c.in(thresholds, (size_t)C, &dthr)) return r;
+  if (int r = c.out(hits, (size_t)C, &dh)) return r;
+  if (int r = c.out(accepted, (size_t)C, &da)) return r;
+  if (int r = c.out(dist, (size_t)C * n_points, &ddist)) return r;
+  if (int r = launch(h, D == 4 ? qt::k_mhmc_process_hits<4> : qt::k_mhmc_process_hits<16>, dim3(C),
+                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, C, M, h->proc.lifp.as<double>(), dx, dcen, dthr,
+                     seed, first_chain, (uint32_t)burn_steps, (uint32_t)n_points, (uint32_t)thinning, step, dh, da, ddist))
+    return r;
+  return c.done();
+}
+
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol, double* choi_out,
                           int32_t* iters, int flags) {
   QT_ENTER(h);

@@ -395,6 +395,68 @@ class Engine:
                                            _ptr(chain), _ptr(acc), _capi.QT_HOST_PTR))
         return (chain[0], acc[0]) if single else (chain, acc)
 
+    def mhmc_process_draws(self, seed, chains, steps, first_chain=0, first_step=0, out=None):
+        """The random numbers of `chains` process chains drawn on the GPU (qt_mhmc_process_draws): (deltas
+        (chains, steps, D*D), uniforms (chains, steps)) of global chains first_chain .. and global steps first_step ..,
+        each number a function of (seed, chain, step, index) alone (include/qtomo.h states the formula: that of
+        `mhmc_draws` with the vector length D*D) -- what `mhmc_process` needs to run the chain of `mhmc_process_hits`.
+        NumPy arrays, or `out` = (deltas, uniforms) float64 torch CUDA tensors of those shapes, filled in stream order.
+        n <= 2, after `set_povm` and `process_setup`."""
+        chains, steps = int(chains), int(steps)
+        ne = self.D * self.D
+        if out is not None:
+            self._dev_call()
+            deltas, uniforms = out
+            assert deltas.numel() == chains * steps * ne and uniforms.numel() == chains * steps
+            flags = _capi.QT_DEVICE_PTR
+        else:
+            deltas, uniforms = np.empty((chains, steps, ne)), np.empty((chains, steps))
+            flags = _capi.QT_HOST_PTR
+        self._chk(self.lib.qt_mhmc_process_draws(self._h, int(seed), int(first_chain), chains, int(first_step), steps,
+                                                 _ptr(deltas), _ptr(uniforms), flags))
+        return deltas, uniforms
+
+    def mhmc_process_hits(self, counts, centres, choi_init, thresholds, seed, burn_steps, n_points, thinning, step,
+                          first_chain=0, return_dist=False):
+        """One Metropolis-Hastings chain per process with its random numbers drawn on the device and nothing of the
+        chain stored (qt_mhmc_process_hits): chain i runs on counts[i] from choi_init[i] with the numbers of global chain
+        first_chain + i (`mhmc_process_draws`), `burn_steps` steps and then n_points * thinning of which every
+        `thinning`-th state, from the first, is kept.  Returns (hits, accepted): hits[i] = the kept states whose real
+        part lies at a Hilbert-Schmidt distance to centres[i] strictly below thresholds[i], accepted[i] = the accepted
+        post-burn steps; with return_dist also the kept distances (C, n_points).  counts (C, D, S, K), centres and
+        choi_init (C, D, D) complex, thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in
+        stream order).  n <= 2."""
+        ne = self.D * self.D
+        if _is_dev(counts):
+            import torch
+
+            self._dev_call()
+            flags = _capi.QT_DEVICE_PTR
+            nchain = counts.shape[0]
+            assert all(t.is_contiguous() for t in (counts, centres, choi_init, thresholds))
+            assert counts.dtype == torch.int64 and centres.dtype == torch.complex128
+            assert choi_init.dtype == torch.complex128 and thresholds.dtype == torch.float64
+            assert counts.numel() == nchain * self.D * self.S * self.K
+            assert centres.numel() == nchain * ne and choi_init.numel() == nchain * ne and thresholds.numel() == nchain
+            hits = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
+            acc = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
+            dist = torch.empty((nchain, int(n_points)), dtype=torch.float64, device=counts.device) if return_dist else None
+        else:
+            flags = _capi.QT_HOST_PTR
+            counts = _i64(counts).reshape(-1, self.D, self.S, self.K)
+            nchain = counts.shape[0]
+            centres = _c128(centres).reshape(nchain, self.D, self.D)
+            choi_init = _c128(choi_init).reshape(nchain, self.D, self.D)
+            thresholds = _f64(thresholds).reshape(nchain)
+            hits = np.zeros(nchain, dtype=np.int64)
+            acc = np.zeros(nchain, dtype=np.int64)
+            dist = np.empty((nchain, int(n_points))) if return_dist else None
+        self._chk(self.lib.qt_mhmc_process_hits(self._h, _ptr(counts), nchain, _ptr(centres), _ptr(choi_init),
+                                                _ptr(thresholds), int(seed), int(first_chain), int(burn_steps),
+                                                int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc),
+                                                _ptr(dist), flags))
+        return (hits, acc, dist) if return_dist else (hits, acc)
+
     def lifp_dev(self, counts, choi, cptp=True, iters=None, status=None):
         self._dev_call()
         self._chk(self.lib.qt_lifp_batch(self._h, _ptr(counts), counts.shape[0], int(bool(cptp)), _ptr(choi), _ptr(iters),

@@ -17,7 +17,8 @@ interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with t
 
 `get_CL_list_state_mhmc` is the reference's interval='mhmc' branch for states: one Metropolis-Hastings chain per trial, all
 of them in one launch that draws its own random numbers and returns, per trial, the hits and the accepted steps
-(`qt_mhmc_state_hits`).
+(`qt_mhmc_state_hits`).  `get_CL_list_channel_mhmc` is the same branch for channels (n <= 2): a chain on the Choi vector
+per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.
 """
 import numpy as np
 
@@ -55,7 +56,8 @@ def _check_arguments(interval, dst, n_iter, n_points, sampler, boot_methods, met
     if interval == "mhmc":
         raise NotImplementedError("interval='mhmc' (a chain per trial) is not implemented here; supported: 'gamma'"
                                   + (", 'boot'" if boot_methods else "")
-                                  + "; the chain study of a state is get_CL_list_state_mhmc")
+                                  + ("; the chain study of a state is get_CL_list_state_mhmc" if boot_methods else
+                                     "; the chain study of a channel is get_CL_list_channel_mhmc"))
     if interval == "boot" and not boot_methods:
         raise NotImplementedError("interval='boot' is not implemented by get_CL_list_channel (supported: 'gamma'); the "
                                   "bootstrap study of a channel is get_CL_list_channel_boot")
@@ -288,8 +290,8 @@ def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n
                         return_details=False):
     """The same study for a channel and its Choi matrix (reference metrics.py:150-319; parameters as there), for
     interval='gamma': the process form of `MomentInterval.radii_batch` at np.linspace(0, 1, n_points).  'boot' and
-    'mhmc' raise NotImplementedError; the bootstrap study of a channel is `get_CL_list_channel_boot`.  `sampler`, `seed`,
-    `return_details` as in `get_CL_list_state`."""
+    'mhmc' raise NotImplementedError; the bootstrap study of a channel is `get_CL_list_channel_boot`, the chain study
+    `get_CL_list_channel_mhmc`.  `sampler`, `seed`, `return_details` as in `get_CL_list_state`."""
     _check_arguments(interval, dst, n_iter, n_points, sampler, (), method_boot)
     n_iter, n_points = int(n_iter), int(n_points)
     tmg = ProcessTomograph(channel, input_states, "hs")
@@ -339,3 +341,57 @@ def get_CL_list_channel_boot(channel, n_iter=1000, n_points=1000, n_measurements
         raise ValueError("a resampled process has no finite Choi matrix (an input state without counts)")
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
                    seed=key)
+
+
+def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",
+                             input_states="proj4", states_init="lin", states_est_method="lin", step=0.01, burn_steps=1000,
+                             thinning=1, *, sampler="device", seed=None, return_details=False):
+    """The interval='mhmc', dst='hs' branch of the reference's get_CL_list_channel (metrics.py:289-298; parameters as
+    there): `n_iter` process tomographies, for each a Metropolis-Hastings chain of the likelihood on the Choi vector around
+    ITS OWN estimate (MHMCProcessInterval with use_new_estimate=False: every proposal projected onto the CPTP set,
+    `burn_steps` steps, then n_points * thinning of which every `thinning`-th state is a sample, the samples' real parts
+    measured against the estimate), and the level at which the true Choi matrix leaves the interval of the sampled
+    distances.  Returns the sorted levels.  (`get_CL_list_channel(interval='mhmc')` keeps its refusal; this is the study's
+    name.)  One and two qubits: a channel of more qubits raises NotImplementedError.
+
+    The trials are formed as in `get_CL_list_channel_boot` (`point_estimate_batch` with its default cptp=True).  All
+    chains of this rank's `shard_bounds(n_iter)` run in ONE launch (`Engine.mhmc_process_hits`), chain t from its own
+    estimate, which is also its centre: the proposal increments and uniforms are drawn on the device, the distance of
+    every sample is formed where the state is held and compared with delta_t = hs_dst(estimate_t, Choi matrix of the
+    channel); per trial, the number of hits and of accepted steps come back.  Keying: Philox key
+    (resolve_seed(seed) + 1) mod 2^64, chain = trial index t, step = burn-in first, then the sampling steps
+    (include/qtomo.h: qt_mhmc_process_draws) -- the numbers of a trial depend neither on the number of ranks nor on its
+    place in a batch, and never on np.random.  The level of trial t is `levels_from_hits(hits_t, n_points)`.
+
+    An estimate that is not finite (an input state without counts) raises ValueError on every rank.  `sampler`, `seed`,
+    `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the accepted post-burn
+    steps / (n_points * thinning), the reference's definition."""
+    _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
+    n_iter, n_points, burn_steps, thinning = int(n_iter), int(n_points), int(burn_steps), int(thinning)
+    if thinning < 1:
+        raise ValueError("thinning must be a positive integer")
+    if burn_steps < 0:
+        raise ValueError("burn_steps must not be negative")
+    if burn_steps + n_points * thinning >= 2**32 - 1:
+        raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
+    if channel.n_qubits > 2:
+        raise NotImplementedError(f"get_CL_list_channel_mhmc runs channels of one and two qubits, not {channel.n_qubits}: "
+                                  "the chain of a three-qubit process has no fused kernel")
+    tmg = ProcessTomograph(channel, input_states, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
+    choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
+    if not np.all(np.isfinite(choi)):  # (the same estimates on every rank: all raise, or none)
+        raise ValueError("a trial has no finite Choi matrix (an input state without counts)")
+    eng = tmg._engine()
+    delta = eng.hs_dist(choi, channel.choi.matrix)
+    key = (base + 1) & (2**64 - 1)
+    lo, hi = qdist.shard_bounds(n_iter)
+    both = np.zeros((2, n_iter), dtype=np.int64)
+    if hi > lo:
+        both[0, lo:hi], both[1, lo:hi] = eng.mhmc_process_hits(counts[lo:hi], choi[lo:hi], choi[lo:hi], delta[lo:hi], key,
+                                                               burn_steps, n_points, thinning, step, first_chain=lo)
+    if qdist.world()[1] > 1:
+        both = qdist.allgather_equal(both).sum(0)
+    hits, accepted = both
+    return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
+                   seed=key, acceptance_rate=accepted / (n_points * thinning))
