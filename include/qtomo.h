@@ -234,6 +234,25 @@ int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, in
 /* the same for dim x dim matrices whatever the handle's n_qubits (Choi matrices of an n-qubit channel: dim = 4^n) */
 int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* centre, int B, double* dist, int flags);
 
+/* ---- quantpy/geometry.py:23-38 trace_dst, :41-56 if_dst, for a batch against a table of centres -------------------
+ * dist[b] = metric(rho_b, centres[(g0 + b) % G]); rho[B][d][d][2], centres[G][d][d][2] with d = 2^n the handle's
+ * dimension, n <= 3 (n = 4, 5: QT_ERR_UNSUPPORTED); needs no POVM.  G = 1, g0 = 0: one centre.  A table with g0 serves a
+ * resample-major batch that starts inside a resample (see qt_lin_dist_group_batch).
+ * Both arguments are taken to be HERMITIAN (the imaginary parts of the diagonals are dropped, the strict lower triangle of
+ * a matrix that is not Hermitian is not what the reference's sqrtm would see); each value comes from the eigenvalues of
+ * one Hermitian matrix per trial, by the Jacobi sweeps of the eigenvalue clip:
+ *   QT_METRIC_TRACE       sum_i |lambda_i(rho_b - centre)| / 2        (|Tr sqrtm(Delta Delta)| / 2 for Hermitian Delta)
+ *   QT_METRIC_INFIDELITY  1 - (sum_i sqrt(max(mu_i, 0)))^2, mu = eigenvalues of the Hermitian part of S rho_b S with
+ *                         S = the Hermitian root of the centre, negative eigenvalues clipped to 0, formed once per call
+ *                         and centre (fidelity is symmetric: the reference takes the root of its first argument)
+ * A value below 1e-15 -- small negative infidelities included -- is returned as 0, as the reference returns it.  A NaN
+ * (or an infinity) in rho_b or in its centre gives dist[b] = NaN and touches no other trial; a trial's bits depend on
+ * its two matrices alone, not on B, G, g0 or its place in the batch.
+ * QT_ERR_ARG: an unknown metric, G < 1, g0 outside [0, G), B < 0, a null array with B > 0.  B == 0 returns 0. */
+enum qt_metric { QT_METRIC_TRACE = 0, QT_METRIC_INFIDELITY = 1 };
+int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, int B, const double* centres, int G, int g0,
+                               double* dist, int flags);
+
 /* ---- a16: quantpy/tomography/interval.py:610-612 (and :683-685) -------------------------------- */
 /* `dist.sort()`: ascending in-place sort of n float64 values in np.sort's order (NaN last; bitonic in LDS up to 8192
  * values, device radix sort above).  The output is np.sort's by value, with canonical bits: either zero is written as

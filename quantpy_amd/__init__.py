@@ -11,7 +11,7 @@ from ._capi import EngineUnavailable  # noqa: F401
 from .base_quantum import BaseQuantum  # noqa: F401
 from .channel import Channel  # noqa: F401
 from .engine import Engine, EngineError, get_engine  # noqa: F401
-from .geometry import hs_dst, if_dst, product, trace_dst  # noqa: F401
+from .geometry import hs_dst, if_dst, if_dst_batch, product, trace_dst, trace_dst_batch  # noqa: F401
 from .measurements import generate_measurement_matrix  # noqa: F401
 from .operator import Operator  # noqa: F401
 from .qobj import Qobj  # noqa: F401

@@ -1254,27 +1254,35 @@ struct Small {
     return r;
   }
 
-  // ---- a7: eigenvalue clip + trace renormalisation by a parallel-order cyclic Jacobi.
-  // In: lane's element of a Hermitian matrix.  Out: lane's element of U max(v, eps) U^dagger / Tr.
+  // ---- the parallel-order cyclic Jacobi eigensolver behind a7 and the trace distance / infidelity.
+  // In: lane's element of a Hermitian matrix A (real diagonal) and of V (the identity, or a basis to carry along).
+  // Out: A' = J^dagger A J with its eigenvalues on the diagonal lanes, V' = V J.
   // Round r = 1 .. d-1 rotates the d/2 disjoint pairs (k, k ^ r): every pair once per sweep.  A
   // round is ONE LDS round trip: the lanes publish A and V, then each lane reads the two 2x2
   // blocks that define the rotations of its column pair {j, j^r} and row pair {i, i^r} together
   // with its three partner elements, and applies A' = J^dagger A J, V' = V J in registers.
-  template <class C>
-  __device__ static cd psd_project(const C& c, cd a, double eps) {
+  // The loop is left when no lane group of the wavefront has off^2 > jtol2 * ||A||_F^2 (a NaN compares false: such a
+  // matrix is never rotated), after 20 sweeps at the latest.
+  // OWN: a group whose own matrix has met the rule keeps its registers while its wavefront neighbours go on, so that a
+  // trial's bits depend on nothing but the trial (n = 3: one trial per wavefront, no difference).
+  // VEC = false: eigenvalues only, V is neither read nor written.
+  template <bool OWN = false, bool VEC = true, class C>
+  __device__ __forceinline__ static void jacobi_sweeps(const C& c, cd& a_io, cd& v_io) {
+    // (the loop runs on values of its own: on the caller's two objects three callers of psd_project allocate a register
+    // differently from the loop written out in psd_project)
+    cd a = a_io, v = v_io;
     const int i = c.i, j = c.j;
-    cd* Ai = c.A();
-    cd* Vi = c.V();
-    cd v{i == j ? 1.0 : 0.0, 0.0};
-    if (i == j) a.im = 0.0;
+    cd* const Ai = c.A();
+    cd* const Vi = c.V();
     const double nrm = gsum<G>(a.re * a.re + a.im * a.im);  // Frobenius norm: invariant
     for (int sweep = 0; sweep < 20; ++sweep) {
       const double off = gsum<G>(i != j ? a.re * a.re + a.im * a.im : 0.0);
-      if (__all(!(off > c.jtol2() * nrm))) break;
+      const bool met = !(off > c.jtol2() * nrm);  // this group's own matrix
+      if (__all(met)) break;
 #pragma unroll 1
       for (int r = 1; r < d; ++r) {
         Ai[c.e] = a;
-        Vi[c.e] = v;
+        if constexpr (VEC) Vi[c.e] = v;
         wave_sync();
         const int pj = j ^ r, pi = i ^ r;
         const int cp = j < pj ? j : pj, cq = j < pj ? pj : j;  // column pair, ordered
@@ -1284,7 +1292,8 @@ struct Small {
         const double r_pp = Ai[rp * LD + rp].re, r_qq = Ai[rq * LD + rq].re;
         const cd r_pq = Ai[rp * LD + rq];
         const cd a_c = Ai[i * LD + pj], a_r = Ai[pi * LD + j], a_x = Ai[pi * LD + pj];
-        const cd v_c = Vi[i * LD + pj];
+        cd v_c{0.0, 0.0};
+        if constexpr (VEC) v_c = Vi[i * LD + pj];
         wave_sync();  // all reads of this image are issued before the next round overwrites it
         double cj, ci;
         cd wj, wi;
@@ -1295,11 +1304,27 @@ struct Small {
         // A'_ij = ci (a_ij cj + a_i,pj wj) + conj(wi) (a_pi,j cj + a_pi,pj wj) ;  V' = V J
         const cd t0 = cadd(cscale(a, cj), cmul(a_c, wj));
         const cd t1 = cadd(cscale(a_r, cj), cmul(a_x, wj));
-        a = cadd(cscale(t0, ci), cmulc(t1, wi));
-        v = cadd(cscale(v, cj), cmul(v_c, wj));
+        const cd an = cadd(cscale(t0, ci), cmulc(t1, wi));
+        if (!(OWN && G < 64 && met)) {
+          a = an;
+          if constexpr (VEC) v = cadd(cscale(v, cj), cmul(v_c, wj));
+        }
         if (i == j) a.im = 0.0;
       }
     }
+    a_io = a;
+    v_io = v;
+  }
+
+  // ---- a7: eigenvalue clip + trace renormalisation.
+  // In: lane's element of a Hermitian matrix.  Out: lane's element of U max(v, eps) U^dagger / Tr.
+  template <class C>
+  __device__ static cd psd_project(const C& c, cd a, double eps) {
+    const int i = c.i, j = c.j;
+    cd* Vi = c.V();
+    cd v{i == j ? 1.0 : 0.0, 0.0};
+    if (i == j) a.im = 0.0;
+    jacobi_sweeps(c, a, v);
     // rebuild with clipped eigenvalues: R_ij = sum_k V_ik max(lam_k, eps) conj(V_jk)
     double* lam = c.lam();
     Vi[c.e] = v;
@@ -1316,6 +1341,102 @@ struct Small {
     const double tr = gsum<G>(i == j ? rr.re : 0.0);
     wave_sync();
     return cd{rr.re / tr, rr.im / tr};
+  }
+
+  // ---- trace distance and infidelity (geometry.py:23-38, 41-56) of Hermitian matrices, by the sweeps above: both are
+  // symmetric functions of the eigenvalues of ONE Hermitian matrix per trial.  No POVM is read and the scratch of a lane
+  // group is two matrix images, so these have a context of their own (k_psd_sqrt, k_metric_dist).
+  static constexpr int kMetricDoubles = 2 * MAT;  // per trial: images X / A and Y / V
+  struct CtxM {
+    int l, i, j, e;
+    double* sm;
+    double tol2;
+    __device__ __forceinline__ cd* A() const { return reinterpret_cast<cd*>(sm); }
+    __device__ __forceinline__ cd* V() const { return reinterpret_cast<cd*>(sm + MAT); }
+    __device__ __forceinline__ double jtol2() const { return tol2; }
+  };
+  __device__ __forceinline__ static void make_ctx_metric(CtxM& c, double* smem_block, double jtol2) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    c.l = lane % G;
+    c.i = c.l / d;
+    c.j = c.l % d;
+    c.e = c.i * LD + c.j;
+    c.sm = smem_block + (wave * TPW + lane / G) * kMetricDoubles;
+    c.tol2 = jtol2;
+  }
+  // What a distance becomes when its matrix holds a NaN or an infinity (the sweeps never rotate such a matrix, so its
+  // diagonal says nothing): n2 = the squared Frobenius norm of the matrix the sweeps were given.
+  __device__ __forceinline__ static double finite_or_nan(double n2, double val) {
+    return n2 < __builtin_inf() ? val : __builtin_nan("");
+  }
+  // geometry.py:23-38 for Hermitian arguments: |Tr sqrt(Delta^2)| / 2 = sum_i |lambda_i(Delta)| / 2, Delta = R - C with
+  // the imaginary parts of its diagonal dropped (as psd_project drops them); 0 below 1e-15.  In: the lane's elements of
+  // R and C.  Every lane of the group returns the same bits.
+  template <class C>
+  __device__ static double trace_dist(const C& c, cd r, cd cen) {
+    cd a{r.re - cen.re, c.i == c.j ? 0.0 : r.im - cen.im}, v{0.0, 0.0};
+    const double n2 = gsum<G>(a.re * a.re + a.im * a.im);
+    jacobi_sweeps<true, false>(c, a, v);
+    const double val = 0.5 * gsum<G>(c.i == c.j ? fabs(a.re) : 0.0);
+    return finite_or_nan(n2, val < 1e-15 ? 0.0 : val);
+  }
+  // The Hermitian root of a Hermitian matrix with its negative eigenvalues clipped to 0: sum_k V_ik sqrt(max(lam_k, 0))
+  // conj(V_jk), real on the diagonal.  NaN throughout for a matrix that holds a NaN or an infinity.
+  template <class C>
+  __device__ static cd psd_sqrt(const C& c, cd a) {
+    const int i = c.i, j = c.j;
+    cd* Ai = c.A();
+    cd* Vi = c.V();
+    cd v{i == j ? 1.0 : 0.0, 0.0};
+    if (i == j) a.im = 0.0;
+    const double n2 = gsum<G>(a.re * a.re + a.im * a.im);
+    jacobi_sweeps<true>(c, a, v);
+    Ai[c.e] = a;
+    Vi[c.e] = v;
+    wave_sync();
+    cd rr{0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < d; ++k) {
+      const double lam = Ai[k * LD + k].re;
+      const double w = sqrt(lam > 0.0 ? lam : 0.0);
+      const cd p = cmulc(Vi[i * LD + k], Vi[j * LD + k]);
+      rr.re += w * p.re;
+      rr.im += w * p.im;
+    }
+    wave_sync();
+    if (i == j) rr.im = 0.0;
+    return cd{finite_or_nan(n2, rr.re), finite_or_nan(n2, rr.im)};
+  }
+  // geometry.py:41-56 for Hermitian arguments: 1 - (Tr sqrt(S R S))^2 = 1 - (sum_i sqrt(max(mu_i, 0)))^2 with S = sqrt(C)
+  // (psd_sqrt; fidelity is symmetric, so the root of the centre stands in for the reference's root of its first
+  // argument) and mu the eigenvalues of the Hermitian part of M = S R S; 0 below 1e-15, small negatives included.
+  // In: the lane's elements of R and S.  M is formed by two d x d products through the group's two images.
+  template <class C>
+  __device__ static double infidelity(const C& c, cd r, cd s) {
+    const int i = c.i, j = c.j;
+    cd* X = c.A();
+    cd* Y = c.V();
+    X[c.e] = s;
+    Y[c.e] = r;
+    wave_sync();
+    cd t{0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < d; ++k) t = cadd(t, cmul(X[i * LD + k], Y[k * LD + j]));  // T = S R
+    wave_sync();
+    Y[c.e] = t;
+    wave_sync();
+    cd m{0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < d; ++k) m = cadd(m, cmul(Y[i * LD + k], X[k * LD + j]));  // M = T S
+    wave_sync();
+    const int src = (int)(threadIdx.x & 63) - c.l + j * d + i;  // the lane of element (j, i)
+    const cd mt{__shfl(m.re, src, 64), __shfl(m.im, src, 64)};
+    cd a{0.5 * (m.re + mt.re), i == j ? 0.0 : 0.5 * (m.im - mt.im)}, v{0.0, 0.0};
+    const double n2 = gsum<G>(a.re * a.re + a.im * a.im);
+    jacobi_sweeps<true, false>(c, a, v);
+    const double rf = gsum<G>(i == j ? sqrt(a.re > 0.0 ? a.re : 0.0) : 0.0);
+    const double val = 1.0 - rf * rf;
+    return finite_or_nan(n2, val < 1e-15 ? 0.0 : val);
   }
 
   // ---- a8: lower Cholesky factor of the matrix whose element this lane holds.
@@ -2077,6 +2198,50 @@ __global__ void __launch_bounds__(256) k_chol_unparam(PovmView pv, const double*
     out[0] = m.re;
     out[1] = m.im;
   }
+}
+
+// Trace distance / infidelity of a batch to a table of centres (geometry.py:23-56; Small::trace_dist, Small::infidelity).
+enum Metric { kMetricTrace = 0, kMetricInfidelity = 1 };
+
+// roots[g] = the Hermitian root of centres[g] (Small::psd_sqrt), g < G: the set-up launch of the infidelity, once per call
+template <int NQ>
+__global__ void __launch_bounds__(256) k_psd_sqrt(const double* __restrict__ centres, int G, double jtol2,
+                                                  double* __restrict__ roots) {
+  using S = Small<NQ>;
+  __shared__ __attribute__((aligned(16))) double smem[S::TPB * S::kMetricDoubles];
+  typename S::CtxM c;
+  S::make_ctx_metric(c, smem, jtol2);
+  bool live;
+  const int g = S::trial_index(G, &live);
+  const int gg = live ? g : G - 1;
+  const double* in = centres + ((size_t)gg * S::D + c.l) * 2;
+  const cd s = S::psd_sqrt(c, cd{in[0], in[1]});
+  if (live) {
+    double* out = roots + ((size_t)g * S::D + c.l) * 2;
+    out[0] = s.re;
+    out[1] = s.im;
+  }
+}
+
+// dist[b] = METRIC(rho[b], centre (g0 + b) % G).  `centres`: the centres themselves (trace distance) or their roots as
+// k_psd_sqrt left them (infidelity).  A trial's bits depend on its two matrices alone: not on B, its place in the batch,
+// its wavefront neighbours (jacobi_sweeps<OWN>) or G.
+template <int NQ, int METRIC>
+__global__ void __launch_bounds__(256) k_metric_dist(const double* __restrict__ rho, int B,
+                                                     const double* __restrict__ centres, int G, int g0, double jtol2,
+                                                     double* __restrict__ dist) {
+  using S = Small<NQ>;
+  __shared__ __attribute__((aligned(16))) double smem[S::TPB * S::kMetricDoubles];
+  typename S::CtxM c;
+  S::make_ctx_metric(c, smem, jtol2);
+  bool live;
+  const int b = S::trial_index(B, &live);
+  const int bb = live ? b : B - 1;  // padding groups recompute the last trial; nothing is stored
+  const double* in = rho + ((size_t)bb * S::D + c.l) * 2;
+  const double* cen = centre_of(centres, G, g0, bb, 2 * S::D) + 2 * c.l;
+  const cd r{in[0], in[1]}, q{cen[0], cen[1]};
+  const double v = METRIC == kMetricTrace ? S::trace_dist(c, r, q) : S::infidelity(c, r, q);
+  if (live && c.l == 0) dist[b] = v;
 }
 
 // a9

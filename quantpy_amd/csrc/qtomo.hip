@@ -137,6 +137,7 @@ struct qt_handle {
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
+  DevBuf metric_ws;  // qt_metric_dist_group_batch, infidelity: the Hermitian roots of the call's G centres
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -1213,7 +1214,7 @@ void qt_destroy(qt_handle_t* h) {
   for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_last})
     b->release();
   for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
-                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
+                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
   h->proc.release();
@@ -1812,6 +1813,45 @@ int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* cen
   if (int r = c.in(centre, ne * 2, &dcn)) return r;
   if (int r = c.out(dist, (size_t)B, &dd)) return r;
   hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, dim, dr, dcn, 1, 0, B, dd);
+  return c.done();
+}
+
+// geometry.py:23-56 for a batch against a table of centres, n <= 3 (k_metric_dist; the infidelity's roots of the centres
+// by k_psd_sqrt, once per call).  Reads no POVM.
+int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, int B, const double* centres, int G, int g0,
+                               double* dist, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "qt_metric_dist_group_batch: n_qubits %d (supported: 1, 2, 3)", h->nq);
+  if (metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
+    return fail(QT_ERR_ARG, "qt_metric_dist_group_batch: unknown metric %d", metric);
+  if (B < 0 || G < 1 || g0 < 0 || g0 >= G || (B > 0 && (!rho || !centres || !dist)))
+    return fail(QT_ERR_ARG, "bad metric_dist_group_batch arguments (B = %d, G = %d, g0 = %d)", B, G, g0);
+  if (B == 0) return 0;
+  const double *dr, *dcn;
+  double* dd;
+  const size_t ne2 = (size_t)h->D * 2;
+  if (int r = c.in(rho, (size_t)B * ne2, &dr)) return r;
+  if (int r = c.in(centres, (size_t)G * ne2, &dcn)) return r;
+  if (int r = c.out(dist, (size_t)B, &dd)) return r;
+  if (metric == QT_METRIC_INFIDELITY) HIPCHK(h->metric_ws.ensure((size_t)G * ne2 * sizeof(double)));
+  if (int r = by_nq(h, [&](auto nq) {
+        constexpr int NQ = decltype(nq)::value;
+        if constexpr (NQ <= 3) {
+          using S = qt::Small<NQ>;
+          const dim3 grid((B + S::TPB - 1) / S::TPB), block(S::NT);
+          if (metric == QT_METRIC_TRACE)
+            return launch(h, qt::k_metric_dist<NQ, qt::kMetricTrace>, grid, block, 0, dr, B, dcn, G, g0, h->jtol2, dd);
+          double* roots = h->metric_ws.as<double>();
+          if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((G + S::TPB - 1) / S::TPB), block, 0, dcn, G, h->jtol2, roots))
+            return r;
+          return launch(h, qt::k_metric_dist<NQ, qt::kMetricInfidelity>, grid, block, 0, dr, B,
+                        static_cast<const double*>(roots), G, g0, h->jtol2, dd);
+        } else {
+          return fail(QT_ERR_UNSUPPORTED, "n_qubits %d", NQ);
+        }
+      }))
+    return r;
   return c.done();
 }
 

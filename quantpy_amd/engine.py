@@ -838,6 +838,38 @@ class Engine:
         self._chk(self.lib.qt_hs_dist_batch(self._h, _ptr(rho), _ptr(centre), rho.shape[0], _ptr(out),
                                             _capi.QT_DEVICE_PTR))
 
+    _METRICS = {"trace": _capi.QT_METRIC_TRACE, "if": _capi.QT_METRIC_INFIDELITY}
+
+    def _metric_code(self, metric):
+        if metric not in self._METRICS:
+            raise ValueError(f"metric must be 'trace' or 'if', not {metric!r}")
+        return self._METRICS[metric]
+
+    def metric_dist(self, rho, centre, metric, g0=0):
+        """Trace distance (metric='trace', geometry.py:23-38) or infidelity ('if', geometry.py:41-56) of Hermitian
+        d x d matrices to `centre`, n <= 3 (qt_metric_dist_group_batch; needs no POVM).  rho (B, d, d) or (d, d); centre
+        (d, d), or a table (G, d, d): trial b is then measured against centre[(g0 + b) % G].  -> (B,) float64, or a
+        float for a single matrix."""
+        code = self._metric_code(metric)
+        rho, cen = _c128(rho), _c128(centre)
+        single = rho.ndim == 2
+        r = rho.reshape(-1, self.d, self.d)
+        assert cen.shape[-2:] == (self.d, self.d) and cen.ndim in (2, 3)
+        out = np.empty(r.shape[0])
+        self._chk(self.lib.qt_metric_dist_group_batch(self._h, code, _ptr(r), r.shape[0], _ptr(cen),
+                                                      cen.shape[0] if cen.ndim == 3 else 1, int(g0), _ptr(out),
+                                                      _capi.QT_HOST_PTR))
+        return out[0] if single else out
+
+    def metric_dist_dev(self, rho, centre, dist, metric, g0=0):
+        """device-pointer form: rho complex128 (B, d, d), centre complex128 (d, d) or (G, d, d), dist float64 (B,) torch
+        CUDA tensors"""
+        code = self._metric_code(metric)
+        self._dev_call()
+        self._chk(self.lib.qt_metric_dist_group_batch(self._h, code, _ptr(rho), rho.shape[0], _ptr(centre),
+                                                      centre.shape[0] if centre.dim() == 3 else 1, int(g0), _ptr(dist),
+                                                      _capi.QT_DEVICE_PTR))
+
 
     def sort_quantiles(self, dist, conf_levels):
         """interval.py:610-612 on the device: sort `dist` (NumPy array: a sorted copy is returned; torch CUDA

@@ -34,6 +34,34 @@ def if_dst(A, B):
     return 0 if dist < 1e-15 else dist
 
 
+def _metric_batch(A, B, metric, host):
+    b = np.asarray(_as_matrix(B), dtype=np.complex128)
+    if not isinstance(A, np.ndarray):
+        A = [a.matrix if hasattr(a, "matrix") else a for a in A]
+    mats = np.asarray(A, dtype=np.complex128)
+    dim = b.shape[0]
+    if mats.ndim != 3 or mats.shape[1:] != (dim, dim) or b.shape != (dim, dim):
+        raise ValueError(f"expected (B, d, d) matrices and one (d, d) matrix, got {mats.shape} and {b.shape}")
+    if dim > 8:
+        return np.array([host(m, b) for m in mats], dtype=np.float64)
+    from .engine import get_engine
+
+    return get_engine(int(np.log2(dim))).metric_dist(mats, b, metric)
+
+
+def trace_dst_batch(A, B):
+    """`trace_dst(a, B)` for every a of A, (B, d, d) or a list of Qobj, against ONE matrix or Qobj B -> (B,) float64.
+    Up to d = 8 in one launch of the HIP engine (qt_metric_dist_group_batch: the eigenvalues of a - B by Jacobi sweeps,
+    for HERMITIAN arguments); above that the host function in a loop."""
+    return _metric_batch(A, B, "trace", trace_dst)
+
+
+def if_dst_batch(A, B):
+    """`if_dst(a, B)` for every a of A, as `trace_dst_batch` (Hermitian arguments; infidelity is symmetric, and the
+    engine takes the root of B once for the batch)."""
+    return _metric_batch(A, B, "if", if_dst)
+
+
 def product(A, B):
     """Hermitian inner product Tr(A B^dagger)."""
     return np.trace(_as_matrix(A) @ np.conj(_as_matrix(B).T), dtype=np.complex128)

@@ -13,6 +13,9 @@ period = n_iter * S and the Born probabilities of the n_iter estimates as its ta
 resamples and writes its distances, and `qt_group_hits` adds, per trial, how many of them lie below that trial's distance
 to the truth.  Counts and distances never leave HBM; 8 * n_iter bytes come back.
 
+`get_CL_list_state_boot(dst='hs' | 'trace' | 'if')` is that study in any of the three distances: for the trace distance and
+the infidelity a chunk's estimates stay in a device workspace and `qt_metric_dist_group_batch` measures them.
+
 interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with the same rule.
 
 `get_CL_list_state_mhmc` is the reference's interval='mhmc' branch for states: one Metropolis-Hastings chain per trial, all
@@ -23,7 +26,7 @@ per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.
 import numpy as np
 
 from . import distributed as qdist
-from .geometry import hs_dst
+from .geometry import hs_dst, if_dst, trace_dst
 from .sampling import SAMPLERS, resolve_seed
 from .tomography.interval import BootstrapProcessInterval, MomentInterval
 from .tomography.process import ProcessTomograph
@@ -62,7 +65,9 @@ def _check_arguments(interval, dst, n_iter, n_points, sampler, boot_methods, met
         raise NotImplementedError("interval='boot' is not implemented by get_CL_list_channel (supported: 'gamma'); the "
                                   "bootstrap study of a channel is get_CL_list_channel_boot")
     if not (dst == "hs" or dst is hs_dst):
-        raise NotImplementedError("only the Hilbert-Schmidt distance (dst='hs') is supported")
+        raise NotImplementedError("only the Hilbert-Schmidt distance (dst='hs') is supported"
+                                  + ("; the bootstrap study of a state in the trace distance or the infidelity is "
+                                     "get_CL_list_state_boot" if boot_methods else ""))
     if interval == "boot" and method_boot not in boot_methods:
         raise NotImplementedError(f"interval='boot' supports method_boot in {boot_methods}, not {method_boot!r}")
     if int(n_iter) < 1 or int(n_points) < 1:
@@ -146,6 +151,49 @@ def get_CL_list_state(state, n_iter=1000, n_points=1000, interval="gamma", n_mea
                    seed=key)
 
 
+def _distance_name(dst):
+    for name, fn in (("hs", hs_dst), ("trace", trace_dst), ("if", if_dst)):
+        if dst == name or dst is fn:
+            return name
+    raise ValueError("Invalid value for argument `dst` (supported: 'hs', 'trace', 'if')")
+
+
+def get_CL_list_state_boot(state, n_iter=1000, n_points=1000, n_measurements=1000, method="lin", method_boot="lin", dst="hs",
+                           povm="proj-set", physical=True, init="lin", tol=1e-3, max_iter=100, *, sampler="device",
+                           seed=None, chunk=None, return_details=False):
+    """The bootstrap study of a state -- `get_CL_list_state(interval='boot')`, parameters, keying of the resamples and
+    details as there -- in any of the three distances: dst = 'hs' | 'trace' | 'if' (or the functions of
+    quantpy_amd.geometry).  `delta` and the resampled distances are both measured in `dst`, as the reference's loop
+    measures them (metrics.py:125-144 with the tomograph's dst).  (`get_CL_list_state` keeps its refusal of the other
+    two; this is the study's name.)
+
+    dst='hs' IS `get_CL_list_state(interval='boot')`: the same call, the same bits.  With 'trace' / 'if' (n <= 3) the
+    chunk's grouped reconstruction writes its density matrices into a device workspace (`Engine.lin_dev` / `mle_dev`),
+    `Engine.metric_dist_dev` measures resample r of trial t against estimate t (the table of the n_iter estimates,
+    trial b against centre b % n_iter), and `group_hits` counts as before: counts, matrices and distances stay in HBM.
+    The distances are those of Hermitian arguments by the engine's Jacobi sweeps (include/qtomo.h:
+    qt_metric_dist_group_batch), within 1e-7 (trace) / 1e-6 (infidelity) of `trace_dst` / `if_dst` on the host."""
+    metric = _distance_name(dst)
+    if metric == "hs":
+        return get_CL_list_state(state, n_iter, n_points, "boot", n_measurements, method, method_boot, "hs", povm, physical,
+                                 init, tol, max_iter, sampler=sampler, seed=seed, chunk=chunk, return_details=return_details)
+    _check_arguments("boot", "hs", n_iter, n_points, sampler, ("lin", "mle"), method_boot)
+    if state.n_qubits > 3:
+        raise NotImplementedError(f"dst={metric!r} is supported up to three qubits")
+    n_iter, n_points = int(n_iter), int(n_points)
+    tmg = StateTomograph(state, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
+    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
+    if info is not None and np.any(info["status"] == 1):
+        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
+    eng = tmg._engine()
+    delta = eng.metric_dist(rho, state.matrix, metric)
+    key = (base + 1) & (2**64 - 1)
+    hits = _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk, metric)
+    return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
+                   seed=key)
+
+
 def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=1000, method="lin", povm="proj-set", init="lin",
                            tol=1e-3, max_iter=100, step=0.01, burn_steps=1000, thinning=1, *, sampler="device", seed=None,
                            return_details=False):
@@ -209,18 +257,30 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
                    seed=key, acceptance_rate=accepted / (n_points * thinning))
 
 
-def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk):
+def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk, metric=None):
     """hits[t] = #{ r < n_points : delta_t > hs_dst(estimate(resample r of trial t), estimate_t) }, this rank's shard of
-    the resamples chunk by chunk on the device, summed over the ranks."""
+    the resamples chunk by chunk on the device, summed over the ranks.  `metric` = 'trace' / 'if': that distance in the
+    place of hs_dst, formed by `metric_dist_dev` from the chunk's density matrices (one workspace, the first chunk's
+    size; a chunk starts at a whole resample, so its first row meets centre 0)."""
     import torch
 
     from . import _capi
 
     n_iter = rho.shape[0]
     pvals = np.clip(eng.born_probs(eng.bloch_from_matrix(rho)), 0, 1).reshape(n_iter * eng.S, eng.K)
+    work = []  # the density matrices of a chunk
 
     def measure(counts, centres, dist, status):
-        if method_boot == "lin":
+        if metric is not None:
+            if not work:
+                work.append(torch.empty((counts.shape[0], eng.d, eng.d), dtype=torch.complex128, device=counts.device))
+            mats = work[0][:counts.shape[0]]
+            if method_boot == "lin":
+                eng.lin_dev(counts, mats, physical=physical, status=status)
+            else:
+                eng.mle_dev(counts, mats, init=init, max_iter=max_iter, tol=tol, status=status)
+            eng.metric_dist_dev(mats, centres, dist, metric)
+        elif method_boot == "lin":
             eng.lin_dist_dev(counts, centres, dist, physical=physical, status=status)
         else:
             eng.mle_dist_dev(counts, centres, dist, init=init, max_iter=max_iter, tol=tol, status=status)

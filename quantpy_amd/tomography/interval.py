@@ -33,7 +33,7 @@ import scipy.stats as sts
 
 from .. import distributed as qdist
 from ..engine import get_engine
-from ..geometry import hs_dst, trace_dst
+from ..geometry import hs_dst, if_dst, trace_dst
 from ..routines import _left_inv
 
 
@@ -57,6 +57,14 @@ def _proposal_increments(dim):
         frozen = multivariate_normal(mean=np.zeros(dim))
         return lambda size: frozen.rvs(size=size).reshape(size, dim)
     return lambda size: np.random.standard_normal((size, dim))
+
+
+def _engine_metric(dst, n_qubits):
+    """'trace' / 'if' when `dst` is the trace distance / infidelity and the engine forms it (n <= 3:
+    Engine.metric_dist), else None."""
+    if n_qubits > 3:
+        return None
+    return "trace" if dst is trace_dst else "if" if dst is if_dst else None
 
 
 def _pop_hidden_keys(kwargs):
@@ -204,6 +212,8 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
     """Parametric bootstrap around `state` (default: the tomograph's reconstructed state) with the
     tomograph's own POVM and shots; distances tmg.dst(resampled estimate, state)."""
 
+    _CHUNK_BYTES = 256 << 20  # density matrices of one chunk of resamples (trace distance / infidelity)
+
     def __init__(self, tmg, n_points=1000, method="lin", physical=True, init="lin", tol=1e-3, max_iter=100,
                  state=None, sampler="numpy", seed=None):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
@@ -219,8 +229,9 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
                 self.state = tmg.point_estimate(method=self.method, physical=self.physical, init=self.init,
                                                 tol=self.tol, max_iter=self.max_iter)
         boot = tmg.__class__(self.state, tmg.dst)
-        if self.n_points and tmg.dst is hs_dst and self.method in ("lin", "mle"):
-            self._setup_fused(boot)
+        metric = _engine_metric(tmg.dst, self.state.n_qubits)
+        if self.n_points and (tmg.dst is hs_dst or metric) and self.method in ("lin", "mle"):
+            self._setup_fused(boot, metric)
             return
         # every resample's counts, one global RNG stream in the reference's order (resample after resample, setting
         # after setting): ONE call of the C restatement of NumPy's sampler instead of n_points x S Python calls
@@ -245,14 +256,17 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
         self.boot_dist = qdist.sharded_map(counts, reconstruct)
         self._finish(self.boot_dist)
 
-    def _setup_fused(self, boot):
+    def _setup_fused(self, boot, metric=None):
         """The loop of interval.py:598-609 for the Hilbert-Schmidt distance and the 'lin' / 'mle' estimators, as this
         rank's shard of it: the shard's counts go to (sampler='numpy': one C call on np.random's stream on rank 0,
         broadcast) or are drawn in (sampler='device': rows keyed by their global index, each rank draws only its own)
         HBM, ONE launch family reconstructs them and writes the distance to `state` (qt_lin_dist_batch /
         qt_mle_dist_batch: 8 bytes per resample leave the kernel, no density matrices), the shard is sorted where it is,
         and `cl_to_dist` evaluates interp1d's order statistics across the ranks (quantpy_amd.distributed.ShardedSample)
-        -- no all-gather of the sample unless somebody reads `boot_dist` / `cl_to_dist.y`."""
+        -- no all-gather of the sample unless somebody reads `boot_dist` / `cl_to_dist.y`.
+        `metric` = 'trace' / 'if' (n <= 3): the same, except that the shard is reconstructed in chunks of whole
+        trials into a workspace of at most `_CHUNK_BYTES` of density matrices, and `Engine.metric_dist_dev` writes each
+        chunk's trace distances / infidelities to `state` into the shard's `dist`: the matrices never leave HBM."""
         import torch
 
         from .. import _capi
@@ -291,11 +305,22 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
         dist = torch.empty(hi - lo, dtype=torch.float64, device=dev)
         status = torch.zeros(hi - lo, dtype=torch.int32, device=dev)
         centre = torch.from_numpy(np.ascontiguousarray(self.state.matrix, dtype=np.complex128)).to(dev)
-        if hi > lo:
+        if hi > lo and metric is None:
             if self.method == "lin":
                 eng.lin_dist_dev(counts, centre, dist, physical=self.physical, status=status)
             else:
                 eng.mle_dist_dev(counts, centre, dist, init=self.init, max_iter=self.max_iter, tol=self.tol, status=status)
+        elif hi > lo:
+            chunk = min(hi - lo, max(1, self._CHUNK_BYTES // (16 * d * d)))
+            rho = torch.empty((chunk, d, d), dtype=torch.complex128, device=dev)
+            for c0 in range(0, hi - lo, chunk):
+                c1 = min(c0 + chunk, hi - lo)
+                if self.method == "lin":
+                    eng.lin_dev(counts[c0:c1], rho[:c1 - c0], physical=self.physical, status=status[c0:c1])
+                else:
+                    eng.mle_dev(counts[c0:c1], rho[:c1 - c0], init=self.init, max_iter=self.max_iter, tol=self.tol,
+                                status=status[c0:c1])
+                eng.metric_dist_dev(rho[:c1 - c0], centre, dist[c0:c1], metric)
         eng.sync()
         st = status.cpu().numpy()
         bad = np.array([int(np.any(st == 1)), int(np.any(st == _capi.TRIAL_SHOTS))])
@@ -381,8 +406,11 @@ class MHMCStateInterval(ConfidenceInterval):
         self.samples = chain[skip::self.thinning][: self.n_points]
         self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
         mats = eng.chol_unparam(self.samples)
+        metric = _engine_metric(tmg.dst, tmg.state.n_qubits)
         if tmg.dst is hs_dst:
             dist = eng.hs_dist(mats, np.asarray(self.state.matrix, dtype=np.complex128))
+        elif metric:
+            dist = eng.metric_dist(mats, np.asarray(self.state.matrix, dtype=np.complex128), metric)
         else:
             dist = np.array([tmg.dst(m, self.state.matrix) for m in mats], dtype=np.float64)
         self._finish(dist)
