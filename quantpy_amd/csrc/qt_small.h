@@ -466,6 +466,7 @@ struct Small {
     __device__ __forceinline__ double* extra() const { return sm + trial_doubles(M, pv.pr.enabled ? pv.pr.R1 : 0); }  // [pv.extra]
     // the launch-uniform facts, read at run time here and compile-time constants in CtxS
     static constexpr bool kGeneric = true;
+    static constexpr int kLaneTables = 0;   // (CtxSV)
     static constexpr bool kHelper = false;  // (WithHelper)
     // (CtxH: the helper wavefront's lift can be called off; a trial's own never is)
     __device__ __forceinline__ static constexpr int verdict_load() { return 0; }
@@ -481,7 +482,14 @@ struct Small {
   };
   // The context of the specialised kernels (SpecArgs): the same roles, the shape known to the compiler.  The table
   // block holds the image of SpecArgs::image and nothing else; the trial scratch keeps the generic layout and offset.
-  struct CtxS {
+  // LT: where the lane tables of matrix_of / bloch_of at n = 3 live.  2: decoded in vector registers -- the kernels that
+  // run one wavefront per SIMD with registers to spare (k_mle_fused*).  1: two packed words per lane, decoded at each
+  // call (k_mle_start, held to 128 VGPRs).  0: no lane tables, the forms of the generic context (k_mle_bfgs: with the
+  // tables its allocation ended at 181 registers instead of 165, above the 168 of three waves per SIMD, and the
+  // saturated iterating batches ran 10-20 % slower, profiles/mle_diet_headline_ab.txt).
+  template <int LT>
+  struct CtxSV {
+    static constexpr bool VC = LT == 2;
     int l, i, j, e;
     double* sm;
     const int* tfwd;            // `last`: the stage-n entries
@@ -499,6 +507,14 @@ struct Small {
     // one wave per SIMD with ~75 VGPRs to spare: there they are pinned in vector registers (make_ctx<true>), where an
     // FMA reads them at no cost.
     double kT[12], kP[12];
+    // matrix_of (n = 3): the d terms of this lane in the order they are added (mat_slots), a byte each: Bloch index k,
+    // bit 7 = negative.  VC: decoded once into the term's address in vec() and the mask that flips its sign.
+    uint32_t mpack[2];
+    const double* mterm[VC ? d : 1];
+    uint32_t msign[VC ? d : 1];
+    // bloch_of (n = 3), VC: the sign masks of the butterfly's three stages (lane & 1, 2, 4) and of the phase
+    uint32_t bflip[VC ? 4 : 1];
+    static constexpr int kLaneTables = LT;
     __device__ __forceinline__ cd* A() const { return reinterpret_cast<cd*>(sm + oA); }
     __device__ __forceinline__ cd* Bm() const { return reinterpret_cast<cd*>(sm + oB); }
     __device__ __forceinline__ cd* V() const { return reinterpret_cast<cd*>(sm + v_offset(M, 6)); }
@@ -524,6 +540,7 @@ struct Small {
     __device__ __forceinline__ double cT(int k) const { return kT[k]; }
     __device__ __forceinline__ double cP(int k) const { return kP[k]; }
   };
+  using CtxS = CtxSV<1>;
   __device__ __forceinline__ static double pin_vgpr(double x) {  // the value, in a vector register from here on
     asm volatile("" : "+v"(x));
     return x;
@@ -534,7 +551,7 @@ struct Small {
   };
   template <class X>
   struct CtxOf<false, X> {
-    using type = CtxS;
+    using type = CtxSV<1>;
   };
   // 16-byte chunks of the table image (SpecArgs::image): `last` padded to four entries, then the two one-qubit tables
   __host__ __device__ static int image_last_ints(int M) { return (M + 3) & ~3; }
@@ -668,6 +685,31 @@ struct Small {
       const int x = c.i, r = c.j, lane = threadIdx.x & 63;
       const cd e = m[r * LD + (r ^ x)];
       cd s{e.re, -e.im};
+      if constexpr (C::kLaneTables != 0) {
+        // the same sums without a select: p - s is p + (-s), and whether a lane subtracts is a lane constant -- a sign
+        // mask per stage, held in registers (CtxSV<2>) or formed from the lane number (CtxSV<1>)
+        uint32_t f[4];
+        if constexpr (C::kLaneTables == 2) {
+#pragma unroll
+          for (int b = 0; b < 4; ++b) f[b] = c.bflip[b];
+        } else {
+          f[0] = (uint32_t)lane << 31;
+          f[1] = ((uint32_t)lane << 30) & 0x80000000u;
+          f[2] = ((uint32_t)lane << 29) & 0x80000000u;
+          f[3] = ((uint32_t)__popc(x & r) << 30) & 0x80000000u;
+        }
+        s = cd{flip_sign(s.re, f[0]) + dpp_f64<0xB1>(s.re), flip_sign(s.im, f[0]) + dpp_f64<0xB1>(s.im)};
+        s = cd{flip_sign(s.re, f[1]) + dpp_f64<0x4E>(s.re), flip_sign(s.im, f[1]) + dpp_f64<0x4E>(s.im)};
+        s = cd{flip_sign(s.re, f[2]) + __shfl_xor(s.re, 4), flip_sign(s.im, f[2]) + __shfl_xor(s.im, 4)};
+        // Re[(-i)^ny s], ny = popc(x & z): s.re, s.im, -s.re, -s.im
+        const double v = flip_sign((__popc(x & r) & 1) ? s.im : s.re, f[3]) / d;
+        double* vec = c.vec();
+        vec[c.bslot] = v;
+        wave_sync();
+        const double mine = vec[c.l];
+        wave_sync();
+        return mine;
+      }
       s = wht_step(s, cd{dpp_f64<0xB1>(s.re), dpp_f64<0xB1>(s.im)}, lane & 1);
       s = wht_step(s, cd{dpp_f64<0x4E>(s.re), dpp_f64<0x4E>(s.im)}, lane & 2);
       s = wht_step(s, cd{__shfl_xor(s.re, 4), __shfl_xor(s.im, 4)}, lane & 4);
@@ -718,20 +760,64 @@ struct Small {
     }
     return pack;
   }
-  template <int... L>
+  // The same bytes in the order a lane adds them, without the real / imaginary flag: an off-diagonal element has d / 2
+  // real terms and d / 2 imaginary ones (x = i ^ j != 0: popc(x & z) is odd for half of the z), so its real terms in
+  // the order of z fill slots 0 .. d/2 - 1 and its imaginary terms the rest; a diagonal element has d real terms and
+  // they fill the slots in the order of z.
+  static constexpr uint64_t mat_slots(int l) {
+    const uint64_t pack = mat_pack(l);
+    uint64_t out = 0;
+    int n = 0;
+    for (int imag = 0; imag < 2; ++imag)
+      for (int z = 0; z < d; ++z) {
+        const uint64_t e = (pack >> (8 * z)) & 0xffu;
+        if ((int)((e >> 6) & 1u) == imag) out |= (e & 0xbfu) << (8 * n++);
+      }
+    return out;
+  }
+  template <bool SLOTS, int... L>
   struct MatTab {
-    static constexpr uint64_t v[sizeof...(L)] = {mat_pack(L)...};
+    static constexpr uint64_t v[sizeof...(L)] = {(SLOTS ? mat_slots(L) : mat_pack(L))...};
   };
-  template <int N, int... L>
-  struct MakeMatTab : MakeMatTab<N - 1, N - 1, L...> {};
-  template <int... L>
-  struct MakeMatTab<0, L...> {
-    using type = MatTab<L...>;
+  template <bool SLOTS, int N, int... L>
+  struct MakeMatTab : MakeMatTab<SLOTS, N - 1, N - 1, L...> {};
+  template <bool SLOTS, int... L>
+  struct MakeMatTab<SLOTS, 0, L...> {
+    using type = MatTab<SLOTS, L...>;
   };
   static_assert(NQ <= 3, "the packed table holds d <= 8 terms of 8 bits");
+  __device__ __forceinline__ static double flip_sign(double v, uint32_t mask) {  // mask 0 / 0x80000000: v / -v, to the bit
+    return __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, v) ^ ((uint64_t)mask << 32));
+  }
   template <class C>
   __device__ static cd matrix_of(const C& c, const double* v) {
-    using Tab = typename MakeMatTab<D>::type;
+    if constexpr (NQ == 3 && C::kLaneTables != 0) {
+      // The specialised start and one-launch kernels: no decision per term is left.  Address and sign of a term are lane
+      // constants (CtxSV: decoded in registers, or two packed words), the real and the imaginary sum are one chain of
+      // adds over the slots -- for a diagonal element the second half goes on from the first, for the others it starts
+      // at zero -- and each lane adds its terms in the order of z as before.  (v is c.vec(): the addresses are decoded
+      // for it.)
+      double t[d];
+#pragma unroll
+      for (int s = 0; s < d; ++s) {
+        if constexpr (C::kLaneTables == 2) {
+          t[s] = flip_sign(*c.mterm[s], c.msign[s]);
+        } else {
+          const uint32_t w = c.mpack[s / 4];
+          const int sh = 8 * (s % 4);
+          t[s] = flip_sign(v[(w >> sh) & 63u], (w << (24 - sh)) & 0x80000000u);
+        }
+      }
+      double a = 0.0;
+#pragma unroll
+      for (int s = 0; s < d / 2; ++s) a += t[s];
+      const bool diag = c.i == c.j;
+      double b = diag ? a : 0.0;
+#pragma unroll
+      for (int s = d / 2; s < d; ++s) b += t[s];
+      return cd{diag ? b : a, diag ? 0.0 : b};
+    }
+    using Tab = typename MakeMatTab<false, D>::type;
     const uint64_t pack = Tab::v[c.l];
     cd s{0.0, 0.0};
 #pragma unroll
@@ -756,6 +842,7 @@ struct Small {
     bool ok, seg;  // seg: K in {2, 4, 8, 16} divides G -- the K outcomes of a setting sit in K neighbouring lanes
     int ri[4];     // specialised kernels: the R-order slots of the rows l + q G (rinv)
     uint4 img;     // ... and this thread's 16-byte chunk of the workgroup's table image
+    uint64_t mat;  // ... and this lane's entry of matrix_of's term table (n = 3: mat_slots)
   };
   __device__ __forceinline__ static void prefetch_counts(Prefetch& pf, const int64_t* counts, const PovmView& pv) {
     const int l = (threadIdx.x & 63) % G, M = pv.M, K = pv.K;
@@ -870,6 +957,7 @@ struct Small {
     const uint4* img = reinterpret_cast<const uint4*>(a.image);
     const int* rinv = reinterpret_cast<const int*>(img + nch);
     pf.img = img[t < nch ? t : nch - 1];
+    if constexpr (NQ == 3) pf.mat = MakeMatTab<true, D>::type::v[l];
     pf.ok = pf.seg = true;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -879,9 +967,10 @@ struct Small {
       pf.ns[q] = a.Ns[mc >> NQ];  // K = d outcomes per setting
     }
   }
-  template <bool VCOEF = false, bool TWIN = false>
-  __device__ static void make_ctx(CtxS& c, double* smem_block, const SpecArgs& a, const Prefetch& pf,
+  template <bool VCOEF = false, bool TWIN = false, int LT>
+  __device__ static void make_ctx(CtxSV<LT>& c, double* smem_block, const SpecArgs& a, const Prefetch& pf,
                                   [[maybe_unused]] int twin = 0) {
+    static_assert(VCOEF == (LT == 2), "the one-wave-per-SIMD kernels keep coefficients and lane tables in vector registers");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     c.l = lane % G;
     const int slot = wave * TPW + lane / G;
@@ -918,6 +1007,24 @@ struct Small {
     // bloch_of (n = 3): lane (x, z) = (i, j) holds the value of Pauli string pauli_index(x, z) = spread(x) ^ 3 spread(z)
     const int sx = (c.i & 1) | ((c.i & 2) << 1) | ((c.i & 4) << 2), sz = (c.j & 1) | ((c.j & 2) << 1) | ((c.j & 4) << 2);
     c.bslot = sx ^ (3 * sz);
+    if constexpr (NQ == 3 && LT != 0) {
+      c.mpack[0] = (uint32_t)pf.mat;
+      c.mpack[1] = (uint32_t)(pf.mat >> 32);
+      if constexpr (VCOEF) {
+#pragma unroll
+        for (int s = 0; s < d; ++s) {
+          const uint32_t e = (c.mpack[s / 4] >> (8 * (s % 4))) & 0xffu;
+          c.mterm[s] = c.sm + oVec + (e & 63u);
+          c.msign[s] = (e & 0x80u) << 24;
+        }
+        // lane = 8 x + z: the butterfly's stage b subtracts in the lanes with bit b of z set; the phase (-i)^popc(x & z)
+        // negates for popc = 2, 3
+        c.bflip[0] = (uint32_t)lane << 31;
+        c.bflip[1] = ((uint32_t)lane << 30) & 0x80000000u;
+        c.bflip[2] = ((uint32_t)lane << 29) & 0x80000000u;
+        c.bflip[3] = ((uint32_t)__popc(c.i & c.j) << 30) & 0x80000000u;
+      }
+    }
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
       c.kT[k] = VCOEF ? pin_vgpr(a.cT[k]) : a.cT[k];
@@ -942,7 +1049,8 @@ struct Small {
   // frequency goes straight there: no parking of the counts in rbuf and no raw[trmap[m]] (two dependent LDS reads)
   // to fetch them back.  The total is the sum of the per-setting sums the shots check forms anyway, continued over the
   // settings: every partial sum is an integer-valued double below 2^53, so any order gives the bits of gsum<G>(part).
-  __device__ static bool load_freq(const CtxS& c, const Prefetch& pf) {
+  template <int LT>
+  __device__ static bool load_freq(const CtxSV<LT>& c, const Prefetch& pf) {
     double dv[4], st[4];
     bool valid[4];
 #pragma unroll
@@ -2635,7 +2743,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFG
   const bool mine = live && ws_active[b] != 0;
   if (!__syncthreads_or(mine)) return;  // nothing left to iterate in this workgroup
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::template CtxOf<GENERIC>::type c;
+  std::conditional_t<GENERIC, typename S::Ctx, typename S::template CtxSV<0>> c;  // (no lane tables: CtxSV)
   const int bb = live ? b : B - 1;
   if constexpr (GENERIC) {
     S::make_ctx(c, smem, pv);
@@ -2679,7 +2787,8 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   using S = Small<NQ>;
   constexpr int D = S::D, G = S::G, d = S::d;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  using Ctx = typename S::template CtxOf<GENERIC>::type;
+  // (one wavefront per SIMD: the specialised context keeps its lane tables decoded in registers)
+  using Ctx = std::conditional_t<GENERIC, typename S::Ctx, typename S::template CtxSV<2>>;
   std::conditional_t<HW, typename S::template WithHelper<Ctx>, Ctx> c;
   [[maybe_unused]] typename S::HelperLink link;
   [[maybe_unused]] typename S::LateX late{false, 0.0, 0};
