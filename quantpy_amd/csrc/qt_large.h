@@ -902,19 +902,17 @@ k_mle_large_start(PovmView pv, const int64_t* __restrict__ counts, int B,
   }
   QT_STAMP(8);
   double fk = 0.0, gk = 0.0;
-  int status = !c.shots_ok ? 5 : (ok ? 0 : 1);
+  const bool evaluate = c.shots_ok && ok;  // uniform: one trial per workgroup
+  double gnorm = 0.0, xn = 0.0;
   bool iterate = false;
-  if (status == 0) {  // uniform: one trial per workgroup
+  if (evaluate) {
     S::nll_grad_inl(c, xk, fk, gk);
     QT_STAMP(9);
-    const double gnorm = S::bmax(c, fabs(gk));
+    gnorm = S::bmax(c, fabs(gk));
     iterate = (gnorm > gtol) && (0 < max_iter);
-    if (!iterate) {
-      const double xn = S::bmax(c, fabs(xk));
-      if (0 >= max_iter) status = 3;
-      else if (gnorm != gnorm || fk != fk || xn != xn) status = 4;
-    }
+    if (!iterate) xn = S::bmax(c, fabs(xk));
   }
+  const int status = mle_start_status(c.shots_ok, ok, iterate, max_iter, gnorm, fk, xn != xn);
   // what the trial returns if BFGS does not move: L L^dagger / Tr at x_k (state.py:214-215)
   double tr;
   const cd m = S::build_llh(c, xk, tr);
@@ -927,10 +925,7 @@ k_mle_large_start(PovmView pv, const int64_t* __restrict__ counts, int B,
   if (c.t == 0) {
     if (iterate) ws_f[b] = fk;
     ws_active[b] = iterate ? 1 : 0;
-    if (nit_out) nit_out[b] = 0;
-    if (nfev_out) nfev_out[b] = status == 0 || status >= 3 ? (status == 5 ? 0 : 1) : 0;
-    if (fun_out) fun_out[b] = fk;
-    if (status_out) status_out[b] = status;
+    store_trial(b, 0, evaluate ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
   }
 }
 
@@ -952,7 +947,7 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
   typename S::Ctx c;
   S::make_ctx(c, smem, pv, counts + (size_t)b * pv.M);
   double xk = ws_x[(size_t)b * D + c.t], gk = ws_g[(size_t)b * D + c.t], fk = ws_f[b];
-  int kiter = 0, nfev = 1, status = 0;
+  int kiter = 0, nfev = 1, status = TRIAL_OK;
   double* my = pairs + (size_t)b * max_iter * 2 * D + c.t;  // s_i[t] at my[2 i D], y_i[t] at my[(2 i + 1) D]
   double* prho = c.pair_rho();
   double* palpha = prho + max_iter;
@@ -964,7 +959,7 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
     ls.start(fk, old_old, S::bsum(c, gk * pk), &stp);
     if (c.t == 0) ls.save(lsb);
   }
-  const int eval_cap = (max_iter + 2) * 130;
+  const int eval_cap = bfgs_eval_cap(max_iter);
   while (true) {  // uniform: one trial per workgroup, every thread holds the same scalars
     double ft, gt;
     QT_STAMP(21);  // (profile build, scripts/phase_timing_large_bfgs.py: the slots keep the LAST iteration's clocks)
@@ -988,7 +983,7 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
     }
     QT_STAMP(22);
     if (++nfev > eval_cap) {
-      status = 2;
+      status = TRIAL_LINESEARCH;
       break;
     }
     const double dphi = S::bsum(c, gt * pk);
@@ -1003,7 +998,7 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
       continue;
     }
     if (r == LS_FAIL) {
-      status = 2;
+      status = TRIAL_LINESEARCH;
       break;
     }
     const double sk = stp * pk;
@@ -1015,15 +1010,16 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
     fk = ft;
     ++kiter;
     const double gnorm = S::bmax(c, fabs(gk));
-    if (!(gnorm > gtol)) break;
+    // bfgs_step_exit (qt_linesearch.h), spelled out: through the call the same four tests cost this kernel 5 / 2 more
+    // spilled registers and, at n = 5, 4 bytes of scratch (every formulation of the call tried)
+    if (gnorm <= gtol) break;
     if (stp * sqrt(pnorm2) <= 0.0) break;
     if (!isfinite(fk)) {
-      status = 2;
+      status = TRIAL_LINESEARCH;
       break;
     }
-    if (!(kiter < max_iter)) break;
-    const double ys = S::bsum(c, yk * sk);
-    const double rhok = (ys == 0.0) ? 1000.0 : 1.0 / ys;
+    if (!(gnorm > gtol && kiter < max_iter)) break;
+    const double rhok = bfgs_rho(S::bsum(c, yk * sk));
     const int np = kiter - 1;  // index of the new pair
     my[(size_t)(2 * np) * D] = sk;
     my[(size_t)(2 * np + 1) * D] = yk;
@@ -1064,21 +1060,15 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
     if (c.t == 0) ls.save(lsb);
     QT_STAMP(20);
   }
-  if (status == 0) {
+  if (status == TRIAL_OK) {  // uniform: the norms are workgroup reductions
     const double gn = S::bmax(c, fabs(gk));
     const double xn = S::bmax(c, fabs(xk));
-    if (kiter >= max_iter) status = 3;
-    else if (gn != gn || fk != fk || xn != xn) status = 4;
+    status = bfgs_final_status(status, kiter, max_iter, gn, fk, xn);
   }
   double tr;
   const cd m = S::build_llh(c, xk, tr);
   S::emit(c, rho, b, cd{m.re / tr, m.im / tr});
-  if (c.t == 0) {
-    if (nit_out) nit_out[b] = kiter;
-    if (nfev_out) nfev_out[b] = nfev;
-    if (fun_out) fun_out[b] = fk;
-    if (status_out) status_out[b] = status;
-  }
+  if (c.t == 0) store_trial(b, kiter, nfev, fk, status, nit_out, nfev_out, fun_out, status_out);
 }
 
 // k_mhmc_state (qt_small.h) at n = 4, 5: one workgroup per chain, thread t owns parameter x[t].  Step t:

@@ -359,4 +359,59 @@ struct LineSearch {
   }
 };
 
+// ---- The scalar decisions of scipy's _minimize_bfgs around the line search, once for every MLE kernel (n <= 3:
+// bfgs_loop, k_mle_start, mle_fused_body in qt_small.h; n = 4, 5: k_mle_large_start, k_mle_large_bfgs in qt_large.h).
+
+// What a trial reports: QT_TRIAL_* of include/qtomo.h (qtomo.hip asserts the equality).  SciPy's warnflag 2 -> 2,
+// 1 -> 3, 3 -> 4.
+enum TrialStatus : int {
+  TRIAL_OK = 0,
+  TRIAL_NOT_PD = 1,
+  TRIAL_LINESEARCH = 2,
+  TRIAL_MAXITER = 3,
+  TRIAL_NAN = 4,
+  TRIAL_SHOTS = 5
+};
+
+// Evaluations after which a trial is stopped with TRIAL_LINESEARCH.  No path of SciPy gets there (<= 100 + 21 trial
+// steps per iteration): the cap is the hard stop that lets every wavefront leave the loop.
+QT_HD int bfgs_eval_cap(int max_iter) { return (max_iter + 2) * 130; }
+
+// rho_k of the update from y_k . s_k ("Divide-by-zero encountered: rhok assumed large")
+QT_HD double bfgs_rho(double ys) { return ys == 0.0 ? 1000.0 : 1.0 / ys; }
+
+// The exits behind an accepted step, in SciPy's order: gradient norm, xrtol = 0, non-finite value (warnflag 2), and
+// the loop condition (gnorm > gtol and k < maxiter: a NaN norm leaves there, behind the value test).  kiter counts
+// the accepted step.  true: the trial leaves the loop.
+QT_HD bool bfgs_step_exit(double gnorm, double gtol, double stp, double pnorm2, double fk, int kiter, int max_iter,
+                          int* status) {
+  if (gnorm <= gtol) return true;
+  if (stp * sqrt(pnorm2) <= 0.0) return true;
+  if (!isfinite(fk)) {
+    *status = TRIAL_LINESEARCH;
+    return true;
+  }
+  return !(gnorm > gtol && kiter < max_iter);
+}
+
+// Behind the loop: a status set inside it stands; otherwise the iteration cap (warnflag 1) goes before NaN in the
+// gradient, the value or the parameters (warnflag 3).  gn, xn: max-norms, NaN if any element is.
+QT_HD int bfgs_final_status(int status, int kiter, int max_iter, double gn, double fk, double xn) {
+  if (status != TRIAL_OK) return status;
+  if (kiter >= max_iter) return TRIAL_MAXITER;
+  if (gn != gn || fk != fk || xn != xn) return TRIAL_NAN;
+  return TRIAL_OK;
+}
+
+// A trial at its start point: the shot check, the Cholesky factorisation, then -- for a trial that does not iterate --
+// the rule above at k = 0.  A trial that iterates gets its status from bfgs_final_status.
+QT_HD int mle_start_status(bool shots_ok, bool ok, bool iterate, int max_iter, double gnorm, double fk, bool xnan) {
+  if (!shots_ok) return TRIAL_SHOTS;
+  if (!ok) return TRIAL_NOT_PD;
+  if (iterate) return TRIAL_OK;
+  if (0 >= max_iter) return TRIAL_MAXITER;
+  if (gnorm != gnorm || fk != fk || xnan) return TRIAL_NAN;
+  return TRIAL_OK;
+}
+
 }  // namespace qt

@@ -1652,7 +1652,7 @@ struct Small {
   // one branch behind a claimed verdict where both waves would go on as the trial).  In the names and comments of
   // HelperLink, "the trial's wave" is the wave on threadIdx.y = 0 up to kLifted and the twin behind it, and "the
   // helper" is the other one: the role swaps with the ownership.  What crosses between the waves goes through the first doubles of the
-  // trial's LDS pair store (bfgs_iterate_2l's `lp`, which nothing touches before the BFGS loop): the lifted matrix,
+  // trial's LDS pair store (TwoLoop::lp, which nothing touches before the BFGS loop): the lifted matrix,
   // the parameters of the sweep and the words below.
   // Data first, then the flag: release stores and acquire loads at workgroup scope, no workgroup barrier besides the
   // one of make_ctx -- the four trials of a workgroup stay uncoupled.  Every wait is a counted loop; whoever runs out
@@ -2373,6 +2373,16 @@ __global__ void __launch_bounds__(256) k_nll_batch(PovmView pv, const double* __
   }
 }
 
+// The scalars of one trial's MLE result (each output is optional), written by the trial's first lane.
+__device__ __forceinline__ void store_trial(int b, int nit, int nfev, double fun, int status,
+                                            int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
+                                            double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
+  if (nit_out) nit_out[b] = nit;
+  if (nfev_out) nfev_out[b] = nfev;
+  if (fun_out) fun_out[b] = fun;
+  if (status_out) status_out[b] = status;
+}
+
 // a10, part 1: starting point (state.py:205-212), Cholesky parametrisation and the first
 // (value, gradient) evaluation.  Trials whose gradient already meets gtol -- every full-rank
 // high-shot trial, where BFGS exits at iteration 0 -- are finished here; the
@@ -2425,14 +2435,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   const double gnorm = gmax<G>(fabs(gk));
   const bool iterate = shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
   if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
-  int status = 0;
-  if (!shots_ok) status = 5;
-  else if (!ok) status = 1;
-  else if (!iterate) {
-    const bool xnan = group_any<G>(xk != xk);
-    if (0 >= max_iter) status = 3;
-    else if (gnorm != gnorm || fk != fk || xnan) status = 4;
-  }
+  const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));
   S::emit(c, rho, b, live, rho_l);
   if (live) {
     if (iterate) {  // the hand-off is written only for trials that go on to k_mle_bfgs
@@ -2442,36 +2445,33 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     if (c.l == 0) {
       if (iterate) ws_f[b] = fk;
       ws_active[b] = iterate ? 1 : 0;
-      if (nit_out) nit_out[b] = 0;
-      if (nfev_out) nfev_out[b] = ok ? 1 : 0;
-      if (fun_out) fun_out[b] = fk;
-      if (status_out) status_out[b] = status;
+      store_trial(b, 0, ok ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
     }
   }
 }
 
 // a10, part 2: the BFGS iterations (scipy _minimize_bfgs) of the trials whose first gradient did not
 // meet gtol.  One (value, gradient) evaluation per loop pass; the line search is the state machine of
-// qt_linesearch.h; the inverse Hessian is one row per lane in registers.  `mine` marks the groups that
-// iterate; the others idle through the evaluations on finite dummy values.
-template <int NQ, class C>
-__device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, double gk,
-                                             double fk, int b, int max_iter, double gtol, EstOut rho,
-                                             int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                             double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
+// qt_linesearch.h, whose scalar rules (bfgs_*) this loop shares with the n = 4, 5 kernel (qt_large.h).  `mine` marks
+// the groups that iterate; the others idle through the evaluations on finite dummy values.
+// ONE loop for both forms of the inverse Hessian; `Dir` says how p = -H g is formed behind an accepted step:
+//   double next(c, np, sk, yk, gk, rhok)  this lane's element of the next direction; (sk, yk, rhok) is pair `np`
+//   kLsInLds                              the caller's LineSearch lives in LDS, shared by the lanes of the group: the
+//                                         loop orders its writes before the next pass's reads
+template <int NQ, class Dir, class C>
+__device__ __forceinline__ void bfgs_loop(const C& c, Dir& dir, LineSearch& ls, bool mine, double xk, double gk,
+                                          double fk, int b, int max_iter, double gtol, EstOut rho,
+                                          int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
+                                          double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
   using S = Small<NQ>;
-  constexpr int D = S::D, G = S::G;
+  constexpr int G = S::G;
   bool active = mine;
-  double H[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) H[k] = (k == c.l) ? 1.0 : 0.0;
   double old_old = fk + sqrt(gsum<G>(gk * gk)) / 2.0;
   double pk = -gk, stp = 0.0;  // H0 = I
-  int kiter = 0, nfev = 1, status = 0;
-  LineSearch ls;
-  double* vec = c.vec();
+  int kiter = 0, nfev = 1, status = TRIAL_OK;
   ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
-  const int eval_cap = (max_iter + 2) * 130;  // hard stop: every wave leaves the loop
+  if constexpr (Dir::kLsInLds) wave_sync();
+  const int eval_cap = bfgs_eval_cap(max_iter);
 
 #ifdef QT_PHASE_TIMING  // slots 21 / 22: clocks in this loop / inside its nll_grad calls; 23 / 24: iterations, evaluations
   long long t_nll = 0;
@@ -2487,7 +2487,7 @@ __device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, d
     t_nll += (long long)__builtin_readcyclecounter() - t_e0;
 #endif
     if (active && ++nfev > eval_cap) {
-      status = 2;
+      status = TRIAL_LINESEARCH;
       active = false;
     }
     if (active) {
@@ -2497,10 +2497,10 @@ __device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, d
       if (r == LS_EVAL) {
         stp = next;
       } else if (r == LS_FAIL) {
-        status = 2;
+        status = TRIAL_LINESEARCH;
         active = false;
       } else {
-        // step accepted: x += s, y = g_new - g, BFGS update (rhok = 1000 if y.s == 0)
+        // step accepted: x += s, y = g_new - g
         const double sk = stp * pk;
         const double pnorm2 = gsum<G>(pk * pk);
         xk = xk + sk;
@@ -2510,54 +2510,15 @@ __device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, d
         fk = ft;
         ++kiter;
         const double gnorm = gmax<G>(fabs(gk));
-        if (!(gnorm > gtol)) {
-          active = false;
-        } else if (stp * sqrt(pnorm2) <= 0.0) {  // xrtol = 0 test
-          active = false;
-        } else if (!isfinite(fk)) {
-          status = 2;
+        if (bfgs_step_exit(gnorm, gtol, stp, pnorm2, fk, kiter, max_iter, &status)) {
           active = false;
         } else {
-          const double ys = gsum<G>(yk * sk);
-          const double rhok = (ys == 0.0) ? 1000.0 : 1.0 / ys;
-          // H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T, expanded with u = H y
-          vec[c.l] = yk;
-          wave_sync();
-          // four partial sums: a lone wave pays ~16 ns per DEPENDENT FP64 instruction under load
-          // (profiles/round1_v14_ubench_valu_f64.txt); a 64-term chain would be 1 us of latency
-          double uu[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int k = 0; k < D; ++k) uu[k & 3] = fma(H[k], vec[k], uu[k & 3]);
-          double u = (uu[0] + uu[1]) + (uu[2] + uu[3]);
-          const double yhy = gsum<G>(yk * u);
-          wave_sync();
-          double* ubuf = reinterpret_cast<double*>(c.A());  // 2 D doubles: u | s
-          ubuf[c.l] = u;
-          ubuf[D + c.l] = sk;
-          wave_sync();
-          const double cc = rhok * rhok * yhy + rhok;
-          // (regrouped as H_lk += a_l s_k + b_l u_k with (u_k, s_k) read as one 16-byte pair: two FMAs per element
-          //  instead of five operations, and measured 6 % SLOWER per iteration -- scripts/bfgs_phase_timing.py)
-#pragma unroll
-          for (int k = 0; k < D; ++k)
-            H[k] += -rhok * (u * ubuf[D + k] + sk * ubuf[k]) + cc * sk * ubuf[D + k];
-          wave_sync();
-          if (!(kiter < max_iter)) {
-            active = false;
-          } else {
-            vec[c.l] = gk;
-            wave_sync();
-            double hh[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int k = 0; k < D; ++k) hh[k & 3] = fma(H[k], vec[k], hh[k & 3]);
-            const double hp = (hh[0] + hh[1]) + (hh[2] + hh[3]);
-            wave_sync();
-            pk = -hp;
-            ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
-          }
+          pk = dir.next(c, kiter - 1, sk, yk, gk, bfgs_rho(gsum<G>(yk * sk)));
+          ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
         }
       }
     }
+    if constexpr (Dir::kLsInLds) wave_sync();
   }
 #ifdef QT_PHASE_TIMING
   QT_STAMP_VAL(21, (long long)__builtin_readcyclecounter() - t_loop0);
@@ -2565,30 +2526,66 @@ __device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, d
   QT_STAMP_VAL(23, (long long)kiter);
   QT_STAMP_VAL(24, (long long)nfev);
 #endif
-  if (status == 0) {
-    const double gn = gmax<G>(fabs(gk));
-    const double xn = gmax<G>(fabs(xk));
-    if (kiter >= max_iter) status = 3;
-    else if (gn != gn || fk != fk || xn != xn) status = 4;
-  }
+  status = bfgs_final_status(status, kiter, max_iter, gmax<G>(fabs(gk)), fk, gmax<G>(fabs(xk)));
   // ---- result: L L^dagger / Tr  (state.py:214-215)
   double tr;
   const cd m = S::build_llh(c, xk, tr);
   S::emit(c, rho, b, mine, cd{m.re / tr, m.im / tr});
-  if (mine) {
-    if (c.l == 0) {
-      if (nit_out) nit_out[b] = kiter;
-      if (nfev_out) nfev_out[b] = nfev;
-      if (fun_out) fun_out[b] = fk;
-      if (status_out) status_out[b] = status;
-    }
-  }
+  if (mine && c.l == 0) store_trial(b, kiter, nfev, fk, status, nit_out, nfev_out, fun_out, status_out);
 }
 
-// The same iterations WITHOUT the inverse Hessian in registers, for batches that fill the chip (k_mle_bfgs): with
-// H_0 = I the matrix scipy updates, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T, is exactly the product form
-// the two-loop recursion evaluates, so p = -H_k g is computed from the (s_i, y_i) pairs of the accepted steps (the
-// n = 4, 5 kernels have always done this, qt_large.h).  Lane l only ever touches element l of each pair: private,
+// The inverse Hessian itself, one row per lane in registers (n = 1, 2: 4 / 16 doubles): the rank-two update with the
+// new pair, then the product with the gradient.
+template <int NQ>
+struct DenseH {
+  static constexpr bool kLsInLds = false;
+  static constexpr int D = Small<NQ>::D, G = Small<NQ>::G;
+  double H[D];
+  template <class C>
+  __device__ __forceinline__ explicit DenseH(const C& c) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) H[k] = (k == c.l) ? 1.0 : 0.0;
+  }
+  template <class C>
+  __device__ __forceinline__ double next(const C& c, int, double sk, double yk, double gk, double rhok) {
+    double* vec = c.vec();
+    // H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T, expanded with u = H y
+    vec[c.l] = yk;
+    wave_sync();
+    // four partial sums: a lone wave pays ~16 ns per DEPENDENT FP64 instruction under load
+    // (profiles/round1_v14_ubench_valu_f64.txt); a 64-term chain would be 1 us of latency
+    double uu[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < D; ++k) uu[k & 3] = fma(H[k], vec[k], uu[k & 3]);
+    double u = (uu[0] + uu[1]) + (uu[2] + uu[3]);
+    const double yhy = gsum<G>(yk * u);
+    wave_sync();
+    double* ubuf = reinterpret_cast<double*>(c.A());  // 2 D doubles: u | s
+    ubuf[c.l] = u;
+    ubuf[D + c.l] = sk;
+    wave_sync();
+    const double cc = rhok * rhok * yhy + rhok;
+    // (regrouped as H_lk += a_l s_k + b_l u_k with (u_k, s_k) read as one 16-byte pair: two FMAs per element
+    //  instead of five operations, and measured 6 % SLOWER per iteration -- scripts/bfgs_phase_timing.py)
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+      H[k] += -rhok * (u * ubuf[D + k] + sk * ubuf[k]) + cc * sk * ubuf[D + k];
+    wave_sync();
+    vec[c.l] = gk;
+    wave_sync();
+    double hh[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < D; ++k) hh[k & 3] = fma(H[k], vec[k], hh[k & 3]);
+    const double hp = (hh[0] + hh[1]) + (hh[2] + hh[3]);
+    wave_sync();
+    return -hp;
+  }
+};
+
+// WITHOUT the inverse Hessian in registers, for batches that fill the chip (k_mle_bfgs): with H_0 = I the matrix
+// scipy updates, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T, is exactly the product form the two-loop
+// recursion evaluates, so p = -H_k g is computed from the (s_i, y_i) pairs of the accepted steps (as at n = 4, 5,
+// qt_large.h, under the same rules of qt_linesearch.h).  Lane l only ever touches element l of each pair: private,
 // coalesced streams in a global workspace `pairs` [B][max_iter][2][D] that stay in L2; rho_i, alpha_i and -- across
 // every evaluation -- the line-search state live in the trial's LDS (`pv.extra` doubles).  Registers: ~150 instead
 // of 256 + 91 AGPRs, i.e. three waves per SIMD instead of one, and 2 k reductions + 4 k FMAs per iteration instead
@@ -2596,133 +2593,88 @@ __device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, d
 // (tests/test_gpu_state.py runs the reference's 70 golden trials through both).
 // LP > 0 (k_mle_fused: one workgroup per CU, LDS to spare): the first LP pairs stay in the trial's LDS and only later
 // ones go to the global workspace -- a lone wave would otherwise wait out an L2 round trip per block of pairs.
+template <int NQ, int LP>
+struct TwoLoop {
+  static constexpr bool kLsInLds = true;
+  static constexpr int D = Small<NQ>::D, G = Small<NQ>::G;
+  double* my;      // s_i[l] at my[2 i D], y_i[l] at my[(2 i + 1) D]
+  double* prho;    // [max_iter]
+  double* palpha;  // [max_iter]
+  double* lp;      // [LP][2][D]: s_i[l] at lp[2 i D], y_i[l] at lp[(2 i + 1) D]
+  template <class C>
+  __device__ __forceinline__ TwoLoop(const C& c, double* __restrict__ pairs, int b, int max_iter)
+      : my(pairs + (size_t)b * max_iter * 2 * D + c.l),
+        prho(c.extra() + LineSearch::SLOTS),
+        palpha(prho + max_iter),
+        lp(palpha + max_iter + c.l) {}
+  template <class C>
+  __device__ __forceinline__ double next(const C& c, int np, double sk, double yk, double gk, double rhok) {
+    if (np < LP) {
+      lp[(2 * np) * D] = sk;
+      lp[(2 * np + 1) * D] = yk;
+    } else {
+      my[(size_t)(2 * np) * D] = sk;
+      my[(size_t)(2 * np + 1) * D] = yk;
+    }
+    if (c.l == 0) prho[np] = rhok;
+    wave_sync();
+    double q = gk;
+    for (int i = np; i >= 0; --i) {
+      double si = sk, yi = yk;
+      if (i != np) {
+        if (i < LP) {
+          si = lp[(2 * i) * D];
+          yi = lp[(2 * i + 1) * D];
+        } else {
+          si = my[(size_t)(2 * i) * D];
+          yi = my[(size_t)(2 * i + 1) * D];
+        }
+      }
+      const double a = prho[i] * gsum<G>(si * q);
+      if (c.l == 0) palpha[i] = a;
+      q = fma(-a, yi, q);
+    }
+    wave_sync();
+    for (int i = 0; i <= np; ++i) {
+      double si = sk, yi = yk;
+      if (i != np) {
+        if (i < LP) {
+          si = lp[(2 * i) * D];
+          yi = lp[(2 * i + 1) * D];
+        } else {
+          si = my[(size_t)(2 * i) * D];
+          yi = my[(size_t)(2 * i + 1) * D];
+        }
+      }
+      const double bb = prho[i] * gsum<G>(yi * q);
+      q = fma(si, palpha[i] - bb, q);
+    }
+    return -q;
+  }
+};
+
+template <int NQ, class C>
+__device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, double gk,
+                                             double fk, int b, int max_iter, double gtol, EstOut rho,
+                                             int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
+                                             double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
+  DenseH<NQ> dir(c);
+  LineSearch ls;
+  bfgs_loop<NQ>(c, dir, ls, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
+}
+
 template <int NQ, int LP = 0, class C>
 __device__ __forceinline__ void bfgs_iterate_2l(const C& c, bool mine, double xk, double gk,
                                                 double fk, int b, int max_iter, double gtol, EstOut rho,
                                                 int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                 double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                 double* __restrict__ pairs) {
-  using S = Small<NQ>;
-  constexpr int D = S::D, G = S::G;
-  bool active = mine;
-  double* my = pairs + (size_t)b * max_iter * 2 * D + c.l;  // s_i[l] at my[2 i D], y_i[l] at my[(2 i + 1) D]
-  double* lsb = c.extra();                                  // [LineSearch::SLOTS]
-  double* prho = lsb + LineSearch::SLOTS;                   // [max_iter]
-  double* palpha = prho + max_iter;                         // [max_iter]
-  double* lp = palpha + max_iter + c.l;                     // [LP][2][D]: s_i[l] at lp[2 i D], y_i[l] at lp[(2 i + 1) D]
-  double old_old = fk + sqrt(gsum<G>(gk * gk)) / 2.0;
-  double pk = -gk, stp = 0.0;  // H0 = I
-  int kiter = 0, nfev = 1, status = 0;
+  TwoLoop<NQ, LP> dir(c, pairs, b, max_iter);
   // The line-search state lives IN LDS (every lane of the group reads and writes the same words with the same values):
   // as a register-resident struct its ~35 doubles plus the temporaries of dcstep made the allocation 240 VGPRs.
   static_assert(sizeof(LineSearch) <= LineSearch::SLOTS * sizeof(double), "LDS slot of the line-search state");
-  LineSearch& ls = *reinterpret_cast<LineSearch*>(lsb);
-  ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
-  wave_sync();
-  const int eval_cap = (max_iter + 2) * 130;  // hard stop: every wave leaves the loop
-  while (__any(active)) {  // per wave: the waves of a workgroup do not synchronise here
-    double ft, gt;
-    S::nll_grad(c, xk + stp * pk, ft, gt);  // executed by the whole wave; finished trials idle through it
-    if (active && ++nfev > eval_cap) {
-      status = 2;
-      active = false;
-    }
-    if (active) {
-      const double dphi = gsum<G>(gt * pk);
-      double next = stp;
-      const int r = ls.advance(stp, ft, dphi, &next);
-      if (r == LS_EVAL) {
-        stp = next;
-      } else if (r == LS_FAIL) {
-        status = 2;
-        active = false;
-      } else {
-        const double sk = stp * pk;
-        const double pnorm2 = gsum<G>(pk * pk);
-        xk = xk + sk;
-        const double yk = gt - gk;
-        gk = gt;
-        old_old = fk;
-        fk = ft;
-        ++kiter;
-        const double gnorm = gmax<G>(fabs(gk));
-        if (!(gnorm > gtol)) {
-          active = false;
-        } else if (stp * sqrt(pnorm2) <= 0.0) {  // xrtol = 0 test
-          active = false;
-        } else if (!isfinite(fk)) {
-          status = 2;
-          active = false;
-        } else if (!(kiter < max_iter)) {
-          active = false;
-        } else {
-          const double ys = gsum<G>(yk * sk);
-          const double rhok = (ys == 0.0) ? 1000.0 : 1.0 / ys;
-          const int np = kiter - 1;  // index of the new pair
-          if (np < LP) {
-            lp[(2 * np) * D] = sk;
-            lp[(2 * np + 1) * D] = yk;
-          } else {
-            my[(size_t)(2 * np) * D] = sk;
-            my[(size_t)(2 * np + 1) * D] = yk;
-          }
-          if (c.l == 0) prho[np] = rhok;
-          wave_sync();
-          double q = gk;
-          for (int i = np; i >= 0; --i) {
-            double si = sk, yi = yk;
-            if (i != np) {
-              if (i < LP) {
-                si = lp[(2 * i) * D];
-                yi = lp[(2 * i + 1) * D];
-              } else {
-                si = my[(size_t)(2 * i) * D];
-                yi = my[(size_t)(2 * i + 1) * D];
-              }
-            }
-            const double a = prho[i] * gsum<G>(si * q);
-            if (c.l == 0) palpha[i] = a;
-            q = fma(-a, yi, q);
-          }
-          wave_sync();
-          for (int i = 0; i <= np; ++i) {
-            double si = sk, yi = yk;
-            if (i != np) {
-              if (i < LP) {
-                si = lp[(2 * i) * D];
-                yi = lp[(2 * i + 1) * D];
-              } else {
-                si = my[(size_t)(2 * i) * D];
-                yi = my[(size_t)(2 * i + 1) * D];
-              }
-            }
-            const double bb = prho[i] * gsum<G>(yi * q);
-            q = fma(si, palpha[i] - bb, q);
-          }
-          pk = -q;
-          ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
-        }
-      }
-    }
-    wave_sync();
-  }
-  if (status == 0) {
-    const double gn = gmax<G>(fabs(gk));
-    const double xn = gmax<G>(fabs(xk));
-    if (kiter >= max_iter) status = 3;
-    else if (gn != gn || fk != fk || xn != xn) status = 4;
-  }
-  double tr;
-  const cd m = S::build_llh(c, xk, tr);
-  S::emit(c, rho, b, mine, cd{m.re / tr, m.im / tr});
-  if (mine) {
-    if (c.l == 0) {
-      if (nit_out) nit_out[b] = kiter;
-      if (nfev_out) nfev_out[b] = nfev;
-      if (fun_out) fun_out[b] = fk;
-      if (status_out) status_out[b] = status;
-    }
-  }
+  LineSearch& ls = *reinterpret_cast<LineSearch*>(c.extra());
+  bfgs_loop<NQ>(c, dir, ls, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
 }
 
 #ifndef QT_BFGS_WAVES
@@ -2801,7 +2753,7 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     if constexpr (GENERIC) r1 = pv.pr.R1;
     const int per_trial = S::trial_doubles(pv.M, r1);
     trial_sm = smem + S::table_doubles(pv.M, r1) + (threadIdx.x >> 6) * (per_trial + pv.extra);
-    link.base = trial_sm + per_trial + LineSearch::SLOTS + 2 * max_iter;  // bfgs_iterate_2l's `lp`
+    link.base = trial_sm + per_trial + LineSearch::SLOTS + 2 * max_iter;  // TwoLoop::lp
     twin = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
     link.pending = 0;
     if (!twin) link.reset();  // (in front of the workgroup barrier of make_ctx: the twin finds its words set up)
@@ -2902,24 +2854,8 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   const bool iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
   if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
   S::emit(c, rho, b, live && !iterate, rho_l);  // (trials that iterate are written at the end of the loop)
-  if (!iterate) {
-    int status = 0;
-    if (!shots_ok) status = 5;
-    else if (!ok) status = 1;
-    else {
-      const bool xnan = group_any<G>(xk != xk);
-      if (0 >= max_iter) status = 3;
-      else if (gnorm != gnorm || fk != fk || xnan) status = 4;
-    }
-    if (live) {
-      if (c.l == 0) {
-        if (nit_out) nit_out[b] = 0;
-        if (nfev_out) nfev_out[b] = ok ? 1 : 0;
-        if (fun_out) fun_out[b] = fk;
-        if (status_out) status_out[b] = status;
-      }
-    }
-  }
+  const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));
+  if (live && !iterate && c.l == 0) store_trial(b, 0, ok ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
   QT_STAMP(10);
   if (!__any(iterate)) return;  // per wave
   if (!iterate) {                // finite dummies for the groups of this wave that are already done

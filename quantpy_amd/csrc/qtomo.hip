@@ -27,6 +27,16 @@
 #include "qt_sampler.h"
 #include "qt_small.h"
 
+// the kernels' names (qt_linesearch.h) for the trial statuses of the public header
+#define QT_SAME_STATUS(name) static_assert((int)qt::TRIAL_##name == (int)QT_TRIAL_##name, "qt::TrialStatus is QT_TRIAL_*")
+QT_SAME_STATUS(OK);
+QT_SAME_STATUS(NOT_PD);
+QT_SAME_STATUS(LINESEARCH);
+QT_SAME_STATUS(MAXITER);
+QT_SAME_STATUS(NAN);
+QT_SAME_STATUS(SHOTS);
+#undef QT_SAME_STATUS
+
 namespace {
 
 #ifdef QT_PHASE_TIMING

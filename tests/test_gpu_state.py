@@ -222,6 +222,53 @@ def test_mle_options_and_statuses(oracle):
     assert eng.mle(np.zeros((0, 27, 8), dtype=np.int64)).shape == (0, 8, 8)  # empty batch
 
 
+_CAPPED_REF = {}
+
+
+def _capped_reference(oracle, n, max_iter, counts):
+    """The oracle's port of scipy BFGS under the same cap: once per (n, max_iter), shared by both launch variants."""
+    if (n, max_iter) not in _CAPPED_REF:
+        a = oracle.measurement_matrix("proj-set", n)
+        _CAPPED_REF[n, max_iter] = [oracle.mle_estimate(c, a, init="mixed", max_iter=max_iter, solver="port")
+                                    for c in counts]
+    return _CAPPED_REF[n, max_iter]
+
+
+@pytest.mark.parametrize("variant", ["fused", "split"])
+@pytest.mark.parametrize("max_iter", [1, 2])
+@pytest.mark.parametrize("n", [1, 2])
+def test_mle_iteration_cap_dense_form(oracle, n, max_iter, variant):
+    """The iteration cap at n = 1, 2 (inverse Hessian in registers), through the one-launch kernel and the split pair:
+    the 17 'mixed'-start trials of tests/golden/mle_diet_bits.npz, whose uncapped runs are recorded there.  A trial
+    that took more than max_iter iterations stops at the cap with QT_TRIAL_MAXITER and the state of scipy's BFGS under
+    the same cap (1e-9: the bound of test_mle_options_and_statuses at n = 3); one that needed no more gives its
+    recorded bits."""
+    import quantpy_amd as qp
+    from quantpy_amd import _capi
+
+    g = load_golden("mle_diet_bits")
+    counts = g[f"n{n}_b17/counts"]
+    rec = {k: g[f"n{n}_b17_mixed/{variant}/{k}"] for k in ("nit", "status", "rho")}
+    eng = _eng(n)
+    a = qp.generate_measurement_matrix("proj-set", n)
+    eng.set_povm(a, np.ones(np.asarray(a).shape[0]) * 400)
+    eng.set_option(_capi.QT_OPT_MLE_FUSED_MAX_WAVES, 0 if variant == "split" else 1024)
+    try:
+        rho, info = eng.mle(counts, init="mixed", max_iter=max_iter, return_info=True)
+    finally:
+        eng.set_option(_capi.QT_OPT_MLE_FUSED_MAX_WAVES, 1024)
+    capped = rec["nit"] > max_iter
+    assert capped.any()
+    ref = _capped_reference(oracle, n, max_iter, counts)
+    for t in range(len(counts)):
+        if capped[t]:
+            assert info["nit"][t] == max_iter and info["status"][t] == _capi.TRIAL_MAXITER, (t, info)
+            assert abs(oracle.infidelity(ref[t], rho[t])) < 1e-9, t
+        else:
+            assert info["nit"][t] == rec["nit"][t] and info["status"][t] == rec["status"][t], (t, info)
+            assert np.array_equal(np.ascontiguousarray(rho[t]).view(np.float64), rec["rho"][t]), t
+
+
 def test_mle_random_batches_vs_oracle(oracle):
     """seeded random trials at ragged batch sizes (partial last wave at n = 1, 2)."""
     for n, shots, nb in ((1, 200, 37), (2, 300, 11), (3, 500, 5)):
