@@ -90,9 +90,13 @@ __device__ __forceinline__ void wave_sync() {
 // four v_readlane across the rows.  Every lane of a group ends with the same bits.
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ double dpp_f64(double v) {
-  // Full row mask: every lane has a source under the permutations used here, so bound_ctrl lets the
-  // compiler drop the zero-initialisation of the destination.  Partial row mask (row_bcast steps):
-  // the rows left out must read as 0.
+  // Full row mask and bound_ctrl: a lane without a source reads 0 and the compiler needs no zero-initialisation of the
+  // destination.  Under the permutations inside a row every lane has a source.  The row_bcast steps once ran with a
+  // partial row mask (0xA, 0xC) so that the rows they do not feed kept their values, which took an initialised
+  // destination (two v_mov_b32 v, 0 per step).  Nothing needs that: the reductions hand out lane 63 alone, whose tree
+  // (r3 + r2) + (r1 + r0) reads lane 47 in the first step and lane 31 -- row 1, fed by the first step -- in the second.
+  // With the full mask rows 0 (first step) and 0 - 1 (second) add a 0 to values that nobody reads.  ROW_MASK stays a
+  // parameter for a caller that does read the other rows.
   const long long b = __builtin_bit_cast(long long, v);
   const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffLL), CTRL, ROW_MASK, 0xf, ROW_MASK == 0xf);
   const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, ROW_MASK == 0xf);
@@ -108,7 +112,8 @@ __device__ __forceinline__ double nanmax(double a, double b) { return (b > a || 
 
 // Across the four rows of a wavefront: row_bcast15 adds the total of row 0 / 2 into row 1 / 3,
 // row_bcast31 adds lane 31 (rows 0+1) into rows 2 and 3, lane 63 then holds (r2 + r3) + (r0 + r1) and
-// is handed to every lane through an SGPR pair (6 + 2 instructions instead of 8 readlanes + 7).
+// is handed to every lane through an SGPR pair (6 + 2 instructions instead of 8 readlanes + 7).  Lane 63 is the only
+// lane anybody reads: what the two steps leave in rows 0 - 2 is not a sum of anything (see dpp_f64).
 template <int G>
 __device__ __forceinline__ double gsum(double v) {
   v += dpp_f64<0xB1>(v);                 // quad_perm [1,0,3,2]
@@ -116,11 +121,30 @@ __device__ __forceinline__ double gsum(double v) {
   if (G >= 8) v += dpp_f64<0x141>(v);    // row_half_mirror
   if (G >= 16) v += dpp_f64<0x140>(v);   // row_mirror
   if (G == 64) {
-    v += dpp_f64<0x142, 0xA>(v);         // row_bcast15 -> rows 1, 3
-    v += dpp_f64<0x143, 0xC>(v);         // row_bcast31 -> rows 2, 3
+    v += dpp_f64<0x142>(v);              // row_bcast15: lane 15 of row 0 / 1 / 2 -> rows 1 / 2 / 3 (row 0: + 0)
+    v += dpp_f64<0x143>(v);              // row_bcast31: lane 31 -> rows 2, 3 (rows 0, 1: + 0)
     v = readlane_f64(v, 63);
   }
   return v;
+}
+// Trace of a d x d matrix held one element per lane (lane = i d + j): the bits of gsum<G>(diag ? x : 0.0), `diag` = this
+// lane is (i, i).  At G = 64 (d = 8) the diagonal sits in lanes 9 i, two per row at positions 2 r and 2 r + 9 of row r,
+// in different halves of the row: in gsum's butterfly the first three steps add + 0.0 to each of them three times and
+// the two of a row first meet in row_mirror, where lane 15 forms x(2 r + 9) + x(2 r).  Here one + 0.0 stands for the
+// three (x + 0.0 is x except that it turns -0.0 into +0.0, and it is idempotent: without it a diagonal of nothing but
+// -0.0 would give -0.0 where gsum gives +0.0), row_shr:9 forms the same sum, same operand order, in lane 2 r + 9 of
+// each row, and as those lanes are not the lane 15 that row_bcast reads, the three sums across the rows go through
+// SGPR pairs: (s3 + s2) in lane 63, (s1 + s0) in lane 27, then their sum in lane 63 -- gsum's tree.  17 instructions
+// as compiled for the 28 of gsum<64> with the select in front of it (profiles/chain_diet_isa.txt).
+template <int G>
+__device__ __forceinline__ double gtrace(bool diag, double x) {
+  double v = diag ? x : 0.0;
+  if (G != 64) return gsum<G>(v);
+  v += 0.0;
+  v += dpp_f64<0x119>(v);                              // row_shr:9, lanes 0 - 8 of a row read 0: s_r in lane 18 r + 9
+  const double hi = v + readlane_f64(v, 45);           // lane 63: s3 + s2
+  const double lo = v + readlane_f64(v, 9);            // lane 27: s1 + s0
+  return readlane_f64(hi + readlane_f64(lo, 27), 63);  // lane 63: (s3 + s2) + (s1 + s0)
 }
 // "Does `pred` hold in any lane of this lane's group": one ballot and a mask (the whole wave at G = 64).  Executed by
 // every lane of the wavefront.
@@ -140,7 +164,8 @@ __device__ __forceinline__ double max_f64(double a, double b) {
   return r;
 }
 // Maximum of non-negative values (every caller passes fabs(.)); a NaN anywhere wins: the butterfly itself passes over
-// NaNs, one ballot finds them.  The rows a row_bcast step leaves out read 0, which is neutral for such inputs.
+// NaNs, one ballot finds them.  The rows a row_bcast step does not feed take the maximum with 0: neutral for such inputs,
+// and none of them is on the way to lane 63.
 template <int G>
 __device__ __forceinline__ double gmax(double v) {
   const bool nan = group_any<G>(v != v);
@@ -149,8 +174,8 @@ __device__ __forceinline__ double gmax(double v) {
   if (G >= 8) v = max_f64(v, dpp_f64<0x141>(v));
   if (G >= 16) v = max_f64(v, dpp_f64<0x140>(v));
   if (G == 64) {
-    v = max_f64(v, dpp_f64<0x142, 0xA>(v));
-    v = max_f64(v, dpp_f64<0x143, 0xC>(v));
+    v = max_f64(v, dpp_f64<0x142>(v));
+    v = max_f64(v, dpp_f64<0x143>(v));
     v = readlane_f64(v, 63);
   }
   return nan ? __builtin_nan("") : v;
@@ -1039,8 +1064,8 @@ struct Small {
     if (G >= 8 && KK < 8) v += dpp_f64<0x141>(v);
     if (G >= 16 && KK < 16) v += dpp_f64<0x140>(v);
     if (G == 64) {
-      v += dpp_f64<0x142, 0xA>(v);
-      v += dpp_f64<0x143, 0xC>(v);
+      v += dpp_f64<0x142>(v);
+      v += dpp_f64<0x143>(v);
       v = readlane_f64(v, 63);
     }
     return v;
@@ -1825,7 +1850,7 @@ struct Small {
     static_assert(G == 64, "one trial per wavefront");
     CtxH c = side_ctx(t, k, t.Bm());
     proj = cd{0.0, 0.0};
-    const bool lifted = __builtin_amdgcn_readfirstlane((int)lift_single_negative(c, lin, d - 1, 1e-15, proj, nullptr)) != 0;
+    const bool lifted = __builtin_amdgcn_readfirstlane((int)lift_single_negative<true>(c, lin, d - 1, 1e-15, proj, nullptr)) != 0;
     QT_STAMP(6);
     // (an abandoned lift finds its kAbort here at the first look)
     if (HelperLink::template poll<1>(k.verdict(), HelperLink::kPending, HelperLink::kHelperPolls) != HelperLink::kGo) return false;
@@ -1879,8 +1904,11 @@ struct Small {
   // Jacobi eigensolver on the untouched input) on a slow ratio, a positive lam, or a failed check.
   // `inverse`: the lane's element of A^{-1} when the caller already has it (cholesky_param<true>, kneg = d - 1).
   // One function for the trial's wavefront and for the helper wavefront of k_mle_fused_hw, which runs it before anybody
-  // knows whether it is wanted and returns false as soon as C::abandoned says it is not (HelperLink).
-  template <class C>
+  // knows whether it is wanted and returns false behind the squaring in which C::abandoned says it is not (HelperLink).
+  // NATURAL: the caller's kneg is d - 1 at compile time (the twin of k_mle_fused_hw: the natural pivot order 0 .. d - 1).
+  // The d steps are then unrolled: the pivot comes from a constant lane, the LDS offsets of row and column p are
+  // immediates, and the step counter, its compare and its branch are gone.  The arithmetic of a step is the same text.
+  template <bool NATURAL = false, class C>
   __device__ static bool lift_single_negative(const C& c, cd r, int kneg, double eps, cd& out,
                                               const cd* inverse = nullptr) {
     static_assert(G == 64, "one trial per wavefront: the flags below are wave-uniform");
@@ -1890,9 +1918,7 @@ struct Small {
     if (i == j) r.im = 0.0;
     cd b = r;
     if (inverse) b = *inverse;
-#pragma unroll 1
-    for (int s = inverse ? d : 0; s < d; ++s) {
-      const int p = s < kneg ? s : (s < d - 1 ? s + 1 : kneg);
+    auto eliminate = [&](int p) {  // one Gauss-Jordan step on pivot p
       Ai[c.e] = b;
       const double piv = readlane_f64(b.re, p * d + p);  // from lane (p, p): no LDS wait before 1 / pivot
       wave_sync();
@@ -1907,14 +1933,30 @@ struct Small {
       if (j == p) nb = cd{-bip.re * inv, -bip.im * inv};
       if (i == p) nb = (j == p) ? cd{inv, 0.0} : t;
       b = nb;
+    };
+    if constexpr (NATURAL) {
+      if (!inverse) {
+#pragma unroll
+        for (int p = 0; p < d; ++p) eliminate(p);
+      }
+    } else {
+#pragma unroll 1
+      for (int s = inverse ? d : 0; s < d; ++s) eliminate(s < kneg ? s : (s < d - 1 ? s + 1 : kneg));
     }
     QT_STAMP(4);
     // X_k is kept at Frobenius norm 1, i.e. sum sigma_i^2 = 1; then ||X_k X_k^dagger||_F^2 = sum sigma_i^4
     // is the purity of that spectrum: one reduction per squaring gives both the scale and the test.
     b = cscale(b, fast_rsqrt(gsum<G>(b.re * b.re + b.im * b.im)));
-    bool certified = false, done = false;
+    // At most seven squarings.  The one that certifies (defect < 1e-7) is followed by exactly one more, which ends the
+    // loop with `certified` set; it ends without it behind the seventh squaring (certifying there is too late) and
+    // behind the third when the ratio is slow; a helper wavefront also leaves once the trial has called the lift off
+    // (it finishes the squaring it is in: the look rides on that squaring's LDS reads).  The tests are wave-uniform and
+    // combined without short-circuit into ONE exit, behind which the two flags tell the ends apart: an iteration that
+    // goes on pays for one branch.  (With an exit per test the compiler numbers the exits in a register and dispatches
+    // on it behind the loop: about twenty scalar instructions per iteration.)
+    bool certified = false, called_off = false;
 #pragma unroll 1
-    for (int k = 1; k <= 7 && !done; ++k) {
+    for (int k = 1;; ++k) {
       Ai[c.e] = b;
       wave_sync();
       [[maybe_unused]] const int verdict = c.verdict_load();  // (helper wavefront: ahead of the reads below, looked at behind them)
@@ -1932,7 +1974,7 @@ struct Small {
       }
       n = cadd(n, n2);
       wave_sync();
-      if (c.abandoned(verdict)) return false;  // helper wavefront: the trial has no use for this lift
+      called_off = c.abandoned(verdict);  // helper wavefront: the trial has no use for this lift
       const double pur = gsum<G>(n.re * n.re + n.im * n.im);
       b = cscale(n, fast_rsqrt(pur));
       const double defect = 1.0 - pur;  // ~ 2 (sigma_2 / sigma_1)^(2^(k+1))
@@ -1940,14 +1982,14 @@ struct Small {
 #ifdef QT_PHASE_TIMING
       if (k <= 5) QT_STAMP(25 + k);
 #endif
-      if (certified) done = true;
-      else if (defect < 1e-7) certified = true;
-      else if (k == 3 && !(defect < 0.05)) return false;  // ratio > ~0.8: the eigensolver is cheaper
+      // k == 3 and not below 0.05: ratio > ~0.8, the eigensolver is cheaper (a defect below 1e-7 never takes that exit)
+      if (called_off | certified | (k == 7) | ((k == 3) & !(defect < 0.05))) break;
+      certified = defect < 1e-7;
     }
     QT_STAMP(5);
-    if (!done) return false;
+    if (called_off || !certified) return false;
     if (i == j) b.im = 0.0;
-    b = cscale(b, 1.0 / gsum<G>(i == j ? b.re : 0.0));      // N = X / Tr X
+    b = cscale(b, 1.0 / gtrace<G>(i == j, b.re));            // N = X / Tr X
     const double lam = gsum<G>(r.re * b.re + r.im * b.im);  // Tr(A N) = sum_ij A_ij conj(N_ij)
     if (!(lam < eps)) return false;
     Ai[c.e] = r;
@@ -1966,7 +2008,7 @@ struct Small {
     if (!(res2 <= 1e-26 * nrm2)) return false;
     const double w = eps - lam;
     cd o{fma(w, b.re, r.re), fma(w, b.im, r.im)};
-    const double tr = gsum<G>(i == j ? o.re : 0.0);
+    const double tr = gtrace<G>(i == j, o.re);
     out = cd{o.re / tr, o.im / tr};
     return true;
   }
@@ -1992,7 +2034,7 @@ struct Small {
     cd out{0.0, 0.0};
     double lscale = 1.0;
     auto pd_epilogue = [&]() {
-      const double tr = gsum<G>(c.i == c.j ? r.re : 0.0);
+      const double tr = gtrace<G>(c.i == c.j, r.re);
       out = cd{r.re / tr, r.im / tr};
       const double rst = tr > 0.0 ? fast_rsqrt(tr) : 1.0 / sqrt(tr);
       x = x * rst;   // L of r/tr
