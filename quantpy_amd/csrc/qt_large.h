@@ -5,8 +5,8 @@
 // same formulas apply with __syncthreads() in place of the wave fence and a two-level (DPP + LDS)
 // reduction in place of the DPP butterfly.  What changes is where things live:
 //   * LDS (<= 160 KB): L, the broadcast vector, and two overlaid work regions X / Y that hold the
-//     stages of the factorised POVM contraction (R-order, see qt_small.h) and, outside of it, the
-//     images of the eigenvalue clip and the gradient matrix.  At n = 5 with 'proj-set' (M = 6^5 = 7776):
+//     stages of the factorised POVM contraction (R-order, see ProductView in qt_args.h) and, outside
+//     of it, the images of the eigenvalue clip and the gradient matrix.  At n = 5 with 'proj-set' (M = 6^5 = 7776):
 //     X = 7776, Y = 5184 doubles -> 127 KB.  Frequencies are not stored: they are re-read from the
 //     counts (int64, gathered through the R-order row map) when needed.
 //   * The BFGS inverse Hessian is never formed.  A dense D x D f64 H (8 MB per trial at n = 5) had to be
@@ -26,9 +26,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qt_args.h"
 #include "qt_linesearch.h"
 #include "qt_signclip_wg.h"
-#include "qt_small.h"
+#include "qt_wave.h"
 
 namespace qt {
 
@@ -1071,7 +1072,7 @@ k_mle_large_bfgs(PovmView pv, const int64_t* __restrict__ counts, int B,
   if (c.t == 0) store_trial(b, kiter, nfev, fk, status, nit_out, nfev_out, fun_out, status_out);
 }
 
-// k_mhmc_state (qt_small.h) at n = 4, 5: one workgroup per chain, thread t owns parameter x[t].  Step t:
+// k_mhmc_state (qt_mhmc_state.h) at n = 4, 5: one workgroup per chain, thread t owns parameter x[t].  Step t:
 //   x' = (x + step * delta_t) / ||x + step * delta_t||,  alpha = exp(nll(x) - nll(x')),  accept iff u_t <= alpha.
 // chain[c][t][:] = the state AFTER step t, accepted[c][t] = 0 / 1.  The accept test reads only values every thread holds
 // bit for bit (f, fn from bsum) and u_t from one address, so the branch is uniform over the workgroup.

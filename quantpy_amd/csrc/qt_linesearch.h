@@ -18,6 +18,7 @@
 #include <math.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define QT_HD __host__ __device__ __forceinline__
 #else
 #define QT_HD inline
@@ -360,7 +361,7 @@ struct LineSearch {
 };
 
 // ---- The scalar decisions of scipy's _minimize_bfgs around the line search, once for every MLE kernel (n <= 3:
-// bfgs_loop, k_mle_start, mle_fused_body in qt_small.h; n = 4, 5: k_mle_large_start, k_mle_large_bfgs in qt_large.h).
+// bfgs_loop, k_mle_start, mle_fused_body in qt_mle_small.h; n = 4, 5: k_mle_large_start, k_mle_large_bfgs in qt_large.h).
 
 // What a trial reports: QT_TRIAL_* of include/qtomo.h (qtomo.hip asserts the equality).  SciPy's warnflag 2 -> 2,
 // 1 -> 3, 3 -> 4.

@@ -6,7 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qt_small.h"  // gsum / dpp reductions
+#include "qt_args.h"  // centre_of
+#include "qt_wave.h"  // gsum / dpp reductions
 
 namespace qt {
 
@@ -543,7 +544,7 @@ __global__ void k_mat_from_bloch(int nq, const double* __restrict__ bloch, int B
 }
 
 // ---- a16: geometry.py:16-20, one wavefront per trial -----------------------------------------
-// `centres` holds G matrices; trial b (= the workgroup) is measured against centre (g0 + b) % G (centre_of, qt_small.h).
+// `centres` holds G matrices; trial b (= the workgroup) is measured against centre (g0 + b) % G (centre_of, qt_args.h).
 __global__ void __launch_bounds__(64) k_hs_dist(int d, const double* __restrict__ rho, const double* __restrict__ centres,
                                                 int G, int g0, int B, double* __restrict__ dist) {
   const int b = blockIdx.x;

@@ -12,9 +12,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qt_args.h"     // centre_of
+#include "qt_ops.h"      // v4f64
+#include "qt_sampler.h"  // mhmc_draw
 #include "qt_signclip_wg.h"
-#include "qt_ops.h"    // v4f64
-#include "qt_small.h"  // gsum
+#include "qt_wave.h"     // gsum
 
 namespace qt {
 
@@ -215,7 +217,7 @@ struct ProcWG {
           const double app = sh.are[p * LDC + p], aqq = sh.are[q * LDC + q];
           const double xr = sh.are[p * LDC + q], xi = sh.aim[p * LDC + q];
           const double ab2 = xr * xr + xi * xi;
-          double cs = 1.0, wre = 0.0, wim = 0.0;  // w = s e^{i phi} = c u a_pq  (see qt_small.h)
+          double cs = 1.0, wre = 0.0, wim = 0.0;  // w = s e^{i phi} = c u a_pq  (see rotation, qt_wave.h)
           if (ab2 > 1e-300) {
             const double dl = 0.5 * (aqq - app);
             const double u = copysign(1.0, dl) / (fabs(dl) + sqrt(dl * dl + ab2));

@@ -21,9 +21,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qt_args.h"         // centre_of
 #include "qt_ops.h"          // v4f64
 #include "qt_signclip_wg.h"  // SignSchedule, sign_clip_degenerate, sign_clip_epilogue
-#include "qt_small.h"        // cd, gsum, wave_sync, readlane_f64
+#include "qt_wave.h"         // cd, gsum, wave_sync, readlane_f64
 
 namespace qt {
 

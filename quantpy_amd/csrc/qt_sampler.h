@@ -14,15 +14,18 @@
 // The binomial / multinomial routines are templates over the generator of uniform doubles and compile for host and
 // device: with `Mt19937` on the host they ARE the bit-exact path above; with `Philox` (counter-based, below) one GPU
 // thread draws one multinomial row independently of every other row (`k_multinomial_rows`, opt-in
-// `sampler="device"`: same distribution, NOT the reference's stream).  Floating-point contraction is off in here:
-// every product and sum rounds as NumPy's build rounds it.
+// `sampler="device"`: same distribution, NOT the reference's stream).  Floating-point contraction is off in every
+// function here that does arithmetic: every product and sum rounds as NumPy's build rounds it.  The pragma is the first
+// statement of each such body, never at file scope: there it would not end with the namespace but hold to the end of
+// the translation unit, and every kernel defined behind this header would lose its FMAs (DESIGN: header map).
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 namespace qt_sampler {
-
-#pragma clang fp contract(off)
 
 #if defined(__HIPCC__)
 #define QT_SAMPLER_HD __host__ __device__
@@ -61,11 +64,13 @@ inline uint32_t Mt19937::next() { return mt_next(*this); }
 
 // the legacy 53-bit double: 27 high bits of one word, 26 of the next
 QT_SAMPLER_HD inline double u53_words(uint32_t w0, uint32_t w1) {
+#pragma clang fp contract(off)
   const int32_t a = (int32_t)(w0 >> 5), b = (int32_t)(w1 >> 6);
   return (a * 67108864.0 + b) / 9007199254740992.0;
 }
 template <class G>
 QT_SAMPLER_HD inline double uniform53(G& g) {
+#pragma clang fp contract(off)
   const uint32_t w0 = g.next();
   const uint32_t w1 = g.next();
   return u53_words(w0, w1);
@@ -124,6 +129,7 @@ struct BinomialSetup {
 // n p <= 30: walk the mass function from 0 upwards; restart with a fresh uniform past `bound`
 template <class G>
 QT_SAMPLER_HD inline int64_t binomial_inversion(G& g, int64_t n, double p, BinomialSetup& s) {
+#pragma clang fp contract(off)
   if (!s.valid || s.btpe || s.n != n || s.p != p) {
     s.valid = true, s.btpe = false, s.n = n, s.p = p;
     s.q = 1.0 - p;
@@ -154,6 +160,7 @@ QT_SAMPLER_HD inline int64_t binomial_inversion(G& g, int64_t n, double p, Binom
 // squeeze / exact acceptance tests of the published algorithm
 template <class G>
 QT_SAMPLER_HD inline int64_t binomial_btpe(G& g, int64_t n, double p, BinomialSetup& s) {
+#pragma clang fp contract(off)
   if (!s.valid || !s.btpe || s.n != n || s.p != p) {
     s.valid = true, s.btpe = true, s.n = n, s.p = p;
     s.r = p < 1.0 - p ? p : 1.0 - p;
@@ -232,6 +239,7 @@ QT_SAMPLER_HD inline int64_t binomial_btpe(G& g, int64_t n, double p, BinomialSe
 
 template <class G>
 QT_SAMPLER_HD inline int64_t legacy_binomial(G& g, double p, int64_t n, BinomialSetup& s) {
+#pragma clang fp contract(off)
   if (n == 0 || p == 0.0) return 0;  // no word consumed (RandomState.multinomial shares random_binomial's early exit)
   if (p <= 0.5) return p * n <= 30.0 ? binomial_inversion(g, n, p, s) : binomial_btpe(g, n, p, s);
   const double q = 1.0 - p;
@@ -241,6 +249,7 @@ QT_SAMPLER_HD inline int64_t legacy_binomial(G& g, double p, int64_t n, Binomial
 // one RandomState.multinomial(n, pvals) row: conditional binomials, first to last-but-one category
 template <class G>
 QT_SAMPLER_HD inline void legacy_multinomial(G& g, int64_t n, const double* pvals, int K, int64_t* out, BinomialSetup* cache) {
+#pragma clang fp contract(off)
   double remaining_p = 1.0;
   int64_t dn = n;
   for (int j = 0; j < K; ++j) out[j] = 0;
@@ -259,6 +268,7 @@ QT_SAMPLER_HD inline void legacy_multinomial(G& g, int64_t n, const double* pval
 // (tests/host/sampler_host.cpp) beside the kernel on the same streams -- same template, same uniforms, same counts.
 QT_SAMPLER_HD inline void philox_multinomial_row(uint64_t seed, uint64_t global_row, int64_t n_s, const double* p, int K,
                                                   int64_t* o) {
+#pragma clang fp contract(off)
   Philox g(seed, global_row, 0u);
   BinomialSetup setup;
   double remaining_p = 1.0;
@@ -286,6 +296,7 @@ QT_SAMPLER_HD inline void philox_multinomial_row(uint64_t seed, uint64_t global_
 // on the host or on any lane of any launch, gets the same number (the libm / device math functions agree to a few ulp
 // in the increments; the uniforms are exact).
 QT_SAMPLER_HD inline double mhmc_draw(uint64_t seed, uint64_t chain, uint32_t step, int D, int l) {
+#pragma clang fp contract(off)
   const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
   const uint32_t ctr[4] = {(uint32_t)(l >> 1), (uint32_t)chain, (uint32_t)(chain >> 32), 1u + step};
   uint32_t w[4];
@@ -302,6 +313,7 @@ QT_SAMPLER_HD inline double mhmc_draw(uint64_t seed, uint64_t chain, uint32_t st
 // mhmc_draw (the table the fused chain kernel never writes: for tests, and for feeding qt_mhmc_state)
 __global__ void __launch_bounds__(256) k_mhmc_draws(uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T, int D,
                                                     double* __restrict__ deltas, double* __restrict__ uniforms) {
+#pragma clang fp contract(off)
   const size_t total = (size_t)C * T * (D + 1);
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
     const int l = (int)(t % (size_t)(D + 1));
@@ -318,6 +330,7 @@ __global__ void __launch_bounds__(256) k_mhmc_draws(uint64_t seed, uint64_t firs
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) k_multinomial_rows(uint64_t seed, uint64_t first_row, long long rows, int period,
                                                           const int64_t* __restrict__ n, const double* __restrict__ pvals,
                                                           int K, int64_t* __restrict__ out) {
+#pragma clang fp contract(off)
   // thread -> row: a wavefront takes ONE setting of 64 consecutive resamples (same n, same p: one branch structure
   // through the set-up and the choice inversion / BTPE), `period` wavefronts cover a block of 64 x period rows
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;

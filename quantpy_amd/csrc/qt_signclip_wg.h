@@ -39,7 +39,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qt_small.h"
+#include "qt_wave.h"
 
 namespace qt {
 

@@ -19,378 +19,20 @@
 //   chol: routines.py:84-101
 //   nll:  tomography/state.py:217-229 (value); gradient derived analytically
 //   mle:  tomography/state.py:204-215 with scipy's BFGS control flow (qt_linesearch.h)
+//
+// Here: Small<NQ> and the estimator kernels that are thin wrappers over it.  Around it: the wave-level primitives in
+// qt_wave.h, the POVM views and per-trial argument structs in qt_args.h, the MLE drivers in qt_mle_small.h, the
+// Metropolis-Hastings chains in qt_mhmc_state.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
-#include "qt_linesearch.h"
+#include "qt_args.h"
+#include "qt_wave.h"
 
 namespace qt {
 
-// Optional per-wave phase stamps (shader clock) for scripts/phase_timing.py: compiled in only with
-// -DQT_PHASE_TIMING (lib/libqtomo_prof.so); the product library carries none of this.
-#ifdef QT_PHASE_TIMING
-__device__ long long* g_qt_prof = nullptr;  // [waves][32]
-// One row per wavefront of threadIdx.y = 0; the helper wavefronts of k_mle_fused_hw (threadIdx.y = 1) have theirs behind
-// those of the whole grid, in the same order.
-#define QT_PROF_ROW \
-  ((size_t)(blockIdx.x + threadIdx.y * gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6))
-#define QT_STAMP(slot)                                                                                   \
-  do {                                                                                                   \
-    if (g_qt_prof && (threadIdx.x & 63) == 0)                                                            \
-      g_qt_prof[QT_PROF_ROW * 32 + (slot)] = (long long)__builtin_readcyclecounter();                    \
-  } while (0)
-#define QT_STAMP_VAL(slot, val)                                                                          \
-  do {                                                                                                   \
-    if (g_qt_prof && (threadIdx.x & 63) == 0)                                                            \
-      g_qt_prof[QT_PROF_ROW * 32 + (slot)] = (val);                                                      \
-  } while (0)
-#else
-#define QT_STAMP(slot) do {} while (0)
-#define QT_STAMP_VAL(slot, val) do {} while (0)
-#endif
-
-// 16-byte aligned: a complex element then moves with ONE ds_read_b128 / ds_write_b128 (4 LDS cycles per
-// wavefront read, conflict-free on consecutive elements).  With 8-byte alignment hipcc emits ds_read2_b64 /
-// ds_write2_b64, whose two 8-byte halves each stride 16 bytes across the lanes: a built-in 2-way bank
-// conflict, 16 cycles per read (measured on the n = 5 Jacobi rounds: 2700 -> see DESIGN 4.5).  Every cd
-// array in LDS starts at an even double offset (checked where the layouts are defined).
-struct alignas(16) cd {
-  double re, im;
-};
-__device__ __forceinline__ cd cmul(cd a, cd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cd cmulc(cd a, cd b) {  // a * conj(b)
-  return {a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im};
-}
-__device__ __forceinline__ cd cadd(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
-// One term Delta_ij Delta_ji of Tr(Delta^2) (geometry.py:16), with its rounding pinned (one product rounded, then one
-// fma) so that every kernel that forms a Hilbert-Schmidt distance gets the same bits from the same operands.
-__device__ __forceinline__ cd hs_term(cd a, cd b) {
-  return {__builtin_fma(a.re, b.re, -(a.im * b.im)), __builtin_fma(a.re, b.im, a.im * b.re)};
-}
-__device__ __forceinline__ cd cscale(cd a, double s) { return {a.re * s, a.im * s}; }
-
-// LDS hand-off inside ONE wavefront: order this wave's LDS writes before its later reads.  The hardware already does:
-// the LDS executes the DS instructions of a wavefront in issue order, each for all 64 lanes before the next starts, so a
-// ds_read behind a ds_write of the same wave sees the data whichever lane wrote it.  What is needed is that the
-// COMPILER keeps the order (to it, another lane's slot is just a different address): a scheduling barrier plus an
-// empty asm with a memory clobber.  Rounds 1-2 used release / acquire fences at workgroup scope here, which cost an
-// `s_waitcnt lgkmcnt(0)` -- a full drain of the LDS queue, ~100 clocks -- at each of the ~100 hand-offs of a trial.
-// (Never a cross-wave hand-off: every use is inside one trial's own scratch; tables shared by a workgroup are
-// published by __syncthreads.)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// ---- group reductions on the DPP network (no LDS round trips) ---------------------------------
-// A butterfly inside rows of 16 lanes (quad_perm, row_half_mirror, row_mirror) and, for G = 64,
-// four v_readlane across the rows.  Every lane of a group ends with the same bits.
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ double dpp_f64(double v) {
-  // Full row mask and bound_ctrl: a lane without a source reads 0 and the compiler needs no zero-initialisation of the
-  // destination.  Under the permutations inside a row every lane has a source.  The row_bcast steps once ran with a
-  // partial row mask (0xA, 0xC) so that the rows they do not feed kept their values, which took an initialised
-  // destination (two v_mov_b32 v, 0 per step).  Nothing needs that: the reductions hand out lane 63 alone, whose tree
-  // (r3 + r2) + (r1 + r0) reads lane 47 in the first step and lane 31 -- row 1, fed by the first step -- in the second.
-  // With the full mask rows 0 (first step) and 0 - 1 (second) add a 0 to values that nobody reads.  ROW_MASK stays a
-  // parameter for a caller that does read the other rows.
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffLL), CTRL, ROW_MASK, 0xf, ROW_MASK == 0xf);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, ROW_MASK == 0xf);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double nanmax(double a, double b) { return (b > a || b != b) ? b : a; }  // NaN wins
-
-// Across the four rows of a wavefront: row_bcast15 adds the total of row 0 / 2 into row 1 / 3,
-// row_bcast31 adds lane 31 (rows 0+1) into rows 2 and 3, lane 63 then holds (r2 + r3) + (r0 + r1) and
-// is handed to every lane through an SGPR pair (6 + 2 instructions instead of 8 readlanes + 7).  Lane 63 is the only
-// lane anybody reads: what the two steps leave in rows 0 - 2 is not a sum of anything (see dpp_f64).
-template <int G>
-__device__ __forceinline__ double gsum(double v) {
-  v += dpp_f64<0xB1>(v);                 // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);                 // quad_perm [2,3,0,1]
-  if (G >= 8) v += dpp_f64<0x141>(v);    // row_half_mirror
-  if (G >= 16) v += dpp_f64<0x140>(v);   // row_mirror
-  if (G == 64) {
-    v += dpp_f64<0x142>(v);              // row_bcast15: lane 15 of row 0 / 1 / 2 -> rows 1 / 2 / 3 (row 0: + 0)
-    v += dpp_f64<0x143>(v);              // row_bcast31: lane 31 -> rows 2, 3 (rows 0, 1: + 0)
-    v = readlane_f64(v, 63);
-  }
-  return v;
-}
-// Trace of a d x d matrix held one element per lane (lane = i d + j): the bits of gsum<G>(diag ? x : 0.0), `diag` = this
-// lane is (i, i).  At G = 64 (d = 8) the diagonal sits in lanes 9 i, two per row at positions 2 r and 2 r + 9 of row r,
-// in different halves of the row: in gsum's butterfly the first three steps add + 0.0 to each of them three times and
-// the two of a row first meet in row_mirror, where lane 15 forms x(2 r + 9) + x(2 r).  Here one + 0.0 stands for the
-// three (x + 0.0 is x except that it turns -0.0 into +0.0, and it is idempotent: without it a diagonal of nothing but
-// -0.0 would give -0.0 where gsum gives +0.0), row_shr:9 forms the same sum, same operand order, in lane 2 r + 9 of
-// each row, and as those lanes are not the lane 15 that row_bcast reads, the three sums across the rows go through
-// SGPR pairs: (s3 + s2) in lane 63, (s1 + s0) in lane 27, then their sum in lane 63 -- gsum's tree.  17 instructions
-// as compiled for the 28 of gsum<64> with the select in front of it (profiles/chain_diet_isa.txt).
-template <int G>
-__device__ __forceinline__ double gtrace(bool diag, double x) {
-  double v = diag ? x : 0.0;
-  if (G != 64) return gsum<G>(v);
-  v += 0.0;
-  v += dpp_f64<0x119>(v);                              // row_shr:9, lanes 0 - 8 of a row read 0: s_r in lane 18 r + 9
-  const double hi = v + readlane_f64(v, 45);           // lane 63: s3 + s2
-  const double lo = v + readlane_f64(v, 9);            // lane 27: s1 + s0
-  return readlane_f64(hi + readlane_f64(lo, 27), 63);  // lane 63: (s3 + s2) + (s1 + s0)
-}
-// "Does `pred` hold in any lane of this lane's group": one ballot and a mask (the whole wave at G = 64).  Executed by
-// every lane of the wavefront.
-template <int G>
-__device__ __forceinline__ bool group_any(bool pred) {
-  const unsigned long long votes = __builtin_amdgcn_ballot_w64(pred);
-  if (G == 64) return votes != 0ull;
-  const int lane = threadIdx.x & 63;
-  return (votes & (((1ull << (G & 63)) - 1ull) << (lane / G * G))) != 0ull;
-}
-// v_max_f64 as it stands: of a NaN and a number it returns the number.  (fmax() in C++ makes the compiler put a
-// canonicalising v_max_f64 v, v, v in front of the operand that comes out of a DPP move -- one extra instruction per
-// level of the butterfly below: 49 instead of 42 for gmax<64>, against 63 for the compare-and-select form.)
-__device__ __forceinline__ double max_f64(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// Maximum of non-negative values (every caller passes fabs(.)); a NaN anywhere wins: the butterfly itself passes over
-// NaNs, one ballot finds them.  The rows a row_bcast step does not feed take the maximum with 0: neutral for such inputs,
-// and none of them is on the way to lane 63.
-template <int G>
-__device__ __forceinline__ double gmax(double v) {
-  const bool nan = group_any<G>(v != v);
-  v = max_f64(v, dpp_f64<0xB1>(v));
-  v = max_f64(v, dpp_f64<0x4E>(v));
-  if (G >= 8) v = max_f64(v, dpp_f64<0x141>(v));
-  if (G >= 16) v = max_f64(v, dpp_f64<0x140>(v));
-  if (G == 64) {
-    v = max_f64(v, dpp_f64<0x142>(v));
-    v = max_f64(v, dpp_f64<0x143>(v));
-    v = readlane_f64(v, 63);
-  }
-  return nan ? __builtin_nan("") : v;
-}
-
-// log(x) and 1/x for the likelihood terms.  The OCML log is correctly rounded through ~85 FP64
-// instructions of double-double arithmetic; the NLL needs neither that nor the special cases beyond
-// "x <= 0 or NaN gives NaN / -inf", and a lone wave pays for every instruction.  x = m 2^e with
-// m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1), log m = 2 s (1 + s^2/3 + s^4/5 + ...): with
-// s^2 <= 0.0295 ten terms reach 2^-55; error ~1.5 ulp.  About 30 instructions.
-__device__ __forceinline__ double recip_nr(double x) {  // 1/x to ~1 ulp: hardware seed + two Newton steps
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(r, fma(-x, r, 1.0), r);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-__device__ __forceinline__ bool log_is_regular(double x) { return x > 0.0 && x < 1.7e308; }  // fast_log's main branch
-__device__ __forceinline__ double fast_log(double x) {
-  if (!(x > 0.0) || !(x < 1.7e308)) return x == 0.0 ? -__builtin_huge_val() : (x > 0.0 ? x : __builtin_nan(""));
-  double m = __builtin_amdgcn_frexp_mant(x);  // [0.5, 1)
-  int e = __builtin_amdgcn_frexp_exp(x);
-  const bool low = m < 0.70710678118654752440;
-  m = low ? m + m : m;
-  e = low ? e - 1 : e;
-  const double num = m - 1.0, den = m + 1.0;
-  const double r = recip_nr(den);
-  double sq = num * r;
-  sq = fma(r, fma(-sq, den, num), sq);  // s = num / den, correctly rounded up to the last bit
-  const double z = sq * sq;
-  // P(z) = 1/3 + z/5 + ... + z^9/21, Estrin's scheme: pairs, then powers z^2, z^4, z^8 (dependency depth 5
-  // instead of the 10 of Horner's rule)
-  const double z2 = z * z, z4 = z2 * z2, z8 = z4 * z4;
-  const double q0 = fma(z, 1.0 / 5.0, 1.0 / 3.0), q1 = fma(z, 1.0 / 9.0, 1.0 / 7.0);
-  const double q2 = fma(z, 1.0 / 13.0, 1.0 / 11.0), q3 = fma(z, 1.0 / 17.0, 1.0 / 15.0);
-  const double q4 = fma(z, 1.0 / 21.0, 1.0 / 19.0);
-  const double r0 = fma(z2, q1, q0), r1 = fma(z2, q3, q2);
-  const double pl = fma(z8, q4, fma(z4, r1, r0));
-  const double lm = fma(sq + sq, pl * z, sq + sq);  // 2 s (1 + z P(z))
-  const double ed = (double)e;
-  return fma(ed, 6.93147180369123816490e-01, fma(ed, 1.90821492927058770002e-10, lm));  // e ln2 (hi + lo) + log m
-}
-
 constexpr bool kLiftSingleNegative = true;  // a7 short cut of Small::lift_single_negative (n = 3)
-
-// 1/sqrt(x) for normal-range positive x: hardware seed (v_rsq_f64) plus two Newton steps -- ~8
-// dependent FP64 instructions instead of the ~25 of a correctly rounded sqrt-then-divide,
-// accurate to ~1 ulp, which is all a Jacobi rotation / Cholesky pivot needs.
-__device__ __forceinline__ double fast_rsqrt(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  double e = fma(-x * y, y, 1.0);
-  y = fma(y * e, fma(e, 0.375, 0.5), y);
-  e = fma(-x * y, y, 1.0);
-  return fma(y * e, 0.5, y);
-}
-
-// sum_m base[m * stride + lane_off] * lds_vec[m], m < n, operand streamed from global memory (L2):
-// the loads of a block of UNR rows are issued back to back before any is consumed (the
-// sched_group_barriers pin that order; hipcc otherwise interleaves load / wait / FMA pairs), and
-// four accumulators keep the FP64 FMAs from forming a single dependency chain.
-template <int UNR>
-__device__ __forceinline__ void dot_block(const double* __restrict__ base, size_t stride, unsigned lane_off,
-                                          const double* lds_vec, int m, double (&acc)[4]) {
-  double av[UNR];
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) av[u] = base[(size_t)(m + u) * stride + lane_off];
-#pragma unroll
-  for (int u = 0; u < UNR; ++u) acc[u & 3] = fma(av[u], lds_vec[m + u], acc[u & 3]);
-  __builtin_amdgcn_sched_group_barrier(0x020, UNR, 0);
-#pragma unroll
-  for (int u = 0; u < UNR; u += 4) {
-    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-  }
-}
-template <int UNR>
-__device__ __forceinline__ double dot_global(const double* __restrict__ base, size_t stride, unsigned lane_off,
-                                             const double* lds_vec, int n) {
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  int m = 0;
-  for (; m + UNR <= n; m += UNR) dot_block<UNR>(base, stride, lane_off, lds_vec, m, acc);
-  if (UNR > 8 && m + 8 <= n) {
-    dot_block<8>(base, stride, lane_off, lds_vec, m, acc);
-    m += 8;
-  }
-  if (UNR > 4 && m + 4 <= n) {
-    dot_block<4>(base, stride, lane_off, lds_vec, m, acc);
-    m += 4;
-  }
-  for (; m < n; ++m) acc[0] = fma(base[(size_t)m * stride + lane_off], lds_vec[m], acc[0]);
-  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-
-// Unitary 2x2 rotation J = [[c, w], [-conj(w), c]] that (nearly) annihilates a_pq of
-// [[app, apq], [conj(apq), aqq]]: with delta = (aqq - app)/2 and
-// u = t/|apq| = sign(delta) / (|delta| + sqrt(delta^2 + |apq|^2)):  c = 1/sqrt(1 + u^2 |apq|^2),
-// w = s e^{i phi} = c u apq.  Only c has to be accurate (it makes J unitary for whatever u is
-// used); u comes from hardware seeds with one Newton step each (~1e-13): the rotated a_pq is
-// kept as computed instead of being set to zero, so an inexact angle costs convergence speed
-// (nothing measurable), never accuracy.
-__device__ __forceinline__ void rotation(double app, double aqq, cd apq, double& cs, cd& w) {
-  const double ab2 = apq.re * apq.re + apq.im * apq.im;
-  cs = 1.0;
-  w = cd{0.0, 0.0};
-  if (ab2 > 1e-300) {
-    const double dl = 0.5 * (aqq - app);
-    const double x = fma(dl, dl, ab2);
-    double y = __builtin_amdgcn_rsq(x);
-    y = fma(y * fma(-x * y, y, 1.0), 0.5, y);
-    const double den = fabs(dl) + x * y;  // |delta| + sqrt(delta^2 + |apq|^2)
-    double z = __builtin_amdgcn_rcp(den);
-    z = fma(z, fma(-den, z, 1.0), z);
-    const double u = copysign(z, dl);
-    cs = fast_rsqrt(fma(u * u, ab2, 1.0));
-    const double cu = cs * u;
-    w = cd{cu * apq.re, cu * apq.im};
-  }
-}
-
-
-// A POVM that is the n-fold tensor product of a one-qubit table T[R1][4] (every built-in POVM and
-// every array with a last axis of 4 -- measurements.py:88-93): the M x D contractions A' b, A'^T r and
-// A'^+ f factor into n small ones, qubit by qubit (R1^q 4^(n-q) outputs of 4 or R1 terms each), which
-// cuts the FP64 work per evaluation ~8x at n = 3 and removes every global load from the inner loops.
-// Intermediate arrays live in the trial's LDS scratch in "R-order": index [r_1 .. r_q][k_(q+1) .. k_n]
-// with r = s * K1 + o the row of T.  The (base, selector) of every output is tabulated on the host.
-struct ProductView {
-  const double* T;      // [R1][4]
-  const double* P1T;    // [R1][4]  P1T[r][k] = pinv(T)[k][r]  (used when the shot weights are uniform)
-  const double* wrowR;  // [M]  N_s / sum(N) of each row, R-order
-  const int* rmap;      // [M]  R-order index -> row m of the (S, K) layout
-  const int* rinv;      // [M]  the inverse map: row m of the (S, K) layout -> R-order index
-  const int* fwd;       // stage tables of the forward pass, stage 1 .. n concatenated: base | sel << 16
-  const int* bwd;       // stage tables of the backward pass, stage n .. 1 concatenated
-  int R1;
-  int uniform;          // all N_s equal
-  double wuni;          // the common weight
-  int enabled;
-  // A six-row table whose rows 2a, 2a+1 are zero outside columns 0 and a+1 (the six-projector POVMs 'proj-set' and
-  // 'proj', and their pseudo-inverses) is "paired": half of every stage's terms are fma(0, x, acc).  The n <= 3
-  // stages then skip them (same terms, same order: same bits) and take the coefficients from here instead of LDS.
-  int pairedT, pairedP;  // T / pinv(T)^T has that shape and QT_OPT_PAIRED_STAGES is on (n <= 3 only)
-  double cT[12], cP[12];  // (u_r, v_r) = (tab[r][0], tab[r][r / 2 + 1]), r = 0 .. 5: the bits of T and P1T
-  const int* last;       // [M] stage-n entries of a paired T: in0 | axis << 8 | (4 r + a + 1) << 16
-};
-
-struct PovmView {
-  const double* Aw;    // [M][D]  shot-weighted A'
-  const double* AwT;   // [D][M]
-  const double* PinvT; // [M][D]  transpose of the left inverse of A'
-  int M;
-  ProductView pr;
-  double jtol2 = 1e-28;  // Jacobi stops when off-diagonal norm^2 <= jtol2 * Frobenius norm^2
-  // shots per setting as registered with qt_set_povm (the weights N_s / sum N inside A' come from these);
-  // every trial's own per-setting totals must be proportional to them (state.py:138-141, 194-197: the
-  // reference takes the weights from the trial's results) or the trial is flagged QT_TRIAL_SHOTS
-  const double* Ns = nullptr;  // [S]
-  int S = 0, K = 0;
-  double ns_tot = 0.0;
-  int extra = 0;  // extra doubles of per-trial LDS behind the scratch (k_mle_bfgs: line-search state + two-loop scalars)
-};
-
-// What the specialised MLE kernels (template parameter GENERIC = false, n <= 3) take instead of a PovmView.  They are
-// compiled for ONE launch-uniform shape, that of every built-in six-projector run: a product POVM with R1 = 6 rows
-// made of three two-outcome settings (so K = d outcomes per setting, M = 6^n <= 4 G rows), both one-qubit tables
-// paired, equal shots per setting, the shots check on.  Nothing else of the POVM is read, so nothing else is passed:
-// the PovmView is 0x1b8 bytes of kernel arguments, most of them dead on this path and all of them live in SGPRs.
-// `image` is built once by qt_set_povm_product, in device memory: the workgroup's LDS table block in its final layout
-// (Small::image_chunks(M) 16-byte chunks: the stage-n entries `last`[M], padded to a multiple of four, then T [6][4]
-// and pinv(T)^T [6][4]) followed by rinv[M].
-struct SpecArgs {
-  const void* image;
-  const double* Ns;  // [S] registered shots per setting
-  double ns_tot, wuni, jtol2;
-  int M, extra;
-  double cT[12], cP[12];  // ProductView::cT / cP
-};
-template <bool GENERIC>
-struct MleArgs {
-  using type = PovmView;
-};
-template <>
-struct MleArgs<false> {
-  using type = SpecArgs;
-};
-
-// t_s / total == N_s / ns_tot, compared as cross products of integer-valued doubles (exact below 2^53; a few
-// ulp of slack beyond that -- one stray count out of N_s < 1e14 is still seen)
-__device__ __forceinline__ bool shots_match(double t_s, double total, double n_s, double ns_tot) {
-  const double a = t_s * ns_tot, b = n_s * total;
-  return fabs(a - b) <= 2e-15 * fabs(b);
-}
-
-// Where an estimator leaves a trial's result: the density matrix and / or -- the body of the bootstrap loop,
-// interval.py:600-609, `dist[i] = dst(point_estimate(...), state)` -- its Hilbert-Schmidt distance (geometry.py:16-20) to
-// `centre`.  With `dist` set and `rho` null a resample costs 8 bytes of HBM writes instead of 16 d^2 and no second pass.
-// A table of G centres serves the nested bootstrap of the coverage study (metrics.py:125-144), where every trial of the
-// study has its own point estimate: the batch is then [resample][trial] and trial b is measured against centre (g0 + b) % G
-// (g0: the group of the launch's first trial, for a launch that starts inside the batch).  G == 1 is the single centre and
-// takes no modulo.
-// Centre (g0 + b) % G of a table of G matrices of dd doubles each.  Defined for every b >= 0.
-__device__ __forceinline__ const double* centre_of(const double* centres, int G, int g0, int b, int dd) {
-  return G > 1 ? centres + (size_t)((unsigned)(g0 + b) % (unsigned)G) * dd : centres;
-}
-
-struct EstOut {
-  double* rho;           // [B][d][d][2], or nullptr when only the distance is wanted
-  const double* centre;  // [G][d][d][2], read when dist != nullptr
-  double* dist;          // [B], or nullptr
-  int G = 1;             // centres in the table (launch-uniform)
-  int g0 = 0;            // group of trial 0 of this launch, < G
-  // The centre of trial b, dd doubles each.  Reduced for every b >= 0, so the lane groups that pad the last workgroup
-  // (b >= B, stores masked) read inside the table too.
-  __device__ __forceinline__ const double* centre_of(int b, int dd) const {
-    return qt::centre_of(centre, G, g0, b, dd);
-  }
-};
 
 template <int NQ>
 struct Small {
@@ -2412,653 +2054,6 @@ __global__ void __launch_bounds__(256) k_nll_batch(PovmView pv, const double* __
   if (live) {
     if (c.l == 0) f[b] = fv;
     if (grad) grad[(size_t)b * S::D + c.l] = gl;
-  }
-}
-
-// The scalars of one trial's MLE result (each output is optional), written by the trial's first lane.
-__device__ __forceinline__ void store_trial(int b, int nit, int nfev, double fun, int status,
-                                            int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                            double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
-  if (nit_out) nit_out[b] = nit;
-  if (nfev_out) nfev_out[b] = nfev;
-  if (fun_out) fun_out[b] = fun;
-  if (status_out) status_out[b] = status;
-}
-
-// a10, part 1: starting point (state.py:205-212), Cholesky parametrisation and the first
-// (value, gradient) evaluation.  Trials whose gradient already meets gtol -- every full-rank
-// high-shot trial, where BFGS exits at iteration 0 -- are finished here; the
-// rest hand x0, g0, f0 to k_mle_bfgs.  Keeping the D x D inverse Hessian out of this kernel
-// keeps its register footprint small.
-// Held to four wavefronts per SIMD (128 VGPRs): the saturated batches run four workgroups per CU, and one
-// register more -- the EstOut pointers of round 3 made it 129 -- takes a workgroup off every CU (measured: 0.372 -> 0.416 ms
-// per 65 536 trials).
-template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_mle_start(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int init,
-                                                   int max_iter, double gtol, EstOut rho,
-                                                   int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                                   double* __restrict__ fun_out, int32_t* __restrict__ status_out,
-                                                   double* __restrict__ ws_x, double* __restrict__ ws_g,
-                                                   double* __restrict__ ws_f, int32_t* __restrict__ ws_active) {
-  using S = Small<NQ>;
-  constexpr int D = S::D, G = S::G, d = S::d;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::template CtxOf<GENERIC>::type c;
-  bool live;
-  const int b = S::trial_index(B, &live);
-  const int bb = live ? b : B - 1;
-  typename S::Prefetch pf;
-  S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
-  bool shots_ok;
-  if constexpr (GENERIC) {
-    S::make_ctx(c, smem, pv);
-    shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
-  } else {
-    S::make_ctx(c, smem, pv, pf);
-    shots_ok = S::load_freq(c, pf);
-  }
-  int ok;
-  double xk;
-  typename S::StartPoint sp;
-  if (init == 0) {
-    double bl;
-    const cd lin = S::lin_invert(c, bl);
-    sp.rho = S::make_feasible(c, lin, &xk, &ok, &sp.lscale);  // physical 'lin' estimate, Cholesky-parametrised
-  } else {
-    sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
-    sp.lscale = 1.0;
-    xk = S::cholesky_param(c, sp.rho, ok);
-  }
-  double fk, gk;
-  cd rho_l;  // L L^dagger / Tr at x_k: what the trial returns if BFGS does not move
-  [[maybe_unused]] typename S::DeferredValue dv;
-  if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
-  else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
-  const double gnorm = gmax<G>(fabs(gk));
-  const bool iterate = shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
-  if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
-  const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));
-  S::emit(c, rho, b, live, rho_l);
-  if (live) {
-    if (iterate) {  // the hand-off is written only for trials that go on to k_mle_bfgs
-      ws_x[(size_t)b * D + c.l] = xk;
-      ws_g[(size_t)b * D + c.l] = gk;
-    }
-    if (c.l == 0) {
-      if (iterate) ws_f[b] = fk;
-      ws_active[b] = iterate ? 1 : 0;
-      store_trial(b, 0, ok ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
-    }
-  }
-}
-
-// a10, part 2: the BFGS iterations (scipy _minimize_bfgs) of the trials whose first gradient did not
-// meet gtol.  One (value, gradient) evaluation per loop pass; the line search is the state machine of
-// qt_linesearch.h, whose scalar rules (bfgs_*) this loop shares with the n = 4, 5 kernel (qt_large.h).  `mine` marks
-// the groups that iterate; the others idle through the evaluations on finite dummy values.
-// ONE loop for both forms of the inverse Hessian; `Dir` says how p = -H g is formed behind an accepted step:
-//   double next(c, np, sk, yk, gk, rhok)  this lane's element of the next direction; (sk, yk, rhok) is pair `np`
-//   kLsInLds                              the caller's LineSearch lives in LDS, shared by the lanes of the group: the
-//                                         loop orders its writes before the next pass's reads
-template <int NQ, class Dir, class C>
-__device__ __forceinline__ void bfgs_loop(const C& c, Dir& dir, LineSearch& ls, bool mine, double xk, double gk,
-                                          double fk, int b, int max_iter, double gtol, EstOut rho,
-                                          int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                          double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
-  using S = Small<NQ>;
-  constexpr int G = S::G;
-  bool active = mine;
-  double old_old = fk + sqrt(gsum<G>(gk * gk)) / 2.0;
-  double pk = -gk, stp = 0.0;  // H0 = I
-  int kiter = 0, nfev = 1, status = TRIAL_OK;
-  ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
-  if constexpr (Dir::kLsInLds) wave_sync();
-  const int eval_cap = bfgs_eval_cap(max_iter);
-
-#ifdef QT_PHASE_TIMING  // slots 21 / 22: clocks in this loop / inside its nll_grad calls; 23 / 24: iterations, evaluations
-  long long t_nll = 0;
-  const long long t_loop0 = (long long)__builtin_readcyclecounter();
-#endif
-  while (__any(active)) {  // per wave: the waves of a workgroup do not synchronise here
-    double ft, gt;
-#ifdef QT_PHASE_TIMING
-    const long long t_e0 = (long long)__builtin_readcyclecounter();
-#endif
-    S::nll_grad(c, xk + stp * pk, ft, gt);  // executed by the whole wave; finished trials idle through it
-#ifdef QT_PHASE_TIMING
-    t_nll += (long long)__builtin_readcyclecounter() - t_e0;
-#endif
-    if (active && ++nfev > eval_cap) {
-      status = TRIAL_LINESEARCH;
-      active = false;
-    }
-    if (active) {
-      const double dphi = gsum<G>(gt * pk);
-      double next = stp;
-      const int r = ls.advance(stp, ft, dphi, &next);
-      if (r == LS_EVAL) {
-        stp = next;
-      } else if (r == LS_FAIL) {
-        status = TRIAL_LINESEARCH;
-        active = false;
-      } else {
-        // step accepted: x += s, y = g_new - g
-        const double sk = stp * pk;
-        const double pnorm2 = gsum<G>(pk * pk);
-        xk = xk + sk;
-        const double yk = gt - gk;
-        gk = gt;
-        old_old = fk;
-        fk = ft;
-        ++kiter;
-        const double gnorm = gmax<G>(fabs(gk));
-        if (bfgs_step_exit(gnorm, gtol, stp, pnorm2, fk, kiter, max_iter, &status)) {
-          active = false;
-        } else {
-          pk = dir.next(c, kiter - 1, sk, yk, gk, bfgs_rho(gsum<G>(yk * sk)));
-          ls.start(fk, old_old, gsum<G>(gk * pk), &stp);
-        }
-      }
-    }
-    if constexpr (Dir::kLsInLds) wave_sync();
-  }
-#ifdef QT_PHASE_TIMING
-  QT_STAMP_VAL(21, (long long)__builtin_readcyclecounter() - t_loop0);
-  QT_STAMP_VAL(22, t_nll);
-  QT_STAMP_VAL(23, (long long)kiter);
-  QT_STAMP_VAL(24, (long long)nfev);
-#endif
-  status = bfgs_final_status(status, kiter, max_iter, gmax<G>(fabs(gk)), fk, gmax<G>(fabs(xk)));
-  // ---- result: L L^dagger / Tr  (state.py:214-215)
-  double tr;
-  const cd m = S::build_llh(c, xk, tr);
-  S::emit(c, rho, b, mine, cd{m.re / tr, m.im / tr});
-  if (mine && c.l == 0) store_trial(b, kiter, nfev, fk, status, nit_out, nfev_out, fun_out, status_out);
-}
-
-// The inverse Hessian itself, one row per lane in registers (n = 1, 2: 4 / 16 doubles): the rank-two update with the
-// new pair, then the product with the gradient.
-template <int NQ>
-struct DenseH {
-  static constexpr bool kLsInLds = false;
-  static constexpr int D = Small<NQ>::D, G = Small<NQ>::G;
-  double H[D];
-  template <class C>
-  __device__ __forceinline__ explicit DenseH(const C& c) {
-#pragma unroll
-    for (int k = 0; k < D; ++k) H[k] = (k == c.l) ? 1.0 : 0.0;
-  }
-  template <class C>
-  __device__ __forceinline__ double next(const C& c, int, double sk, double yk, double gk, double rhok) {
-    double* vec = c.vec();
-    // H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T, expanded with u = H y
-    vec[c.l] = yk;
-    wave_sync();
-    // four partial sums: a lone wave pays ~16 ns per DEPENDENT FP64 instruction under load
-    // (profiles/round1_v14_ubench_valu_f64.txt); a 64-term chain would be 1 us of latency
-    double uu[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < D; ++k) uu[k & 3] = fma(H[k], vec[k], uu[k & 3]);
-    double u = (uu[0] + uu[1]) + (uu[2] + uu[3]);
-    const double yhy = gsum<G>(yk * u);
-    wave_sync();
-    double* ubuf = reinterpret_cast<double*>(c.A());  // 2 D doubles: u | s
-    ubuf[c.l] = u;
-    ubuf[D + c.l] = sk;
-    wave_sync();
-    const double cc = rhok * rhok * yhy + rhok;
-    // (regrouped as H_lk += a_l s_k + b_l u_k with (u_k, s_k) read as one 16-byte pair: two FMAs per element
-    //  instead of five operations, and measured 6 % SLOWER per iteration -- scripts/bfgs_phase_timing.py)
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-      H[k] += -rhok * (u * ubuf[D + k] + sk * ubuf[k]) + cc * sk * ubuf[D + k];
-    wave_sync();
-    vec[c.l] = gk;
-    wave_sync();
-    double hh[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < D; ++k) hh[k & 3] = fma(H[k], vec[k], hh[k & 3]);
-    const double hp = (hh[0] + hh[1]) + (hh[2] + hh[3]);
-    wave_sync();
-    return -hp;
-  }
-};
-
-// WITHOUT the inverse Hessian in registers, for batches that fill the chip (k_mle_bfgs): with H_0 = I the matrix
-// scipy updates, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T, is exactly the product form the two-loop
-// recursion evaluates, so p = -H_k g is computed from the (s_i, y_i) pairs of the accepted steps (as at n = 4, 5,
-// qt_large.h, under the same rules of qt_linesearch.h).  Lane l only ever touches element l of each pair: private,
-// coalesced streams in a global workspace `pairs` [B][max_iter][2][D] that stay in L2; rho_i, alpha_i and -- across
-// every evaluation -- the line-search state live in the trial's LDS (`pv.extra` doubles).  Registers: ~150 instead
-// of 256 + 91 AGPRs, i.e. three waves per SIMD instead of one, and 2 k reductions + 4 k FMAs per iteration instead
-// of two 64-term products and a 64-entry rank-two update.  Same iterates as the dense form to rounding
-// (tests/test_gpu_state.py runs the reference's 70 golden trials through both).
-// LP > 0 (k_mle_fused: one workgroup per CU, LDS to spare): the first LP pairs stay in the trial's LDS and only later
-// ones go to the global workspace -- a lone wave would otherwise wait out an L2 round trip per block of pairs.
-template <int NQ, int LP>
-struct TwoLoop {
-  static constexpr bool kLsInLds = true;
-  static constexpr int D = Small<NQ>::D, G = Small<NQ>::G;
-  double* my;      // s_i[l] at my[2 i D], y_i[l] at my[(2 i + 1) D]
-  double* prho;    // [max_iter]
-  double* palpha;  // [max_iter]
-  double* lp;      // [LP][2][D]: s_i[l] at lp[2 i D], y_i[l] at lp[(2 i + 1) D]
-  template <class C>
-  __device__ __forceinline__ TwoLoop(const C& c, double* __restrict__ pairs, int b, int max_iter)
-      : my(pairs + (size_t)b * max_iter * 2 * D + c.l),
-        prho(c.extra() + LineSearch::SLOTS),
-        palpha(prho + max_iter),
-        lp(palpha + max_iter + c.l) {}
-  template <class C>
-  __device__ __forceinline__ double next(const C& c, int np, double sk, double yk, double gk, double rhok) {
-    if (np < LP) {
-      lp[(2 * np) * D] = sk;
-      lp[(2 * np + 1) * D] = yk;
-    } else {
-      my[(size_t)(2 * np) * D] = sk;
-      my[(size_t)(2 * np + 1) * D] = yk;
-    }
-    if (c.l == 0) prho[np] = rhok;
-    wave_sync();
-    double q = gk;
-    for (int i = np; i >= 0; --i) {
-      double si = sk, yi = yk;
-      if (i != np) {
-        if (i < LP) {
-          si = lp[(2 * i) * D];
-          yi = lp[(2 * i + 1) * D];
-        } else {
-          si = my[(size_t)(2 * i) * D];
-          yi = my[(size_t)(2 * i + 1) * D];
-        }
-      }
-      const double a = prho[i] * gsum<G>(si * q);
-      if (c.l == 0) palpha[i] = a;
-      q = fma(-a, yi, q);
-    }
-    wave_sync();
-    for (int i = 0; i <= np; ++i) {
-      double si = sk, yi = yk;
-      if (i != np) {
-        if (i < LP) {
-          si = lp[(2 * i) * D];
-          yi = lp[(2 * i + 1) * D];
-        } else {
-          si = my[(size_t)(2 * i) * D];
-          yi = my[(size_t)(2 * i + 1) * D];
-        }
-      }
-      const double bb = prho[i] * gsum<G>(yi * q);
-      q = fma(si, palpha[i] - bb, q);
-    }
-    return -q;
-  }
-};
-
-template <int NQ, class C>
-__device__ __forceinline__ void bfgs_iterate(const C& c, bool mine, double xk, double gk,
-                                             double fk, int b, int max_iter, double gtol, EstOut rho,
-                                             int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                             double* __restrict__ fun_out, int32_t* __restrict__ status_out) {
-  DenseH<NQ> dir(c);
-  LineSearch ls;
-  bfgs_loop<NQ>(c, dir, ls, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
-}
-
-template <int NQ, int LP = 0, class C>
-__device__ __forceinline__ void bfgs_iterate_2l(const C& c, bool mine, double xk, double gk,
-                                                double fk, int b, int max_iter, double gtol, EstOut rho,
-                                                int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                                double* __restrict__ fun_out, int32_t* __restrict__ status_out,
-                                                double* __restrict__ pairs) {
-  TwoLoop<NQ, LP> dir(c, pairs, b, max_iter);
-  // The line-search state lives IN LDS (every lane of the group reads and writes the same words with the same values):
-  // as a register-resident struct its ~35 doubles plus the temporaries of dcstep made the allocation 240 VGPRs.
-  static_assert(sizeof(LineSearch) <= LineSearch::SLOTS * sizeof(double), "LDS slot of the line-search state");
-  LineSearch& ls = *reinterpret_cast<LineSearch*>(c.extra());
-  bfgs_loop<NQ>(c, dir, ls, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
-}
-
-#ifndef QT_BFGS_WAVES
-#define QT_BFGS_WAVES 2  // waves per SIMD the BFGS kernel is compiled for; measured at B = 65 536 (15-iteration trials): 3 waves
-                         // (<= 168 VGPRs, 18 spilled) 5.29 ms, 2 waves (205 VGPRs, no scratch) 5.39 ms -- instruction-bound either way
-#endif
-template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFGS_WAVES))) k_mle_bfgs(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
-                                                  double gtol, EstOut rho, int32_t* __restrict__ nit_out,
-                                                  int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
-                                                  int32_t* __restrict__ status_out, const double* __restrict__ ws_x,
-                                                  const double* __restrict__ ws_g, const double* __restrict__ ws_f,
-                                                  const int32_t* __restrict__ ws_active, double* __restrict__ pairs) {
-  using S = Small<NQ>;
-  constexpr int D = S::D;
-  bool live;
-  const int b = S::trial_index(B, &live);
-  const bool mine = live && ws_active[b] != 0;
-  if (!__syncthreads_or(mine)) return;  // nothing left to iterate in this workgroup
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  std::conditional_t<GENERIC, typename S::Ctx, typename S::template CtxSV<0>> c;  // (no lane tables: CtxSV)
-  const int bb = live ? b : B - 1;
-  if constexpr (GENERIC) {
-    S::make_ctx(c, smem, pv);
-    S::load_freq(c, counts + (size_t)bb * pv.M);
-  } else {
-    typename S::Prefetch pf;
-    S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
-    S::make_ctx(c, smem, pv, pf);
-    S::load_freq(c, pf);
-  }
-  // inactive trials of a live wave idle through the loop on dummy finite values
-  const double xk = mine ? ws_x[(size_t)b * D + c.l] : (c.l < S::d ? 1.0 : 0.0);
-  const double gk = mine ? ws_g[(size_t)b * D + c.l] : 0.0;
-  const double fk = mine ? ws_f[b] : 0.0;
-  // n = 3: two-loop form (the 64 x 64 inverse Hessian would cost 128 VGPRs per lane); n = 1, 2: H is 4 / 16 doubles
-  // per lane and stays in registers
-  if constexpr (NQ == 3)
-    bfgs_iterate_2l<NQ>(c, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
-  else
-    bfgs_iterate<NQ>(c, mine, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
-}
-
-constexpr int kFusedLdsPairs = 24;  // (s, y) pairs of k_mle_fused<3> kept in LDS: 24 KB per trial, 4 trials per workgroup
-// ... and of k_mle_fused_hw<3>, whose workgroup also holds a scratch per twin wavefront: 16 KB per trial.  (Where a pair
-// lives changes no bit of the iteration.)
-constexpr int kFusedHwLdsPairs = 16;
-
-// a10 in ONE launch, for batches small enough that its 256-VGPR footprint (two waves per SIMD) is no
-// handicap: start point, first evaluation and -- for the waves that still hold an open trial -- the BFGS
-// loop.  Saves the second launch (2.5-4 us when nothing iterates, ~10 % of a 1000-trial step).
-// HW (k_mle_fused_hw, n = 3, 'lin' start): launched with blocks of 256 x 2 threads.  threadIdx.y = 0 are the four
-// trial wavefronts, exactly as without HW; threadIdx.y = 1 are their twins (Small::HelperLink), wavefront 4 + t on
-// the SIMD of wavefront t and with the same threadIdx.x, hence the same trial.  A twin runs the same prologue on the
-// same counts with a scratch of its own (make_ctx<.., TWIN>) and parts from the trial's wave behind lin_invert.
-template <int NQ, bool GENERIC, bool HW = false>
-__device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::type& pv, const int64_t* __restrict__ counts, int B, int init,
-                                               int max_iter, double gtol, EstOut rho,
-                                               int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                               double* __restrict__ fun_out, int32_t* __restrict__ status_out,
-                                               double* __restrict__ pairs) {
-  using S = Small<NQ>;
-  constexpr int D = S::D, G = S::G, d = S::d;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  // (one wavefront per SIMD: the specialised context keeps its lane tables decoded in registers)
-  using Ctx = std::conditional_t<GENERIC, typename S::Ctx, typename S::template CtxSV<2>>;
-  std::conditional_t<HW, typename S::template WithHelper<Ctx>, Ctx> c;
-  [[maybe_unused]] typename S::HelperLink link;
-  [[maybe_unused]] typename S::LateX late{false, 0.0, 0};
-  [[maybe_unused]] int twin = 0;               // HW: this wavefront is a twin (wave-uniform)
-  [[maybe_unused]] double* trial_sm = nullptr;  // HW: the scratch of the trial (a twin's own is c.sm)
-  if constexpr (HW) {
-    static_assert(NQ == 3, "one trial per wavefront");
-    static_assert(S::HelperLink::doubles() <= kFusedHwLdsPairs * 2 * D, "the hand-off lives in the LDS pair store");
-    int r1 = 6;  // the product POVM's one-qubit rows (the generic body is launched with HW only for a product POVM)
-    if constexpr (GENERIC) r1 = pv.pr.R1;
-    const int per_trial = S::trial_doubles(pv.M, r1);
-    trial_sm = smem + S::table_doubles(pv.M, r1) + (threadIdx.x >> 6) * (per_trial + pv.extra);
-    link.base = trial_sm + per_trial + LineSearch::SLOTS + 2 * max_iter;  // TwoLoop::lp
-    twin = __builtin_amdgcn_readfirstlane((int)threadIdx.y);
-    link.pending = 0;
-    if (!twin) link.reset();  // (in front of the workgroup barrier of make_ctx: the twin finds its words set up)
-    // The twin is the younger wave of its SIMD and loses the arbitration by age, and it carries the chain the launch
-    // waits for (a clipped trial's prologue, lift and evaluation); the older wave has thousands of clocks to spare in
-    // every class.  Once, for the whole kernel.  (Measured: profiles/mle_twin_wave_headline_ab.txt.)
-    if (twin) __builtin_amdgcn_s_setprio(1);
-    c.link = &link;
-    c.xtra = trial_sm + per_trial;
-    c.late = &late;
-  }
-  bool live;
-  const int b = S::trial_index(B, &live);
-  const int bb = live ? b : B - 1;
-  typename S::Prefetch pf;
-  S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
-  bool shots_ok;
-  if constexpr (GENERIC) {
-    S::template make_ctx<HW>(c, smem, pv, twin);
-    QT_STAMP(0);
-    shots_ok = S::load_freq(c, counts + (size_t)bb * pv.M, &pf);
-  } else {
-    S::template make_ctx<true, HW>(c, smem, pv, pf, twin);
-    QT_STAMP(0);
-    shots_ok = S::load_freq(c, pf);
-  }
-  QT_STAMP(1);
-  int ok;
-  double xk;
-  typename S::StartPoint sp;
-  [[maybe_unused]] cd lin;
-  if (init == 0) {
-    double bl;
-    lin = S::lin_invert(c, bl);
-    QT_STAMP(2);
-    // one wave per SIMD: the speculative inverse rides along in the sweep (cholesky_param<SPEC>); HW: the twin
-    // wavefront, which holds the same `lin`, speculates, through the whole lift, and the sweep here is the plain one
-    bool feasible = false;
-    if constexpr (HW) {
-      if (twin) {
-        // lifted, claimed and published: the matrix stays in these registers and this wave goes on as the trial
-        if (!S::twin_lift(c, link, lin, sp.rho)) {
-          S::HelperLink::publish(link.gone(), 1);
-          return;
-        }
-        sp.lscale = 1.0;
-        link.pending = 1;
-        feasible = true;
-      }
-    }
-    if (!feasible) sp.rho = S::template make_feasible<!HW>(c, lin, &xk, &ok, &sp.lscale);
-    if constexpr (HW) {
-      if (!twin && __builtin_amdgcn_readfirstlane(link.pending)) {
-        // the twin owns the trial from here: factorise its matrix for it and leave, writing no output
-        int r1 = 6;
-        if constexpr (GENERIC) r1 = pv.pr.R1;
-        double* twin_sm = smem + S::twin_offset(pv.M, r1, pv.extra) + (threadIdx.x >> 6) * S::trial_doubles(pv.M, r1);
-        S::sweep_for(c, link, sp.rho, reinterpret_cast<cd*>(twin_sm + S::oB));
-        S::HelperLink::publish(link.gone(), 1);
-        return;
-      }
-    }
-  } else {
-    sp.rho = cd{c.i == c.j ? 1.0 / d : 0.0, 0.0};
-    sp.lscale = 1.0;
-    xk = S::cholesky_param(c, sp.rho, ok);
-  }
-  QT_STAMP(8);
-  double fk, gk;
-  cd rho_l;
-  [[maybe_unused]] typename S::DeferredValue dv;
-  bool evaluate = true;
-  if constexpr (HW) {
-    if (__builtin_amdgcn_readfirstlane(link.pending)) {
-      // the front of the evaluation beside the helper's factorisation of sp.rho (its lift); x arrives where Tr is formed
-      if constexpr (GENERIC) S::template nll_grad<false, decltype(c), true>(c, 0.0, fk, gk, &rho_l, true, &sp);
-      else S::template nll_grad<true, decltype(c), true>(c, 0.0, fk, gk, &rho_l, true, &sp, &dv);
-      xk = late.x;
-      ok = late.ok;
-      // Nothing came, or the short cut left something non-positive behind (make_feasible): the serial path, as
-      // without a helper, and the evaluation again from the top.  (One trial per wave: both facts are wave-uniform.)
-      const bool got = __builtin_amdgcn_readfirstlane((int)late.got) != 0;
-      if (!got) xk = S::cholesky_param(c, sp.rho, ok);
-      ok = __builtin_amdgcn_readfirstlane(ok);
-      evaluate = !got || !ok;
-      if (!ok) {
-        sp.rho = S::psd_project(c, lin, 1e-15);
-        xk = S::cholesky_param(c, sp.rho, ok);
-      }
-    }
-  }
-  if (evaluate) {
-    if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
-    else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
-  }
-  const double gnorm = gmax<G>(fabs(gk));
-  QT_STAMP(9);
-  const bool iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
-  if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
-  S::emit(c, rho, b, live && !iterate, rho_l);  // (trials that iterate are written at the end of the loop)
-  const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));
-  if (live && !iterate && c.l == 0) store_trial(b, 0, ok ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
-  QT_STAMP(10);
-  if (!__any(iterate)) return;  // per wave
-  if (!iterate) {                // finite dummies for the groups of this wave that are already done
-    xk = (c.l < d) ? 1.0 : 0.0;
-    gk = 0.0;
-    fk = 0.0;
-  }
-  // n = 3: two-loop form, the first kFusedLdsPairs (s, y) pairs in LDS (the 64 x 64 inverse Hessian took 128 VGPRs per lane
-  // and ~460 AGPR moves per iteration); n = 1, 2: the 4 / 16-entry Hessian rows stay in registers
-  if constexpr (HW) link.await_gone();  // the hand-off region is the front of the LDS pair store
-  if constexpr (NQ == 3)
-    bfgs_iterate_2l<NQ, HW ? kFusedHwLdsPairs : kFusedLdsPairs>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out,
-                                              status_out, pairs);
-  else
-    bfgs_iterate<NQ>(c, iterate, xk, gk, fk, b, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out);
-}
-
-// Two entry points over the same body: the fully mixed start (`init = 'mixed'`: every trial iterates, ~10x the duration)
-// runs under its own kernel name, so that a profiler's per-kernel average of k_mle_fused is the average of the
-// 'lin'-start launches (bench.py's timed steps) and not a mixture with the iterating side measurements.
-template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) k_mle_fused(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
-                                                   double gtol, EstOut rho, int32_t* __restrict__ nit_out,
-                                                   int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
-                                                   int32_t* __restrict__ status_out, double* __restrict__ pairs) {
-  mle_fused_body<NQ, GENERIC>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
-}
-template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) k_mle_fused_mixed(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B,
-                                                         int max_iter, double gtol, EstOut rho,
-                                                         int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
-                                                         double* __restrict__ fun_out, int32_t* __restrict__ status_out,
-                                                         double* __restrict__ pairs) {
-  mle_fused_body<NQ, GENERIC>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
-}
-
-// The 'lin' start with a twin wavefront per trial (mle_fused_body<.., HW>): blocks of 256 x 2 threads, the grid of
-// k_mle_fused, its LDS layout with kFusedHwLdsPairs pairs and the twins' scratches behind it (Small::lds_bytes_twin).
-// Two waves per SIMD: the 256 registers of the body are what a wave can have.
-template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(512) k_mle_fused_hw(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
-                                                      double gtol, EstOut rho, int32_t* __restrict__ nit_out,
-                                                      int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
-                                                      int32_t* __restrict__ status_out, double* __restrict__ pairs) {
-  mle_fused_body<NQ, GENERIC, true>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
-}
-
-// Metropolis-Hastings chain on the Cholesky parameters (reference mhmc.py:80-119 with
-// `normalized_update`, interval.py:735-750): one chain per lane group.  Step t, from the increment delta_t of this lane's
-// parameter and the uniform u_t of the chain (mhmc_step, the one body of both kernels below):
-//   x' = (x + step * delta_t) / ||x + step * delta_t||,  alpha = exp(nll(x) - nll(x')),  accept iff u_t <= alpha.
-// x, f: the state and its NLL, replaced on acceptance.  Executed by every lane of the wavefront.
-template <int NQ, class C>
-__device__ __forceinline__ bool mhmc_step(const C& c, double step, double delta, double u, double& x, double& f) {
-  using S = Small<NQ>;
-  const double xp = fma(step, delta, x);
-  const double nrm = sqrt(gsum<S::G>(xp * xp));
-  const double xn = xp / nrm;
-  double fn, unused;
-  S::nll_grad(c, xn, fn, unused, nullptr, false);
-  const double alpha = exp(f - fn);
-  const bool acc = u <= alpha;  // false for a NaN alpha, like the reference's comparison
-  if (acc) {
-    x = xn;
-    f = fn;
-  }
-  return acc;
-}
-
-// The increments and the uniforms drawn on the host in the reference's order:
-// chain[c][t][:] = the state AFTER step t, accepted[c][t] = 0 / 1.
-template <int NQ>
-__global__ void __launch_bounds__(256) k_mhmc_state(PovmView pv, const int64_t* __restrict__ counts, int C,
-                                                    const double* __restrict__ x_init, const double* __restrict__ deltas,
-                                                    const double* __restrict__ uniforms, int T_steps, double step,
-                                                    double* __restrict__ chain, int32_t* __restrict__ accepted) {
-  using S = Small<NQ>;
-  constexpr int D = S::D;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::Ctx c;
-  S::make_ctx(c, smem, pv);
-  bool live;
-  const int b = S::trial_index(C, &live);
-  const int bb = live ? b : C - 1;
-  S::load_freq(c, counts + (size_t)bb * pv.M);
-  double x = x_init[(size_t)bb * D + c.l];
-  double f, unused;
-  S::nll_grad(c, x, f, unused, nullptr, false);
-  const double* dl = deltas + (size_t)bb * T_steps * D + c.l;
-  const double* un = uniforms + (size_t)bb * T_steps;
-  for (int t = 0; t < T_steps; ++t) {
-    const bool acc = mhmc_step<NQ>(c, step, dl[(size_t)t * D], un[t], x, f);
-    if (live) {
-      chain[((size_t)b * T_steps + t) * D + c.l] = x;
-      if (c.l == 0) accepted[(size_t)b * T_steps + t] = acc ? 1 : 0;
-    }
-  }
-}
-
-}  // namespace qt
-// qt_sampler.h is NOT included from here: its `#pragma clang fp contract(off)` holds to the end of the translation unit,
-// and this header is the first that qtomo.hip reaches -- every kernel in front of the sampler would lose its contractions
-// (and change its last bits).  The definition follows in qt_sampler.h, which qtomo.hip includes.
-namespace qt_sampler {
-__host__ __device__ inline double mhmc_draw(uint64_t seed, uint64_t chain, uint32_t step, int D, int l);
-}
-namespace qt {
-
-// The chain of the coverage study (metrics.get_CL_list_state_mhmc): the same steps on numbers the lanes draw themselves
-// (qt_sampler::mhmc_draw, global chain first_chain + b, global step = burn-in steps first, then the n_points * thinning
-// sampling steps), and of the chain only three numbers per trial leave the registers.  Post-burn step s is kept when
-// s % thinning == 0 (mhmc.py:80-84); on a kept step the lane forms its element of L L^dagger as k_chol_unparam does and
-// the group its Hilbert-Schmidt distance to centres[b] (hs_to_centre):
-//   hits[b] = #{ kept : thresholds[b] > distance }  (strict: a NaN never counts),  accepted[b] = accepted post-burn steps,
-//   dist[b][k] (nullable) = the distance of kept state k.
-// Lane 0 of a live group counts in registers and stores once; every lane runs the distance and the reductions.
-template <int NQ>
-__global__ void __launch_bounds__(256) k_mhmc_state_hits(PovmView pv, const int64_t* __restrict__ counts, int C,
-                                                         const double* __restrict__ centres, const double* __restrict__ x_init,
-                                                         const double* __restrict__ thresholds, uint64_t seed,
-                                                         uint64_t first_chain, uint32_t burn_steps, uint32_t n_points,
-                                                         uint32_t thinning, double step, int64_t* __restrict__ hits,
-                                                         int64_t* __restrict__ accepted, double* __restrict__ dist) {
-  using S = Small<NQ>;
-  constexpr int D = S::D;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  typename S::Ctx c;
-  S::make_ctx(c, smem, pv);
-  bool live;
-  const int b = S::trial_index(C, &live);
-  const int bb = live ? b : C - 1;
-  S::load_freq(c, counts + (size_t)bb * pv.M);
-  double x = x_init[(size_t)bb * D + c.l];
-  double f, unused;
-  S::nll_grad(c, x, f, unused, nullptr, false);
-  const uint64_t gc = first_chain + (uint64_t)bb;
-  const double* centre = centres + (size_t)bb * 2 * D;
-  const double thr = thresholds[bb];
-  const bool writer = live && c.l == 0;
-  uint32_t j = 0;
-  for (; j < burn_steps; ++j)
-    mhmc_step<NQ>(c, step, qt_sampler::mhmc_draw(seed, gc, j, D, c.l), qt_sampler::mhmc_draw(seed, gc, j, D, D), x, f);
-  int64_t n_hit = 0, n_acc = 0;
-  uint32_t kept = 0, to_keep = 0;  // to_keep: steps until the next kept one
-  const uint32_t total = n_points * thinning;  // (< 2^32 - 1 with the burn-in: checked by the entry)
-  for (uint32_t s = 0; s < total; ++s, ++j) {
-    n_acc += mhmc_step<NQ>(c, step, qt_sampler::mhmc_draw(seed, gc, j, D, c.l), qt_sampler::mhmc_draw(seed, gc, j, D, D), x, f);
-    if (to_keep == 0) {  // (launch-uniform)
-      double tr;
-      const cd m = S::build_llh(c, x, tr);
-      const double v = S::hs_to_centre(c, m, centre);
-      n_hit += thr > v;
-      if (dist && writer) dist[(size_t)b * n_points + kept] = v;
-      ++kept;
-      to_keep = thinning;
-    }
-    --to_keep;
-  }
-  if (writer) {
-    hits[b] = n_hit;
-    accepted[b] = n_acc;
   }
 }
 

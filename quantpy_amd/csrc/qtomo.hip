@@ -19,6 +19,8 @@
 #include "qt_large.h"
 #include "qt_lp.h"
 #include "qt_lp_large.h"
+#include "qt_mhmc_state.h"
+#include "qt_mle_small.h"
 #include "qt_ops.h"
 #include "qt_polytope.h"
 #include "qt_process.h"
@@ -691,7 +693,7 @@ struct MleArrays {
   }
 };
 
-// The split MLE pair: k_mle_start / k_mle_bfgs (qt_small.h) at n <= 3, k_mle_large_start / k_mle_large_bfgs (qt_large.h)
+// The split MLE pair: k_mle_start / k_mle_bfgs (qt_mle_small.h) at n <= 3, k_mle_large_start / k_mle_large_bfgs (qt_large.h)
 // at n = 4, 5.
 template <int NQ, bool GENERIC>
 auto mle_split_kernels() {

@@ -1,6 +1,6 @@
 """Iterating regime of the n = 3 MLE (init = 'mixed', ~16 BFGS iterations): clocks of the BFGS loop and of the
 (value, gradient) evaluations inside it, per wavefront, from the profile build
-(QTOMO_LIB=quantpy_amd/lib/libqtomo_prof.so; slots 21-24 of qt_small.h bfgs_loop)."""
+(QTOMO_LIB=quantpy_amd/lib/libqtomo_prof.so; slots 21-24 of qt_mle_small.h bfgs_loop)."""
 import ctypes
 import os
 import sys

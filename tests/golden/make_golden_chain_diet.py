@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/chain_diet_bits.npz: what the n = 3 entries that use the 64-lane reductions of qt_small.h (and
+"""Generate tests/golden/chain_diet_bits.npz: what the n = 3 entries that use the 64-lane reductions of qt_wave.h (and
 are not replayed by mle_diet_bits.npz) write for a fixed list of calls, to the bit.  It was recorded once, on an MI355X,
 with the library of the commit before the second "instruction diet" (cross-row reduction stages without row masks, trace
 reductions that start where two diagonal lanes meet, the Gauss-Jordan inverse unrolled in natural pivot order, the

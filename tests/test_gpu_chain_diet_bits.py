@@ -1,4 +1,4 @@
-"""GPU: the n = 3 entries that use the 64-lane reductions of qt_small.h and are not replayed by test_gpu_mle_diet_bits.py
+"""GPU: the n = 3 entries that use the 64-lane reductions of qt_wave.h and are not replayed by test_gpu_mle_diet_bits.py
 give the bits recorded in tests/golden/chain_diet_bits.npz.  The fixture was written once by
 tests/golden/make_golden_chain_diet.py with the library of the commit before the second "instruction diet" (cross-row
 reduction stages without row masks, trace reductions from the stage where two diagonal lanes meet, the Gauss-Jordan

@@ -1,4 +1,4 @@
-"""CPU: a NumPy MODEL of the 64-lane reductions of quantpy_amd/csrc/qt_small.h (gsum<64>, gmax<64>, gtrace<64>), stage by
+"""CPU: a NumPy MODEL of the 64-lane reductions of quantpy_amd/csrc/qt_wave.h (gsum<64>, gmax<64>, gtrace<64>), stage by
 stage -- it is not the device code, and it runs no kernel.  What it checks is the argument the kernels rest on: lane 63,
 the only lane the reductions hand out, holds the same bits
 
@@ -58,7 +58,7 @@ def vmax(a, b):
 
 
 def nanmax(a, b):
-    """nanmax of qt_small.h, (b > a || b != b) ? b : a -- a NaN in b wins"""
+    """nanmax of qt_wave.h, (b > a || b != b) ? b : a -- a NaN in b wins"""
     with np.errstate(invalid="ignore"):
         return np.where((b > a) | (b != b), b, a)
 
