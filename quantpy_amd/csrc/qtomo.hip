@@ -397,7 +397,10 @@ int launch(qt_handle_t* h, void (*kernel)(P...), dim3 grid, dim3 block, size_t l
   if (lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail(QT_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();  // reported here: the next hipGetLastError() check, on any handle, must not find it
+      return fail(QT_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+    }
   }
   kernel<<<grid, block, lds, h->stream>>>(args...);
   return 0;
@@ -707,6 +710,31 @@ auto mle_povm_arg(const qt_handle_t* h, const Plan& p) {
   else return h->spec_args(p.pv.extra);
 }
 
+// The largest max_iter whose BFGS launch of the split pair (povm_plan<NQ>(h, ., extra) in mle_batch_impl: 2 doubles per
+// iteration and trial behind the scratch, at n = 3 for each of a workgroup's TPB trials and behind the parked
+// line-search state) fits a CU's LDS with the handle's POVM -- beside the LDS that the compiled kernel holds by itself
+// (k_mle_bfgs<3, .>: 256 B), which the dynamic part cannot use.  `spec`: the specialised instantiation runs (n = 3).
+template <int NQ>
+int mle_iter_cap(const qt_handle_t* h, bool spec, int* cap) {
+  size_t base, per_iter;
+  const void* kernel;
+  if constexpr (NQ == 3) {
+    base = qt::Small<3>::lds_bytes(h->M, h->prod.enabled ? h->prod.R1 : 0, qt::LineSearch::SLOTS);
+    per_iter = (size_t)qt::Small<3>::TPB * 2 * sizeof(double);
+    kernel = spec ? reinterpret_cast<const void*>(mle_split_kernels<3, false>().second)
+                  : reinterpret_cast<const void*>(mle_split_kernels<3, true>().second);
+  } else {
+    base = qt::Large<NQ>::lds_bytes(h->M, h->prod.R1, 0);
+    per_iter = 2 * sizeof(double);
+    kernel = reinterpret_cast<const void*>(mle_split_kernels<NQ, true>().second);
+  }
+  hipFuncAttributes attr;
+  HIPCHK(hipFuncGetAttributes(&attr, kernel));
+  base += attr.sharedSizeBytes;
+  *cap = base > kLdsLimit ? 0 : (int)((kLdsLimit - base) / per_iter);
+  return 0;
+}
+
 // a8-a10 (+ a16 when `dist` is asked for): one body behind qt_mle_batch, qt_mle_dist_batch and qt_mle_dist_group_batch.
 // `centre` holds G matrices; trial b is measured against centre b % G (qt::EstOut).
 int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, const double* centre, int G,
@@ -732,17 +760,32 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
   if (int r = c.out(status, (size_t)B, &dst)) return r;
   if (int r = c.out(dist, (size_t)B, &ddist)) return r;
   const qt::EstOut eo{drho, dcen, ddist, G, 0};
-  if (h->nq >= 4) {
-    if (int r = prepare_large(h, init == QT_INIT_LIN)) return r;
-    if (max_iter > 4096) return fail(QT_ERR_UNSUPPORTED, "max_iter > 4096 is not supported for n_qubits >= 4");
-  }
-  // n = 3 keeps rho_i / alpha_i of every BFGS iteration in the trial's LDS (16 bytes per iteration and trial):
-  // the one-launch kernel (which also keeps 24 pairs there) up to 256 iterations, the split pair up to 2000
-  if (h->nq == 3 && max_iter > 2000)
-    return fail(QT_ERR_UNSUPPORTED, "max_iter > 2000 is not supported for n_qubits = 3 (LDS holds the two-loop scalars)");
-  const int mi = max_iter > 0 ? max_iter : 1;
+  // n >= 3 keeps rho_i / alpha_i of every BFGS iteration in the trial's LDS (16 bytes per iteration and trial): at most
+  // 4096 iterations at n = 4, 5 and 2000 at n = 3 (the one-launch kernel, which also keeps 24 pairs there, up to 256 of
+  // them), and no more than fit a CU's LDS beside this POVM's scratch (mle_iter_cap) -- refused here, before any launch.
+  // (Up to 256 iterations the cap is not worked out: what does not fit then is refused by launch().)
   h->last_mle_spec = h->spec_eligible();
   h->last_mle_helper = false;
+  if (h->nq >= 3) {
+    const int ceiling = h->nq == 3 ? 2000 : 4096;
+    if (max_iter > ceiling)
+      return fail(QT_ERR_UNSUPPORTED, "max_iter > %d is not supported for n_qubits = %d (LDS holds the two-loop scalars)", ceiling, h->nq);
+    if (max_iter > 256) {
+      int cap = 0;
+      if (int r = by_nq(h, [&](auto nq) -> int {
+            constexpr int NQ = decltype(nq)::value;
+            if constexpr (NQ >= 3) return mle_iter_cap<NQ>(h, h->last_mle_spec, &cap);
+            else return 0;
+          }))
+        return r;
+      if (max_iter > cap)
+        return fail(QT_ERR_UNSUPPORTED, "max_iter = %d is not supported for this POVM at n_qubits = %d: beside its %d rows a CU's "
+                    "LDS holds the two-loop scalars of at most %d iterations", max_iter, h->nq, h->M, cap);
+    }
+  }
+  if (h->nq >= 4)
+    if (int r = prepare_large(h, init == QT_INIT_LIN)) return r;
+  const int mi = max_iter > 0 ? max_iter : 1;
   return by_nq(h, [&](auto nq) -> int {
     constexpr int NQ = decltype(nq)::value;
     if constexpr (NQ <= 3) {
