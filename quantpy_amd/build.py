@@ -13,6 +13,11 @@ LIB = os.path.join(LIB_DIR, "libqtomo.so")
 # with registers to spare, and the ILP strategy (loads hoisted, independent chains interleaved) measured
 # 4-5 % faster on every n = 3 kernel (profiles/round1_v11_*).
 SCHED_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# A kernel's leading pointer and scalar arguments, up to its first struct, arrive in SGPRs at wave launch instead of
+# through an s_load from the argument segment (a cold read in front of every address).  The n <= 3 MLE kernels lead with
+# what their first loads need (csrc/qt_args.h: mle_front).  A kernel that leads with a struct preloads nothing.
+PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+FLAGS = SCHED_FLAGS + PRELOAD_FLAGS
 
 
 def _hipcc():
@@ -26,7 +31,7 @@ def _source_hash():
     """SHA-256 over the HIP sources, the public header and the compiler flags."""
     import hashlib
 
-    h = hashlib.sha256(" ".join(SCHED_FLAGS).encode())
+    h = hashlib.sha256(" ".join(FLAGS).encode())
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + [os.path.join(os.path.dirname(_HERE), "include", "qtomo.h")]
     for path in srcs:
         h.update(os.path.basename(path).encode())
@@ -49,7 +54,7 @@ def build_profile_library(verbose=False):
     inside the kernels; loaded only when QTOMO_LIB points at it, see scripts/phase_timing.py)."""
     os.makedirs(LIB_DIR, exist_ok=True)
     out = os.path.join(LIB_DIR, "libqtomo_prof.so")
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-DQT_PHASE_TIMING", *SCHED_FLAGS,
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-DQT_PHASE_TIMING", *FLAGS,
            "-o", out, os.path.join(CSRC, "qtomo.hip")]
     if verbose:
         print(" ".join(cmd))
@@ -62,7 +67,7 @@ def build_library(force=False, verbose=False):
     if not force and not _stale():
         return LIB
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *SCHED_FLAGS,
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *FLAGS,
            "-o", LIB + ".tmp", os.path.join(CSRC, "qtomo.hip")]
     if verbose:
         print(" ".join(cmd))

@@ -73,6 +73,27 @@ struct MleArgs<false> {
   using type = SpecArgs;
 };
 
+// The n <= 3 MLE kernels (qt_mle_small.h) lead with what the first batch of a trial's loads needs, as plain pointers and
+// ints in front of the struct: (counts, image, Ns, B, M, extra, max_iter, gtol).  The compiler preloads a kernel's leading
+// plain arguments into SGPRs at wave launch (build.py: PRELOAD_FLAGS) and stops at the first aggregate, so the addresses of
+// those loads hang on no load of the argument segment: 0.2 us of the 8.9 us headline step (DESIGN 4.1,
+// profiles/trial_front_headline_ab.txt).  The struct keeps its fields; mle_front writes the leading values into the
+// kernel's copy, and the body reads one struct as before.  A PovmView has no image: the generic launch passes nullptr in
+// that slot.
+__device__ __forceinline__ SpecArgs mle_front(SpecArgs a, const void* image, const double* Ns, int M, int extra) {
+  a.image = image;
+  a.Ns = Ns;
+  a.M = M;
+  a.extra = extra;
+  return a;
+}
+__device__ __forceinline__ PovmView mle_front(PovmView pv, const void*, const double* Ns, int M, int extra) {
+  pv.Ns = Ns;
+  pv.M = M;
+  pv.extra = extra;
+  return pv;
+}
+
 // t_s / total == N_s / ns_tot, compared as cross products of integer-valued doubles (exact below 2^53; a few
 // ulp of slack beyond that -- one stray count out of N_s < 1e14 is still seen)
 __device__ __forceinline__ bool shots_match(double t_s, double total, double n_s, double ns_tot) {

@@ -21,8 +21,8 @@ namespace qt {
 // register more -- the EstOut pointers of round 3 made it 129 -- takes a workgroup off every CU (measured: 0.372 -> 0.416 ms
 // per 65 536 trials).
 template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_mle_start(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int init,
-                                                   int max_iter, double gtol, EstOut rho,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_mle_start(const int64_t* __restrict__ counts, const void* image, const double* Ns, int B, int M, int extra,
+                                                   int max_iter, double gtol, typename MleArgs<GENERIC>::type pv0, int init, EstOut rho,
                                                    int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                    double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                    double* __restrict__ ws_x, double* __restrict__ ws_g,
@@ -34,8 +34,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   bool live;
   const int b = S::trial_index(B, &live);
   const int bb = live ? b : B - 1;
+  const auto pv = mle_front(pv0, image, Ns, M, extra);
   typename S::Prefetch pf;
   S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
+  if constexpr (!GENERIC) S::take_coefs(c, pv);
   bool shots_ok;
   if constexpr (GENERIC) {
     S::make_ctx(c, smem, pv);
@@ -311,8 +313,8 @@ __device__ __forceinline__ void bfgs_iterate_2l(const C& c, bool mine, double xk
                          // (<= 168 VGPRs, 18 spilled) 5.29 ms, 2 waves (205 VGPRs, no scratch) 5.39 ms -- instruction-bound either way
 #endif
 template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFGS_WAVES))) k_mle_bfgs(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
-                                                  double gtol, EstOut rho, int32_t* __restrict__ nit_out,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFGS_WAVES))) k_mle_bfgs(const int64_t* __restrict__ counts, const void* image, const double* Ns, int B, int M, int extra, int max_iter,
+                                                  double gtol, typename MleArgs<GENERIC>::type pv0, EstOut rho, int32_t* __restrict__ nit_out,
                                                   int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                   int32_t* __restrict__ status_out, const double* __restrict__ ws_x,
                                                   const double* __restrict__ ws_g, const double* __restrict__ ws_f,
@@ -326,12 +328,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_BFG
   extern __shared__ __attribute__((aligned(16))) double smem[];
   std::conditional_t<GENERIC, typename S::Ctx, typename S::template CtxSV<0>> c;  // (no lane tables: CtxSV)
   const int bb = live ? b : B - 1;
+  const auto pv = mle_front(pv0, image, Ns, M, extra);
   if constexpr (GENERIC) {
     S::make_ctx(c, smem, pv);
     S::load_freq(c, counts + (size_t)bb * pv.M);
   } else {
+    // (behind the ws_active vote: a workgroup with nothing to iterate reads no counts)
     typename S::Prefetch pf;
     S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
+    S::take_coefs(c, pv);
     S::make_ctx(c, smem, pv, pf);
     S::load_freq(c, pf);
   }
@@ -375,6 +380,14 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
   [[maybe_unused]] typename S::LateX late{false, 0.0, 0};
   [[maybe_unused]] int twin = 0;               // HW: this wavefront is a twin (wave-uniform)
   [[maybe_unused]] double* trial_sm = nullptr;  // HW: the scratch of the trial (a twin's own is c.sm)
+  // The trial's loads first: nothing but its index stands in front of them (a lone wave issues ~one instruction per 7
+  // clocks, and the counts are a cold read).  The twin set-up follows in their shadow.
+  bool live;
+  const int b = S::trial_index(B, &live);
+  const int bb = live ? b : B - 1;
+  typename S::Prefetch pf;
+  S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
+  if constexpr (!GENERIC) S::take_coefs(c, pv);
   if constexpr (HW) {
     static_assert(NQ == 3, "one trial per wavefront");
     static_assert(S::HelperLink::doubles() <= kFusedHwLdsPairs * 2 * D, "the hand-off lives in the LDS pair store");
@@ -394,11 +407,6 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     c.xtra = trial_sm + per_trial;
     c.late = &late;
   }
-  bool live;
-  const int b = S::trial_index(B, &live);
-  const int bb = live ? b : B - 1;
-  typename S::Prefetch pf;
-  S::prefetch_counts(pf, counts + (size_t)bb * pv.M, pv);
   bool shots_ok;
   if constexpr (GENERIC) {
     S::template make_ctx<HW>(c, smem, pv, twin);
@@ -506,30 +514,30 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
 // runs under its own kernel name, so that a profiler's per-kernel average of k_mle_fused is the average of the
 // 'lin'-start launches (bench.py's timed steps) and not a mixture with the iterating side measurements.
 template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) k_mle_fused(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
-                                                   double gtol, EstOut rho, int32_t* __restrict__ nit_out,
+__global__ void __launch_bounds__(256) k_mle_fused(const int64_t* __restrict__ counts, const void* image, const double* Ns, int B, int M, int extra, int max_iter,
+                                                   double gtol, typename MleArgs<GENERIC>::type pv, EstOut rho, int32_t* __restrict__ nit_out,
                                                    int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                    int32_t* __restrict__ status_out, double* __restrict__ pairs) {
-  mle_fused_body<NQ, GENERIC>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ, GENERIC>(mle_front(pv, image, Ns, M, extra), counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(256) k_mle_fused_mixed(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B,
-                                                         int max_iter, double gtol, EstOut rho,
+__global__ void __launch_bounds__(256) k_mle_fused_mixed(const int64_t* __restrict__ counts, const void* image, const double* Ns, int B, int M, int extra,
+                                                         int max_iter, double gtol, typename MleArgs<GENERIC>::type pv, EstOut rho,
                                                          int32_t* __restrict__ nit_out, int32_t* __restrict__ nfev_out,
                                                          double* __restrict__ fun_out, int32_t* __restrict__ status_out,
                                                          double* __restrict__ pairs) {
-  mle_fused_body<NQ, GENERIC>(pv, counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ, GENERIC>(mle_front(pv, image, Ns, M, extra), counts, B, 1, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 
 // The 'lin' start with a twin wavefront per trial (mle_fused_body<.., HW>): blocks of 256 x 2 threads, the grid of
 // k_mle_fused, its LDS layout with kFusedHwLdsPairs pairs and the twins' scratches behind it (Small::lds_bytes_twin).
 // Two waves per SIMD: the 256 registers of the body are what a wave can have.
 template <int NQ, bool GENERIC>
-__global__ void __launch_bounds__(512) k_mle_fused_hw(typename MleArgs<GENERIC>::type pv, const int64_t* __restrict__ counts, int B, int max_iter,
-                                                      double gtol, EstOut rho, int32_t* __restrict__ nit_out,
+__global__ void __launch_bounds__(512) k_mle_fused_hw(const int64_t* __restrict__ counts, const void* image, const double* Ns, int B, int M, int extra, int max_iter,
+                                                      double gtol, typename MleArgs<GENERIC>::type pv, EstOut rho, int32_t* __restrict__ nit_out,
                                                       int32_t* __restrict__ nfev_out, double* __restrict__ fun_out,
                                                       int32_t* __restrict__ status_out, double* __restrict__ pairs) {
-  mle_fused_body<NQ, GENERIC, true>(pv, counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
+  mle_fused_body<NQ, GENERIC, true>(mle_front(pv, image, Ns, M, extra), counts, B, 0, max_iter, gtol, rho, nit_out, nfev_out, fun_out, status_out, pairs);
 }
 
 }  // namespace qt

@@ -484,11 +484,20 @@ struct Proc64 {
 
 // mode 0: Dykstra CPTP, 1: TP only, 2: CP only  (process.py:231-278); in / out [B][64][64] complex, row-major;
 // ws: Proc64::kWsComplex complex numbers per process (modes 0 and 2)
-__global__ void __launch_bounds__(Proc64::NT) k_cptp_project64(const double* __restrict__ in, int B, int mode, int n_iter,
-                                                                double tol, double* __restrict__ out,
+// The launch-uniform options lead, as a struct: a kernel that leads with an aggregate takes none of its arguments
+// preloaded into SGPRs (build.py: PRELOAD_FLAGS).  This kernel sits at 256 VGPRs, and with its 14 dwords of plain
+// arguments held in SGPRs from the entry on it went from 32 to 56 B of scratch per lane.
+struct Cptp64Opts {
+  int mode, n_iter;
+  double tol;
+};
+__global__ void __launch_bounds__(Proc64::NT) k_cptp_project64(Cptp64Opts opts, const double* __restrict__ in, int B,
+                                                                double* __restrict__ out,
                                                                 int32_t* __restrict__ iters, int32_t* __restrict__ status,
                                                                 double* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) double sm64[];
+  const int mode = opts.mode, n_iter = opts.n_iter;
+  const double tol = opts.tol;
   const int b = blockIdx.x;
   if (b >= B) return;
   const Proc64::Map m(threadIdx.x);

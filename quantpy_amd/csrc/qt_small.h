@@ -503,12 +503,13 @@ struct Small {
   // The counts are the only HBM read of a trial.  Issued at the very top of the kernel (before the
   // workgroup stages its tables and meets at the barrier of make_ctx) their latency runs in the shadow
   // of that set-up; up to 4 values per lane are held in registers until load_freq picks them up.
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // (a register value: HIP's uint4 is a struct, copied through memory)
   struct Prefetch {
     int64_t v[4];
     double ns[4];  // N_s of the settings rows l + q G belong to (segmented check) or of setting s = lane (ns[0])
     bool ok, seg;  // seg: K in {2, 4, 8, 16} divides G -- the K outcomes of a setting sit in K neighbouring lanes
     int ri[4];     // specialised kernels: the R-order slots of the rows l + q G (rinv)
-    uint4 img;     // ... and this thread's 16-byte chunk of the workgroup's table image
+    u32x4 img;     // ... and this thread's 16-byte chunk of the workgroup's table image
     uint64_t mat;  // ... and this lane's entry of matrix_of's term table (n = 3: mat_slots)
   };
   __device__ __forceinline__ static void prefetch_counts(Prefetch& pf, const int64_t* counts, const PovmView& pv) {
@@ -621,7 +622,7 @@ struct Small {
   // tables in three load -> wait -> write loops, each an exposed L2 round trip of a lone wave.
   __device__ __forceinline__ static void prefetch_counts(Prefetch& pf, const int64_t* counts, const SpecArgs& a) {
     const int l = (threadIdx.x & 63) % G, M = a.M, nch = image_chunks(M), t = threadIdx.x;
-    const uint4* img = reinterpret_cast<const uint4*>(a.image);
+    const u32x4* img = reinterpret_cast<const u32x4*>(a.image);
     const int* rinv = reinterpret_cast<const int*>(img + nch);
     pf.img = img[t < nch ? t : nch - 1];
     if constexpr (NQ == 3) pf.mat = MakeMatTab<true, D>::type::v[l];
@@ -632,6 +633,18 @@ struct Small {
       pf.v[q] = counts[mc];
       pf.ri[q] = rinv[mc];
       pf.ns[q] = a.Ns[mc >> NQ];  // K = d outcomes per setting
+    }
+  }
+  // The rest of the argument struct, asked for straight behind the batch above: the 24 coefficients are the second fetch
+  // from the argument segment, and requested here their wait falls behind the issue of the counts' loads instead of
+  // standing alone in front of the workgroup barrier.  CtxSV::VC: pinned in vector registers, which the one-wave-per-SIMD
+  // kernels hold for them through the whole kernel anyway.  make_ctx fills in the rest of the context.
+  template <int LT>
+  __device__ __forceinline__ static void take_coefs(CtxSV<LT>& c, const SpecArgs& a) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      c.kT[k] = CtxSV<LT>::VC ? pin_vgpr(a.cT[k]) : a.cT[k];
+      c.kP[k] = CtxSV<LT>::VC ? pin_vgpr(a.cP[k]) : a.cP[k];
     }
   }
   template <bool VCOEF = false, bool TWIN = false, int LT>
@@ -647,7 +660,7 @@ struct Small {
     c.M = a.M;
     c.Mp = (a.M + 1) & ~1;
     c.a = a;
-    if (!(TWIN && twin) && (int)threadIdx.x < image_chunks(a.M)) reinterpret_cast<uint4*>(smem_block)[threadIdx.x] = pf.img;
+    if (!(TWIN && twin) && (int)threadIdx.x < image_chunks(a.M)) reinterpret_cast<u32x4*>(smem_block)[threadIdx.x] = pf.img;
     c.tfwd = reinterpret_cast<const int*>(smem_block);
     c.ttab = smem_block + image_last_ints(a.M) / 2;
     c.ptab = c.ttab + 24;
@@ -691,11 +704,6 @@ struct Small {
         c.bflip[2] = ((uint32_t)lane << 29) & 0x80000000u;
         c.bflip[3] = ((uint32_t)__popc(c.i & c.j) << 30) & 0x80000000u;
       }
-    }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      c.kT[k] = VCOEF ? pin_vgpr(a.cT[k]) : a.cT[k];
-      c.kP[k] = VCOEF ? pin_vgpr(a.cP[k]) : a.cP[k];
     }
   }
   // the butterfly of gsum<G> from stride KK on: for values already summed over aligned groups of KK lanes

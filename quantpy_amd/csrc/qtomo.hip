@@ -709,6 +709,15 @@ auto mle_povm_arg(const qt_handle_t* h, const Plan& p) {
   if constexpr (GENERIC) return p.pv;
   else return h->spec_args(p.pv.extra);
 }
+// One launch of an n <= 3 MLE kernel: the leading plain arguments (qt_args.h: mle_front) taken off the POVM struct that
+// follows them, then `rest`.  The generic kernels have no table image: nullptr.
+template <bool GENERIC, class K, class... R>
+int launch_mle(qt_handle_t* h, K kernel, const Plan& p, const int64_t* counts, int B, int max_iter, double tol, R... rest) {
+  const auto pv = mle_povm_arg<GENERIC>(h, p);
+  const void* image = nullptr;
+  if constexpr (!GENERIC) image = pv.image;
+  return launch(h, kernel, p, counts, image, pv.Ns, B, pv.M, pv.extra, max_iter, tol, pv, rest...);
+}
 
 // The largest max_iter whose BFGS launch of the split pair (povm_plan<NQ>(h, ., extra) in mle_batch_impl: 2 doubles per
 // iteration and trial behind the scratch, at n = 3 for each of a workgroup's TPB trials and behind the parked
@@ -816,12 +825,12 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
               h->last_mle_helper = true;
               p.block = dim3(qt::Small<NQ>::NT, 2);  // y = 1: the twin wavefronts
               p.lds = lds_hw;
-              return launch(h, qt::k_mle_fused_hw<NQ, GEN>, p, mle_povm_arg<GEN>(h, p), dc, B, max_iter, tol, eo, dnit, dnfev,
-                            dfun, dst, h->hess.as<double>());
+              return launch_mle<GEN>(h, qt::k_mle_fused_hw<NQ, GEN>, p, dc, B, max_iter, tol, eo, dnit, dnfev, dfun, dst,
+                                     h->hess.as<double>());
             }
           }
-          return launch(h, init == QT_INIT_LIN ? qt::k_mle_fused<NQ, GEN> : qt::k_mle_fused_mixed<NQ, GEN>, p,
-                        mle_povm_arg<GEN>(h, p), dc, B, max_iter, tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>());
+          return launch_mle<GEN>(h, init == QT_INIT_LIN ? qt::k_mle_fused<NQ, GEN> : qt::k_mle_fused_mixed<NQ, GEN>, p, dc, B,
+                                 max_iter, tol, eo, dnit, dnfev, dfun, dst, h->hess.as<double>());
         };
         if (int r = h->last_mle_spec ? fused(std::false_type()) : fused(std::true_type())) return r;
         return c.done(status, B);
@@ -849,17 +858,24 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
       constexpr bool GEN = decltype(generic)::value || NQ >= 4;
       const auto [k_start, k_bfgs] = mle_split_kernels<NQ, GEN>();
       const Plan ps = povm_plan<NQ>(h, B);
-      if (int r = launch(h, k_start, ps, mle_povm_arg<GEN>(h, ps), dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, all.x,
-                         all.g, all.f, all.act))
-        return r;
+      int r;
+      if constexpr (NQ <= 3)
+        r = launch_mle<GEN>(h, k_start, ps, dc, B, max_iter, tol, init, eo, dnit, dnfev, dfun, dst, all.x, all.g, all.f, all.act);
+      else
+        r = launch(h, k_start, ps, ps.pv, dc, B, init, max_iter, tol, eo, dnit, dnfev, dfun, dst, all.x, all.g, all.f, all.act);
+      if (r) return r;
       const int extra = NQ >= 4 ? max_iter : (NQ == 3 ? qt::LineSearch::SLOTS + 2 * mi : 0);
       for (int b0 = 0; b0 < B; b0 += chunk) {
         const int nb = B - b0 < chunk ? B - b0 : chunk;
         const MleArrays a = all.at(b0);
         const Plan p = povm_plan<NQ>(h, nb, extra);
-        if (int r = launch(h, k_bfgs, p, mle_povm_arg<GEN>(h, p), a.counts, nb, max_iter, tol, a.eo, a.nit, a.nfev, a.fun,
-                           a.status, a.x, a.g, a.f, a.act, h->hess.as<double>()))
-          return r;
+        if constexpr (NQ <= 3)
+          r = launch_mle<GEN>(h, k_bfgs, p, a.counts, nb, max_iter, tol, a.eo, a.nit, a.nfev, a.fun, a.status, a.x, a.g, a.f,
+                              a.act, h->hess.as<double>());
+        else
+          r = launch(h, k_bfgs, p, p.pv, a.counts, nb, max_iter, tol, a.eo, a.nit, a.nfev, a.fun, a.status, a.x, a.g, a.f,
+                     a.act, h->hess.as<double>());
+        if (r) return r;
       }
       return c.done(status, B);
     };
@@ -877,8 +893,8 @@ int project(qt_handle_t* h, const double* in, int B, int mode, int n_iter, doubl
             int32_t* status, const double* centres = nullptr, int G = 1, int g0 = 0, double* dist = nullptr) {
   if (h->D == 64) {
     if (mode != 1) HIPCHK(h->proc_ws.ensure((size_t)B * qt::Proc64::kWsComplex * 2 * sizeof(double)));
-    return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes, in, B, mode, n_iter, tol, out,
-                  iters, status, h->proc_ws.as<double>());
+    return launch(h, qt::k_cptp_project64, dim3(B), dim3(qt::Proc64::NT), qt::Proc64::kLdsBytes,
+                  qt::Cptp64Opts{mode, n_iter, tol}, in, B, out, iters, status, h->proc_ws.as<double>());
   }
   if (h->D == 16)
     return launch(h, qt::k_cptp_wave16, dim3((B + 3) / 4), dim3(256), 0, in, B, mode, n_iter, tol, out, iters, status, centres, G, g0, dist);

@@ -8,9 +8,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from quantpy_amd.build import CSRC, SCHED_FLAGS, _hipcc  # noqa: E402
+from quantpy_amd.build import CSRC, FLAGS, _hipcc  # noqa: E402
 
-out = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *SCHED_FLAGS,
+out = subprocess.run([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *FLAGS,
                       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/qtomo_report.so", os.path.join(CSRC, "qtomo.hip")],
                      capture_output=True, text=True)
 text = out.stderr
