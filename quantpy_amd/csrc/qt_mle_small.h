@@ -12,6 +12,20 @@
 
 namespace qt {
 
+// What the start of a trial asks of its first gradient's max-norm: whether it is above gtol (the trial iterates) and
+// whether it is a NaN (mle_start_status reads it for nothing else).  The specialised n = 3 kernels answer with two
+// ballots -- gnorm > gtol <=> no element is a NaN and some element is above; gnorm != gnorm <=> some element is a
+// NaN -- and hand mle_start_status 0 or a NaN in place of the norm: the v_max_f64 butterfly of gmax stood between the
+// evaluation and the stores of every trial.  (The BFGS loop's norms are gmax: bfgs_step_exit compares them.)
+template <int NQ, bool GENERIC>
+constexpr bool kStartBallots = NQ == 3 && !GENERIC && kLaneLeftovers;
+template <int G>
+__device__ __forceinline__ double start_norm_ballots(double gk, double gtol, bool& above) {
+  const bool nan = group_any<G>(gk != gk);
+  above = !nan && group_any<G>(fabs(gk) > gtol);
+  return nan ? __builtin_nan("") : 0.0;
+}
+
 // a10, part 1: starting point (state.py:205-212), Cholesky parametrisation and the first
 // (value, gradient) evaluation.  Trials whose gradient already meets gtol -- every full-rank
 // high-shot trial, where BFGS exits at iteration 0 -- are finished here; the
@@ -63,8 +77,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
   [[maybe_unused]] typename S::DeferredValue dv;
   if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
   else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
-  const double gnorm = gmax<G>(fabs(gk));
-  const bool iterate = shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
+  double gnorm;
+  bool iterate;
+  if constexpr (kStartBallots<NQ, GENERIC>) {
+    bool above;
+    gnorm = start_norm_ballots<G>(gk, gtol, above);
+    iterate = shots_ok && ok && above && (0 < max_iter);
+  } else {
+    gnorm = gmax<G>(fabs(gk));
+    iterate = shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
+  }
   if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
   const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));
   S::emit(c, rho, b, live, rho_l);
@@ -486,9 +508,18 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     if constexpr (GENERIC) S::nll_grad(c, xk, fk, gk, &rho_l, true, &sp);
     else S::template nll_grad<true>(c, xk, fk, gk, &rho_l, true, &sp, &dv);
   }
-  const double gnorm = gmax<G>(fabs(gk));
-  QT_STAMP(9);
-  const bool iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
+  double gnorm;
+  bool iterate;
+  if constexpr (kStartBallots<NQ, GENERIC>) {
+    bool above;
+    gnorm = start_norm_ballots<G>(gk, gtol, above);
+    QT_STAMP(9);
+    iterate = live && shots_ok && ok && above && (0 < max_iter);
+  } else {
+    gnorm = gmax<G>(fabs(gk));
+    QT_STAMP(9);
+    iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
+  }
   if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
   S::emit(c, rho, b, live && !iterate, rho_l);  // (trials that iterate are written at the end of the loop)
   const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));

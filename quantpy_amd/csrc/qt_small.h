@@ -34,6 +34,16 @@ namespace qt {
 
 constexpr bool kLiftSingleNegative = true;  // a7 short cut of Small::lift_single_negative (n = 3)
 
+// Two parts of the n = 3 specialised MLE kernels that can be built without (-DNAME=0), for the A/B libraries of
+// profiles/lane_constants_headline_ab.txt.
+#ifndef QT_LANE_INT_FRONT
+#define QT_LANE_INT_FRONT 1    // load_freq sums counts below 2^22 as 32-bit integers
+#endif
+#ifndef QT_LANE_LEFTOVERS
+#define QT_LANE_LEFTOVERS 1    // no second store of the Bloch element in nll_grad; ballots for the first gradient norm
+#endif
+constexpr bool kLaneLeftovers = QT_LANE_LEFTOVERS != 0;
+
 template <int NQ>
 struct Small {
   static constexpr int d = 1 << NQ;
@@ -720,34 +730,112 @@ struct Small {
     }
     return v;
   }
+  // The same two butterflies on 32-bit integers: v_add_u32 takes the DPP operand itself, one instruction per level and
+  // value where a double takes two moves and an add.
+  template <int CTRL>
+  __device__ __forceinline__ static uint32_t dpp_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+  }
+  template <int KK>
+  __device__ __forceinline__ static uint32_t segsum_u32(uint32_t v) {
+    v += dpp_u32<0xB1>(v);
+    if (KK >= 4) v += dpp_u32<0x4E>(v);
+    if (KK >= 8) v += dpp_u32<0x141>(v);
+    if (KK >= 16) v += dpp_u32<0x140>(v);
+    return v;
+  }
+  template <int KK>
+  __device__ __forceinline__ static uint32_t gsum_above_u32(uint32_t v) {
+    if (KK < 2) v += dpp_u32<0xB1>(v);
+    if (KK < 4) v += dpp_u32<0x4E>(v);
+    if (G >= 8 && KK < 8) v += dpp_u32<0x141>(v);
+    if (G >= 16 && KK < 16) v += dpp_u32<0x140>(v);
+    if (G == 64) {
+      v += dpp_u32<0x142>(v);
+      v += dpp_u32<0x143>(v);
+      v = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+    }
+    return v;
+  }
   // load_freq of the specialised shape.  A lane knows the R-order slot of each of its rows (Prefetch::ri), so the
   // frequency goes straight there: no parking of the counts in rbuf and no raw[trmap[m]] (two dependent LDS reads)
   // to fetch them back.  The total is the sum of the per-setting sums the shots check forms anyway, continued over the
   // settings: every partial sum is an integer-valued double below 2^53, so any order gives the bits of gsum<G>(part).
+  // INTEGER FRONT (n = 3, the kernels with lane tables): where every count of the wavefront lies in [0, 2^22) -- one
+  // ballot, wave-uniform -- the per-setting sums and the total are formed as 32-bit integers (216 counts below 2^22: the
+  // total is below 2^30) and converted once.  Every number involved is an integer below 2^53, which a double holds
+  // exactly: the doubles are those of the sums on doubles, bit for bit.  Anything else takes that path.
+  static constexpr bool kIntFront = NQ == 3 && QT_LANE_INT_FRONT != 0;
   template <int LT>
   __device__ static bool load_freq(const CtxSV<LT>& c, const Prefetch& pf) {
-    double dv[4], st[4];
-    bool valid[4];
+    if constexpr (kIntFront && LT != 0) {
+      return load_freq_int(c, pf);
+    } else {
+      double dv[4], st[4];
+      bool valid[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        valid[q] = c.l + q * G < c.M;
+        dv[q] = valid[q] ? (double)pf.v[q] : 0.0;
+        st[q] = segsum_c<d>(dv[q]);
+      }
+      const double total = gsum_above<d>((st[0] + st[1]) + (st[2] + st[3]));
+      const double inv = 1.0 / total;
+      bool bad = false;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) bad |= valid[q] & !shots_match(st[q], total, pf.ns[q], c.a.ns_tot);
+      double* fq = c.freq();
+      double* dummy = c.rbuf();  // rows beyond M: one slot of a buffer nobody reads before writing it
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *(valid[q] ? fq + pf.ri[q] : dummy) = dv[q] * inv;
+      const unsigned long long votes = __builtin_amdgcn_ballot_w64(bad);
+      const int lane = threadIdx.x & 63;
+      const unsigned long long mine = (G == 64) ? ~0ull : (((1ull << (G & 63)) - 1ull) << (lane / G * G));
+      wave_sync();
+      return (votes & mine) == 0ull;
+    }
+  }
+  // (A function of its own, with the statements behind the sums written out a second time: shared with the form above
+  // they come out of the compiler in another order there, and k_mle_bfgs and the n = 1, 2 kernels keep their
+  // instruction streams, scripts/isa_identity.py.)
+  template <int LT>
+  __device__ __forceinline__ static bool load_freq_int(const CtxSV<LT>& c, const Prefetch& pf) {
+    static_assert(G == 64, "one trial per wavefront");
+    double dv[4], st[4], total;
+    bool valid[4], small = true;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       valid[q] = c.l + q * G < c.M;
-      dv[q] = valid[q] ? (double)pf.v[q] : 0.0;
-      st[q] = segsum_c<d>(dv[q]);
+      small &= (unsigned long long)pf.v[q] < (1ull << 22);
     }
-    const double total = gsum_above<d>((st[0] + st[1]) + (st[2] + st[3]));
+    if (__builtin_amdgcn_ballot_w64(!small) == 0ull) {
+      uint32_t is[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t iv = valid[q] ? (uint32_t)pf.v[q] : 0u;
+        is[q] = segsum_u32<d>(iv);
+        dv[q] = (double)iv;
+        st[q] = (double)is[q];
+      }
+      total = (double)gsum_above_u32<d>((is[0] + is[1]) + (is[2] + is[3]));
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        dv[q] = valid[q] ? (double)pf.v[q] : 0.0;
+        st[q] = segsum_c<d>(dv[q]);
+      }
+      total = gsum_above<d>((st[0] + st[1]) + (st[2] + st[3]));
+    }
     const double inv = 1.0 / total;
     bool bad = false;
 #pragma unroll
     for (int q = 0; q < 4; ++q) bad |= valid[q] & !shots_match(st[q], total, pf.ns[q], c.a.ns_tot);
     double* fq = c.freq();
-    double* dummy = c.rbuf();  // rows beyond M: one slot of a buffer nobody reads before writing it
+    double* dummy = c.rbuf();
 #pragma unroll
     for (int q = 0; q < 4; ++q) *(valid[q] ? fq + pf.ri[q] : dummy) = dv[q] * inv;
-    const unsigned long long votes = __builtin_amdgcn_ballot_w64(bad);
-    const int lane = threadIdx.x & 63;
-    const unsigned long long mine = (G == 64) ? ~0ull : (((1ull << (G & 63)) - 1ull) << (lane / G * G));
     wave_sync();
-    return (votes & mine) == 0ull;
+    return __builtin_amdgcn_ballot_w64(bad) == 0ull;
   }
 
   // ---- factorised contractions for product POVMs -----------------------------------------------
@@ -1804,8 +1892,12 @@ struct Small {
     const double bl = bloch_of(c, A);
     QT_STAMP(13);
     double* vec = c.vec();
-    vec[c.l] = bl;
-    wave_sync();
+    // (n = 3 with lane tables: bloch_of has just left the whole Bloch vector in vec and read this element back from
+    // it -- a second store of it would only put an LDS round trip in front of the first forward stage)
+    if constexpr (!(NQ == 3 && C::kLaneTables != 0 && kLaneLeftovers)) {
+      vec[c.l] = bl;
+      wave_sync();
+    }
     // p = d * A' b ;  f = -sum freq log(p + 1e-10) ;  r = freq / (p + 1e-10)
     double fpart = 0.0;
     const double* fr = c.freq();
