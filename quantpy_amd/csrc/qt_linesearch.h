@@ -415,4 +415,14 @@ QT_HD int mle_start_status(bool shots_ok, bool ok, bool iterate, int max_iter, d
   return TRIAL_OK;
 }
 
+// The one-launch kernels store the scalars of the common case -- nit = 0, nfev = 1, TRIAL_OK -- in front of a trial's
+// first evaluation when the caller does not ask for the value.  true: that triple is what store_trial would write at
+// the start point (nit = 0, nfev = ok ? 1 : 0, mle_start_status), so nothing is written again.  (A trial that iterates
+// answers true as well: its scalars are the BFGS loop's, later, whatever was stored early.)
+QT_HD bool mle_early_scalars_final(bool shots_ok, bool ok, bool iterate, int max_iter, double gnorm, double fk,
+                                   bool xnan, bool fun_wanted) {
+  if (fun_wanted) return false;
+  return ok && mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, xnan) == TRIAL_OK;
+}
+
 }  // namespace qt

@@ -481,6 +481,18 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     xk = S::cholesky_param(c, sp.rho, ok);
   }
   QT_STAMP(8);
+  // A trial that stops at iteration 0 returns sp.rho, and every wave that gets here owns its trial (the other wave of a
+  // twin pair has left above): the matrix and the scalars of the common case leave NOW, so that their write latency
+  // lies beside the evaluation and not behind the last instruction of the launch's slowest wave.  Behind the
+  // evaluation the wave writes only what differs (mle_early_scalars_final; the matrix if a fallback replaced it).  A
+  // trial that iterates is written again by the BFGS loop: the same lanes and addresses, later in program order.
+  [[maybe_unused]] bool early_rho = false, early_scalars = false;  // wave-uniform
+  if constexpr (kEarlyOutputs) {
+    S::emit_rho(c, rho, b, live, sp.rho);
+    early_rho = true;
+    early_scalars = fun_out == nullptr;
+    if (early_scalars && live && c.l == 0) store_trial(b, 0, 1, 0.0, TRIAL_OK, nit_out, nfev_out, nullptr, status_out);
+  }
   double fk, gk;
   cd rho_l;
   [[maybe_unused]] typename S::DeferredValue dv;
@@ -501,6 +513,7 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
       if (!ok) {
         sp.rho = S::psd_project(c, lin, 1e-15);
         xk = S::cholesky_param(c, sp.rho, ok);
+        early_rho = false;  // (the matrix stored above is not the one this trial returns)
       }
     }
   }
@@ -521,9 +534,17 @@ __device__ __forceinline__ void mle_fused_body(const typename MleArgs<GENERIC>::
     iterate = live && shots_ok && ok && (gnorm > gtol) && (0 < max_iter);
   }
   if constexpr (!GENERIC) fk = S::value_if_needed(c, dv, iterate || fun_out != nullptr);
-  S::emit(c, rho, b, live && !iterate, rho_l);  // (trials that iterate are written at the end of the loop)
-  const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, group_any<G>(xk != xk));
-  if (live && !iterate && c.l == 0) store_trial(b, 0, ok ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
+  // (trials that iterate are written at the end of the loop)
+  if constexpr (kEarlyOutputs) {
+    S::emit_dist(c, rho, b, live && !iterate, rho_l);
+    if (!early_rho) S::emit_rho(c, rho, b, live && !iterate, rho_l);
+  } else {
+    S::emit(c, rho, b, live && !iterate, rho_l);
+  }
+  const bool xnan = group_any<G>(xk != xk);
+  const int status = mle_start_status(shots_ok, ok, iterate, max_iter, gnorm, fk, xnan);
+  const bool stored = early_scalars && mle_early_scalars_final(shots_ok, ok, iterate, max_iter, gnorm, fk, xnan, fun_out != nullptr);
+  if (live && !iterate && c.l == 0 && !stored) store_trial(b, 0, ok ? 1 : 0, fk, status, nit_out, nfev_out, fun_out, status_out);
   QT_STAMP(10);
   if (!__any(iterate)) return;  // per wave
   if (!iterate) {                // finite dummies for the groups of this wave that are already done

@@ -43,6 +43,16 @@ constexpr bool kLiftSingleNegative = true;  // a7 short cut of Small::lift_singl
 #define QT_LANE_LEFTOVERS 1    // no second store of the Bloch element in nll_grad; ballots for the first gradient norm
 #endif
 constexpr bool kLaneLeftovers = QT_LANE_LEFTOVERS != 0;
+// Two re-orderings of the clipped trial's chain in k_mle_fused_hw<3, .> that move no floating-point operation, each
+// built without by -DNAME=0 (profiles/lift_tail_headline_ab.txt; three more were measured there and are not in the source):
+#ifndef QT_LIFT_ONE_EXIT
+#define QT_LIFT_ONE_EXIT 1     // lift_single_negative: the result beside the residual check, one test behind both
+#endif
+#ifndef QT_EARLY_OUTPUTS
+#define QT_EARLY_OUTPUTS 1     // mle_fused_body: the start matrix and the common scalars are stored in front of the evaluation
+#endif
+constexpr bool kLiftOneExit = QT_LIFT_ONE_EXIT != 0;
+constexpr bool kEarlyOutputs = QT_EARLY_OUTPUTS != 0;
 
 template <int NQ>
 struct Small {
@@ -1646,6 +1656,8 @@ struct Small {
   // NATURAL: the caller's kneg is d - 1 at compile time (the twin of k_mle_fused_hw: the natural pivot order 0 .. d - 1).
   // The d steps are then unrolled: the pivot comes from a constant lane, the LDS offsets of row and column p are
   // immediates, and the step counter, its compare and its branch are gone.  The arithmetic of a step is the same text.
+  // `out` is written whenever the squarings certify, also when the checks behind them refuse (kLiftOneExit): a caller
+  // reads it only behind `true`.
   template <bool NATURAL = false, class C>
   __device__ static bool lift_single_negative(const C& c, cd r, int kneg, double eps, cd& out,
                                               const cd* inverse = nullptr) {
@@ -1729,6 +1741,29 @@ struct Small {
     if (i == j) b.im = 0.0;
     b = cscale(b, 1.0 / gtrace<G>(i == j, b.re));            // N = X / Tr X
     const double lam = gsum<G>(r.re * b.re + r.im * b.im);  // Tr(A N) = sum_ij A_ij conj(N_ij)
+    if constexpr (kLiftOneExit) {
+      // The result needs lam and not the residual: both in one basic block, so that the trace and the divisions of
+      // `out` run beside the 16-FMA chains and the two reductions of the check, and ONE wave-uniform test behind them,
+      // combined without short-circuit (as in the squaring loop).  Same operations, operands and order as below.
+      Ai[c.e] = r;
+      Vi[c.e] = b;
+      const double w = eps - lam;
+      const cd o{fma(w, b.re, r.re), fma(w, b.im, r.im)};
+      const double tr = gtrace<G>(i == j, o.re);
+      out = cd{o.re / tr, o.im / tr};
+      wave_sync();
+      cd q{-lam * b.re, -lam * b.im};
+#pragma unroll
+      for (int k = 0; k < d; ++k) {  // (A N)_ij, N Hermitian
+        const cd u = Ai[i * LD + k], v = Vi[j * LD + k];
+        q.re = fma(u.re, v.re, fma(u.im, v.im, q.re));
+        q.im = fma(u.im, v.re, fma(-u.re, v.im, q.im));
+      }
+      wave_sync();
+      const double res2 = gsum<G>(q.re * q.re + q.im * q.im);
+      const double nrm2 = gsum<G>(r.re * r.re + r.im * r.im);
+      return (lam < eps) & (res2 <= 1e-26 * nrm2);  // (a NaN on either side refuses, as !(a < b) did)
+    }
     if (!(lam < eps)) return false;
     Ai[c.e] = r;
     Vi[c.e] = b;
@@ -1957,6 +1992,8 @@ struct Small {
     wave_sync();
     cd g = matrix_of(c, vec);
     QT_STAMP(17);
+    // (LATE: collect in front of matrix_of, so that the poll, Tr and the divisions' denominator half overlap its add
+    // chain, was measured 0.07 us SLOWER: profiles/lift_tail_headline_ab.txt)
     if constexpr (LATE) {
       LateX& lx = *c.late;
       lx.x = 1.0;
@@ -2011,6 +2048,23 @@ struct Small {
       const double v = hs_to_centre(c, r, o.centre_of(b, 2 * D));  // b: this lane group's trial
       if (store && c.l == 0) o.dist[b] = v;
     }
+    if (store && o.rho) {
+      double* out = o.rho + ((size_t)b * D + c.l) * 2;
+      out[0] = r.re;
+      out[1] = r.im;
+    }
+  }
+  // The two halves of emit on their own: mle_fused_body stores the matrix in front of the first evaluation and the
+  // distance behind it.
+  template <class C>
+  __device__ __forceinline__ static void emit_dist(const C& c, const EstOut& o, int b, bool store, cd r) {
+    if (o.dist) {
+      const double v = hs_to_centre(c, r, o.centre_of(b, 2 * D));
+      if (store && c.l == 0) o.dist[b] = v;
+    }
+  }
+  template <class C>
+  __device__ __forceinline__ static void emit_rho(const C& c, const EstOut& o, int b, bool store, cd r) {
     if (store && o.rho) {
       double* out = o.rho + ((size_t)b * D + c.l) * 2;
       out[0] = r.re;
