@@ -26,6 +26,7 @@
 #include "qt_process.h"
 #include "qt_process64.h"
 #include "qt_process_wave16.h"
+#include "qt_product_tables.h"
 #include "qt_sampler.h"
 #include "qt_small.h"
 
@@ -113,6 +114,39 @@ struct ProcessState {
   }
 };
 
+// What a registration (qt_set_povm / qt_set_povm_product) says about the POVM.  PovmState::reset assigns a fresh one, so
+// a member added here is forgotten with the rest.  A registration fills it in as it goes and sets `registered` -- and,
+// for a product POVM, `prod` -- as its last step: one that returns an error leaves a handle without a POVM.
+struct PovmDesc {
+  bool registered = false;
+  double ns_tot = 0.0;  // sum of the registered shots per setting
+  double ns_max = 0.0;  // the largest of them (product POVMs): the n >= 4 count cache holds 32-bit counts
+  // The dense operands A, A^T, A', A'^T ([M][D] each: 64 MB at n = 5) exist when `dense_ready`; a product POVM at n >= 4
+  // never reads them and builds them only on demand (ensure_dense: A from the one-qubit table unless `a_loaded`),
+  // likewise the dense left inverse (`pinv_ready`, compute_dense_pinv).
+  bool a_loaded = false, dense_ready = false, pinv_ready = false;
+  int S1 = 0, K1 = 0;       // a product POVM's one-qubit factor: S1 settings of K1 outcomes, table T [S1 K1][4]
+  qt::ProductView prod{};   // the product description as the kernels take it: pointers into the buffers below
+  int paired_tables = 0;    // what qt_set_povm_product found: bit 0 = T is paired, bit 1 = pinv(T)^T is
+  bool image_ready = false;  // `image` holds the table image (qt::SpecArgs::image: built when both tables are paired)
+};
+
+// The registered POVM: its description and the device memory that description points into, which outlives it for the
+// next registration to reuse (DevBuf::ensure).
+struct PovmState : PovmDesc {
+  DevBuf Ns;                                // [S] shots per setting
+  DevBuf A, AT, Aw, AwT, Pinv, PinvT;       // dense operands and left inverse
+  DevBuf T, P1, P1T;                        // [R1][4] one-qubit table, [4][R1] its left inverse, [R1][4] the transpose
+  DevBuf wrow, rmap, rinv, fwd, bwd, last;  // qt_product_tables.h
+  DevBuf image;
+  void reset() { static_cast<PovmDesc&>(*this) = PovmDesc{}; }
+  void release() {
+    reset();
+    for (DevBuf* b : {&Ns, &A, &AT, &Aw, &AwT, &Pinv, &PinvT, &T, &P1, &P1T, &wrow, &rmap, &rinv, &fwd, &bwd, &last, &image})
+      b->release();
+  }
+};
+
 }  // namespace
 
 struct qt_handle {
@@ -126,18 +160,14 @@ struct qt_handle {
   // waited for (Call::done).  Transfers above kMailMax, or when the box is full, take the direct route.
   char* mail = nullptr;
   size_t mail_used = 0;
-  // POVM cache.  The dense operands A, A^T, A', A'^T ([M][D] each: 64 MB at n = 5) exist when `dense_ready`;
-  // a product POVM at n >= 4 never reads them and builds them only on demand (ensure_dense), likewise the dense
-  // left inverse (`pinv_ready`, compute_dense_pinv).
-  bool povm_set = false, dense_ready = false, a_loaded = false, pinv_ready = false;
+  // The registered POVM (PovmState).  Its shape stays here, written by begin_povm alone: the whole file reads h->M.
+  PovmState povm;
   int S = 0, K = 0, M = 0;
-  DevBuf A, AT, Aw, AwT, Pinv, PinvT, Ns, info;
-  // packed row digits of the Kronecker assembly (k_povm_kron), cached per (S1, K1)
+  DevBuf info;
+  // packed row digits of the Kronecker assembly (k_povm_kron), cached per (S1, K1): qt_povm_kron's cache, which says
+  // nothing about the registered POVM
   DevBuf kron_dig;
   int kron_S1 = 0, kron_K1 = 0;
-  // product-POVM (Kronecker) description, valid when prod.enabled
-  DevBuf pr_T, pr_P1, pr_P1T, pr_wrow, pr_rmap, pr_rinv, pr_fwd, pr_bwd, pr_last, pr_image;
-  qt::ProductView prod{};
   // staging for host-pointer calls: one buffer per array of a call, in the order the call registers them (Call)
   DevBuf stage[kStageBufs];
   DevBuf aug;      // [cols][2 cols] Gauss-Jordan workspace of enqueue_left_inverse
@@ -161,16 +191,12 @@ struct qt_handle {
   bool proc_set = false;  // `proc` describes the current POVM: a set-up succeeded after the last qt_set_povm
   bool proc_dense = false;  // qt_process_prefer_dense: qt_lifp_batch multiplies by the dense left inverse where it has a choice
 
-  double ns_tot = 0.0;  // sum of the registered shots per setting
   bool check_shots = true;  // qt_set_option(QT_OPT_SHOTS_CHECK) / QTOMO_SKIP_SHOTS_CHECK=1 at qt_create
   int fused_max_waves = 1024;  // qt_set_option(QT_OPT_MLE_FUSED_MAX_WAVES): largest batch (in trial-waves) of k_mle_fused
   int lifp_dist_slice = 0;  // qt_set_option(QT_OPT_LIFP_DIST_SLICE): processes per slice of qt_lifp_dist_batch (0: the byte bound's)
-  double ns_max = 0.0;  // largest registered shot number (product POVMs): the n >= 4 count cache holds 32-bit counts
   bool paired_stages = true;  // qt_set_option(QT_OPT_PAIRED_STAGES): let paired tables take their own stages (n <= 3)
-  int paired_tables = 0;      // what qt_set_povm_product found: bit 0 = T is paired, bit 1 = pinv(T)^T is
   // qt_set_option(QT_OPT_MLE_SPECIALISE): let an eligible POVM take the specialised MLE kernels (GENERIC = false, n <= 3)
   bool mle_specialise = true;
-  bool image_ready = false;    // pr_image holds the table image of the current POVM (built when both tables are paired)
   bool last_mle_spec = false;  // which instantiation the last MLE launch took (qt_get_mle_specialised)
   // qt_set_option(QT_OPT_MLE_HELPER_WAVE): let the one-launch 'lin' start at n = 3 run k_mle_fused_hw (a helper wavefront
   // per trial, which runs the single-negative lift on speculation and a lifted trial's second Cholesky sweep)
@@ -180,23 +206,23 @@ struct qt_handle {
   // K = d, M = 6^n <= 4 G and the segmented shots check), both tables paired and their stages on, equal shots, the
   // shots check on.  Everything else -- 'sic', 'proj4', 'proj', unequal shots, plain arrays -- takes the generic body.
   bool spec_eligible() const {
-    return mle_specialise && nq <= 3 && povm_set && prod.enabled && prod.R1 == 6 && K == d && paired_stages &&
-           paired_tables == 3 && image_ready && prod.uniform && check_shots;
+    return mle_specialise && nq <= 3 && povm.registered && povm.prod.enabled && povm.prod.R1 == 6 && K == d &&
+           paired_stages && povm.paired_tables == 3 && povm.image_ready && povm.prod.uniform && check_shots;
   }
   qt::SpecArgs spec_args(int extra) const {
-    qt::SpecArgs a{pr_image.p, Ns.as<double>(), ns_tot, prod.wuni, jtol2, M, extra, {}, {}};
+    qt::SpecArgs a{povm.image.p, povm.Ns.as<double>(), povm.ns_tot, povm.prod.wuni, jtol2, M, extra, {}, {}};
     for (int k = 0; k < 12; ++k) {
-      a.cT[k] = prod.cT[k];
-      a.cP[k] = prod.cP[k];
+      a.cT[k] = povm.prod.cT[k];
+      a.cP[k] = povm.prod.cP[k];
     }
     return a;
   }
   // the POVM as the estimator kernels read it; `extra` (PovmView::extra) comes with the launch's LDS size (Plan)
   qt::PovmView view(int extra) const {
-    qt::PovmView v{Aw.as<double>(), AwT.as<double>(), PinvT.as<double>(), M, prod, jtol2,
-                   check_shots ? Ns.as<double>() : nullptr, S, K, ns_tot, extra};
-    v.pr.pairedT = paired_stages ? paired_tables & 1 : 0;
-    v.pr.pairedP = paired_stages ? (paired_tables >> 1) & 1 : 0;
+    qt::PovmView v{povm.Aw.as<double>(), povm.AwT.as<double>(), povm.PinvT.as<double>(), M, povm.prod, jtol2,
+                   check_shots ? povm.Ns.as<double>() : nullptr, S, K, povm.ns_tot, extra};
+    v.pr.pairedT = paired_stages ? povm.paired_tables & 1 : 0;
+    v.pr.pairedP = paired_stages ? (povm.paired_tables >> 1) & 1 : 0;
     return v;
   }
   // Jacobi stopping rule off^2 <= jtol2 * ||A||_F^2.  Measured on the C2 batch: the last sweep takes off^2
@@ -436,7 +462,7 @@ Plan large_plan(const qt_handle_t* h, int B, int M, int R1, int max_iter) {
   size_t lds = qt::Large<NQ>::lds_bytes(M, R1, max_iter);
   int extra = 0;
   const size_t cache = 4 * (size_t)M + 8;
-  if (NQ == 5 && h->prod.enabled && h->ns_max < 4294967296.0 && lds + cache <= kLdsLimit) {
+  if (NQ == 5 && h->povm.prod.enabled && h->povm.ns_max < 4294967296.0 && lds + cache <= kLdsLimit) {
     extra = (int)(lds / 8);
     lds += cache;
   }
@@ -446,8 +472,8 @@ Plan large_plan(const qt_handle_t* h, int B, int M, int R1, int max_iter) {
 // An estimator over the handle's POVM.  `extra`: doubles per trial behind the scratch at n <= 3, BFGS iterations at n >= 4.
 template <int NQ>
 Plan povm_plan(const qt_handle_t* h, int B, int extra = 0) {
-  if constexpr (NQ <= 3) return small_plan<NQ>(h, B, h->M, h->prod.enabled ? h->prod.R1 : 0, extra);
-  else return large_plan<NQ>(h, B, h->M, h->prod.R1, extra);
+  if constexpr (NQ <= 3) return small_plan<NQ>(h, B, h->M, h->povm.prod.enabled ? h->povm.prod.R1 : 0, extra);
+  else return large_plan<NQ>(h, B, h->M, h->povm.prod.R1, extra);
 }
 
 // The Cholesky parametrisation, which reads no POVM: scratch only, and an empty PovmView.
@@ -478,22 +504,20 @@ int by_nq(const qt_handle_t* h, F f) {
 // chip-wide variant (qt_ops.h) beyond -- the 256 x 256 complex Gram matrix of 2-qubit process tomography takes
 // 12.5 ms in one workgroup and 1.8 ms as 2 x 256 small launches.
 template <int CPLX>
-void launch_gauss_jordan(qt_handle_t* h, int n, double* aug, int* info) {
-  if (n < 128) {
-    hipLaunchKernelGGL(qt::k_gauss_jordan<CPLX>, dim3(1), dim3(1024), 0, h->stream, n, aug, info);
-    return;
-  }
-  hipLaunchKernelGGL(qt::k_gj_identity<CPLX>, dim3(grid_for((size_t)n * n)), dim3(256), 0, h->stream, n, aug, info);
+int launch_gauss_jordan(qt_handle_t* h, int n, double* aug, int* info) {
+  if (n < 128) return launch(h, qt::k_gauss_jordan<CPLX>, dim3(1), dim3(1024), 0, n, aug, info);
+  if (int r = launch(h, qt::k_gj_identity<CPLX>, dim3(grid_for((size_t)n * n)), dim3(256), 0, n, aug, info)) return r;
   for (int k = 0; k < n; ++k) {
-    hipLaunchKernelGGL(qt::k_gj_pivot<CPLX>, dim3(1), dim3(1024), 0, h->stream, n, aug, k, info);
-    hipLaunchKernelGGL(qt::k_gj_eliminate<CPLX>, dim3(n), dim3(256), 0, h->stream, n, aug, k);
+    if (int r = launch(h, qt::k_gj_pivot<CPLX>, dim3(1), dim3(1024), 0, n, aug, k, info)) return r;
+    if (int r = launch(h, qt::k_gj_eliminate<CPLX>, dim3(n), dim3(256), 0, n, aug, k)) return r;
   }
+  return 0;
 }
 
 template <int W>
-void launch_transpose(qt_handle_t* h, const double* in, int R, int C, double* out) {
+int launch_transpose(qt_handle_t* h, const double* in, int R, int C, double* out) {
   constexpr int TS = 64 / W;
-  hipLaunchKernelGGL(qt::k_transpose_tiled<W>, dim3((C + TS - 1) / TS, (R + TS - 1) / TS), dim3(256), 0, h->stream, in, R, C, out);
+  return launch(h, qt::k_transpose_tiled<W>, dim3((C + TS - 1) / TS, (R + TS - 1) / TS), dim3(256), 0, in, R, C, out);
 }
 
 // out[cols][rows] = inv(A^T A) A^T of A[rows][cols], real (W = 1) or complex (W = 2; plain transposes, routines.py:69-71):
@@ -505,16 +529,16 @@ int enqueue_left_inverse(qt_handle_t* h, const double* A, int rows, int cols, do
   HIPCHK(h->aug.ensure((size_t)cols * 2 * cols * W * sizeof(double)));
   HIPCHK(h->info.ensure(sizeof(int)));
   double* g = h->aug.as<double>();
-  hipLaunchKernelGGL(qt::k_gemm<CPLX>, dim3((cols + 15) / 16, (cols + 15) / 16), dim3(64), 0, h->stream, cols, cols, rows, A,
-                     cols, 1, A, cols, 0, g, 2 * cols);
-  launch_gauss_jordan<CPLX>(h, cols, g, h->info.as<int>());
-  hipLaunchKernelGGL(qt::k_gemm<CPLX>, dim3((rows + 15) / 16, (cols + 15) / 16), dim3(64), 0, h->stream, cols, rows, cols,
-                     g + (size_t)cols * W, 2 * cols, 0, AT ? AT : A, AT ? rows : cols, AT ? 0 : 1, out, rows);
-  return 0;
+  if (int r = launch(h, qt::k_gemm<CPLX>, dim3((cols + 15) / 16, (cols + 15) / 16), dim3(64), 0, cols, cols, rows, A, cols, 1,
+                     A, cols, 0, g, 2 * cols))
+    return r;
+  if (int r = launch_gauss_jordan<CPLX>(h, cols, g, h->info.as<int>())) return r;
+  return launch(h, qt::k_gemm<CPLX>, dim3((rows + 15) / 16, (cols + 15) / 16), dim3(64), 0, cols, rows, cols,
+                g + (size_t)cols * W, 2 * cols, 0, AT ? AT : A, AT ? rows : cols, AT ? 0 : 1, out, rows);
 }
 
 int need_povm(qt_handle_t* h) {
-  if (!h->povm_set) return fail(QT_ERR_STATE, "qt_set_povm has not been called on this handle");
+  if (!h->povm.registered) return fail(QT_ERR_STATE, "qt_set_povm has not been called on this handle");
   return 0;
 }
 
@@ -555,73 +579,80 @@ int launch_povm_kron(qt_handle_t* h, const double* dtable, int S1, int K1, doubl
   for (int q = 0; q < h->nq; ++q) total *= (size_t)S1 * K1;
   if ((total >> (2 * h->nq)) > ((size_t)1 << 31)) return fail(QT_ERR_UNSUPPORTED, "POVM tensor too large");
   // >> 256 workgroups, each lane a 16-byte store per pass
-  hipLaunchKernelGGL(qt::k_povm_kron, dim3(grid_for(total / 2, 256, 4096)), dim3(256), 0, h->stream, h->nq, dtable, S1 * K1,
-                     h->kron_dig.as<unsigned long long>(), total, dout);
-  return 0;
+  return launch(h, qt::k_povm_kron, dim3(grid_for(total / 2, 256, 4096)), dim3(256), 0, h->nq, dtable, S1 * K1,
+                h->kron_dig.as<unsigned long long>(), total, dout);
 }
 
 // Dense operands A ([M][D]; the Kronecker power of the table for a product POVM), A^T, A', A'^T -- built when first
 // needed: Born kernel / dense estimators at n <= 3, process set-up, the dense left inverse.
 int ensure_dense(qt_handle_t* h) {
-  if (h->dense_ready) return 0;
+  PovmState& pm = h->povm;
+  if (pm.dense_ready) return 0;
   const size_t bytes = (size_t)h->M * h->D * sizeof(double);
-  HIPCHK(h->A.ensure(bytes));
-  HIPCHK(h->AT.ensure(bytes));
-  HIPCHK(h->Aw.ensure(bytes));
-  HIPCHK(h->AwT.ensure(bytes));
-  if (!h->a_loaded) {
-    if (!h->pr_T.p || h->kron_S1 * h->kron_K1 == 0) return fail(QT_ERR_STATE, "no POVM tensor to build the dense operands from");
-    if (int r = launch_povm_kron(h, h->pr_T.as<double>(), h->kron_S1, h->kron_K1, h->A.as<double>())) return r;
-    h->a_loaded = true;
+  HIPCHK(pm.A.ensure(bytes));
+  HIPCHK(pm.AT.ensure(bytes));
+  HIPCHK(pm.Aw.ensure(bytes));
+  HIPCHK(pm.AwT.ensure(bytes));
+  if (!pm.a_loaded) {
+    if (pm.S1 * pm.K1 == 0) return fail(QT_ERR_STATE, "no POVM tensor to build the dense operands from");
+    if (int r = launch_povm_kron(h, pm.T.as<double>(), pm.S1, pm.K1, pm.A.as<double>())) return r;
+    pm.a_loaded = true;
   }
-  hipLaunchKernelGGL(qt::k_povm_setup, dim3((h->D + 63) / 64, (h->M + 63) / 64), dim3(256), 0, h->stream, h->A.as<double>(),
-                     h->Ns.as<double>(), h->ns_tot, h->K, h->M, h->D, h->AT.as<double>(), h->Aw.as<double>(),
-                     h->AwT.as<double>());
+  if (int r = launch(h, qt::k_povm_setup, dim3((h->D + 63) / 64, (h->M + 63) / 64), dim3(256), 0, pm.A.as<double>(),
+                     pm.Ns.as<double>(), pm.ns_tot, h->K, h->M, h->D, pm.AT.as<double>(), pm.Aw.as<double>(), pm.AwT.as<double>()))
+    return r;
   HIPCHK(hipGetLastError());
-  h->dense_ready = true;
+  pm.dense_ready = true;
   return 0;
 }
 
 // Dense left inverse inv(A'^T A') A'^T of the cached weighted POVM.
 int compute_dense_pinv(qt_handle_t* h) {
   if (int r = ensure_dense(h)) return r;
+  PovmState& pm = h->povm;
   const int D = h->D, M = h->M;
   const size_t bytes = (size_t)M * D * sizeof(double);
-  HIPCHK(h->Pinv.ensure(bytes));
-  HIPCHK(h->PinvT.ensure(bytes));
-  if (int r = enqueue_left_inverse<1>(h, h->Aw.as<double>(), M, D, h->Pinv.as<double>(), h->AwT.as<double>())) return r;
-  launch_transpose<1>(h, h->Pinv.as<double>(), D, M, h->PinvT.as<double>());
+  HIPCHK(pm.Pinv.ensure(bytes));
+  HIPCHK(pm.PinvT.ensure(bytes));
+  if (int r = enqueue_left_inverse<1>(h, pm.Aw.as<double>(), M, D, pm.Pinv.as<double>(), pm.AwT.as<double>())) return r;
+  if (int r = launch_transpose<1>(h, pm.Pinv.as<double>(), D, M, pm.PinvT.as<double>())) return r;
   int info = 0;
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "A^T A is singular (no pivot in column %d): POVM not informationally complete", info - 1);
-  h->pinv_ready = true;
+  pm.pinv_ready = true;
   return 0;
 }
 
 // n >= 4: what the launch about to be made reads besides the factorised tables.  A plain tensor (qt_set_povm) has its
 // dense operands and left inverse already; a product POVM with unequal shots needs the dense left inverse for 'lin'.
 int prepare_large(qt_handle_t* h, bool needs_lin) {
-  if (h->prod.enabled && needs_lin && !h->prod.uniform && !h->pinv_ready) return compute_dense_pinv(h);
+  if (h->povm.prod.enabled && needs_lin && !h->povm.prod.uniform && !h->povm.pinv_ready) return compute_dense_pinv(h);
   return 0;
 }
 
-// Start of qt_set_povm / qt_set_povm_product: forget the previous POVM, record the shape.
+// Start of qt_set_povm / qt_set_povm_product: forget the previous POVM and the process set-up on top of it, record the
+// shape.  (The device memory of both stays, for reuse.)
 int begin_povm(qt_handle_t* h, int S, int K) {
   const size_t M = (size_t)S * K;
   if (M < (size_t)h->D) return fail(QT_ERR_SINGULAR, "POVM has %zu rows < D = %d: not informationally complete", M, h->D);
-  h->povm_set = false;
+  h->povm.reset();
   h->proc_set = false;
-  h->dense_ready = h->a_loaded = h->pinv_ready = false;
-  h->prod = qt::ProductView{};
-  h->paired_tables = 0;
-  h->image_ready = false;
   h->S = S;
   h->K = K;
   h->M = (int)M;
-  HIPCHK(h->Ns.ensure(S * sizeof(double)));
+  HIPCHK(h->povm.Ns.ensure(S * sizeof(double)));
   HIPCHK(h->info.ensure(sizeof(int)));
+  return 0;
+}
+
+// buf = v, enqueued on the handle's stream: `v` must outlive the copy
+template <class T>
+int upload(qt_handle_t* h, DevBuf& buf, const std::vector<T>& v) {
+  if (v.empty()) return 0;
+  HIPCHK(buf.ensure(v.size() * sizeof(T)));
+  HIPCHK(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
   return 0;
 }
 
@@ -728,12 +759,12 @@ int mle_iter_cap(const qt_handle_t* h, bool spec, int* cap) {
   size_t base, per_iter;
   const void* kernel;
   if constexpr (NQ == 3) {
-    base = qt::Small<3>::lds_bytes(h->M, h->prod.enabled ? h->prod.R1 : 0, qt::LineSearch::SLOTS);
+    base = qt::Small<3>::lds_bytes(h->M, h->povm.prod.enabled ? h->povm.prod.R1 : 0, qt::LineSearch::SLOTS);
     per_iter = (size_t)qt::Small<3>::TPB * 2 * sizeof(double);
     kernel = spec ? reinterpret_cast<const void*>(mle_split_kernels<3, false>().second)
                   : reinterpret_cast<const void*>(mle_split_kernels<3, true>().second);
   } else {
-    base = qt::Large<NQ>::lds_bytes(h->M, h->prod.R1, 0);
+    base = qt::Large<NQ>::lds_bytes(h->M, h->povm.prod.R1, 0);
     per_iter = 2 * sizeof(double);
     kernel = reinterpret_cast<const void*>(mle_split_kernels<NQ, true>().second);
   }
@@ -810,8 +841,8 @@ int mle_batch_impl(qt_handle_t* h, const int64_t* counts, int B, int init, int m
           // k_mle_fused_hw (the generic body meets its twins at the barrier behind the product POVM's tables) keeps fewer
           // pairs in LDS and a scratch per twin wavefront behind the trials'; where that does not fit, k_mle_fused runs
           const int extra_hw = state + qt::kFusedHwLdsPairs * 2 * h->D;
-          lds_hw = qt::Small<3>::lds_bytes_twin(h->M, h->prod.R1, extra_hw);
-          helper = h->mle_helper_wave && init == QT_INIT_LIN && h->prod.enabled && lds_hw <= kLdsLimit;
+          lds_hw = qt::Small<3>::lds_bytes_twin(h->M, h->povm.prod.R1, extra_hw);
+          helper = h->mle_helper_wave && init == QT_INIT_LIN && h->povm.prod.enabled && lds_hw <= kLdsLimit;
           const int lds_pairs = helper ? qt::kFusedHwLdsPairs : qt::kFusedLdsPairs;
           extra = state + lds_pairs * 2 * h->D;
           const int over = mi > lds_pairs ? mi : 1;  // (indexed by pair number: rows below lds_pairs stay unused)
@@ -915,7 +946,7 @@ int enqueue_factors(qt_handle_t* h, int groups, int info[2]) {
   HIPCHK(hipMemcpyAsync(&info[0], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (int r = enqueue_left_inverse<2>(h, ps.emats.as<double>(), M, D, ps.vp_pinv.as<double>())) return r;
   HIPCHK(hipMemcpyAsync(&info[1], h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  launch_transpose<2>(h, ps.vp_pinv.as<double>(), D, M, ps.vp_pinvT.as<double>());
+  if (int r = launch_transpose<2>(h, ps.vp_pinv.as<double>(), D, M, ps.vp_pinvT.as<double>())) return r;
   if (groups)
     return launch(h, qt::k_vp_perm, dim3(grid_for((size_t)groups * M * 32)), dim3(256), 0, ps.vp_pinvT.as<double>(), M, D, d,
                   groups, ps.vp_perm.as<double>());
@@ -946,7 +977,7 @@ int pgdb64_trial(qt_handle_t* h, const int64_t* counts, int B, const double* cur
 
 // a5 on device arrays, the launches behind qt_born_probs and qt_process_born_probs: p[B][M] from bloch[B][D]
 int born_launch(qt_handle_t* h, const double* din, int B, double* dout) {
-  if (h->nq >= 4 && h->prod.enabled) {  // factorised contraction, one workgroup per state
+  if (h->nq >= 4 && h->povm.prod.enabled) {  // factorised contraction, one workgroup per state
     const Plan pl = h->nq == 4 ? povm_plan<4>(h, B) : povm_plan<5>(h, B);
     return launch(h, h->nq == 4 ? qt::k_born_large<4> : qt::k_born_large<5>, pl, pl.pv, din, B, dout);
   }
@@ -960,15 +991,13 @@ int born_launch(qt_handle_t* h, const double* din, int B, double* dout) {
     int grid = (B + 16 * 16 - 1) / (16 * 16);
     if (grid > 256) grid = 256;
     const auto kern = h->D == 4 ? qt::k_born_mfma<4> : (h->D == 16 ? qt::k_born_mfma<16> : qt::k_born_mfma<64>);
-    if (int r = launch(h, kern, dim3(grid), dim3(1024), at_bytes, h->AT.as<double>(), h->M, Mp, h->d, din, B, dout)) return r;
-  } else {
-    const int TB = h->D <= 256 ? 8 : 4;  // states per workgroup
-    int gy = (B + TB - 1) / TB;
-    if (gy > 2048) gy = 2048;
-    hipLaunchKernelGGL((TB == 8 ? qt::k_born<8> : qt::k_born<4>), dim3(gx, gy), dim3(256), TB * h->D * sizeof(double), h->stream,
-                       h->AT.as<double>(), h->M, h->D, h->d, din, B, dout);
+    return launch(h, kern, dim3(grid), dim3(1024), at_bytes, h->povm.AT.as<double>(), h->M, Mp, h->d, din, B, dout);
   }
-  return 0;
+  const int TB = h->D <= 256 ? 8 : 4;  // states per workgroup
+  int gy = (B + TB - 1) / TB;
+  if (gy > 2048) gy = 2048;
+  return launch(h, TB == 8 ? qt::k_born<8> : qt::k_born<4>, dim3(gx, gy), dim3(256), TB * h->D * sizeof(double),
+                h->povm.AT.as<double>(), h->M, h->D, h->d, din, B, dout);
 }
 
 }  // namespace
@@ -1282,9 +1311,8 @@ void qt_destroy(qt_handle_t* h) {
   if (!h) return;
   DeviceScope scope(h->device);
   (void)hipStreamSynchronize(h->stream);
-  for (DevBuf* b : {&h->pr_T, &h->pr_P1, &h->pr_P1T, &h->pr_wrow, &h->pr_rmap, &h->pr_rinv, &h->pr_fwd, &h->pr_bwd, &h->pr_last})
-    b->release();
-  for (DevBuf* b : {&h->A, &h->AT, &h->Aw, &h->AwT, &h->Pinv, &h->PinvT, &h->Ns, &h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
+  h->povm.release();
+  for (DevBuf* b : {&h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
                     &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
     b->release();
   for (DevBuf& b : h->stage) b.release();
@@ -1337,7 +1365,7 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
 
 int qt_get_paired_tables(qt_handle_t* h) {
   QT_ENTER(h);
-  return h->povm_set && h->prod.enabled ? h->paired_tables : 0;
+  return h->povm.registered && h->povm.prod.enabled ? h->povm.paired_tables : 0;
 }
 
 int qt_get_mle_specialised(qt_handle_t* h) {
@@ -1412,18 +1440,18 @@ int qt_set_povm(qt_handle_t* h, const double* A, int S, int K, const double* Ns,
   Call c(h, flags);
   if (!A || !Ns || S < 1 || K < 1) return fail(QT_ERR_ARG, "bad set_povm arguments");
   if (int r = begin_povm(h, S, K)) return r;
-  HIPCHK(h->A.ensure((size_t)S * K * h->D * sizeof(double)));
-  if (int r = c.copy_in(h->A.as<double>(), A, (size_t)S * K * h->D)) return r;
-  if (int r = c.copy_in(h->Ns.as<double>(), Ns, (size_t)S)) return r;
-  h->a_loaded = true;
+  PovmState& pm = h->povm;
+  HIPCHK(pm.A.ensure((size_t)S * K * h->D * sizeof(double)));
+  if (int r = c.copy_in(pm.A.as<double>(), A, (size_t)S * K * h->D)) return r;
+  if (int r = c.copy_in(pm.Ns.as<double>(), Ns, (size_t)S)) return r;
+  pm.a_loaded = true;
   {
     std::vector<double> ns;
     if (int r = c.read(ns, Ns, (size_t)S)) return r;
-    h->ns_tot = 0.0;
-    for (double v : ns) h->ns_tot += v;
+    for (double v : ns) pm.ns_tot += v;
   }
   if (int r = compute_dense_pinv(h)) return r;  // a plain tensor: the dense operands ARE the POVM
-  h->povm_set = true;
+  pm.registered = true;
   return 0;
 }
 
@@ -1431,156 +1459,79 @@ int qt_set_povm_product(qt_handle_t* h, const double* povm1, int S1, int K1, con
   QT_ENTER(h);
   Call c(h, flags);
   if (!povm1 || !Ns || S1 < 1 || K1 < 1) return fail(QT_ERR_ARG, "bad set_povm_product arguments");
-  const int n = h->nq, R1 = S1 * K1;
-  long long S = 1, K = 1, M = 1;
-  for (int q = 0; q < n; ++q) {
-    S *= S1;
-    K *= K1;
-    M *= R1;
-  }
-  if (M > (1 << 15)) return fail(QT_ERR_UNSUPPORTED, "product POVM with %lld rows is too large", M);
-  if (R1 > 255) return fail(QT_ERR_UNSUPPORTED, "one-qubit table with %d rows (> 255)", R1);
-  if (int r = begin_povm(h, (int)S, (int)K)) return r;
-  // host copies of the small inputs (table and shots) for the index tables
+  const int n = h->nq;
+  auto refused = [](qt::TablesStatus st, const qt::ProductShape& sh) {
+    if (st == qt::TABLES_ROWS) return fail(QT_ERR_UNSUPPORTED, "product POVM with %lld rows is too large", sh.M);
+    return fail(QT_ERR_UNSUPPORTED, "one-qubit table with %lld rows (> 255)", sh.R1);
+  };
+  qt::ProductTables tb;
+  if (qt::TablesStatus st = qt::product_shape(n, S1, K1, &tb.shape)) return refused(st, tb.shape);
+  const int R1 = (int)tb.shape.R1;
+  if (int r = begin_povm(h, (int)tb.shape.S, (int)tb.shape.K)) return r;
+  PovmState& pm = h->povm;
+  // host copies of the small inputs (table and shots), and the index tables from them
   std::vector<double> t1, ns;
   if (int r = c.read(t1, povm1, (size_t)R1 * 4)) return r;
-  if (int r = c.read(ns, Ns, (size_t)S)) return r;
-  HIPCHK(h->pr_T.ensure(t1.size() * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(h->pr_T.p, t1.data(), t1.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->Ns.p, ns.data(), ns.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  double tot = 0.0;
-  bool uniform = true;
-  for (long long s = 0; s < S; ++s) {
-    tot += ns[s];
-    if (ns[s] != ns[0]) uniform = false;
-  }
-  h->ns_tot = tot;
-  if (int r = ensure_kron_digits(h, S1, K1)) return r;
+  if (int r = c.read(ns, Ns, (size_t)tb.shape.S)) return r;
+  if (qt::TablesStatus st = qt::build_product_tables(n, S1, K1, ns.data(), t1.data(), &tb)) return refused(st, tb.shape);
+  if (int r = upload(h, pm.T, t1)) return r;
+  if (int r = upload(h, pm.Ns, ns)) return r;
+  pm.ns_tot = tb.tot;
+  pm.ns_max = tb.ns_max;
+  pm.S1 = S1;
+  pm.K1 = K1;
   // The dense operands (a2 tensor + transposes; Born GEMM, dense fallbacks, process set-up) are cheap at n <= 3 and
   // built now; at n = 4, 5 (6 x 64 MB at n = 5) the factorised estimators never read them: on demand only.
   // The dense left inverse is needed by 'lin' when the shots differ between settings (n <= 3).
   if (n <= 3) {
-    if (int r = uniform ? ensure_dense(h) : compute_dense_pinv(h)) return r;
+    if (int r = tb.uniform ? ensure_dense(h) : compute_dense_pinv(h)) return r;
   }
   // pinv of the one-qubit table, on the device: inv(T^T T) T^T  ([4][R1]) and its transpose
-  HIPCHK(h->pr_P1.ensure((size_t)4 * R1 * sizeof(double)));
-  HIPCHK(h->pr_P1T.ensure((size_t)4 * R1 * sizeof(double)));
-  if (int r = enqueue_left_inverse<1>(h, h->pr_T.as<double>(), R1, 4, h->pr_P1.as<double>())) return r;
-  launch_transpose<1>(h, h->pr_P1.as<double>(), 4, R1, h->pr_P1T.as<double>());
-  // host-side index bookkeeping: R-order row map, shot weights, stage tables
-  std::vector<int> rmap((size_t)M), fwd, bwd;
-  std::vector<double> wrow((size_t)M);
-  for (long long mr = 0; mr < M; ++mr) {  // mr = [r_1 .. r_n], r_q = s_q K1 + o_q
-    long long rem = mr, s = 0, o = 0, sp = 1, op = 1;
-    for (int q = n - 1; q >= 0; --q) {
-      const int r = (int)(rem % R1);
-      rem /= R1;
-      s += (r / K1) * sp;
-      o += (r % K1) * op;
-      sp *= S1;
-      op *= K1;
-    }
-    rmap[mr] = (int)(s * K + o);
-    wrow[mr] = ns[s] / tot;
-  }
-  auto ipow = [](long long b, int e) {
-    long long r = 1;
-    for (int i = 0; i < e; ++i) r *= b;
-    return r;
-  };
-  for (int q = 1; q <= n; ++q) {  // forward stage q: out[r_1..r_q][k_(q+1)..k_n]
-    const long long Kq = ipow(4, n - q), n_out = ipow(R1, q) * Kq;
-    for (long long o = 0; o < n_out; ++o) {
-      const long long rpre = o / (R1 * Kq), rq = (o / Kq) % R1, krest = o % Kq;
-      fwd.push_back((int)((rpre * 4 * Kq + krest) | (rq << 16)));
-    }
-  }
-  for (int q = n; q >= 1; --q) {  // backward stage q: out[r_1..r_(q-1)][k_q..k_n]
-    const long long Kq = ipow(4, n - q), n_out = ipow(R1, q - 1) * 4 * Kq;
-    for (long long o = 0; o < n_out; ++o) {
-      const long long rpre = o / (4 * Kq), kq = (o / Kq) % 4, krest = o % Kq;
-      bwd.push_back((int)((rpre * R1 * Kq + krest) | (kq << 16)));
-    }
-  }
-  std::vector<int> rinv((size_t)M);
-  for (long long mr = 0; mr < M; ++mr) rinv[(size_t)rmap[mr]] = (int)mr;
-  HIPCHK(h->pr_rinv.ensure(rinv.size() * sizeof(int)));
-  HIPCHK(hipMemcpyAsync(h->pr_rinv.p, rinv.data(), rinv.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h->pr_rmap.ensure(rmap.size() * sizeof(int)));
-  HIPCHK(h->pr_wrow.ensure(wrow.size() * sizeof(double)));
-  HIPCHK(h->pr_fwd.ensure(fwd.size() * sizeof(int)));
-  HIPCHK(h->pr_bwd.ensure(bwd.size() * sizeof(int)));
-  HIPCHK(hipMemcpyAsync(h->pr_rmap.p, rmap.data(), rmap.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->pr_wrow.p, wrow.data(), wrow.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->pr_fwd.p, fwd.data(), fwd.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->pr_bwd.p, bwd.data(), bwd.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  // A paired table (ProductView::pairedT) at n <= 3: the entries of forward stage n, row by row in R-order
-  // (in0 = 4 r_pre, axis = in0 + a + 1, and the place 4 r + a + 1 of v_r in the table).  pinv(T)^T is classified
-  // below on the values the kernels read, i.e. on the device's result, with no tolerance.
-  const bool try_paired = n <= 3 && R1 == 6;
-  auto is_paired = [](const double* tab) {  // [6][4]
-    for (int r = 0; r < 6; ++r)
-      for (int k = 1; k < 4; ++k)
-        if (k != r / 2 + 1 && tab[r * 4 + k] != 0.0) return false;
-    return true;
-  };
-  const bool pairedT = try_paired && is_paired(t1.data());
-  if (pairedT) {
-    std::vector<int> last((size_t)M);
-    for (long long o = 0; o < M; ++o) {
-      const int rpre = (int)(o / 6), r = (int)(o % 6), a = r / 2;
-      last[(size_t)o] = (4 * rpre) | (4 * rpre + a + 1) << 8 | (4 * r + a + 1) << 16;
-    }
-    HIPCHK(h->pr_last.ensure(last.size() * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(h->pr_last.p, last.data(), last.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  }
+  HIPCHK(pm.P1.ensure((size_t)4 * R1 * sizeof(double)));
+  HIPCHK(pm.P1T.ensure((size_t)4 * R1 * sizeof(double)));
+  if (int r = enqueue_left_inverse<1>(h, pm.T.as<double>(), R1, 4, pm.P1.as<double>())) return r;
+  if (int r = launch_transpose<1>(h, pm.P1.as<double>(), 4, R1, pm.P1T.as<double>())) return r;
+  if (int r = upload(h, pm.rinv, tb.rinv)) return r;
+  if (int r = upload(h, pm.rmap, tb.rmap)) return r;
+  if (int r = upload(h, pm.wrow, tb.wrow)) return r;
+  if (int r = upload(h, pm.fwd, tb.fwd)) return r;
+  if (int r = upload(h, pm.bwd, tb.bwd)) return r;
+  if (int r = upload(h, pm.last, tb.last)) return r;
+  // The pivot report and, for the shape that has paired stages, pinv(T)^T: it is classified on the values the kernels
+  // read, i.e. on the device's result.
   int info = 0;
   double p1t[24] = {};
   HIPCHK(hipMemcpyAsync(&info, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (try_paired) HIPCHK(hipMemcpyAsync(p1t, h->pr_P1T.p, sizeof(p1t), hipMemcpyDeviceToHost, h->stream));
+  if (tb.try_paired) HIPCHK(hipMemcpyAsync(p1t, pm.P1T.p, sizeof(p1t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   if (info != 0) return fail(QT_ERR_SINGULAR, "the one-qubit table is not informationally complete");
-  const bool pairedP = try_paired && is_paired(p1t);
-  for (int r = 0; r < 6 && try_paired; ++r) {
-    h->prod.cT[2 * r] = t1[r * 4];
-    h->prod.cT[2 * r + 1] = t1[r * 4 + r / 2 + 1];
-    h->prod.cP[2 * r] = p1t[r * 4];
-    h->prod.cP[2 * r + 1] = p1t[r * 4 + r / 2 + 1];
-  }
-  h->prod.last = h->pr_last.as<int>();
-  h->paired_tables = (pairedT ? 1 : 0) | (pairedP ? 2 : 0);
-  if (pairedT && pairedP && K == (1 << n)) {
-    // The table image of the specialised MLE kernels (qt::SpecArgs::image): the workgroup's LDS table block in its
-    // final layout -- `last` padded to four entries, T, pinv(T)^T as the device computed it -- and rinv behind it.
-    const int nl = (int)((M + 3) & ~3LL);
-    std::vector<int> image((size_t)nl + 2 * 48 + (size_t)M, 0);
-    for (long long o = 0; o < M; ++o) {
-      const int rpre = (int)(o / 6), r = (int)(o % 6), a = r / 2;
-      image[(size_t)o] = (4 * rpre) | (4 * rpre + a + 1) << 8 | (4 * r + a + 1) << 16;
+  qt::ProductView pv{};
+  pv.T = pm.T.as<double>();
+  pv.P1T = pm.P1T.as<double>();
+  pv.wrowR = pm.wrow.as<double>();
+  pv.rmap = pm.rmap.as<int>();
+  pv.rinv = pm.rinv.as<int>();
+  pv.fwd = pm.fwd.as<int>();
+  pv.bwd = pm.bwd.as<int>();
+  pv.last = pm.last.as<int>();
+  pv.R1 = R1;
+  pv.uniform = tb.uniform ? 1 : 0;
+  pv.wuni = tb.wuni;
+  pv.enabled = 1;
+  if (tb.try_paired) {
+    const qt::PairedTables pt = qt::classify_paired(tb, p1t);
+    memcpy(pv.cT, pt.cT, sizeof pv.cT);
+    memcpy(pv.cP, pt.cP, sizeof pv.cP);
+    pm.paired_tables = (tb.pairedT ? 1 : 0) | (pt.pairedP ? 2 : 0);
+    if (!pt.image.empty()) {
+      if (int r = upload(h, pm.image, pt.image)) return r;
+      HIPCHK(hipStreamSynchronize(h->stream));  // `pt` goes out of scope
+      pm.image_ready = true;
     }
-    memcpy(image.data() + nl, t1.data(), 24 * sizeof(double));
-    memcpy(image.data() + nl + 48, p1t, 24 * sizeof(double));
-    memcpy(image.data() + nl + 96, rinv.data(), (size_t)M * sizeof(int));
-    HIPCHK(h->pr_image.ensure(image.size() * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(h->pr_image.p, image.data(), image.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->image_ready = true;
   }
-  h->prod.T = h->pr_T.as<double>();
-  h->prod.P1T = h->pr_P1T.as<double>();
-  h->prod.wrowR = h->pr_wrow.as<double>();
-  h->prod.rmap = h->pr_rmap.as<int>();
-  h->prod.rinv = h->pr_rinv.as<int>();
-  h->ns_max = 0.0;
-  for (double v : ns) h->ns_max = v > h->ns_max ? v : h->ns_max;
-  h->prod.fwd = h->pr_fwd.as<int>();
-  h->prod.bwd = h->pr_bwd.as<int>();
-  h->prod.R1 = R1;
-  h->prod.uniform = uniform ? 1 : 0;
-  h->prod.wuni = ns[0] / tot;
-  h->prod.enabled = 1;
-  h->povm_set = true;
+  pm.prod = pv;
+  pm.registered = true;
   return 0;
 }
 
@@ -1589,9 +1540,9 @@ int qt_get_left_inverse(qt_handle_t* h, double* out, int flags) {
   Call c(h, flags);
   if (int r = need_povm(h)) return r;
   if (!out) return fail(QT_ERR_ARG, "null out");
-  if (!h->pinv_ready)
+  if (!h->povm.pinv_ready)
     if (int r = compute_dense_pinv(h)) return r;
-  if (int r = c.copy_out(out, h->Pinv.as<double>(), (size_t)h->D * h->M)) return r;
+  if (int r = c.copy_out(out, h->povm.Pinv.as<double>(), (size_t)h->D * h->M)) return r;
   return c.done();
 }
 
@@ -2426,7 +2377,7 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
   HIPCHK(ps.emats.ensure((size_t)M * D * 2 * sizeof(double)));
   if (int r = c.copy_in(ps.in_states.as<double>(), in_states, (size_t)D * D * 2)) return r;
   // E_m = sum_k A'[m][k] P_k  (process.py:204: Qobj(povm_bloch).matrix)
-  if (int r = launch(h, qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->nq, h->Aw.as<double>(), M,
+  if (int r = launch(h, qt::k_mat_from_bloch, dim3(grid_for((size_t)M * D)), dim3(256), 0, h->nq, h->povm.Aw.as<double>(), M,
                      ps.emats.as<double>()))
     return r;
   // n = 3 keeps the Kronecker-factored design matrix only (qt_process64.h): L = (V_S (x) V_P) Pi^T, L^+ = Pi (V_S^+ (x) V_P^+).
@@ -2444,7 +2395,7 @@ int qt_process_setup(qt_handle_t* h, const double* in_states, int flags) {
                        ps.emats.as<double>(), lifp))
       return r;
     if (int r = enqueue_left_inverse<2>(h, lifp, (int)R, (int)C2, pinv)) return r;
-    launch_transpose<2>(h, pinv, (int)C2, (int)R, pinvT);
+    if (int r = launch_transpose<2>(h, pinv, (int)C2, (int)R, pinvT)) return r;
     if (h->nq == 2) {  // the batched GEMM of qt_lifp_batch reads the left inverse in row-major Choi order
       HIPCHK(ps.pinvR.ensure(R * C2 * 2 * sizeof(double)));
       if (int r = launch(h, qt::k_choi_order_rows, dim3(grid_for(R * C2)), dim3(256), 0, pinvT, R, D, ps.pinvR.as<double>()))
