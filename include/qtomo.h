@@ -252,6 +252,22 @@ int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* cen
 enum qt_metric { QT_METRIC_TRACE = 0, QT_METRIC_INFIDELITY = 1 };
 int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, int B, const double* centres, int G, int g0,
                                double* dist, int flags);
+/* ---- the same (quantpy/geometry.py:23-38 trace_dst, :41-56 if_dst) for dim x dim matrices on ANY handle ------------
+ * dist[b] = metric(rho_b, centres[(g0 + b) % G]); rho[B][dim][dim][2], centres[G][dim][dim][2], whatever the handle's
+ * n_qubits (as qt_hs_dist_dim); needs no POVM.
+ *   dim = 2, 4, 8   the kernels of qt_metric_dist_group_batch: the same bits as that entry on a handle of that size
+ *   dim = 16, 32    four- and five-qubit states, the Choi matrix of a two-qubit channel: one workgroup per trial, the same
+ *                   Jacobi sweeps (at most 32 of them instead of 20) and the same formulas, element for element
+ *   any other dim   QT_ERR_UNSUPPORTED (supported: 2, 4, 8, 16, 32; a three-qubit Choi matrix is dim = 64)
+ * Both arguments are taken to be HERMITIAN, exactly as above: the imaginary parts of the diagonals are dropped, the trace
+ * distance is sum_i |lambda_i(rho_b - centre)| / 2, the infidelity 1 - (sum_i sqrt(max(mu_i, 0)))^2 with mu the
+ * eigenvalues of the Hermitian part of S rho_b S, S = the clipped Hermitian root of the centre, formed once per call and
+ * centre.  A value below 1e-15 -- small negative infidelities included -- is returned as 0.  A NaN (or an infinity) in
+ * rho_b or in its centre gives dist[b] = NaN and touches no other trial; a trial's bits depend on its two matrices
+ * alone, not on B, G, g0 or its place in the batch.
+ * QT_ERR_ARG: an unknown metric, G < 1, g0 outside [0, G), B < 0, a null array with B > 0.  B == 0 returns 0. */
+int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
+                       double* dist, int flags);
 
 /* ---- a16: quantpy/tomography/interval.py:610-612 (and :683-685) -------------------------------- */
 /* `dist.sort()`: ascending in-place sort of n float64 values in np.sort's order (NaN last; bitonic in LDS up to 8192

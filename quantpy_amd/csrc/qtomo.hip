@@ -19,6 +19,7 @@
 #include "qt_large.h"
 #include "qt_lp.h"
 #include "qt_lp_large.h"
+#include "qt_metric_dim.h"
 #include "qt_mhmc_state.h"
 #include "qt_mle_small.h"
 #include "qt_ops.h"
@@ -179,7 +180,7 @@ struct qt_handle {
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
-  DevBuf metric_ws;  // qt_metric_dist_group_batch, infidelity: the Hermitian roots of the call's G centres
+  DevBuf metric_ws;  // qt_metric_dist_group_batch / qt_metric_dist_dim, infidelity: the Hermitian roots of the call's G centres
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -1255,6 +1256,34 @@ int lifp_batch_impl(qt_handle_t* h, bool with_dist, const int64_t* counts, int B
   return c.done(status, B);
 }
 
+// dist[b] = metric(rho[b], centre (g0 + b) % G) for 2^NQ x 2^NQ matrices, NQ <= 3, all pointers on the device
+// (k_metric_dist; the infidelity's roots of the centres by k_psd_sqrt into metric_ws, once per call)
+template <int NQ>
+int metric_small(qt_handle_t* h, int metric, const double* dr, int B, const double* dcn, int G, int g0, double* dd) {
+  using S = qt::Small<NQ>;
+  const dim3 grid((B + S::TPB - 1) / S::TPB), block(S::NT);
+  if (metric == QT_METRIC_TRACE)
+    return launch(h, qt::k_metric_dist<NQ, qt::kMetricTrace>, grid, block, 0, dr, B, dcn, G, g0, h->jtol2, dd);
+  HIPCHK(h->metric_ws.ensure((size_t)G * S::D * 2 * sizeof(double)));
+  double* roots = h->metric_ws.as<double>();
+  if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((G + S::TPB - 1) / S::TPB), block, 0, dcn, G, h->jtol2, roots)) return r;
+  return launch(h, qt::k_metric_dist<NQ, qt::kMetricInfidelity>, grid, block, 0, dr, B, static_cast<const double*>(roots), G,
+                g0, h->jtol2, dd);
+}
+
+// The same for DIM = 16, 32: one workgroup of DIM^2 threads per trial and per centre (k_metric_dist_dim, k_psd_sqrt_dim)
+template <int DIM>
+int metric_dim(qt_handle_t* h, int metric, const double* dr, int B, const double* dcn, int G, int g0, double* dd) {
+  const dim3 block(DIM * DIM);
+  if (metric == QT_METRIC_TRACE)
+    return launch(h, qt::k_metric_dist_dim<DIM, qt::kMetricTrace>, dim3(B), block, 0, dr, B, dcn, G, g0, h->jtol2, dd);
+  HIPCHK(h->metric_ws.ensure((size_t)G * DIM * DIM * 2 * sizeof(double)));
+  double* roots = h->metric_ws.as<double>();
+  if (int r = launch(h, qt::k_psd_sqrt_dim<DIM>, dim3(G), block, 0, dcn, G, h->jtol2, roots)) return r;
+  return launch(h, qt::k_metric_dist_dim<DIM, qt::kMetricInfidelity>, dim3(B), block, 0, dr, B,
+                static_cast<const double*>(roots), G, g0, h->jtol2, dd);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1856,24 +1885,46 @@ int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, in
   if (int r = c.in(rho, (size_t)B * ne2, &dr)) return r;
   if (int r = c.in(centres, (size_t)G * ne2, &dcn)) return r;
   if (int r = c.out(dist, (size_t)B, &dd)) return r;
-  if (metric == QT_METRIC_INFIDELITY) HIPCHK(h->metric_ws.ensure((size_t)G * ne2 * sizeof(double)));
   if (int r = by_nq(h, [&](auto nq) {
         constexpr int NQ = decltype(nq)::value;
         if constexpr (NQ <= 3) {
-          using S = qt::Small<NQ>;
-          const dim3 grid((B + S::TPB - 1) / S::TPB), block(S::NT);
-          if (metric == QT_METRIC_TRACE)
-            return launch(h, qt::k_metric_dist<NQ, qt::kMetricTrace>, grid, block, 0, dr, B, dcn, G, g0, h->jtol2, dd);
-          double* roots = h->metric_ws.as<double>();
-          if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((G + S::TPB - 1) / S::TPB), block, 0, dcn, G, h->jtol2, roots))
-            return r;
-          return launch(h, qt::k_metric_dist<NQ, qt::kMetricInfidelity>, grid, block, 0, dr, B,
-                        static_cast<const double*>(roots), G, g0, h->jtol2, dd);
+          return metric_small<NQ>(h, metric, dr, B, dcn, G, g0, dd);
         } else {
           return fail(QT_ERR_UNSUPPORTED, "n_qubits %d", NQ);
         }
       }))
     return r;
+  return c.done();
+}
+
+// The same for dim x dim matrices on any handle, whatever its n_qubits: dim 2, 4, 8 by the kernels above (the same bits),
+// dim 16, 32 by one workgroup per trial (qt_metric_dim.h).  Reads no POVM.
+int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
+                       double* dist, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
+    return fail(QT_ERR_ARG, "qt_metric_dist_dim: unknown metric %d", metric);
+  if (dim != 2 && dim != 4 && dim != 8 && dim != 16 && dim != 32)
+    return fail(QT_ERR_UNSUPPORTED, "qt_metric_dist_dim: dim %d (supported: 2, 4, 8, 16, 32)", dim);
+  if (B < 0 || G < 1 || g0 < 0 || g0 >= G || (B > 0 && (!rho || !centres || !dist)))
+    return fail(QT_ERR_ARG, "bad metric_dist_dim arguments (B = %d, G = %d, g0 = %d)", B, G, g0);
+  if (B == 0) return 0;
+  const double *dr, *dcn;
+  double* dd;
+  const size_t ne2 = (size_t)dim * dim * 2;
+  if (int r = c.in(rho, (size_t)B * ne2, &dr)) return r;
+  if (int r = c.in(centres, (size_t)G * ne2, &dcn)) return r;
+  if (int r = c.out(dist, (size_t)B, &dd)) return r;
+  int r = 0;
+  switch (dim) {
+    case 2: r = metric_small<1>(h, metric, dr, B, dcn, G, g0, dd); break;
+    case 4: r = metric_small<2>(h, metric, dr, B, dcn, G, g0, dd); break;
+    case 8: r = metric_small<3>(h, metric, dr, B, dcn, G, g0, dd); break;
+    case 16: r = metric_dim<16>(h, metric, dr, B, dcn, G, g0, dd); break;
+    default: r = metric_dim<32>(h, metric, dr, B, dcn, G, g0, dd); break;
+  }
+  if (r) return r;
   return c.done();
 }
 

@@ -870,6 +870,30 @@ class Engine:
                                                       centre.shape[0] if centre.dim() == 3 else 1, int(g0), _ptr(dist),
                                                       _capi.QT_DEVICE_PTR))
 
+    def metric_dist_dim(self, rho, centre, metric, g0=0):
+        """`metric_dist` for dim x dim matrices whatever this engine's n_qubits, dim = rho.shape[-1] in (2, 4, 8, 16, 32)
+        (qt_metric_dist_dim; needs no POVM): four- and five-qubit states, the Choi matrix of a two-qubit channel.  rho
+        (B, dim, dim) or (dim, dim); centre (dim, dim), or a table (G, dim, dim): trial b is then measured against
+        centre[(g0 + b) % G].  -> (B,) float64, or a float for a single matrix."""
+        code = self._metric_code(metric)
+        rho, cen = _c128(rho), _c128(centre)
+        single = rho.ndim == 2
+        dim = rho.shape[-1]
+        r = rho.reshape(-1, dim, dim)
+        assert cen.shape[-2:] == (dim, dim) and cen.ndim in (2, 3)
+        out = np.empty(r.shape[0])
+        self._chk(self.lib.qt_metric_dist_dim(self._h, code, dim, _ptr(r), r.shape[0], _ptr(cen),
+                                              cen.shape[0] if cen.ndim == 3 else 1, int(g0), _ptr(out), _capi.QT_HOST_PTR))
+        return out[0] if single else out
+
+    def metric_dist_dim_dev(self, rho, centre, dist, metric, g0=0):
+        """device-pointer form: rho complex128 (B, dim, dim), centre complex128 (dim, dim) or (G, dim, dim), dist float64
+        (B,) torch CUDA tensors"""
+        code = self._metric_code(metric)
+        self._dev_call()
+        self._chk(self.lib.qt_metric_dist_dim(self._h, code, rho.shape[-1], _ptr(rho), rho.shape[0], _ptr(centre),
+                                              centre.shape[0] if centre.dim() == 3 else 1, int(g0), _ptr(dist),
+                                              _capi.QT_DEVICE_PTR))
 
     def sort_quantiles(self, dist, conf_levels):
         """interval.py:610-612 on the device: sort `dist` (NumPy array: a sorted copy is returned; torch CUDA

@@ -14,7 +14,8 @@ resamples and writes its distances, and `qt_group_hits` adds, per trial, how man
 to the truth.  Counts and distances never leave HBM; 8 * n_iter bytes come back.
 
 `get_CL_list_state_boot(dst='hs' | 'trace' | 'if')` is that study in any of the three distances: for the trace distance and
-the infidelity a chunk's estimates stay in a device workspace and `qt_metric_dist_group_batch` measures them.
+the infidelity a chunk's estimates stay in a device workspace and `qt_metric_dist_group_batch` (n <= 3) /
+`qt_metric_dist_dim` (n = 4, 5) measures them.
 
 interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with the same rule.
 
@@ -167,19 +168,18 @@ def get_CL_list_state_boot(state, n_iter=1000, n_points=1000, n_measurements=100
     measures them (metrics.py:125-144 with the tomograph's dst).  (`get_CL_list_state` keeps its refusal of the other
     two; this is the study's name.)
 
-    dst='hs' IS `get_CL_list_state(interval='boot')`: the same call, the same bits.  With 'trace' / 'if' (n <= 3) the
+    dst='hs' IS `get_CL_list_state(interval='boot')`: the same call, the same bits.  With 'trace' / 'if' the
     chunk's grouped reconstruction writes its density matrices into a device workspace (`Engine.lin_dev` / `mle_dev`),
-    `Engine.metric_dist_dev` measures resample r of trial t against estimate t (the table of the n_iter estimates,
-    trial b against centre b % n_iter), and `group_hits` counts as before: counts, matrices and distances stay in HBM.
-    The distances are those of Hermitian arguments by the engine's Jacobi sweeps (include/qtomo.h:
-    qt_metric_dist_group_batch), within 1e-7 (trace) / 1e-6 (infidelity) of `trace_dst` / `if_dst` on the host."""
+    `Engine.metric_dist_dev` (n <= 3) / `metric_dist_dim_dev` (n = 4, 5) measures resample r of trial t against
+    estimate t (the table of the n_iter estimates, trial b against centre b % n_iter), and `group_hits` counts as
+    before: counts, matrices and distances stay in HBM.  The distances are those of Hermitian arguments by the engine's Jacobi sweeps
+    (include/qtomo.h: qt_metric_dist_group_batch, qt_metric_dist_dim), within 1e-7 (trace) / 1e-6 (infidelity) of
+    `trace_dst` / `if_dst` on the host."""
     metric = _distance_name(dst)
     if metric == "hs":
         return get_CL_list_state(state, n_iter, n_points, "boot", n_measurements, method, method_boot, "hs", povm, physical,
                                  init, tol, max_iter, sampler=sampler, seed=seed, chunk=chunk, return_details=return_details)
     _check_arguments("boot", "hs", n_iter, n_points, sampler, ("lin", "mle"), method_boot)
-    if state.n_qubits > 3:
-        raise NotImplementedError(f"dst={metric!r} is supported up to three qubits")
     n_iter, n_points = int(n_iter), int(n_points)
     tmg = StateTomograph(state, "hs")
     counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
@@ -187,7 +187,7 @@ def get_CL_list_state_boot(state, n_iter=1000, n_points=1000, n_measurements=100
     if info is not None and np.any(info["status"] == 1):
         raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
     eng = tmg._engine()
-    delta = eng.metric_dist(rho, state.matrix, metric)
+    delta = (eng.metric_dist if eng.d <= 8 else eng.metric_dist_dim)(rho, state.matrix, metric)
     key = (base + 1) & (2**64 - 1)
     hits = _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk, metric)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
@@ -260,8 +260,8 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
 def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk, metric=None):
     """hits[t] = #{ r < n_points : delta_t > hs_dst(estimate(resample r of trial t), estimate_t) }, this rank's shard of
     the resamples chunk by chunk on the device, summed over the ranks.  `metric` = 'trace' / 'if': that distance in the
-    place of hs_dst, formed by `metric_dist_dev` from the chunk's density matrices (one workspace, the first chunk's
-    size; a chunk starts at a whole resample, so its first row meets centre 0)."""
+    place of hs_dst, formed by `metric_dist_dev` (n = 4, 5: `metric_dist_dim_dev`) from the chunk's density matrices (one
+    workspace, the first chunk's size; a chunk starts at a whole resample, so its first row meets centre 0)."""
     import torch
 
     from . import _capi
@@ -279,7 +279,7 @@ def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init,
                 eng.lin_dev(counts, mats, physical=physical, status=status)
             else:
                 eng.mle_dev(counts, mats, init=init, max_iter=max_iter, tol=tol, status=status)
-            eng.metric_dist_dev(mats, centres, dist, metric)
+            (eng.metric_dist_dev if eng.d <= 8 else eng.metric_dist_dim_dev)(mats, centres, dist, metric)
         elif method_boot == "lin":
             eng.lin_dist_dev(counts, centres, dist, physical=physical, status=status)
         else:
