@@ -407,6 +407,27 @@ int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, ui
 int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
                        const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
                        int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags);
+/* The same chains with the kept states measured in trace distance or infidelity (geometry.py:23-38, :41-56): every
+ * argument as in qt_mhmc_state_hits, `metric` behind the handle as in qt_metric_dist_*.  The chain, its Philox keying and
+ * the kept-step rule are the device functions of qt_mhmc_state_hits: for the same (seed, first_chain, counts, x_init)
+ * accepted[] is bit-identical to that entry's.  The distance of a kept state is the value qt_metric_dist_group_batch
+ * returns for unparam(x) (L L^dagger as qt_chol_unparam forms it) and centres[i], by the same device functions:
+ *   both arguments taken as HERMITIAN, the imaginary parts of the diagonals dropped,
+ *   QT_METRIC_TRACE       sum_k |lambda_k(R - C)| / 2,
+ *   QT_METRIC_INFIDELITY  1 - (sum_k sqrt(max(mu_k, 0)))^2, mu the eigenvalues of the Hermitian part of S R S, S the
+ *                         clipped Hermitian root of the centre (the roots of the C centres are made once per call, by the
+ *                         set-up kernel of qt_metric_dist_group_batch into its workspace: the same root bits),
+ *   a value below 1e-15 returned as 0; a NaN or infinity in centres[i] gives NaN distances, which never count as hits
+ *   (hits[i] = 0), and touches no other chain.
+ * A chain's bits depend on its own inputs and its global chain index alone: not on C or its place in the batch.
+ * hits[i] = #{ kept : thresholds[i] > distance } (strict); accepted, dist NULLABLE as above.
+ * QT_ERR_ARG: everything qt_mhmc_state_hits refuses, and a metric other than QT_METRIC_TRACE / QT_METRIC_INFIDELITY (the
+ * Hilbert-Schmidt distance stays with qt_mhmc_state_hits); n = 4, 5: QT_ERR_UNSUPPORTED before any launch; C = 0 returns 0
+ * without a launch. */
+int qt_mhmc_state_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                              const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                              int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                              double* dist, int flags);
 
 /* ---- a11-a15: quantpy/tomography/process.py -------------------------------------------------- */
 /* Process tomography of an n-qubit channel (handle created with n_qubits = n; n <= 3: 'lifp', the projections and
@@ -501,6 +522,29 @@ int qt_mhmc_process_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, i
 int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
                          const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
                          int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags);
+/* The same chains with the REAL PART of the kept points measured in trace distance or infidelity (geometry.py:23-38,
+ * :41-56): every argument as in qt_mhmc_process_hits, `metric` behind the handle as in qt_metric_dist_*.  The chain, its
+ * Philox keying and the kept-step rule are the device functions of qt_mhmc_process_hits: for the same (seed, first_chain,
+ * counts, choi_init) accepted[] is bit-identical to that entry's.  The distance of a kept point X is the value
+ * qt_metric_dist_dim returns at dim = D = 4^n for Re(X) and centres[i], by the same device functions:
+ *   both arguments taken as HERMITIAN, the imaginary parts of the diagonals dropped,
+ *   QT_METRIC_TRACE       sum_k |lambda_k(Re(X) - C)| / 2,
+ *   QT_METRIC_INFIDELITY  1 - (sum_k sqrt(max(mu_k, 0)))^2, mu the eigenvalues of the Hermitian part of S Re(X) S, S the
+ *                         clipped Hermitian root of the centre (made once per call by the set-up kernel of
+ *                         qt_metric_dist_dim into its workspace: the same root bits),
+ *   a value below 1e-15 returned as 0; a NaN or infinity in centres[i] gives NaN distances, which never count as hits
+ *   (hits[i] = 0), and touches no other chain.
+ * (A Choi matrix here has trace 2^n, so the infidelity of two of them is 1 - (~2^n)^2 < 1e-15 and comes back as 0, as
+ * geometry.py:52-54 returns it: meaningful only for centres scaled to unit trace.)
+ * A chain's bits depend on its own inputs and its global chain index alone: not on C or its place in the batch.
+ * hits[i] = #{ kept : thresholds[i] > distance } (strict); accepted, dist NULLABLE as above.
+ * QT_ERR_ARG: everything qt_mhmc_process_hits refuses, and a metric other than QT_METRIC_TRACE / QT_METRIC_INFIDELITY;
+ * n = 3: QT_ERR_UNSUPPORTED before any launch; C = 0 returns 0 without a launch; a missing POVM or qt_process_setup
+ * fails as there. */
+int qt_mhmc_process_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                                const double* choi_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                                double* dist, int flags);
 /* projections alone (process.py:231-278): mode 0 = CPTP (Dykstra), 1 = TP, 2 = CP */
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol,
                           double* choi_out, int32_t* iters, int flags);

@@ -66,17 +66,19 @@ __global__ void __launch_bounds__(256) k_mhmc_state(PovmView pv, const int64_t* 
 // (qt_sampler::mhmc_draw, global chain first_chain + b, global step = burn-in steps first, then the n_points * thinning
 // sampling steps), and of the chain only three numbers per trial leave the registers.  Post-burn step s is kept when
 // s % thinning == 0 (mhmc.py:80-84); on a kept step the lane forms its element of L L^dagger as k_chol_unparam does and
-// the group its Hilbert-Schmidt distance to centres[b] (hs_to_centre):
+// the group its distance to centres[b] (k_mhmc_state_hits: Hilbert-Schmidt, hs_to_centre):
 //   hits[b] = #{ kept : thresholds[b] > distance }  (strict: a NaN never counts),  accepted[b] = accepted post-burn steps,
 //   dist[b][k] (nullable) = the distance of kept state k.
 // Lane 0 of a live group counts in registers and stores once; every lane runs the distance and the reductions.
-template <int NQ>
-__global__ void __launch_bounds__(256) k_mhmc_state_hits(PovmView pv, const int64_t* __restrict__ counts, int C,
-                                                         const double* __restrict__ centres, const double* __restrict__ x_init,
-                                                         const double* __restrict__ thresholds, uint64_t seed,
-                                                         uint64_t first_chain, uint32_t burn_steps, uint32_t n_points,
-                                                         uint32_t thinning, double step, int64_t* __restrict__ hits,
-                                                         int64_t* __restrict__ accepted, double* __restrict__ dist) {
+// `distance(c, m, centre)`: the group's distance of the kept state to its centre, the same bits in every lane of the group.
+template <int NQ, class Dist>
+__device__ __forceinline__ void mhmc_state_hits_body(PovmView pv, const int64_t* __restrict__ counts, int C,
+                                                     const double* __restrict__ centres, const double* __restrict__ x_init,
+                                                     const double* __restrict__ thresholds, uint64_t seed,
+                                                     uint64_t first_chain, uint32_t burn_steps, uint32_t n_points,
+                                                     uint32_t thinning, double step, int64_t* __restrict__ hits,
+                                                     int64_t* __restrict__ accepted, double* __restrict__ dist,
+                                                     Dist distance) {
   using S = Small<NQ>;
   constexpr int D = S::D;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -104,7 +106,7 @@ __global__ void __launch_bounds__(256) k_mhmc_state_hits(PovmView pv, const int6
     if (to_keep == 0) {  // (launch-uniform)
       double tr;
       const cd m = S::build_llh(c, x, tr);
-      const double v = S::hs_to_centre(c, m, centre);
+      const double v = distance(c, m, centre);
       n_hit += thr > v;
       if (dist && writer) dist[(size_t)b * n_points + kept] = v;
       ++kept;
@@ -116,6 +118,43 @@ __global__ void __launch_bounds__(256) k_mhmc_state_hits(PovmView pv, const int6
     hits[b] = n_hit;
     accepted[b] = n_acc;
   }
+}
+
+template <int NQ>
+__global__ void __launch_bounds__(256) k_mhmc_state_hits(PovmView pv, const int64_t* __restrict__ counts, int C,
+                                                         const double* __restrict__ centres, const double* __restrict__ x_init,
+                                                         const double* __restrict__ thresholds, uint64_t seed,
+                                                         uint64_t first_chain, uint32_t burn_steps, uint32_t n_points,
+                                                         uint32_t thinning, double step, int64_t* __restrict__ hits,
+                                                         int64_t* __restrict__ accepted, double* __restrict__ dist) {
+  using S = Small<NQ>;
+  mhmc_state_hits_body<NQ>(pv, counts, C, centres, x_init, thresholds, seed, first_chain, burn_steps, n_points, thinning, step,
+                           hits, accepted, dist, [](const typename S::Ctx& c, cd m, const double* __restrict__ centre) {
+                             return S::hs_to_centre(c, m, centre);
+                           });
+}
+
+// The same chain with the kept states measured in trace distance or infidelity (qt_mhmc_state_metric_hits): the value
+// k_metric_dist returns for L L^dagger and centres[b], by the same device functions (Small::trace_dist, Small::infidelity
+// on jacobi_sweeps<OWN>: at n = 1 sixteen chains share a wavefront, at n = 2 four, and a chain's bits do not depend on
+// how many sweeps its neighbours take).  METRIC = kMetricInfidelity: `centres` holds the roots k_psd_sqrt made of them.
+// The sweeps' two matrix images are the chain context's own A() and V(): scratch of nll_grad and build_llh, whose last
+// reads lie behind a wave_sync by the time the kept state's element is returned; the frequencies, the one thing a chain
+// keeps in LDS from step to step, lie behind them (V() is on rbuf or has a block of its own, Small::v_offset).
+template <int NQ, int METRIC>
+__global__ void __launch_bounds__(256) k_mhmc_state_metric_hits(PovmView pv, const int64_t* __restrict__ counts, int C,
+                                                                const double* __restrict__ centres,
+                                                                const double* __restrict__ x_init,
+                                                                const double* __restrict__ thresholds, uint64_t seed,
+                                                                uint64_t first_chain, uint32_t burn_steps, uint32_t n_points,
+                                                                uint32_t thinning, double step, int64_t* __restrict__ hits,
+                                                                int64_t* __restrict__ accepted, double* __restrict__ dist) {
+  using S = Small<NQ>;
+  mhmc_state_hits_body<NQ>(pv, counts, C, centres, x_init, thresholds, seed, first_chain, burn_steps, n_points, thinning, step,
+                           hits, accepted, dist, [](const typename S::Ctx& c, cd m, const double* __restrict__ centre) {
+                             const cd q{centre[2 * c.l], centre[2 * c.l + 1]};
+                             return METRIC == kMetricTrace ? S::trace_dist(c, m, q) : S::infidelity(c, m, q);
+                           });
 }
 
 }  // namespace qt

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "qt_args.h"     // centre_of
+#include "qt_metric_dim.h"  // MetricDim, Small::trace_dist / infidelity: the metric form of the process chain
 #include "qt_ops.h"      // v4f64
 #include "qt_sampler.h"  // mhmc_draw
 #include "qt_signclip_wg.h"
@@ -697,23 +698,19 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process(const int64_
 //   hits[b] = #{ kept : thresholds[b] > distance }  (strict: a NaN never counts),  accepted[b] = accepted post-burn steps,
 //   dist[b][k] (nullable) = the distance of kept state k.
 // Every thread counts (the decisions are uniform over the workgroup); thread 0 stores.
-template <int DC>
-__global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process_hits(const int64_t* __restrict__ counts, int C, int M,
-                                                                     const double* __restrict__ lifp,
-                                                                     const double* __restrict__ choi_init,
-                                                                     const double* __restrict__ centres,
-                                                                     const double* __restrict__ thresholds, uint64_t seed,
-                                                                     uint64_t first_chain, uint32_t burn_steps,
-                                                                     uint32_t n_points, uint32_t thinning, double step,
-                                                                     int64_t* __restrict__ hits, int64_t* __restrict__ accepted,
-                                                                     double* __restrict__ dist) {
-  using W = ProcWG<DC>;
-  constexpr int NE = W::NE;
-  __shared__ typename W::Sh sh;
-  __shared__ double cre[NE], cim[NE];
-  extern __shared__ double dynsh[];  // cnt[R] | p[R]
+// `distance(c, xr, centre)`: the workgroup's distance of the kept point to its centre, the same bits in every thread.
+template <int DC, class Dist>
+__device__ __forceinline__ void mhmc_process_hits_body(typename ProcWG<DC>::Sh& sh, double* cre, double* cim, double* dynsh,
+                                                       const int64_t* __restrict__ counts, int M,
+                                                       const double* __restrict__ lifp, const double* __restrict__ choi_init,
+                                                       const double* __restrict__ centres,
+                                                       const double* __restrict__ thresholds, uint64_t seed,
+                                                       uint64_t first_chain, uint32_t burn_steps, uint32_t n_points,
+                                                       uint32_t thinning, double step, int64_t* __restrict__ hits,
+                                                       int64_t* __restrict__ accepted, double* __restrict__ dist,
+                                                       Dist distance) {
+  constexpr int NE = ProcWG<DC>::NE;
   const int b = blockIdx.x;
-  if (b >= C) return;
   const ProcChain<DC> c(sh, cre, cim, dynsh, lifp, M);
   const int tid = c.tid;
   const bool act = c.act;
@@ -739,7 +736,7 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process_hits(const i
   for (uint32_t s = 0; s < total; ++s, ++j) {
     n_acc += one_step(j);
     if (to_keep == 0) {  // (launch-uniform)
-      const double v = c.real_part_dist(xr, centre);
+      const double v = distance(c, xr, centre);
       n_hit += thr > v;
       if (dist && tid == 0) dist[(size_t)b * n_points + kept] = v;
       ++kept;
@@ -750,6 +747,81 @@ __global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process_hits(const i
   if (tid == 0) {
     hits[b] = n_hit;
     accepted[b] = n_acc;
+  }
+}
+
+template <int DC>
+__global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process_hits(const int64_t* __restrict__ counts, int C, int M,
+                                                                     const double* __restrict__ lifp,
+                                                                     const double* __restrict__ choi_init,
+                                                                     const double* __restrict__ centres,
+                                                                     const double* __restrict__ thresholds, uint64_t seed,
+                                                                     uint64_t first_chain, uint32_t burn_steps,
+                                                                     uint32_t n_points, uint32_t thinning, double step,
+                                                                     int64_t* __restrict__ hits, int64_t* __restrict__ accepted,
+                                                                     double* __restrict__ dist) {
+  using W = ProcWG<DC>;
+  constexpr int NE = W::NE;
+  __shared__ typename W::Sh sh;
+  __shared__ double cre[NE], cim[NE];
+  extern __shared__ double dynsh[];  // cnt[R] | p[R]
+  if ((int)blockIdx.x >= C) return;
+  mhmc_process_hits_body<DC>(sh, cre, cim, dynsh, counts, M, lifp, choi_init, centres, thresholds, seed, first_chain, burn_steps,
+                             n_points, thinning, step, hits, accepted, dist,
+                             [](const ProcChain<DC>& c, double xr, const double* __restrict__ centre) {
+                               return c.real_part_dist(xr, centre);
+                             });
+}
+
+// The same chain with the real part of the kept points measured in trace distance or infidelity
+// (qt_mhmc_process_metric_hits): the value qt_metric_dist_dim returns for Re(X) and centres[b] at dim = DC, by the same
+// device functions.  METRIC = kMetricInfidelity: `centres` holds the roots k_psd_sqrt<2> / k_psd_sqrt_dim<16> made of them.
+//   DC = 16: thread (i, j) = (tid / 16, tid % 16) is MetricDim<16>'s mapping.  Its two images and reduction scratch (1104
+//     doubles) lie on Sh::clip (1712), the block of the CP step's eigenvalue clip: dead outside dykstra, and the barriers
+//     of nll_of stand between the step's last projection and the distance.  Every break in MetricDim::sweeps is taken on
+//     bsum bits, so the barriers stay workgroup-uniform; the kept-step branch around the call is launch-uniform.
+//   DC = 4: one wavefront, 16 active threads.  The lane-group form Small<2> (d = 4, G = 16) with a CtxM of its own
+//     (2 KB); lanes 16-63 take group 0's elements (__shfl from lane tid % 16) and its centre, so the wavefront's four
+//     groups hold the same matrix, leave the sweeps together, and every thread returns group 0's bits.
+template <int DC, int METRIC>
+__global__ void __launch_bounds__(ProcWG<DC>::NT, 2) k_mhmc_process_metric_hits(
+    const int64_t* __restrict__ counts, int C, int M, const double* __restrict__ lifp, const double* __restrict__ choi_init,
+    const double* __restrict__ centres, const double* __restrict__ thresholds, uint64_t seed, uint64_t first_chain,
+    uint32_t burn_steps, uint32_t n_points, uint32_t thinning, double step, double jtol2, int64_t* __restrict__ hits,
+    int64_t* __restrict__ accepted, double* __restrict__ dist) {
+  using W = ProcWG<DC>;
+  constexpr int NE = W::NE;
+  __shared__ typename W::Sh sh;
+  __shared__ double cre[NE], cim[NE];
+  extern __shared__ double dynsh[];  // cnt[R] | p[R]
+  if ((int)blockIdx.x >= C) return;
+  if constexpr (DC == 16) {
+    using MD = MetricDim<16>;
+    static_assert(MD::kDoubles <= W::kClipDoubles && MD::NT == W::NT, "the metric context lies on Sh::clip");
+    typename MD::Ctx mc;
+    MD::make_ctx(mc, sh.clip, jtol2);
+    mhmc_process_hits_body<DC>(sh, cre, cim, dynsh, counts, M, lifp, choi_init, centres, thresholds, seed, first_chain,
+                               burn_steps, n_points, thinning, step, hits, accepted, dist,
+                               [&mc](const ProcChain<DC>& c, double xr, const double* __restrict__ centre) {
+                                 const cd q{centre[2 * c.tid], centre[2 * c.tid + 1]};
+                                 const double v = METRIC == kMetricTrace ? MD::trace_dist(mc, cd{xr, 0.0}, q)
+                                                                         : MD::infidelity(mc, cd{xr, 0.0}, q);
+                                 __syncthreads();  // the last reduction's partials are read before the next step's clip writes
+                                 return v;
+                               });
+  } else {
+    using S = Small<2>;
+    static_assert(DC == 4 && S::G == NE && W::NT == 64, "one wavefront, four lane groups of one Choi matrix");
+    __shared__ __attribute__((aligned(16))) double msm[S::TPW * S::kMetricDoubles];
+    typename S::CtxM mc;
+    S::make_ctx_metric(mc, msm, jtol2);
+    mhmc_process_hits_body<DC>(sh, cre, cim, dynsh, counts, M, lifp, choi_init, centres, thresholds, seed, first_chain,
+                               burn_steps, n_points, thinning, step, hits, accepted, dist,
+                               [&mc](const ProcChain<DC>& c, double xr, const double* __restrict__ centre) {
+                                 const cd r{__shfl(xr, mc.l, 64), 0.0};
+                                 const cd q{centre[2 * mc.l], centre[2 * mc.l + 1]};
+                                 return METRIC == kMetricTrace ? S::trace_dist(mc, r, q) : S::infidelity(mc, r, q);
+                               });
   }
 }
 

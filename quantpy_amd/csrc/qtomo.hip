@@ -1754,18 +1754,23 @@ int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, ui
   return c.done();
 }
 
-int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
-                       const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
-                       int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+// qt_mhmc_state_hits (`hs`: the metric is not read) and qt_mhmc_state_metric_hits: the same checks, staging and launch
+// plan; the infidelity's roots of the C centres by k_psd_sqrt into metric_ws first, as metric_small has them
+static int mhmc_state_hits_impl(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C, const double* centres,
+                                const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                                double* dist, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
-  if (int r = mhmc_device_nq(h, "qt_mhmc_state_hits")) return r;
+  if (int r = mhmc_device_nq(h, fn)) return r;
   if (int r = need_povm(h)) return r;
+  if (!hs && metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
+    return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
   if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
       (C > 0 && (!counts || !centres || !x_init || !thresholds || !hits || !accepted)))
-    return fail(QT_ERR_ARG, "bad mhmc_state_hits arguments");
+    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
   if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
-    return fail(QT_ERR_ARG, "qt_mhmc_state_hits: burn_steps + n_points * thinning must be below 2^32 - 1");
+    return fail(QT_ERR_ARG, "%s: burn_steps + n_points * thinning must be below 2^32 - 1", fn);
   if (C == 0) return 0;
   const int64_t* dc;
   const double *dcen, *dx, *dthr;
@@ -1781,15 +1786,42 @@ int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const doubl
   if (int r = by_nq(h, [&](auto nq) {
         constexpr int NQ = decltype(nq)::value;
         if constexpr (NQ <= 3) {
+          using S = qt::Small<NQ>;
           const Plan p = povm_plan<NQ>(h, C);
-          return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, dc, C, dcen, dx, dthr, seed, first_chain, (uint32_t)burn_steps,
-                        (uint32_t)n_points, (uint32_t)thinning, step, dh, da, ddist);
+          const uint32_t nb = (uint32_t)burn_steps, np = (uint32_t)n_points, th = (uint32_t)thinning;
+          if (hs)
+            return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, dc, C, dcen, dx, dthr, seed, first_chain, nb, np, th, step, dh,
+                          da, ddist);
+          if (metric == QT_METRIC_TRACE)
+            return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, dc, C, dcen, dx, dthr, seed,
+                          first_chain, nb, np, th, step, dh, da, ddist);
+          HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
+          double* roots = h->metric_ws.as<double>();
+          if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((C + S::TPB - 1) / S::TPB), dim3(S::NT), 0, dcen, C, h->jtol2, roots))
+            return r;
+          return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, dc, C,
+                        static_cast<const double*>(roots), dx, dthr, seed, first_chain, nb, np, th, step, dh, da, ddist);
         } else {
           return 0;  // (refused above)
         }
       }))
     return r;
   return c.done();
+}
+
+int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
+                       const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                       int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  return mhmc_state_hits_impl(h, "qt_mhmc_state_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
+                              burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
+}
+
+int qt_mhmc_state_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                              const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                              int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                              double* dist, int flags) {
+  return mhmc_state_hits_impl(h, "qt_mhmc_state_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
+                              first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
 }
 
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
@@ -2703,19 +2735,24 @@ int qt_mhmc_process_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, i
   return c.done();
 }
 
-int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
-                         const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
-                         int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+// qt_mhmc_process_hits (`hs`: the metric is not read) and qt_mhmc_process_metric_hits: the same checks and staging; the
+// infidelity's roots of the C centres into metric_ws first, by the set-up kernel of qt_metric_dist_dim at dim = D
+static int mhmc_process_hits_impl(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C,
+                                  const double* centres, const double* choi_init, const double* thresholds, uint64_t seed,
+                                  uint64_t first_chain, int burn_steps, int n_points, int thinning, double step, int64_t* hits,
+                                  int64_t* accepted, double* dist, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
-  if (int r = mhmc_process_device_nq(h, "qt_mhmc_process_hits")) return r;
+  if (int r = mhmc_process_device_nq(h, fn)) return r;
   if (int r = need_povm(h)) return r;
   if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+  if (!hs && metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
+    return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
   if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
       (C > 0 && (!counts || !centres || !choi_init || !thresholds || !hits || !accepted)))
-    return fail(QT_ERR_ARG, "bad mhmc_process_hits arguments");
+    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
   if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
-    return fail(QT_ERR_ARG, "qt_mhmc_process_hits: burn_steps + n_points * thinning must be below 2^32 - 1");
+    return fail(QT_ERR_ARG, "%s: burn_steps + n_points * thinning must be below 2^32 - 1", fn);
   if (C == 0) return 0;
   const int D = h->D, M = h->M;
   const size_t ne = (size_t)D * D;
@@ -2732,11 +2769,47 @@ int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const dou
   if (int r = c.out(hits, (size_t)C, &dh)) return r;
   if (int r = c.out(accepted, (size_t)C, &da)) return r;
   if (int r = c.out(dist, (size_t)C * n_points, &ddist)) return r;
-  if (int r = launch(h, D == 4 ? qt::k_mhmc_process_hits<4> : qt::k_mhmc_process_hits<16>, dim3(C),
-                     dim3(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT), dyn, dc, C, M, h->proc.lifp.as<double>(), dx, dcen, dthr,
-                     seed, first_chain, (uint32_t)burn_steps, (uint32_t)n_points, (uint32_t)thinning, step, dh, da, ddist))
+  const dim3 block(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT);
+  const double* lifp = h->proc.lifp.as<double>();
+  const uint32_t nb = (uint32_t)burn_steps, np = (uint32_t)n_points, th = (uint32_t)thinning;
+  if (hs) {
+    if (int r = launch(h, D == 4 ? qt::k_mhmc_process_hits<4> : qt::k_mhmc_process_hits<16>, dim3(C), block, dyn, dc, C, M, lifp,
+                       dx, dcen, dthr, seed, first_chain, nb, np, th, step, dh, da, ddist))
+      return r;
+    return c.done();
+  }
+  if (metric == QT_METRIC_INFIDELITY) {
+    HIPCHK(h->metric_ws.ensure((size_t)C * ne * 2 * sizeof(double)));
+    double* roots = h->metric_ws.as<double>();
+    using S2 = qt::Small<2>;
+    if (int r = D == 4 ? launch(h, qt::k_psd_sqrt<2>, dim3((C + S2::TPB - 1) / S2::TPB), dim3(S2::NT), 0, dcen, C, h->jtol2, roots)
+                       : launch(h, qt::k_psd_sqrt_dim<16>, dim3(C), dim3(qt::MetricDim<16>::NT), 0, dcen, C, h->jtol2, roots))
+      return r;
+    dcen = roots;
+  }
+  auto kernel = metric == QT_METRIC_TRACE
+                    ? (D == 4 ? qt::k_mhmc_process_metric_hits<4, qt::kMetricTrace> : qt::k_mhmc_process_metric_hits<16, qt::kMetricTrace>)
+                    : (D == 4 ? qt::k_mhmc_process_metric_hits<4, qt::kMetricInfidelity>
+                              : qt::k_mhmc_process_metric_hits<16, qt::kMetricInfidelity>);
+  if (int r = launch(h, kernel, dim3(C), block, dyn, dc, C, M, lifp, dx, dcen, dthr, seed, first_chain, nb, np, th, step, h->jtol2,
+                     dh, da, ddist))
     return r;
   return c.done();
+}
+
+int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
+                         const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                         int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  return mhmc_process_hits_impl(h, "qt_mhmc_process_hits", true, 0, counts, C, centres, choi_init, thresholds, seed, first_chain,
+                                burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
+}
+
+int qt_mhmc_process_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                                const double* choi_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                                double* dist, int flags) {
+  return mhmc_process_hits_impl(h, "qt_mhmc_process_metric_hits", false, metric, counts, C, centres, choi_init, thresholds, seed,
+                                first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
 }
 
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol, double* choi_out,

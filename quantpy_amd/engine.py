@@ -417,7 +417,7 @@ class Engine:
         return deltas, uniforms
 
     def mhmc_process_hits(self, counts, centres, choi_init, thresholds, seed, burn_steps, n_points, thinning, step,
-                          first_chain=0, return_dist=False):
+                          first_chain=0, return_dist=False, metric=None):
         """One Metropolis-Hastings chain per process with its random numbers drawn on the device and nothing of the
         chain stored (qt_mhmc_process_hits): chain i runs on counts[i] from choi_init[i] with the numbers of global chain
         first_chain + i (`mhmc_process_draws`), `burn_steps` steps and then n_points * thinning of which every
@@ -425,7 +425,9 @@ class Engine:
         part lies at a Hilbert-Schmidt distance to centres[i] strictly below thresholds[i], accepted[i] = the accepted
         post-burn steps; with return_dist also the kept distances (C, n_points).  counts (C, D, S, K), centres and
         choi_init (C, D, D) complex, thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in
-        stream order).  n <= 2."""
+        stream order).  n <= 2.  metric='trace' / 'if': the same chains with the distance `metric_dist_dim` returns for
+        the real part of a kept state and centres[i] (qt_mhmc_process_metric_hits); None: Hilbert-Schmidt."""
+        code = None if metric is None else self._metric_code(metric)
         ne = self.D * self.D
         if _is_dev(counts):
             import torch
@@ -451,10 +453,12 @@ class Engine:
             hits = np.zeros(nchain, dtype=np.int64)
             acc = np.zeros(nchain, dtype=np.int64)
             dist = np.empty((nchain, int(n_points))) if return_dist else None
-        self._chk(self.lib.qt_mhmc_process_hits(self._h, _ptr(counts), nchain, _ptr(centres), _ptr(choi_init),
-                                                _ptr(thresholds), int(seed), int(first_chain), int(burn_steps),
-                                                int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc),
-                                                _ptr(dist), flags))
+        tail = (_ptr(counts), nchain, _ptr(centres), _ptr(choi_init), _ptr(thresholds), int(seed), int(first_chain),
+                int(burn_steps), int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags)
+        if code is None:
+            self._chk(self.lib.qt_mhmc_process_hits(self._h, *tail))
+        else:
+            self._chk(self.lib.qt_mhmc_process_metric_hits(self._h, code, *tail))
         return (hits, acc, dist) if return_dist else (hits, acc)
 
     def lifp_dev(self, counts, choi, cptp=True, iters=None, status=None):
@@ -702,7 +706,7 @@ class Engine:
         return deltas, uniforms
 
     def mhmc_state_hits(self, counts, centres, x_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain=0,
-                        return_dist=False):
+                        return_dist=False, metric=None):
         """One Metropolis-Hastings chain per trial with its random numbers drawn on the device and nothing of the chain
         stored (qt_mhmc_state_hits): chain i runs on counts[i] from x_init[i] (`chol_param(centres[i])`) with the numbers
         of global chain first_chain + i (`mhmc_draws`), `burn_steps` steps and then n_points * thinning of which every
@@ -710,7 +714,9 @@ class Engine:
         Hilbert-Schmidt distance to centres[i] lies strictly below thresholds[i], accepted[i] = the accepted post-burn
         steps; with return_dist also the kept distances (C, n_points).  counts (C, S, K), centres (C, d, d) complex,
         x_init (C, D), thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in stream order).
-        n <= 3."""
+        n <= 3.  metric='trace' / 'if': the same chains with the distance `metric_dist` returns for a kept state and
+        centres[i] (qt_mhmc_state_metric_hits); None: Hilbert-Schmidt."""
+        code = None if metric is None else self._metric_code(metric)
         if _is_dev(counts):
             import torch
 
@@ -734,9 +740,12 @@ class Engine:
             hits = np.zeros(nchain, dtype=np.int64)
             acc = np.zeros(nchain, dtype=np.int64)
             dist = np.empty((nchain, int(n_points))) if return_dist else None
-        self._chk(self.lib.qt_mhmc_state_hits(self._h, _ptr(counts), nchain, _ptr(centres), _ptr(x_init), _ptr(thresholds),
-                                              int(seed), int(first_chain), int(burn_steps), int(n_points), int(thinning),
-                                              float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags))
+        tail = (_ptr(counts), nchain, _ptr(centres), _ptr(x_init), _ptr(thresholds), int(seed), int(first_chain),
+                int(burn_steps), int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags)
+        if code is None:
+            self._chk(self.lib.qt_mhmc_state_hits(self._h, *tail))
+        else:
+            self._chk(self.lib.qt_mhmc_state_metric_hits(self._h, code, *tail))
         return (hits, acc, dist) if return_dist else (hits, acc)
 
     def mle_dev(self, counts, rho, init="lin", max_iter=100, tol=1e-3, nit=None, nfev=None, fun=None, status=None):

@@ -22,7 +22,10 @@ interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with t
 `get_CL_list_state_mhmc` is the reference's interval='mhmc' branch for states: one Metropolis-Hastings chain per trial, all
 of them in one launch that draws its own random numbers and returns, per trial, the hits and the accepted steps
 (`qt_mhmc_state_hits`).  `get_CL_list_channel_mhmc` is the same branch for channels (n <= 2): a chain on the Choi vector
-per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.
+per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.  Both take dst='hs' | 'trace' | 'if': for the
+other two distances the chain kernels run the Jacobi-sweep metrics on the state they hold (`qt_mhmc_state_metric_hits`,
+`qt_mhmc_process_metric_hits`).  `get_CL_list_channel_boot_dst` is the process bootstrap study in any of the three: it
+measures a chunk's Choi matrices with `qt_metric_dist_dim`.
 """
 import numpy as np
 
@@ -196,8 +199,8 @@ def get_CL_list_state_boot(state, n_iter=1000, n_points=1000, n_measurements=100
 
 def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=1000, method="lin", povm="proj-set", init="lin",
                            tol=1e-3, max_iter=100, step=0.01, burn_steps=1000, thinning=1, *, sampler="device", seed=None,
-                           return_details=False):
-    """The interval='mhmc', dst='hs' branch of the reference's get_CL_list_state (metrics.py:125-144; parameters as
+                           return_details=False, dst="hs"):
+    """The interval='mhmc' branch of the reference's get_CL_list_state (metrics.py:125-144; parameters as
     there): `n_iter` experiments, for each a Metropolis-Hastings chain of the likelihood on the Cholesky parameters around
     ITS OWN point estimate (MHMCStateInterval: `burn_steps` steps, then n_points * thinning of which every `thinning`-th
     state is a sample), and the level at which the true state leaves the interval of the sampled distances.  Returns the
@@ -220,6 +223,12 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
     a rounding error.  (1e-13 is the size below which `qt_chol_param` stops trusting a pivot: a hundred times the clip,
     and far below the eigenvalues of an estimate of a full-rank state.)  Use a mixed state, or method='mle' on one.
 
+    dst (keyword-only) = 'hs' | 'trace' | 'if', or the functions of quantpy_amd.geometry: the distance of the study.  'hs'
+    is the call described above, the same bits.  Otherwise delta_t = `Engine.metric_dist`(estimate_t, state) and the
+    chains run through `Engine.mhmc_state_hits(metric=dst)`: the same chains (the accepted steps do not depend on the
+    distance) with every sample measured as `metric_dist` measures it, by the same device functions in the kernel that
+    holds the sample (include/qtomo.h: qt_mhmc_state_metric_hits).
+
     `sampler`, `seed`, `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the
     accepted post-burn steps / (n_points * thinning), the reference's definition."""
     _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
@@ -230,13 +239,15 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
         raise ValueError("burn_steps must not be negative")
     if burn_steps + n_points * thinning >= 2**32 - 1:
         raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
+    metric = _distance_name(dst)
+    metric = None if metric == "hs" else metric
     tmg = StateTomograph(state, "hs")
     counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
     rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
     if info is not None and np.any(info["status"] == 1):
         raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
     eng = tmg._engine()
-    delta = eng.hs_dist(rho, state.matrix)
+    delta = eng.hs_dist(rho, state.matrix) if metric is None else eng.metric_dist(rho, state.matrix, metric)
     x0, status = eng.chol_param(rho)
     # ... and none for the estimate less the floor: its smallest eigenvalue is not above _PD_FLOOR (a NaN is refused too)
     _, shifted = eng.chol_param(rho - _PD_FLOOR * np.eye(rho.shape[-1]))
@@ -249,7 +260,8 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
     both = np.zeros((2, n_iter), dtype=np.int64)
     if hi > lo:
         both[0, lo:hi], both[1, lo:hi] = eng.mhmc_state_hits(counts[lo:hi], rho[lo:hi], x0[lo:hi], delta[lo:hi], key,
-                                                             burn_steps, n_points, thinning, step, first_chain=lo)
+                                                             burn_steps, n_points, thinning, step, first_chain=lo,
+                                                             metric=metric)
     if qdist.world()[1] > 1:
         both = qdist.allgather_equal(both).sum(0)
     hits, accepted = both
@@ -381,19 +393,59 @@ def get_CL_list_channel_boot(channel, n_iter=1000, n_points=1000, n_measurements
     neither on `chunk` nor on the number of ranks; each rank takes `shard_bounds(n_points)` of the resamples, the hits are
     summed and every rank returns the same list.  A chunk of whole resamples is one `device_multinomial`, one
     `qt_lifp_dist_group_batch` (process b against centre b % n_iter) and one `qt_group_hits`; the level of trial t is
-    `levels_from_hits`: np.linspace(0, 1, n_points)[hits_t - 1], hits_t the resampled distances strictly below delta_t."""
+    `levels_from_hits`: np.linspace(0, 1, n_points)[hits_t - 1], hits_t the resampled distances strictly below delta_t.
+
+    The same study in the trace distance or the infidelity is `get_CL_list_channel_boot_dst`."""
+    return _channel_boot(channel, n_iter, n_points, n_measurements, method, povm, input_states, cptp, states_init,
+                         states_est_method, sampler, seed, chunk, return_details, "hs")
+
+
+def get_CL_list_channel_boot_dst(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",
+                                 input_states="proj4", cptp=True, states_init="lin", states_est_method="lin", *,
+                                 sampler="device", seed=None, chunk=None, return_details=False, dst="hs"):
+    """`get_CL_list_channel_boot` -- parameters, keying of the resamples and details as there -- in any of the three
+    distances: dst = 'hs' | 'trace' | 'if', or the functions of quantpy_amd.geometry, as `get_CL_list_state_boot` is for
+    states.  (`get_CL_list_channel_boot` keeps the argument list its callers and tests know; this is the study's name
+    with a distance.)
+
+    dst='hs' IS `get_CL_list_channel_boot`: the same call, the same bits.  Otherwise `delta` and the resampled distances
+    are measured in `dst`: a chunk's Choi matrices go into one device workspace of the first chunk's size
+    (`Engine.lifp_dev`) and `Engine.metric_dist_dim_dev` measures resample r of trial t against estimate t (the table of
+    the n_iter estimates, process b against centre b % n_iter), as `_boot_hits` does it for states; n <= 2 (dim = 4, 16).
+    A Choi matrix here has trace 2^n, not 1, so `if_dst` of two of them is 1 - (about 2^n)^2 < 1e-15 and comes back as 0,
+    exactly as geometry.py:52-54 returns it in the reference.  dst='if' on a channel is therefore accepted and faithful,
+    and degenerate: every distance, every `delta` and every level is 0."""
+    return _channel_boot(channel, n_iter, n_points, n_measurements, method, povm, input_states, cptp, states_init,
+                         states_est_method, sampler, seed, chunk, return_details, dst)
+
+
+def _channel_boot(channel, n_iter, n_points, n_measurements, method, povm, input_states, cptp, states_init,
+                  states_est_method, sampler, seed, chunk, return_details, dst):
     _check_arguments("boot", "hs", n_iter, n_points, sampler, ("lifp",), "lifp")
+    metric = _distance_name(dst)
+    metric = None if metric == "hs" else metric
     n_iter, n_points = int(n_iter), int(n_points)
     tmg = ProcessTomograph(channel, input_states, "hs")
     counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
     choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
     eng = tmg._engine()
-    delta = eng.hs_dist(choi, channel.choi.matrix)
+    delta = (eng.hs_dist(choi, channel.choi.matrix) if metric is None else
+             eng.metric_dist_dim(choi, channel.choi.matrix, metric))
     key = (base + 1) & (2**64 - 1)
     pvals = eng.process_born_probs(choi)
+    work = []  # the Choi matrices of a chunk
 
     def measure(resamples, centres, dist, status):
-        eng.lifp_dist_dev(resamples, centres, dist, cptp=cptp, status=status)
+        if metric is None:
+            eng.lifp_dist_dev(resamples, centres, dist, cptp=cptp, status=status)
+            return
+        import torch
+
+        if not work:
+            work.append(torch.empty((resamples.shape[0], eng.D, eng.D), dtype=torch.complex128, device=resamples.device))
+        mats = work[0][:resamples.shape[0]]
+        eng.lifp_dev(resamples, mats, cptp=cptp, status=status)
+        eng.metric_dist_dim_dev(mats, centres, dist, metric)
 
     hits, bad = _chunked_hits(eng, choi, (eng.D, eng.S, eng.K), pvals, tmg.tomographs[0].n_measurements, delta, n_points,
                               key, chunk, measure, lambda status: (status != 0).any().reshape(1))
@@ -405,8 +457,8 @@ def get_CL_list_channel_boot(channel, n_iter=1000, n_points=1000, n_measurements
 
 def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",
                              input_states="proj4", states_init="lin", states_est_method="lin", step=0.01, burn_steps=1000,
-                             thinning=1, *, sampler="device", seed=None, return_details=False):
-    """The interval='mhmc', dst='hs' branch of the reference's get_CL_list_channel (metrics.py:289-298; parameters as
+                             thinning=1, *, sampler="device", seed=None, return_details=False, dst="hs"):
+    """The interval='mhmc' branch of the reference's get_CL_list_channel (metrics.py:289-298; parameters as
     there): `n_iter` process tomographies, for each a Metropolis-Hastings chain of the likelihood on the Choi vector around
     ITS OWN estimate (MHMCProcessInterval with use_new_estimate=False: every proposal projected onto the CPTP set,
     `burn_steps` steps, then n_points * thinning of which every `thinning`-th state is a sample, the samples' real parts
@@ -423,6 +475,15 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     (include/qtomo.h: qt_mhmc_process_draws) -- the numbers of a trial depend neither on the number of ranks nor on its
     place in a batch, and never on np.random.  The level of trial t is `levels_from_hits(hits_t, n_points)`.
 
+    dst (keyword-only) = 'hs' | 'trace' | 'if', or the functions of quantpy_amd.geometry: 'hs' is the call described
+    above, the same bits.  Otherwise delta_t = `Engine.metric_dist_dim`(estimate_t, Choi matrix of the channel) and the
+    chains run through `Engine.mhmc_process_hits(metric=dst)`: the same chains with the real part of every sample
+    measured as `metric_dist_dim` measures it, in the kernel that holds the sample (include/qtomo.h:
+    qt_mhmc_process_metric_hits).
+    A Choi matrix here has trace 2^n, not 1, so `if_dst` of two of them is 1 - (about 2^n)^2 < 1e-15 and comes back as 0,
+    exactly as geometry.py:52-54 returns it in the reference.  dst='if' on a channel is therefore accepted and faithful,
+    and degenerate: every distance, every `delta` and every level is 0.
+
     An estimate that is not finite (an input state without counts) raises ValueError on every rank.  `sampler`, `seed`,
     `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the accepted post-burn
     steps / (n_points * thinning), the reference's definition."""
@@ -434,6 +495,8 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
         raise ValueError("burn_steps must not be negative")
     if burn_steps + n_points * thinning >= 2**32 - 1:
         raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
+    metric = _distance_name(dst)
+    metric = None if metric == "hs" else metric
     if channel.n_qubits > 2:
         raise NotImplementedError(f"get_CL_list_channel_mhmc runs channels of one and two qubits, not {channel.n_qubits}: "
                                   "the chain of a three-qubit process has no fused kernel")
@@ -443,13 +506,15 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     if not np.all(np.isfinite(choi)):  # (the same estimates on every rank: all raise, or none)
         raise ValueError("a trial has no finite Choi matrix (an input state without counts)")
     eng = tmg._engine()
-    delta = eng.hs_dist(choi, channel.choi.matrix)
+    delta = (eng.hs_dist(choi, channel.choi.matrix) if metric is None else
+             eng.metric_dist_dim(choi, channel.choi.matrix, metric))
     key = (base + 1) & (2**64 - 1)
     lo, hi = qdist.shard_bounds(n_iter)
     both = np.zeros((2, n_iter), dtype=np.int64)
     if hi > lo:
         both[0, lo:hi], both[1, lo:hi] = eng.mhmc_process_hits(counts[lo:hi], choi[lo:hi], choi[lo:hi], delta[lo:hi], key,
-                                                               burn_steps, n_points, thinning, step, first_chain=lo)
+                                                               burn_steps, n_points, thinning, step, first_chain=lo,
+                                                               metric=metric)
     if qdist.world()[1] > 1:
         both = qdist.allgather_equal(both).sum(0)
     hits, accepted = both

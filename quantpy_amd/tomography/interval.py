@@ -775,6 +775,9 @@ class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
                                                              sampler=self.sampler, seed=self.seed))
         self.boot_counts = counts
         centre = self.channel.choi
+        # trace distance / infidelity of the Choi matrices on the engine up to two qubits (dim 4, 16), as
+        # MHMCProcessInterval measures its samples; three qubits keep the host loop
+        metric = _engine_metric(tmg.dst, 2 * tmg.channel.n_qubits)
 
         def reconstruct(shard):
             # the reference's loop (interval.py:675-680) passes method, states_physical, states_init and cptp;
@@ -783,6 +786,8 @@ class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
                                              states_physical=self.states_physical, states_init=self.states_init)
             if tmg.dst is hs_dst:
                 return get_engine(tmg.channel.n_qubits).hs_dist(choi, centre.matrix)  # 4^n x 4^n matrices on the channel's engine
+            if metric:
+                return get_engine(tmg.channel.n_qubits).metric_dist_dim(choi, centre.matrix, metric)
             from ..qobj import Qobj
 
             return np.array([tmg.dst(Qobj(c), centre) for c in choi], dtype=np.float64)
