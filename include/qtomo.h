@@ -429,6 +429,36 @@ int qt_mhmc_state_metric_hits(qt_handle_t* h, int metric, const int64_t* counts,
                               int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
                               double* dist, int flags);
 
+/* qt_mhmc_draws with the vector length given instead of read from the handle, on a handle of any size (no POVM is read):
+ * deltas[C][T][dim], uniforms[C][T] by the definition stated at qt_mhmc_draws with D = dim -- the same kernel, so
+ * dim = 4^n on an n <= 3 handle gives the bits of qt_mhmc_draws.  dim even, 2 <= dim <= 4096, else QT_ERR_ARG;
+ * first_step + T >= 2^32 - 1: QT_ERR_ARG; C = 0 or T = 0 returns 0.  With dim = 256, 1024 it is what qt_mhmc_state needs
+ * to run the chain of qt_mhmc_state_large_hits at n = 4, 5. */
+int qt_mhmc_draws_dim(qt_handle_t* h, int dim, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
+                      double* deltas, double* uniforms, int flags);
+
+/* qt_mhmc_state_hits for n = 4, 5 handles: every argument, the kept-step rule, hits (strict, a NaN threshold or distance
+ * never counts), accepted and the NULLABLE dist as there; numbers as qt_mhmc_draws_dim(dim = 4^n) gives them for global
+ * chain first_chain + i.  One workgroup of 4^n threads per chain runs the steps of qt_mhmc_state at these sizes operand
+ * for operand -- that entry on the numbers of qt_mhmc_draws_dim accepts exactly the same steps -- forms a kept state as
+ * qt_chol_unparam does and its distance to centres[i] as qt_hs_dist_dim defines it (the order of the d^2-term sum is the
+ * workgroup's: within 10 d^2 2^-52 of that entry).  No LDS beyond the chain's own.
+ * QT_ERR_ARG as qt_mhmc_state_hits; n <= 3: QT_ERR_UNSUPPORTED before any launch (the entry there is
+ * qt_mhmc_state_hits); C = 0 returns 0 without a launch. */
+int qt_mhmc_state_large_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
+                             const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                             int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags);
+/* qt_mhmc_state_metric_hits for n = 4, 5 handles: the chains of qt_mhmc_state_large_hits (accepted[] bit-identical to that
+ * entry's) with a kept state measured as qt_metric_dist_dim(dim = 2^n) measures unparam(x) against centres[i], by the same
+ * device functions in the kernel that holds the state; the infidelity's roots of the C centres are made once per call by
+ * the set-up kernel of qt_metric_dist_dim into its workspace (the same root bits).  A NaN or infinity in centres[i] gives
+ * NaN distances and hits[i] = 0, and touches no other chain.  QT_ERR_ARG: everything qt_mhmc_state_large_hits refuses and
+ * an unknown metric; n <= 3: QT_ERR_UNSUPPORTED (the entry there is qt_mhmc_state_metric_hits). */
+int qt_mhmc_state_large_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                                    const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                    int burn_steps, int n_points, int thinning, double step, int64_t* hits,
+                                    int64_t* accepted, double* dist, int flags);
+
 /* ---- a11-a15: quantpy/tomography/process.py -------------------------------------------------- */
 /* Process tomography of an n-qubit channel (handle created with n_qubits = n; n <= 3: 'lifp', the projections and
  * what builds on them ('states', the bootstrap), 'pgdb' and the process chain all run for n <= 3; at n = 3 through the

@@ -65,6 +65,12 @@ SIGNATURES = {
                                     _c_dbl, _vp, _vp, _vp, _c_int]),
     "qt_mhmc_state_metric_hits": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _c_int,
                                            _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
+    "qt_mhmc_draws_dim": (_c_int, [_vp, _c_int, ctypes.c_uint64, ctypes.c_uint64, _c_int, ctypes.c_uint32, _c_int, _vp, _vp,
+                                   _c_int]),
+    "qt_mhmc_state_large_hits": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _c_int, _c_int,
+                                          _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
+    "qt_mhmc_state_large_metric_hits": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                                 _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
     "qt_lin_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_int]),
     "qt_mle_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _c_int]),

@@ -49,11 +49,34 @@ struct MetricDim {
     c.sm = smem;
     c.tol2 = jtol2;
   }
+  // The same context with the two images and the reduction slots wherever the caller has them: a kernel that holds more
+  // in LDS than a metric (the n = 4, 5 chain of qt_mhmc_state_large.h) lends the scratch it already has.  A type of its own,
+  // and every function below a template on the context: Ctx and the code of the kernels built on it stay what they were.
+  struct CtxAt {
+    int t, i, j, e;
+    cd *a, *v;  // MAT doubles each
+    double* r;  // [16]
+    double tol2;
+    __device__ __forceinline__ cd* A() const { return a; }
+    __device__ __forceinline__ cd* V() const { return v; }
+    __device__ __forceinline__ double* red() const { return r; }
+  };
+  __device__ __forceinline__ static void make_ctx(CtxAt& c, cd* img_a, cd* img_v, double* red, double jtol2) {
+    c.t = threadIdx.x;
+    c.i = c.t / d;
+    c.j = c.t % d;
+    c.e = c.i * LD + c.j;
+    c.a = img_a;
+    c.v = img_v;
+    c.r = red;
+    c.tol2 = jtol2;
+  }
 
   // Sum over the workgroup, the same bits in every thread (Large::bsum): a wavefront's butterfly, then the NW partials in
   // a fixed order.  Two barriers: the first keeps the partials of the reduction before this one until everybody has read
   // them -- and orders any LDS image access before the call against any after it.
-  __device__ static double bsum(const Ctx& c, double v) {
+  template <class C>
+  __device__ static double bsum(const C& c, double v) {
     v = gsum<64>(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) c.red()[threadIdx.x >> 6] = v;
@@ -80,8 +103,8 @@ struct MetricDim {
   // barrier each: a thread that writes image p in round r + 2 has passed the barrier of round r + 1, which the slowest
   // thread reaches only after its reads of round r.  (The reduction at the head of a sweep, and of the caller behind the
   // loop, starts with a barrier.)
-  template <bool VEC>
-  __device__ __forceinline__ static void sweeps(const Ctx& c, cd& a_io, cd& v_io, double nrm) {
+  template <bool VEC, class C>
+  __device__ __forceinline__ static void sweeps(const C& c, cd& a_io, cd& v_io, double nrm) {
     cd a = a_io, v{0.0, 0.0};
     if constexpr (VEC) v = v_io;  // (without V the caller's object is neither read nor written: it folds away)
     const int i = c.i, j = c.j;
@@ -131,7 +154,8 @@ struct MetricDim {
 
   // Small::trace_dist: sum_i |lambda_i(R - C)| / 2, the imaginary parts of the diagonal dropped; 0 below 1e-15.
   // In: the thread's elements of R and C.  Every thread returns the same bits.
-  __device__ static double trace_dist(const Ctx& c, cd r, cd cen) {
+  template <class C>
+  __device__ static double trace_dist(const C& c, cd r, cd cen) {
     cd a{r.re - cen.re, c.i == c.j ? 0.0 : r.im - cen.im}, v{0.0, 0.0};
     const double n2 = bsum(c, norm2(a));
     sweeps<false>(c, a, v, n2);
@@ -141,7 +165,8 @@ struct MetricDim {
 
   // Small::psd_sqrt: sum_k V_ik sqrt(max(lam_k, 0)) conj(V_jk), real on the diagonal; NaN throughout for a matrix that
   // holds a NaN or an infinity.
-  __device__ static cd psd_sqrt(const Ctx& c, cd a) {
+  template <class C>
+  __device__ static cd psd_sqrt(const C& c, cd a) {
     const int i = c.i, j = c.j;
     cd* Ai = c.A();
     cd* Vi = c.V();
@@ -167,7 +192,8 @@ struct MetricDim {
 
   // Small::infidelity: 1 - (sum_i sqrt(max(mu_i, 0)))^2, mu the eigenvalues of the Hermitian part (real diagonal) of
   // M = S R S; 0 below 1e-15, small negatives included.  In: the thread's elements of R and of S = psd_sqrt(C).
-  __device__ static double infidelity(const Ctx& c, cd r, cd s) {
+  template <class C>
+  __device__ static double infidelity(const C& c, cd r, cd s) {
     const int i = c.i, j = c.j;
     cd* X = c.A();
     cd* Y = c.V();

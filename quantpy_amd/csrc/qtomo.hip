@@ -21,6 +21,7 @@
 #include "qt_lp_large.h"
 #include "qt_metric_dim.h"
 #include "qt_mhmc_state.h"
+#include "qt_mhmc_state_large.h"
 #include "qt_mle_small.h"
 #include "qt_ops.h"
 #include "qt_polytope.h"
@@ -1754,15 +1755,27 @@ int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, ui
   return c.done();
 }
 
-// qt_mhmc_state_hits (`hs`: the metric is not read) and qt_mhmc_state_metric_hits: the same checks, staging and launch
-// plan; the infidelity's roots of the C centres by k_psd_sqrt into metric_ws first, as metric_small has them
+// The device arrays of a fused state chain call, as staged by mhmc_state_hits_impl
+struct MhmcHitsArgs {
+  const int64_t* counts;
+  const double *centres, *x_init, *thresholds;
+  int64_t *hits, *accepted;
+  double* dist;
+  uint32_t burn_steps, n_points, thinning;
+};
+
+// What differs between the entries for n <= 3 and for n = 4, 5: the refusal of the other sizes (a == null) and the kernels
+typedef int (*MhmcHitsLaunch)(qt_handle_t* h, const char* fn, bool hs, int metric, int C, uint64_t seed, uint64_t first_chain,
+                              double step, const MhmcHitsArgs* a);
+
+// The four entries of the fused state chain (`hs`: the metric is not read): the same checks and staging
 static int mhmc_state_hits_impl(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C, const double* centres,
                                 const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
                                 int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
-                                double* dist, int flags) {
+                                double* dist, int flags, MhmcHitsLaunch launch_chains) {
   QT_ENTER(h);
   Call c(h, flags);
-  if (int r = mhmc_device_nq(h, fn)) return r;
+  if (int r = launch_chains(h, fn, hs, metric, C, seed, first_chain, step, nullptr)) return r;  // the sizes this entry serves
   if (int r = need_povm(h)) return r;
   if (!hs && metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
     return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
@@ -1772,48 +1785,54 @@ static int mhmc_state_hits_impl(qt_handle_t* h, const char* fn, bool hs, int met
   if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
     return fail(QT_ERR_ARG, "%s: burn_steps + n_points * thinning must be below 2^32 - 1", fn);
   if (C == 0) return 0;
-  const int64_t* dc;
-  const double *dcen, *dx, *dthr;
-  int64_t *dh, *da;
-  double* ddist;
-  if (int r = c.in(counts, (size_t)C * h->M, &dc)) return r;
-  if (int r = c.in(centres, (size_t)C * h->D * 2, &dcen)) return r;
-  if (int r = c.in(x_init, (size_t)C * h->D, &dx)) return r;
-  if (int r = c.in(thresholds, (size_t)C, &dthr)) return r;
-  if (int r = c.out(hits, (size_t)C, &dh)) return r;
-  if (int r = c.out(accepted, (size_t)C, &da)) return r;
-  if (int r = c.out(dist, (size_t)C * n_points, &ddist)) return r;
-  if (int r = by_nq(h, [&](auto nq) {
-        constexpr int NQ = decltype(nq)::value;
-        if constexpr (NQ <= 3) {
-          using S = qt::Small<NQ>;
-          const Plan p = povm_plan<NQ>(h, C);
-          const uint32_t nb = (uint32_t)burn_steps, np = (uint32_t)n_points, th = (uint32_t)thinning;
-          if (hs)
-            return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, dc, C, dcen, dx, dthr, seed, first_chain, nb, np, th, step, dh,
-                          da, ddist);
-          if (metric == QT_METRIC_TRACE)
-            return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, dc, C, dcen, dx, dthr, seed,
-                          first_chain, nb, np, th, step, dh, da, ddist);
-          HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
-          double* roots = h->metric_ws.as<double>();
-          if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((C + S::TPB - 1) / S::TPB), dim3(S::NT), 0, dcen, C, h->jtol2, roots))
-            return r;
-          return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, dc, C,
-                        static_cast<const double*>(roots), dx, dthr, seed, first_chain, nb, np, th, step, dh, da, ddist);
-        } else {
-          return 0;  // (refused above)
-        }
-      }))
-    return r;
+  MhmcHitsArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t)burn_steps, (uint32_t)n_points,
+                 (uint32_t)thinning};
+  if (int r = c.in(counts, (size_t)C * h->M, &a.counts)) return r;
+  if (int r = c.in(centres, (size_t)C * h->D * 2, &a.centres)) return r;
+  if (int r = c.in(x_init, (size_t)C * h->D, &a.x_init)) return r;
+  if (int r = c.in(thresholds, (size_t)C, &a.thresholds)) return r;
+  if (int r = c.out(hits, (size_t)C, &a.hits)) return r;
+  if (int r = c.out(accepted, (size_t)C, &a.accepted)) return r;
+  if (int r = c.out(dist, (size_t)C * n_points, &a.dist)) return r;
+  if (int r = launch_chains(h, fn, hs, metric, C, seed, first_chain, step, &a)) return r;
   return c.done();
+}
+
+// n <= 3: the plan of the estimators, the infidelity's roots of the C centres by k_psd_sqrt into metric_ws first, as
+// metric_small has them.  a == null: only the refusal of n = 4, 5.
+static int mhmc_state_hits_small(qt_handle_t* h, const char* fn, bool hs, int metric, int C, uint64_t seed, uint64_t first_chain,
+                                 double step, const MhmcHitsArgs* a) {
+  if (!a) return mhmc_device_nq(h, fn);
+  return by_nq(h, [&](auto nq) {
+    constexpr int NQ = decltype(nq)::value;
+    if constexpr (NQ <= 3) {
+      using S = qt::Small<NQ>;
+      const Plan p = povm_plan<NQ>(h, C);
+      if (hs)
+        return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, a->counts, C, a->centres, a->x_init, a->thresholds, seed,
+                      first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits, a->accepted, a->dist);
+      if (metric == QT_METRIC_TRACE)
+        return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, a->counts, C, a->centres, a->x_init,
+                      a->thresholds, seed, first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits, a->accepted,
+                      a->dist);
+      HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
+      double* roots = h->metric_ws.as<double>();
+      if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((C + S::TPB - 1) / S::TPB), dim3(S::NT), 0, a->centres, C, h->jtol2, roots))
+        return r;
+      return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, a->counts, C,
+                    static_cast<const double*>(roots), a->x_init, a->thresholds, seed, first_chain, a->burn_steps, a->n_points,
+                    a->thinning, step, a->hits, a->accepted, a->dist);
+    } else {
+      return 0;  // (refused above)
+    }
+  });
 }
 
 int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
                        const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
                        int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
   return mhmc_state_hits_impl(h, "qt_mhmc_state_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
-                              burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
+                              burn_steps, n_points, thinning, step, hits, accepted, dist, flags, mhmc_state_hits_small);
 }
 
 int qt_mhmc_state_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
@@ -1821,7 +1840,8 @@ int qt_mhmc_state_metric_hits(qt_handle_t* h, int metric, const int64_t* counts,
                               int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
                               double* dist, int flags) {
   return mhmc_state_hits_impl(h, "qt_mhmc_state_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
-                              first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
+                              first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags,
+                              mhmc_state_hits_small);
 }
 
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
@@ -2829,6 +2849,77 @@ int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode
   if (int r = c.out(iters, (size_t)B, &dit)) return r;
   if (int r = project(h, din, B, mode, n_iter, tol, dout, dit, nullptr)) return r;
   return c.done();
+}
+
+// ---- the chain coverage study at n = 4, 5 (qt_mhmc_state_large.h)
+// qt_mhmc_draws with the vector length given: any handle, no POVM
+int qt_mhmc_draws_dim(qt_handle_t* h, int dim, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
+                      double* deltas, double* uniforms, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (dim < 2 || dim > 4096 || (dim & 1)) return fail(QT_ERR_ARG, "qt_mhmc_draws_dim: dim %d (even, 2 .. 4096)", dim);
+  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad mhmc_draws_dim arguments");
+  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "qt_mhmc_draws_dim: steps beyond 2^32 - 2");
+  if (C == 0 || T == 0) return 0;
+  double *dd, *du;
+  const size_t ct = (size_t)C * T;
+  if (int r = c.out(deltas, ct * dim, &dd)) return r;
+  if (int r = c.out(uniforms, ct, &du)) return r;
+  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (dim + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain,
+                     C, first_step, T, dim, dd, du))
+    return r;
+  return c.done();
+}
+
+// qt_mhmc_state_hits and qt_mhmc_state_metric_hits for n = 4, 5 handles (mhmc_state_hits_impl): one workgroup per chain on
+// the plan of qt_mhmc_state at these sizes, the infidelity's roots of the C centres by k_psd_sqrt_dim into metric_ws first,
+// as metric_dim has them.  a == null: only the refusal of n <= 3.  (These stand behind every older entry: the device code
+// of a kernel is laid out where its first launch is compiled, so the kernels that were here before stay where they were.)
+static int mhmc_state_hits_large(qt_handle_t* h, const char* fn, bool hs, int metric, int C, uint64_t seed, uint64_t first_chain,
+                                 double step, const MhmcHitsArgs* a) {
+  if (!a) {
+    if (h->nq > 3) return 0;
+    return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 4, 5 (got %d): the entry for n <= 3 is %s", fn, h->nq,
+                hs ? "qt_mhmc_state_hits" : "qt_mhmc_state_metric_hits");
+  }
+  return by_nq(h, [&](auto nq) {
+    constexpr int NQ = decltype(nq)::value;
+    if constexpr (NQ >= 4) {
+      using S = qt::Large<NQ>;
+      const Plan p = povm_plan<NQ>(h, C);
+      if (hs)
+        return launch(h, qt::k_mhmc_state_large_hits<NQ>, p, p.pv, a->counts, C, a->centres, a->x_init, a->thresholds, seed,
+                      first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits, a->accepted, a->dist);
+      if (metric == QT_METRIC_TRACE)
+        return launch(h, qt::k_mhmc_state_large_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, a->counts, C, a->centres,
+                      a->x_init, a->thresholds, seed, first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits,
+                      a->accepted, a->dist);
+      HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
+      double* roots = h->metric_ws.as<double>();
+      if (int r = launch(h, qt::k_psd_sqrt_dim<S::d>, dim3(C), dim3(S::NT), 0, a->centres, C, h->jtol2, roots)) return r;
+      return launch(h, qt::k_mhmc_state_large_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, a->counts, C,
+                    static_cast<const double*>(roots), a->x_init, a->thresholds, seed, first_chain, a->burn_steps, a->n_points,
+                    a->thinning, step, a->hits, a->accepted, a->dist);
+    } else {
+      return 0;  // (refused above)
+    }
+  });
+}
+
+int qt_mhmc_state_large_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
+                             const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                             int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  return mhmc_state_hits_impl(h, "qt_mhmc_state_large_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
+                              burn_steps, n_points, thinning, step, hits, accepted, dist, flags, mhmc_state_hits_large);
+}
+
+int qt_mhmc_state_large_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                                    const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                    int burn_steps, int n_points, int thinning, double step, int64_t* hits,
+                                    int64_t* accepted, double* dist, int flags) {
+  return mhmc_state_hits_impl(h, "qt_mhmc_state_large_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
+                              first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags,
+                              mhmc_state_hits_large);
 }
 
 }  // extern "C"

@@ -705,6 +705,23 @@ class Engine:
                                          _ptr(uniforms), flags))
         return deltas, uniforms
 
+    def mhmc_draws_dim(self, dim, seed, chains, steps, first_chain=0, first_step=0, out=None):
+        """`mhmc_draws` with the vector length `dim` given (qt_mhmc_draws_dim; even, 2 .. 4096) on an engine of any size:
+        (deltas (chains, steps, dim), uniforms (chains, steps)).  dim = D = 256, 1024 feeds `mhmc_state` the numbers of
+        `mhmc_state_large_hits`; dim = D at n <= 3 gives the bits of `mhmc_draws`."""
+        dim, chains, steps = int(dim), int(chains), int(steps)
+        if out is not None:
+            self._dev_call()
+            deltas, uniforms = out
+            assert deltas.numel() == chains * steps * dim and uniforms.numel() == chains * steps
+            flags = _capi.QT_DEVICE_PTR
+        else:
+            deltas, uniforms = np.empty((chains, steps, max(dim, 0))), np.empty((chains, steps))
+            flags = _capi.QT_HOST_PTR
+        self._chk(self.lib.qt_mhmc_draws_dim(self._h, dim, int(seed), int(first_chain), chains, int(first_step), steps,
+                                             _ptr(deltas), _ptr(uniforms), flags))
+        return deltas, uniforms
+
     def mhmc_state_hits(self, counts, centres, x_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain=0,
                         return_dist=False, metric=None):
         """One Metropolis-Hastings chain per trial with its random numbers drawn on the device and nothing of the chain
@@ -717,6 +734,23 @@ class Engine:
         n <= 3.  metric='trace' / 'if': the same chains with the distance `metric_dist` returns for a kept state and
         centres[i] (qt_mhmc_state_metric_hits); None: Hilbert-Schmidt."""
         code = None if metric is None else self._metric_code(metric)
+        return self._mhmc_state_hits("qt_mhmc_state_hits", "qt_mhmc_state_metric_hits", code, counts, centres, x_init,
+                                     thresholds, seed, burn_steps, n_points, thinning, step, first_chain, return_dist)
+
+    def mhmc_state_large_hits(self, counts, centres, x_init, thresholds, seed, burn_steps, n_points, thinning, step,
+                              first_chain=0, return_dist=False, metric=None):
+        """`mhmc_state_hits` for n = 4, 5 (qt_mhmc_state_large_hits): the same arguments and results, one workgroup per
+        chain drawing the numbers of `mhmc_draws_dim(D, ...)`, the steps of `mhmc_state` at these sizes, a kept state's
+        Hilbert-Schmidt distance as `hs_dist` defines it.  metric='trace' / 'if': the distance `metric_dist_dim` returns
+        for a kept state and centres[i] (qt_mhmc_state_large_metric_hits).  n <= 3 is refused: `mhmc_state_hits`."""
+        code = None if metric is None else self._metric_code(metric)
+        return self._mhmc_state_hits("qt_mhmc_state_large_hits", "qt_mhmc_state_large_metric_hits", code, counts, centres,
+                                     x_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain, return_dist)
+
+    def _mhmc_state_hits(self, entry, metric_entry, code, counts, centres, x_init, thresholds, seed, burn_steps, n_points,
+                         thinning, step, first_chain, return_dist):
+        """The argument handling of `mhmc_state_hits` and `mhmc_state_large_hits`.  code None: the library's `entry`
+        (Hilbert-Schmidt); else `metric_entry`, which takes the metric's code behind the handle."""
         if _is_dev(counts):
             import torch
 
@@ -743,9 +777,9 @@ class Engine:
         tail = (_ptr(counts), nchain, _ptr(centres), _ptr(x_init), _ptr(thresholds), int(seed), int(first_chain),
                 int(burn_steps), int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags)
         if code is None:
-            self._chk(self.lib.qt_mhmc_state_hits(self._h, *tail))
+            self._chk(getattr(self.lib, entry)(self._h, *tail))
         else:
-            self._chk(self.lib.qt_mhmc_state_metric_hits(self._h, code, *tail))
+            self._chk(getattr(self.lib, metric_entry)(self._h, code, *tail))
         return (hits, acc, dist) if return_dist else (hits, acc)
 
     def mle_dev(self, counts, rho, init="lin", max_iter=100, tol=1e-3, nit=None, nfev=None, fun=None, status=None):

@@ -229,6 +229,14 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
     distance) with every sample measured as `metric_dist` measures it, by the same device functions in the kernel that
     holds the sample (include/qtomo.h: qt_mhmc_state_metric_hits).
 
+    Four- and five-qubit states run the same study through `Engine.mhmc_state_large_hits` (one workgroup per chain;
+    include/qtomo.h: qt_mhmc_state_large_hits, qt_mhmc_state_large_metric_hits) with delta_t from `Engine.hs_dist` or
+    `Engine.metric_dist_dim`; arguments, keying, sharding and details are those above.  At the default 1000 shots per
+    setting the 'lin' estimates of a four- or five-qubit state are not positive definite even for a state as mixed as
+    GHZ / 2 + 1 / 2d (smallest eigenvalue of the unclipped estimate about -0.003 at n = 4 and -0.02 at n = 5, against
+    +0.020 at 10 000 and +0.012 at 100 000 shots), so the study raises LinAlgError there, as stated above.  The remedy:
+    more shots (`n_measurements`), or method='mle'.
+
     `sampler`, `seed`, `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the
     accepted post-burn steps / (n_points * thinning), the reference's definition."""
     _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
@@ -247,7 +255,12 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
     if info is not None and np.any(info["status"] == 1):
         raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
     eng = tmg._engine()
-    delta = eng.hs_dist(rho, state.matrix) if metric is None else eng.metric_dist(rho, state.matrix, metric)
+    large = eng.d > 8  # n = 4, 5: one workgroup per chain, the metrics of qt_metric_dist_dim
+    if metric is None:
+        delta = eng.hs_dist(rho, state.matrix)
+    else:
+        delta = (eng.metric_dist_dim if large else eng.metric_dist)(rho, state.matrix, metric)
+    chain_hits = eng.mhmc_state_large_hits if large else eng.mhmc_state_hits
     x0, status = eng.chol_param(rho)
     # ... and none for the estimate less the floor: its smallest eigenvalue is not above _PD_FLOOR (a NaN is refused too)
     _, shifted = eng.chol_param(rho - _PD_FLOOR * np.eye(rho.shape[-1]))
@@ -259,9 +272,8 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
     lo, hi = qdist.shard_bounds(n_iter)
     both = np.zeros((2, n_iter), dtype=np.int64)
     if hi > lo:
-        both[0, lo:hi], both[1, lo:hi] = eng.mhmc_state_hits(counts[lo:hi], rho[lo:hi], x0[lo:hi], delta[lo:hi], key,
-                                                             burn_steps, n_points, thinning, step, first_chain=lo,
-                                                             metric=metric)
+        both[0, lo:hi], both[1, lo:hi] = chain_hits(counts[lo:hi], rho[lo:hi], x0[lo:hi], delta[lo:hi], key, burn_steps,
+                                                    n_points, thinning, step, first_chain=lo, metric=metric)
     if qdist.world()[1] > 1:
         both = qdist.allgather_equal(both).sum(0)
     hits, accepted = both
