@@ -1285,6 +1285,51 @@ int metric_dim(qt_handle_t* h, int metric, const double* dr, int B, const double
                 static_cast<const double*>(roots), G, g0, h->jtol2, dd);
 }
 
+// The device arrays of a fused chain call, as staged by mhmc_hits_call
+struct MhmcHitsArgs {
+  const int64_t* counts;
+  const double *centres, *init, *thresholds;
+  int64_t *hits, *accepted;
+  double* dist;
+  uint32_t burn_steps, n_points, thinning;
+};
+
+// Elements per chain of its counts, of its centre and of its starting point
+struct MhmcHitsElems {
+  size_t counts, centre, init;
+};
+
+// The six entries of the fused chains (`hs`: the metric is not read): the same checks and staging.  `refuse(elems)` makes
+// the entry's own refusals, in its order, and states the sizes of a chain; `launch_chains(args)` enqueues its kernels.
+template <class Refuse, class Launch>
+int mhmc_hits_call(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C, const double* centres,
+                   const double* init, const double* thresholds, int burn_steps, int n_points, int thinning, int64_t* hits,
+                   int64_t* accepted, double* dist, int flags, Refuse refuse, Launch launch_chains) {
+  QT_ENTER(h);
+  Call c(h, flags, fn);
+  MhmcHitsElems n{};
+  if (int r = refuse(n)) return r;
+  if (!hs && metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
+    return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
+  if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
+      (C > 0 && (!counts || !centres || !init || !thresholds || !hits || !accepted)))
+    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
+  if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
+    return fail(QT_ERR_ARG, "%s: burn_steps + n_points * thinning must be below 2^32 - 1", fn);
+  if (C == 0) return 0;
+  MhmcHitsArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t)burn_steps, (uint32_t)n_points,
+                 (uint32_t)thinning};
+  if (int r = c.in(counts, (size_t)C * n.counts, &a.counts)) return r;
+  if (int r = c.in(centres, (size_t)C * n.centre, &a.centres)) return r;
+  if (int r = c.in(init, (size_t)C * n.init, &a.init)) return r;
+  if (int r = c.in(thresholds, (size_t)C, &a.thresholds)) return r;
+  if (int r = c.out(hits, (size_t)C, &a.hits)) return r;
+  if (int r = c.out(accepted, (size_t)C, &a.accepted)) return r;
+  if (int r = c.out(dist, (size_t)C * n_points, &a.dist)) return r;
+  if (int r = launch_chains(a)) return r;
+  return c.done();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1731,117 +1776,88 @@ int qt_mhmc_state(qt_handle_t* h, const int64_t* counts, int C, const double* x_
   return c.done();
 }
 
-// The two entries of the chain whose numbers are drawn on the device (qt_sampler::mhmc_draw): n <= 3
+// The entries of the state chain whose numbers are drawn on the device (qt_sampler::mhmc_draw) that serve n <= 3 only
 static int mhmc_device_nq(const qt_handle_t* h, const char* fn) {
   if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 1..3 (got %d): the device-drawn chain has no n = 4, 5 kernel", fn, h->nq);
   return 0;
 }
 
-int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T, double* deltas,
-                  double* uniforms, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (int r = mhmc_device_nq(h, "qt_mhmc_draws")) return r;
-  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad mhmc_draws arguments");
-  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "qt_mhmc_draws: steps beyond 2^32 - 2");
+// The three entries of the draws, behind their own preconditions: deltas[C][T][len] and uniforms[C][T]
+static int mhmc_draws_call(qt_handle_t* h, const char* fn, int len, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step,
+                           int T, double* deltas, double* uniforms, int flags) {
+  Call c(h, flags, fn);
+  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
+  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "%s: steps beyond 2^32 - 2", fn);
   if (C == 0 || T == 0) return 0;
   double *dd, *du;
   const size_t ct = (size_t)C * T;
-  if (int r = c.out(deltas, ct * h->D, &dd)) return r;
+  if (int r = c.out(deltas, ct * len, &dd)) return r;
   if (int r = c.out(uniforms, ct, &du)) return r;
-  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (h->D + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain,
-                     C, first_step, T, h->D, dd, du))
+  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (len + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain,
+                     C, first_step, T, len, dd, du))
     return r;
   return c.done();
 }
 
-// The device arrays of a fused state chain call, as staged by mhmc_state_hits_impl
-struct MhmcHitsArgs {
-  const int64_t* counts;
-  const double *centres, *x_init, *thresholds;
-  int64_t *hits, *accepted;
-  double* dist;
-  uint32_t burn_steps, n_points, thinning;
-};
-
-// What differs between the entries for n <= 3 and for n = 4, 5: the refusal of the other sizes (a == null) and the kernels
-typedef int (*MhmcHitsLaunch)(qt_handle_t* h, const char* fn, bool hs, int metric, int C, uint64_t seed, uint64_t first_chain,
-                              double step, const MhmcHitsArgs* a);
-
-// The four entries of the fused state chain (`hs`: the metric is not read): the same checks and staging
-static int mhmc_state_hits_impl(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C, const double* centres,
-                                const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
-                                int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
-                                double* dist, int flags, MhmcHitsLaunch launch_chains) {
+int qt_mhmc_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T, double* deltas,
+                  double* uniforms, int flags) {
   QT_ENTER(h);
-  Call c(h, flags);
-  if (int r = launch_chains(h, fn, hs, metric, C, seed, first_chain, step, nullptr)) return r;  // the sizes this entry serves
-  if (int r = need_povm(h)) return r;
-  if (!hs && metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
-    return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
-  if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
-      (C > 0 && (!counts || !centres || !x_init || !thresholds || !hits || !accepted)))
-    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
-  if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
-    return fail(QT_ERR_ARG, "%s: burn_steps + n_points * thinning must be below 2^32 - 1", fn);
-  if (C == 0) return 0;
-  MhmcHitsArgs a{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t)burn_steps, (uint32_t)n_points,
-                 (uint32_t)thinning};
-  if (int r = c.in(counts, (size_t)C * h->M, &a.counts)) return r;
-  if (int r = c.in(centres, (size_t)C * h->D * 2, &a.centres)) return r;
-  if (int r = c.in(x_init, (size_t)C * h->D, &a.x_init)) return r;
-  if (int r = c.in(thresholds, (size_t)C, &a.thresholds)) return r;
-  if (int r = c.out(hits, (size_t)C, &a.hits)) return r;
-  if (int r = c.out(accepted, (size_t)C, &a.accepted)) return r;
-  if (int r = c.out(dist, (size_t)C * n_points, &a.dist)) return r;
-  if (int r = launch_chains(h, fn, hs, metric, C, seed, first_chain, step, &a)) return r;
-  return c.done();
+  if (int r = mhmc_device_nq(h, "qt_mhmc_draws")) return r;
+  return mhmc_draws_call(h, "qt_mhmc_draws", h->D, seed, first_chain, C, first_step, T, deltas, uniforms, flags);
 }
 
-// n <= 3: the plan of the estimators, the infidelity's roots of the C centres by k_psd_sqrt into metric_ws first, as
-// metric_small has them.  a == null: only the refusal of n = 4, 5.
-static int mhmc_state_hits_small(qt_handle_t* h, const char* fn, bool hs, int metric, int C, uint64_t seed, uint64_t first_chain,
-                                 double step, const MhmcHitsArgs* a) {
-  if (!a) return mhmc_device_nq(h, fn);
-  return by_nq(h, [&](auto nq) {
-    constexpr int NQ = decltype(nq)::value;
-    if constexpr (NQ <= 3) {
-      using S = qt::Small<NQ>;
-      const Plan p = povm_plan<NQ>(h, C);
-      if (hs)
-        return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, a->counts, C, a->centres, a->x_init, a->thresholds, seed,
-                      first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits, a->accepted, a->dist);
-      if (metric == QT_METRIC_TRACE)
-        return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, a->counts, C, a->centres, a->x_init,
-                      a->thresholds, seed, first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits, a->accepted,
-                      a->dist);
-      HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
-      double* roots = h->metric_ws.as<double>();
-      if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((C + S::TPB - 1) / S::TPB), dim3(S::NT), 0, a->centres, C, h->jtol2, roots))
-        return r;
-      return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, a->counts, C,
-                    static_cast<const double*>(roots), a->x_init, a->thresholds, seed, first_chain, a->burn_steps, a->n_points,
-                    a->thinning, step, a->hits, a->accepted, a->dist);
-    } else {
-      return 0;  // (refused above)
-    }
-  });
+// qt_mhmc_state_hits and qt_mhmc_state_metric_hits (mhmc_hits_call), n <= 3: the plan of the estimators, the infidelity's
+// roots of the C centres by k_psd_sqrt into metric_ws first, as metric_small has them
+static int mhmc_state_hits_small(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C, const double* centres,
+                                 const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                 int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                                 double* dist, int flags) {
+  auto refuse = [&](MhmcHitsElems& n) {
+    if (int r = mhmc_device_nq(h, fn)) return r;
+    n = {(size_t)h->M, (size_t)h->D * 2, (size_t)h->D};
+    return need_povm(h);
+  };
+  auto launch_chains = [&](const MhmcHitsArgs& a) {
+    return by_nq(h, [&](auto nq) {
+      constexpr int NQ = decltype(nq)::value;
+      if constexpr (NQ <= 3) {
+        using S = qt::Small<NQ>;
+        const Plan p = povm_plan<NQ>(h, C);
+        if (hs)
+          return launch(h, qt::k_mhmc_state_hits<NQ>, p, p.pv, a.counts, C, a.centres, a.init, a.thresholds, seed, first_chain,
+                        a.burn_steps, a.n_points, a.thinning, step, a.hits, a.accepted, a.dist);
+        if (metric == QT_METRIC_TRACE)
+          return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, a.counts, C, a.centres, a.init,
+                        a.thresholds, seed, first_chain, a.burn_steps, a.n_points, a.thinning, step, a.hits, a.accepted, a.dist);
+        HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
+        double* roots = h->metric_ws.as<double>();
+        if (int r = launch(h, qt::k_psd_sqrt<NQ>, dim3((C + S::TPB - 1) / S::TPB), dim3(S::NT), 0, a.centres, C, h->jtol2, roots))
+          return r;
+        return launch(h, qt::k_mhmc_state_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, a.counts, C,
+                      static_cast<const double*>(roots), a.init, a.thresholds, seed, first_chain, a.burn_steps, a.n_points,
+                      a.thinning, step, a.hits, a.accepted, a.dist);
+      } else {
+        return 0;  // (refused above)
+      }
+    });
+  };
+  return mhmc_hits_call(h, fn, hs, metric, counts, C, centres, x_init, thresholds, burn_steps, n_points, thinning, hits, accepted,
+                        dist, flags, refuse, launch_chains);
 }
 
 int qt_mhmc_state_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
                        const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
                        int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
-  return mhmc_state_hits_impl(h, "qt_mhmc_state_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
-                              burn_steps, n_points, thinning, step, hits, accepted, dist, flags, mhmc_state_hits_small);
+  return mhmc_state_hits_small(h, "qt_mhmc_state_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
+                               burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
 }
 
 int qt_mhmc_state_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
                               const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
                               int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
                               double* dist, int flags) {
-  return mhmc_state_hits_impl(h, "qt_mhmc_state_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
-                              first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags,
-                              mhmc_state_hits_small);
+  return mhmc_state_hits_small(h, "qt_mhmc_state_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
+                               first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
 }
 
 int qt_mle_batch(qt_handle_t* h, const int64_t* counts, int B, int init, int max_iter, double tol, double* rho,
@@ -1890,20 +1906,11 @@ int qt_group_hits(qt_handle_t* h, const double* dist, int B, int G, const double
 }
 
 int qt_hs_dist_batch(qt_handle_t* h, const double* rho, const double* centre, int B, double* dist, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (B < 0 || (B > 0 && (!rho || !centre || !dist))) return fail(QT_ERR_ARG, "bad hs_dist arguments");
-  if (B == 0) return 0;
-  const double *dr, *dcn;
-  double* dd;
-  if (int r = c.in(rho, (size_t)B * h->D * 2, &dr)) return r;
-  if (int r = c.in(centre, (size_t)h->D * 2, &dcn)) return r;
-  if (int r = c.out(dist, (size_t)B, &dd)) return r;
-  hipLaunchKernelGGL(qt::k_hs_dist, dim3(B), dim3(64), 0, h->stream, h->d, dr, dcn, 1, 0, B, dd);
-  return c.done();
+  if (!h) return fail(QT_ERR_ARG, "null handle");
+  return qt_hs_dist_dim(h, h->d, rho, centre, B, dist, flags);
 }
 
-// the same for dim x dim matrices of any size (the Choi matrices of an n-qubit channel are 4^n x 4^n: 2n-qubit objects)
+// for dim x dim matrices of any size (the Choi matrices of an n-qubit channel are 4^n x 4^n: 2n-qubit objects)
 int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* centre, int B, double* dist, int flags) {
   QT_ENTER(h);
   Call c(h, flags);
@@ -1919,48 +1926,17 @@ int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* cen
   return c.done();
 }
 
-// geometry.py:23-56 for a batch against a table of centres, n <= 3 (k_metric_dist; the infidelity's roots of the centres
-// by k_psd_sqrt, once per call).  Reads no POVM.
-int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, int B, const double* centres, int G, int g0,
-                               double* dist, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "qt_metric_dist_group_batch: n_qubits %d (supported: 1, 2, 3)", h->nq);
-  if (metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
-    return fail(QT_ERR_ARG, "qt_metric_dist_group_batch: unknown metric %d", metric);
-  if (B < 0 || G < 1 || g0 < 0 || g0 >= G || (B > 0 && (!rho || !centres || !dist)))
-    return fail(QT_ERR_ARG, "bad metric_dist_group_batch arguments (B = %d, G = %d, g0 = %d)", B, G, g0);
-  if (B == 0) return 0;
-  const double *dr, *dcn;
-  double* dd;
-  const size_t ne2 = (size_t)h->D * 2;
-  if (int r = c.in(rho, (size_t)B * ne2, &dr)) return r;
-  if (int r = c.in(centres, (size_t)G * ne2, &dcn)) return r;
-  if (int r = c.out(dist, (size_t)B, &dd)) return r;
-  if (int r = by_nq(h, [&](auto nq) {
-        constexpr int NQ = decltype(nq)::value;
-        if constexpr (NQ <= 3) {
-          return metric_small<NQ>(h, metric, dr, B, dcn, G, g0, dd);
-        } else {
-          return fail(QT_ERR_UNSUPPORTED, "n_qubits %d", NQ);
-        }
-      }))
-    return r;
-  return c.done();
-}
-
-// The same for dim x dim matrices on any handle, whatever its n_qubits: dim 2, 4, 8 by the kernels above (the same bits),
-// dim 16, 32 by one workgroup per trial (qt_metric_dim.h).  Reads no POVM.
-int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
-                       double* dist, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
-    return fail(QT_ERR_ARG, "qt_metric_dist_dim: unknown metric %d", metric);
+// geometry.py:23-56 for a batch of dim x dim matrices against a table of centres, behind QT_ENTER: dim 2, 4, 8 by
+// k_metric_dist, dim 16, 32 by one workgroup per trial (qt_metric_dim.h); the infidelity's roots of the centres once per
+// call.  Reads no POVM.  `fn`, the entry, words the errors.
+static int metric_dist_call(qt_handle_t* h, const char* fn, int metric, int dim, const double* rho, int B, const double* centres,
+                            int G, int g0, double* dist, int flags) {
+  Call c(h, flags, fn);
+  if (metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY) return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
   if (dim != 2 && dim != 4 && dim != 8 && dim != 16 && dim != 32)
-    return fail(QT_ERR_UNSUPPORTED, "qt_metric_dist_dim: dim %d (supported: 2, 4, 8, 16, 32)", dim);
+    return fail(QT_ERR_UNSUPPORTED, "%s: dim %d (supported: 2, 4, 8, 16, 32)", fn, dim);
   if (B < 0 || G < 1 || g0 < 0 || g0 >= G || (B > 0 && (!rho || !centres || !dist)))
-    return fail(QT_ERR_ARG, "bad metric_dist_dim arguments (B = %d, G = %d, g0 = %d)", B, G, g0);
+    return fail(QT_ERR_ARG, "bad %s arguments (B = %d, G = %d, g0 = %d)", fn + 3, B, G, g0);
   if (B == 0) return 0;
   const double *dr, *dcn;
   double* dd;
@@ -1978,6 +1954,21 @@ int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, i
   }
   if (r) return r;
   return c.done();
+}
+
+// ... of the handle's own size, n <= 3
+int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, int B, const double* centres, int G, int g0,
+                               double* dist, int flags) {
+  QT_ENTER(h);
+  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "qt_metric_dist_group_batch: n_qubits %d (supported: 1, 2, 3)", h->nq);
+  return metric_dist_call(h, "qt_metric_dist_group_batch", metric, h->d, rho, B, centres, G, g0, dist, flags);
+}
+
+// ... of any supported size on any handle, whatever its n_qubits (dim 2, 4, 8: the same bits as on a handle of that size)
+int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
+                       double* dist, int flags) {
+  QT_ENTER(h);
+  return metric_dist_call(h, "qt_metric_dist_dim", metric, dim, rho, B, centres, G, g0, dist, flags);
 }
 
 // ---- a16: interval.py:610-612 ------------------------------------------------------------------------
@@ -2725,96 +2716,63 @@ int qt_mhmc_process(qt_handle_t* h, const int64_t* counts, int C, const double* 
   return c.done();
 }
 
-// The two entries of the process chain whose numbers are drawn on the device (qt_sampler::mhmc_draw with vector length
-// D^2): n <= 2, the one-workgroup chain of qt_process.h
-static int mhmc_process_device_nq(const qt_handle_t* h, const char* fn) {
+// What the entries of the process chain whose numbers are drawn on the device (qt_sampler::mhmc_draw with vector length
+// D^2) ask of the handle: n <= 2, the one-workgroup chain of qt_process.h, then a POVM and the input states
+static int mhmc_process_ready(qt_handle_t* h, const char* fn) {
   if (h->nq > 2)
     return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 1..2 (got %d): the device-drawn process chain has no n = 3 kernel", fn,
                 h->nq);
+  if (int r = need_povm(h)) return r;
+  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
   return 0;
 }
 
 int qt_mhmc_process_draws(qt_handle_t* h, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
                           double* deltas, double* uniforms, int flags) {
   QT_ENTER(h);
-  Call c(h, flags);
-  if (int r = mhmc_process_device_nq(h, "qt_mhmc_process_draws")) return r;
-  if (int r = need_povm(h)) return r;
-  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
-  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad mhmc_process_draws arguments");
-  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "qt_mhmc_process_draws: steps beyond 2^32 - 2");
-  if (C == 0 || T == 0) return 0;
-  double *dd, *du;
-  const size_t ct = (size_t)C * T;
-  const int ne = h->D * h->D;
-  if (int r = c.out(deltas, ct * ne, &dd)) return r;
-  if (int r = c.out(uniforms, ct, &du)) return r;
-  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (ne + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain, C,
-                     first_step, T, ne, dd, du))
-    return r;
-  return c.done();
+  if (int r = mhmc_process_ready(h, "qt_mhmc_process_draws")) return r;
+  return mhmc_draws_call(h, "qt_mhmc_process_draws", h->D * h->D, seed, first_chain, C, first_step, T, deltas, uniforms, flags);
 }
 
-// qt_mhmc_process_hits (`hs`: the metric is not read) and qt_mhmc_process_metric_hits: the same checks and staging; the
-// infidelity's roots of the C centres into metric_ws first, by the set-up kernel of qt_metric_dist_dim at dim = D
+// qt_mhmc_process_hits and qt_mhmc_process_metric_hits (mhmc_hits_call): one workgroup per chain; the infidelity's roots
+// of the C centres into metric_ws first, by the set-up kernel of qt_metric_dist_dim at dim = D
 static int mhmc_process_hits_impl(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C,
                                   const double* centres, const double* choi_init, const double* thresholds, uint64_t seed,
                                   uint64_t first_chain, int burn_steps, int n_points, int thinning, double step, int64_t* hits,
                                   int64_t* accepted, double* dist, int flags) {
-  QT_ENTER(h);
-  Call c(h, flags);
-  if (int r = mhmc_process_device_nq(h, fn)) return r;
-  if (int r = need_povm(h)) return r;
-  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
-  if (!hs && metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY)
-    return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
-  if (C < 0 || burn_steps < 0 || n_points < 0 || thinning < 1 ||
-      (C > 0 && (!counts || !centres || !choi_init || !thresholds || !hits || !accepted)))
-    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
-  if ((uint64_t)burn_steps + (uint64_t)n_points * (uint64_t)thinning >= 0xffffffffull)
-    return fail(QT_ERR_ARG, "%s: burn_steps + n_points * thinning must be below 2^32 - 1", fn);
-  if (C == 0) return 0;
-  const int D = h->D, M = h->M;
-  const size_t ne = (size_t)D * D;
-  const size_t dyn = (size_t)2 * D * M * sizeof(double);
-  if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
-  const int64_t* dc;
-  const double *dcen, *dx, *dthr;
-  int64_t *dh, *da;
-  double* ddist;
-  if (int r = c.in(counts, (size_t)C * D * M, &dc)) return r;
-  if (int r = c.in(centres, (size_t)C * ne * 2, &dcen)) return r;
-  if (int r = c.in(choi_init, (size_t)C * ne * 2, &dx)) return r;
-  if (int r = c.in(thresholds, (size_t)C, &dthr)) return r;
-  if (int r = c.out(hits, (size_t)C, &dh)) return r;
-  if (int r = c.out(accepted, (size_t)C, &da)) return r;
-  if (int r = c.out(dist, (size_t)C * n_points, &ddist)) return r;
-  const dim3 block(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT);
-  const double* lifp = h->proc.lifp.as<double>();
-  const uint32_t nb = (uint32_t)burn_steps, np = (uint32_t)n_points, th = (uint32_t)thinning;
-  if (hs) {
-    if (int r = launch(h, D == 4 ? qt::k_mhmc_process_hits<4> : qt::k_mhmc_process_hits<16>, dim3(C), block, dyn, dc, C, M, lifp,
-                       dx, dcen, dthr, seed, first_chain, nb, np, th, step, dh, da, ddist))
-      return r;
-    return c.done();
-  }
-  if (metric == QT_METRIC_INFIDELITY) {
-    HIPCHK(h->metric_ws.ensure((size_t)C * ne * 2 * sizeof(double)));
-    double* roots = h->metric_ws.as<double>();
-    using S2 = qt::Small<2>;
-    if (int r = D == 4 ? launch(h, qt::k_psd_sqrt<2>, dim3((C + S2::TPB - 1) / S2::TPB), dim3(S2::NT), 0, dcen, C, h->jtol2, roots)
-                       : launch(h, qt::k_psd_sqrt_dim<16>, dim3(C), dim3(qt::MetricDim<16>::NT), 0, dcen, C, h->jtol2, roots))
-      return r;
-    dcen = roots;
-  }
-  auto kernel = metric == QT_METRIC_TRACE
-                    ? (D == 4 ? qt::k_mhmc_process_metric_hits<4, qt::kMetricTrace> : qt::k_mhmc_process_metric_hits<16, qt::kMetricTrace>)
-                    : (D == 4 ? qt::k_mhmc_process_metric_hits<4, qt::kMetricInfidelity>
-                              : qt::k_mhmc_process_metric_hits<16, qt::kMetricInfidelity>);
-  if (int r = launch(h, kernel, dim3(C), block, dyn, dc, C, M, lifp, dx, dcen, dthr, seed, first_chain, nb, np, th, step, h->jtol2,
-                     dh, da, ddist))
-    return r;
-  return c.done();
+  auto refuse = [&](MhmcHitsElems& n) {
+    const size_t ne2 = (size_t)h->D * h->D * 2;
+    n = {(size_t)h->D * h->M, ne2, ne2};
+    return mhmc_process_ready(h, fn);
+  };
+  auto launch_chains = [&](const MhmcHitsArgs& a) {
+    const int D = h->D, M = h->M;
+    const size_t dyn = (size_t)2 * D * M * sizeof(double);
+    if (dyn > 32 * 1024) return fail(QT_ERR_UNSUPPORTED, "POVM has too many rows for the process kernel");
+    const dim3 block(D == 4 ? qt::ProcWG<4>::NT : qt::ProcWG<16>::NT);
+    const double *lifp = h->proc.lifp.as<double>(), *dcen = a.centres;
+    if (hs)
+      return launch(h, D == 4 ? qt::k_mhmc_process_hits<4> : qt::k_mhmc_process_hits<16>, dim3(C), block, dyn, a.counts, C, M, lifp,
+                    a.init, dcen, a.thresholds, seed, first_chain, a.burn_steps, a.n_points, a.thinning, step, a.hits, a.accepted,
+                    a.dist);
+    if (metric == QT_METRIC_INFIDELITY) {
+      HIPCHK(h->metric_ws.ensure((size_t)C * D * D * 2 * sizeof(double)));
+      double* roots = h->metric_ws.as<double>();
+      using S2 = qt::Small<2>;
+      if (int r = D == 4 ? launch(h, qt::k_psd_sqrt<2>, dim3((C + S2::TPB - 1) / S2::TPB), dim3(S2::NT), 0, dcen, C, h->jtol2, roots)
+                         : launch(h, qt::k_psd_sqrt_dim<16>, dim3(C), dim3(qt::MetricDim<16>::NT), 0, dcen, C, h->jtol2, roots))
+        return r;
+      dcen = roots;
+    }
+    auto kernel = metric == QT_METRIC_TRACE
+                      ? (D == 4 ? qt::k_mhmc_process_metric_hits<4, qt::kMetricTrace> : qt::k_mhmc_process_metric_hits<16, qt::kMetricTrace>)
+                      : (D == 4 ? qt::k_mhmc_process_metric_hits<4, qt::kMetricInfidelity>
+                                : qt::k_mhmc_process_metric_hits<16, qt::kMetricInfidelity>);
+    return launch(h, kernel, dim3(C), block, dyn, a.counts, C, M, lifp, a.init, dcen, a.thresholds, seed, first_chain, a.burn_steps,
+                  a.n_points, a.thinning, step, h->jtol2, a.hits, a.accepted, a.dist);
+  };
+  return mhmc_hits_call(h, fn, hs, metric, counts, C, centres, choi_init, thresholds, burn_steps, n_points, thinning, hits, accepted,
+                        dist, flags, refuse, launch_chains);
 }
 
 int qt_mhmc_process_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
@@ -2856,70 +2814,65 @@ int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode
 int qt_mhmc_draws_dim(qt_handle_t* h, int dim, uint64_t seed, uint64_t first_chain, int C, uint32_t first_step, int T,
                       double* deltas, double* uniforms, int flags) {
   QT_ENTER(h);
-  Call c(h, flags);
   if (dim < 2 || dim > 4096 || (dim & 1)) return fail(QT_ERR_ARG, "qt_mhmc_draws_dim: dim %d (even, 2 .. 4096)", dim);
-  if (C < 0 || T < 0 || (C > 0 && T > 0 && (!deltas || !uniforms))) return fail(QT_ERR_ARG, "bad mhmc_draws_dim arguments");
-  if ((uint64_t)first_step + (uint64_t)T >= 0xffffffffull) return fail(QT_ERR_ARG, "qt_mhmc_draws_dim: steps beyond 2^32 - 2");
-  if (C == 0 || T == 0) return 0;
-  double *dd, *du;
-  const size_t ct = (size_t)C * T;
-  if (int r = c.out(deltas, ct * dim, &dd)) return r;
-  if (int r = c.out(uniforms, ct, &du)) return r;
-  if (int r = launch(h, qt_sampler::k_mhmc_draws, dim3(grid_for(ct * (dim + 1), 256, 1 << 16)), dim3(256), 0, seed, first_chain,
-                     C, first_step, T, dim, dd, du))
-    return r;
-  return c.done();
+  return mhmc_draws_call(h, "qt_mhmc_draws_dim", dim, seed, first_chain, C, first_step, T, deltas, uniforms, flags);
 }
 
-// qt_mhmc_state_hits and qt_mhmc_state_metric_hits for n = 4, 5 handles (mhmc_state_hits_impl): one workgroup per chain on
-// the plan of qt_mhmc_state at these sizes, the infidelity's roots of the C centres by k_psd_sqrt_dim into metric_ws first,
-// as metric_dim has them.  a == null: only the refusal of n <= 3.  (These stand behind every older entry: the device code
-// of a kernel is laid out where its first launch is compiled, so the kernels that were here before stay where they were.)
-static int mhmc_state_hits_large(qt_handle_t* h, const char* fn, bool hs, int metric, int C, uint64_t seed, uint64_t first_chain,
-                                 double step, const MhmcHitsArgs* a) {
-  if (!a) {
-    if (h->nq > 3) return 0;
-    return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 4, 5 (got %d): the entry for n <= 3 is %s", fn, h->nq,
-                hs ? "qt_mhmc_state_hits" : "qt_mhmc_state_metric_hits");
-  }
-  return by_nq(h, [&](auto nq) {
-    constexpr int NQ = decltype(nq)::value;
-    if constexpr (NQ >= 4) {
-      using S = qt::Large<NQ>;
-      const Plan p = povm_plan<NQ>(h, C);
-      if (hs)
-        return launch(h, qt::k_mhmc_state_large_hits<NQ>, p, p.pv, a->counts, C, a->centres, a->x_init, a->thresholds, seed,
-                      first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits, a->accepted, a->dist);
-      if (metric == QT_METRIC_TRACE)
-        return launch(h, qt::k_mhmc_state_large_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, a->counts, C, a->centres,
-                      a->x_init, a->thresholds, seed, first_chain, a->burn_steps, a->n_points, a->thinning, step, a->hits,
-                      a->accepted, a->dist);
-      HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
-      double* roots = h->metric_ws.as<double>();
-      if (int r = launch(h, qt::k_psd_sqrt_dim<S::d>, dim3(C), dim3(S::NT), 0, a->centres, C, h->jtol2, roots)) return r;
-      return launch(h, qt::k_mhmc_state_large_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, a->counts, C,
-                    static_cast<const double*>(roots), a->x_init, a->thresholds, seed, first_chain, a->burn_steps, a->n_points,
-                    a->thinning, step, a->hits, a->accepted, a->dist);
-    } else {
-      return 0;  // (refused above)
-    }
-  });
+// qt_mhmc_state_large_hits and qt_mhmc_state_large_metric_hits (mhmc_hits_call), n = 4, 5: one workgroup per chain on the
+// plan of qt_mhmc_state at these sizes, the infidelity's roots of the C centres by k_psd_sqrt_dim into metric_ws first, as
+// metric_dim has them.  (These stand behind every older entry: the kernel templates are instantiated, and their device code
+// laid out, in the order in which this file first names them, so the kernels that were here before stay where they were.)
+static int mhmc_state_hits_large(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C, const double* centres,
+                                 const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                 int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
+                                 double* dist, int flags) {
+  auto refuse = [&](MhmcHitsElems& n) {
+    if (h->nq <= 3)
+      return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 4, 5 (got %d): the entry for n <= 3 is %s", fn, h->nq,
+                  hs ? "qt_mhmc_state_hits" : "qt_mhmc_state_metric_hits");
+    n = {(size_t)h->M, (size_t)h->D * 2, (size_t)h->D};
+    return need_povm(h);
+  };
+  auto launch_chains = [&](const MhmcHitsArgs& a) {
+    return by_nq(h, [&](auto nq) {
+      constexpr int NQ = decltype(nq)::value;
+      if constexpr (NQ >= 4) {
+        using S = qt::Large<NQ>;
+        const Plan p = povm_plan<NQ>(h, C);
+        if (hs)
+          return launch(h, qt::k_mhmc_state_large_hits<NQ>, p, p.pv, a.counts, C, a.centres, a.init, a.thresholds, seed,
+                        first_chain, a.burn_steps, a.n_points, a.thinning, step, a.hits, a.accepted, a.dist);
+        if (metric == QT_METRIC_TRACE)
+          return launch(h, qt::k_mhmc_state_large_metric_hits<NQ, qt::kMetricTrace>, p, p.pv, a.counts, C, a.centres, a.init,
+                        a.thresholds, seed, first_chain, a.burn_steps, a.n_points, a.thinning, step, a.hits, a.accepted, a.dist);
+        HIPCHK(h->metric_ws.ensure((size_t)C * S::D * 2 * sizeof(double)));
+        double* roots = h->metric_ws.as<double>();
+        if (int r = launch(h, qt::k_psd_sqrt_dim<S::d>, dim3(C), dim3(S::NT), 0, a.centres, C, h->jtol2, roots)) return r;
+        return launch(h, qt::k_mhmc_state_large_metric_hits<NQ, qt::kMetricInfidelity>, p, p.pv, a.counts, C,
+                      static_cast<const double*>(roots), a.init, a.thresholds, seed, first_chain, a.burn_steps, a.n_points,
+                      a.thinning, step, a.hits, a.accepted, a.dist);
+      } else {
+        return 0;  // (refused above)
+      }
+    });
+  };
+  return mhmc_hits_call(h, fn, hs, metric, counts, C, centres, x_init, thresholds, burn_steps, n_points, thinning, hits, accepted,
+                        dist, flags, refuse, launch_chains);
 }
 
 int qt_mhmc_state_large_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* x_init,
                              const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
                              int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
-  return mhmc_state_hits_impl(h, "qt_mhmc_state_large_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
-                              burn_steps, n_points, thinning, step, hits, accepted, dist, flags, mhmc_state_hits_large);
+  return mhmc_state_hits_large(h, "qt_mhmc_state_large_hits", true, 0, counts, C, centres, x_init, thresholds, seed, first_chain,
+                               burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
 }
 
 int qt_mhmc_state_large_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
                                     const double* x_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
                                     int burn_steps, int n_points, int thinning, double step, int64_t* hits,
                                     int64_t* accepted, double* dist, int flags) {
-  return mhmc_state_hits_impl(h, "qt_mhmc_state_large_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
-                              first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags,
-                              mhmc_state_hits_large);
+  return mhmc_state_hits_large(h, "qt_mhmc_state_large_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
+                               first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
 }
 
 }  // extern "C"

@@ -425,41 +425,12 @@ class Engine:
         part lies at a Hilbert-Schmidt distance to centres[i] strictly below thresholds[i], accepted[i] = the accepted
         post-burn steps; with return_dist also the kept distances (C, n_points).  counts (C, D, S, K), centres and
         choi_init (C, D, D) complex, thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in
-        stream order).  n <= 2.  metric='trace' / 'if': the same chains with the distance `metric_dist_dim` returns for
+        stream order).  n <= 2.  metric='trace' / 'if': the same chains with the distance `metric_dist` returns for
         the real part of a kept state and centres[i] (qt_mhmc_process_metric_hits); None: Hilbert-Schmidt."""
         code = None if metric is None else self._metric_code(metric)
-        ne = self.D * self.D
-        if _is_dev(counts):
-            import torch
-
-            self._dev_call()
-            flags = _capi.QT_DEVICE_PTR
-            nchain = counts.shape[0]
-            assert all(t.is_contiguous() for t in (counts, centres, choi_init, thresholds))
-            assert counts.dtype == torch.int64 and centres.dtype == torch.complex128
-            assert choi_init.dtype == torch.complex128 and thresholds.dtype == torch.float64
-            assert counts.numel() == nchain * self.D * self.S * self.K
-            assert centres.numel() == nchain * ne and choi_init.numel() == nchain * ne and thresholds.numel() == nchain
-            hits = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
-            acc = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
-            dist = torch.empty((nchain, int(n_points)), dtype=torch.float64, device=counts.device) if return_dist else None
-        else:
-            flags = _capi.QT_HOST_PTR
-            counts = _i64(counts).reshape(-1, self.D, self.S, self.K)
-            nchain = counts.shape[0]
-            centres = _c128(centres).reshape(nchain, self.D, self.D)
-            choi_init = _c128(choi_init).reshape(nchain, self.D, self.D)
-            thresholds = _f64(thresholds).reshape(nchain)
-            hits = np.zeros(nchain, dtype=np.int64)
-            acc = np.zeros(nchain, dtype=np.int64)
-            dist = np.empty((nchain, int(n_points))) if return_dist else None
-        tail = (_ptr(counts), nchain, _ptr(centres), _ptr(choi_init), _ptr(thresholds), int(seed), int(first_chain),
-                int(burn_steps), int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags)
-        if code is None:
-            self._chk(self.lib.qt_mhmc_process_hits(self._h, *tail))
-        else:
-            self._chk(self.lib.qt_mhmc_process_metric_hits(self._h, code, *tail))
-        return (hits, acc, dist) if return_dist else (hits, acc)
+        return self._chain_hits("qt_mhmc_process", code, ((self.D, self.S, self.K), (self.D, self.D), (self.D, self.D)), counts,
+                                centres, choi_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain,
+                                return_dist)
 
     def lifp_dev(self, counts, choi, cptp=True, iters=None, status=None):
         self._dev_call()
@@ -708,7 +679,7 @@ class Engine:
     def mhmc_draws_dim(self, dim, seed, chains, steps, first_chain=0, first_step=0, out=None):
         """`mhmc_draws` with the vector length `dim` given (qt_mhmc_draws_dim; even, 2 .. 4096) on an engine of any size:
         (deltas (chains, steps, dim), uniforms (chains, steps)).  dim = D = 256, 1024 feeds `mhmc_state` the numbers of
-        `mhmc_state_large_hits`; dim = D at n <= 3 gives the bits of `mhmc_draws`."""
+        `mhmc_state_hits` at n = 4, 5; dim = D at n <= 3 gives the bits of `mhmc_draws`."""
         dim, chains, steps = int(dim), int(chains), int(steps)
         if out is not None:
             self._dev_call()
@@ -731,55 +702,53 @@ class Engine:
         Hilbert-Schmidt distance to centres[i] lies strictly below thresholds[i], accepted[i] = the accepted post-burn
         steps; with return_dist also the kept distances (C, n_points).  counts (C, S, K), centres (C, d, d) complex,
         x_init (C, D), thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in stream order).
-        n <= 3.  metric='trace' / 'if': the same chains with the distance `metric_dist` returns for a kept state and
-        centres[i] (qt_mhmc_state_metric_hits); None: Hilbert-Schmidt."""
+        metric='trace' / 'if': the same chains with the distance `metric_dist` returns for a kept state and centres[i]
+        (qt_mhmc_state_metric_hits); None: Hilbert-Schmidt.  n = 4, 5 (qt_mhmc_state_large_hits,
+        qt_mhmc_state_large_metric_hits): one workgroup per chain drawing the numbers of `mhmc_draws_dim(D, ...)`, the
+        steps of `mhmc_state` at these sizes.  This method is the place that picks the library's entry by the size."""
         code = None if metric is None else self._metric_code(metric)
-        return self._mhmc_state_hits("qt_mhmc_state_hits", "qt_mhmc_state_metric_hits", code, counts, centres, x_init,
-                                     thresholds, seed, burn_steps, n_points, thinning, step, first_chain, return_dist)
+        return self._chain_hits("qt_mhmc_state" if self.n <= 3 else "qt_mhmc_state_large", code,
+                                ((self.S, self.K), (self.d, self.d), (self.D,)), counts, centres, x_init, thresholds, seed,
+                                burn_steps, n_points, thinning, step, first_chain, return_dist)
 
-    def mhmc_state_large_hits(self, counts, centres, x_init, thresholds, seed, burn_steps, n_points, thinning, step,
-                              first_chain=0, return_dist=False, metric=None):
-        """`mhmc_state_hits` for n = 4, 5 (qt_mhmc_state_large_hits): the same arguments and results, one workgroup per
-        chain drawing the numbers of `mhmc_draws_dim(D, ...)`, the steps of `mhmc_state` at these sizes, a kept state's
-        Hilbert-Schmidt distance as `hs_dist` defines it.  metric='trace' / 'if': the distance `metric_dist_dim` returns
-        for a kept state and centres[i] (qt_mhmc_state_large_metric_hits).  n <= 3 is refused: `mhmc_state_hits`."""
-        code = None if metric is None else self._metric_code(metric)
-        return self._mhmc_state_hits("qt_mhmc_state_large_hits", "qt_mhmc_state_large_metric_hits", code, counts, centres,
-                                     x_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain, return_dist)
+    mhmc_state_large_hits = mhmc_state_hits  # (tests and scripts/ call it by this name at n = 4, 5)
 
-    def _mhmc_state_hits(self, entry, metric_entry, code, counts, centres, x_init, thresholds, seed, burn_steps, n_points,
-                         thinning, step, first_chain, return_dist):
-        """The argument handling of `mhmc_state_hits` and `mhmc_state_large_hits`.  code None: the library's `entry`
-        (Hilbert-Schmidt); else `metric_entry`, which takes the metric's code behind the handle."""
+    def _chain_hits(self, stem, code, shapes, counts, centres, init, thresholds, seed, burn_steps, n_points, thinning, step,
+                    first_chain, return_dist):
+        """The argument handling of `mhmc_state_hits` and `mhmc_process_hits`.  code None: the library's `stem`_hits
+        (Hilbert-Schmidt); else `stem`_metric_hits, which takes the metric's code behind the handle.  `shapes`: those of
+        one chain's counts, of its complex centre and of its starting point (a vector: real; a matrix: complex)."""
+        complex_init = len(shapes[2]) == 2
         if _is_dev(counts):
             import torch
 
             self._dev_call()
             flags = _capi.QT_DEVICE_PTR
             nchain = counts.shape[0]
-            assert all(t.is_contiguous() for t in (counts, centres, x_init, thresholds))
-            assert counts.dtype == torch.int64 and centres.dtype == torch.complex128
-            assert x_init.dtype == torch.float64 and thresholds.dtype == torch.float64
-            assert centres.numel() == nchain * self.D and x_init.numel() == nchain * self.D and thresholds.numel() == nchain
+            args = (counts, centres, init, thresholds)
+            assert all(t.is_contiguous() for t in args)
+            assert [t.dtype for t in args] == [torch.int64, torch.complex128,
+                                               torch.complex128 if complex_init else torch.float64, torch.float64]
+            assert [t.numel() for t in args] == [nchain * int(np.prod(s)) for s in shapes] + [nchain]
             hits = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
             acc = torch.zeros(nchain, dtype=torch.int64, device=counts.device)
             dist = torch.empty((nchain, int(n_points)), dtype=torch.float64, device=counts.device) if return_dist else None
         else:
             flags = _capi.QT_HOST_PTR
-            counts = _i64(counts).reshape(-1, self.S, self.K)
+            counts = _i64(counts).reshape(-1, *shapes[0])
             nchain = counts.shape[0]
-            centres = _c128(centres).reshape(nchain, self.d, self.d)
-            x_init = _f64(x_init).reshape(nchain, self.D)
+            centres = _c128(centres).reshape(nchain, *shapes[1])
+            init = (_c128 if complex_init else _f64)(init).reshape(nchain, *shapes[2])
             thresholds = _f64(thresholds).reshape(nchain)
             hits = np.zeros(nchain, dtype=np.int64)
             acc = np.zeros(nchain, dtype=np.int64)
             dist = np.empty((nchain, int(n_points))) if return_dist else None
-        tail = (_ptr(counts), nchain, _ptr(centres), _ptr(x_init), _ptr(thresholds), int(seed), int(first_chain),
+        tail = (_ptr(counts), nchain, _ptr(centres), _ptr(init), _ptr(thresholds), int(seed), int(first_chain),
                 int(burn_steps), int(n_points), int(thinning), float(step), _ptr(hits), _ptr(acc), _ptr(dist), flags)
         if code is None:
-            self._chk(getattr(self.lib, entry)(self._h, *tail))
+            self._chk(getattr(self.lib, stem + "_hits")(self._h, *tail))
         else:
-            self._chk(getattr(self.lib, metric_entry)(self._h, code, *tail))
+            self._chk(getattr(self.lib, stem + "_metric_hits")(self._h, code, *tail))
         return (hits, acc, dist) if return_dist else (hits, acc)
 
     def mle_dev(self, counts, rho, init="lin", max_iter=100, tol=1e-3, nit=None, nfev=None, fun=None, status=None):
@@ -878,8 +847,8 @@ class Engine:
 
     def hs_dist_dev(self, rho, centre, out):
         self._dev_call()
-        self._chk(self.lib.qt_hs_dist_batch(self._h, _ptr(rho), _ptr(centre), rho.shape[0], _ptr(out),
-                                            _capi.QT_DEVICE_PTR))
+        self._chk(self.lib.qt_hs_dist_dim(self._h, rho.shape[-1], _ptr(rho), _ptr(centre), rho.shape[0], _ptr(out),
+                                          _capi.QT_DEVICE_PTR))
 
     _METRICS = {"trace": _capi.QT_METRIC_TRACE, "if": _capi.QT_METRIC_INFIDELITY}
 
@@ -888,34 +857,24 @@ class Engine:
             raise ValueError(f"metric must be 'trace' or 'if', not {metric!r}")
         return self._METRICS[metric]
 
+    def distance(self, mats, centre, metric=None, g0=0):
+        """The distance of every matrix of `mats` to `centre`, whatever their size and this engine's: metric None / 'hs' is
+        `hs_dist` (one centre), 'trace' / 'if' is `metric_dist` (a centre, or a table read from row g0).  The package
+        measures matrices against a centre through this method and asks about their dimension nowhere else."""
+        if metric is None or metric == "hs":
+            return self.hs_dist(mats, centre)
+        return self.metric_dist(mats, centre, metric, g0)
+
+    def distance_dev(self, mats, centre, dist, metric=None, g0=0):
+        """device-pointer form of `distance`: `hs_dist_dev` or `metric_dist_dev` into dist float64 (B,)"""
+        if metric is None or metric == "hs":
+            return self.hs_dist_dev(mats, centre, dist)
+        return self.metric_dist_dev(mats, centre, dist, metric, g0)
+
     def metric_dist(self, rho, centre, metric, g0=0):
         """Trace distance (metric='trace', geometry.py:23-38) or infidelity ('if', geometry.py:41-56) of Hermitian
-        d x d matrices to `centre`, n <= 3 (qt_metric_dist_group_batch; needs no POVM).  rho (B, d, d) or (d, d); centre
-        (d, d), or a table (G, d, d): trial b is then measured against centre[(g0 + b) % G].  -> (B,) float64, or a
-        float for a single matrix."""
-        code = self._metric_code(metric)
-        rho, cen = _c128(rho), _c128(centre)
-        single = rho.ndim == 2
-        r = rho.reshape(-1, self.d, self.d)
-        assert cen.shape[-2:] == (self.d, self.d) and cen.ndim in (2, 3)
-        out = np.empty(r.shape[0])
-        self._chk(self.lib.qt_metric_dist_group_batch(self._h, code, _ptr(r), r.shape[0], _ptr(cen),
-                                                      cen.shape[0] if cen.ndim == 3 else 1, int(g0), _ptr(out),
-                                                      _capi.QT_HOST_PTR))
-        return out[0] if single else out
-
-    def metric_dist_dev(self, rho, centre, dist, metric, g0=0):
-        """device-pointer form: rho complex128 (B, d, d), centre complex128 (d, d) or (G, d, d), dist float64 (B,) torch
-        CUDA tensors"""
-        code = self._metric_code(metric)
-        self._dev_call()
-        self._chk(self.lib.qt_metric_dist_group_batch(self._h, code, _ptr(rho), rho.shape[0], _ptr(centre),
-                                                      centre.shape[0] if centre.dim() == 3 else 1, int(g0), _ptr(dist),
-                                                      _capi.QT_DEVICE_PTR))
-
-    def metric_dist_dim(self, rho, centre, metric, g0=0):
-        """`metric_dist` for dim x dim matrices whatever this engine's n_qubits, dim = rho.shape[-1] in (2, 4, 8, 16, 32)
-        (qt_metric_dist_dim; needs no POVM): four- and five-qubit states, the Choi matrix of a two-qubit channel.  rho
+        dim x dim matrices to `centre`, whatever this engine's n_qubits, dim = rho.shape[-1] in (2, 4, 8, 16, 32)
+        (qt_metric_dist_dim; needs no POVM): states of up to five qubits, the Choi matrix of a two-qubit channel.  rho
         (B, dim, dim) or (dim, dim); centre (dim, dim), or a table (G, dim, dim): trial b is then measured against
         centre[(g0 + b) % G].  -> (B,) float64, or a float for a single matrix."""
         code = self._metric_code(metric)
@@ -929,7 +888,7 @@ class Engine:
                                               cen.shape[0] if cen.ndim == 3 else 1, int(g0), _ptr(out), _capi.QT_HOST_PTR))
         return out[0] if single else out
 
-    def metric_dist_dim_dev(self, rho, centre, dist, metric, g0=0):
+    def metric_dist_dev(self, rho, centre, dist, metric, g0=0):
         """device-pointer form: rho complex128 (B, dim, dim), centre complex128 (dim, dim) or (G, dim, dim), dist float64
         (B,) torch CUDA tensors"""
         code = self._metric_code(metric)
@@ -937,6 +896,8 @@ class Engine:
         self._chk(self.lib.qt_metric_dist_dim(self._h, code, rho.shape[-1], _ptr(rho), rho.shape[0], _ptr(centre),
                                               centre.shape[0] if centre.dim() == 3 else 1, int(g0), _ptr(dist),
                                               _capi.QT_DEVICE_PTR))
+
+    metric_dist_dim, metric_dist_dim_dev = metric_dist, metric_dist_dev  # (tests and scripts/ call them by these names)
 
     def sort_quantiles(self, dist, conf_levels):
         """interval.py:610-612 on the device: sort `dist` (NumPy array: a sorted copy is returned; torch CUDA

@@ -14,8 +14,8 @@ resamples and writes its distances, and `qt_group_hits` adds, per trial, how man
 to the truth.  Counts and distances never leave HBM; 8 * n_iter bytes come back.
 
 `get_CL_list_state_boot(dst='hs' | 'trace' | 'if')` is that study in any of the three distances: for the trace distance and
-the infidelity a chunk's estimates stay in a device workspace and `qt_metric_dist_group_batch` (n <= 3) /
-`qt_metric_dist_dim` (n = 4, 5) measures them.
+the infidelity a chunk's estimates stay in a device workspace and `Engine.distance_dev` (`qt_metric_dist_dim`) measures
+them.
 
 interval='gamma' is `MomentInterval.radii_batch` over the batch of trials with the same rule.
 
@@ -25,7 +25,7 @@ of them in one launch that draws its own random numbers and returns, per trial, 
 per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.  Both take dst='hs' | 'trace' | 'if': for the
 other two distances the chain kernels run the Jacobi-sweep metrics on the state they hold (`qt_mhmc_state_metric_hits`,
 `qt_mhmc_process_metric_hits`).  `get_CL_list_channel_boot_dst` is the process bootstrap study in any of the three: it
-measures a chunk's Choi matrices with `qt_metric_dist_dim`.
+measures a chunk's Choi matrices the same way.
 """
 import numpy as np
 
@@ -101,6 +101,66 @@ def _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, keyed):
     return counts, (_shared_seed(seed) if keyed else None)
 
 
+def _state_trials(state, n_iter, n_measurements, povm, sampler, seed, keyed, method, init, max_iter, tol):
+    """The trials of a state study -> (tomograph, its engine, counts, resolved seed, estimates); an MLE that could not start
+    raises LinAlgError."""
+    tmg = StateTomograph(state, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, keyed)
+    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
+    if info is not None and np.any(info["status"] == 1):
+        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
+    return tmg, tmg._engine(), counts, base, rho
+
+
+def _chain_arguments(n_iter, n_points, burn_steps, thinning, sampler, dst):
+    """The argument checks of the two chain studies -> (n_iter, n_points, burn_steps, thinning) as ints and the engine's
+    name of `dst` (None: Hilbert-Schmidt)."""
+    _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
+    n_iter, n_points, burn_steps, thinning = int(n_iter), int(n_points), int(burn_steps), int(thinning)
+    if thinning < 1:
+        raise ValueError("thinning must be a positive integer")
+    if burn_steps < 0:
+        raise ValueError("burn_steps must not be negative")
+    if burn_steps + n_points * thinning >= 2**32 - 1:
+        raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
+    metric = _distance_name(dst)
+    return n_iter, n_points, burn_steps, thinning, None if metric == "hs" else metric
+
+
+def _sharded_chain_hits(chain_hits, per_trial, *args, **kwargs):
+    """(hits, accepted) of all trials: this rank's `shard_bounds` of the chains in one `chain_hits` launch on those rows
+    of the `per_trial` arrays, chain = trial index, summed over the ranks."""
+    n_iter = per_trial[0].shape[0]
+    lo, hi = qdist.shard_bounds(n_iter)
+    both = np.zeros((2, n_iter), dtype=np.int64)
+    if hi > lo:
+        both[0, lo:hi], both[1, lo:hi] = chain_hits(*(a[lo:hi] for a in per_trial), *args, first_chain=lo, **kwargs)
+    if qdist.world()[1] > 1:
+        both = qdist.allgather_equal(both).sum(0)
+    return both
+
+
+def _chunk_measure(eng, metric, shape, fused, reconstruct):
+    """`measure(counts, centres, dist, status)` of `_chunked_hits`.  metric None: `fused`, the launch family that forms the
+    Hilbert-Schmidt distances itself.  'trace' / 'if': `reconstruct(counts, mats, status)` into one workspace of `shape`
+    matrices, allocated at the first chunk's size (a chunk starts at a whole resample, so its first row meets centre 0),
+    and `Engine.distance_dev` on it."""
+    if metric is None:
+        return fused
+    work = []
+
+    def measure(counts, centres, dist, status):
+        if not work:
+            import torch
+
+            work.append(torch.empty((counts.shape[0],) + shape, dtype=torch.complex128, device=counts.device))
+        mats = work[0][:counts.shape[0]]
+        reconstruct(counts, mats, status)
+        eng.distance_dev(mats, centres, dist, metric)
+
+    return measure
+
+
 def _result(levels, return_details, **details):
     if return_details:
         return dict(levels=levels, **details)
@@ -138,13 +198,9 @@ def get_CL_list_state(state, n_iter=1000, n_points=1000, interval="gamma", n_mea
     number of resampled distances strictly below delta_t (`levels_from_hits`)."""
     _check_arguments(interval, dst, n_iter, n_points, sampler, ("lin", "mle"), method_boot)
     n_iter, n_points = int(n_iter), int(n_points)
-    tmg = StateTomograph(state, "hs")
-    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, interval == "boot")
-    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
-    if info is not None and np.any(info["status"] == 1):
-        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
-    eng = tmg._engine()
-    delta = eng.hs_dist(rho, state.matrix)
+    tmg, eng, counts, base, rho = _state_trials(state, n_iter, n_measurements, povm, sampler, seed, interval == "boot",
+                                                method, init, max_iter, tol)
+    delta = eng.distance(rho, state.matrix)
     if interval == "gamma":
         cls = np.linspace(0, 1, n_points)
         levels, hits = _levels_from_radii(delta, MomentInterval(tmg).radii_batch(counts, cls), cls)
@@ -173,24 +229,19 @@ def get_CL_list_state_boot(state, n_iter=1000, n_points=1000, n_measurements=100
 
     dst='hs' IS `get_CL_list_state(interval='boot')`: the same call, the same bits.  With 'trace' / 'if' the
     chunk's grouped reconstruction writes its density matrices into a device workspace (`Engine.lin_dev` / `mle_dev`),
-    `Engine.metric_dist_dev` (n <= 3) / `metric_dist_dim_dev` (n = 4, 5) measures resample r of trial t against
-    estimate t (the table of the n_iter estimates, trial b against centre b % n_iter), and `group_hits` counts as
-    before: counts, matrices and distances stay in HBM.  The distances are those of Hermitian arguments by the engine's Jacobi sweeps
-    (include/qtomo.h: qt_metric_dist_group_batch, qt_metric_dist_dim), within 1e-7 (trace) / 1e-6 (infidelity) of
-    `trace_dst` / `if_dst` on the host."""
+    `Engine.distance_dev` measures resample r of trial t against estimate t (the table of the n_iter estimates, trial b
+    against centre b % n_iter), and `group_hits` counts as before: counts, matrices and distances stay in HBM.  The
+    distances are those of Hermitian arguments by the engine's Jacobi sweeps (include/qtomo.h: qt_metric_dist_dim), within
+    1e-7 (trace) / 1e-6 (infidelity) of `trace_dst` / `if_dst` on the host."""
     metric = _distance_name(dst)
     if metric == "hs":
         return get_CL_list_state(state, n_iter, n_points, "boot", n_measurements, method, method_boot, "hs", povm, physical,
                                  init, tol, max_iter, sampler=sampler, seed=seed, chunk=chunk, return_details=return_details)
     _check_arguments("boot", "hs", n_iter, n_points, sampler, ("lin", "mle"), method_boot)
     n_iter, n_points = int(n_iter), int(n_points)
-    tmg = StateTomograph(state, "hs")
-    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
-    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
-    if info is not None and np.any(info["status"] == 1):
-        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
-    eng = tmg._engine()
-    delta = (eng.metric_dist if eng.d <= 8 else eng.metric_dist_dim)(rho, state.matrix, metric)
+    tmg, eng, counts, base, rho = _state_trials(state, n_iter, n_measurements, povm, sampler, seed, True, method, init,
+                                                max_iter, tol)
+    delta = eng.distance(rho, state.matrix, metric)
     key = (base + 1) & (2**64 - 1)
     hits = _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk, metric)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
@@ -224,43 +275,24 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
     and far below the eigenvalues of an estimate of a full-rank state.)  Use a mixed state, or method='mle' on one.
 
     dst (keyword-only) = 'hs' | 'trace' | 'if', or the functions of quantpy_amd.geometry: the distance of the study.  'hs'
-    is the call described above, the same bits.  Otherwise delta_t = `Engine.metric_dist`(estimate_t, state) and the
+    is the call described above, the same bits.  Otherwise delta_t = `Engine.distance`(estimate_t, state, dst) and the
     chains run through `Engine.mhmc_state_hits(metric=dst)`: the same chains (the accepted steps do not depend on the
     distance) with every sample measured as `metric_dist` measures it, by the same device functions in the kernel that
     holds the sample (include/qtomo.h: qt_mhmc_state_metric_hits).
 
-    Four- and five-qubit states run the same study through `Engine.mhmc_state_large_hits` (one workgroup per chain;
-    include/qtomo.h: qt_mhmc_state_large_hits, qt_mhmc_state_large_metric_hits) with delta_t from `Engine.hs_dist` or
-    `Engine.metric_dist_dim`; arguments, keying, sharding and details are those above.  At the default 1000 shots per
-    setting the 'lin' estimates of a four- or five-qubit state are not positive definite even for a state as mixed as
-    GHZ / 2 + 1 / 2d (smallest eigenvalue of the unclipped estimate about -0.003 at n = 4 and -0.02 at n = 5, against
-    +0.020 at 10 000 and +0.012 at 100 000 shots), so the study raises LinAlgError there, as stated above.  The remedy:
-    more shots (`n_measurements`), or method='mle'.
+    Four- and five-qubit states run the same study through the same two methods (one workgroup per chain; include/qtomo.h:
+    qt_mhmc_state_large_hits, qt_mhmc_state_large_metric_hits); arguments, keying, sharding and details are those above.
+    At the default 1000 shots per setting the 'lin' estimates of a four- or five-qubit state are not positive definite
+    even for a state as mixed as GHZ / 2 + 1 / 2d (smallest eigenvalue of the unclipped estimate about -0.003 at n = 4
+    and -0.02 at n = 5, against +0.020 at 10 000 and +0.012 at 100 000 shots), so the study raises LinAlgError there, as
+    stated above.  The remedy: more shots (`n_measurements`), or method='mle'.
 
     `sampler`, `seed`, `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the
     accepted post-burn steps / (n_points * thinning), the reference's definition."""
-    _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
-    n_iter, n_points, burn_steps, thinning = int(n_iter), int(n_points), int(burn_steps), int(thinning)
-    if thinning < 1:
-        raise ValueError("thinning must be a positive integer")
-    if burn_steps < 0:
-        raise ValueError("burn_steps must not be negative")
-    if burn_steps + n_points * thinning >= 2**32 - 1:
-        raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
-    metric = _distance_name(dst)
-    metric = None if metric == "hs" else metric
-    tmg = StateTomograph(state, "hs")
-    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
-    rho, info = tmg.point_estimate_batch(counts, method=method, init=init, max_iter=max_iter, tol=tol)
-    if info is not None and np.any(info["status"] == 1):
-        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
-    eng = tmg._engine()
-    large = eng.d > 8  # n = 4, 5: one workgroup per chain, the metrics of qt_metric_dist_dim
-    if metric is None:
-        delta = eng.hs_dist(rho, state.matrix)
-    else:
-        delta = (eng.metric_dist_dim if large else eng.metric_dist)(rho, state.matrix, metric)
-    chain_hits = eng.mhmc_state_large_hits if large else eng.mhmc_state_hits
+    n_iter, n_points, burn_steps, thinning, metric = _chain_arguments(n_iter, n_points, burn_steps, thinning, sampler, dst)
+    tmg, eng, counts, base, rho = _state_trials(state, n_iter, n_measurements, povm, sampler, seed, True, method, init,
+                                                max_iter, tol)
+    delta = eng.distance(rho, state.matrix, metric)
     x0, status = eng.chol_param(rho)
     # ... and none for the estimate less the floor: its smallest eigenvalue is not above _PD_FLOOR (a NaN is refused too)
     _, shifted = eng.chol_param(rho - _PD_FLOOR * np.eye(rho.shape[-1]))
@@ -269,14 +301,8 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
         raise np.linalg.LinAlgError(f"the estimate of trial {int(np.flatnonzero(bad)[0])} is not positive definite: "
                                     "no Cholesky factor to start its chain from")
     key = (base + 1) & (2**64 - 1)
-    lo, hi = qdist.shard_bounds(n_iter)
-    both = np.zeros((2, n_iter), dtype=np.int64)
-    if hi > lo:
-        both[0, lo:hi], both[1, lo:hi] = chain_hits(counts[lo:hi], rho[lo:hi], x0[lo:hi], delta[lo:hi], key, burn_steps,
-                                                    n_points, thinning, step, first_chain=lo, metric=metric)
-    if qdist.world()[1] > 1:
-        both = qdist.allgather_equal(both).sum(0)
-    hits, accepted = both
+    hits, accepted = _sharded_chain_hits(eng.mhmc_state_hits, (counts, rho, x0, delta), key, burn_steps, n_points, thinning,
+                                         step, metric=metric)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=rho, delta=delta, hits=hits,
                    seed=key, acceptance_rate=accepted / (n_points * thinning))
 
@@ -284,31 +310,22 @@ def get_CL_list_state_mhmc(state, n_iter=1000, n_points=1000, n_measurements=100
 def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init, tol, max_iter, chunk, metric=None):
     """hits[t] = #{ r < n_points : delta_t > hs_dst(estimate(resample r of trial t), estimate_t) }, this rank's shard of
     the resamples chunk by chunk on the device, summed over the ranks.  `metric` = 'trace' / 'if': that distance in the
-    place of hs_dst, formed by `metric_dist_dev` (n = 4, 5: `metric_dist_dim_dev`) from the chunk's density matrices (one
-    workspace, the first chunk's size; a chunk starts at a whole resample, so its first row meets centre 0)."""
+    place of hs_dst, formed from the chunk's density matrices (`_chunk_measure`)."""
     import torch
 
     from . import _capi
 
     n_iter = rho.shape[0]
     pvals = np.clip(eng.born_probs(eng.bloch_from_matrix(rho)), 0, 1).reshape(n_iter * eng.S, eng.K)
-    work = []  # the density matrices of a chunk
-
-    def measure(counts, centres, dist, status):
-        if metric is not None:
-            if not work:
-                work.append(torch.empty((counts.shape[0], eng.d, eng.d), dtype=torch.complex128, device=counts.device))
-            mats = work[0][:counts.shape[0]]
-            if method_boot == "lin":
-                eng.lin_dev(counts, mats, physical=physical, status=status)
-            else:
-                eng.mle_dev(counts, mats, init=init, max_iter=max_iter, tol=tol, status=status)
-            (eng.metric_dist_dev if eng.d <= 8 else eng.metric_dist_dim_dev)(mats, centres, dist, metric)
-        elif method_boot == "lin":
-            eng.lin_dist_dev(counts, centres, dist, physical=physical, status=status)
-        else:
-            eng.mle_dist_dev(counts, centres, dist, init=init, max_iter=max_iter, tol=tol, status=status)
-
+    if method_boot == "lin":
+        opts = dict(physical=physical)
+        fused, plain = eng.lin_dist_dev, eng.lin_dev
+    else:
+        opts = dict(init=init, max_iter=max_iter, tol=tol)
+        fused, plain = eng.mle_dist_dev, eng.mle_dev
+    measure = _chunk_measure(eng, metric, (eng.d, eng.d),
+                             lambda counts, centres, dist, status: fused(counts, centres, dist, status=status, **opts),
+                             lambda counts, mats, status: plain(counts, mats, status=status, **opts))
     hits, bad = _chunked_hits(eng, rho, (eng.S, eng.K), pvals, tmg.n_measurements, delta, n_points, key, chunk, measure,
                               lambda status: torch.stack([(status == 1).any(), (status == _capi.TRIAL_SHOTS).any()]))
     if bad[0]:
@@ -381,7 +398,7 @@ def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n
     tmg = ProcessTomograph(channel, input_states, "hs")
     counts, _ = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, False)
     choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
-    delta = tmg._engine().hs_dist(choi, channel.choi.matrix)
+    delta = tmg._engine().distance(choi, channel.choi.matrix)
     cls = np.linspace(0, 1, n_points)
     levels, hits = _levels_from_radii(delta, MomentInterval(tmg).radii_batch(counts, cls), cls)
     return _result(levels, return_details, counts=counts, estimates=choi, delta=delta, hits=hits, seed=None)
@@ -422,7 +439,7 @@ def get_CL_list_channel_boot_dst(channel, n_iter=1000, n_points=1000, n_measurem
 
     dst='hs' IS `get_CL_list_channel_boot`: the same call, the same bits.  Otherwise `delta` and the resampled distances
     are measured in `dst`: a chunk's Choi matrices go into one device workspace of the first chunk's size
-    (`Engine.lifp_dev`) and `Engine.metric_dist_dim_dev` measures resample r of trial t against estimate t (the table of
+    (`Engine.lifp_dev`) and `Engine.distance_dev` measures resample r of trial t against estimate t (the table of
     the n_iter estimates, process b against centre b % n_iter), as `_boot_hits` does it for states; n <= 2 (dim = 4, 16).
     A Choi matrix here has trace 2^n, not 1, so `if_dst` of two of them is 1 - (about 2^n)^2 < 1e-15 and comes back as 0,
     exactly as geometry.py:52-54 returns it in the reference.  dst='if' on a channel is therefore accepted and faithful,
@@ -441,24 +458,13 @@ def _channel_boot(channel, n_iter, n_points, n_measurements, method, povm, input
     counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
     choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
     eng = tmg._engine()
-    delta = (eng.hs_dist(choi, channel.choi.matrix) if metric is None else
-             eng.metric_dist_dim(choi, channel.choi.matrix, metric))
+    delta = eng.distance(choi, channel.choi.matrix, metric)
     key = (base + 1) & (2**64 - 1)
     pvals = eng.process_born_probs(choi)
-    work = []  # the Choi matrices of a chunk
-
-    def measure(resamples, centres, dist, status):
-        if metric is None:
-            eng.lifp_dist_dev(resamples, centres, dist, cptp=cptp, status=status)
-            return
-        import torch
-
-        if not work:
-            work.append(torch.empty((resamples.shape[0], eng.D, eng.D), dtype=torch.complex128, device=resamples.device))
-        mats = work[0][:resamples.shape[0]]
-        eng.lifp_dev(resamples, mats, cptp=cptp, status=status)
-        eng.metric_dist_dim_dev(mats, centres, dist, metric)
-
+    measure = _chunk_measure(eng, metric, (eng.D, eng.D),
+                             lambda counts, centres, dist, status: eng.lifp_dist_dev(counts, centres, dist, cptp=cptp,
+                                                                                     status=status),
+                             lambda counts, mats, status: eng.lifp_dev(counts, mats, cptp=cptp, status=status))
     hits, bad = _chunked_hits(eng, choi, (eng.D, eng.S, eng.K), pvals, tmg.tomographs[0].n_measurements, delta, n_points,
                               key, chunk, measure, lambda status: (status != 0).any().reshape(1))
     if bad[0]:
@@ -488,9 +494,9 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     place in a batch, and never on np.random.  The level of trial t is `levels_from_hits(hits_t, n_points)`.
 
     dst (keyword-only) = 'hs' | 'trace' | 'if', or the functions of quantpy_amd.geometry: 'hs' is the call described
-    above, the same bits.  Otherwise delta_t = `Engine.metric_dist_dim`(estimate_t, Choi matrix of the channel) and the
+    above, the same bits.  Otherwise delta_t = `Engine.distance`(estimate_t, Choi matrix of the channel, dst) and the
     chains run through `Engine.mhmc_process_hits(metric=dst)`: the same chains with the real part of every sample
-    measured as `metric_dist_dim` measures it, in the kernel that holds the sample (include/qtomo.h:
+    measured as `metric_dist` measures it, in the kernel that holds the sample (include/qtomo.h:
     qt_mhmc_process_metric_hits).
     A Choi matrix here has trace 2^n, not 1, so `if_dst` of two of them is 1 - (about 2^n)^2 < 1e-15 and comes back as 0,
     exactly as geometry.py:52-54 returns it in the reference.  dst='if' on a channel is therefore accepted and faithful,
@@ -499,16 +505,7 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     An estimate that is not finite (an input state without counts) raises ValueError on every rank.  `sampler`, `seed`,
     `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the accepted post-burn
     steps / (n_points * thinning), the reference's definition."""
-    _check_arguments("gamma", "hs", n_iter, n_points, sampler, (), None)
-    n_iter, n_points, burn_steps, thinning = int(n_iter), int(n_points), int(burn_steps), int(thinning)
-    if thinning < 1:
-        raise ValueError("thinning must be a positive integer")
-    if burn_steps < 0:
-        raise ValueError("burn_steps must not be negative")
-    if burn_steps + n_points * thinning >= 2**32 - 1:
-        raise ValueError("burn_steps + n_points * thinning must be below 2^32 - 1")
-    metric = _distance_name(dst)
-    metric = None if metric == "hs" else metric
+    n_iter, n_points, burn_steps, thinning, metric = _chain_arguments(n_iter, n_points, burn_steps, thinning, sampler, dst)
     if channel.n_qubits > 2:
         raise NotImplementedError(f"get_CL_list_channel_mhmc runs channels of one and two qubits, not {channel.n_qubits}: "
                                   "the chain of a three-qubit process has no fused kernel")
@@ -518,17 +515,9 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     if not np.all(np.isfinite(choi)):  # (the same estimates on every rank: all raise, or none)
         raise ValueError("a trial has no finite Choi matrix (an input state without counts)")
     eng = tmg._engine()
-    delta = (eng.hs_dist(choi, channel.choi.matrix) if metric is None else
-             eng.metric_dist_dim(choi, channel.choi.matrix, metric))
+    delta = eng.distance(choi, channel.choi.matrix, metric)
     key = (base + 1) & (2**64 - 1)
-    lo, hi = qdist.shard_bounds(n_iter)
-    both = np.zeros((2, n_iter), dtype=np.int64)
-    if hi > lo:
-        both[0, lo:hi], both[1, lo:hi] = eng.mhmc_process_hits(counts[lo:hi], choi[lo:hi], choi[lo:hi], delta[lo:hi], key,
-                                                               burn_steps, n_points, thinning, step, first_chain=lo,
-                                                               metric=metric)
-    if qdist.world()[1] > 1:
-        both = qdist.allgather_equal(both).sum(0)
-    hits, accepted = both
+    hits, accepted = _sharded_chain_hits(eng.mhmc_process_hits, (counts, choi, choi, delta), key, burn_steps, n_points,
+                                         thinning, step, metric=metric)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
                    seed=key, acceptance_rate=accepted / (n_points * thinning))

@@ -60,8 +60,7 @@ def _proposal_increments(dim):
 
 
 def _engine_metric(dst, n_qubits):
-    """'trace' / 'if' when `dst` is the trace distance / infidelity and the engine forms it (n <= 3:
-    Engine.metric_dist; n = 4, 5: Engine.metric_dist_dim), else None."""
+    """'trace' / 'if' when `dst` is the trace distance / infidelity and the engine forms it (Engine.distance), else None."""
     if n_qubits > 5:
         return None
     return "trace" if dst is trace_dst else "if" if dst is if_dst else None
@@ -248,7 +247,7 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
             if info is not None and np.any(info["status"] == 1):
                 raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
             if tmg.dst is hs_dst:
-                return get_engine(centre.n_qubits).hs_dist(rho, centre.matrix)
+                return get_engine(centre.n_qubits).distance(rho, centre.matrix)
             from ..qobj import Qobj
 
             return np.array([tmg.dst(Qobj(r), centre) for r in rho], dtype=np.float64)
@@ -265,9 +264,8 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
         and `cl_to_dist` evaluates interp1d's order statistics across the ranks (quantpy_amd.distributed.ShardedSample)
         -- no all-gather of the sample unless somebody reads `boot_dist` / `cl_to_dist.y`.
         `metric` = 'trace' / 'if': the same, except that the shard is reconstructed in chunks of whole
-        trials into a workspace of at most `_CHUNK_BYTES` of density matrices, and `Engine.metric_dist_dev` (n <= 3) /
-        `Engine.metric_dist_dim_dev` (n = 4, 5) writes each chunk's trace distances / infidelities to `state` into the
-        shard's `dist`: the matrices never leave HBM."""
+        trials into a workspace of at most `_CHUNK_BYTES` of density matrices, and `Engine.distance_dev` writes each
+        chunk's trace distances / infidelities to `state` into the shard's `dist`: the matrices never leave HBM."""
         import torch
 
         from .. import _capi
@@ -314,7 +312,6 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
         elif hi > lo:
             chunk = min(hi - lo, max(1, self._CHUNK_BYTES // (16 * d * d)))
             rho = torch.empty((chunk, d, d), dtype=torch.complex128, device=dev)
-            measure = eng.metric_dist_dev if d <= 8 else eng.metric_dist_dim_dev
             for c0 in range(0, hi - lo, chunk):
                 c1 = min(c0 + chunk, hi - lo)
                 if self.method == "lin":
@@ -322,7 +319,7 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
                 else:
                     eng.mle_dev(counts[c0:c1], rho[:c1 - c0], init=self.init, max_iter=self.max_iter, tol=self.tol,
                                 status=status[c0:c1])
-                measure(rho[:c1 - c0], centre, dist[c0:c1], metric)
+                eng.distance_dev(rho[:c1 - c0], centre, dist[c0:c1], metric)
         eng.sync()
         st = status.cpu().numpy()
         bad = np.array([int(np.any(st == 1)), int(np.any(st == _capi.TRIAL_SHOTS))])
@@ -409,11 +406,8 @@ class MHMCStateInterval(ConfidenceInterval):
         self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
         mats = eng.chol_unparam(self.samples)
         metric = _engine_metric(tmg.dst, tmg.state.n_qubits)
-        if tmg.dst is hs_dst:
-            dist = eng.hs_dist(mats, np.asarray(self.state.matrix, dtype=np.complex128))
-        elif metric:
-            measure = eng.metric_dist if tmg.state.n_qubits <= 3 else eng.metric_dist_dim
-            dist = measure(mats, np.asarray(self.state.matrix, dtype=np.complex128), metric)
+        if tmg.dst is hs_dst or metric:
+            dist = eng.distance(mats, np.asarray(self.state.matrix, dtype=np.complex128), metric)
         else:
             dist = np.array([tmg.dst(m, self.state.matrix) for m in mats], dtype=np.float64)
         self._finish(dist)
@@ -725,12 +719,10 @@ class MHMCProcessInterval(ConfidenceInterval):
         self.samples = np.ascontiguousarray(chain[skip::self.thinning][: self.n_points].real)
         self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
         # trace distance / infidelity of the Choi matrices, 2n-qubit objects: on the engine up to two qubits (dim 4, 16);
-        # the real parts of Hermitian chain states are symmetric, hence Hermitian, which is what metric_dist_dim takes
+        # the real parts of Hermitian chain states are symmetric, hence Hermitian, which is what metric_dist takes
         metric = _engine_metric(tmg.dst, 2 * self.channel.n_qubits)
-        if tmg.dst is hs_dst:
-            dist = get_engine(self.channel.n_qubits).hs_dist(self.samples, centre)
-        elif metric:
-            dist = eng.metric_dist_dim(self.samples, centre, metric)
+        if tmg.dst is hs_dst or metric:
+            dist = eng.distance(self.samples, centre, metric)
         else:
             dist = np.array([tmg.dst(m, centre) for m in self.samples], dtype=np.float64)
         dist = np.sort(dist)
@@ -784,10 +776,8 @@ class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
             # `tol` and `states_est_method` stay at point_estimate's defaults there, and so they do here
             choi = boot.point_estimate_batch(shard, method=self.method, cptp=self.cptp,
                                              states_physical=self.states_physical, states_init=self.states_init)
-            if tmg.dst is hs_dst:
-                return get_engine(tmg.channel.n_qubits).hs_dist(choi, centre.matrix)  # 4^n x 4^n matrices on the channel's engine
-            if metric:
-                return get_engine(tmg.channel.n_qubits).metric_dist_dim(choi, centre.matrix, metric)
+            if tmg.dst is hs_dst or metric:  # 4^n x 4^n matrices on the channel's engine
+                return get_engine(tmg.channel.n_qubits).distance(choi, centre.matrix, metric)
             from ..qobj import Qobj
 
             return np.array([tmg.dst(Qobj(c), centre) for c in choi], dtype=np.float64)

@@ -8,7 +8,8 @@ Usage: python scripts/isa_identity.py <tree-a> <tree-b> [extra compiler flags]
 Compiles quantpy_amd/csrc/qtomo.hip of both trees with the flags of quantpy_amd/build.py plus -S --cuda-device-only,
 cuts each assembly file into functions (symbol label .. .Lfunc_end) and kernel descriptors (.amdhsa_kernel ..
 .end_amdhsa_kernel), drops comments and the function index of local labels (.LBB12_3 -> .LBBN_3: it moves when
-definitions move), and prints the symbols that only one tree has and those whose text differs.  Everything else in the
+definitions move), and prints the symbols that only one tree has, those whose text differs, and whether the function symbols stand
+in the same order (`order: same`, or the first position where the two sequences differ).  Everything else in the
 file -- the __hip_cuid_* symbol, the metadata block -- is ignored.  Exit status 1 if either list is non-empty.
 It compares text and nothing else: a refactor that is meant to leave every kernel alone is checked by this, not by a
 timing."""
@@ -34,7 +35,7 @@ def start_compile(tree, out, extra):
     if tree.endswith(".s"):
         return None
     src = os.path.join(tree, "quantpy_amd", "csrc", "qtomo.hip")
-    cmd = [qt_build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *qt_build.SCHED_FLAGS, *extra,
+    cmd = [qt_build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *qt_build.FLAGS, *extra,
            "-S", "--cuda-device-only", "-o", out, src]
     return subprocess.Popen(cmd)
 
@@ -69,6 +70,15 @@ def functions(path):
     return out
 
 
+def order_line(fa, fb):
+    """The sequence of function symbols of the two files: the same, or the first position where it differs."""
+    sa, sb = ([s for s in f if not s.endswith(" (descriptor)")] for f in (fa, fb))
+    if sa == sb:
+        return "order: same"
+    k = next((i for i, (x, y) in enumerate(zip(sa, sb)) if x != y), min(len(sa), len(sb)))
+    return f"order: differs at position {k}: a has {sa[k] if k < len(sa) else None}, b has {sb[k] if k < len(sb) else None}"
+
+
 def main(argv):
     if len(argv) < 3:
         print(__doc__)
@@ -84,7 +94,7 @@ def main(argv):
         fa, fb = (functions(a) for a in asm)
     only_a, only_b = sorted(set(fa) - set(fb)), sorted(set(fb) - set(fa))
     differ = sorted(s for s in set(fa) & set(fb) if fa[s] != fb[s])
-    print(f"flags: {' '.join(qt_build.SCHED_FLAGS + extra)}")
+    print(f"flags: {' '.join(qt_build.FLAGS + extra)}")
     for tag, f in (("a", fa), ("b", fb)):
         kernels = sum(1 for s in f if s.endswith(" (descriptor)"))
         print(f"{tag}: {len(f) - kernels} functions, {kernels} kernel descriptors, {sum(map(len, f.values()))} lines")
@@ -95,6 +105,7 @@ def main(argv):
     print(f"differ: {len(differ)}")
     for s in differ:
         print(f"  {s}: {len(fa[s])} lines in a, {len(fb[s])} in b")
+    print(order_line(fa, fb))
     return 1 if only_a or only_b or differ else 0
 
 
