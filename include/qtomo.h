@@ -268,6 +268,27 @@ int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, in
  * QT_ERR_ARG: an unknown metric, G < 1, g0 outside [0, G), B < 0, a null array with B > 0.  B == 0 returns 0. */
 int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
                        double* dist, int flags);
+/* ---- the same (quantpy/geometry.py:23-38 trace_dst, :41-56 if_dst) up to dim = 64, the Choi matrix of a three-qubit
+ * channel; a sibling because qt_metric_dist_dim's refusal of dim = 64 is part of that entry's contract -----------------
+ * dist[b] = metric(rho_b, centres[(g0 + b) % G]); rho[B][dim][dim][2], centres[G][dim][dim][2], on ANY handle, whatever
+ * its n_qubits; needs no POVM.
+ *   dim = 2, 4, 8, 16, 32   the code of qt_metric_dist_dim: the same bits as that entry
+ *   dim = 64                one workgroup of 1024 threads per trial, four elements per thread; a round's 32 rotations are
+ *                           formed once and handed round through LDS; at most 48 sweeps; the same formulas, but NOT the
+ *                           bits a one-thread-per-element kernel would give: the values are within 1e-13 max(1, Tr)
+ *                           (trace distance) and 1e-12 (infidelity of full-rank arguments; 1e-6 otherwise) of float64
+ *                           linear algebra.  135 296 B of LDS per workgroup.
+ *   any other dim           QT_ERR_UNSUPPORTED (supported: 2, 4, 8, 16, 32, 64)
+ * Both arguments are taken to be HERMITIAN, exactly as above: the imaginary parts of the diagonals are dropped, the trace
+ * distance is sum_i |lambda_i(rho_b - centre)| / 2, the infidelity 1 - (sum_i sqrt(max(mu_i, 0)))^2 with mu the
+ * eigenvalues of the Hermitian part of S rho_b S, S = the clipped Hermitian root of the centre (the SECOND argument),
+ * formed once per call and centre into the handle's workspace (G * 2 * dim^2 doubles).  A value below 1e-15 -- small
+ * negative infidelities included -- is returned as +0.  A NaN (or an infinity) in rho_b or in its centre gives
+ * dist[b] = NaN and touches no other trial; a trial's bits depend on its two matrices alone, not on B, G, g0, its place in
+ * the batch or host- against device-pointer staging.
+ * QT_ERR_ARG: an unknown metric, G < 1, g0 outside [0, G), B < 0, a null array with B > 0.  B == 0 returns 0. */
+int qt_metric_dist_mat(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
+                       double* dist, int flags);
 
 /* ---- a16: quantpy/tomography/interval.py:610-612 (and :683-685) -------------------------------- */
 /* `dist.sort()`: ascending in-place sort of n float64 values in np.sort's order (NaN last; bitonic in LDS up to 8192

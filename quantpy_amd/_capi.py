@@ -14,7 +14,7 @@ QT_INIT_MIXED = 1
 QT_STREAM_LEGACY = 1  # qt_set_stream: the legacy default ("null") stream
 QT_OPT_SHOTS_CHECK, QT_OPT_MLE_FUSED_MAX_WAVES, QT_OPT_PAIRED_STAGES, QT_OPT_MLE_SPECIALISE = 1, 2, 3, 4  # qt_set_option
 QT_OPT_LIFP_DIST_SLICE = 5  # processes per slice of qt_lifp_dist_batch (0: the library's byte bound)
-QT_METRIC_TRACE, QT_METRIC_INFIDELITY = 0, 1  # qt_metric_dist_group_batch, qt_metric_dist_dim
+QT_METRIC_TRACE, QT_METRIC_INFIDELITY = 0, 1  # qt_metric_dist_group_batch, qt_metric_dist_dim, qt_metric_dist_mat
 QT_OPT_MLE_HELPER_WAVE = 6  # n = 3 one-launch MLE, 'lin' start: a helper wavefront per trial lifts on speculation (0: the kernel without)
 
 # status codes (include/qtomo.h)
@@ -81,6 +81,7 @@ SIGNATURES = {
     "qt_hs_dist_dim": (_c_int, [_vp, _c_int, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_metric_dist_group_batch": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int]),
     "qt_metric_dist_dim": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int]),
+    "qt_metric_dist_mat": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _vp, _c_int]),
     "qt_sort_f64": (_c_int, [_vp, _vp, ctypes.c_longlong, _c_int]),
     "qt_sorted_quantiles": (_c_int, [_vp, _vp, ctypes.c_longlong, _vp, _c_int, _vp, _c_int]),
     "qt_select_splitters": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _vp, _c_int]),

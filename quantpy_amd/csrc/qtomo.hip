@@ -20,6 +20,7 @@
 #include "qt_lp.h"
 #include "qt_lp_large.h"
 #include "qt_metric_dim.h"
+#include "qt_metric_dim64.h"
 #include "qt_mhmc_state.h"
 #include "qt_mhmc_state_large.h"
 #include "qt_mle_small.h"
@@ -181,7 +182,7 @@ struct qt_handle {
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
-  DevBuf metric_ws;  // qt_metric_dist_group_batch / qt_metric_dist_dim, infidelity: the Hermitian roots of the call's G centres
+  DevBuf metric_ws;  // qt_metric_dist_group_batch / _dim / _mat, infidelity: the Hermitian roots of the call's G centres
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -1285,6 +1286,20 @@ int metric_dim(qt_handle_t* h, int metric, const double* dr, int B, const double
                 static_cast<const double*>(roots), G, g0, h->jtol2, dd);
 }
 
+// The same for dim 64: one workgroup of 1024 threads per trial and per centre, four elements per thread, dynamic LDS
+// (k_metric_dist_dim64, k_psd_sqrt_dim64)
+int metric_dim64(qt_handle_t* h, int metric, const double* dr, int B, const double* dcn, int G, int g0, double* dd) {
+  using W = qt::MetricDim64;
+  const dim3 block(W::NT);
+  if (metric == QT_METRIC_TRACE)
+    return launch(h, qt::k_metric_dist_dim64<qt::kMetricTrace>, dim3(B), block, W::kLdsBytes, dr, B, dcn, G, g0, h->jtol2, dd);
+  HIPCHK(h->metric_ws.ensure((size_t)G * W::NE * 2 * sizeof(double)));
+  double* roots = h->metric_ws.as<double>();
+  if (int r = launch(h, qt::k_psd_sqrt_dim64, dim3(G), block, W::kLdsBytes, dcn, G, h->jtol2, roots)) return r;
+  return launch(h, qt::k_metric_dist_dim64<qt::kMetricInfidelity>, dim3(B), block, W::kLdsBytes, dr, B,
+                static_cast<const double*>(roots), G, g0, h->jtol2, dd);
+}
+
 // The device arrays of a fused chain call, as staged by mhmc_hits_call
 struct MhmcHitsArgs {
   const int64_t* counts;
@@ -1927,14 +1942,15 @@ int qt_hs_dist_dim(qt_handle_t* h, int dim, const double* rho, const double* cen
 }
 
 // geometry.py:23-56 for a batch of dim x dim matrices against a table of centres, behind QT_ENTER: dim 2, 4, 8 by
-// k_metric_dist, dim 16, 32 by one workgroup per trial (qt_metric_dim.h); the infidelity's roots of the centres once per
-// call.  Reads no POVM.  `fn`, the entry, words the errors.
-static int metric_dist_call(qt_handle_t* h, const char* fn, int metric, int dim, const double* rho, int B, const double* centres,
-                            int G, int g0, double* dist, int flags) {
+// k_metric_dist, dim 16, 32 by one workgroup per trial (qt_metric_dim.h), dim 64 the same with four elements per thread
+// (qt_metric_dim64.h); the infidelity's roots of the centres once per call.  Reads no POVM.  `fn`, the entry, words the
+// errors; `max_dim`, 32 or 64, is the largest dim it admits.
+static int metric_dist_call(qt_handle_t* h, const char* fn, int max_dim, int metric, int dim, const double* rho, int B,
+                            const double* centres, int G, int g0, double* dist, int flags) {
   Call c(h, flags, fn);
   if (metric != QT_METRIC_TRACE && metric != QT_METRIC_INFIDELITY) return fail(QT_ERR_ARG, "%s: unknown metric %d", fn, metric);
-  if (dim != 2 && dim != 4 && dim != 8 && dim != 16 && dim != 32)
-    return fail(QT_ERR_UNSUPPORTED, "%s: dim %d (supported: 2, 4, 8, 16, 32)", fn, dim);
+  if (dim < 2 || dim > max_dim || (dim & (dim - 1)))
+    return fail(QT_ERR_UNSUPPORTED, "%s: dim %d (supported: 2, 4, 8, 16, 32%s)", fn, dim, max_dim == 64 ? ", 64" : "");
   if (B < 0 || G < 1 || g0 < 0 || g0 >= G || (B > 0 && (!rho || !centres || !dist)))
     return fail(QT_ERR_ARG, "bad %s arguments (B = %d, G = %d, g0 = %d)", fn + 3, B, G, g0);
   if (B == 0) return 0;
@@ -1950,7 +1966,8 @@ static int metric_dist_call(qt_handle_t* h, const char* fn, int metric, int dim,
     case 4: r = metric_small<2>(h, metric, dr, B, dcn, G, g0, dd); break;
     case 8: r = metric_small<3>(h, metric, dr, B, dcn, G, g0, dd); break;
     case 16: r = metric_dim<16>(h, metric, dr, B, dcn, G, g0, dd); break;
-    default: r = metric_dim<32>(h, metric, dr, B, dcn, G, g0, dd); break;
+    case 32: r = metric_dim<32>(h, metric, dr, B, dcn, G, g0, dd); break;
+    default: r = metric_dim64(h, metric, dr, B, dcn, G, g0, dd); break;
   }
   if (r) return r;
   return c.done();
@@ -1961,14 +1978,21 @@ int qt_metric_dist_group_batch(qt_handle_t* h, int metric, const double* rho, in
                                double* dist, int flags) {
   QT_ENTER(h);
   if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "qt_metric_dist_group_batch: n_qubits %d (supported: 1, 2, 3)", h->nq);
-  return metric_dist_call(h, "qt_metric_dist_group_batch", metric, h->d, rho, B, centres, G, g0, dist, flags);
+  return metric_dist_call(h, "qt_metric_dist_group_batch", 32, metric, h->d, rho, B, centres, G, g0, dist, flags);
 }
 
 // ... of any supported size on any handle, whatever its n_qubits (dim 2, 4, 8: the same bits as on a handle of that size)
 int qt_metric_dist_dim(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
                        double* dist, int flags) {
   QT_ENTER(h);
-  return metric_dist_call(h, "qt_metric_dist_dim", metric, dim, rho, B, centres, G, g0, dist, flags);
+  return metric_dist_call(h, "qt_metric_dist_dim", 32, metric, dim, rho, B, centres, G, g0, dist, flags);
+}
+
+// ... and of dim 64 as well (a three-qubit Choi matrix): below 64 the very code of qt_metric_dist_dim
+int qt_metric_dist_mat(qt_handle_t* h, int metric, int dim, const double* rho, int B, const double* centres, int G, int g0,
+                       double* dist, int flags) {
+  QT_ENTER(h);
+  return metric_dist_call(h, "qt_metric_dist_mat", 64, metric, dim, rho, B, centres, G, g0, dist, flags);
 }
 
 // ---- a16: interval.py:610-612 ------------------------------------------------------------------------

@@ -873,8 +873,8 @@ class Engine:
 
     def metric_dist(self, rho, centre, metric, g0=0):
         """Trace distance (metric='trace', geometry.py:23-38) or infidelity ('if', geometry.py:41-56) of Hermitian
-        dim x dim matrices to `centre`, whatever this engine's n_qubits, dim = rho.shape[-1] in (2, 4, 8, 16, 32)
-        (qt_metric_dist_dim; needs no POVM): states of up to five qubits, the Choi matrix of a two-qubit channel.  rho
+        dim x dim matrices to `centre`, whatever this engine's n_qubits, dim = rho.shape[-1] in (2, 4, 8, 16, 32, 64)
+        (qt_metric_dist_mat; needs no POVM): states of up to five qubits, the Choi matrix of a channel of up to three.  rho
         (B, dim, dim) or (dim, dim); centre (dim, dim), or a table (G, dim, dim): trial b is then measured against
         centre[(g0 + b) % G].  -> (B,) float64, or a float for a single matrix."""
         code = self._metric_code(metric)
@@ -884,16 +884,16 @@ class Engine:
         r = rho.reshape(-1, dim, dim)
         assert cen.shape[-2:] == (dim, dim) and cen.ndim in (2, 3)
         out = np.empty(r.shape[0])
-        self._chk(self.lib.qt_metric_dist_dim(self._h, code, dim, _ptr(r), r.shape[0], _ptr(cen),
+        self._chk(self.lib.qt_metric_dist_mat(self._h, code, dim, _ptr(r), r.shape[0], _ptr(cen),
                                               cen.shape[0] if cen.ndim == 3 else 1, int(g0), _ptr(out), _capi.QT_HOST_PTR))
         return out[0] if single else out
 
     def metric_dist_dev(self, rho, centre, dist, metric, g0=0):
-        """device-pointer form: rho complex128 (B, dim, dim), centre complex128 (dim, dim) or (G, dim, dim), dist float64
-        (B,) torch CUDA tensors"""
+        """device-pointer form, dim in (2, 4, 8, 16, 32, 64): rho complex128 (B, dim, dim), centre complex128 (dim, dim) or
+        (G, dim, dim), dist float64 (B,) torch CUDA tensors"""
         code = self._metric_code(metric)
         self._dev_call()
-        self._chk(self.lib.qt_metric_dist_dim(self._h, code, rho.shape[-1], _ptr(rho), rho.shape[0], _ptr(centre),
+        self._chk(self.lib.qt_metric_dist_mat(self._h, code, rho.shape[-1], _ptr(rho), rho.shape[0], _ptr(centre),
                                               centre.shape[0] if centre.dim() == 3 else 1, int(g0), _ptr(dist),
                                               _capi.QT_DEVICE_PTR))
 

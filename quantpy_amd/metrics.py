@@ -440,7 +440,7 @@ def get_CL_list_channel_boot_dst(channel, n_iter=1000, n_points=1000, n_measurem
     dst='hs' IS `get_CL_list_channel_boot`: the same call, the same bits.  Otherwise `delta` and the resampled distances
     are measured in `dst`: a chunk's Choi matrices go into one device workspace of the first chunk's size
     (`Engine.lifp_dev`) and `Engine.distance_dev` measures resample r of trial t against estimate t (the table of
-    the n_iter estimates, process b against centre b % n_iter), as `_boot_hits` does it for states; n <= 2 (dim = 4, 16).
+    the n_iter estimates, process b against centre b % n_iter), as `_boot_hits` does it for states; n <= 3 (dim = 4, 16, 64).
     A Choi matrix here has trace 2^n, not 1, so `if_dst` of two of them is 1 - (about 2^n)^2 < 1e-15 and comes back as 0,
     exactly as geometry.py:52-54 returns it in the reference.  dst='if' on a channel is therefore accepted and faithful,
     and degenerate: every distance, every `delta` and every level is 0."""

@@ -59,9 +59,10 @@ def _proposal_increments(dim):
     return lambda size: np.random.standard_normal((size, dim))
 
 
-def _engine_metric(dst, n_qubits):
-    """'trace' / 'if' when `dst` is the trace distance / infidelity and the engine forms it (Engine.distance), else None."""
-    if n_qubits > 5:
+def _engine_metric(dst, n_qubits, max_qubits=5):
+    """'trace' / 'if' when `dst` is the trace distance / infidelity and the engine forms it (Engine.distance), else None.
+    `max_qubits`: the largest object the caller hands over -- 6 for the Choi matrix of a three-qubit channel (dim 64)."""
+    if n_qubits > max_qubits:
         return None
     return "trace" if dst is trace_dst else "if" if dst is if_dst else None
 
@@ -718,9 +719,9 @@ class MHMCProcessInterval(ConfidenceInterval):
         # dropped there (NumPy's ComplexWarning), and the distances are those of the real parts
         self.samples = np.ascontiguousarray(chain[skip::self.thinning][: self.n_points].real)
         self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
-        # trace distance / infidelity of the Choi matrices, 2n-qubit objects: on the engine up to two qubits (dim 4, 16);
-        # the real parts of Hermitian chain states are symmetric, hence Hermitian, which is what metric_dist takes
-        metric = _engine_metric(tmg.dst, 2 * self.channel.n_qubits)
+        # trace distance / infidelity of the Choi matrices, 2n-qubit objects: on the engine (dim 4, 16, 64); the real
+        # parts of Hermitian chain states are symmetric, hence Hermitian, which is what metric_dist takes
+        metric = _engine_metric(tmg.dst, 2 * self.channel.n_qubits, max_qubits=6)
         if tmg.dst is hs_dst or metric:
             dist = eng.distance(self.samples, centre, metric)
         else:
@@ -767,9 +768,9 @@ class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
                                                              sampler=self.sampler, seed=self.seed))
         self.boot_counts = counts
         centre = self.channel.choi
-        # trace distance / infidelity of the Choi matrices on the engine up to two qubits (dim 4, 16), as
-        # MHMCProcessInterval measures its samples; three qubits keep the host loop
-        metric = _engine_metric(tmg.dst, 2 * tmg.channel.n_qubits)
+        # trace distance / infidelity of the Choi matrices on the engine (dim 4, 16, 64), as MHMCProcessInterval measures
+        # its samples
+        metric = _engine_metric(tmg.dst, 2 * tmg.channel.n_qubits, max_qubits=6)
 
         def reconstruct(shard):
             # the reference's loop (interval.py:675-680) passes method, states_physical, states_init and cptp;
