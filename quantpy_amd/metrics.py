@@ -31,8 +31,9 @@ import numpy as np
 
 from . import distributed as qdist
 from .geometry import hs_dst, if_dst, trace_dst
-from .sampling import SAMPLERS, resolve_seed
-from .tomography.interval import BootstrapProcessInterval, MomentInterval
+from .sampling import SAMPLERS, device_chunks, shared_seed
+from .tomography.interval import (_PROCESS_ERRORS, _STATE_ERRORS, BootstrapProcessInterval, MomentInterval, _agreed_flags,
+                                  _distance_buffers, _error_flags, _raise_flagged)
 from .tomography.process import ProcessTomograph
 from .tomography.state import StateTomograph
 
@@ -80,25 +81,17 @@ def _check_arguments(interval, dst, n_iter, n_points, sampler, boot_methods, met
         raise ValueError(f"sampler must be one of {SAMPLERS}, not {sampler!r}")
 
 
-def _shared_seed(seed):
-    """resolve_seed(seed), rank 0's on every rank."""
-    key = resolve_seed(seed)
-    if qdist.world()[1] > 1:
-        key = int(qdist.broadcast_array(np.array([key], dtype=np.uint64).view(np.int64)).view(np.uint64)[0])
-    return key
-
-
 def _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, keyed):
     """(counts of the n_iter experiments, the resolved seed), the same on every rank: rank 0's stream (sampler='numpy',
     np.random's in the reference's order; the seed is resolved behind the draws, and only when `keyed` resamples will
     need it) or rank 0's Philox key (sampler='device')."""
     if sampler == "device":
-        key = _shared_seed(seed)
+        key = shared_seed(seed)
         return tmg.experiment_batch(n_measurements, povm, repeats=n_iter, sampler="device", seed=key), key
     counts = tmg.experiment_batch(n_measurements, povm, repeats=n_iter)
     if qdist.world()[1] > 1:
         counts = qdist.broadcast_array(counts)
-    return counts, (_shared_seed(seed) if keyed else None)
+    return counts, (shared_seed(seed) if keyed else None)
 
 
 def _state_trials(state, n_iter, n_measurements, povm, sampler, seed, keyed, method, init, max_iter, tol):
@@ -311,10 +304,6 @@ def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init,
     """hits[t] = #{ r < n_points : delta_t > hs_dst(estimate(resample r of trial t), estimate_t) }, this rank's shard of
     the resamples chunk by chunk on the device, summed over the ranks.  `metric` = 'trace' / 'if': that distance in the
     place of hs_dst, formed from the chunk's density matrices (`_chunk_measure`)."""
-    import torch
-
-    from . import _capi
-
     n_iter = rho.shape[0]
     pvals = np.clip(eng.born_probs(eng.bloch_from_matrix(rho)), 0, 1).reshape(n_iter * eng.S, eng.K)
     if method_boot == "lin":
@@ -326,35 +315,24 @@ def _boot_hits(eng, tmg, rho, delta, n_points, key, method_boot, physical, init,
     measure = _chunk_measure(eng, metric, (eng.d, eng.d),
                              lambda counts, centres, dist, status: fused(counts, centres, dist, status=status, **opts),
                              lambda counts, mats, status: plain(counts, mats, status=status, **opts))
-    hits, bad = _chunked_hits(eng, rho, (eng.S, eng.K), pvals, tmg.n_measurements, delta, n_points, key, chunk, measure,
-                              lambda status: torch.stack([(status == 1).any(), (status == _capi.TRIAL_SHOTS).any()]))
-    if bad[0]:
-        raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
-    if bad[1]:
-        raise ValueError("per-setting totals of a trial do not match the registered shots")
-    return hits
+    return _chunked_hits(eng, rho, (eng.S, eng.K), pvals, tmg.n_measurements, delta, n_points, key, chunk, measure,
+                         _STATE_ERRORS)
 
 
-def _chunked_hits(eng, centres, trial_shape, pvals, shots, delta, n_points, key, chunk, measure, flags):
+def _chunked_hits(eng, centres, trial_shape, pvals, shots, delta, n_points, key, chunk, measure, errors):
     """The chunk loop of both nested bootstraps.  `centres` (n_iter, ., .) are the trials' estimates, one trial's counts
     have shape `trial_shape` = (..., S, K), `pvals` is the table of the n_iter estimates (rows of K) and `shots` the (S,)
-    totals of a setting.  This rank's `shard_bounds(n_points)` of the resamples runs in chunks of whole resamples through
-    one count buffer: `device_multinomial` (row r * rows-per-resample + ... of the table keyed by `key`),
+    totals of a setting.  This rank's `shard_bounds(n_points)` of the resamples runs in chunks of whole resamples
+    (`sampling.device_chunks`: a resample of all trials is the unit of the table keyed by `key`) through
     `measure(counts, centres, dist, status)` -- a grouped launch family on device tensors -- and `group_hits` against
-    `delta`.  `flags(status)` gives a bool tensor of the error conditions seen in a chunk.  Returns (hits (n_iter,)
-    summed over the ranks, flags OR-ed over chunks and ranks): every rank raises, or none."""
+    `delta`.  The `errors` seen in a chunk (interval._error_flags), OR-ed over chunks and ranks (one all-gather, then
+    the one of the hits), are raised in order: every rank raises, or none.  Returns hits (n_iter,) summed over the ranks."""
     import torch
 
     n_iter = centres.shape[0]
     n_out = trial_shape[-1]
     rows = int(np.prod(trial_shape[:-1])) * n_iter  # table rows per resample of all trials
-    dev = torch.device("cuda", eng.device)
-    p_d = torch.from_numpy(np.ascontiguousarray(pvals, dtype=np.float64).reshape(rows, n_out)).to(dev)
-    shots = np.atleast_1d(np.asarray(shots)).astype(np.int64)
-    n_d = torch.from_numpy(np.tile(shots, rows // len(shots))).to(dev)
-    centres = torch.from_numpy(np.ascontiguousarray(centres, dtype=np.complex128)).to(dev)
-    thr = torch.from_numpy(np.ascontiguousarray(delta, dtype=np.float64)).to(dev)
-    hits = torch.zeros(n_iter, dtype=torch.int64, device=dev)
+    shots = np.atleast_1d(np.asarray(shots))
     per_resample = rows * n_out * 8
     chunk = int(chunk) if chunk else max(1, _CHUNK_BYTES // per_resample)
     # The batch size of a launch is a 32-bit int.  (A caller's `chunk` is otherwise taken as given: the count buffer
@@ -362,26 +340,25 @@ def _chunked_hits(eng, centres, trial_shape, pvals, shots, delta, n_points, key,
     chunk = max(1, min(chunk, (2**31 - 1) // n_iter))
     lo, hi = qdist.shard_bounds(n_points)
     chunk = min(chunk, max(hi - lo, 1))
-    counts = torch.empty((chunk * n_iter,) + tuple(trial_shape), dtype=torch.int64, device=dev)
-    dist = torch.empty(chunk * n_iter, dtype=torch.float64, device=dev)
-    status = torch.zeros(chunk * n_iter, dtype=torch.int32, device=dev)
+    dist, status, centres = _distance_buffers(eng, chunk * n_iter, centres)
+    thr = torch.from_numpy(np.ascontiguousarray(delta, dtype=np.float64)).to(dist.device)
+    hits = torch.zeros(n_iter, dtype=torch.int64, device=dist.device)
     bad = None
-    for r0 in range(lo, hi, chunk):
-        b = min(chunk, hi - r0) * n_iter
-        eng.device_multinomial(n_d, p_d, (b // n_iter) * rows, key, first_row=r0 * rows, out=counts[:b])
-        measure(counts[:b], centres, dist[:b], status[:b])
+    for _, counts in device_chunks(eng, np.tile(shots, rows // len(shots)), np.reshape(pvals, (rows, n_out)), rows, lo, hi,
+                                   chunk, key, (n_iter,) + tuple(trial_shape)):
+        counts = counts.flatten(0, 1)  # row r * n_iter + t = resample r of trial t
+        b = counts.shape[0]
+        measure(counts, centres, dist[:b], status[:b])
         eng.group_hits(dist[:b], thr, hits)
-        seen = flags(status[:b])
+        seen = _error_flags(status[:b], errors)
         bad = seen if bad is None else bad | seen
     eng.sync()
-    if bad is None:  # (a rank without resamples)
-        bad = torch.zeros_like(flags(status[:0]))
-    bad = bad.cpu().numpy().astype(np.int64)
+    bad = _agreed_flags(_error_flags(status[:0], errors) if bad is None else bad)  # (None: a rank without resamples)
     hits = hits.cpu().numpy()
-    if qdist.world()[1] > 1:  # every rank raises, or none
-        bad = qdist.allgather_equal(bad).max(axis=0)
+    if qdist.world()[1] > 1:
         hits = qdist.allgather_equal(hits).sum(0)
-    return hits, bad
+    _raise_flagged(bad, errors)
+    return hits
 
 
 def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n_measurements=1000, method="lifp",
@@ -465,10 +442,8 @@ def _channel_boot(channel, n_iter, n_points, n_measurements, method, povm, input
                              lambda counts, centres, dist, status: eng.lifp_dist_dev(counts, centres, dist, cptp=cptp,
                                                                                      status=status),
                              lambda counts, mats, status: eng.lifp_dev(counts, mats, cptp=cptp, status=status))
-    hits, bad = _chunked_hits(eng, choi, (eng.D, eng.S, eng.K), pvals, tmg.tomographs[0].n_measurements, delta, n_points,
-                              key, chunk, measure, lambda status: (status != 0).any().reshape(1))
-    if bad[0]:
-        raise ValueError("a resampled process has no finite Choi matrix (an input state without counts)")
+    hits = _chunked_hits(eng, choi, (eng.D, eng.S, eng.K), pvals, tmg.tomographs[0].n_measurements, delta, n_points,
+                         key, chunk, measure, _PROCESS_ERRORS)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
                    seed=key)
 

@@ -10,12 +10,17 @@ publishes, under the generator's lock).
 `device_multinomial` is the opt-in alternative for callers that need the distribution but not the reference's stream
 (`sampler="device"` on `experiment` / `experiment_batch` / the bootstrap intervals): the draws are made on the GPU
 (`qt_device_multinomial`, one Philox stream per row), which takes the sampler out of a bootstrap's critical path.
+
+What the bootstraps and the coverage studies do with that sampler has one owner each here: `shared_seed` (the key of a
+table, the same on every rank), `check_pvals`, `device_chunks` (a range of a keyed table drawn chunk by chunk into one
+device buffer) and `trial_chunks` (the trial loop of the polytope studies for both samplers).
 """
 import ctypes
 
 import numpy as np
 
 from . import _capi
+from . import distributed as qdist
 
 _STATE_WORDS = 624  # mt19937_state: uint32 key[624]; int pos  (numpy/random/src/mt19937/mt19937.h)
 _layout_checked = {}  # id(bit generator) -> (bit generator, address or None)
@@ -98,6 +103,60 @@ def resolve_seed(seed):
         lo, hi = (int(w) for w in np.random.randint(0, 2**32, size=2, dtype=np.uint64))
         seed = lo | (hi << 32)
     return int(seed) & (2**64 - 1)
+
+
+def shared_seed(seed):
+    """resolve_seed(seed), rank 0's on every rank: one Philox key for a whole table, whichever rank draws a row.  One
+    broadcast when there are several ranks, none otherwise; np.random's stream moves on every rank as resolve_seed
+    moves it."""
+    key = resolve_seed(seed)
+    if qdist.world()[1] > 1:
+        key = int(qdist.broadcast_array(np.array([key], dtype=np.uint64).view(np.int64)).view(np.uint64)[0])
+    return key
+
+
+def check_pvals(pvals):
+    """What np.random.multinomial asks of every row of a table (S, K), with its message: no negative entry, and the
+    first K - 1 entries sum to at most 1 + 1e-12."""
+    pvals = np.asarray(pvals)
+    if not (np.all(pvals >= 0) and np.all(pvals[:, :-1].sum(1) <= 1.0 + 1e-12)):
+        raise ValueError("sum(pvals[:-1]) > 1.0")
+
+
+def device_chunks(engine, shots, pvals, rows_per_unit, first, last, chunk, seed, unit_shape):
+    """The units `first` .. `last` - 1 of a Philox-keyed count table, drawn `chunk` units at a time into ONE device buffer:
+    yields (unit0, counts), counts an int64 CUDA view (units,) + unit_shape that the next draw overwrites.  A unit -- a
+    bootstrap resample, a trial of a study -- is `rows_per_unit` consecutive rows of the table; `shots` (P,) and `pvals`
+    (P, K) are one period of it (row r ~ multinomial(shots[r % P], pvals[r % P]) from the stream (seed, r):
+    `Engine.device_multinomial`), uploaded once.  Rows are keyed by their index in the whole table, so neither `chunk`
+    nor the range (a rank's shard) changes a draw.  The draws run on the engine's stream: a chunk's draw waits for what
+    the caller launched on the chunk before it.  An empty range uploads, allocates and launches nothing."""
+    if last <= first:
+        return
+    import torch
+
+    dev = torch.device("cuda", engine.device)
+    n_d = torch.from_numpy(np.ascontiguousarray(np.asarray(shots).astype(np.int64))).to(dev)
+    p_d = torch.from_numpy(np.ascontiguousarray(pvals, dtype=np.float64)).to(dev)
+    chunk = max(1, min(int(chunk), last - first))
+    buffer = torch.empty((chunk,) + tuple(unit_shape), dtype=torch.int64, device=dev)
+    for unit0 in range(first, last, chunk):
+        counts = buffer[: min(chunk, last - unit0)]
+        engine.device_multinomial(n_d, p_d, counts.shape[0] * rows_per_unit, seed, first_row=unit0 * rows_per_unit,
+                                  out=counts)
+        yield unit0, counts
+
+
+def trial_chunks(engine, shots, pvals, n_trials, chunk, sampler, seed):
+    """The trials of a polytope study `chunk` at a time, for both samplers: yields (trial0, counts (trials, R, K)).
+    'numpy': `draw_counts` per chunk on np.random's stream, trial after trial in the reference's order, as a NumPy
+    array.  'device': `device_chunks` with a trial as the unit -- row trial * R + r of the table keyed by `seed`, which
+    the caller has resolved -- as a CUDA view."""
+    if sampler == "device":
+        yield from device_chunks(engine, shots, pvals, len(pvals), 0, n_trials, chunk, seed, np.shape(pvals))
+        return
+    for trial0 in range(0, n_trials, chunk):
+        yield trial0, draw_counts(shots, pvals, min(chunk, n_trials - trial0), "numpy", None)
 
 
 def device_multinomial(n, pvals, repeats=1, seed=None, engine=None):

@@ -31,10 +31,12 @@ from scipy.interpolate import interp1d
 
 import scipy.stats as sts
 
+from .. import _capi
 from .. import distributed as qdist
 from ..engine import get_engine
 from ..geometry import hs_dst, if_dst, trace_dst
 from ..routines import _left_inv
+from ..sampling import check_pvals, device_chunks, shared_seed
 
 
 class Mode(Enum):
@@ -67,6 +69,11 @@ def _engine_metric(dst, n_qubits, max_qubits=5):
     return "trace" if dst is trace_dst else "if" if dst is if_dst else None
 
 
+def _levels_or_default(conf_levels):
+    """The grid of confidence levels every interval is evaluated on when the caller names none."""
+    return np.linspace(1e-3, 1 - 1e-3, 1000) if conf_levels is None else conf_levels
+
+
 def _pop_hidden_keys(kwargs):
     return {k: v for k, v in kwargs.items() if k not in ("self", "tmg") and not k.startswith("__")}
 
@@ -88,8 +95,7 @@ class ConfidenceInterval(ABC):
             setattr(self, name, value)
 
     def __call__(self, conf_levels=None):
-        if conf_levels is None:
-            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
+        conf_levels = _levels_or_default(conf_levels)
         if not hasattr(self, "cl_to_dist"):
             self.setup()
         return self.cl_to_dist(conf_levels), conf_levels
@@ -178,9 +184,62 @@ class MomentInterval(ConfidenceInterval):
         return np.sqrt(distr.ppf(np.asarray(conf_levels, dtype=np.float64)[None, :])) * self._alpha(dim)
 
 
+def _distance_buffers(eng, n, centre):
+    """On the engine's device: (dist float64 (n,), status int32 (n,) zeroed, `centre` as complex128)."""
+    import torch
+
+    dev = torch.device("cuda", eng.device)
+    return (torch.empty(n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+            torch.from_numpy(np.ascontiguousarray(centre, dtype=np.complex128)).to(dev))
+
+
+# What a batch of resamples raises, in order of precedence: (status code -- None: any but 0 --, exception, text).
+_STATE_ERRORS = ((1, np.linalg.LinAlgError, "starting point of the MLE is not positive definite"),
+                 (_capi.TRIAL_SHOTS, ValueError, "per-setting totals of a trial do not match the registered shots"))
+_PROCESS_ERRORS = ((None, ValueError, "a resampled process has no finite Choi matrix (an input state without counts)"),)
+
+
+def _error_flags(status, errors):
+    """Bool device tensor: which of `errors` the int32 `status` of a batch shows."""
+    import torch
+
+    flags = [(status != 0 if code is None else status == code).any() for code, _, _ in errors]
+    return torch.stack(flags) if len(flags) > 1 else flags[0].reshape(1)  # (one flag: no launch of its own)
+
+
+def _agreed_flags(bad):
+    """This rank's `_error_flags` OR-ed over the ranks, as int64 on the host: every rank raises, or none.  One
+    `allgather_equal` when there are several ranks -- a rank with an empty shard takes part with zeros."""
+    bad = bad.cpu().numpy().astype(np.int64)
+    if qdist.world()[1] > 1:
+        bad = qdist.allgather_equal(bad).max(axis=0)
+    return bad
+
+
+def _raise_flagged(bad, errors):
+    for flag, (_, kind, text) in zip(bad, errors):
+        if flag:
+            raise kind(text)
+
+
 class _ShardedBootstrap:
     """What the one-pass bootstraps keep of their resamples: `boot_dist` and `boot_counts`, plain attributes on the
     two-pass paths, fetched from where `_setup_fused` left them on first use otherwise."""
+
+    def _finish_fused(self, boot, eng, counts, dist, status, errors):
+        """The end of a one-pass bootstrap, whose launches wrote this rank's `dist` and `status`: sync; the shard's
+        `errors`, agreed over the ranks (`_agreed_flags`: one collective), are raised in order; sampler='device' on one
+        rank leaves `boot` with the results of the last resample (`counts[-1]`), as the last experiment() would;
+        `boot_dist` keeps the distances in resample order on the device (all-gathered when read); the shard is sorted
+        where it is, and `cl_to_dist` evaluates interp1d's order statistics across the ranks (distributed.ShardedSample)
+        -- no all-gather of the sample unless somebody reads `boot_dist` / `cl_to_dist.y`."""
+        eng.sync()
+        _raise_flagged(_agreed_flags(_error_flags(status, errors)), errors)
+        if self.sampler == "device" and qdist.world()[1] == 1:
+            boot.results = counts[-1].cpu().numpy()
+        self._dist_shard, self._boot_dist = dist.clone(), None  # resample order; the sample below is sorted in place
+        self.sample = qdist.ShardedSample(dist, self.n_points, engine=eng)
+        self.cl_to_dist = _SampleInterp(self.sample)
 
     @property
     def boot_dist(self):
@@ -259,52 +318,38 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
     def _setup_fused(self, boot, metric=None):
         """The loop of interval.py:598-609 for the Hilbert-Schmidt distance and the 'lin' / 'mle' estimators, as this
         rank's shard of it: the shard's counts go to (sampler='numpy': one C call on np.random's stream on rank 0,
-        broadcast) or are drawn in (sampler='device': rows keyed by their global index, each rank draws only its own)
-        HBM, ONE launch family reconstructs them and writes the distance to `state` (qt_lin_dist_batch /
-        qt_mle_dist_batch: 8 bytes per resample leave the kernel, no density matrices), the shard is sorted where it is,
-        and `cl_to_dist` evaluates interp1d's order statistics across the ranks (quantpy_amd.distributed.ShardedSample)
-        -- no all-gather of the sample unless somebody reads `boot_dist` / `cl_to_dist.y`.
+        broadcast) or are drawn in (sampler='device': row resample * S + setting of the table keyed by `shared_seed`,
+        each rank draws only its own: `device_chunks`, the shard as one chunk) HBM, ONE launch family reconstructs them
+        and writes the distance to `state` (qt_lin_dist_batch / qt_mle_dist_batch: 8 bytes per resample leave the
+        kernel, no density matrices), and `_finish_fused` ends the pass.
         `metric` = 'trace' / 'if': the same, except that the shard is reconstructed in chunks of whole
         trials into a workspace of at most `_CHUNK_BYTES` of density matrices, and `Engine.distance_dev` writes each
         chunk's trace distances / infidelities to `state` into the shard's `dist`: the matrices never leave HBM."""
         import torch
 
-        from .. import _capi
-        from ..sampling import resolve_seed
-        from .state import born_probabilities
-
         tmg = self.tmg
-        rank, world = qdist.world()
         lo, hi = qdist.shard_bounds(self.n_points)
-        povm_matrix, shots = boot._experiment_arguments(tmg.n_measurements, tmg.povm_matrix)
+        povm_matrix, shots, pvals = boot._experiment_tables(tmg.n_measurements, tmg.povm_matrix)
         boot.povm_matrix, boot.n_measurements = povm_matrix, np.asarray(shots)
         eng = boot._engine()
         dev = torch.device("cuda", eng.device)
-        n_set, n_out = np.asarray(povm_matrix).shape[:2]
+        n_set, n_out = pvals.shape
         d = 2 ** self.state.n_qubits
         if self.sampler == "device":
-            pvals = born_probabilities(povm_matrix, self.state.bloch)
-            if not (np.all(pvals >= 0) and np.all(pvals[:, :-1].sum(1) <= 1.0 + 1e-12)):
-                raise ValueError("sum(pvals[:-1]) > 1.0")
-            seed = resolve_seed(self.seed)
-            if world > 1:  # one Philox key for the whole table: rank 0's
-                seed = int(qdist.broadcast_array(np.array([seed], dtype=np.uint64).view(np.int64)).view(np.uint64)[0])
-            counts = torch.empty((hi - lo, n_set, n_out), dtype=torch.int64, device=dev)
-            if hi > lo:
-                eng.device_multinomial(np.asarray(shots).astype(np.int64), pvals, (hi - lo) * n_set, seed,
-                                       first_row=lo * n_set, out=counts)
+            check_pvals(pvals)
+            seed = shared_seed(self.seed)
+            counts = torch.empty((0, n_set, n_out), dtype=torch.int64, device=dev)
+            for _, counts in device_chunks(eng, shots, pvals, n_set, lo, hi, hi - lo, seed, (n_set, n_out)):
+                pass  # the whole shard is one chunk: `boot_counts` reads it
             self._boot_counts_host, self._boot_counts_device = None, counts
         elif self.sampler == "numpy":
-            host = boot.experiment_batch(tmg.n_measurements, tmg.povm_matrix, self.n_points) if rank == 0 or world == 1 else \
+            host = boot.experiment_batch(tmg.n_measurements, tmg.povm_matrix, self.n_points) if qdist.world()[0] == 0 else \
                 np.empty((self.n_points, n_set, n_out), dtype=np.int64)
-            host = qdist.broadcast_array(host)
-            self.boot_counts = host
-            counts = torch.from_numpy(np.ascontiguousarray(host[lo:hi])).to(dev)
+            self.boot_counts = qdist.broadcast_array(host)
+            counts = torch.from_numpy(np.ascontiguousarray(self.boot_counts[lo:hi])).to(dev)
         else:
             raise ValueError(f"sampler must be 'numpy' or 'device', not {self.sampler!r}")
-        dist = torch.empty(hi - lo, dtype=torch.float64, device=dev)
-        status = torch.zeros(hi - lo, dtype=torch.int32, device=dev)
-        centre = torch.from_numpy(np.ascontiguousarray(self.state.matrix, dtype=np.complex128)).to(dev)
+        dist, status, centre = _distance_buffers(eng, hi - lo, self.state.matrix)
         if hi > lo and metric is None:
             if self.method == "lin":
                 eng.lin_dist_dev(counts, centre, dist, physical=self.physical, status=status)
@@ -321,21 +366,7 @@ class BootstrapStateInterval(_ShardedBootstrap, ConfidenceInterval):
                     eng.mle_dev(counts[c0:c1], rho[:c1 - c0], init=self.init, max_iter=self.max_iter, tol=self.tol,
                                 status=status[c0:c1])
                 eng.distance_dev(rho[:c1 - c0], centre, dist[c0:c1], metric)
-        eng.sync()
-        st = status.cpu().numpy()
-        bad = np.array([int(np.any(st == 1)), int(np.any(st == _capi.TRIAL_SHOTS))])
-        if world > 1:  # every rank raises, or none
-            bad = qdist.allgather_equal(bad).max(axis=0)
-        if bad[0]:
-            raise np.linalg.LinAlgError("starting point of the MLE is not positive definite")
-        if bad[1]:
-            raise ValueError("per-setting totals of a trial do not match the registered shots")
-        if self.sampler == "device" and world == 1:
-            boot.results = counts[-1].cpu().numpy()  # the tomograph is left as the last experiment() would leave it
-        self._dist_shard = dist.clone()  # resample order (boot_dist); the sample below is sorted in place
-        self._boot_dist = None
-        self.sample = qdist.ShardedSample(dist, self.n_points, engine=eng)
-        self.cl_to_dist = _SampleInterp(self.sample)
+        self._finish_fused(boot, eng, counts, dist, status, _STATE_ERRORS)
 
 
 class _SampleInterp:
@@ -363,20 +394,59 @@ class _SampleInterp:
         return np.linspace(0, 1, self.sample.n_total)
 
 
-class MHMCStateInterval(ConfidenceInterval):
+class _ChainInterval(ConfidenceInterval):
+    """The chain set-up of both MHMC intervals.  A subclass names the start point (`_start`), the engine's chain
+    (`_CHAIN`) and what a kept chain state is (`_kept`)."""
+
+    def _sample_distances(self, eng, dim, centre, metric):
+        """One run of the chain in `dim` real parameters -> the distances of its samples to `centre`, unsorted.
+        `_x_t` is the state the next run continues from, `_burned` whether the burn-in is behind it; without
+        `warm_start` (or on the first run) the chain starts at `_start` and burns in.  The random numbers are drawn as
+        the reference draws them (`_proposal_increments`, then `numpy.random.rand`: increments before uniforms, the
+        burn-in's before the samples') and the whole run is ONE launch of `_CHAIN`.  Sets `samples` (every
+        `thinning`-th state behind the burn-in) and `acceptance_rate` (the accepted share of the steps behind it)."""
+        tmg = self.tmg
+        if not (self.warm_start and hasattr(self, "_x_t")):
+            self._x_t, self._burned = self._start(eng, centre), False
+        jump = _proposal_increments(dim)
+        total = self.n_points * self.thinning
+        skip = 0 if self._burned else self.burn_steps
+        parts = [(jump(steps), np.random.rand(steps)) for steps in ([total] if self._burned else [skip, total])]
+        deltas, uniforms = (np.concatenate(part) for part in zip(*parts))
+        chain, accepted = getattr(eng, self._CHAIN)(tmg.results, self._x_t, deltas, uniforms, self.step)
+        self._burned = True
+        if len(chain):
+            self._x_t = chain[-1].copy()
+        self.samples, mats = self._kept(eng, chain[skip::self.thinning][: self.n_points])
+        self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
+        if tmg.dst is hs_dst or metric:
+            return eng.distance(mats, centre, metric)
+        return np.array([tmg.dst(m, centre) for m in mats], dtype=np.float64)
+
+
+class MHMCStateInterval(_ChainInterval):
     """Metropolis-Hastings samples of the likelihood on the Cholesky parameters around the point estimate
-    (reference interval.py:689-750, mhmc.py): distances tmg.dst(sample, state), sorted.
-    The random numbers are drawn here exactly as the reference draws them -- proposal increments from
-    scipy's frozen `multivariate_normal(zeros(4^n))`, then `numpy.random.rand`, first for the burn-in,
-    then for the samples -- and the chain itself (one likelihood evaluation per step, inherently serial)
-    runs in one launch of `qt_mhmc_state`, for n = 1 .. 5 qubits (n = 4, 5: one workgroup per chain)."""
+    (reference interval.py:689-750, mhmc.py): distances tmg.dst(sample, state), sorted.  The random numbers are
+    drawn on the host in the reference's order (`_ChainInterval`); the chain itself (one likelihood evaluation per
+    step, inherently serial) runs in one launch of `qt_mhmc_state`, for n = 1 .. 5 qubits (n = 4, 5: one workgroup
+    per chain)."""
 
     def __init__(self, tmg, n_points=1000, step=0.01, burn_steps=1000, thinning=1, warm_start=False,
                  use_new_estimate=False, state=None, verbose=False):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
 
-    def setup(self):
+    _CHAIN = "mhmc_state"
 
+    def _start(self, eng, centre):
+        x0, status = eng.chol_param(centre)
+        if status == 1:  # the reference fails inside scipy.linalg.cholesky here
+            raise np.linalg.LinAlgError("the state the chain starts from is not positive definite")
+        return x0
+
+    def _kept(self, eng, chain):
+        return chain, eng.chol_unparam(chain)  # samples: Cholesky parameters; measured: their density matrices
+
+    def setup(self):
         if self.mode == Mode.CHANNEL:
             raise NotImplementedError("This interval works only for state tomography")
         tmg = self.tmg
@@ -384,34 +454,9 @@ class MHMCStateInterval(ConfidenceInterval):
             self.state = tmg.reconstructed_state
         elif self.state is None:
             self.state = tmg.point_estimate(method="mle", physical=True)
-        eng = tmg._engine()
-        dim = 4**tmg.state.n_qubits
-        if not (self.warm_start and hasattr(self, "_x_t")):
-            x0, status = eng.chol_param(np.asarray(self.state.matrix, dtype=np.complex128))
-            if status == 1:  # the reference fails inside scipy.linalg.cholesky here
-                raise np.linalg.LinAlgError("the state the chain starts from is not positive definite")
-            self._x_t, self._burned = x0, False
-        jump = _proposal_increments(dim)
-        parts = []
-        if not self._burned:
-            parts.append((jump(self.burn_steps), np.random.rand(self.burn_steps)))
-        total = self.n_points * self.thinning
-        parts.append((jump(total), np.random.rand(total)))
-        deltas = np.concatenate([p[0] for p in parts])
-        uniforms = np.concatenate([p[1] for p in parts])
-        chain, accepted = eng.mhmc_state(tmg.results, self._x_t, deltas, uniforms, self.step)
-        skip = 0 if self._burned else self.burn_steps
-        self._burned = True
-        self._x_t = chain[-1].copy() if len(chain) else self._x_t
-        self.samples = chain[skip::self.thinning][: self.n_points]
-        self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
-        mats = eng.chol_unparam(self.samples)
-        metric = _engine_metric(tmg.dst, tmg.state.n_qubits)
-        if tmg.dst is hs_dst or metric:
-            dist = eng.distance(mats, np.asarray(self.state.matrix, dtype=np.complex128), metric)
-        else:
-            dist = np.array([tmg.dst(m, self.state.matrix) for m in mats], dtype=np.float64)
-        self._finish(dist)
+        centre = np.asarray(self.state.matrix, dtype=np.complex128)
+        self._finish(self._sample_distances(tmg._engine(), 4**tmg.state.n_qubits, centre,
+                                            _engine_metric(tmg.dst, tmg.state.n_qubits)))
 
 
 class SugiyamaInterval(ConfidenceInterval):
@@ -422,8 +467,6 @@ class SugiyamaInterval(ConfidenceInterval):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
 
     def setup(self):
-        from ..geometry import if_dst, trace_dst
-
         if self.mode == Mode.CHANNEL:
             raise NotImplementedError("Sugiyama interval works only for state tomography")
         tmg = self.tmg
@@ -460,8 +503,7 @@ class HolderInterval(ConfidenceInterval):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
 
     def __call__(self, conf_levels=None):
-        if conf_levels is None:
-            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
+        conf_levels = _levels_or_default(conf_levels)
         if not hasattr(self, "intervals"):
             self.setup()
         results = [interval(conf_levels) for interval in self.intervals]
@@ -532,7 +574,36 @@ def _objective_or_one(value, to_fidelity):
     return np.where(np.isfinite(value) & (value != 0.0), to_fidelity(value), 1.0)
 
 
-class MomentFidelityStateInterval(MomentInterval):
+class _FidelityBounds:
+    """A two-sided interval: `interval(conf_levels)` -> ((lower bounds, upper bounds), conf_levels), interpolated in the
+    table `_tabulate` leaves (`conf_levels`, `dist_min`, `dist_max`, `cl_to_dist_min`, `cl_to_dist_max`)."""
+
+    def __call__(self, conf_levels=None):
+        conf_levels = _levels_or_default(conf_levels)
+        if not hasattr(self, "cl_to_dist_max"):
+            self.setup()
+        return (self.cl_to_dist_min(conf_levels), self.cl_to_dist_max(conf_levels)), conf_levels
+
+    def _tabulate(self, conf_levels, dist_min, dist_max):
+        self.conf_levels, self.dist_min, self.dist_max = conf_levels, dist_min, dist_max
+        self.cl_to_dist_min = interp1d(conf_levels, dist_min)
+        self.cl_to_dist_max = interp1d(conf_levels, dist_max)
+
+    def _tabulate_polytope(self, lp, deltas, frequencies, shots, to_min, to_max):
+        """The end of a polytope interval's setup(): lp = (objectives (n_points, 2) of min c . x and min -c . x, status,
+        iterations) at `deltas`.  A program that did not converge raises; the bounds are to_min / to_max of the
+        objectives through `_objective_or_one`, the level of a widening is `count_confidence(delta)`."""
+        obj, status, iters = lp
+        bad = np.flatnonzero((status == _capi.LP_NOT_CONVERGED).any(axis=1))
+        if bad.size:
+            raise RuntimeError(f"the interior-point LP solver did not converge at delta index {bad[:8].tolist()}")
+        self.deltas, self.lp_status, self.lp_iters = deltas, status, iters
+        shots = np.asarray(shots, dtype=np.float64)
+        self._tabulate(np.array([count_confidence(d, frequencies, shots) for d in deltas]),
+                       _objective_or_one(obj[:, 0], to_min), _objective_or_one(obj[:, 1], to_max))
+
+
+class MomentFidelityStateInterval(_FidelityBounds, MomentInterval):
     """Fidelity bounds with a target state from the moment interval's radii (reference interval.py:113-160).
 
     For every level of a fixed 280-point grid the reference solves two SOCPs with cvxopt: minimise (maximise)
@@ -549,13 +620,6 @@ class MomentFidelityStateInterval(MomentInterval):
         super().__init__(tmg, distr_type=distr_type)
         self.target_state = target_state
         _state_only(self, "MomentFidelityStateInterval")
-
-    def __call__(self, conf_levels=None):
-        if conf_levels is None:
-            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
-        if not hasattr(self, "cl_to_dist_max"):
-            self.setup()
-        return (self.cl_to_dist_min(conf_levels), self.cl_to_dist_max(conf_levels)), conf_levels
 
     @staticmethod
     def levels():
@@ -580,14 +644,10 @@ class MomentFidelityStateInterval(MomentInterval):
         norm = np.linalg.norm(c[1:])
         low = np.where(rho2 >= 0, centre - rho * norm, np.nan)     # min c . x
         high = np.where(rho2 >= 0, -centre - rho * norm, np.nan)   # min -c . x
-        self.conf_levels = conf_levels
-        self.dist_min = _objective_or_one(low, lambda v: v * dim)
-        self.dist_max = _objective_or_one(high, lambda v: -v * dim)
-        self.cl_to_dist_min = interp1d(conf_levels, self.dist_min)
-        self.cl_to_dist_max = interp1d(conf_levels, self.dist_max)
+        self._tabulate(conf_levels, _objective_or_one(low, lambda v: v * dim), _objective_or_one(high, lambda v: -v * dim))
 
 
-class PolytopeStateInterval(ConfidenceInterval):
+class PolytopeStateInterval(_FidelityBounds, ConfidenceInterval):
     """Fidelity bounds with a target state from a polytope of states (Kiktenko et al., arXiv:2109.04734; reference
     interval.py:268-335).
 
@@ -610,13 +670,6 @@ class PolytopeStateInterval(ConfidenceInterval):
 
     def _lp(self, A, C, b):
         return get_engine(self.tmg.state.n_qubits).lp_ineq_batch(A, C, b)
-
-    def __call__(self, conf_levels=None):
-        if conf_levels is None:
-            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
-        if not hasattr(self, "cl_to_dist_max"):
-            self.setup()
-        return (self.cl_to_dist_min(conf_levels), self.cl_to_dist_max(conf_levels)), conf_levels
 
     def programs(self):
         """(A, b (n_points, M), c, deltas, frequencies) of the reference's LPs (interval.py:297-316)."""
@@ -644,19 +697,8 @@ class PolytopeStateInterval(ConfidenceInterval):
             self.target_state = tmg.state
         dim = 2**tmg.state.n_qubits
         A, b, c, deltas, frequencies = self.programs()
-        obj, status, iters = self._lp(A, np.stack([c, -c]), b)
-        from .. import _capi
-
-        bad = np.flatnonzero((status == _capi.LP_NOT_CONVERGED).any(axis=1))
-        if bad.size:
-            raise RuntimeError(f"the interior-point LP solver did not converge at delta index {bad[:8].tolist()}")
-        self.deltas, self.lp_status, self.lp_iters = deltas, status, iters
-        self.dist_min = _objective_or_one(obj[:, 0], lambda v: 1 / dim + v * dim)
-        self.dist_max = _objective_or_one(obj[:, 1], lambda v: 1 / dim - v * dim)
-        shots = np.asarray(tmg.n_measurements, dtype=np.float64)
-        self.conf_levels = np.array([count_confidence(d, frequencies, shots) for d in deltas])
-        self.cl_to_dist_min = interp1d(self.conf_levels, self.dist_min)
-        self.cl_to_dist_max = interp1d(self.conf_levels, self.dist_max)
+        self._tabulate_polytope(self._lp(A, np.stack([c, -c]), b), deltas, frequencies, tmg.n_measurements,
+                                lambda v: 1 / dim + v * dim, lambda v: 1 / dim - v * dim)
 
 
 def _needs_cvxopt(name, lines, see=""):
@@ -674,7 +716,7 @@ PolytopeProcessInterval = _needs_cvxopt(
     ".  The same fidelity bounds, from the batched GPU LP solver, are quantpy_amd.tomography.polytopes.ProcessFidelityInterval.")
 
 
-class MHMCProcessInterval(ConfidenceInterval):
+class MHMCProcessInterval(_ChainInterval):
     """Metropolis-Hastings samples of the process likelihood on the Choi vector (reference
     interval.py:763-850): every proposal x + step * delta is projected onto the CPTP set
     (`_cptp_update_rule`, process.py:279-281), the target is exp(-nll) with the raw counts.  Draws on the
@@ -687,8 +729,18 @@ class MHMCProcessInterval(ConfidenceInterval):
                  channel=None, verbose=False, return_samples=False):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
 
-    def setup(self):
+    _CHAIN = "mhmc_process"
 
+    def _start(self, eng, centre):
+        return centre.copy()
+
+    def _kept(self, eng, chain):
+        # mhmc.py:66 collects the samples in a REAL array: the imaginary parts of the chain states are
+        # dropped there (NumPy's ComplexWarning), and the distances are those of the real parts
+        real = np.ascontiguousarray(chain.real)
+        return real, real
+
+    def setup(self):
         if self.mode == Mode.STATE:
             raise NotImplementedError("This interval works only for process tomography")
         tmg = self.tmg
@@ -697,36 +749,11 @@ class MHMCProcessInterval(ConfidenceInterval):
         elif self.channel is None:
             self.channel = tmg.point_estimate(self.method, states_est_method=self.states_est_method,
                                               states_physical=self.states_physical, states_init=self.states_init)
-        eng = tmg._engine()
-        dim = 16**tmg.channel.n_qubits
         centre = np.asarray(self.channel.choi.matrix, dtype=np.complex128)
-        if not (self.warm_start and hasattr(self, "_x_t")):
-            self._x_t, self._burned = centre.copy(), False
-        jump = _proposal_increments(dim)
-        parts = []
-        if not self._burned:
-            parts.append((jump(self.burn_steps), np.random.rand(self.burn_steps)))
-        total = self.n_points * self.thinning
-        parts.append((jump(total), np.random.rand(total)))
-        deltas = np.concatenate([p[0] for p in parts])
-        uniforms = np.concatenate([p[1] for p in parts])
-        chain, accepted = eng.mhmc_process(tmg.results, self._x_t, deltas, uniforms, self.step)
-        skip = 0 if self._burned else self.burn_steps
-        self._burned = True
-        if len(chain):
-            self._x_t = chain[-1].copy()
-        # mhmc.py:66 collects the samples in a REAL array: the imaginary parts of the chain states are
-        # dropped there (NumPy's ComplexWarning), and the distances are those of the real parts
-        self.samples = np.ascontiguousarray(chain[skip::self.thinning][: self.n_points].real)
-        self.acceptance_rate = float(accepted[skip:].mean()) if total else 0.0
         # trace distance / infidelity of the Choi matrices, 2n-qubit objects: on the engine (dim 4, 16, 64); the real
         # parts of Hermitian chain states are symmetric, hence Hermitian, which is what metric_dist takes
         metric = _engine_metric(tmg.dst, 2 * self.channel.n_qubits, max_qubits=6)
-        if tmg.dst is hs_dst or metric:
-            dist = eng.distance(self.samples, centre, metric)
-        else:
-            dist = np.array([tmg.dst(m, centre) for m in self.samples], dtype=np.float64)
-        dist = np.sort(dist)
+        dist = np.sort(self._sample_distances(tmg._engine(), 16**tmg.channel.n_qubits, centre, metric))
         conf_levels = np.linspace(0, 1, len(dist))
         if self.return_samples:
             return dist, conf_levels, self.acceptance_rate, list(self.samples)
@@ -792,36 +819,28 @@ class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
         np.random's stream on rank 0, broadcast) or are drawn in (sampler='device': row (resample * 4^n + input) * S +
         setting of the table keyed by that global index, `ProcessTomograph.experiment_batch`'s keying, so each rank
         draws only its own rows) HBM, qt_lifp_dist_batch reconstructs them and writes the distance to `channel` -- 8
-        bytes per resample leave the kernels, no Choi matrices -- and the sorted shard stays where it is behind a
-        `ShardedSample`.  The device sampler's shard is drawn and consumed `chunk` resamples at a time in one count
-        buffer; rows being keyed globally, the chunking changes no draw.  As in the reference's loop, `cptp` is passed
-        on and `tol` is not."""
+        bytes per resample leave the kernels, no Choi matrices -- and `_finish_fused` ends the pass.  The device
+        sampler's shard is drawn and consumed `chunk` resamples at a time (`device_chunks`: the chunking changes no
+        draw).  As in the reference's loop, `cptp` is passed on and `tol` is not."""
         import torch
 
-        from ..sampling import resolve_seed
-
-        rank, world = qdist.world()
         lo, hi = qdist.shard_bounds(self.n_points)
         if self.sampler == "numpy":
             if self.seed is not None:  # (every rank: what draw_counts tells rank 0)
                 raise ValueError("sampler='numpy' draws from np.random's global stream: seed it with np.random.seed")
-            if rank == 0:
+            if qdist.world()[0] == 0:
                 host = boot.experiment_batch(shots, povm=povm, repeats=self.n_points)
             else:
                 povm_matrix, shots_set, probas = boot._experiment_tables(shots, povm)
                 host = np.empty((self.n_points, len(boot.tomographs), povm_matrix.shape[0], probas.shape[1]), dtype=np.int64)
-            host = qdist.broadcast_array(host)
-            self.boot_counts = host
+            self.boot_counts = host = qdist.broadcast_array(host)
             n_in, n_set, n_out = host.shape[1:]
         elif self.sampler == "device":
             povm_matrix, shots_set, probas = boot._experiment_tables(shots, povm)
             n_in = len(boot.tomographs)
             n_set, n_out = probas.shape[0] // n_in, probas.shape[1]
-            if not (np.all(probas >= 0) and np.all(probas[:, :-1].sum(1) <= 1.0 + 1e-12)):
-                raise ValueError("sum(pvals[:-1]) > 1.0")
-            seed = resolve_seed(self.seed)
-            if world > 1:  # one Philox key for the whole table: rank 0's
-                seed = int(qdist.broadcast_array(np.array([seed], dtype=np.uint64).view(np.int64)).view(np.uint64)[0])
+            check_pvals(probas)
+            seed = shared_seed(self.seed)
             shots_rows = np.tile(np.asarray(shots_set).astype(np.int64), n_in)
         else:
             raise ValueError(f"sampler must be 'numpy' or 'device', not {self.sampler!r}")
@@ -829,39 +848,20 @@ class BootstrapProcessInterval(_ShardedBootstrap, ConfidenceInterval):
             for t in boot.tomographs:
                 t.povm_matrix, t.n_measurements = povm_matrix, np.asarray(shots_set)
         eng = boot._engine()
-        dev = torch.device("cuda", eng.device)
         rows = n_in * n_set  # table rows per resample
-        dist = torch.empty(hi - lo, dtype=torch.float64, device=dev)
-        status = torch.zeros(hi - lo, dtype=torch.int32, device=dev)
-        centre = torch.from_numpy(np.ascontiguousarray(self.channel.choi.matrix, dtype=np.complex128)).to(dev)
-        if self.sampler == "numpy":
-            if hi > lo:
-                counts = torch.from_numpy(np.ascontiguousarray(host[lo:hi])).to(dev)
-                eng.lifp_dist_dev(counts, centre, dist, cptp=self.cptp, status=status)
-        else:
+        dist, status, centre = _distance_buffers(eng, hi - lo, self.channel.choi.matrix)
+        counts = None
+        if self.sampler == "numpy" and hi > lo:
+            counts = torch.from_numpy(np.ascontiguousarray(host[lo:hi])).to(dist.device)
+            eng.lifp_dist_dev(counts, centre, dist, cptp=self.cptp, status=status)
+        elif self.sampler == "device":
             chunk = int(self.chunk) if self.chunk else max(1, self._CHUNK_BYTES // (rows * n_out * 8))
-            chunk = max(1, min(chunk, hi - lo))
-            n_d, p_d = torch.from_numpy(shots_rows).to(dev), torch.from_numpy(np.ascontiguousarray(probas)).to(dev)
-            buf = torch.empty((chunk, n_in, n_set, n_out), dtype=torch.int64, device=dev)
-            for c0 in range(lo, hi, chunk):  # one stream: a chunk's draw waits for the reconstruction before it
-                counts = buf[: min(chunk, hi - c0)]
-                eng.device_multinomial(n_d, p_d, counts.shape[0] * rows, seed, first_row=c0 * rows, out=counts)
-                eng.lifp_dist_dev(counts, centre, dist[c0 - lo: c0 - lo + counts.shape[0]], cptp=self.cptp,
-                                  status=status[c0 - lo: c0 - lo + counts.shape[0]])
+            # one stream: a chunk's draw waits for the reconstruction before it
+            for c0, counts in device_chunks(eng, shots_rows, probas, rows, lo, hi, chunk, seed, (n_in, n_set, n_out)):
+                c1 = c0 + counts.shape[0]
+                eng.lifp_dist_dev(counts, centre, dist[c0 - lo: c1 - lo], cptp=self.cptp, status=status[c0 - lo: c1 - lo])
             self._boot_counts_host = None
             self._boot_counts_device = lambda: (
                 eng.device_multinomial(shots_rows, probas, (hi - lo) * rows, seed, first_row=lo * rows) if hi > lo else
                 np.empty((0, n_out), dtype=np.int64)).reshape(hi - lo, n_in, n_set, n_out)
-        eng.sync()
-        bad = np.array([int(torch.any(status != 0).item())])
-        if world > 1:  # every rank raises, or none
-            bad = qdist.allgather_equal(bad).max(axis=0)
-        if bad[0]:
-            raise ValueError("a resampled process has no finite Choi matrix (an input state without counts)")
-        if self.sampler == "device" and world == 1:  # the tomographs are left as the last experiment() would leave them
-            for t, last in zip(boot.tomographs, counts[-1].cpu().numpy()):
-                t.results = last
-        self._dist_shard = dist.clone()  # resample order (boot_dist); the sample below is sorted in place
-        self._boot_dist = None
-        self.sample = qdist.ShardedSample(dist, self.n_points, engine=eng)
-        self.cl_to_dist = _SampleInterp(self.sample)
+        self._finish_fused(boot, eng, counts, dist, status, _PROCESS_ERRORS)

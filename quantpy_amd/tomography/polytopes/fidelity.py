@@ -10,16 +10,11 @@ four-qubit state 255).
 three qubits; the classes here are the ones to use.
 """
 import numpy as np
-from scipy.interpolate import interp1d
-
 from ... import _capi
 from ...engine import any_engine, get_engine
-from ...sampling import SAMPLERS, draw_counts, resolve_seed
-from ..interval import (ConfidenceInterval, Mode, PolytopeStateInterval, _objective_or_one, _pop_hidden_keys,
-                        count_confidence, count_delta)
-from ..process import ProcessTomograph
-from ..state import StateTomograph, born_probabilities
-from .verification import _weighted_povm, chunk_trials
+from ...sampling import SAMPLERS, draw_counts, resolve_seed, trial_chunks
+from ..interval import ConfidenceInterval, Mode, PolytopeStateInterval, _FidelityBounds, _pop_hidden_keys, count_delta
+from .verification import _weighted_povm, chunk_trials, qpt_tables, qst_tables
 
 __all__ = ["ProcessFidelityInterval", "StateFidelityInterval", "fidelity_qpt", "fidelity_qst", "process_matrix",
            "process_programs"]
@@ -75,7 +70,7 @@ class StateFidelityInterval(PolytopeStateInterval):
         return res
 
 
-class ProcessFidelityInterval(ConfidenceInterval):
+class ProcessFidelityInterval(_FidelityBounds, ConfidenceInterval):
     """Fidelity bounds with a target channel from the polytope of a process tomography (reference
     PolytopeProcessInterval, interval.py:338-418), n = 1 and 2 qubits.
 
@@ -90,13 +85,6 @@ class ProcessFidelityInterval(ConfidenceInterval):
         super().__init__(tmg, **_pop_hidden_keys(locals()))
         if self.mode != Mode.CHANNEL:
             raise NotImplementedError("ProcessFidelityInterval works only for process tomography")
-
-    def __call__(self, conf_levels=None):
-        if conf_levels is None:
-            conf_levels = np.linspace(1e-3, 1 - 1e-3, 1000)
-        if not hasattr(self, "cl_to_dist_max"):
-            self.setup()
-        return (self.cl_to_dist_min(conf_levels), self.cl_to_dist_max(conf_levels)), conf_levels
 
     def programs(self):
         """(A, b (n_points, M), c, deltas, frequencies (D, S, K)) of the reference's LPs (interval.py:362-400)."""
@@ -121,17 +109,9 @@ class ProcessFidelityInterval(ConfidenceInterval):
         dim = 4**tmg.channel.n_qubits
         A, b, c, deltas, frequencies = self.programs()
         engine = get_engine(tmg.channel.n_qubits)
-        (obj, status, iters), self.lp_resolved = engine._lp_ineq_by_size(A, np.stack([c, -c]), b)
-        bad = np.flatnonzero((status == _capi.LP_NOT_CONVERGED).any(axis=1))
-        if bad.size:
-            raise RuntimeError(f"the interior-point LP solver did not converge at delta index {bad[:8].tolist()}")
-        self.deltas, self.lp_status, self.lp_iters = deltas, status, iters
-        self.dist_min = _objective_or_one(obj[:, 0], lambda v: 1 / dim + v)
-        self.dist_max = _objective_or_one(obj[:, 1], lambda v: 1 / dim - v)
-        shots = np.asarray(tmg.tomographs[0].n_measurements, dtype=np.float64)
-        self.conf_levels = np.array([count_confidence(d, frequencies, shots) for d in deltas])
-        self.cl_to_dist_min = interp1d(self.conf_levels, self.dist_min)
-        self.cl_to_dist_max = interp1d(self.conf_levels, self.dist_max)
+        lp, self.lp_resolved = engine._lp_ineq_by_size(A, np.stack([c, -c]), b)
+        self._tabulate_polytope(lp, deltas, frequencies, tmg.tomographs[0].n_measurements, lambda v: 1 / dim + v,
+                                lambda v: 1 / dim - v)
 
 
 def _study(probas, shots, A, offset, c, scale, base, clip_b, conf_levels, n_trials, sampler, seed, return_table, chunk):
@@ -147,10 +127,7 @@ def _study(probas, shots, A, offset, c, scale, base, clip_b, conf_levels, n_tria
     if sampler == "numpy":
         draw_counts(shots, probas, 1, "numpy", seed)  # the notebook runs one experiment before its loop
     else:
-        import torch
-
         seed = resolve_seed(seed)
-        device = torch.device("cuda", engine.device)
     if chunk is None:
         cap = kLaunchProgramsSmall if A.shape[1] <= 64 else kLaunchProgramsLarge
         chunk = min(chunk_trials(n_trials, n_rows * n_out, n_lv), cap // (2 * max(n_lv, 1)), kRhsBytes // (8 * m * max(n_lv, 1)))
@@ -163,16 +140,11 @@ def _study(probas, shots, A, offset, c, scale, base, clip_b, conf_levels, n_tria
     iters = np.zeros((n_trials, n_lv, 2), dtype=np.int32)
     resolved = np.zeros((n_trials, n_lv), dtype=bool)
     shots_rows = np.asarray(shots, dtype=np.float64)[:, None]
-    for start in range(0, n_trials, chunk):
-        size = min(chunk, n_trials - start)
-        if sampler == "numpy":
-            counts = draw_counts(shots, probas, size, "numpy", None)
-            dl = engine.polytope_coverage(counts, shots, levels, return_deltas=True)
-        else:  # rows of the Philox stream (seed, trial * R + setting): the chunking does not change a draw
-            counts_d = torch.empty((size, n_rows, n_out), dtype=torch.int64, device=device)
-            engine.device_multinomial(shots, probas, size * n_rows, seed, first_row=start * n_rows, out=counts_d)
-            dl = engine.polytope_coverage(counts_d, shots, levels, return_deltas=True)
-            counts = counts_d.cpu().numpy()
+    for start, counts in trial_chunks(engine, shots, probas, n_trials, chunk, sampler, seed):
+        size = counts.shape[0]
+        dl = engine.polytope_coverage(counts, shots, levels, return_deltas=True)
+        if sampler == "device":
+            counts = counts.cpu().numpy()
         if n_lv == 0:
             continue
         freq = np.clip(counts.reshape(size, n_rows, n_out) / shots_rows, 1e-15, 1 - 1e-15).reshape(size, 1, m)
@@ -207,12 +179,8 @@ def fidelity_qst(state, target_state, conf_levels, n_measurements=1000, n_trials
     if n > 4:
         raise NotImplementedError(f"fidelity_qst supports n <= 4 qubits (4^n - 1 <= 255 LP variables); got n = {n}")
     dim = 2**n
-    povm_matrix, shots = StateTomograph(state)._experiment_arguments(n_measurements, "proj-set")
-    shots = np.asarray(shots, dtype=np.float64)
-    weighted = _weighted_povm(np.asarray(povm_matrix, dtype=np.float64), shots)
-    A = np.ascontiguousarray(weighted[:, 1:]) * dim
+    probas, shots, weighted, A = qst_tables(state, n_measurements)
     c = np.asarray(target_state.bloch, dtype=np.float64)[1:]
-    probas = born_probabilities(povm_matrix, state.bloch)
     return _study(probas, shots, A, weighted[:, 0], c, float(dim), 1 / dim, True, conf_levels, n_trials, sampler, seed,
                   return_table, chunk)
 
@@ -227,14 +195,8 @@ def fidelity_qpt(channel, target_channel, conf_levels, n_measurements=1000, n_tr
     if n > 2:
         raise NotImplementedError(f"fidelity_qpt supports n <= 2 qubits (16^n - 4^n <= 255 LP variables); got n = {n}")
     dim = 4**n
-    tmg = ProcessTomograph(channel, input_states=input_states)
-    outputs = [StateTomograph(channel.transform(rho)) for rho in tmg.input_basis.elements]
-    povm_matrix, shots = outputs[0]._experiment_arguments(n_measurements, "proj-set")
-    shots = np.asarray(shots, dtype=np.float64)
-    weighted = _weighted_povm(np.asarray(povm_matrix, dtype=np.float64), shots)
-    states_matrix = np.asarray([rho.T.bloch for rho in tmg.input_basis.elements], dtype=np.float64)
+    probas, shots, weighted, states_matrix = qpt_tables(channel, n_measurements, input_states)
     A = process_matrix(states_matrix, weighted, dim)
     c = np.asarray(target_channel.choi.bloch, dtype=np.float64).reshape(dim, dim)[:, 1:].ravel()
-    probas = np.concatenate([born_probabilities(povm_matrix, out.state.bloch) for out in outputs])
-    return _study(probas, np.tile(shots, len(outputs)), A, np.tile(weighted[:, 0], len(outputs)), c, 1.0, 1 / dim, False,
-                  conf_levels, n_trials, sampler, seed, return_table, chunk)
+    return _study(probas, shots, A, np.tile(weighted[:, 0], len(states_matrix)), c, 1.0, 1 / dim, False, conf_levels,
+                  n_trials, sampler, seed, return_table, chunk)

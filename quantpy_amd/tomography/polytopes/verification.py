@@ -9,9 +9,9 @@ file (they carry `__test__ = False` as a second guard).
 import numpy as np
 
 from ...engine import any_engine
-from ...sampling import SAMPLERS, draw_counts, resolve_seed
+from ...sampling import SAMPLERS, draw_counts, resolve_seed, trial_chunks
 from ..process import ProcessTomograph
-from ..state import StateTomograph, born_probabilities
+from ..state import StateTomograph
 
 # One launch handles a chunk of trials.  A chunk is bounded by the work of its launch -- trials x levels x 34 bisection
 # steps x table entries <= kLaunchEvaluations evaluations of exp(-n KL), which at an estimated 5e10 evaluations per
@@ -38,26 +38,16 @@ def _run(probas, shots, truth, clip_b, conf_levels, n_trials, sampler, seed, ret
     if sampler not in SAMPLERS:
         raise ValueError(f"sampler must be one of {SAMPLERS}, not {sampler!r}")
     levels = np.asarray(conf_levels, dtype=np.float64)
-    n_rows, n_out = probas.shape
     engine = any_engine()
     if sampler == "numpy":
         # the reference runs one experiment before its loop (verification.py:13-14, :45-46) and one per trial
         draw_counts(shots, probas, 1, "numpy", seed)
     else:
-        import torch
-
         seed = resolve_seed(seed)
-        device = torch.device("cuda", engine.device)
-    chunk = chunk_trials(n_trials, n_rows * n_out, levels.size)
+    chunk = chunk_trials(n_trials, probas.size, levels.size)
     covered = np.zeros(levels.size, dtype=np.int64)
     hits, deltas = [], []
-    for start in range(0, n_trials, chunk):
-        size = min(chunk, n_trials - start)
-        if sampler == "numpy":
-            counts = draw_counts(shots, probas, size, "numpy", None)
-        else:  # rows of the Philox stream (seed, trial * R + setting): the chunking does not change a draw
-            counts = torch.empty((size, n_rows, n_out), dtype=torch.int64, device=device)
-            engine.device_multinomial(shots, probas, size * n_rows, seed, first_row=start * n_rows, out=counts)
+    for _, counts in trial_chunks(engine, shots, probas, n_trials, chunk, sampler, seed):
         res = engine.polytope_coverage(counts, shots, levels, truth=truth, clip_b=clip_b, covered=covered,
                                        return_deltas=return_table, return_hits=return_table)
         if return_table:
@@ -74,17 +64,33 @@ def _run(probas, shots, truth, clip_b, conf_levels, n_trials, sampler, seed, ret
     return fractions
 
 
-def qst_setup(state, n_measurements, povm="proj-set"):
-    """(probas (S, K), shots (S,), truth (S K,)) of test_qst: the outcome distributions that feed the sampler, the shots
-    per setting, and t = A x_true + W[:, 0] (verification.py:17-25).  `povm`: the reference uses the default,
-    'proj-set'; an (S, K, 4^n) array is taken as it is."""
-    dim = 2**state.n_qubits
-    povm_matrix, shots = StateTomograph(state)._experiment_arguments(n_measurements, povm)
+def qst_tables(state, n_measurements, povm="proj-set"):
+    """What both state studies are built from: (probas (S, K), shots (S,), W (S K, 4^n), A (S K, 4^n - 1)) -- the outcome
+    distributions that feed the sampler, the shots per setting, the shot-weighted POVM rows and the polytope's matrix
+    A = W[:, 1:] * d (verification.py:17-23)."""
+    povm_matrix, shots, probas = StateTomograph(state)._experiment_tables(n_measurements, povm)
     shots = np.asarray(shots, dtype=np.float64)
     weighted = _weighted_povm(povm_matrix, shots)
-    bloch = np.asarray(state.bloch, dtype=np.float64)
-    truth = (np.ascontiguousarray(weighted[:, 1:]) * dim) @ bloch[1:] + weighted[:, 0]
-    return born_probabilities(povm_matrix, state.bloch), shots, truth
+    return probas, shots, weighted, np.ascontiguousarray(weighted[:, 1:]) * 2**state.n_qubits
+
+
+def qpt_tables(channel, n_measurements, input_states="sic", povm="proj-set"):
+    """The process counterpart: (probas (D S, K), shots (D S,), W (S K, 4^n), states_matrix (D, 4^n)) from the
+    throw-away tomograph's `_experiment_tables` -- row input * S + setting -- and the Bloch vectors of the transposed
+    input states (verification.py:43-55)."""
+    tmg = ProcessTomograph(channel, input_states=input_states)
+    povm_matrix, shots, probas = tmg._experiment_tables(n_measurements, povm)
+    shots = np.asarray(shots, dtype=np.float64)
+    states_matrix = np.asarray([rho.T.bloch for rho in tmg.input_basis.elements], dtype=np.float64)
+    return probas, np.tile(shots, len(states_matrix)), _weighted_povm(povm_matrix, shots), states_matrix
+
+
+def qst_setup(state, n_measurements, povm="proj-set"):
+    """(probas (S, K), shots (S,), truth (S K,)) of test_qst: `qst_tables` and t = A x_true + W[:, 0]
+    (verification.py:24-25).  `povm`: the reference uses the default, 'proj-set'; an (S, K, 4^n) array is taken as it
+    is."""
+    probas, shots, weighted, A = qst_tables(state, n_measurements, povm)
+    return probas, shots, A @ np.asarray(state.bloch, dtype=np.float64)[1:] + weighted[:, 0]
 
 
 def qpt_setup(channel, n_measurements, input_states="sic", povm="proj-set"):
@@ -92,16 +98,10 @@ def qpt_setup(channel, n_measurements, input_states="sic", povm="proj-set"):
     (input Bloch vectors) (x) (weighted POVM rows), so the true outcome probabilities are a small matrix product; the
     dense (D S K) x (16^n - 4^n) matrix of the reference is never formed."""
     dim = 4**channel.n_qubits
-    tmg = ProcessTomograph(channel, input_states=input_states)
-    outputs = [StateTomograph(channel.transform(state)) for state in tmg.input_basis.elements]
-    povm_matrix, shots = outputs[0]._experiment_arguments(n_measurements, povm)
-    shots = np.asarray(shots, dtype=np.float64)
-    weighted = _weighted_povm(povm_matrix, shots)
-    states_matrix = np.asarray([rho.T.bloch for rho in tmg.input_basis.elements], dtype=np.float64)
+    probas, shots, weighted, states_matrix = qpt_tables(channel, n_measurements, input_states, povm)
     choi = np.asarray(channel.choi.bloch, dtype=np.float64).reshape(dim, dim)[:, 1:]  # indices i with i % dim != 0
     truth = (states_matrix @ choi @ weighted[:, 1:].T) * dim + weighted[None, :, 0]
-    probas = np.concatenate([born_probabilities(povm_matrix, out.state.bloch) for out in outputs])
-    return probas, np.tile(shots, len(outputs)), np.ravel(truth)
+    return probas, shots, np.ravel(truth)
 
 
 def test_qst(state, conf_levels, n_measurements=1000, n_trials=1000, *, sampler="numpy", seed=None, return_table=False):

@@ -73,6 +73,12 @@ class StateTomograph:
             raise ValueError("Wrong length for argument `n_measurements`")
         return povm_matrix, n_measurements
 
+    def _experiment_tables(self, n_measurements, povm):
+        """What the sampler draws for one experiment: (povm_matrix, shots (S,), probas (S, K)) -- the counterpart of
+        `ProcessTomograph._experiment_tables`.  The tomograph is not changed."""
+        povm_matrix, shots = self._experiment_arguments(n_measurements, povm)
+        return povm_matrix, shots, born_probabilities(povm_matrix, self.state.bloch)
+
     def experiment(self, n_measurements, povm="proj-set", warm_start=False, sampler="numpy", seed=None):
         """Draw measurement outcomes.
 
