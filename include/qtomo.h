@@ -599,6 +599,43 @@ int qt_mhmc_process_metric_hits(qt_handle_t* h, int metric, const int64_t* count
 /* projections alone (process.py:231-278): mode 0 = CPTP (Dykstra), 1 = TP, 2 = CP */
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol,
                           double* choi_out, int32_t* iters, int flags);
+/* The 'states' process estimator (process.py:316-327) on B trials of reconstructed output states,
+ * states[B][D][d][d][2] in the order of qt_process_setup's input states, n <= 3:
+ *     C_b[(i,k)][(j,l)] = sum_s weights[(i,j)][s] rho_b,s[k][l]        (row index i d + k, column index j d + l)
+ * with weights[D][D][2], row (i,j) = i d + j and column s, built by the caller:
+ * weights[(i,j)][s] = sum_e unit_e[i][j] c_e,s for the coordinates c_e of the single-entry matrices in the input basis
+ * and unit_e = sum_s c_e,s rho_in,s -- the reference's sum_e unit_e (x) sum_s c_e,s rho_s.  weights is in the pointer
+ * space of the other arguments.  Every entry of C_b is one chain of fused multiply-adds over s = 0 .. D - 1.
+ * cptp = 0: assembly only; projected[B] and iters[B] (both NULLABLE) are zero.
+ * cptp != 0: the conditional projection of the reference.  A trial that passes the test of qt_choi_is_cptp_batch
+ * (atol = 1e-5) keeps its assembled matrix bit for bit, projected[b] = 0, iters[b] = 0.  A trial that fails receives
+ * exactly what qt_cptp_project_batch(mode 0, n_iter 1000, tol 1e-12) returns for its assembled matrix, bit for bit,
+ * with its iteration count, projected[b] = 1.  The failing trials are compacted on the device and projected in one
+ * launch; their NUMBER is read back to size it, so with cptp the call waits for the handle's stream once per 128 MB of
+ * Choi matrices (524 288 trials at n = 1, 32 768 at n = 2, 2048 at n = 3), also with QT_DEVICE_PTR.
+ * A trial's bits depend on its own inputs only, not on B or its place in the batch.
+ * n = 4, 5: QT_ERR_UNSUPPORTED before any launch; a missing POVM or qt_process_setup fails as qt_lifp_batch does;
+ * B = 0 returns 0 without a launch. */
+int qt_states_choi_batch(qt_handle_t* h, const double* states, int B, const double* weights, int cptp, double* choi,
+                         int32_t* projected, int32_t* iters, int flags);
+/* The same call plus dist[b] = hs_dst(C_b, centres[b % G]) for a table centres[G][D][D][2], formed by qt_hs_dist_dim's
+ * kernel on the final matrices: the bootstrap coverage study of the 'states' estimator, with the conventions of
+ * qt_lifp_dist_group_batch (resample-major batch, G >= 1 else QT_ERR_ARG).  choi is NULLABLE: without it no matrix leaves
+ * the device, and the matrices of one 128 MB slice at a time live in a handle workspace. */
+int qt_states_choi_dist_group_batch(qt_handle_t* h, const double* states, int B, const double* weights, int cptp,
+                                    const double* centres, int G, double* choi, double* dist, int32_t* projected,
+                                    int32_t* iters, int flags);
+/* The device form of Channel.is_cptp(atol) (channel.py:144-157) on arbitrary matrices choi[B][D][D][2], n <= 3 (no POVM
+ * needed): ok[b] = 1 when
+ *   - every entry of choi[b] is finite,
+ *   - R[i][j] = sum_k C[(i,k)][(j,k)] has |R - 1| <= atol + 1e-5 |1| element by element on the complex modulus
+ *     (np.allclose's rule: rtol at its default 1e-5, so the diagonal gets 1e-5 more than the off-diagonal), and
+ *   - the smallest eigenvalue of the Hermitian part (C + C^H) / 2 is >= -atol, decided by an L D L^H factorisation of
+ *     Herm(C) + atol 1 with a positive-pivot test;
+ * else ok[b] = 0.  CONTRACT: the flag equals the host's is_cptp whenever the smallest eigenvalue and the largest
+ * trace-preservation residual are both farther than 1e-9 from their thresholds; inside that band either answer is
+ * allowed.  atol >= 0 and finite, else QT_ERR_ARG; n = 4, 5: QT_ERR_UNSUPPORTED; B = 0 returns 0 without a launch. */
+int qt_choi_is_cptp_batch(qt_handle_t* h, const double* choi, int B, double atol, int32_t* ok, int flags);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,9 @@ SIGNATURES = {
     "qt_mhmc_process_metric_hits": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _c_int,
                                              _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
     "qt_cptp_project_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_int]),
+    "qt_states_choi_batch": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_int]),
+    "qt_states_choi_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
+    "qt_choi_is_cptp_batch": (_c_int, [_vp, _vp, _c_int, _c_dbl, _vp, _c_int]),
 }
 
 _lib = None

@@ -32,6 +32,7 @@
 #include "qt_product_tables.h"
 #include "qt_sampler.h"
 #include "qt_small.h"
+#include "qt_states_choi.h"
 
 // the kernels' names (qt_linesearch.h) for the trial statuses of the public header
 #define QT_SAME_STATUS(name) static_assert((int)qt::TRIAL_##name == (int)QT_TRIAL_##name, "qt::TrialStatus is QT_TRIAL_*")
@@ -231,6 +232,10 @@ struct qt_handle {
   // Jacobi stopping rule off^2 <= jtol2 * ||A||_F^2.  Measured on the C2 batch: the last sweep takes off^2
   // from > 1e-9 to < 1e-28 in one go, so no looser threshold saves a sweep without costing accuracy.
   double jtol2 = 1e-28;
+  // qt_states_choi_batch, one slice: the test's flags, the failing trials' places (fail[nb + 1], its exclusive sum pos[nb + 1],
+  // the scan's temporary storage), their matrices before and after the projection with its iteration counts, and the
+  // slice's Choi matrices when the caller of qt_states_choi_dist_group_batch wants only the distances
+  DevBuf sc_ok, sc_fail, sc_pos, sc_tmp, sc_in, sc_out, sc_iters, sc_choi;
 };
 
 namespace {
@@ -1403,7 +1408,8 @@ void qt_destroy(qt_handle_t* h) {
   (void)hipStreamSynchronize(h->stream);
   h->povm.release();
   for (DevBuf* b : {&h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
-                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp})
+                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp,
+                    &h->sc_ok, &h->sc_fail, &h->sc_pos, &h->sc_tmp, &h->sc_in, &h->sc_out, &h->sc_iters, &h->sc_choi})
     b->release();
   for (DevBuf& b : h->stage) b.release();
   h->proc.release();
@@ -2912,3 +2918,153 @@ extern "C" int qt_debug_set_prof(void* device_ptr) {
   return hipMemcpyToSymbol(HIP_SYMBOL(qt::g_qt_prof), &p, sizeof(p)) == hipSuccess ? 0 : -3;
 }
 #endif
+
+// (Behind everything else, so that the device code of the kernels above keeps its place in the code object.)
+namespace {
+
+// ---- the 'states' process estimator behind qt_states_choi_batch and its siblings (qt_states_choi.h) ------------------
+// f(std::integral_constant<int, d>()) for the handle's d = 2, 4, 8 (the callers have refused n > 3)
+template <class F>
+int by_small_d(const qt_handle_t* h, F f) {
+  switch (h->d) {
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, 8>());
+  }
+}
+
+// the test of B matrices into dok[B] and, when wanted, the failing flags dfail[B + 1] (k_choi_is_cptp)
+int launch_is_cptp(qt_handle_t* h, const double* dchoi, int B, double atol, int32_t* dok, int32_t* dfail) {
+  return by_small_d(h, [&](auto dc) {
+    using W = qt::StatesChoi<decltype(dc)::value>;
+    return launch(h, qt::k_choi_is_cptp<decltype(dc)::value>, dim3((B + W::TPB - 1) / W::TPB), dim3(W::NT), W::kTestLds, dchoi, B,
+                  atol, dok, dfail);
+  });
+}
+
+// The conditional projection of B assembled matrices on the device, in place: the test (is_cptp's atol = 1e-5), the
+// failing trials compacted in batch order (an exclusive sum of their flags), the projection launcher of
+// qt_cptp_project_batch(mode 0, n_iter 1000, tol 1e-12) on the compacted copy, and its results put back.  The number of
+// failing trials comes back to the host -- ONE read-back, for which the stream is waited for -- since it sizes the
+// projection's launch and workspaces.  projected[B] / iters[B] (either may be null) are written for every trial.
+int project_failing(qt_handle_t* h, double* dchoi, int B, int32_t* dproj, int32_t* dit) {
+  const int ne2 = h->D * h->D * 2;
+  HIPCHK(h->sc_ok.ensure((size_t)B * sizeof(int32_t)));
+  HIPCHK(h->sc_fail.ensure(((size_t)B + 1) * sizeof(int32_t)));
+  HIPCHK(h->sc_pos.ensure(((size_t)B + 1) * sizeof(int32_t)));
+  int32_t *ok = h->sc_ok.as<int32_t>(), *failing = h->sc_fail.as<int32_t>(), *pos = h->sc_pos.as<int32_t>();
+  if (int r = launch_is_cptp(h, dchoi, B, 1e-5, ok, failing)) return r;
+  size_t tmp_bytes = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, failing, pos, B + 1, h->stream));
+  HIPCHK(h->sc_tmp.ensure(tmp_bytes));
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(h->sc_tmp.p, tmp_bytes, failing, pos, B + 1, h->stream));
+  int32_t n_fail = 0;
+  char* m = mail_alloc(h, sizeof(int32_t));
+  HIPCHK(hipMemcpyAsync(m ? (void*)m : (void*)&n_fail, pos + B, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (int r = wait_stream(h)) return r;
+  if (m) memcpy(&n_fail, m, sizeof(int32_t));
+  if (n_fail < 0 || n_fail > B) return fail(QT_ERR_HIP, "states_choi: %d of %d trials reported as failing", n_fail, B);
+  if (n_fail > 0) {
+    HIPCHK(h->sc_in.ensure((size_t)n_fail * ne2 * sizeof(double)));
+    HIPCHK(h->sc_out.ensure((size_t)n_fail * ne2 * sizeof(double)));
+    HIPCHK(h->sc_iters.ensure((size_t)n_fail * sizeof(int32_t)));
+    const int r = by_small_d(h, [&](auto dc) {
+      return launch(h, qt::k_choi_gather<decltype(dc)::value>, dim3(B), dim3(256), 0, (const double*)dchoi, B, (const int32_t*)ok,
+                    (const int32_t*)pos, h->sc_in.as<double>());
+    });
+    if (r) return r;
+    if (int r = project(h, h->sc_in.as<double>(), n_fail, 0, 1000, 1e-12, h->sc_out.as<double>(), h->sc_iters.as<int32_t>(), nullptr))
+      return r;
+  }
+  if (n_fail > 0 || dproj || dit)
+    return by_small_d(h, [&](auto dc) {
+      return launch(h, qt::k_choi_scatter<decltype(dc)::value>, dim3(B), dim3(256), 0, h->sc_out.as<const double>(),
+                    h->sc_iters.as<const int32_t>(), B, (const int32_t*)ok, (const int32_t*)pos, dchoi, dproj, dit);
+    });
+  return 0;
+}
+
+// qt_states_choi_batch (`with_dist` false) and qt_states_choi_dist_group_batch.  The batch runs in slices of 128 MB of Choi
+// matrices (524 288 trials at n = 1, 32 768 at n = 2, 2048 at n = 3), so that every workspace that follows the batch stays
+// bounded; with cptp there is one read-back (project_failing) per slice.  The same bits whatever the slice: every kernel
+// here treats a trial by itself.
+int states_choi_impl(qt_handle_t* h, bool with_dist, const double* states, int B, const double* weights, int cptp,
+                     const double* centres, int G, double* choi, double* dist, int32_t* projected, int32_t* iters, int flags,
+                     const char* fn) {
+  QT_ENTER(h);
+  Call c(h, flags, fn);
+  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "%s: process tomography supports n_qubits 1..3 in this release", fn);
+  if (int r = need_povm(h)) return r;
+  if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+  if (B < 0 || G < 1 || (B > 0 && (!states || !weights || (with_dist ? !centres || !dist : !choi))))
+    return fail(QT_ERR_ARG, "bad %s arguments", fn + 3);
+  if (B == 0) return 0;
+  const int D = h->D;
+  const size_t ne2 = (size_t)D * D * 2;
+  const double *ds, *dw, *dcen;
+  double *dchoi, *ddist;
+  int32_t *dproj, *dit;
+  if (int r = c.in(states, (size_t)B * ne2, &ds)) return r;
+  if (int r = c.in(weights, ne2, &dw)) return r;
+  if (int r = c.in(centres, with_dist ? (size_t)G * ne2 : 0, &dcen)) return r;
+  if (int r = c.out(choi, (size_t)B * ne2, &dchoi)) return r;
+  if (int r = c.out(with_dist ? dist : nullptr, (size_t)B, &ddist)) return r;
+  if (int r = c.out(projected, (size_t)B, &dproj)) return r;
+  if (int r = c.out(iters, (size_t)B, &dit)) return r;
+  const int slice = (int)(((size_t)128 << 20) / (ne2 * sizeof(double)));
+  for (int b0 = 0; b0 < B; b0 += slice) {
+    const int nb = B - b0 < slice ? B - b0 : slice;
+    double* m = dchoi ? dchoi + (size_t)b0 * ne2 : nullptr;
+    if (!m) {
+      HIPCHK(h->sc_choi.ensure((size_t)nb * ne2 * sizeof(double)));
+      m = h->sc_choi.as<double>();
+    }
+    const int r = by_small_d(h, [&](auto dc) {
+      using W = qt::StatesChoi<decltype(dc)::value>;
+      return launch(h, qt::k_states_choi<decltype(dc)::value>, dim3((nb + W::TPB - 1) / W::TPB), dim3(W::NT), W::kAssemblyLds,
+                    ds + (size_t)b0 * ne2, nb, dw, m);
+    });
+    if (r) return r;
+    if (cptp) {
+      if (int r2 = project_failing(h, m, nb, dproj ? dproj + b0 : nullptr, dit ? dit + b0 : nullptr)) return r2;
+    }
+    if (ddist)
+      if (int r2 = launch(h, qt::k_hs_dist, dim3(nb), dim3(64), 0, D, (const double*)m, dcen, G, b0 % G, nb, ddist + b0)) return r2;
+  }
+  if (!cptp) {
+    if (dproj) HIPCHK(hipMemsetAsync(dproj, 0, (size_t)B * sizeof(int32_t), h->stream));
+    if (dit) HIPCHK(hipMemsetAsync(dit, 0, (size_t)B * sizeof(int32_t), h->stream));
+  }
+  return c.done();
+}
+
+}  // namespace
+
+extern "C" {
+
+int qt_states_choi_batch(qt_handle_t* h, const double* states, int B, const double* weights, int cptp, double* choi,
+                         int32_t* projected, int32_t* iters, int flags) {
+  return states_choi_impl(h, false, states, B, weights, cptp, nullptr, 1, choi, nullptr, projected, iters, flags, __func__);
+}
+
+int qt_states_choi_dist_group_batch(qt_handle_t* h, const double* states, int B, const double* weights, int cptp,
+                                    const double* centres, int G, double* choi, double* dist, int32_t* projected, int32_t* iters,
+                                    int flags) {
+  return states_choi_impl(h, true, states, B, weights, cptp, centres, G, choi, dist, projected, iters, flags, __func__);
+}
+
+int qt_choi_is_cptp_batch(qt_handle_t* h, const double* choi, int B, double atol, int32_t* ok, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (h->nq > 3) return fail(QT_ERR_UNSUPPORTED, "qt_choi_is_cptp_batch: process tomography supports n_qubits 1..3 in this release");
+  if (B < 0 || !(atol >= 0.0) || !std::isfinite(atol) || (B > 0 && (!choi || !ok))) return fail(QT_ERR_ARG, "bad choi_is_cptp_batch arguments");
+  if (B == 0) return 0;
+  const double* dchoi;
+  int32_t* dok;
+  if (int r = c.in(choi, (size_t)B * h->D * h->D * 2, &dchoi)) return r;
+  if (int r = c.out(ok, (size_t)B, &dok)) return r;
+  if (int r = launch_is_cptp(h, dchoi, B, atol, dok, nullptr)) return r;
+  return c.done();
+}
+
+}  // extern "C"

@@ -506,6 +506,63 @@ class Engine:
             out, iters = out[0], iters[0]
         return (out, iters) if return_iters else out
 
+    def states_choi(self, states, weights, cptp=True, return_info=False):
+        """The 'states' estimator on reconstructed output states (qt_states_choi_batch): states (B, D, d, d) or (D, d, d)
+        complex in the order of `process_setup`'s input states, weights (D, D) complex (ProcessTomograph._states_weights)
+        -> Choi (B, D, D) / (D, D).  cptp: a trial that fails `is_cptp` is replaced by its `cptp_project`, the others stay
+        as assembled; return_info appends dict(projected, iters), per trial."""
+        s = _c128(states)
+        single = s.ndim == 3
+        s = s.reshape(-1, self.D, self.d, self.d)
+        w = _c128(weights)
+        assert w.shape == (self.D, self.D)
+        b = s.shape[0]
+        choi = np.empty((b, self.D, self.D), dtype=np.complex128)
+        projected = np.zeros(b, dtype=np.int32)
+        iters = np.zeros(b, dtype=np.int32)
+        self._chk(self.lib.qt_states_choi_batch(self._h, _ptr(s), b, _ptr(w), int(bool(cptp)), _ptr(choi), _ptr(projected),
+                                                _ptr(iters), _capi.QT_HOST_PTR))
+        if single:
+            choi, projected, iters = choi[0], projected[0], iters[0]
+        return (choi, dict(projected=projected, iters=iters)) if return_info else choi
+
+    def states_choi_dev(self, states, weights, choi, cptp=True, projected=None, iters=None):
+        """device-pointer form: states complex128 (B, D, d, d), weights complex128 (D, D), choi complex128 (B, D, D),
+        projected / iters int32 (B,) optional: torch CUDA tensors.  With cptp the call waits for the stream once per slice
+        (include/qtomo.h: the number of failing trials sizes the projection)."""
+        self._dev_call()
+        self._chk(self.lib.qt_states_choi_batch(self._h, _ptr(states), states.shape[0], _ptr(weights), int(bool(cptp)),
+                                                _ptr(choi), _ptr(projected), _ptr(iters), _capi.QT_DEVICE_PTR))
+
+    def states_choi_dist_dev(self, states, weights, centres, dist, cptp=True, choi=None, projected=None, iters=None):
+        """`states_choi_dev` plus dist[b] = hs_dst(Choi_b, centres[b % G]) for a centre table (G, D, D) -- a single centre
+        (D, D) is G = 1 -- into dist float64 (B,) (qt_states_choi_dist_group_batch); choi optional."""
+        self._dev_call()
+        g = centres.shape[0] if centres.dim() == 3 else 1
+        self._chk(self.lib.qt_states_choi_dist_group_batch(self._h, _ptr(states), states.shape[0], _ptr(weights),
+                                                           int(bool(cptp)), _ptr(centres), g, _ptr(choi), _ptr(dist),
+                                                           _ptr(projected), _ptr(iters), _capi.QT_DEVICE_PTR))
+
+    def is_cptp(self, choi, atol=1e-5):
+        """Channel.is_cptp(atol) of Choi matrices (B, D, D) / (D, D) on the device (qt_choi_is_cptp_batch) -> bool array /
+        bool.  Equal to the host's answer unless the smallest eigenvalue or the largest trace-preservation residual lies
+        within 1e-9 of its threshold.  A torch CUDA tensor in gives an int32 CUDA tensor (1 / 0), in stream order."""
+        if _is_dev(choi):
+            import torch
+
+            self._dev_call()
+            assert choi.is_contiguous() and tuple(choi.shape[1:]) == (self.D, self.D)
+            ok = torch.empty(choi.shape[0], dtype=torch.int32, device=choi.device)
+            self._chk(self.lib.qt_choi_is_cptp_batch(self._h, _ptr(choi), choi.shape[0], float(atol), _ptr(ok),
+                                                     _capi.QT_DEVICE_PTR))
+            return ok
+        c = _c128(choi)
+        single = c.ndim == 2
+        c = c.reshape(-1, self.D, self.D)
+        ok = np.zeros(c.shape[0], dtype=np.int32)
+        self._chk(self.lib.qt_choi_is_cptp_batch(self._h, _ptr(c), c.shape[0], float(atol), _ptr(ok), _capi.QT_HOST_PTR))
+        return bool(ok[0]) if single else ok.astype(bool)
+
     # ---- a4 / a3 ----------------------------------------------------------------------------
     def born_probs(self, bloch, out=None):
         if _is_dev(bloch):

@@ -25,7 +25,9 @@ of them in one launch that draws its own random numbers and returns, per trial, 
 per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.  Both take dst='hs' | 'trace' | 'if': for the
 other two distances the chain kernels run the Jacobi-sweep metrics on the state they hold (`qt_mhmc_state_metric_hits`,
 `qt_mhmc_process_metric_hits`).  `get_CL_list_channel_boot_dst` is the process bootstrap study in any of the three: it
-measures a chunk's Choi matrices the same way.
+measures a chunk's Choi matrices the same way.  `get_CL_list_channel_boot_states` is that study with the resamples
+reconstructed from their output states (method_boot='states'): a chunk's states by `lin_dev` / `mle_dev`, their Choi
+matrices, the conditional CPTP projection and the distances by `qt_states_choi_dist_group_batch`.
 """
 import numpy as np
 
@@ -368,8 +370,9 @@ def get_CL_list_channel(channel, n_iter=1000, interval="gamma", n_points=1000, n
                         return_details=False):
     """The same study for a channel and its Choi matrix (reference metrics.py:150-319; parameters as there), for
     interval='gamma': the process form of `MomentInterval.radii_batch` at np.linspace(0, 1, n_points).  'boot' and
-    'mhmc' raise NotImplementedError; the bootstrap study of a channel is `get_CL_list_channel_boot`, the chain study
-    `get_CL_list_channel_mhmc`.  `sampler`, `seed`, `return_details` as in `get_CL_list_state`."""
+    'mhmc' raise NotImplementedError; the bootstrap study of a channel is `get_CL_list_channel_boot` (method_boot='lifp')
+    or `get_CL_list_channel_boot_states` (method_boot='states'), the chain study `get_CL_list_channel_mhmc`.  `sampler`,
+    `seed`, `return_details` as in `get_CL_list_state`."""
     _check_arguments(interval, dst, n_iter, n_points, sampler, (), method_boot)
     n_iter, n_points = int(n_iter), int(n_points)
     tmg = ProcessTomograph(channel, input_states, "hs")
@@ -446,6 +449,93 @@ def _channel_boot(channel, n_iter, n_points, n_measurements, method, povm, input
                          key, chunk, measure, _PROCESS_ERRORS)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
                    seed=key)
+
+
+# What a chunk of 'states' resamples raises, in order (the codes are those `_states_boot_measure` writes per process).
+_STATES_BOOT_ERRORS = ((1, np.linalg.LinAlgError, "starting point of the MLE is not positive definite"),
+                       (2, ValueError, _PROCESS_ERRORS[0][2]))
+
+
+def get_CL_list_channel_boot_states(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",
+                                    input_states="proj4", cptp=True, states_physical=True, states_init="lin",
+                                    states_est_method="lin", states_est_method_boot="lin", *, sampler="device", seed=None,
+                                    chunk=None, return_details=False, dst="hs"):
+    """The interval='boot', method_boot='states' branch of the reference's get_CL_list_channel (metrics.py:299-309;
+    parameters as there): `n_iter` process tomographies, each bootstrapped with `n_points` resamples around ITS OWN Choi
+    estimate, every resample reconstructed from its output states.  Returns the sorted levels.
+    (`get_CL_list_channel(interval='boot')` keeps its refusal; this is the study's name.)
+
+    Trials, `delta`, the Philox keying of the resamples, sharding over the ranks, chunking by whole resamples, `sampler`,
+    `seed`, `chunk`, `return_details` and `dst` = 'hs' | 'trace' | 'if' are exactly those of `get_CL_list_channel_boot_dst`.
+    A resample is reconstructed as `point_estimate_batch(counts, method='states', cptp=cptp,
+    states_est_method=states_est_method_boot, states_physical=states_physical, states_init=states_init)` reconstructs it,
+    that method's other defaults included (an 'mle' of at most 1000 iterations with tol 1e-10).  states_est_method_boot
+    outside ('lin', 'mle') raises NotImplementedError before any device work.
+
+    A chunk never leaves the device: `device_multinomial`; `Engine.lin_dev` / `mle_dev` on its chunk * n_iter * D count
+    tensors into one workspace of the first chunk's size; `Engine.states_choi_dist_dev` against the table of the n_iter
+    estimates (process b against centre b % n_iter) for 'hs', or `states_choi_dev` and `distance_dev` for 'trace' / 'if';
+    `group_hits`.  (With cptp the number of resamples that fail the CPTP test comes back to the host, once per slice of
+    `qt_states_choi_batch`: it sizes the projection's launch.)  An output-state MLE that cannot start raises
+    np.linalg.LinAlgError, a resample without a finite Choi matrix ValueError, on every rank."""
+    if states_est_method_boot not in ("lin", "mle"):
+        raise NotImplementedError("get_CL_list_channel_boot_states supports states_est_method_boot in ('lin', 'mle'), not "
+                                  f"{states_est_method_boot!r}")
+    _check_arguments("boot", "hs", n_iter, n_points, sampler, ("lifp",), "lifp")
+    metric = _distance_name(dst)
+    metric = None if metric == "hs" else metric
+    n_iter, n_points = int(n_iter), int(n_points)
+    tmg = ProcessTomograph(channel, input_states, "hs")
+    counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
+    choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
+    eng = tmg._engine()
+    delta = eng.distance(choi, channel.choi.matrix, metric)
+    key = (base + 1) & (2**64 - 1)
+    pvals = eng.process_born_probs(choi)
+    measure = _states_boot_measure(eng, tmg._states_weights(), metric, states_est_method_boot, states_physical, states_init,
+                                   cptp)
+    hits = _chunked_hits(eng, choi, (eng.D, eng.S, eng.K), pvals, tmg.tomographs[0].n_measurements, delta, n_points,
+                         key, chunk, measure, _STATES_BOOT_ERRORS)
+    return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
+                   seed=key)
+
+
+def _states_boot_measure(eng, weights, metric, method_boot, physical, init, cptp):
+    """`measure(counts, centres, dist, status)` of `_chunked_hits` for the 'states' resamples: the chunk's b * D output
+    states by `lin_dev` / `mle_dev` (the MLE with point_estimate_batch's defaults n_iter = 1000, tol = 1e-10) into one
+    workspace of the first chunk's size, then the Choi matrices and their distances.  status[p] of process p: 1 where an
+    output-state MLE could not start, else 2 where an output state is not finite, else 0."""
+    work = {}
+
+    def measure(counts, centres, dist, status):
+        import torch
+
+        b, dd = counts.shape[0], eng.D
+        if not work:
+            dev = counts.device
+            work["states"] = torch.empty((b * dd, eng.d, eng.d), dtype=torch.complex128, device=dev)
+            work["status"] = torch.zeros(b * dd, dtype=torch.int32, device=dev)
+            work["weights"] = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.complex128)).to(dev)
+            if metric is not None:
+                work["choi"] = torch.empty((b, dd, dd), dtype=torch.complex128, device=dev)
+        states, state_status = work["states"][:b * dd], work["status"][:b * dd]
+        flat = counts.reshape(b * dd, eng.S, eng.K)
+        if method_boot == "lin":
+            eng.lin_dev(flat, states, physical=physical, status=state_status)
+        else:
+            eng.mle_dev(flat, states, init=init, max_iter=1000, tol=1e-10, status=state_status)
+        per_process = states.view(b, dd, eng.d, eng.d)
+        if metric is None:
+            eng.states_choi_dist_dev(per_process, work["weights"], centres, dist, cptp=cptp)
+        else:
+            choi = work["choi"][:b]
+            eng.states_choi_dev(per_process, work["weights"], choi, cptp=cptp)
+            eng.distance_dev(choi, centres, dist, metric)
+        no_start = (state_status.view(b, dd) == 1).any(dim=1)
+        finite = torch.isfinite(torch.view_as_real(states).view(b, -1)).all(dim=1)
+        status.copy_(torch.where(no_start, 1, torch.where(finite, 0, 2)).to(torch.int32))
+
+    return measure
 
 
 def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",

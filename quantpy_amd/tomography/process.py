@@ -4,7 +4,8 @@ A process is probed by preparing each state of an input basis, applying the chan
 state tomography on the output.  Counts are simulated on the host (same RNG order as the
 reference: input state by input state, POVM setting by setting); the estimator -- design
 matrix, its left inverse, Choi linear inversion and the Dykstra CPTP projection -- runs on the
-GPU (qt_process_setup / qt_lifp_batch / qt_cptp_project_batch).
+GPU (qt_process_setup / qt_lifp_batch / qt_cptp_project_batch), and so does the 'states' estimator behind the
+reconstruction of the output states: Choi assembly, CPTP test and conditional projection (qt_states_choi_batch).
 """
 import numpy as np
 
@@ -134,7 +135,8 @@ class ProcessTomograph:
         """Choi matrix from the reconstructed output states (reference process.py:316-327): all 4^n
         output tomographs are reconstructed in ONE batched launch, then
         C = sum_ij E_ij (x) sum_s c_ij,s rho_out,s with c_ij the coordinates of E_ij in the input basis;
-        projected onto CPTP only if it is not CPTP already."""
+        projected onto CPTP only if it is not CPTP already (`Engine.states_choi` with the weights of `_states_weights`:
+        assembly, the device form of `Channel.is_cptp` and the projection in one call)."""
         first = self.tomographs[0]
         eng = get_engine(self.channel.n_qubits)
         eng.set_povm(first.povm_matrix, first.n_measurements)
@@ -148,23 +150,28 @@ class ProcessTomograph:
             raise ValueError("Invalid value for argument `method`")
         for tmg, rho in zip(self.tomographs, outs):
             tmg.reconstructed_state = Qobj(rho)
-        ins = np.stack([np.asarray(s.matrix, dtype=np.complex128) for s in self.input_basis.elements])
-        coeff = self._decomposed_single_entries  # (d^2, D): row ij = coordinates of E_ij
-        units = np.einsum("es,sab->eab", coeff, ins)           # the single-entry matrices, recomposed
-        images = np.einsum("es,sab->eab", coeff, np.asarray(outs))  # their images under the channel
-        choi = np.zeros((ins.shape[1] ** 2,) * 2, dtype=np.complex128)
-        for unit, image in zip(units, images):
-            choi += np.kron(unit, image)
+        choi = self._engine().states_choi(outs, self._states_weights(), cptp=cptp)
         self.reconstructed_channel = Channel(choi)
-        if cptp and not self.reconstructed_channel.is_cptp(verbose=False):
-            self.reconstructed_channel = self.cptp_projection(self.reconstructed_channel)
         return self.reconstructed_channel
+
+    def _states_weights(self):
+        """W (D, D) complex of `Engine.states_choi`, W[(i,j), s] = sum_e unit_e[i,j] c_e,s: c_e = the coordinates of the
+        single-entry matrix E_e in the input basis (`Basis.decompose`) and unit_e = sum_s c_e,s rho_in,s that matrix as the
+        reference recomposes it, so that sum_e unit_e (x) sum_s c_e,s rho_out,s is
+        C[(i,k), (j,l)] = sum_s W[(i,j), s] rho_out,s[k,l].  The one place that builds it."""
+        ins = np.stack([np.asarray(s.matrix, dtype=np.complex128) for s in self.input_basis.elements])
+        coeff = self._decomposed_single_entries  # (d^2, D): row e = coordinates of E_e
+        units = np.einsum("es,sab->eab", coeff, ins)  # the single-entry matrices, recomposed
+        dim = ins.shape[1]
+        return np.ascontiguousarray(np.einsum("eij,es->ijs", units, coeff).reshape(dim * dim, dim * dim))
 
     def point_estimate_batch(self, counts, method="lifp", cptp=True, n_iter=1000, tol=1e-10, states_est_method="lin",
                              states_physical=True, states_init="lin", pgdb_stop="reference"):
         """Extension: counts (B, D, S, K) measured with this tomograph's POVM, shots and input states -> Choi
         matrices (B, D, D), every resample in the same launch(es).  Same estimators and defaults as
-        `point_estimate`; this is what BootstrapProcessInterval runs."""
+        `point_estimate`; this is what BootstrapProcessInterval runs.  method='states': all B * 4^n output states in one
+        launch, then `Engine.states_choi` -- the B Choi matrices, their CPTP test and the projection of those that fail
+        it, on the device."""
         counts = np.asarray(counts)
         if method == "lifp":
             return self._engine().lifp(counts, cptp=cptp)
@@ -186,17 +193,7 @@ class ProcessTomograph:
         else:
             raise ValueError("Invalid value for argument `method`")
         outs = outs.reshape((b, dd) + outs.shape[1:])
-        ins = np.stack([np.asarray(s.matrix, dtype=np.complex128) for s in self.input_basis.elements])
-        coeff = self._decomposed_single_entries
-        units = np.einsum("es,sab->eab", coeff, ins)
-        images = np.einsum("es,bsac->beac", coeff, outs)
-        dim = ins.shape[1]
-        choi = np.einsum("eij,bekl->bikjl", units, images).reshape(b, dim * dim, dim * dim)  # sum_e unit_e (x) image_e
-        if cptp:
-            bad = [i for i in range(b) if not Channel(choi[i]).is_cptp(verbose=False)]
-            if bad:
-                choi[bad] = eng.cptp_project(choi[bad], mode="cptp")
-        return choi
+        return self._engine().states_choi(outs, self._states_weights(), cptp=cptp)
 
     @property
     def _lifp_oper(self):
