@@ -93,14 +93,18 @@ int qt_set_stream(qt_handle_t* h, void* hip_stream);
  * linear-inversion matrix and lifts it on speculation beside the first Cholesky sweep; where the sweep asks for the
  * lift, the twin keeps the clipped matrix and goes on as the trial (evaluation, outputs, BFGS loop) while the first
  * wavefront factorises that matrix for it.  The launch keeps 16 instead of 24 BFGS pairs per trial in LDS, and where
- * its layout does not fit a CU's LDS the kernel without twins runs; 0 launches that kernel.  Both give the same bits. */
+ * its layout does not fit a CU's LDS the kernel without twins runs; 0 launches that kernel.  Both give the same bits.
+ * QT_OPT_MHMC_PROCESS_SLICE (default 0): qt_mhmc_process_large_hits and qt_mhmc_process_large_metric_hits run their
+ * chains in slices of this many, which bounds their workspace (about 0.6 MB per chain of a slice); 0 takes 1024.  The
+ * same bits whatever the slice. */
 enum qt_option {
   QT_OPT_SHOTS_CHECK = 1,
   QT_OPT_MLE_FUSED_MAX_WAVES = 2,
   QT_OPT_PAIRED_STAGES = 3,
   QT_OPT_MLE_SPECIALISE = 4,
   QT_OPT_LIFP_DIST_SLICE = 5,
-  QT_OPT_MLE_HELPER_WAVE = 6
+  QT_OPT_MLE_HELPER_WAVE = 6,
+  QT_OPT_MHMC_PROCESS_SLICE = 7
 };
 int qt_set_option(qt_handle_t* h, int option, double value);
 /* Which one-qubit tables of the current product POVM have that shape: bit 0 = T, bit 1 = pinv(T) as computed on the
@@ -596,6 +600,53 @@ int qt_mhmc_process_metric_hits(qt_handle_t* h, int metric, const int64_t* count
                                 const double* choi_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
                                 int burn_steps, int n_points, int thinning, double step, int64_t* hits, int64_t* accepted,
                                 double* dist, int flags);
+/* qt_mhmc_process_hits for n = 3 handles: every argument, the kept-step rule (post-burn step s is kept when
+ * s % thinning == 0), hits (strict: a NaN threshold or distance never counts), accepted, the NULLABLE dist[C][n_points],
+ * the argument errors (QT_ERR_ARG: burn_steps < 0, n_points < 0, thinning < 1, burn_steps + n_points * thinning >=
+ * 2^32 - 1, a null array with C > 0) and C = 0 (returns 0 without a launch) as there.  counts[C][D][S][K],
+ * centres[C][D][D][2], choi_init[C][D][D][2], thresholds[C], D = 64.
+ * Numbers: chain i runs on counts[i] from choi_init[i] with the numbers of global chain first_chain + i at vector length
+ * 4096, as qt_mhmc_draws_dim(dim = 4096) writes them out (no draws entry of its own is needed: that one reads no POVM and
+ * serves any handle): increment l of global step j belongs to the column-stacked entry l of the Choi vector -- element
+ * (row, col) of the row-major matrix takes l = 64 col + row, how qt_mhmc_process indexes `deltas` -- and Philox block
+ * q = 2048 holds the step's uniform.
+ * Steps: those of qt_mhmc_process at n = 3, a launch family per step -- the proposal x + step * delta (one fused
+ * multiply-add per element) with its draws, the CPTP projection (1000 iterations, tol 1e-12), the model and the NLL, the
+ * accept rule u <= exp(nll(x) - nll(x')) with its draw -- through the same device functions: for the same (seed,
+ * first_chain, counts, choi_init) accepted[i] equals, exactly, what qt_mhmc_process accepts behind the burn-in on the
+ * numbers of qt_mhmc_draws_dim.  The chain's point stays on the device; per chain only hits, accepted and dist leave it.
+ * Distance: hs_dst(Re(X), centres[i]) of a kept state X is formed by the kernel that decides the step, as qt_hs_dist_dim
+ * forms it (Delta = Re(X) - centre, sqrt(|sum_ij Delta_ij Delta_ji|) / sqrt(2), 0 below 1e-15) with its own order of the
+ * 4096-term sum: within 1e-12 absolute of qt_hs_dist_dim on the written-out chain for distances below 1 (for a
+ * Hermitian centre the terms are non-negative, so any order is within 4096 * 2^-52 relative on the sum, half of that on
+ * the root).
+ * A chain's bits depend on its own inputs and its global chain index alone: not on C or its place in the batch.
+ * Workspace is O(min(C, slice)), about 0.6 MB per chain of a slice (the current point, the trial and its projection at
+ * 64 KB each, 320 KB of the projection's own, the NLL's tile partials; the metric entry adds 64 KB for the kept state and,
+ * for the infidelity, 64 KB per chain of the CALL for the centres' roots): the chains run in slices of
+ * QT_OPT_MHMC_PROCESS_SLICE chains (default 1024), one after the other on the handle's stream, with plain launches and
+ * no host synchronisation.  The same bits whatever the slice.
+ * n <= 2 (and n >= 4): QT_ERR_UNSUPPORTED before any launch, the text naming qt_mhmc_process_hits, the entry for n <= 2;
+ * then a missing POVM, then a missing qt_process_setup: QT_ERR_STATE, as there. */
+int qt_mhmc_process_large_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
+                               const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                               int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags);
+/* qt_mhmc_process_metric_hits for n = 3 handles: the chains of qt_mhmc_process_large_hits (accepted[] bit-identical to
+ * that entry's) with the REAL PART of every kept point measured in trace distance or infidelity; `metric` behind the
+ * handle as in qt_metric_dist_*, every other argument as there.  On a kept step the deciding kernel leaves Re(X), with
+ * zero imaginary parts, in a per-chain buffer, qt_metric_dist_mat's kernel for dim = 64 measures it against centres[i]
+ * (the infidelity's roots of the C centres made once per call by that entry's set-up kernel), and a tally kernel
+ * compares with thresholds[i] (strict), counts the hit and writes dist[i][k]: the distances are bit-identical to
+ * qt_metric_dist_mat(dim = 64) on the real parts of the written-out chain.  Conventions of the two metrics, the
+ * degenerate infidelity of trace-2^n Choi matrices (every distance 0) and the NaN rule (a NaN or infinity in centres[i]
+ * gives NaN distances and hits[i] = 0, and touches no other chain) as in qt_mhmc_process_metric_hits.
+ * QT_ERR_ARG: everything qt_mhmc_process_large_hits refuses, and a metric other than QT_METRIC_TRACE /
+ * QT_METRIC_INFIDELITY; n <= 2: QT_ERR_UNSUPPORTED before any launch (the entry there is qt_mhmc_process_metric_hits);
+ * a missing POVM or qt_process_setup, C = 0, determinism, workspace and slices as in qt_mhmc_process_large_hits. */
+int qt_mhmc_process_large_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                                      const double* choi_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                      int burn_steps, int n_points, int thinning, double step, int64_t* hits,
+                                      int64_t* accepted, double* dist, int flags);
 /* projections alone (process.py:231-278): mode 0 = CPTP (Dykstra), 1 = TP, 2 = CP */
 int qt_cptp_project_batch(qt_handle_t* h, const double* choi_in, int B, int mode, int n_iter, double tol,
                           double* choi_out, int32_t* iters, int flags);

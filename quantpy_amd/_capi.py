@@ -16,6 +16,7 @@ QT_OPT_SHOTS_CHECK, QT_OPT_MLE_FUSED_MAX_WAVES, QT_OPT_PAIRED_STAGES, QT_OPT_MLE
 QT_OPT_LIFP_DIST_SLICE = 5  # processes per slice of qt_lifp_dist_batch (0: the library's byte bound)
 QT_METRIC_TRACE, QT_METRIC_INFIDELITY = 0, 1  # qt_metric_dist_group_batch, qt_metric_dist_dim, qt_metric_dist_mat
 QT_OPT_MLE_HELPER_WAVE = 6  # n = 3 one-launch MLE, 'lin' start: a helper wavefront per trial lifts on speculation (0: the kernel without)
+QT_OPT_MHMC_PROCESS_SLICE = 7  # chains per slice of qt_mhmc_process_large_hits / _metric_hits (0: the library's 1024)
 
 # status codes (include/qtomo.h)
 QT_ERR_ARG, QT_ERR_STATE, QT_ERR_HIP, QT_ERR_SINGULAR, QT_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
@@ -115,6 +116,10 @@ SIGNATURES = {
                                       _c_dbl, _vp, _vp, _vp, _c_int]),
     "qt_mhmc_process_metric_hits": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _c_int,
                                              _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
+    "qt_mhmc_process_large_hits": (_c_int, [_vp, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _c_int, _c_int,
+                                            _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
+    "qt_mhmc_process_large_metric_hits": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64,
+                                                   _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int]),
     "qt_cptp_project_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_int]),
     "qt_states_choi_batch": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_int]),
     "qt_states_choi_dist_group_batch": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),

@@ -858,6 +858,23 @@ __global__ void __launch_bounds__(256) k_fwd64_nll(const int64_t* __restrict__ c
   if (threadIdx.x == 0) fpart[(size_t)c * nt + tile] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The three pieces of a chain step that every n = 3 chain kernel takes from here, so that the chain of qt_mhmc_process and
+// the device-drawn chain of qt_mhmc_process_large_hits (qt_mhmc_process64.h) round alike whatever stands next to them:
+//   mhmc64_nll       the NLL of a point from the row tiles' partial sums of k_fwd64_nll, summed in tile order
+//   mhmc64_proposal  element (row, col) of x + step * delta, delta the increment of the column-stacked entry col DC + row:
+//                    ONE fused multiply-add, written out (left to the compiler, a kernel under the sampler's
+//                    no-contraction pragma would round the product first)
+//   mhmc64_accept    the accept rule u <= exp(nll(x) - nll(x')); false for a NaN on either side
+__device__ __forceinline__ double mhmc64_nll(const double* __restrict__ fpart, int c, int nt) {
+  double sum = 0.0;
+  for (int k = 0; k < nt; ++k) sum += fpart[(size_t)c * nt + k];  // the same order in every thread
+  return -sum;
+}
+__device__ __forceinline__ cd mhmc64_proposal(cd cur, double step, double delta) {
+  return cd{__builtin_fma(step, delta, cur.re), cur.im};
+}
+__device__ __forceinline__ bool mhmc64_accept(double u, double f, double fn) { return u <= exp(f - fn); }
+
 // the accept test of a chain step on the tiles' partial sums (k_mhmc64_accept's second half); t = -1: the starting point
 __global__ void __launch_bounds__(256) k_mhmc64_decide(int C, int nt, int T_steps, int t, const double* __restrict__ fpart,
                                                        const double* __restrict__ proposal,
@@ -866,9 +883,7 @@ __global__ void __launch_bounds__(256) k_mhmc64_decide(int C, int nt, int T_step
                                                        int32_t* __restrict__ accepted) {
   const int c = blockIdx.x;
   if (c >= C) return;
-  double sum = 0.0;
-  for (int k = 0; k < nt; ++k) sum += fpart[(size_t)c * nt + k];  // the same order in every thread
-  const double fn = -sum;
+  const double fn = mhmc64_nll(fpart, c, nt);
   if (t < 0) {
     if (threadIdx.x == 0) fcur[c] = fn;
     return;
@@ -877,7 +892,7 @@ __global__ void __launch_bounds__(256) k_mhmc64_decide(int C, int nt, int T_step
   cd* cur = reinterpret_cast<cd*>(x) + (size_t)c * S::NE;
   const cd* prop = reinterpret_cast<const cd*>(proposal) + (size_t)c * S::NE;
   const double f = fcur[c];
-  const bool acc = uniforms[(size_t)c * T_steps + t] <= exp(f - fn);
+  const bool acc = mhmc64_accept(uniforms[(size_t)c * T_steps + t], f, fn);
   cd* out = reinterpret_cast<cd*>(chain_out) + ((size_t)c * T_steps + t) * S::NE;
   for (int k = threadIdx.x; k < S::NE; k += 256) {
     const cd v = acc ? prop[k] : cur[k];
@@ -1028,7 +1043,7 @@ __global__ void __launch_bounds__(256) k_mhmc64_propose(int C, int T_steps, int 
   const double* dl = deltas + ((size_t)c * T_steps + t) * Pgdb64::NE;
   for (int k = threadIdx.x; k < Pgdb64::NE; k += 256) {
     const int row = k >> 6, col = k & 63;
-    out[k] = cd{cur[k].re + step * dl[col * Pgdb64::DC + row], cur[k].im};  // delta is indexed like the column-stacked vector
+    out[k] = mhmc64_proposal(cur[k], step, dl[col * Pgdb64::DC + row]);  // delta is indexed like the column-stacked vector
   }
 }
 

@@ -33,6 +33,7 @@
 #include "qt_sampler.h"
 #include "qt_small.h"
 #include "qt_states_choi.h"
+#include "qt_mhmc_process64.h"  // (behind the older headers: its kernels are laid out behind theirs)
 
 // the kernels' names (qt_linesearch.h) for the trial statuses of the public header
 #define QT_SAME_STATUS(name) static_assert((int)qt::TRIAL_##name == (int)QT_TRIAL_##name, "qt::TrialStatus is QT_TRIAL_*")
@@ -184,6 +185,7 @@ struct qt_handle {
   DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
   DevBuf metric_ws;  // qt_metric_dist_group_batch / _dim / _mat, infidelity: the Hermitian roots of the call's G centres
+  DevBuf mhmc_parked;  // qt_mhmc_process_large_metric_hits: a slice's kept states Re(X) and, behind them, their distances
   // MLE hand-off between k_mle_start and k_mle_bfgs
   DevBuf ws_x, ws_g, ws_f, ws_act;
   // BFGS (s, y) history of the n >= 4 kernels (max_iter x 2 D doubles per trial of a chunk)
@@ -198,6 +200,7 @@ struct qt_handle {
   bool check_shots = true;  // qt_set_option(QT_OPT_SHOTS_CHECK) / QTOMO_SKIP_SHOTS_CHECK=1 at qt_create
   int fused_max_waves = 1024;  // qt_set_option(QT_OPT_MLE_FUSED_MAX_WAVES): largest batch (in trial-waves) of k_mle_fused
   int lifp_dist_slice = 0;  // qt_set_option(QT_OPT_LIFP_DIST_SLICE): processes per slice of qt_lifp_dist_batch (0: the byte bound's)
+  int mhmc_process_slice = 0;  // qt_set_option(QT_OPT_MHMC_PROCESS_SLICE): chains per slice of qt_mhmc_process_large_hits (0: 1024)
   bool paired_stages = true;  // qt_set_option(QT_OPT_PAIRED_STAGES): let paired tables take their own stages (n <= 3)
   // qt_set_option(QT_OPT_MLE_SPECIALISE): let an eligible POVM take the specialised MLE kernels (GENERIC = false, n <= 3)
   bool mle_specialise = true;
@@ -1408,7 +1411,7 @@ void qt_destroy(qt_handle_t* h) {
   (void)hipStreamSynchronize(h->stream);
   h->povm.release();
   for (DevBuf* b : {&h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
-                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp,
+                    &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->mhmc_parked, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp,
                     &h->sc_ok, &h->sc_fail, &h->sc_pos, &h->sc_tmp, &h->sc_in, &h->sc_out, &h->sc_iters, &h->sc_choi})
     b->release();
   for (DevBuf& b : h->stage) b.release();
@@ -1454,6 +1457,10 @@ int qt_set_option(qt_handle_t* h, int option, double value) {
     case QT_OPT_LIFP_DIST_SLICE:
       if (!(value >= 0.0 && value <= 16777216.0)) return fail(QT_ERR_ARG, "QT_OPT_LIFP_DIST_SLICE out of range");
       h->lifp_dist_slice = (int)value;
+      return 0;
+    case QT_OPT_MHMC_PROCESS_SLICE:
+      if (!(value >= 0.0 && value <= 16777216.0)) return fail(QT_ERR_ARG, "QT_OPT_MHMC_PROCESS_SLICE out of range");
+      h->mhmc_process_slice = (int)value;
       return 0;
     default: return fail(QT_ERR_ARG, "unknown option %d", option);
   }
@@ -2903,6 +2910,122 @@ int qt_mhmc_state_large_metric_hits(qt_handle_t* h, int metric, const int64_t* c
                                     int64_t* accepted, double* dist, int flags) {
   return mhmc_state_hits_large(h, "qt_mhmc_state_large_metric_hits", false, metric, counts, C, centres, x_init, thresholds, seed,
                                first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
+}
+
+// ---- the chain coverage study of three-qubit channels (qt_mhmc_process64.h)
+// qt_mhmc_process_large_hits and qt_mhmc_process_large_metric_hits (mhmc_hits_call), n = 3: the launch family of
+// qt_mhmc_process with the draws inside the propose and decide kernels, in slices of chains (QT_OPT_MHMC_PROCESS_SLICE)
+// that bound the workspaces; no host synchronisation inside a slice, none between slices either.  Per chain of a slice:
+// the current point (hess), the trial (ws_g) and its projection (ws_f) at 64 KB each, the projection's workspace
+// (proc_ws, Proc64::kWsComplex), the NLL and its tile partials (ws_x) and, metric entry, the parked state and its distance
+// (mhmc_parked).  The infidelity's roots of all C centres are made once per call (metric_ws), as metric_dim64 makes them.
+static int mhmc_process_large_hits_impl(qt_handle_t* h, const char* fn, bool hs, int metric, const int64_t* counts, int C,
+                                        const double* centres, const double* choi_init, const double* thresholds,
+                                        uint64_t seed, uint64_t first_chain, int burn_steps, int n_points, int thinning,
+                                        double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  auto refuse = [&](MhmcHitsElems& n) {
+    if (h->nq != 3)
+      return fail(QT_ERR_UNSUPPORTED, "%s supports n_qubits 3 (got %d): the entry for n <= 2 is %s", fn, h->nq,
+                  hs ? "qt_mhmc_process_hits" : "qt_mhmc_process_metric_hits");
+    const size_t ne2 = (size_t)h->D * h->D * 2;
+    n = {(size_t)h->D * h->M, ne2, ne2};
+    if (int r = need_povm(h)) return r;
+    if (!h->proc_set) return fail(QT_ERR_STATE, "qt_process_setup has not been called");
+    return 0;
+  };
+  auto launch_chains = [&](const MhmcHitsArgs& a) {
+    if (!h->proc.factored) return fail(QT_ERR_STATE, "%s: qt_process_setup left no factored operator", fn);
+    using K = qt::Mhmc64;
+    using W = qt::MetricDim64;
+    const int M = h->M, nt = qt::Fwd64::tiles(M);
+    const size_t ne2 = (size_t)K::NE * 2;
+    const int slice = h->mhmc_process_slice > 0 ? h->mhmc_process_slice : 1024;
+    const int ns = C < slice ? C : slice;  // the chains of the largest slice
+    HIPCHK(h->ws_x.ensure(((size_t)ns + (size_t)ns * nt) * sizeof(double)));
+    HIPCHK(h->ws_g.ensure((size_t)ns * ne2 * sizeof(double)));
+    HIPCHK(h->ws_f.ensure((size_t)ns * ne2 * sizeof(double)));
+    HIPCHK(h->hess.ensure((size_t)ns * ne2 * sizeof(double)));
+    if (!hs) HIPCHK(h->mhmc_parked.ensure(((size_t)ns * ne2 + (size_t)ns) * sizeof(double)));
+    double *fcur = h->ws_x.as<double>(), *fpart = fcur + ns, *x = h->hess.as<double>();
+    double *trial = h->ws_g.as<double>(), *proj = h->ws_f.as<double>();
+    double *parked = hs ? nullptr : h->mhmc_parked.as<double>(), *value = hs ? nullptr : parked + (size_t)ns * ne2;
+    const double *vs = h->proc.in_states.as<double>(), *vp = h->proc.emats.as<double>(), *none = nullptr;
+    const double* dcen = a.centres;
+    if (!hs && metric == QT_METRIC_INFIDELITY) {
+      HIPCHK(h->metric_ws.ensure((size_t)C * ne2 * sizeof(double)));
+      double* roots = h->metric_ws.as<double>();
+      if (int r = launch(h, qt::k_psd_sqrt_dim64, dim3(C), dim3(W::NT), W::kLdsBytes, a.centres, C, h->jtol2, roots)) return r;
+      dcen = roots;
+    }
+    HIPCHK(hipMemsetAsync(a.hits, 0, (size_t)C * sizeof(int64_t), h->stream));
+    HIPCHK(hipMemsetAsync(a.accepted, 0, (size_t)C * sizeof(int64_t), h->stream));
+    const uint32_t total = a.burn_steps + a.n_points * a.thinning;  // (< 2^32 - 1: checked by mhmc_hits_call)
+    for (int b0 = 0; b0 < C; b0 += slice) {
+      const int nb = C - b0 < slice ? C - b0 : slice;
+      const uint64_t gc0 = first_chain + (uint64_t)b0;
+      const int64_t* dc = a.counts + (size_t)b0 * K::DC * M;
+      const double *cen = dcen + (size_t)b0 * ne2, *thr = a.thresholds + b0;
+      int64_t *dh = a.hits + b0, *da = a.accepted + b0;
+      double* dd = a.dist ? a.dist + (size_t)b0 * a.n_points : nullptr;
+      HIPCHK(hipMemcpyAsync(x, a.init + (size_t)b0 * ne2, (size_t)nb * ne2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+      // the NLL of the starting points, as qt_mhmc_process takes it (t = -1: no table is read)
+      if (int r = launch(h, qt::k_fwd64_nll, dim3(nb * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, nb, M, vs, vp, x, none, 0, fpart))
+        return r;
+      if (int r = launch(h, qt::k_mhmc64_decide, dim3(nb), dim3(256), 0, nb, nt, 0, -1, fpart, none, none, x, fcur,
+                         (double*)nullptr, (int32_t*)nullptr))
+        return r;
+      uint32_t kept = 0, to_keep = 0;  // to_keep: steps until the next kept one (mhmc_process_hits_body)
+      for (uint32_t j = 0; j < total; ++j) {
+        const bool post = j >= a.burn_steps, keep = post && to_keep == 0;
+        if (int r = launch(h, qt::k_mhmc64_propose_draw, dim3(nb), dim3(K::NT), 0, nb, seed, gc0, j, step, x, trial)) return r;
+        if (int r = project(h, trial, nb, 0, 1000, 1e-12, proj, nullptr, nullptr)) return r;
+        if (int r = launch(h, qt::k_fwd64_nll, dim3(nb * nt), dim3(256), qt::Fwd64::kLdsBytes, dc, nb, M, vs, vp, x, proj, 1, fpart))
+          return r;
+        const qt::Mhmc64Step s{j, post ? 1 : 0, keep ? 1 : 0, kept};
+        if (int r = launch(h, qt::k_mhmc64_decide_hits, dim3(nb), dim3(K::NT), 0, nb, nt, s, seed, gc0, fpart, proj, x, fcur, cen,
+                           thr, a.n_points, dh, da, dd, parked))
+          return r;
+        if (post) {
+          if (keep) {
+            if (!hs) {
+              if (int r = metric == QT_METRIC_TRACE
+                              ? launch(h, qt::k_metric_dist_dim64<qt::kMetricTrace>, dim3(nb), dim3(W::NT), W::kLdsBytes, parked,
+                                       nb, cen, nb, 0, h->jtol2, value)
+                              : launch(h, qt::k_metric_dist_dim64<qt::kMetricInfidelity>, dim3(nb), dim3(W::NT), W::kLdsBytes,
+                                       parked, nb, cen, nb, 0, h->jtol2, value))
+                return r;
+              if (int r = launch(h, qt::k_mhmc64_tally, dim3((nb + 255) / 256), dim3(256), 0, nb, value, thr, a.n_points, kept, dh,
+                                 dd))
+                return r;
+            }
+            ++kept;
+            to_keep = a.thinning;
+          }
+          --to_keep;
+        }
+      }
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  return mhmc_hits_call(h, fn, hs, metric, counts, C, centres, choi_init, thresholds, burn_steps, n_points, thinning, hits, accepted,
+                        dist, flags, refuse, launch_chains);
+}
+
+int qt_mhmc_process_large_hits(qt_handle_t* h, const int64_t* counts, int C, const double* centres, const double* choi_init,
+                               const double* thresholds, uint64_t seed, uint64_t first_chain, int burn_steps, int n_points,
+                               int thinning, double step, int64_t* hits, int64_t* accepted, double* dist, int flags) {
+  return mhmc_process_large_hits_impl(h, "qt_mhmc_process_large_hits", true, 0, counts, C, centres, choi_init, thresholds, seed,
+                                      first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist, flags);
+}
+
+int qt_mhmc_process_large_metric_hits(qt_handle_t* h, int metric, const int64_t* counts, int C, const double* centres,
+                                      const double* choi_init, const double* thresholds, uint64_t seed, uint64_t first_chain,
+                                      int burn_steps, int n_points, int thinning, double step, int64_t* hits,
+                                      int64_t* accepted, double* dist, int flags) {
+  return mhmc_process_large_hits_impl(h, "qt_mhmc_process_large_metric_hits", false, metric, counts, C, centres, choi_init,
+                                      thresholds, seed, first_chain, burn_steps, n_points, thinning, step, hits, accepted, dist,
+                                      flags);
 }
 
 }  // extern "C"

@@ -187,7 +187,8 @@ class Engine:
         _capi.QT_OPT_MLE_HELPER_WAVE (n = 3, one-launch `mle` / `mle_dist` from the 'lin' start: 1 = a helper wavefront
         per trial clips the linear-inversion matrix on speculation beside the first Cholesky sweep and factorises the
         result beside the first evaluation, 0 = the kernel without helpers, see `mle_helper_wave`; the same bits either
-        way)."""
+        way), _capi.QT_OPT_MHMC_PROCESS_SLICE (n = 3: chains per slice of `mhmc_process_hits`; 0 = the library's 1024; the
+        same bits whatever the slice)."""
         self._chk(self.lib.qt_set_option(self._h, int(option), float(value)))
 
     @property
@@ -401,7 +402,7 @@ class Engine:
         each number a function of (seed, chain, step, index) alone (include/qtomo.h states the formula: that of
         `mhmc_draws` with the vector length D*D) -- what `mhmc_process` needs to run the chain of `mhmc_process_hits`.
         NumPy arrays, or `out` = (deltas, uniforms) float64 torch CUDA tensors of those shapes, filled in stream order.
-        n <= 2, after `set_povm` and `process_setup`."""
+        n <= 2, after `set_povm` and `process_setup`; at n = 3 `mhmc_draws_dim(D * D, ...)` writes the numbers out."""
         chains, steps = int(chains), int(steps)
         ne = self.D * self.D
         if out is not None:
@@ -425,12 +426,17 @@ class Engine:
         part lies at a Hilbert-Schmidt distance to centres[i] strictly below thresholds[i], accepted[i] = the accepted
         post-burn steps; with return_dist also the kept distances (C, n_points).  counts (C, D, S, K), centres and
         choi_init (C, D, D) complex, thresholds (C,): NumPy arrays (NumPy results) or torch CUDA tensors (tensors, in
-        stream order).  n <= 2.  metric='trace' / 'if': the same chains with the distance `metric_dist` returns for
-        the real part of a kept state and centres[i] (qt_mhmc_process_metric_hits); None: Hilbert-Schmidt."""
+        stream order).  metric='trace' / 'if': the same chains with the distance `metric_dist` returns for
+        the real part of a kept state and centres[i] (qt_mhmc_process_metric_hits); None: Hilbert-Schmidt.
+        n = 3 (qt_mhmc_process_large_hits, qt_mhmc_process_large_metric_hits): the launch family of `mhmc_process` per
+        step, drawing the numbers of `mhmc_draws_dim(D * D, ...)`, in slices of QT_OPT_MHMC_PROCESS_SLICE chains.  This
+        method is the place that picks the library's entry by the size."""
         code = None if metric is None else self._metric_code(metric)
-        return self._chain_hits("qt_mhmc_process", code, ((self.D, self.S, self.K), (self.D, self.D), (self.D, self.D)), counts,
-                                centres, choi_init, thresholds, seed, burn_steps, n_points, thinning, step, first_chain,
-                                return_dist)
+        return self._chain_hits("qt_mhmc_process" if self.n <= 2 else "qt_mhmc_process_large", code,
+                                ((self.D, self.S, self.K), (self.D, self.D), (self.D, self.D)), counts, centres, choi_init,
+                                thresholds, seed, burn_steps, n_points, thinning, step, first_chain, return_dist)
+
+    mhmc_process_large_hits = mhmc_process_hits  # (tests and scripts/ call it by this name at n = 3)
 
     def lifp_dev(self, counts, choi, cptp=True, iters=None, status=None):
         self._dev_call()

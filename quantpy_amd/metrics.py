@@ -24,7 +24,9 @@ of them in one launch that draws its own random numbers and returns, per trial, 
 (`qt_mhmc_state_hits`).  `get_CL_list_channel_mhmc` is the same branch for channels (n <= 2): a chain on the Choi vector
 per trial with the CPTP projection in every step, `qt_mhmc_process_hits`.  Both take dst='hs' | 'trace' | 'if': for the
 other two distances the chain kernels run the Jacobi-sweep metrics on the state they hold (`qt_mhmc_state_metric_hits`,
-`qt_mhmc_process_metric_hits`).  `get_CL_list_channel_boot_dst` is the process bootstrap study in any of the three: it
+`qt_mhmc_process_metric_hits`).  `get_CL_list_channel_mhmc_large` is that study for channels of up to three qubits: at
+n = 3 the chain is a launch family per step with the draws inside its kernels (`qt_mhmc_process_large_hits`,
+`qt_mhmc_process_large_metric_hits`).  `get_CL_list_channel_boot_dst` is the process bootstrap study in any of the three: it
 measures a chunk's Choi matrices the same way.  `get_CL_list_channel_boot_states` is that study with the resamples
 reconstructed from their output states (method_boot='states'): a chunk's states by `lin_dev` / `mle_dev`, their Choi
 matrices, the conditional CPTP projection and the distances by `qt_states_choi_dist_group_batch`.
@@ -547,7 +549,8 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     `burn_steps` steps, then n_points * thinning of which every `thinning`-th state is a sample, the samples' real parts
     measured against the estimate), and the level at which the true Choi matrix leaves the interval of the sampled
     distances.  Returns the sorted levels.  (`get_CL_list_channel(interval='mhmc')` keeps its refusal; this is the study's
-    name.)  One and two qubits: a channel of more qubits raises NotImplementedError.
+    name.)  One and two qubits: a channel of more qubits raises NotImplementedError; `get_CL_list_channel_mhmc_large` is
+    the same study for one to three qubits.
 
     The trials are formed as in `get_CL_list_channel_boot` (`point_estimate_batch` with its default cptp=True).  All
     chains of this rank's `shard_bounds(n_iter)` run in ONE launch (`Engine.mhmc_process_hits`), chain t from its own
@@ -570,10 +573,19 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
     An estimate that is not finite (an input state without counts) raises ValueError on every rank.  `sampler`, `seed`,
     `return_details` as in `get_CL_list_state`; the details also hold `acceptance_rate`, per trial the accepted post-burn
     steps / (n_points * thinning), the reference's definition."""
-    n_iter, n_points, burn_steps, thinning, metric = _chain_arguments(n_iter, n_points, burn_steps, thinning, sampler, dst)
+    chain = _chain_arguments(n_iter, n_points, burn_steps, thinning, sampler, dst)
     if channel.n_qubits > 2:
         raise NotImplementedError(f"get_CL_list_channel_mhmc runs channels of one and two qubits, not {channel.n_qubits}: "
                                   "the chain of a three-qubit process has no fused kernel")
+    return _channel_mhmc_study(channel, chain, n_measurements, method, povm, input_states, states_init, states_est_method,
+                               step, sampler, seed, return_details)
+
+
+def _channel_mhmc_study(channel, chain, n_measurements, method, povm, input_states, states_init, states_est_method, step,
+                        sampler, seed, return_details):
+    """The body of `get_CL_list_channel_mhmc` and `get_CL_list_channel_mhmc_large`; `chain`: what `_chain_arguments`
+    returned.  `Engine.mhmc_process_hits` picks the library's entry by the size of the channel."""
+    n_iter, n_points, burn_steps, thinning, metric = chain
     tmg = ProcessTomograph(channel, input_states, "hs")
     counts, base = _trial_counts(tmg, n_measurements, povm, n_iter, sampler, seed, True)
     choi = tmg.point_estimate_batch(counts, method=method, states_est_method=states_est_method, states_init=states_init)
@@ -586,3 +598,33 @@ def get_CL_list_channel_mhmc(channel, n_iter=1000, n_points=1000, n_measurements
                                          thinning, step, metric=metric)
     return _result(levels_from_hits(hits, n_points), return_details, counts=counts, estimates=choi, delta=delta, hits=hits,
                    seed=key, acceptance_rate=accepted / (n_points * thinning))
+
+
+def get_CL_list_channel_mhmc_large(channel, n_iter=1000, n_points=1000, n_measurements=1000, method="lifp", povm="proj-set",
+                                   input_states="proj4", states_init="lin", states_est_method="lin", step=0.01,
+                                   burn_steps=1000, thinning=1, *, sampler="device", seed=None, return_details=False,
+                                   dst="hs"):
+    """`get_CL_list_channel_mhmc` for channels of one, two and three qubits: the same study, arguments, defaults, keying,
+    sharding and details.  At n <= 2 it is that function -- the same bits; that name refuses three qubits, this one serves
+    them.  A channel of more than three qubits raises NotImplementedError.
+
+    n = 3: the chains run through `qt_mhmc_process_large_hits` / `qt_mhmc_process_large_metric_hits` (include/qtomo.h): per
+    step the launches of `Engine.mhmc_process` at n = 3 -- proposal, CPTP projection, model and NLL, accept test -- with the
+    numbers of `Engine.mhmc_draws_dim(4096, ...)` drawn inside the proposing and the deciding kernel, and the kept state
+    measured where it lies; per trial the hits and the accepted steps come back.  The chains of a rank run in slices of
+    1024 (QT_OPT_MHMC_PROCESS_SLICE), about 0.6 MB of workspace per chain of a slice.
+
+    `step` must be chosen for the shots: the process likelihood uses the raw counts and sharpens with them.  At
+    n_measurements = 10 000 per setting step = 1e-5 accepts about half of the proposals of a three-qubit chain
+    (tests/test_gpu_batch_positions.py); the default step = 0.01 accepts nothing at n = 3.
+
+    Cost at n = 3 (profiles/process_mhmc_large_coverage_timing.txt; depolarizing channel, 10 000 shots, step 1e-5): the
+    defaults' 2000 steps of 1000 chains take 3.3 s end to end in 'hs' and 7.4 s in 'trace', 1.5 / 3.6 ms per step; the CPTP
+    projection (1.0 ms) and the model and NLL (0.6 ms) make up an 'hs' step, the 64 x 64 eigen-solves (4.2 ms per kept
+    step) most of a 'trace' one."""
+    chain = _chain_arguments(n_iter, n_points, burn_steps, thinning, sampler, dst)
+    if channel.n_qubits > 3:
+        raise NotImplementedError(f"get_CL_list_channel_mhmc_large runs channels of one to three qubits, not "
+                                  f"{channel.n_qubits}")
+    return _channel_mhmc_study(channel, chain, n_measurements, method, povm, input_states, states_init, states_est_method,
+                               step, sampler, seed, return_details)
