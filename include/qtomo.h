@@ -381,6 +381,20 @@ int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double
 int qt_lp_ineq_large_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                            double* obj, double* x, int32_t* status, int32_t* iters, int flags);
 
+/* The same programs, arguments, statuses and return value for 1 <= N <= 1023 (csrc/qt_lp_xl.h): the polytope of a
+ * five-qubit state (N = 4^5 - 1; A is 7776 x 1023 with 'proj-set').  The normal matrix (up to 1024 x 1024, 8 MB) lives
+ * in a per-workgroup slice of a global workspace and is formed on the FP64 matrix cores; the blocked Cholesky and its
+ * pivot rule are those of qt_lp_ineq_large_batch.  A workgroup occupies a compute unit, so a call launches at most 256
+ * of them and its workspace is 8 388 608 + 56 M bytes per workgroup, at most 4 GB in all (2.3 GB for 256 workgroups at
+ * M = 7776; a call with fewer programs allocates for those only).  The workspace grows to the largest call and stays
+ * with the handle until qt_destroy.  N > 1023 is QT_ERR_UNSUPPORTED, and so is an M whose seven M-vectors do not fit the
+ * 4 GB beside one normal matrix (M > 76 million).  At 7776 x 1023 a program takes 3.7 s (187 ms per iteration, measured
+ * on an MI355X: profiles/lp_xl_timing.txt) and 256 of them 5.0 s: callers split large batches into launches of about
+ * 256 programs.  Below 256 variables the entry agrees with qt_lp_ineq_large_batch to the solver's tolerance, not bit
+ * for bit. */
+int qt_lp_ineq_xl_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                        double* obj, double* x, int32_t* status, int32_t* iters, int flags);
+
 /* ---- f4: quantpy/tomography/polytopes (the coverage study of arXiv:2109.04734, Fig. 1) over a batch of trials ------
  * A trial is a count table counts[b][R][K] with shots[r] per setting (for a process the output tomographs are stacked,
  * R = inputs x settings, and shots repeats the first tomograph's, as utils.py:11 broadcasts them);

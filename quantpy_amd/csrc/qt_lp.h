@@ -18,7 +18,8 @@
 // contains a barrier depends only on values that are uniform over the workgroup (block reductions, LDS).
 //
 // The iteration (lp_phase) and the per-workgroup driver (lp_run) are templates: k_lp_ineq_large (qt_lp_large.h, up to
-// 255 variables) runs the same text on its own primitives.  A kernel supplies one struct of primitives (LpSmall here).
+// 255 variables) and k_lp_ineq_xl (qt_lp_xl.h, up to 1023) run the same text on their own primitives.  A kernel
+// supplies one struct of primitives (LpSmall here).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -168,6 +169,7 @@ __device__ inline void lp_ratio(double x, double dx, double* amin) {
 // What differs between the kernels that run lp_phase / lp_run below is one struct P per kernel.  It holds A, M, N and
 // vec (the six M-vectors s, z, r_p, w, w2, w3 of this workgroup's workspace), names the kernel's LDS block (Shared: y,
 // dy, rd, u, c, red and what the primitives need) and supplies
+//   kCols                 the most columns it takes, the phase-1 column included (see QT_LP_COLS),
 //   ws_doubles(M)         doubles of global workspace per workgroup,
 //   matvec(v), av(i, v)   make A v available / (A v)_i for the v of the last matvec, over the first N columns,
 //   colsum(sh, v, p1)     sh.u[j] = (A^T v)_j, and sh.u[N] = sum v (read in phase 1 only),
@@ -181,6 +183,7 @@ __device__ inline void lp_ratio(double x, double dx, double* amin) {
 // k_lp_ineq's: the normal matrix in LDS, (A v)_i computed where it is read (no M-vector for it).
 struct LpSmall {
   using Shared = LpShared;
+  static constexpr int kCols = kLpMaxN + 1;
   const double* __restrict__ A;
   int M, N;
   double* vec;
@@ -212,7 +215,19 @@ struct LpSmall {
   __device__ __forceinline__ void solve(LpShared& sh, int n, double* v) const { lp_solve(sh, n, v); }
 };
 
-// One phase of the interior-point method, for both kernels: every tolerance and test of the method is here and in
+// QT_LP_COLS(P, j, n, statement): the statement for every column j < n, spread over the workgroup.  Where P's columns fit
+// its threads (kCols <= kLpNT, the two kernels with up to 256 columns) that is `if (t < n)`, spelled as it was before
+// there was a third kernel (their device code is compared, scripts/isa_identity.py); otherwise a loop in strides of the
+// workgroup.  A macro and not a function that takes a lambda: the captures change the code of the first two kernels.
+#define QT_LP_COLS(P, j, n, ...)                     \
+  if constexpr (P::kCols <= kLpNT) {                 \
+    const int j = threadIdx.x;                       \
+    if (j < (n)) __VA_ARGS__                         \
+  } else {                                           \
+    for (int j = threadIdx.x; j < (n); j += kLpNT) __VA_ARGS__ \
+  }
+
+// One phase of the interior-point method, for every kernel: every tolerance and test of the method is here and in
 // lp_run, nowhere else in device code.  In: sh.y[0..n) (n = N + p1), sh.c[0..n), s, z (global, this LP's rows).
 // Returns LP_FEASIBLE (phase 1: x strictly feasible), LP_INFEASIBLE (phase 1 converged), LP_OPTIMAL, LP_UNBOUNDED or
 // LP_NOT_CONVERGED.  On LP_FEASIBLE the last matvec was of sh.y.
@@ -245,7 +260,7 @@ __device__ __forceinline__ int lp_phase(typename P::Shared& sh, const P& p, bool
       dres = fmax(dres, fabs(rdj));
     }
     __syncthreads();
-    if (t < n) sh.rd[t] = (t < N ? sh.u[t] : -sh.u[N]) + sh.c[t];
+    QT_LP_COLS(P, j, n, sh.rd[j] = (j < N ? sh.u[j] : -sh.u[N]) + sh.c[j];)
     __syncthreads();
     *iters += 1;
     const double gap = sums[0], mu = gap / M;
@@ -265,7 +280,7 @@ __device__ __forceinline__ int lp_phase(typename P::Shared& sh, const P& p, bool
     // ---- predictor: r_sz = s z
     for (int i = t; i < M; i += kLpNT) w[i] = z[i] - z[i] * rp[i] / s[i];
     p.colsum(sh, w, p1);
-    if (t < n) sh.dy[t] = -sh.rd[t] + (t < N ? sh.u[t] : -sh.u[N]);
+    QT_LP_COLS(P, j, n, sh.dy[j] = -sh.rd[j] + (j < N ? sh.u[j] : -sh.u[N]);)
     __syncthreads();
     p.solve(sh, n, sh.dy);
     p.matvec(sh.dy);
@@ -297,7 +312,7 @@ __device__ __forceinline__ int lp_phase(typename P::Shared& sh, const P& p, bool
       w[i] = (rsz - z[i] * rp[i]) / s[i];
     }
     p.colsum(sh, w, p1);
-    if (t < n) sh.dy[t] = -sh.rd[t] + (t < N ? sh.u[t] : -sh.u[N]);
+    QT_LP_COLS(P, j, n, sh.dy[j] = -sh.rd[j] + (j < N ? sh.u[j] : -sh.u[N]);)
     __syncthreads();
     p.solve(sh, n, sh.dy);
     p.matvec(sh.dy);
@@ -321,7 +336,7 @@ __device__ __forceinline__ int lp_phase(typename P::Shared& sh, const P& p, bool
       s[i] = fma(ap, rp[i], s[i]);
       z[i] = fma(ad, w3[i], z[i]);
     }
-    if (t < n) sh.y[t] = fma(ap, sh.dy[t], sh.y[t]);
+    QT_LP_COLS(P, j, n, sh.y[j] = fma(ap, sh.dy[j], sh.y[j]);)
     __syncthreads();
   }
   return LP_NOT_CONVERGED;
@@ -359,10 +374,10 @@ __device__ __forceinline__ void lp_run(typename P::Shared& sh, const P& p, const
     int st = LP_NOT_CONVERGED;
     // phase 1 from x = 0, t0 = max(-b, 0) + 1: s = b + t0 >= 1, z = 1 / M (the dual's sum z = 1 holds)
     const double t0 = fmax(bm[1], 0.0) + 1.0;
-    if (t <= N) {
-      sh.y[t] = (t == N) ? t0 : 0.0;
-      sh.c[t] = (t == N) ? 1.0 : 0.0;
-    }
+    QT_LP_COLS(P, j, N + 1, {
+      sh.y[j] = (j == N) ? t0 : 0.0;
+      sh.c[j] = (j == N) ? 1.0 : 0.0;
+    })
     for (int i = t; i < M; i += kLpNT) {
       s[i] = b[i] + t0;
       z[i] = 1.0 / M;
@@ -381,7 +396,7 @@ __device__ __forceinline__ void lp_run(typename P::Shared& sh, const P& p, const
       lp_reduce<1, false>(ssum, sh.red);
       const double smean = ssum[0] / M;
       for (int i = t; i < M; i += kLpNT) z[i] = smean / s[i];
-      if (t < N) sh.c[t] = c[t];
+      QT_LP_COLS(P, j, N, sh.c[j] = c[j];)
       __syncthreads();
       st = lp_phase(sh, p, false, b, amax[0], bn, fmax(1.0, cm[0]), &it);
     }
@@ -399,10 +414,14 @@ __device__ __forceinline__ void lp_run(typename P::Shared& sh, const P& p, const
       status[lp] = st;
       if (iters) iters[lp] = it;
     }
-    if (xout && t < N) xout[(size_t)lp * N + t] = sh.y[t];
+    if (xout) {
+      QT_LP_COLS(P, j, N, xout[(size_t)lp * N + j] = sh.y[j];)
+    }
     __syncthreads();  // sh.y / sh.c are rewritten by the next program
   }
 }
+
+#undef QT_LP_COLS
 
 // grid: persistent workgroups over the R * O programs; ws: gridDim.x * LpSmall::ws_doubles(M) doubles
 __global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A, int M, int N,

@@ -339,6 +339,7 @@ __device__ __noinline__ void lg_solve(LgShared& sh, const double* H, int n, doub
 // workspace, A v through a seventh M-vector behind the six of the iteration.
 struct LpLarge {
   using Shared = LgShared;
+  static constexpr int kCols = kLgLD;
   const double* __restrict__ A;
   int M, N;
   double *H, *vec, *ax;

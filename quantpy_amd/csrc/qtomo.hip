@@ -19,6 +19,7 @@
 #include "qt_large.h"
 #include "qt_lp.h"
 #include "qt_lp_large.h"
+#include "qt_lp_xl.h"
 #include "qt_metric_dim.h"
 #include "qt_metric_dim64.h"
 #include "qt_mhmc_state.h"
@@ -183,6 +184,9 @@ struct qt_handle {
   DevBuf moment_freq, moment_part, moment_qpart;  // k_moment_cols: counts / ns, the blocks' partial sums, Q_ab in pieces
   DevBuf lp_ws;  // qt_lp_ineq_batch: six M-vectors per workgroup
   DevBuf lp_large_ws;  // qt_lp_ineq_large_batch: the normal matrix and seven M-vectors per workgroup
+  // qt_lp_ineq_xl_batch: the same with an 8 MB normal matrix, one workgroup per compute unit; up to 2.3 GB after a call
+  // with 256 five-qubit programs, kept until qt_destroy like every workspace here
+  DevBuf lp_xl_ws;
   DevBuf poly_ws;  // qt_polytope_coverage: hits[B][L] when the caller wants only the counts
   DevBuf metric_ws;  // qt_metric_dist_group_batch / _dim / _mat, infidelity: the Hermitian roots of the call's G centres
   DevBuf mhmc_parked;  // qt_mhmc_process_large_metric_hits: a slice's kept states Re(X) and, behind them, their distances
@@ -1412,7 +1416,8 @@ void qt_destroy(qt_handle_t* h) {
   h->povm.release();
   for (DevBuf* b : {&h->info, &h->kron_dig, &h->aug, &h->proc_ws, &h->lifp_dist_ws, &h->born_ws,
                     &h->gram, &h->moment_freq, &h->moment_part, &h->moment_qpart, &h->poly_ws, &h->metric_ws, &h->mhmc_parked, &h->ws_x, &h->ws_g, &h->ws_f, &h->ws_act, &h->hess, &h->sort_alt, &h->sort_tmp,
-                    &h->sc_ok, &h->sc_fail, &h->sc_pos, &h->sc_tmp, &h->sc_in, &h->sc_out, &h->sc_iters, &h->sc_choi})
+                    &h->sc_ok, &h->sc_fail, &h->sc_pos, &h->sc_tmp, &h->sc_in, &h->sc_out, &h->sc_iters, &h->sc_choi,
+                    &h->lp_ws, &h->lp_large_ws, &h->lp_xl_ws})
     b->release();
   for (DevBuf& b : h->stage) b.release();
   h->proc.release();
@@ -2280,12 +2285,18 @@ int qt_moment_freq_batch(qt_handle_t* h, const double* freq, int B, int S, int K
   return c.done();
 }
 
-// ---- f3: interval.py:268-335, the LPs of PolytopeStateInterval (qt_lp.h, qt_lp_large.h) --------------------------------
-// Both LP entries: `name` for the messages, at most max_n variables, per_wg bytes of workspace per workgroup in `ws`.
-// The large entry refuses a workgroup's workspace above 256 MB (refuse_ws); the small one then runs one workgroup.
+// ---- f3: interval.py:268-335, the LPs of PolytopeStateInterval (qt_lp.h, qt_lp_large.h, qt_lp_xl.h) --------------------
+// The LP entries: `name` for the messages, at most max_n variables, per_wg bytes of workspace per workgroup in `ws`, at
+// most max_grid workgroups and ws_cap bytes of workspace in all.  The large entries refuse a workgroup's workspace
+// above the cap (refuse_ws); the small one then runs one workgroup.
+constexpr size_t kLpWsCap = (size_t)256 << 20;
+// qt_lp_ineq_xl_batch: a workgroup holds 124 KB of LDS, so one runs per compute unit (256), each with 8 MB + 7 M doubles
+constexpr long long kLpXlGrid = 256;
+constexpr size_t kLpXlWsCap = (size_t)4 << 30;
 using LpKernel = void (*)(const double*, int, int, const double*, int, const double*, int, double*, double*, int32_t*,
                           int32_t*, double*);
-static int lp_ineq_entry(qt_handle_t* h, const char* name, int max_n, size_t per_wg, bool refuse_ws, DevBuf qt_handle_t::*ws,
+static int lp_ineq_entry(qt_handle_t* h, const char* name, int max_n, size_t per_wg, bool refuse_ws, long long max_grid,
+                         size_t ws_cap, DevBuf qt_handle_t::*ws,
                          LpKernel kernel, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                          double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
   QT_ENTER(h);
@@ -2305,12 +2316,12 @@ static int lp_ineq_entry(qt_handle_t* h, const char* name, int max_n, size_t per
   if (int r = c.out(x, (size_t)P * N, &dx)) return r;
   if (int r = c.out(status, (size_t)P, &dst)) return r;
   if (int r = c.out(iters, (size_t)P, &dit)) return r;
-  // persistent workgroups: at most 2048, and at most 256 MB of workspace (the large kernel takes about 0.6 MB each:
-  // about 400 workgroups)
-  long long grid = P < 2048 ? P : 2048;
-  const long long by_ws = (long long)((256u << 20) / per_wg);
+  // persistent workgroups: at most max_grid, and at most ws_cap of workspace (2048 and 256 MB for the two smaller
+  // kernels: the large one takes about 0.6 MB each, about 400 workgroups)
+  long long grid = P < max_grid ? P : max_grid;
+  const long long by_ws = (long long)(ws_cap / per_wg);
   if (by_ws < 1 && refuse_ws)
-    return fail(QT_ERR_UNSUPPORTED, "%s: M = %d needs more than 256 MB of workspace per program", name, M);
+    return fail(QT_ERR_UNSUPPORTED, "%s: M = %d needs more than %zu MB of workspace per program", name, M, ws_cap >> 20);
   if (grid > by_ws) grid = by_ws > 0 ? by_ws : 1;
   HIPCHK((h->*ws).ensure((size_t)grid * per_wg));
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(qt::kLpNT), 0, h->stream, dA, M, N, dC, O, db, R, dobj, dx, dst, dit,
@@ -2320,15 +2331,23 @@ static int lp_ineq_entry(qt_handle_t* h, const char* name, int max_n, size_t per
 
 int qt_lp_ineq_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                      double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
-  return lp_ineq_entry(h, "qt_lp_ineq_batch", qt::kLpMaxN, qt::LpSmall::ws_doubles(M) * sizeof(double), false, &qt_handle_t::lp_ws,
+  return lp_ineq_entry(h, "qt_lp_ineq_batch", qt::kLpMaxN, qt::LpSmall::ws_doubles(M) * sizeof(double), false, 2048, kLpWsCap,
+                       &qt_handle_t::lp_ws,
                        qt::k_lp_ineq, A, M, N, C, O, b, R, obj, x, status, iters, flags);
 }
 
 // The same programs for 65 ... 255 variables (qt_lp_large.h): the normal matrix lives in the workspace, not in LDS.
 int qt_lp_ineq_large_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                            double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
-  return lp_ineq_entry(h, "qt_lp_ineq_large_batch", qt::kLgMaxN, qt::LpLarge::ws_doubles(M) * sizeof(double), true,
-                       &qt_handle_t::lp_large_ws, qt::k_lp_ineq_large, A, M, N, C, O, b, R, obj, x, status, iters, flags);
+  return lp_ineq_entry(h, "qt_lp_ineq_large_batch", qt::kLgMaxN, qt::LpLarge::ws_doubles(M) * sizeof(double), true, 2048,
+                       kLpWsCap, &qt_handle_t::lp_large_ws, qt::k_lp_ineq_large, A, M, N, C, O, b, R, obj, x, status, iters, flags);
+}
+
+// The same programs for up to 1023 variables (qt_lp_xl.h): the polytope of a five-qubit state.
+int qt_lp_ineq_xl_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
+                        double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
+  return lp_ineq_entry(h, "qt_lp_ineq_xl_batch", qt::kXlMaxN, qt::LpXl::ws_doubles(M) * sizeof(double), true, kLpXlGrid,
+                       kLpXlWsCap, &qt_handle_t::lp_xl_ws, qt::k_lp_ineq_xl, A, M, N, C, O, b, R, obj, x, status, iters, flags);
 }
 
 // ---- f4: polytopes/utils.py:4-27, verification.py:9-78 over a batch of trials (qt_polytope.h) -------------------------

@@ -1039,14 +1039,23 @@ class Engine:
         instead of ending the program, so at N <= 64 the two agree to the solver's tolerance, not bit for bit."""
         return self._lp_call(self.lib.qt_lp_ineq_large_batch, A, C, b, return_x)
 
+    def lp_ineq_xl_batch(self, A, C, b, return_x=False):
+        """lp_ineq_large_batch for 1 <= N <= 1023 variables (qt_lp_ineq_xl_batch): the same arguments and results.
+        The normal matrix (8 MB) is formed on the FP64 matrix cores; a workgroup occupies a compute unit, so a call
+        runs at most 256 programs at a time and callers split long batches (polytopes.fidelity).  At N <= 255 the two
+        agree to the solver's tolerance, not bit for bit."""
+        return self._lp_call(self.lib.qt_lp_ineq_xl_batch, A, C, b, return_x)
+
     def _lp_ineq_by_size(self, A, C, b, return_x=False):
         """The LP kernel for this number of variables -> (lp_ineq_batch's tuple, resolved).  N <= 64 keeps
         lp_ineq_batch and its bits; a right-hand side with a program that it leaves NOT_CONVERGED (its plain Cholesky
         breaks down near a degenerate optimum, e.g. the polytope programs of a pure target state) is solved again by
         lp_ineq_large_batch, whose factorisation replaces a vanishing pivot, and takes that kernel's results for all
         its objectives.  resolved (R,) bool marks those right-hand sides (all True above 64 variables: the large
-        kernel solved everything)."""
+        kernel solved everything, or above 255 variables lp_ineq_xl_batch, which has the same factorisation)."""
         rhs = _f64(np.atleast_2d(b))
+        if np.shape(A)[1] > 255:
+            return self.lp_ineq_xl_batch(A, C, rhs, return_x), np.ones(rhs.shape[0], dtype=bool)
         if np.shape(A)[1] > 64:
             return self.lp_ineq_large_batch(A, C, rhs, return_x), np.ones(rhs.shape[0], dtype=bool)
         res = self.lp_ineq_batch(A, C, rhs, return_x)

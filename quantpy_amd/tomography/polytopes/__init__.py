@@ -3,4 +3,5 @@ reference's `quantpy.tomography.polytopes` with the per-(trial, level) bisection
 the fidelity bounds of Fig. 2 (`fidelity`: the interval classes and the study over many simulated tomographs, on the
 batched LP kernels)."""
 from . import fidelity, utils, verification  # noqa: F401
-from .fidelity import ProcessFidelityInterval, StateFidelityInterval, fidelity_qpt, fidelity_qst  # noqa: F401
+from .fidelity import (ProcessFidelityInterval, StateFidelityInterval, StateFidelityIntervalXL, fidelity_qpt,  # noqa: F401
+                       fidelity_qst, fidelity_qst_xl)

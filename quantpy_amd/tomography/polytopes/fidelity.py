@@ -2,10 +2,12 @@
 the reference's `PolytopeProcessInterval` (interval.py:338-418) and the study "Multiple intervals for fidelity" of
 polytopes/notebooks/Fidelity.ipynb, with every linear program of a call in one launch of the batched interior-point
 solver -- qt_lp_ineq_batch up to 64 variables, qt_lp_ineq_large_batch up to 255 (a two-qubit process has 240, a
-four-qubit state 255).
+four-qubit state 255), qt_lp_ineq_xl_batch up to 1023 (a five-qubit state).
 
 `ProcessFidelityInterval` and `StateFidelityInterval` are the interval classes (one tomograph, n_points widenings);
 `fidelity_qpt` and `fidelity_qst` simulate many tomographs and bound the fidelity of each at given confidence levels.
+`StateFidelityIntervalXL` and `fidelity_qst_xl` are the state versions up to five qubits (the names without XL keep
+their limit of four).
 `quantpy_amd.PolytopeProcessInterval` stays the reference's placeholder and `PolytopeStateInterval` keeps its limit of
 three qubits; the classes here are the ones to use.
 """
@@ -16,14 +18,32 @@ from ...sampling import SAMPLERS, draw_counts, resolve_seed, trial_chunks
 from ..interval import ConfidenceInterval, Mode, PolytopeStateInterval, _FidelityBounds, _pop_hidden_keys, count_delta
 from .verification import _weighted_povm, chunk_trials, qpt_tables, qst_tables
 
-__all__ = ["ProcessFidelityInterval", "StateFidelityInterval", "fidelity_qpt", "fidelity_qst", "process_matrix",
-           "process_programs"]
+__all__ = ["ProcessFidelityInterval", "StateFidelityInterval", "StateFidelityIntervalXL", "fidelity_qpt", "fidelity_qst",
+           "fidelity_qst_xl", "process_matrix", "process_programs"]
 
 # Programs per launch of the study functions: a program of the large kernel occupies a workgroup for milliseconds
-# (DESIGN 4.8), one of the small kernel for tens of microseconds; both bounds keep a launch well under a second.
+# (DESIGN 4.8), one of the small kernel for tens of microseconds; both bounds keep a launch well under a second.  A
+# program of the XL kernel (above 255 variables) occupies a compute unit for 3.7 s at 7776 x 1023 (measured:
+# profiles/lp_xl_timing.txt), and the grid has 256 workgroups: one program each, so that a launch ends with its first
+# wave of programs (5.0 s for 256 of them).
 kLaunchProgramsSmall = 1 << 16
 kLaunchProgramsLarge = 1 << 12
+kLaunchProgramsXL = 256
 kRhsBytes = 128 << 20
+
+
+def _launch_cap(n_variables):
+    return kLaunchProgramsSmall if n_variables <= 64 else kLaunchProgramsLarge if n_variables <= 255 else kLaunchProgramsXL
+
+
+def _lp_in_launches(engine, A, C, b):
+    """engine._lp_ineq_by_size(A, C, b); above 255 variables in launches of at most kLaunchProgramsXL programs (whole
+    right-hand sides).  The programs are independent, so the split changes no bit."""
+    per = max(1, kLaunchProgramsXL // len(C))
+    if A.shape[1] <= 255 or len(b) <= per:
+        return engine._lp_ineq_by_size(A, C, b)
+    parts = [engine._lp_ineq_by_size(A, C, b[i:i + per]) for i in range(0, len(b), per)]
+    return tuple(np.concatenate([p[0][k] for p in parts]) for k in range(3)), np.concatenate([p[1] for p in parts])
 
 
 def process_matrix(states_matrix, weighted, dim):
@@ -67,6 +87,19 @@ class StateFidelityInterval(PolytopeStateInterval):
 
     def _lp(self, A, C, b):
         res, self.lp_resolved = get_engine(self.tmg.state.n_qubits)._lp_ineq_by_size(A, C, b)
+        return res
+
+
+class StateFidelityIntervalXL(StateFidelityInterval):
+    """`StateFidelityInterval` up to five qubits.  At n <= 4 it is that class, bit for bit; at n = 5 (1023 variables, A
+    is 7776 x 1023 with 'proj-set') the programs run on qt_lp_ineq_xl_batch, in launches of kLaunchProgramsXL programs:
+    the default n_points = 1000 is eight launches of 5 s each (36 s measured for the whole setup(),
+    profiles/lp_xl_timing.txt)."""
+
+    _MAX_QUBITS, _MAX_VARIABLES = 5, 1023
+
+    def _lp(self, A, C, b):
+        res, self.lp_resolved = _lp_in_launches(get_engine(self.tmg.state.n_qubits), A, C, b)
         return res
 
 
@@ -129,8 +162,8 @@ def _study(probas, shots, A, offset, c, scale, base, clip_b, conf_levels, n_tria
     else:
         seed = resolve_seed(seed)
     if chunk is None:
-        cap = kLaunchProgramsSmall if A.shape[1] <= 64 else kLaunchProgramsLarge
-        chunk = min(chunk_trials(n_trials, n_rows * n_out, n_lv), cap // (2 * max(n_lv, 1)), kRhsBytes // (8 * m * max(n_lv, 1)))
+        chunk = min(chunk_trials(n_trials, n_rows * n_out, n_lv), _launch_cap(A.shape[1]) // (2 * max(n_lv, 1)),
+                    kRhsBytes // (8 * m * max(n_lv, 1)))
     chunk = int(max(1, min(chunk, max(n_trials, 1))))
     C = np.stack([c, -c])
     f_min = np.full((n_trials, n_lv), np.nan)
@@ -152,7 +185,7 @@ def _study(probas, shots, A, offset, c, scale, base, clip_b, conf_levels, n_tria
         if clip_b:
             b = np.clip(b, 1e-15, 1 - 1e-15)
         b = (b - offset).reshape(size * n_lv, m)
-        (obj, st, it), large = engine._lp_ineq_by_size(A, C, b)
+        (obj, st, it), large = _lp_in_launches(engine, A, C, b)
         sl = slice(start, start + size)
         obj = np.where(st == _capi.LP_OPTIMAL, obj, np.nan).reshape(size, n_lv, 2)
         lo, hi = base + scale * obj[..., 0], base - scale * obj[..., 1]
@@ -173,11 +206,29 @@ def fidelity_qst(state, target_state, conf_levels, n_measurements=1000, n_trials
     StateFidelityInterval; n <= 4).  -> (f_min, f_max), each (n_trials, L); NaN in both where one of the two programs
     is not optimal (no mapping to 1 here).  return_table=True adds a dict with `deltas` (n_trials, L), `lp_status` and
     `lp_iters` (n_trials, L, 2) and `lp_resolved` (n_trials, L) bool: True where the programs were solved by the large
-    kernel (always above 64 variables; below, where the small kernel left one NOT_CONVERGED).  sampler / seed: as verification.test_qst.  chunk: trials per launch (default: bounded
-    by the work and the memory of a launch); the results do not depend on it."""
+    kernel (always above 64 variables; below, where the small kernel left one NOT_CONVERGED).  sampler / seed: as
+    verification.test_qst.  chunk: trials per launch (default: bounded by the work and the memory of a launch); the
+    results do not depend on it."""
+    return _fidelity_qst("fidelity_qst", 4, state, target_state, conf_levels, n_measurements, n_trials, sampler, seed,
+                         return_table, chunk)
+
+
+def fidelity_qst_xl(state, target_state, conf_levels, n_measurements=1000, n_trials=100, *, sampler="numpy", seed=None,
+                    return_table=False, chunk=None):
+    """`fidelity_qst` up to five qubits: the same arguments and results, the same bits at n <= 4.  At n = 5 the
+    programs (1023 variables) run on qt_lp_ineq_xl_batch, at most kLaunchProgramsXL of them per launch whatever
+    `chunk` says; every (trial, level) costs two programs of 3.7 s (measured, profiles/lp_xl_timing.txt) on one compute
+    unit each."""
+    return _fidelity_qst("fidelity_qst_xl", 5, state, target_state, conf_levels, n_measurements, n_trials, sampler, seed,
+                         return_table, chunk)
+
+
+def _fidelity_qst(name, max_qubits, state, target_state, conf_levels, n_measurements, n_trials, sampler, seed, return_table,
+                  chunk):
     n = state.n_qubits
-    if n > 4:
-        raise NotImplementedError(f"fidelity_qst supports n <= 4 qubits (4^n - 1 <= 255 LP variables); got n = {n}")
+    if n > max_qubits:
+        raise NotImplementedError(f"{name} supports n <= {max_qubits} qubits (4^n - 1 <= {4**max_qubits - 1} LP variables); "
+                                  f"got n = {n}")
     dim = 2**n
     probas, shots, weighted, A = qst_tables(state, n_measurements)
     c = np.asarray(target_state.bloch, dtype=np.float64)[1:]
