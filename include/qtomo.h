@@ -395,6 +395,30 @@ int qt_lp_ineq_large_batch(qt_handle_t* h, const double* A, int M, int N, const 
 int qt_lp_ineq_xl_batch(qt_handle_t* h, const double* A, int M, int N, const double* C, int O, const double* b, int R,
                         double* obj, double* x, int32_t* status, int32_t* iters, int flags);
 
+/* The primitives of one of the three LP kernels, run once on the caller's vectors: a test and diagnosis entry, not a
+ * production path (a whole solve hides a wrong entry of H behind a few more iterations; this shows it).
+ * kernel: 0 = qt_lp_ineq_batch's (N <= 64), 1 = qt_lp_ineq_large_batch's (N <= 255), 2 = qt_lp_ineq_xl_batch's
+ * (N <= 1023); sizes are refused as by those entries (QT_ERR_ARG for N < 1 or M < N, QT_ERR_UNSUPPORTED above the
+ * kernel's N or workspace).  Inputs: A[M][N]; w[M], the weights of the normal matrix; vm[M]; vn[n].  p1 (0 / 1) adds the
+ * phase-1 column, -1 in every row: n = N + p1.  mode 0 factors as the kernel does inside a solve (plain Cholesky for
+ * kernel 0; for 1 and 2 a pivot not above 1e-11 of its diagonal entry of H is replaced by that entry); mode 1 is the
+ * kernels' rank test (no border: p1 must be 0; a pivot not above 1e-12 of its diagonal entry is a breakdown).
+ * Outputs, each nullable:
+ *   normal[n][n]  the lower triangle of H = A^T diag(w) A (bordered) as the kernel forms it, before factoring,
+ *   factor[n][n]  the lower triangle of its Cholesky factor L (undefined where ok is 0),
+ *   u[n]          A^T vm, and u[N] = sum(vm) with p1,
+ *   ax[M]         A vn[0..N),
+ *   solved[n]     (L L^T)^-1 vn (written only where ok is 1),
+ *   ok[1]         1 if the factorisation succeeded, 0 on a breakdown.
+ * The upper triangles of normal and factor are not written.  Before the launch the entry fills the kernel's workspace
+ * slice and every non-null output with 0xFF bytes (a NaN in every double), and the kernel does the same to its LDS: a
+ * primitive that reads an entry nothing wrote (the upper triangle of H, a column past n, a row past n of a partly
+ * filled block) hands a NaN on, and what the call leaves unwritten stays all-ones.  One workgroup, on the handle's
+ * workspace of the chosen kernel.  Returns 0. */
+int qt_lp_pieces(qt_handle_t* h, int kernel, const double* A, int M, int N, const double* w, const double* vm,
+                 const double* vn, int p1, int mode, double* normal, double* factor, double* u, double* ax, double* solved,
+                 int32_t* ok, int flags);
+
 /* ---- f4: quantpy/tomography/polytopes (the coverage study of arXiv:2109.04734, Fig. 1) over a batch of trials ------
  * A trial is a count table counts[b][R][K] with shots[r] per setting (for a process the output tomographs are stacked,
  * R = inputs x settings, and shots repeats the first tomograph's, as utils.py:11 broadcasts them);

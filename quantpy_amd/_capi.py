@@ -96,6 +96,8 @@ SIGNATURES = {
     "qt_lp_ineq_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
     "qt_lp_ineq_large_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
     "qt_lp_ineq_xl_batch": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _c_int]),
+    "qt_lp_pieces": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _c_int]),
     "qt_polytope_confidence": (_c_int, [_vp, _vp, ctypes.c_longlong, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int]),
     "qt_polytope_coverage": (_c_int, [_vp, _vp, ctypes.c_longlong, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp,
                                       _c_int]),

@@ -18,6 +18,8 @@ SCHED_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # what their first loads need (csrc/qt_args.h: mle_front).  A kernel that leads with a struct preloads nothing.
 PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 FLAGS = SCHED_FLAGS + PRELOAD_FLAGS
+# qtomo.hip is the library; qt_lp_pieces.hip holds the kernel of the test entry qt_lp_pieces, apart from the kernels it inspects
+SOURCES = [os.path.join(CSRC, "qtomo.hip"), os.path.join(CSRC, "qt_lp_pieces.hip")]
 
 
 def _hipcc():
@@ -55,7 +57,7 @@ def build_profile_library(verbose=False):
     os.makedirs(LIB_DIR, exist_ok=True)
     out = os.path.join(LIB_DIR, "libqtomo_prof.so")
     cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-DQT_PHASE_TIMING", *FLAGS,
-           "-o", out, os.path.join(CSRC, "qtomo.hip")]
+           "-o", out, *SOURCES]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -63,12 +65,12 @@ def build_profile_library(verbose=False):
 
 
 def build_library(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950 -shared -fPIC csrc/qtomo.hip -> lib/libqtomo.so"""
+    """hipcc --offload-arch=gfx950 -shared -fPIC csrc/qtomo.hip csrc/qt_lp_pieces.hip -> lib/libqtomo.so"""
     if not force and not _stale():
         return LIB
     os.makedirs(LIB_DIR, exist_ok=True)
     cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", *FLAGS,
-           "-o", LIB + ".tmp", os.path.join(CSRC, "qtomo.hip")]
+           "-o", LIB + ".tmp", *SOURCES]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

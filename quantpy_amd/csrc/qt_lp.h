@@ -173,6 +173,8 @@ __device__ inline void lp_ratio(double x, double dx, double* amin) {
 //   ws_doubles(M)         doubles of global workspace per workgroup,
 //   matvec(v), av(i, v)   make A v available / (A v)_i for the v of the last matvec, over the first N columns,
 //   colsum(sh, v, p1)     sh.u[j] = (A^T v)_j, and sh.u[N] = sum v (read in phase 1 only),
+//   normal(sh, w, p1)     H = A^T diag(w) A with the phase-1 border, lower triangle (factor and full_rank start with it),
+//   h_at(sh, i, j)        entry (i, j), j <= i, of H or of its factor, whichever came last (read by k_lp_pieces only),
 //   factor(sh, w, p1)     H = A^T diag(w) A with the phase-1 border, then its Cholesky factor; false on a breakdown,
 //   full_rank(sh, w)      the same for the rank test: no border, a pivot below 1e-12 of its diagonal entry is a breakdown,
 //   solve(sh, n, v)       v <- H^{-1} v with the last factor.
@@ -213,6 +215,8 @@ struct LpSmall {
     return lp_cholesky(sh, N, 1e-12);
   }
   __device__ __forceinline__ void solve(LpShared& sh, int n, double* v) const { lp_solve(sh, n, v); }
+  // entry (i, j), j <= i, of the normal matrix or of its factor, whichever was computed last (k_lp_pieces reads them out)
+  __device__ __forceinline__ double h_at(const LpShared& sh, int i, int j) const { return sh.H[i * kLpLD + j]; }
 };
 
 // QT_LP_COLS(P, j, n, statement): the statement for every column j < n, spread over the workgroup.  Where P's columns fit
@@ -423,6 +427,7 @@ __device__ __forceinline__ void lp_run(typename P::Shared& sh, const P& p, const
 
 #undef QT_LP_COLS
 
+#ifndef QT_LP_PRIMITIVES_ONLY  // qt_lp_pieces.hip takes the primitives without the kernel (one definition per library)
 // grid: persistent workgroups over the R * O programs; ws: gridDim.x * LpSmall::ws_doubles(M) doubles
 __global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A, int M, int N,
                                                    const double* __restrict__ C, int O, const double* __restrict__ bb,
@@ -432,5 +437,6 @@ __global__ void __launch_bounds__(kLpNT) k_lp_ineq(const double* __restrict__ A,
   __shared__ LpShared sh;
   lp_run(sh, LpSmall(A, M, N, ws + blockIdx.x * LpSmall::ws_doubles(M)), C, O, bb, R, obj, xout, status, iters);
 }
+#endif
 
 }  // namespace qt

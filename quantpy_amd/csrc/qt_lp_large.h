@@ -354,17 +354,22 @@ struct LpLarge {
   // phase 2 starts from the ax that phase 1's last matvec(sh.y) left here
   __device__ __forceinline__ double av(int i, const double*) const { return ax[i]; }
   __device__ __forceinline__ void colsum(LgShared& sh, const double* v, bool p1) const { lg_colsum(sh, A, M, N, v, p1); }
-  __device__ __forceinline__ bool factor(LgShared& sh, const double* w, bool p1) const {
+  __device__ __forceinline__ void normal(LgShared& sh, const double* w, bool p1) const {
     lg_normal(sh, A, M, N, p1, w, H);  // its first barrier orders the writes of w
+  }
+  __device__ __forceinline__ bool factor(LgShared& sh, const double* w, bool p1) const {
+    normal(sh, w, p1);
     return lg_cholesky(sh, H, N + (p1 ? 1 : 0), kLgPivot, true);
   }
   __device__ __forceinline__ bool full_rank(LgShared& sh, const double* w) const {
-    lg_normal(sh, A, M, N, false, w, H);
+    normal(sh, w, false);
     return lg_cholesky(sh, H, N, 1e-12, false);
   }
   __device__ __forceinline__ void solve(LgShared& sh, int n, double* v) const { lg_solve(sh, H, n, v); }
+  __device__ __forceinline__ double h_at(const LgShared&, int i, int j) const { return H[(size_t)i * kLgLD + j]; }
 };
 
+#ifndef QT_LP_PRIMITIVES_ONLY  // qt_lp_pieces.hip takes the primitives without the kernel (one definition per library)
 // grid: persistent workgroups over the R * O programs; ws: gridDim.x * LpLarge::ws_doubles(M) doubles
 __global__ void __launch_bounds__(kLpNT) k_lp_ineq_large(const double* __restrict__ A, int M, int N,
                                                          const double* __restrict__ C, int O,
@@ -374,5 +379,6 @@ __global__ void __launch_bounds__(kLpNT) k_lp_ineq_large(const double* __restric
   __shared__ LgShared sh;
   lp_run(sh, LpLarge(A, M, N, ws + blockIdx.x * LpLarge::ws_doubles(M)), C, O, bb, R, obj, xout, status, iters);
 }
+#endif
 
 }  // namespace qt

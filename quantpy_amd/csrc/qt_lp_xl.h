@@ -316,19 +316,23 @@ struct LpXl {
   // phase 2 starts from the ax that phase 1's last matvec(sh.y) left here
   __device__ __forceinline__ double av(int i, const double*) const { return ax[i]; }
   __device__ __forceinline__ void colsum(XlShared& sh, const double* v, bool p1) const { xl_colsum(sh, A, M, N, v, p1); }
-  __device__ __forceinline__ bool factor(XlShared& sh, const double* w, bool p1) const {
+  __device__ __forceinline__ void normal(XlShared& sh, const double* w, bool p1) const {
     __syncthreads();  // w was written by other threads
     xl_normal(sh, A, M, N, p1, w, H);
+  }
+  __device__ __forceinline__ bool factor(XlShared& sh, const double* w, bool p1) const {
+    normal(sh, w, p1);
     return xl_cholesky(sh, H, N + (p1 ? 1 : 0), kLgPivot, true);
   }
   __device__ __forceinline__ bool full_rank(XlShared& sh, const double* w) const {
-    __syncthreads();
-    xl_normal(sh, A, M, N, false, w, H);
+    normal(sh, w, false);
     return xl_cholesky(sh, H, N, 1e-12, false);
   }
   __device__ __forceinline__ void solve(XlShared& sh, int n, double* v) const { xl_solve(sh, H, n, v); }
+  __device__ __forceinline__ double h_at(const XlShared&, int i, int j) const { return H[(size_t)i * kXlLD + j]; }
 };
 
+#ifndef QT_LP_PRIMITIVES_ONLY  // qt_lp_pieces.hip takes the primitives without the kernel (one definition per library)
 // grid: persistent workgroups over the R * O programs; ws: gridDim.x * LpXl::ws_doubles(M) doubles
 __global__ void __launch_bounds__(kLpNT) k_lp_ineq_xl(const double* __restrict__ A, int M, int N,
                                                       const double* __restrict__ C, int O, const double* __restrict__ bb,
@@ -338,5 +342,6 @@ __global__ void __launch_bounds__(kLpNT) k_lp_ineq_xl(const double* __restrict__
   __shared__ XlShared sh;
   lp_run(sh, LpXl(A, M, N, ws + blockIdx.x * LpXl::ws_doubles(M)), C, O, bb, R, obj, xout, status, iters);
 }
+#endif
 
 }  // namespace qt

@@ -93,7 +93,7 @@ struct DevBuf {
   }
 };
 
-constexpr int kStageBufs = 8;  // arrays one host-pointer call may stage (qt_mle_batch: counts, centres and six outputs)
+constexpr int kStageBufs = 10;  // arrays one host-pointer call may stage (qt_lp_pieces: four inputs and six outputs)
 
 // What qt_process_setup keeps of the design matrix L (rows vec(rho_s (x) E_m^T)).  n <= 2 keeps it dense (`lifp` ..
 // `pinvR`); n = 3 keeps only the left inverses of its Kronecker factors (qt_process64.h: `factored`); n = 2 builds those
@@ -1359,6 +1359,13 @@ int mhmc_hits_call(qt_handle_t* h, const char* fn, bool hs, int metric, const in
 
 }  // namespace
 
+// qt_lp_pieces.hip: the kernel of qt_lp_pieces is compiled on its own, so that the LP kernels here do not depend on it
+namespace qt {
+void lp_pieces_launch(int kernel, hipStream_t stream, const double* A, int M, int N, const double* w, const double* vm,
+                      const double* vn, int p1, int mode, double* normal, double* factor, double* u, double* ax,
+                      double* solved, int32_t* ok, double* ws);
+}
+
 extern "C" {
 
 int qt_version(void) { return 100; }
@@ -2348,6 +2355,63 @@ int qt_lp_ineq_xl_batch(qt_handle_t* h, const double* A, int M, int N, const dou
                         double* obj, double* x, int32_t* status, int32_t* iters, int flags) {
   return lp_ineq_entry(h, "qt_lp_ineq_xl_batch", qt::kXlMaxN, qt::LpXl::ws_doubles(M) * sizeof(double), true, kLpXlGrid,
                        kLpXlWsCap, &qt_handle_t::lp_xl_ws, qt::k_lp_ineq_xl, A, M, N, C, O, b, R, obj, x, status, iters, flags);
+}
+
+// The primitives of one of the three LP kernels, run once by one workgroup on the caller's vectors (k_lp_pieces): a test
+// and diagnosis entry.  The workgroup's workspace slice and every output are filled with 0xFF bytes (NaN) before the launch.
+static int lp_pieces_entry(qt_handle_t* h, Call& c, int kernel, const char* what, int max_n, size_t per_wg, bool refuse_ws,
+                           size_t ws_cap, DevBuf& ws, const double* A, int M, int N, const double* w, const double* vm,
+                           const double* vn, int p1, int mode, double* normal, double* factor, double* u, double* ax,
+                           double* solved, int32_t* ok) {
+  if (N > max_n) return fail(QT_ERR_UNSUPPORTED, "qt_lp_pieces: %s supports up to %d variables (got %d)", what, max_n, N);
+  if (refuse_ws && per_wg > ws_cap)
+    return fail(QT_ERR_UNSUPPORTED, "qt_lp_pieces: M = %d needs more than %zu MB of workspace per program", M, ws_cap >> 20);
+  const size_t n = (size_t)N + (p1 ? 1 : 0);
+  const double *dA, *dw, *dvm, *dvn;
+  double *dnormal, *dfactor, *du, *dax, *dsolved;
+  int32_t* dok;
+  if (int r = c.in(A, (size_t)M * N, &dA)) return r;
+  if (int r = c.in(w, (size_t)M, &dw)) return r;
+  if (int r = c.in(vm, (size_t)M, &dvm)) return r;
+  if (int r = c.in(vn, n, &dvn)) return r;
+  if (int r = c.out(normal, n * n, &dnormal)) return r;
+  if (int r = c.out(factor, n * n, &dfactor)) return r;
+  if (int r = c.out(u, n, &du)) return r;
+  if (int r = c.out(ax, (size_t)M, &dax)) return r;
+  if (int r = c.out(solved, n, &dsolved)) return r;
+  if (int r = c.out(ok, (size_t)1, &dok)) return r;
+  HIPCHK(ws.ensure(per_wg));
+  HIPCHK(hipMemsetAsync(ws.p, 0xFF, per_wg, h->stream));
+  const struct {
+    void* p;
+    size_t bytes;
+  } outs[] = {{dnormal, n * n * sizeof(double)}, {dfactor, n * n * sizeof(double)}, {du, n * sizeof(double)},
+              {dax, (size_t)M * sizeof(double)}, {dsolved, n * sizeof(double)},     {dok, sizeof(int32_t)}};
+  for (const auto& o : outs)
+    if (o.p) HIPCHK(hipMemsetAsync(o.p, 0xFF, o.bytes, h->stream));
+  qt::lp_pieces_launch(kernel, h->stream, dA, M, N, dw, dvm, dvn, p1, mode, dnormal, dfactor, du, dax, dsolved, dok,
+                       ws.as<double>());
+  return c.done();
+}
+
+int qt_lp_pieces(qt_handle_t* h, int kernel, const double* A, int M, int N, const double* w, const double* vm,
+                 const double* vn, int p1, int mode, double* normal, double* factor, double* u, double* ax, double* solved,
+                 int32_t* ok, int flags) {
+  QT_ENTER(h);
+  Call c(h, flags);
+  if (!A || !w || !vm || !vn) return fail(QT_ERR_ARG, "qt_lp_pieces: null array");
+  if (N < 1 || M < N) return fail(QT_ERR_ARG, "qt_lp_pieces: bad sizes (M=%d N=%d)", M, N);
+  if (kernel < 0 || kernel > 2 || (p1 != 0 && p1 != 1) || (mode != 0 && mode != 1) || (mode == 1 && p1))
+    return fail(QT_ERR_ARG, "qt_lp_pieces: bad selector (kernel=%d p1=%d mode=%d; the rank test has no border)", kernel, p1, mode);
+  if (kernel == 0)
+    return lp_pieces_entry(h, c, 0, "k_lp_ineq", qt::kLpMaxN, qt::LpSmall::ws_doubles(M) * sizeof(double),
+                            false, kLpWsCap, h->lp_ws, A, M, N, w, vm, vn, p1, mode, normal, factor, u, ax, solved, ok);
+  if (kernel == 1)
+    return lp_pieces_entry(h, c, 1, "k_lp_ineq_large", qt::kLgMaxN,
+                            qt::LpLarge::ws_doubles(M) * sizeof(double), true, kLpWsCap, h->lp_large_ws, A, M, N, w, vm, vn, p1,
+                            mode, normal, factor, u, ax, solved, ok);
+  return lp_pieces_entry(h, c, 2, "k_lp_ineq_xl", qt::kXlMaxN, qt::LpXl::ws_doubles(M) * sizeof(double), true,
+                          kLpXlWsCap, h->lp_xl_ws, A, M, N, w, vm, vn, p1, mode, normal, factor, u, ax, solved, ok);
 }
 
 // ---- f4: polytopes/utils.py:4-27, verification.py:9-78 over a batch of trials (qt_polytope.h) -------------------------

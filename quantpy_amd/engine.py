@@ -1065,6 +1065,27 @@ class Engine:
                 old[resolved] = new
         return res, resolved
 
+    def lp_pieces(self, kernel, A, w, vm, vn, p1=False, mode=0):
+        """The primitives of one LP kernel, run once (qt_lp_pieces; for tests and diagnosis): kernel 0 / 1 / 2 =
+        lp_ineq_batch's / lp_ineq_large_batch's / lp_ineq_xl_batch's, A (M, N), weights w (M,), vm (M,), vn (n,) with
+        n = N + p1; mode 0 = the kernel's factorisation inside a solve, 1 = its rank test (no border) -> a dict with
+        normal (n, n) = A^T diag(w) A, bordered with p1, and factor (n, n) = its Cholesky factor (lower triangles; the
+        upper ones keep the entry's 0xFF fill), u (n,) = A^T vm [, sum vm], ax (M,) = A vn[:N], solved (n,) =
+        (L L^T)^-1 vn (the fill where ok is 0) and ok (int)."""
+        a = _f64(A)
+        m, nv = a.shape
+        n = nv + (1 if p1 else 0)
+        w, vm, vn = _f64(w), _f64(vm), _f64(vn)
+        assert w.shape == (m,) and vm.shape == (m,) and vn.shape == (n,)
+        out = {"normal": np.empty((n, n)), "factor": np.empty((n, n)), "u": np.empty(n), "ax": np.empty(m),
+               "solved": np.empty(n)}
+        ok = np.empty(1, dtype=np.int32)
+        self._chk(self.lib.qt_lp_pieces(self._h, int(kernel), _ptr(a), m, nv, _ptr(w), _ptr(vm), _ptr(vn), int(bool(p1)), int(mode),
+                                        _ptr(out["normal"]), _ptr(out["factor"]), _ptr(out["u"]), _ptr(out["ax"]),
+                                        _ptr(out["solved"]), _ptr(ok), _capi.QT_HOST_PTR))
+        out["ok"] = int(ok[0])
+        return out
+
     def _lp_call(self, fn, A, C, b, return_x):
         a = _f64(A)
         c = _f64(np.atleast_2d(C))

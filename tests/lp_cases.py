@@ -1,4 +1,4 @@
-"""Hard linear programs for the two batched LP kernels (csrc/qt_lp.h, csrc/qt_lp_large.h), shared by the host test of
+"""Hard linear programs for the three batched LP kernels (csrc/qt_lp.h, csrc/qt_lp_large.h, csrc/qt_lp_xl.h), shared by the host test of
 the NumPy model (test_lp_cases_host.py) and the GPU test (test_gpu_lp_hard.py):
 
     minimise c . x  subject to  A x <= b,  x free.
@@ -24,7 +24,10 @@ is seeded by the family's name and N, and the families that transform `random` (
                        (_ROW_OBJECTIVE); every solver finds their optimum
 
 Sizes: the small kernel's list is N in SMALL_N with M = 3 N + 1, the large kernel's N in LARGE_N with M = 2 N + 3, where
-the family leaves M free.  References are HiGHS's, computed once per case and process (`reference`).  At N >= 224 a
+the family leaves M free; the XL kernel's list ('xl') is N in XL_N with the large list's M, every size of it shared as
+below, and one full-width program, XL_FULL: the half-box at N = 1023 (M = 2045, optimum -1 exactly), which drives the
+pivot replacement at n = 1024 (profiles/lp_xl_hard_cases.txt has the model's run of it, which the host test leaves
+out).  References are HiGHS's, computed once per case and process (`reference`).  At N >= 224 a
 HiGHS solve takes about a second, so there the families that transform `random` share its one solve (their optimum is
 the same number, or moves by c . x1), dual_degenerate keeps one of its two k and slab one of its two widths per size,
 and the families whose answer is known by construction (primal_degenerate, the half-box, infeasible) are not solved at
@@ -40,6 +43,8 @@ from scipy.optimize import linprog
 
 SMALL_N = (1, 2, 15, 63, 64)
 LARGE_N = (15, 64, 65, 96, 97, 128, 129, 224, 255)
+XL_N = (257, 385)
+XL_FULL = ("dual_degenerate-halfbox-N1023", 1023)
 SHARED_FROM = 224  # sizes from here on share HiGHS solves (module docstring)
 
 # name: the case's id; status: the expected lp_model / qt_lp_status; exact: the optimum known by construction or None;
@@ -57,7 +62,7 @@ def _rng(family, N):
 
 
 def rows_of(kind, N):
-    return 3 * N + 1 if kind == "small" else 2 * N + 3
+    return 3 * N + 1 if kind == "small" else 2 * N + 3  # 'large' and 'xl'
 
 
 def bounded_lp(rng, M, N):
@@ -81,11 +86,21 @@ def primal_degenerate(N, M=None):
     return A, b, -rng.uniform(0.5, 1.5, N)
 
 
+def _halfbox(N):
+    Q = np.linalg.qr(_rng("dual_degenerate", N).standard_normal((N, N)))[0]
+    return np.vstack([np.eye(N), -np.eye(N)[1:]]) @ Q, Q
+
+
+def dual_degenerate_halfbox(N):
+    """The rotated half-box alone (the 'halfbox' variant of dual_degenerate, without the `random` program beside it)."""
+    half, Q = _halfbox(N)
+    return half, np.ones(2 * N - 1), -Q[0]
+
+
 def dual_degenerate(N, M):
     A, b, _ = random(N, M)
     out = {"k%d" % k: (A, b, -A[k % M]) for k in (0, 5)}
-    Q = np.linalg.qr(_rng("dual_degenerate", N).standard_normal((N, N)))[0]
-    half = np.vstack([np.eye(N), -np.eye(N)[1:]]) @ Q
+    half, Q = _halfbox(N)
     out["halfbox"] = (half, np.ones(2 * N - 1), -Q[0])
     out["halfbox_unbounded"] = (half, np.ones(2 * N - 1), Q[0].copy())
     return out
@@ -157,16 +172,16 @@ _SHARES_RANDOM = ("row_scaled", "col_scaled", "duplicated", "offset")
 @functools.lru_cache(maxsize=None)
 def _cases(kind):
     out = {}
-    for N in (SMALL_N if kind == "small" else LARGE_N):
+    for N in {"small": SMALL_N, "large": LARGE_N, "xl": XL_N}[kind]:
         M = rows_of(kind, N)
         shared = N >= SHARED_FROM
         for family in FAMILIES:
             made = globals()[family](N, M)
             variants = made if isinstance(made, dict) else {"": made}
             if shared and family == "dual_degenerate":
-                del variants["k5" if N == 224 else "k0"]
+                del variants["k5" if N in (224, 257) else "k0"]
             if shared and family == "slab":
-                del variants["1e-6" if N == 224 else "1e-3"]
+                del variants["1e-6" if N in (224, 257) else "1e-3"]
             for tag, prog in variants.items():
                 name = "%s%s-N%d" % (family, "-" + tag if tag else "", N)
                 A, b, c = (np.ascontiguousarray(v, dtype=np.float64) for v in prog[:3])
@@ -186,11 +201,15 @@ def _cases(kind):
                 else:
                     family_of = family
                 out[name] = Case(name, family_of, N, A, b, c, status, exact, base)
+    if kind == "xl":
+        name, N = XL_FULL
+        A, b, c = (np.ascontiguousarray(v, dtype=np.float64) for v in dual_degenerate_halfbox(N))
+        out[name] = Case(name, "dual_degenerate", N, A, b, c, lp_model.OPTIMAL, -1.0, None)
     return out
 
 
 def names(kind):
-    """Case ids of the 'small' or the 'large' list, in a fixed order."""
+    """Case ids of the 'small', the 'large' or the 'xl' list, in a fixed order."""
     return list(_cases(kind))
 
 

@@ -29,9 +29,10 @@ def _max_step(x, dx):
     return np.min(-x[neg] / dx[neg]) if neg.any() else np.inf
 
 
-def cholesky_replacing(H, rel):
+def cholesky_replacing(H, rel, trace=None):
     """Right-looking Cholesky of H in which a pivot not above rel * (its diagonal entry of H) is replaced by that entry
-    -> (L, number of replaced pivots).  Raises LinAlgError on a diagonal entry that is not positive."""
+    -> (L, number of replaced pivots).  Raises LinAlgError on a diagonal entry that is not positive.  Works in H's
+    precision (float64 or longdouble).  trace: a list that receives (pivot / diagonal entry, replaced) per column."""
     n = H.shape[0]
     L = np.tril(H)
     d0 = np.diag(H).copy()
@@ -40,6 +41,8 @@ def cholesky_replacing(H, rel):
         p = L[k, k]
         if not np.isfinite(p) or not d0[k] > 0.0:
             raise np.linalg.LinAlgError("breakdown")
+        if trace is not None:
+            trace.append((float(p / d0[k]), not p > rel * d0[k]))
         if not p > rel * d0[k]:
             p = d0[k]
             replaced += 1

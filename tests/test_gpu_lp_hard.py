@@ -1,6 +1,7 @@
-"""The two batched LP kernels (qt_lp_ineq_batch, csrc/qt_lp.h; qt_lp_ineq_large_batch, csrc/qt_lp_large.h) on the hard
-programs of tests/lp_cases.py -- degenerate, thin, ill-scaled, at the kernels' seams (the small kernel's cap of 64
-variables, the large kernel's 32-column panels and 64-column tiles) -- and on launches in which a persistent workgroup
+"""The three batched LP kernels (qt_lp_ineq_batch, csrc/qt_lp.h; qt_lp_ineq_large_batch, csrc/qt_lp_large.h;
+qt_lp_ineq_xl_batch, csrc/qt_lp_xl.h) on the hard programs of tests/lp_cases.py -- degenerate, thin, ill-scaled, at the
+kernels' seams (the small kernel's cap of 64 variables, the large kernel's 32-column panels and 64-column tiles, the XL
+kernel's 256-thread strides and 128-column blocks) -- and on launches in which a persistent workgroup
 solves one program after another.  Expected optima are HiGHS's (lp_cases.reference); test_lp_cases_host.py shows that
 the algorithm itself (tests/lp_model.py) stays within a fifth of TOL on every case.
 
@@ -69,6 +70,19 @@ def test_large_kernel_on_hard_programs(eng, name):
     ref_status, ref, _ = lp_cases.reference("large", name)
     assert ref_status == cs.status
     _check_case("large", cs, ref, *_solve_case(eng.lp_ineq_large_batch, cs))
+
+
+@pytest.mark.parametrize("name", lp_cases.names("xl"))
+def test_xl_kernel_on_hard_programs(eng, name):
+    import time
+
+    cs = lp_cases.case("xl", name)
+    ref_status, ref, _ = lp_cases.reference("xl", name)
+    assert ref_status == cs.status
+    t0 = time.perf_counter()
+    res = _solve_case(eng.lp_ineq_xl_batch, cs)
+    print("LPHARD xl", name, "seconds %.2f" % (time.perf_counter() - t0))
+    _check_case("xl", cs, ref, *res)
 
 
 @pytest.mark.parametrize("name", lp_cases.names("small"))
@@ -145,10 +159,17 @@ def _nine_rhs(rng, A, feasible, infeasible):
     return b[[0, 7, 1, 2, 8, 3, 4, 5, 6]], 1, 4
 
 
-def _grid(large, M, P):
+def _grid(kernel, M, P):
     """lp_ineq_entry's launch: min(programs, 2 048, 256 MB / the workgroup's workspace), the workspace being
-    LpSmall::ws_doubles(M) = 6 M and LpLarge::ws_doubles(M) = 256 * 256 + 7 M doubles."""
-    return min(P, 2048, (256 << 20) // (8 * (256 * 256 + 7 * M if large else 6 * M)))
+    LpSmall::ws_doubles(M) = 6 M and LpLarge::ws_doubles(M) = 256 * 256 + 7 M doubles; for the XL kernel
+    min(programs, 256, 4 GB / the workspace), LpXl::ws_doubles(M) = 1024 * 1024 + 7 M doubles."""
+    if kernel == "xl":
+        return min(P, 256, (4 << 30) // (8 * (1024 * 1024 + 7 * M)))
+    return min(P, 2048, (256 << 20) // (8 * (256 * 256 + 7 * M if kernel == "large" else 6 * M)))
+
+
+def _entry(eng, kernel):
+    return {"small": eng.lp_ineq_batch, "large": eng.lp_ineq_large_batch, "xl": eng.lp_ineq_xl_batch}[kernel]
 
 
 def _followed(status, grid):
@@ -177,12 +198,11 @@ def _check_isolation(fn, A, C, rhs, R, alone=None):
     return res, alone
 
 
-def _isolation(eng, large, M, N, R):
+def _isolation(eng, kernel, M, N, R):
     from quantpy_amd import _capi
 
     OPT, INF, UNB, NC = _capi.LP_OPTIMAL, _capi.LP_INFEASIBLE, _capi.LP_UNBOUNDED, _capi.LP_NOT_CONVERGED
-    fn = eng.lp_ineq_large_batch if large else eng.lp_ineq_batch
-    kernel = "large" if large else "small"
+    fn = _entry(eng, kernel)
     rng = np.random.default_rng(1000 * M + N)
     # a bounded polytope: u^T A = 0 for a u > 0, so A x <= A x0 - 1 has no solution
     A, _ = lp_cases.bounded_lp(rng, M, N)
@@ -190,7 +210,7 @@ def _isolation(eng, large, M, N, R):
                                     lambda g: A @ g.standard_normal(N) - 1.0)
     c = rng.standard_normal(N)
     C = np.stack([c, -c, rng.standard_normal(N)])
-    grid = _grid(large, M, 2 * R)
+    grid = _grid(kernel, M, 2 * R)
     assert 2 * R > grid and (grid // 2) % CYCLE != 0 and grid % 2 == 0
     (obj, status, iters, x), alone = _check_isolation(fn, A, C[:2], rhs, R)
     followed = _followed(status, grid)
@@ -229,7 +249,7 @@ def _isolation(eng, large, M, N, R):
     G = rng.standard_normal((2, N))
     G[:, 0] = -np.abs(G[:, 0]) - 0.1
     C = np.vstack([Q[:1], G @ Q])
-    grid = _grid(large, Mh, 3 * R)
+    grid = _grid(kernel, Mh, 3 * R)
     assert 3 * R > grid and grid % 3 != 0
     (obj, status, iters, x), alone = _check_isolation(fn, half, C, rhs, R)
     followed = _followed(status, grid)
@@ -253,23 +273,33 @@ def _isolation(eng, large, M, N, R):
 
 def test_small_kernel_programs_do_not_depend_on_their_predecessor(eng):
     M, N, R = 7, 3, 1100
-    assert 2 * R > 2048 == _grid(False, M, 2 * R)  # more programs than the launch has workgroups
-    _isolation(eng, False, M, N, R)
+    assert 2 * R > 2048 == _grid("small", M, 2 * R)  # more programs than the launch has workgroups
+    _isolation(eng, "small", M, N, R)
 
 
 def test_large_kernel_programs_do_not_depend_on_their_predecessor(eng):
     # LpLarge::ws_doubles(M) = 256 * 256 + 7 M doubles: 528 208 B at M = 70, and 256 MB hold 508 such workgroups (505 at
     # the half-box's M = 129)
     M, N, R = 70, 65, 300
-    assert 2 * R > _grid(True, M, 2 * R) == 508 and _grid(True, 2 * N - 1, 3 * R) == 505
-    _isolation(eng, True, M, N, R)
+    assert 2 * R > _grid("large", M, 2 * R) == 508 and _grid("large", 2 * N - 1, 3 * R) == 505
+    _isolation(eng, "large", M, N, R)
 
 
-@pytest.mark.parametrize("large,M,N", [(False, 46, 15), (False, 193, 64), (True, 133, 65), (True, 261, 129)])
-def test_nan_in_an_objective_and_in_A(eng, large, M, N):
+def test_xl_kernel_programs_do_not_depend_on_their_predecessor(eng):
+    # one workgroup per compute unit: 256 of them, each with an 8 MB normal matrix that the next program finds as the
+    # last one left it, and 48 KB of LDS vectors.  600 and 900 programs on 256 workgroups: 256 is even, 128 is no
+    # multiple of CYCLE = 9 and 256 none of 3, as _isolation asks
+    M, N, R = 70, 65, 300
+    assert 2 * R > _grid("xl", M, 2 * R) == 256 and 3 * R > _grid("xl", 2 * N - 1, 3 * R) == 256
+    _isolation(eng, "xl", M, N, R)
+
+
+@pytest.mark.parametrize("kernel,M,N", [("small", 46, 15), ("small", 193, 64), ("large", 133, 65), ("large", 261, 129),
+                                        ("xl", 300, 257)])
+def test_nan_in_an_objective_and_in_A(eng, kernel, M, N):
     from quantpy_amd import _capi
 
-    fn = eng.lp_ineq_large_batch if large else eng.lp_ineq_batch
+    fn = _entry(eng, kernel)
     rng = np.random.default_rng(77 * M + N)
     A, ax0 = lp_cases.bounded_lp(rng, M, N)
     b = ax0[None, :] + rng.uniform(0.01, 1.0, (3, M))

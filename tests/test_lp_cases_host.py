@@ -1,5 +1,5 @@
 """The NumPy model of the LP kernels (tests/lp_model.py) against HiGHS on the hard programs of tests/lp_cases.py: the
-small kernel's list with its plain Cholesky, the large kernel's with the pivot safeguard.  No GPU.  This is what
+small kernel's list with its plain Cholesky, the large kernel's and the XL kernel's with the pivot safeguard.  No GPU.  This is what
 test_gpu_lp_hard.py rests on: the algorithm alone stays within a fifth of that test's tolerance on every case, so a
 kernel that misses it there differs from the algorithm and not merely in its summation order."""
 import lp_cases
@@ -48,6 +48,16 @@ def test_model_with_safeguard_on_the_large_list(name):
         _check_optimum(cs, ref, obj, x)
 
 
+@pytest.mark.parametrize("name", [n for n in lp_cases.names("xl") if n != lp_cases.XL_FULL[0]])
+def test_model_with_safeguard_on_the_xl_list(name):
+    """The full-width half-box (XL_FULL) is left out: the model takes 11 s there; its run (OPTIMAL, 9 iterations,
+    1.0e-14 off -1) is filed in profiles/lp_xl_hard_cases.txt."""
+    cs, ref, status, obj, iters, x = _check("xl", name, lp_model.LARGE_PIVOT)
+    assert status == cs.status and iters <= 200
+    if status == lp_model.OPTIMAL:
+        _check_optimum(cs, ref, obj, x)
+
+
 def test_threshold_of_the_safeguard_matters_on_these_cases():
     """With the safeguard's threshold at 0 (only a non-positive pivot is replaced, a pivot of rounding noise is kept)
     the model loses dual-degenerate programs of the large list that it solves at LARGE_PIVOT: the cases can tell the two
@@ -71,14 +81,19 @@ def test_status_codes_are_the_model_s():
 
 
 def test_case_lists_cover_every_family_and_size():
-    for kind, sizes in (("small", lp_cases.SMALL_N), ("large", lp_cases.LARGE_N)):
-        seen = {(lp_cases.case(kind, n).family, lp_cases.case(kind, n).N) for n in lp_cases.names(kind)}
+    for kind, sizes in (("small", lp_cases.SMALL_N), ("large", lp_cases.LARGE_N), ("xl", lp_cases.XL_N)):
+        seen = {(lp_cases.case(kind, n).family, lp_cases.case(kind, n).N) for n in lp_cases.names(kind)
+                if n != lp_cases.XL_FULL[0]}
         assert {v for v in seen if v[0] != "row_objective"} == {(f, N) for f in lp_cases.FAMILIES for N in sizes}
     # sizes the kernels' seams sit at: the small kernel's cap, and both sides of the large kernel's panels and tiles
     assert 64 in lp_cases.SMALL_N and {64, 65, 96, 97, 128, 129, 255} <= set(lp_cases.LARGE_N)
-    for name in lp_cases.names("large"):
-        cs = lp_cases.case("large", name)
-        assert cs.A.shape[0] >= cs.N and cs.A.shape == (cs.b.size, cs.c.size)
+    assert min(lp_cases.XL_N) > 256 and min(lp_cases.XL_N) >= lp_cases.SHARED_FROM  # above the large kernel; solves shared
+    full = lp_cases.case("xl", lp_cases.XL_FULL[0])
+    assert full.A.shape == (2045, 1023) and full.exact == -1.0 and lp_cases.reference("xl", full.name)[1:] == (-1.0, "exact")
+    for kind in ("large", "xl"):
+        for name in lp_cases.names(kind):
+            cs = lp_cases.case(kind, name)
+            assert cs.A.shape[0] >= cs.N and cs.A.shape == (cs.b.size, cs.c.size)
     # the programs are the same in every process: fixed seeds
     a = lp_cases.case("small", "row_scaled-N15")
     lp_cases._cases.cache_clear()
